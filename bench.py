@@ -6,16 +6,21 @@ deterministic gradient reduce for every column of this rank (`colnde_loss_grad_d
 one RCCL SUM all-reduce of [grad(19,563); 6 loss terms; total] (the only exchange step).
 Columns shard across ranks with no other data-path collective: weak scaling, per-GPU columns fixed.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--columns C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--columns C] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line (metric/unit from BASELINE.json) carrying `roofline` (dominant kernel = the adjoint
-kernel, HIP-event timed on its own stream through colnde_kernel_time) and `cpu_baseline` (the C port of the
-oracle on the box's host cores, bounded sample, rank 0 at N = 1 only).
+kernel, HIP-event timed on its own stream through colnde_kernel_time, from the K timed steps themselves).
+A plain run does only what that line needs: set up, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR`
+writes what the last timed step computed (DIR/<name>.npy; the inputs are seeded, so two builds compare file for file).
+`--full` adds everything else, all after the timed region: the K steps again without kernel events (shader clock,
+board power), the device copy bandwidth, the F32_MFMA opt-out, the self-check against the C port, `cpu_baseline`
+(the C port of the oracle on the box's host cores, bounded sample, rank 0 at N = 1 only), the other BASELINE
+configs, the all-reduce timed alone (N > 1) and the full record on disk.
 
 Matrix arithmetic (include/colnde.h COLNDE_MATRIX_*): the headline runs the library default, BF16X3_EXACT — f32 operands split exactly into
 three bf16 parts, six bf16 MFMA products per k-block, f32 accumulation: f32 arithmetic on the bf16 pipe (`dtype` stays "f32"; VERDICT r3 ruling).
-The same step under F32_MFMA is measured after the timed region and reported beside it (`opt_out`).  Because the kernels then run a MIX of
+With --full the same step under F32_MFMA is measured after the timed region and reported beside it (`opt_out`).  Because the kernels then run a MIX of
 bf16 and f32 MFMA instructions, `roofline.frac` is the matrix-pipe TIME fraction (executed bf16-MFMA flop / 2.5 PF + executed f32-MFMA flop /
 157.3 TF, over the kernel's duration), never algorithmic flops over the f32 peak; the algorithmic f32-equivalent TFLOP/s is `roofline.achieved`.
 """
@@ -54,6 +59,26 @@ EXECUTED_MFMA_FLOP_PER_STAGE32 = {
     "adjoint": {"bf16x3_exact": (162 * 32768, 336 * 4096), "f32_mfma": (0, 552 * 4096)},       # rt_adjoint_kernel<ACT, true[, true]>
     "dw1": {"bf16x3_exact": (180 * 32768, 0), "f32_mfma": (0, 240 * 4096)},                    # rt_dw1[_split]_kernel
 }
+
+
+DUMP_BUDGET_BYTES = 60 << 20                                       # --dump-outputs: all arrays of one run together (with the .npy headers below 64 MB)
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the arrays the timed path handed its caller in the last timed step, one DIR/<name>.npy each, float32.  When they
+    exceed `budget` bytes together, each keeps a fixed seeded sample of its elements (flattened, in index order) and the flat indices of
+    that sample go beside it as DIR/<name>_index.npy (float64), so the sample is the same from run to run."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            # 4 bytes of value + 8 of index per kept element; one element per array is set aside so that every array keeps at least one
+            k = min(a.size, 1 + ((budget - 12 * len(arrays)) * a.nbytes // total) // 12)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def pipe_time_fraction(kernel, arithmetic, stages32, seconds):
@@ -459,7 +484,7 @@ def free_convection_workload(args, world, rank, local_rank, dev, comm, dist):
     barrier()
     nde.set_profiling(True)
     nde.reset_kernel_times()
-    sensors = GpuSensors(dev).start() if rank == 0 else None     # (a host thread reading two sysfs nodes every 20 ms: nothing on the GPU)
+    sensors = GpuSensors(dev).start() if rank == 0 and args.full else None     # (a host thread reading two sysfs nodes every 20 ms: nothing on the GPU)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -475,6 +500,9 @@ def free_convection_workload(args, world, rank, local_rank, dev, comm, dist):
     elapsed = float(te.item())
     km = {k: nde.kernel_time(k)[0] / max(nde.kernel_time(k)[1], 1) for k in ("forward", "adjoint", "dw1", "reduce")}
     res = out.cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        npar = nde.n_params
+        dump_outputs(args.dump_outputs, {"gradient": res[:npar], "loss_terms": res[npar:npar + 6], "loss_total": res[npar + 6:npar + 7]})
     if rank == 0:
         cs = ncol * world * p.cfg.n_steps
         mlp = 2 * (64 * 256 + 256 * 256 + 256 * 63)
@@ -581,15 +609,18 @@ def inference_workload(args, world, rank, local_rank, dev, comm, dist):
     slots = torch.zeros(world, dtype=torch.float32, device=dev)
     slots[rank] = own / args.steps * 1e3
     reduce_(slots, "sum")
-    # the shard's first columns against the float32 C port (rank 0; outside the timed region)
+    # --full: the shard's first columns against the float32 C port (rank 0; outside the timed region)
     check = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"forcing": out.cpu().numpy()})              # rank 0's shard of the last timed step
     if rank == 0:
-        from oracle import cref
-        k = min(ncol, 256)
-        ref = cref.infer_forcing(cfg, T[lo:lo + k], tf[lo:lo + k], wts, 1024.0)
-        got = out[:k].cpu().numpy()
-        err = float(np.linalg.norm(got.astype(np.float64) - ref) / (np.linalg.norm(ref) + 1e-300))
-        check = {"rel_l2_error": err, "tolerance": 2e-6, "columns": k, "ok": bool(err < 2e-6), "against": "oracle/colnde_ref.c"}
+        if args.full:
+            from oracle import cref
+            k = min(ncol, 256)
+            ref = cref.infer_forcing(cfg, T[lo:lo + k], tf[lo:lo + k], wts, 1024.0)
+            got = out[:k].cpu().numpy()
+            err = float(np.linalg.norm(got.astype(np.float64) - ref) / (np.linalg.norm(ref) + 1e-300))
+            check = {"rel_l2_error": err, "tolerance": 2e-6, "columns": k, "ok": bool(err < 2e-6), "against": "oracle/colnde_ref.c"}
         mlp = 2 * (32 * 128 + 128 * 128 + 128 * 31)
         print(json.dumps({
             "metric": "columns/sec, double_gyre_nn inference forcing (BASELINE configs[4])", "value": n_global * args.steps / elapsed, "unit": "columns/s",
@@ -679,7 +710,7 @@ def compact_line(full):
             "errors": [k for k, v in cfgs.items() if isinstance(v, dict) and ("error" in v or "skipped" in v)] or None}
     line["loss_total"] = full.get("loss_total")
     line["grad_l2"] = full.get("grad_l2")
-    line["full_record"] = "gpurun_out/bench_full.json"
+    line["full_record"] = full.get("full_record")                 # set by --full, the only runs that write the record
     return _sig(line)
 
 
@@ -720,8 +751,14 @@ def main():
                          "(default 16384) columns per GPU x 64 levels x 512 RK4 steps, one RCCL all-reduce of the 98,631-float result buffer per iteration.  "
                          "inference: BASELINE configs[4] — the double_gyre_nn forcing on --global-columns (default 65536 = 256 x 256) columns x 32 levels dealt "
                          "over the N GPUs by column, no collective")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the block that times the other BASELINE configs after the headline (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, at most 64 MB in all: a fixed seeded sample beyond that)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure: the steps again without kernel events "
+                         "(clock, power), copy bandwidth, the F32_MFMA opt-out, the self-check against the C port, the CPU baseline, the other BASELINE "
+                         "configs, the all-reduce alone (N > 1), the full record on disk")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the F32_MFMA opt-out and the block that times the other BASELINE configs after the headline (N = 1 only)")
     args = ap.parse_args()
 
     if args.substeps < 1 or args.steps < 1 or args.frames < 2:
@@ -864,32 +901,38 @@ def main():
     ms_red, n_red = nde.kernel_time("reduce")
     ms_dw1, n_dw1 = nde.kernel_time("dw1")
     nde.set_profiling(False)
-    # the same K steps once more with the per-kernel HIP events off (reported beside the headline, never instead of it)
-    barrier()
-    sensors = GpuSensors(dev).start() if rank == 0 else None
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    elapsed_plain = max_over_ranks(time.perf_counter() - t0)
-    clock = sensors.stop() if sensors is not None else None
-    if clock and clock.get("board_power_W_mean"):
-        clock["energy_J_per_step"] = clock["board_power_W_mean"] * elapsed_plain / args.steps       # what a power-limited board makes the figure of merit
-    res = out.cpu().numpy()
+    res = out.cpu().numpy()                           # the last timed step's result buffer [grad; 6 loss terms; total; 0]
+    if rank == 0 and args.dump_outputs:
+        npar = nde.n_params
+        dump_outputs(args.dump_outputs, {"gradient": res[:npar], "loss_terms": res[npar:npar + 6], "loss_total": res[npar + 6:npar + 7]})
+    elapsed_plain = clock = None
+    if args.full:
+        # the same K steps once more with the per-kernel HIP events off (reported beside the headline, never instead of it)
+        barrier()
+        sensors = GpuSensors(dev).start() if rank == 0 else None
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        elapsed_plain = max_over_ranks(time.perf_counter() - t0)
+        clock = sensors.stop() if sensors is not None else None
+        if clock and clock.get("board_power_W_mean"):
+            clock["energy_J_per_step"] = clock["board_power_W_mean"] * elapsed_plain / args.steps       # what a power-limited board makes the figure of merit
     per_rank_ms = allreduce_ms = None
     if comm is not None or dist is not None:
         slots = torch.zeros(world, dtype=torch.float32, device=dev)
         slots[rank] = own_compute / args.steps * 1e3
         allreduce_raw(slots, "sum")
         per_rank_ms = [float(x) for x in slots.cpu()]
-        # the exchange step alone: K all-reduces of the result buffer, back to back
-        scratch = out.clone()
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            allreduce_raw(scratch, "sum")
-        torch.cuda.synchronize()
-        allreduce_ms = max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3
+        if args.full:
+            # the exchange step alone: K all-reduces of the result buffer, back to back
+            scratch = out.clone()
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                allreduce_raw(scratch, "sum")
+            torch.cuda.synchronize()
+            allreduce_ms = max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3
 
     if rank == 0:
         colsteps_per_step = n_global * cfg.n_steps
@@ -946,7 +989,7 @@ def main():
             "value": value, "unit": "column-timesteps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_without_kernel_events": elapsed_plain / args.steps * 1e3,
+            "ms_per_step_without_kernel_events": None if elapsed_plain is None else elapsed_plain / args.steps * 1e3,
             "higher_is_better": True, "scaling": "strong" if args.global_columns > 0 else "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {
@@ -999,13 +1042,14 @@ def main():
             "loss_total": float(res[nde.n_params + 6]),
             "grad_l2": float(np.linalg.norm(res[:nde.n_params])),
         }
-        if world == 1:
+        extras = world == 1 and args.full                # the measurements and checks beyond the headline: --full, one rank, outside the timed region
+        if extras:
             # outside the timed region: the box's own copy bandwidth, beside the guide's 6.29 TB/s and the 8 TB/s vendor figure
             cp = measured_copy_bandwidth(dev)
             line["roofline"]["hbm"]["device_copy_GBps_measured_on_this_box"] = cp
             if cp:
                 line["roofline"]["hbm"]["frac_of_measured_copy"] = ab["adjoint"] * units_per_launch / adj_s / 1e9 / cp
-        if world == 1 and regtile and not args.no_configs:
+        if extras and regtile and not args.no_configs:
             # opt-out, outside the timed region, same handle and tapes: the same step under COLNDE_MATRIX_F32_MFMA (v_mfma_f32_* throughout)
             try:
                 gd = out[:nde.n_params].clone()
@@ -1044,13 +1088,13 @@ def main():
             finally:
                 nde.set_profiling(False)
                 nde.set_matrix_arithmetic("bf16x3_exact")
-        if world == 1:
+        if extras:
             # the bench checks its own launch (VERDICT r3 task 4c): 8 columns of this handle's forward solve against the float32 C port
             try:
                 line["self_check"] = check_forward_against_port(nde, prob, w, dev)
             except Exception as e:
                 line["self_check"] = {"ok": False, "error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(prob, scal)
         else:
             line["cpu_baseline"] = None
@@ -1066,7 +1110,9 @@ def main():
             except OSError:
                 pass
 
-        if world == 1 and not args.no_configs:
+        if args.full:
+            line["full_record"] = os.path.relpath(full_path, ROOT)
+        if world == 1 and args.full and not args.no_configs:
             # The side configs run after the headline's timed region with its tapes released.  The headline is safe before they start: on stderr
             # and in gpurun_out/ (a side config that takes the process down cannot take the measurement with it).
             save_full()
@@ -1079,7 +1125,9 @@ def main():
                 line["configs"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
         # The FULL record (side configs, per-kernel blocks, PMC tables, plan) goes to gpurun_out/bench_full.json; stdout carries ONE compact
         # line (< 8 KB: VERDICT r4 — the 25 KB line of round 4 did not parse) with exactly what the contract reads, and stderr stays short too.
-        save_full()
+        # A plain run writes no record: its line is all it measured.
+        if args.full:
+            save_full()
         print(json.dumps(compact_line(line)), flush=True)
         if world == 1 and line.get("self_check") and not line["self_check"].get("ok"):
             raise SystemExit("bench.py: the forward solve of the timed handle misses the C port: %r" % (line["self_check"],))

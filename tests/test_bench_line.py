@@ -71,3 +71,33 @@ def test_stdout_is_one_line_in_the_source():
     main_src = src[src.index("def main():"):]
     prints = [ln.strip() for ln in main_src.splitlines() if ln.strip().startswith("print(") and "file=sys.stderr" not in ln]
     assert prints == ["print(json.dumps(compact_line(line)), flush=True)"], prints
+
+
+def test_plain_run_options_are_there():
+    """`--full` (everything beyond the headline) and `--dump-outputs DIR` are options of every run; --help needs neither torch nor a GPU."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-1500:]
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_past_the_budget(tmp_path):
+    import numpy as np
+    bench.dump_outputs(str(tmp_path / "small"), {"gradient": np.arange(10, dtype=np.float64), "loss_total": np.float32([3.5])})
+    assert sorted(os.listdir(tmp_path / "small")) == ["gradient.npy", "loss_total.npy"]
+    g = np.load(tmp_path / "small" / "gradient.npy")
+    assert g.dtype == np.float32 and np.array_equal(g, np.arange(10))
+    big = {"forcing": np.random.default_rng(1).standard_normal((4096, 32)).astype(np.float32), "loss_total": np.float32([1.0])}
+    budget = 64 << 10
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, budget=budget)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["forcing.npy", "forcing_index.npy", "loss_total.npy", "loss_total_index.npy"]
+    assert sum(np.load(tmp_path / "a" / n).nbytes for n in names) <= budget
+    idx, vals = np.load(tmp_path / "a" / "forcing_index.npy"), np.load(tmp_path / "a" / "forcing.npy")
+    assert idx.dtype == np.float64 and vals.dtype == np.float32 and len(vals) > 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(vals, big["forcing"].reshape(-1)[idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b" / "forcing_index.npy"), idx)            # the same sample from run to run
+    assert np.load(tmp_path / "a" / "loss_total.npy").tolist() == [1.0]
+    assert bench.DUMP_BUDGET_BYTES + 4096 <= 64 * 10 ** 6
