@@ -68,6 +68,14 @@ SYMBOLS = [
     ("colnde_allreduce_result_dev", ctypes.c_int, [_V, _V, _V]),
     ("colnde_plan", ctypes.c_int, [_V, ctypes.POINTER(ctypes.c_int)]),
     ("colnde_describe", ctypes.c_int, [_V, ctypes.c_char_p, ctypes.c_int]),
+    ("colnde_create_ensemble", ctypes.c_int, [_V, ctypes.c_int, _V, ctypes.POINTER(_V)]),
+    ("colnde_n_models", ctypes.c_int, [_V]),
+    ("colnde_ensemble_set_physics", ctypes.c_int, [_V, _V]),
+    ("colnde_ensemble_forward_dev", ctypes.c_int, [_V, _V, _V]),
+    ("colnde_ensemble_loss_dev", ctypes.c_int, [_V, _V, _F, _V]),
+    ("colnde_ensemble_loss_grad_dev", ctypes.c_int, [_V, _V, _F, _V]),
+    ("colnde_ensemble_loss_grad", ctypes.c_int, [_V, _V, _F, _V]),
+    ("colnde_ensemble_adam_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V] + [ctypes.c_float] * 5),
     ("colnde_set_profiling", ctypes.c_int, [_V, ctypes.c_int]),
     ("colnde_kernel_time", ctypes.c_int, [_V, ctypes.c_int, _F, ctypes.POINTER(ctypes.c_int)]),
     ("colnde_reset_kernel_times", ctypes.c_int, [_V]),

@@ -27,6 +27,14 @@ static int fail(const char* fmt, ...) {
     return 1;
 }
 
+// Entry points that take ONE weight vector refuse an ensemble handle (colnde_create_ensemble)
+#define SINGLE_MODEL_ONLY(h)                                                                                                              \
+    do {                                                                                                                                  \
+        if ((h) && (h)->ensemble)                                                                                                         \
+            return fail("%s takes one weight vector, but this handle holds an ensemble of %d models: use colnde_ensemble_* (include/colnde.h)", \
+                        __func__, (h)->n_models);                                                                                         \
+    } while (0)
+
 // shared with comm.hip (not part of the public header)
 extern "C" int colnde_internal_set_error(const char* msg) { g_err = msg ? msg : "error"; return 1; }
 
@@ -105,6 +113,14 @@ struct colnde_handle {
     bool ag_rows = false;           // the tile16 kernels keep the activation rows in global memory (DevModel::ag)
     bool substeps_chosen = false;   // the count in use came out of choose_substeps_impl (colnde_describe says so, with the estimate)
     float* d_rkc = nullptr;         // RKC2 coefficient table (DevModel::rkc)
+    // ensembles (colnde_create_ensemble): n_models models of this configuration in one launch per kernel (blockIdx.y = model)
+    bool ensemble = false;
+    int n_models = 1;
+    std::vector<RtPhys> phys_host;  // per-model closure constants (closure_constants), and their device copy
+    RtPhys* d_phys = nullptr;
+    RtEns ens;                      // per-model strides of the buffers a model owns
+    size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)
+    int ens_rkc_stages = 0;         // RKC2, automatic stage count: the largest any model needs (refresh_rkc)
     std::vector<PendingEvent> pending;
     double ms[K_COUNT] = {};
     int launches[K_COUNT] = {};
@@ -234,6 +250,15 @@ extern "C" int colnde_min_substeps(const colnde_config* c) {
     return need <= 1.0 ? 1 : (int)ceil(need);
 }
 
+// inv_dRi, inv_Pr and c_rib of the Richardson-number closure from the five Pacanowski-Philander constants: ONE expression for the single
+// handle (build_model) and for every model of an ensemble, so that model k and a handle built with model k's constants see identical floats
+static RtPhys closure_constants(float nu0, float nu_minus, float dRi, float Ric, float Pr) {
+    RtPhys p;
+    p.nu0 = nu0; p.nu_minus = nu_minus; p.Ric = Ric; p.inv_dRi = 1.0f / dRi; p.inv_Pr = 1.0f / Pr; p.c_rib = -nu_minus / (2.0f * dRi);
+    p.pad0 = 0.0f; p.pad1 = 0.0f;
+    return p;
+}
+
 static void build_model(const colnde_config* c, DevModel* m, PackInfo* pk) {
     memset(m, 0, sizeof(*m));
     memset(pk, 0, sizeof(*pk));
@@ -294,7 +319,8 @@ static void build_model(const colnde_config* c, DevModel* m, PackInfo* pk) {
     m->C_fc = (sg[5] / sg[2]) * (c->tau / c->H);
     m->sig_u = sg[0]; m->sig_v = sg[1]; m->mu_u = mu[0]; m->mu_v = mu[1];
     m->mu_wT = mu[5]; m->sig_wT = sg[5]; m->mu_T = mu[2]; m->sig_T = sg[2];
-    m->nu0 = c->nu0; m->nu_minus = c->nu_minus; m->Ric = c->Ric; m->dRi = c->dRi; m->inv_dRi = 1.0f / c->dRi; m->inv_Pr = 1.0f / c->Pr; m->c_rib = -c->nu_minus / (2.0f * c->dRi); m->Pr = c->Pr;
+    const RtPhys ph = closure_constants(c->nu0, c->nu_minus, c->dRi, c->Ric, c->Pr);
+    m->nu0 = ph.nu0; m->nu_minus = ph.nu_minus; m->Ric = ph.Ric; m->dRi = c->dRi; m->inv_dRi = ph.inv_dRi; m->inv_Pr = ph.inv_Pr; m->c_rib = ph.c_rib; m->Pr = c->Pr;
     m->kappa = c->kappa; m->eps = c->eps; m->ca_K = c->ca_K; m->tau = c->tau; m->alpha_g = c->alpha * c->g;
 }
 
@@ -356,7 +382,7 @@ static int ensure_ag(colnde_handle* h, size_t tiles) {
 // frozen at creation would be too short for a longer step — unstable — and wastefully long for a shorter one).  Uploaded in stream order.
 static int refresh_rkc(colnde_handle* h) {
     if (h->cfg.stepper != COLNDE_STEPPER_RKC2) return 0;
-    const int s = colnde_rkc_stages(&h->cfg);
+    const int s = h->ens_rkc_stages ? h->ens_rkc_stages : colnde_rkc_stages(&h->cfg);
     if (s < 2) return 1;
     if (s == h->m.nst && !h->rkc_host.empty()) return 0;
     std::vector<double> tab;
@@ -594,7 +620,7 @@ extern "C" void colnde_destroy(colnde_handle* h) {
     drain_events(h);
     void* ptrs[] = {h->d_rt_tapez, h->d_rt_tape, h->d_rt_tape2, h->d_rt_slab, h->d_wimg, h->d_w, h->d_wf, h->d_wb, h->d_x0, h->d_bcs, h->d_truth, h->d_sol, h->d_tape, h->d_slab, h->d_out,
                     h->d_times, h->d_partial, h->d_tmp_a, h->d_tmp_b, h->d_tmp_c, h->d_tiles, h->d_bias_zoff, h->d_bias_goff, h->d_dwtape, h->d_macros, h->d_t16_ztape, h->d_rkc, h->d_ag, h->d_sf, h->d_sb,
-                    h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_masks, h->d_fc_switch, h->d_fc_lam, h->d_fc_simgf, h->d_fc_simgb};
+                    h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_masks, h->d_fc_switch, h->d_fc_lam, h->d_fc_simgf, h->d_fc_simgb, h->d_phys};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     dw_split_free(h->dw_split);
@@ -621,6 +647,7 @@ extern "C" int colnde_set_matrix_arithmetic(colnde_handle* h, int ma) {
 extern "C" int colnde_matrix_arithmetic(const colnde_handle* h) { return h ? h->cfg.matrix_arithmetic : -1; }
 
 extern "C" int colnde_set_global_columns(colnde_handle* h, int64_t n) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (n < h->n_col) return fail("global column count %lld < local %d", (long long)n, h->n_col);
     h->n_col_total = n;
@@ -719,6 +746,7 @@ static void loss_weights(const colnde_handle* h, const float scalings[6], LossWe
 // ---- rhs -----------------------------------------------------------------------------------------------
 extern "C" int colnde_rhs_dev(colnde_handle* h, const float* d_x, const float* d_weights, const float* d_bcs, float t,
                               float* d_dx, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_x || !d_weights || !d_bcs || !d_dx) return fail("null pointer argument");
     if (n_columns < 1) return fail("n_columns must be >= 1");
@@ -745,6 +773,7 @@ static int ensure_tmp(colnde_handle* h, size_t n_columns) {
 
 extern "C" int colnde_rhs(colnde_handle* h, const float* x, const float* weights, const float* bcs, float t, float* dx,
                           int n_columns) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!x || !weights || !bcs || !dx) return fail("null pointer argument");
     if (n_columns < 1) return fail("n_columns must be >= 1");
@@ -919,6 +948,7 @@ static int forward_impl(colnde_handle* h, const float* d_weights, float* d_sol, 
 
 
 extern "C" int colnde_forward_dev(colnde_handle* h, const float* d_weights, float* d_sol) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_weights) return fail("null weights");
     HIPCHK(hipSetDevice(h->device));
@@ -926,6 +956,7 @@ extern "C" int colnde_forward_dev(colnde_handle* h, const float* d_weights, floa
 }
 
 extern "C" int colnde_forward(colnde_handle* h, const float* weights, float* sol) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!weights) return fail("null weights");
     HIPCHK(hipSetDevice(h->device));
@@ -939,6 +970,7 @@ extern "C" int colnde_forward(colnde_handle* h, const float* weights, float* sol
 
 // ---- loss / loss + gradient ----------------------------------------------------------------------------
 extern "C" int colnde_loss_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out8) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_weights || !scalings || !d_out8) return fail("null pointer argument");
     if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
@@ -954,6 +986,7 @@ extern "C" int colnde_loss_dev(colnde_handle* h, const float* d_weights, const f
 }
 
 extern "C" int colnde_loss(colnde_handle* h, const float* weights, const float scalings[6], float terms[6], float* total) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!weights || !scalings || !terms || !total) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
@@ -1209,6 +1242,7 @@ static int t16_plan_dwtape(colnde_handle* h) {
 }
 
 extern "C" int colnde_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_weights || !scalings || !d_out) return fail("null pointer argument");
     if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
@@ -1389,6 +1423,7 @@ extern "C" int colnde_loss_grad_dev(colnde_handle* h, const float* d_weights, co
 
 extern "C" int colnde_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float terms[6],
                                 float* total, float* grad) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!weights || !scalings || !terms || !total || !grad) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
@@ -1402,6 +1437,310 @@ extern "C" int colnde_loss_grad(colnde_handle* h, const float* weights, const fl
     for (int q = 0; q < 6; q++) terms[q] = o[q];
     *total = o[6];
     if (!std::isfinite(o[6])) return fail("the loss is not finite (%g): the solve left the stable regime (time step, weights or inputs)", o[6]);
+    return 0;
+}
+
+// ---- ensembles: K models of one architecture side by side (colnde_create_ensemble) ---------------------------------------------------------------
+// The reference's sweep (wind_mixing/train_NDE_args.jl: activation, ADAM rate and Pacanowski-Philander constants per process) trains many small
+// models of ONE architecture on the same simulations.  Here every kernel of a training iteration runs once for all K models with the model index in
+// blockIdx.y: the net-split pair (rt16sh_*), the weight packers, tile16's dW GEMM, the loss and gradient reductions and the ADAM step.  A model owns
+// its packed weights, solution, tapes and slab rows (RtEns strides) and its closure constants (RtPhys); x0, bcs and truth are shared.
+
+// the configuration of model k: cfg with row k of physics ([K][5]: nu0, nu_minus, dRi, Ric, Pr)
+static colnde_config model_config(const colnde_config* cfg, const float* physics, int k) {
+    colnde_config c = *cfg;
+    if (physics) {
+        const float* r = physics + (size_t)5 * k;
+        c.nu0 = r[0]; c.nu_minus = r[1]; c.dRi = r[2]; c.Ric = r[3]; c.Pr = r[4];
+    }
+    return c;
+}
+
+// The shared sub-step count against every model's stability bound; RKC2 with automatic stages: the largest stage count any model needs.
+// *min_sub / *stages: the ensemble's bound and stage count (stages = 0 for RK4).
+static int ens_stability(const colnde_config* cfg, int K, const float* physics, int* min_sub, int* stages) {
+    *min_sub = 1;
+    *stages = 0;
+    for (int k = 0; k < K; k++) {
+        const colnde_config c = model_config(cfg, physics, k);
+        if (physics) {
+            const float* r = physics + (size_t)5 * k;
+            for (int q = 0; q < 5; q++)
+                if (!std::isfinite(r[q])) return fail("physics[%d][%d] = %g is not finite", k, q, r[q]);
+            if (!(c.dRi > 0.0f) || !(c.Pr > 0.0f)) return fail("physics[%d]: dRi = %g and Pr = %g must be > 0", k, c.dRi, c.Pr);
+        }
+        const int ms = colnde_min_substeps(&c);
+        if (ms < 0) return 1;
+        *min_sub = std::max(*min_sub, ms);
+        if (cfg->stepper == COLNDE_STEPPER_RKC2 && !cfg->rkc_stages) *stages = std::max(*stages, colnde_rkc_stages(&c));
+        const char* e = getenv("COLNDE_ALLOW_UNSTABLE_DT");
+        if (cfg->substeps < ms && !(e && atoi(e) != 0))
+            return fail("model %d (nu0 = %g, nu_minus = %g, Pr = %g) needs substeps >= %d for a stable step (colnde_min_substeps; lambda = -%.4g), but the "
+                        "ensemble shares substeps = %d (COLNDE_ALLOW_UNSTABLE_DT=1 overrides)", k, c.nu0, c.nu_minus, c.Pr, ms, stiff_lambda(&c), cfg->substeps);
+    }
+    return 0;
+}
+
+static int ens_upload_physics(colnde_handle* h, const float* physics) {
+    std::vector<RtPhys> ph((size_t)h->n_models);
+    for (int k = 0; k < h->n_models; k++) {
+        const colnde_config c = model_config(&h->cfg, physics, k);
+        ph[k] = closure_constants(c.nu0, c.nu_minus, c.dRi, c.Ric, c.Pr);
+    }
+    // (kernels in flight on the stream may still read the previous table: the copy is ordered on the stream and completed before returning)
+    HIPCHK(hipMemcpyAsync(h->d_phys, ph.data(), ph.size() * sizeof(RtPhys), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->phys_host.swap(ph);
+    return 0;
+}
+
+// The tapes of all K models, planned once at creation: tile16's taped-dW formats for ONE block of all columns per model (the net-split pair has no
+// column-block loop across models), the rich tape while the K models' 16-column tiles number at most 128 (2,048 columns in flight: the single
+// handle's crossover, which counts concurrent tiles whoever owns them).  Refused with the bytes it needs when it does not fit.
+static int ens_plan_tapes(colnde_handle* h) {
+    const DevModel& m = h->m;
+    const int K = h->n_models;
+    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
+    const size_t n_rec = (size_t)h->n_tiles * n_steps * m.nst;
+    const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
+    std::vector<DwMacro> mac;
+    build_dw_macros(h, n_rec, mac);                          // the slice count a single handle of this size plans: same reduction order
+    h->t16_rows = h->n_tiles + h->dw_slices;
+    const size_t f_tape = n_rec * CT * m.ns, f_dw = n_rec * CT * R, f_rich = n_rec * rt_split_rich_record_floats(),
+                 f_plain = n_rec * CT * t16_ztape_col_floats(m), f_slab = (size_t)h->t16_rows * P8,
+                 f_sol = (size_t)h->n_col * h->cfg.n_save * m.ns, f_img = RT_IMG_STRIDE;
+    const char* er = getenv("COLNDE_T16_SPLIT_RICH");
+    const bool forced = er && *er;
+    bool rich = forced ? atoi(er) != 0 : (size_t)K * h->n_tiles <= 128;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t margin = ((size_t)3 << 30) + (size_t)K * (P8 * 2 + 256 * 8) * sizeof(float);
+    const size_t budget = free_b > margin ? free_b - margin : 0;
+    auto per_model = [&](bool r) { return (f_tape + f_dw + (r ? f_rich : f_plain) + f_slab + f_sol + f_img) * sizeof(float); };
+    if (rich && !forced && (size_t)K * per_model(true) > budget) rich = false;       // the automatic rich tape gives way to the plain one, as for one handle
+    const size_t need = per_model(rich);
+    if ((size_t)K * need > budget)
+        return fail("an ensemble of %d models needs %zu bytes of device memory for its tapes, slab rows and solutions (%zu per model, %s tape, "
+                    "%d substeps x %d stages x %d save intervals); %zu bytes are free (3 GB kept in reserve): use fewer models per handle",
+                    K, (size_t)K * need, need, rich ? "rich" : "plain", h->cfg.substeps, m.nst, h->cfg.n_save - 1, free_b);
+    const size_t f_z = rich ? f_rich : f_plain;
+    hipError_t e = hipMalloc((void**)&h->d_dwtape, (size_t)K * f_dw * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tape, (size_t)K * f_tape * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_t16_ztape, (size_t)K * f_z * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_slab, (size_t)K * f_slab * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_macros, mac.size() * sizeof(DwMacro));
+    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("allocating the ensemble's tapes (%zu bytes, %zu per model) failed: %s", (size_t)K * need, need, hipGetErrorString(e));
+    }
+    h->t16_dwtape = 1;
+    h->t16_block = h->n_tiles * CT;
+    h->t16_nblocks = 1;
+    h->split_rich = rich;
+    h->ens.wimg = f_img;
+    h->ens.sol = f_sol;
+    h->ens.tape = f_tape;
+    h->ens.ztape = f_z;
+    h->ens.dwtape = f_dw;
+    h->ens.slab = f_slab;
+    h->ens.n_models = K;
+    h->ens.phys = h->d_phys;
+    h->ens_model_bytes = need;
+    return 0;
+}
+
+extern "C" int colnde_create_ensemble(const colnde_config* cfg, int n_models, const float* physics, colnde_handle** out) {
+    if (!out) return fail("null out pointer");
+    *out = nullptr;
+    if (validate(cfg)) return 1;
+    if (n_models < 1 || n_models > 65535) return fail("n_models = %d outside 1..65535", n_models);
+    // only the configurations on which AUTO runs the four-wave net-split pair: those kernels carry the model index
+    if (cfg->model != COLNDE_MODEL_WIND_MIXING)
+        return fail("ensembles cover the wind-mixing NDE on the net-split kernels: the free-convection models (fc32 / tile16) run one handle per model");
+    if (cfg->inplace_variant) return fail("ensembles train on the training RHS: inplace_variant (the NDE! evaluation RHS) is not supported");
+    if (cfg->engine != COLNDE_ENGINE_AUTO)
+        return fail("ensembles run the net-split kernels engine AUTO selects: engine forced to %d is not supported (those engines have no model index)", cfg->engine);
+    if (cfg->substeps == 0)
+        return fail("substeps = 0 (chosen from reltol by the first solve) is not supported: the models share one sub-step count, and the tapes are sized at "
+                    "creation — choose it with a single handle (colnde_choose_substeps) and pass it");
+    if (cfg->n_columns > 8192)
+        return fail("%d columns per model: ensembles cover the net-split range (at most 8,192 columns per model); above it regtile runs one handle per model",
+                    cfg->n_columns);
+    {
+        DevModel dm;
+        PackInfo pk;
+        build_model(cfg, &dm, &pk);
+        if (!rt_supported(dm))
+            return fail("ensembles cover the net-split shape only (Nz = 32, three 96-50-20-31 nets, one hidden activation, training RHS, no smoothing): "
+                        "wide networks and other architectures run one handle per model");
+    }
+    if (physics && !cfg->modified_pacanowski_philander)
+        return fail("a physics array needs modified_pacanowski_philander = 1: without the Richardson-number closure the five constants are unused (pass NULL)");
+    // the environment switches that send a single handle down paths without a model index
+    static const char* const no_index[] = {"COLNDE_T16_FWD_HELPER", "COLNDE_T16_ADJ_HELPER", "COLNDE_T16_FWD_SPLIT", "COLNDE_T16_ADJ_SPLIT", "COLNDE_T16_ZTAPE",
+                                           "COLNDE_T16_DWTAPE"};
+    for (const char* name : no_index) {
+        const char* e = getenv(name);
+        if (e && *e && atoi(e) == 0)
+            return fail("%s=0 selects kernels without a model index (the three-wave or tile16 kernels, or no delta / pre-activation tape): ensembles refuse it", name);
+    }
+    if (getenv("COLNDE_T16_BLOCK")) return fail("COLNDE_T16_BLOCK: ensembles hold one block of columns per model (the column-block loop has no model index)");
+    int min_sub = 1, stages = 0;
+    if (ens_stability(cfg, n_models, physics, &min_sub, &stages)) return 1;
+    colnde_handle* h = nullptr;
+    if (colnde_create(cfg, &h)) return 1;
+    if (h->use_rt || h->use_fc || h->ag_rows || !h->fwd_split || !h->adj_split || !h->fwd_helper || !h->adj_helper) {
+        colnde_destroy(h);
+        return fail("this configuration does not run the four-wave net-split pair under engine AUTO: ensembles refuse it");
+    }
+    h->ensemble = true;
+    h->n_models = n_models;
+    h->min_substeps = min_sub;
+    if (stages > 0 && stages != h->m.nst) {
+        h->ens_rkc_stages = stages;
+        if (refresh_rkc(h)) { colnde_destroy(h); return 1; }
+    } else if (stages > 0) {
+        h->ens_rkc_stages = stages;
+    }
+    const size_t K = (size_t)n_models, P = (size_t)h->m.n_params;
+    auto realloc_ = [&](float** p, size_t n) {
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+        if (hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return true;
+    };
+    if (!realloc_(&h->d_w, K * P) || !realloc_(&h->d_out, K * (P + 8)) || !realloc_(&h->d_partial, K * 256 * 8) ||
+        !realloc_(&h->d_sol, K * h->n_col * h->cfg.n_save * h->m.ns) || !realloc_(&h->d_wimg, K * RT_IMG_STRIDE) ||
+        hipMalloc((void**)&h->d_phys, K * sizeof(RtPhys)) != hipSuccess) {
+        (void)hipGetLastError();
+        colnde_destroy(h);
+        return fail("allocating the ensemble's per-model buffers (%d models) failed", n_models);
+    }
+    if (ens_upload_physics(h, physics) || ens_plan_tapes(h)) { colnde_destroy(h); return 1; }
+    *out = h;
+    return 0;
+}
+
+extern "C" int colnde_n_models(const colnde_handle* h) { return h ? h->n_models : -1; }
+
+static int ensemble_only(const colnde_handle* h) {
+    if (!h) return fail("null handle");
+    if (!h->ensemble) return fail("not an ensemble handle: colnde_ensemble_* take the handles of colnde_create_ensemble (colnde_create: the single-model calls)");
+    return 0;
+}
+
+extern "C" int colnde_ensemble_set_physics(colnde_handle* h, const float* physics) {
+    if (ensemble_only(h)) return 1;
+    if (!physics) return fail("null physics array");
+    if (!h->cfg.modified_pacanowski_philander)
+        return fail("a physics array needs modified_pacanowski_philander = 1: without the Richardson-number closure the five constants are unused");
+    HIPCHK(hipSetDevice(h->device));
+    int min_sub = 1, stages = 0;
+    if (ens_stability(&h->cfg, h->n_models, physics, &min_sub, &stages)) return 1;
+    // the tapes hold the stage count planned at creation
+    if (stages > h->m.nst)
+        return fail("the new constants need %d RKC2 stages per step, the ensemble's tapes were planned for %d: create a new ensemble", stages, h->m.nst);
+    if (ens_upload_physics(h, physics)) return 1;
+    h->min_substeps = min_sub;
+    return 0;
+}
+
+// forward solve of all K models (with_tape: into the ensemble's tapes)
+static int ens_forward(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape) {
+    if (!h->have_problem) return fail("colnde_set_problem has not been called");
+    if (check_stability(h)) return 1;
+    RtEns ens = h->ens;
+    ens.sol = (size_t)h->n_col * h->cfg.n_save * h->m.ns;
+    Timed tm(h, K_FORWARD);
+    hipError_t e = rt_launch_pack(h->m, d_weights, h->d_wimg, h->stream, h->n_models);
+    if (e == hipSuccess)
+        e = rt_launch_forward_split(h->m, h->d_wimg, h->d_x0, h->d_bcs, h->d_times, h->cfg.n_save, h->cfg.substeps, d_sol,
+                                    with_tape ? h->d_tape : nullptr, with_tape ? h->d_t16_ztape : nullptr, h->n_col, with_tape && h->split_rich,
+                                    true, h->sp_fwd, h->stream, ens);
+    if (e != hipSuccess) return fail("ensemble forward launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_forward_dev(colnde_handle* h, const float* d_weights, float* d_sol) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !d_sol) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    return ens_forward(h, d_weights, d_sol, false);
+}
+
+extern "C" int colnde_ensemble_loss_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out8) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !scalings || !d_out8) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    HIPCHK(hipSetDevice(h->device));
+    if (ens_forward(h, d_weights, h->d_sol, false)) return 1;
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    const int nblk = 256;
+    hipError_t e = launch_loss(h->m, h->d_sol, h->d_truth, h->cfg.n_save, h->n_col, h->d_partial, nblk, h->stream, h->n_models, h->ens.sol);
+    if (e == hipSuccess) e = launch_reduce(h->d_partial, nblk, 0, 8, lw, d_out8, h->stream, h->n_models, (size_t)nblk * 8, 8);
+    if (e != hipSuccess) return fail("ensemble loss launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !scalings || !d_out) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    HIPCHK(hipSetDevice(h->device));
+    const int K = h->n_models, stride = h->m.n_params + 8;
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->ens.slab * sizeof(float), h->stream));
+    if (ens_forward(h, d_weights, h->d_sol, true)) return 1;
+    hipError_t e;
+    {
+        Timed tm(h, K_ADJOINT);
+        e = rt_launch_adjoint_split(h->m, h->d_wimg, h->d_times, h->cfg.n_save, h->cfg.substeps, h->d_sol, h->d_truth, h->d_tape, h->d_t16_ztape, lw,
+                                    h->d_slab, h->n_col, h->d_dwtape, h->split_rich, true, h->sp_adj, h->stream, h->ens);
+        if (e != hipSuccess) return fail("ensemble adjoint launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        Timed tm(h, K_DW1);
+        const size_t n_rec = (size_t)h->n_tiles * (h->cfg.n_save - 1) * h->cfg.substeps * h->m.nst;
+        float* rows = h->d_slab + (size_t)h->n_tiles * stride;
+        e = (h->sp_dw && !h->dw_split.passes.empty())
+            ? launch_dw_gemm_split(h->d_dwtape, n_rec, (int)dwtape_row_floats(h->m), h->dw_split, h->dw_slices, rows, stride, h->stream, K, h->ens.dwtape, h->ens.slab)
+            : launch_dw_gemm(h->d_dwtape, n_rec, (int)dwtape_row_floats(h->m), h->d_macros, h->n_macros, h->dw_slices, rows, stride, h->stream, K, h->ens.dwtape,
+                             h->ens.slab);
+        if (e != hipSuccess) return fail("ensemble dW GEMM launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        Timed tm(h, K_REDUCE);
+        e = launch_reduce(h->d_slab, h->t16_rows, h->m.n_params, stride, lw, d_out, h->stream, K, h->ens.slab, stride);
+        if (e != hipSuccess) return fail("ensemble reduce launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+extern "C" int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float* out) {
+    if (ensemble_only(h)) return 1;
+    if (!weights || !scalings || !out) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t K = (size_t)h->n_models, P = (size_t)h->m.n_params;
+    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * K * P, hipMemcpyHostToDevice, h->stream));
+    if (colnde_ensemble_loss_grad_dev(h, h->d_w, scalings, h->d_out)) return 1;
+    HIPCHK(hipMemcpyAsync(out, h->d_out, sizeof(float) * K * (P + 8), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_result, float* d_m, float* d_v, const float* d_eta,
+                                             float beta1, float beta2, float eps, float beta1_t, float beta2_t) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !d_result || !d_m || !d_v || !d_eta) return fail("null pointer argument");
+    if (!(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f)) return fail("0 <= beta < 1 required");
+    if (!(beta1_t < 1.0f && beta2_t < 1.0f)) return fail("running powers beta^t must be < 1");
+    HIPCHK(hipSetDevice(h->device));
+    Timed tm(h, K_ADAM);
+    hipError_t e = launch_adam_ensemble(d_weights, d_result, h->m.n_params + 8, d_m, d_v, d_eta, beta1, beta2, eps, beta1_t, beta2_t, h->m.n_params,
+                                        h->n_models, h->stream);
+    if (e != hipSuccess) return fail("ensemble ADAM launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 
@@ -1448,6 +1787,7 @@ static float richardson_factor(const colnde_handle* h) {
 static float norm_floor(float reltol) { return 1e-6f / (reltol > 0.0f ? reltol : 1e-3f); }
 
 extern "C" int colnde_error_estimate_dev(colnde_handle* h, const float* d_weights, float* max_rel_err) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_weights || !max_rel_err) return fail("null pointer argument");
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
@@ -1468,6 +1808,7 @@ extern "C" int colnde_error_estimate_dev(colnde_handle* h, const float* d_weight
 }
 
 extern "C" int colnde_error_estimate(colnde_handle* h, const float* weights, float* max_rel_err) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!weights || !max_rel_err) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
@@ -1524,6 +1865,7 @@ static int choose_substeps_impl(colnde_handle* h, const float* d_weights, float 
 }
 
 extern "C" int colnde_choose_substeps(colnde_handle* h, const float* weights, float reltol, int* substeps, float* estimate) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!weights) return fail("null weights");
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
@@ -1541,6 +1883,7 @@ extern "C" int colnde_substeps(const colnde_handle* h) { return h ? h->cfg.subst
 // Impose a sub-step count (e.g. the MAX over ranks of what colnde_choose_substeps chose on each shard).  Refused once the tapes are planned (the count
 // sizes them) and outside the stepper's stability bound; clears a pending substeps = 0.
 extern "C" int colnde_set_substeps(colnde_handle* h, int substeps) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (substeps < 1) return fail("substeps must be >= 1");
     if (substeps == h->cfg.substeps && !h->auto_substeps) return 0;
@@ -1560,6 +1903,7 @@ extern "C" int colnde_set_substeps(colnde_handle* h, int substeps) {
 
 // ---- flux diagnostics: predict_flux and loss_per_tstep ---------------------------------------------------------------------------------
 extern "C" int colnde_flux_dev(colnde_handle* h, const float* d_x, const float* d_weights, const float* d_bcs, float t, float* d_flux, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_x || !d_weights || !d_bcs || !d_flux) return fail("null pointer argument");
     if (n_columns < 1) return fail("n_columns must be >= 1");
@@ -1573,6 +1917,7 @@ extern "C" int colnde_flux_dev(colnde_handle* h, const float* d_x, const float* 
 }
 
 extern "C" int colnde_flux(colnde_handle* h, const float* x, const float* weights, const float* bcs, float t, float* flux, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!x || !weights || !bcs || !flux) return fail("null pointer argument");
     if (n_columns < 1) return fail("n_columns must be >= 1");
@@ -1603,6 +1948,7 @@ extern "C" int colnde_flux(colnde_handle* h, const float* x, const float* weight
 }
 
 extern "C" int colnde_loss_per_tstep_dev(colnde_handle* h, const float* d_weights, float* d_out) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_weights || !d_out) return fail("null pointer argument");
     if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
@@ -1614,6 +1960,7 @@ extern "C" int colnde_loss_per_tstep_dev(colnde_handle* h, const float* d_weight
 }
 
 extern "C" int colnde_loss_per_tstep(colnde_handle* h, const float* weights, float* out) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!weights || !out) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
@@ -1640,10 +1987,12 @@ extern "C" int colnde_loss_per_tstep(colnde_handle* h, const float* weights, flo
 static int infer_impl(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, float Lz, float* d_out, int n_columns, float sign);
 extern "C" int colnde_infer_forcing_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux,
                                         float Lz, float* d_out, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
     return infer_impl(h, d_weights, d_T, d_top_flux, Lz, d_out, n_columns, 1.0f);
 }
 extern "C" int colnde_infer_dz_wT_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux,
                                       float Lz, float* d_out, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
     return infer_impl(h, d_weights, d_T, d_top_flux, Lz, d_out, n_columns, -1.0f);
 }
 static int infer_impl(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, float Lz, float* d_out, int n_columns, float sign) {
@@ -1673,10 +2022,12 @@ static int infer_impl(colnde_handle* h, const float* d_weights, const float* d_T
 static int infer_host(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz, float* out, int n_columns, float sign);
 extern "C" int colnde_infer_forcing(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz,
                                     float* out, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
     return infer_host(h, weights, T, top_flux, Lz, out, n_columns, 1.0f);
 }
 extern "C" int colnde_infer_dz_wT(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz,
                                   float* out, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
     return infer_host(h, weights, T, top_flux, Lz, out, n_columns, -1.0f);
 }
 static int infer_host(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz, float* out, int n_columns, float sign) {
@@ -1838,6 +2189,7 @@ extern "C" int colnde_scale_dev(colnde_handle* h, const float* d_x, int64_t coun
 // [grad; terms; total; 0] of this rank summed over the communicator, on the handle's stream (comm.hip)
 extern "C" int colnde_comm_allreduce_dev(colnde_comm* c, float* d_buf, int64_t n, int op, void* hip_stream);
 extern "C" int colnde_allreduce_result_dev(colnde_handle* h, colnde_comm* comm, float* d_out) {
+    SINGLE_MODEL_ONLY(h);
     if (!h || !comm || !d_out) return fail("null argument");
     return colnde_comm_allreduce_dev(comm, d_out, (int64_t)h->m.n_params + 8, 0, (void*)h->stream);
 }
@@ -1847,6 +2199,7 @@ extern "C" int colnde_pretrain_flux_dev(colnde_handle* h, int flux_type, float* 
                                         const float* d_bcs, const float* d_flux, const int32_t* d_order, int n_samples,
                                         float gradient_scaling, float eta, float beta1, float beta2, float eps, double beta_t[2],
                                         int update, float* mean_loss) {
+    SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_theta || !d_profiles || !d_bcs || !d_flux || !beta_t || !mean_loss) return fail("null pointer argument");
     if (update && (!d_m || !d_v)) return fail("the ADAM moments are needed when update != 0");
@@ -1936,6 +2289,7 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
     snprintf(t, sizeof t, "engine=%s columns=%d stepper=%s substeps=%d%s", eng, h->cfg.n_columns, h->cfg.stepper == COLNDE_STEPPER_RKC2 ? "rkc2" : "rk4",
              h->cfg.substeps, why);
     s += t;
+    if (h->ensemble) { snprintf(t, sizeof t, " models=%d tape_bytes_per_model=%zu", h->n_models, h->ens_model_bytes); s += t; }
     if (h->cfg.stepper == COLNDE_STEPPER_RKC2) { snprintf(t, sizeof t, " rkc_stages=%d%s", h->m.nst, h->cfg.rkc_stages ? "" : "(automatic)"); s += t; }
     snprintf(t, sizeof t, " matrix_arithmetic=%s forward=%s adjoint=%s dw=%s", h->cfg.matrix_arithmetic == COLNDE_MATRIX_BF16X3_EXACT ? "bf16x3_exact" : "f32_mfma",
              (info[7] & 2) ? "bf16x3" : "f32", (info[7] & 4) ? "bf16x3" : "f32", (info[7] & 8) ? "bf16x3" : "f32");

@@ -13,6 +13,8 @@ hipError_t launch_mpp_diffusion(const float* u, const float* v, const float* T, 
                                 hipStream_t stream);
 hipError_t launch_adam_step(float* w, const float* grad, float* m, float* v, float eta, float beta1, float beta2, float eps,
                             float beta1_t, float beta2_t, int n, hipStream_t stream);
+hipError_t launch_adam_ensemble(float* w, const float* grad, int grad_stride, float* m, float* v, const float* eta, float beta1, float beta2,
+                                float eps, float beta1_t, float beta2_t, int n, int n_models, hipStream_t stream);
 // data preparation: rows are profiles ([n_rows][N] -> [n_rows][n]); face = 0: block means, 1: linear interpolation keeping the end points
 hipError_t launch_coarse_grain(const float* in, int n_rows, int N, int n, int face, float* out, hipStream_t stream);
 hipError_t launch_zscore_stats(const float* x, long count, float* out2 /* mu, sigma */, hipStream_t stream);

@@ -161,6 +161,30 @@ hipError_t launch_adam_step(float* w, const float* grad, float* m, float* v, flo
     return hipGetLastError();
 }
 
+// The same update for an ensemble of K models in one launch (blockIdx.y = model): weights, moments [K][n], the gradient read at
+// stride g_stride straight from the result buffer of colnde_ensemble_loss_grad_dev ([K][n + 8]: gradient first), eta[K] per model.
+__global__ void __launch_bounds__(256) adam_ensemble_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, const float* __restrict__ eta, float b1, float b2, float eps,
+                                                             float c1, float c2, int n, int g_stride) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const size_t k = blockIdx.y, o = k * (size_t)n + i;
+    const float gi = g[k * (size_t)g_stride + i];
+    const float mi = b1 * m[o] + (1.0f - b1) * gi;
+    const float vi = b2 * v[o] + (1.0f - b2) * gi * gi;
+    m[o] = mi;
+    v[o] = vi;
+    w[o] -= mi * c1 / (sqrtf(vi * c2) + eps) * eta[k];
+}
+
+hipError_t launch_adam_ensemble(float* w, const float* grad, int grad_stride, float* m, float* v, const float* eta, float beta1, float beta2,
+                                float eps, float beta1_t, float beta2_t, int n, int n_models, hipStream_t stream) {
+    if (n < 1 || n_models < 1 || grad_stride < n) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(adam_ensemble_kernel, dim3((n + 255) / 256, n_models), dim3(256), 0, stream, w, grad, m, v, eta, beta1, beta2, eps,
+                       1.0f / (1.0f - beta1_t), 1.0f / (1.0f - beta2_t), n, grad_stride);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // data preparation: wind_mixing/src/data_containers.jl:343-427 coarse-grains every LES profile
 // 128 -> 32 cells / 129 -> 33 faces and z-scores each variable before training.

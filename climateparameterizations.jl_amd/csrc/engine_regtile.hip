@@ -317,7 +317,10 @@ extern __shared__ __attribute__((aligned(16))) float rt_smem[];
 // ------------------------------------------------------------------------------------------------
 // weight image
 // ------------------------------------------------------------------------------------------------
-__global__ void rt_pack_kernel(DevModel m, const float* __restrict__ w, float* __restrict__ img) {
+__global__ void rt_pack_kernel(DevModel m, const float* __restrict__ w, float* __restrict__ img, int img_stride) {
+    // ensembles: blockIdx.y = model, weights [K][n_params] -> images img_stride floats apart (grid.y = 1: one model)
+    w += (size_t)blockIdx.y * m.n_params;
+    img += (size_t)blockIdx.y * img_stride;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < RT_IMG_FLOATS; e += gridDim.x * blockDim.x) {
         float v = 0.0f;
         if (e < RT_W2C) {
@@ -385,7 +388,9 @@ __global__ void rt_pack_split_kernel(const float* __restrict__ img, unsigned* __
 
 // ... and for the net-split adjoint's W1_n^T products (RT_NSA_*: rt16sh_adjoint_kernel<ACT, RICH, false, true>): group G = (n * 2 + kb) * 6 + tile, lane (i, kq),
 // element e <-> W1_n[feature 4 (8 kb + e) + kq][x index 16 tile + i] (zero beyond feature 49); planes h, m interleaved per group, plane l behind them
-__global__ void rt_pack_split_nsadj_kernel(const float* __restrict__ img, unsigned* __restrict__ simg) {
+__global__ void rt_pack_split_nsadj_kernel(const float* __restrict__ img, unsigned* __restrict__ simg, int img_stride) {
+    img += (size_t)blockIdx.y * img_stride;                 // ensembles: blockIdx.y = model
+    simg += (size_t)blockIdx.y * img_stride;
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < 36 * 256; x += gridDim.x * blockDim.x) {
         const int G = x >> 8, lane = (x >> 2) & 63, pr = x & 3;
         const int n = G / 12, kb = (G / 6) & 1, tile = G % 6, i = lane & 15, kq = lane >> 4;
@@ -405,7 +410,9 @@ __global__ void rt_pack_split_nsadj_kernel(const float* __restrict__ img, unsign
 
 // ... and for the net-split forward kernel (RT_SIMG2_*): layer 1 per net (tiles of that kernel: quad Q = 4 t + (i & 3) of the net's 13, feature
 // 4 Q + (i >> 2)), layer 2 as above, and the 8 live lanes of each net's fourth layer-1 tile (quad 12: features 48, 49 -> rows i = 0, 4)
-__global__ void rt_pack_split_ns_kernel(const float* __restrict__ img, unsigned* __restrict__ simg) {
+__global__ void rt_pack_split_ns_kernel(const float* __restrict__ img, unsigned* __restrict__ simg, int img_stride) {
+    img += (size_t)blockIdx.y * img_stride;                 // ensembles: blockIdx.y = model
+    simg += (size_t)blockIdx.y * img_stride;
     auto put = [&](unsigned* o, int plane_stride, float v0, float v1) {
         const float r0 = v0 - __uint_as_float(__float_as_uint(v0) & 0xffff0000u), r1 = v1 - __uint_as_float(__float_as_uint(v1) & 0xffff0000u);
         const float l0 = r0 - __uint_as_float(__float_as_uint(r0) & 0xffff0000u), l1 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
@@ -2365,6 +2372,13 @@ rt16s_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __
 #endif
 }
 
+// The Pacanowski-Philander constants of the kernels that read them per model (ensembles: RtEns::phys)
+__device__ __forceinline__ RtPhys rt_phys_of(const DevModel& m) {
+    RtPhys p;
+    p.nu0 = m.nu0; p.nu_minus = m.nu_minus; p.Ric = m.Ric; p.inv_dRi = m.inv_dRi; p.inv_Pr = m.inv_Pr; p.c_rib = m.c_rib; p.pad0 = 0.0f; p.pad1 = 0.0f;
+    return p;
+}
+
 // The same solve with a FOURTH wavefront (the workgroup's idle SIMD) as helper: it evaluates the Richardson-number closure of all three variables
 // once per stage — the diffusive face fluxes go to LDS, the rich tape's nine pullback coefficients to HBM — while the three net waves run their
 // chains; a second bare barrier per stage (B) hands the fluxes over.  Every wave executes exactly the barriers (B) and (A) in every stage.
@@ -2374,7 +2388,13 @@ template <int ACT, bool RICH, bool RKC = false, bool SPLIT = false>
 __global__ void __launch_bounds__(256)
 rt16sh_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ x0, const float* __restrict__ bcs,
                      const float* __restrict__ save_times, int n_save, int substeps, float* __restrict__ sol,
-                     float* __restrict__ t16_tape, float* __restrict__ t16_ztape, int n_col) {
+                     float* __restrict__ t16_tape, float* __restrict__ t16_ztape, int n_col, RtEns ens) {
+    // ensembles: blockIdx.y = model — its weight image, solution, tapes and closure constants (x0, bcs shared); grid.y = 1: one model
+    wimg += (size_t)blockIdx.y * ens.wimg;
+    if (sol) sol += (size_t)blockIdx.y * ens.sol;
+    if (t16_tape) t16_tape += (size_t)blockIdx.y * ens.tape;
+    if (t16_ztape) t16_ztape += (size_t)blockIdx.y * ens.ztape;
+    const RtPhys ph = ens.phys ? ens.phys[blockIdx.y] : rt_phys_of(m);
     float* wl = rt_smem;
     const u32x4* simg = reinterpret_cast<const u32x4*>(rt_smem);
     f32x4v* ex = reinterpret_cast<f32x4v*>(rt_smem + ((RT_IMG_FLOATS + 3) & ~3));          // [2 buffers][3 variables][2 tiles][64 lanes]
@@ -2450,8 +2470,8 @@ rt16sh_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* _
     const float Nz = 32.0f;
     const float L2E = 1.4426950408889634f;
     const float cU = m.sig_u * Nz, sU = m.sig_u * m.eps, cV = m.sig_v * Nz, sV = m.sig_v * m.eps, cB = m.B * Nz, sB = m.B * m.eps;
-    const float kE = 2.0f * m.inv_dRi * L2E, oE = -2.0f * m.Ric * m.inv_dRi * L2E, cE = 30.0f * L2E;
-    const float nA = -0.5f * m.nu_minus, nB = m.nu0 + 0.5f * m.nu_minus;
+    const float kE = 2.0f * ph.inv_dRi * L2E, oE = -2.0f * ph.Ric * ph.inv_dRi * L2E, cE = 30.0f * L2E;
+    const float nA = -0.5f * ph.nu_minus, nB = ph.nu0 + 0.5f * ph.nu_minus;
     const float s0n = n == 0 ? m.s0[0] : (n == 1 ? m.s0[1] : m.s0[2]);
     const float An = n == 0 ? m.A[0] : (n == 1 ? m.A[1] : m.A[2]);
     int step = 0, buf = 0;
@@ -2479,8 +2499,8 @@ rt16sh_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* _
                     V16 C[3];
                     if (m.mpp) {
                         const V16 Ud = shift_down16(Xs[0], lane, 0.0f), Vd = shift_down16(Xs[1], lane, 0.0f), Td = shift_down16(Xs[2], lane, 0.0f);
-                        const float f0 = -m.cs[0] * Nz, f1 = -m.cs[1] * Nz, f2 = -m.cs[2] * m.inv_Pr * Nz;
-                        const float m0 = -m.cs[0], m1 = -m.cs[1], m2 = -m.cs[2] * m.inv_Pr, nr = Nz * m.c_rib;
+                        const float f0 = -m.cs[0] * Nz, f1 = -m.cs[1] * Nz, f2 = -m.cs[2] * ph.inv_Pr * Nz;
+                        const float m0 = -m.cs[0], m1 = -m.cs[1], m2 = -m.cs[2] * ph.inv_Pr, nr = Nz * ph.c_rib;
 #pragma unroll
                         for (int tau = 0; tau < 2; tau++)
 #pragma unroll
@@ -2780,7 +2800,7 @@ __device__ __forceinline__ void rt16_run_ops(const float (&a)[NC][N], f32x4t (&a
         for (int c = 0; c < NC; c++) acc[c] = mfma16t(a[c][k], bval(k), acc[c]);
 }
 
-__device__ __forceinline__ void rt16_physics_vjp(const DevModel& m, const V16 (&X)[3], V16 (&kd)[3], int lane, V16 (&xb)[3]) {
+__device__ __forceinline__ void rt16_physics_vjp(const DevModel& m, const RtPhys& ph, const V16 (&X)[3], V16 (&kd)[3], int lane, V16 (&xb)[3]) {
     const float Nz = 32.0f;
     const int g = lane >> 4;
 #pragma unroll
@@ -2807,10 +2827,10 @@ __device__ __forceinline__ void rt16_physics_vjp(const DevModel& m, const V16 (&
         // the arithmetic of rt_physics_vjp, uniform factors folded
         const float cU = m.sig_u * Nz, sU = m.sig_u * m.eps, cV = m.sig_v * Nz, sV = m.sig_v * m.eps, cB = m.B * Nz, sB = m.B * m.eps;
         const float L2E = 1.4426950408889634f;
-        const float kE = 2.0f * m.inv_dRi * L2E, oE = -2.0f * m.Ric * m.inv_dRi * L2E, cE = 30.0f * L2E;
-        const float nA = -0.5f * m.nu_minus, nB = m.nu0 + 0.5f * m.nu_minus;
-        const float m0 = -m.cs[0], m1 = -m.cs[1], m2 = -m.cs[2] * m.inv_Pr;
-        const float n0 = m0 * Nz * m.c_rib, n1 = m1 * Nz * m.c_rib, n2 = m2 * Nz * m.c_rib;
+        const float kE = 2.0f * ph.inv_dRi * L2E, oE = -2.0f * ph.Ric * ph.inv_dRi * L2E, cE = 30.0f * L2E;
+        const float nA = -0.5f * ph.nu_minus, nB = ph.nu0 + 0.5f * ph.nu_minus;
+        const float m0 = -m.cs[0], m1 = -m.cs[1], m2 = -m.cs[2] * ph.inv_Pr;
+        const float n0 = m0 * Nz * ph.c_rib, n1 = m1 * Nz * ph.c_rib, n2 = m2 * Nz * ph.c_rib;
         const float q0 = -2.0f * m.sig_u, q1 = -2.0f * m.sig_v;
 #pragma unroll
         for (int tau = 0; tau < 2; tau++)
@@ -3097,7 +3117,7 @@ rt16s_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __
 #pragma unroll
                         for (int r = 0; r < 4; r++) Z2[u][r] = (4 * u + r < 5) ? z2p[(4 * u + r) < 5 ? 4 * u + r : 0] : 0.0f;
                     if (qs > 0) prefetch(qs - 1);
-                    rt16_physics_vjp(m, X, kb, lane, xbp);                               // kb now holds dO
+                    rt16_physics_vjp(m, rt_phys_of(m), X, kb, lane, xbp);                // kb now holds dO
                 }
                 RT_STAMP(0);
                 V16 dO;                 // (element-wise selects on the wave-uniform n: a select between the aggregates becomes a scratch array)
@@ -3263,7 +3283,15 @@ __global__ void __launch_bounds__(256)
 rt16sh_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ save_times, int n_save, int substeps,
                       const float* __restrict__ sol, const float* __restrict__ truth, const float* __restrict__ t16_tape,
                       const float* __restrict__ t16_ztape, LossWeights lw, float* __restrict__ slab, int n_col,
-                      float* __restrict__ dwtape) {
+                      float* __restrict__ dwtape, RtEns ens) {
+    // ensembles: blockIdx.y = model — its weight image, solution, tapes, slab rows and closure constants (truth shared); grid.y = 1: one model
+    wimg += (size_t)blockIdx.y * ens.wimg;
+    sol += (size_t)blockIdx.y * ens.sol;
+    t16_tape += (size_t)blockIdx.y * ens.tape;
+    t16_ztape += (size_t)blockIdx.y * ens.ztape;
+    slab += (size_t)blockIdx.y * ens.slab;
+    dwtape += (size_t)blockIdx.y * ens.dwtape;
+    const RtPhys ph = ens.phys ? ens.phys[blockIdx.y] : rt_phys_of(m);
     // SPLIT: LDS holds the fp32 image from W2 on (addressed through wl as before: wl[RT_W2C + x]), no fp32 W1
     constexpr int IMG0 = SPLIT ? RT_W2C : 0;
     constexpr int IMGF = ((RT_IMG_FLOATS - IMG0) + 3) & ~3;
@@ -3429,7 +3457,7 @@ rt16sh_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* _
 #pragma unroll
                         for (int q = 0; q < 3; q++) X[q] = Xp[q];
                         if (qs > 0) prefetch(PHYS_Q(qs - 1));
-                        rt16_physics_vjp(m, X, kb, lane, xbp);
+                        rt16_physics_vjp(m, ph, X, kb, lane, xbp);
                     }
 #pragma unroll
                     for (int q = 0; q < 3; q++)
@@ -3886,8 +3914,8 @@ hipError_t rt_set_attributes() {
     return hipSuccess;
 }
 
-hipError_t rt_launch_pack(const DevModel& m, const float* w, float* wimg, hipStream_t stream) {
-    hipLaunchKernelGGL(rt_pack_kernel, dim3((RT_IMG_FLOATS + 255) / 256), dim3(256), 0, stream, m, w, wimg);
+hipError_t rt_launch_pack(const DevModel& m, const float* w, float* wimg, hipStream_t stream, int n_models) {
+    hipLaunchKernelGGL(rt_pack_kernel, dim3((RT_IMG_FLOATS + 255) / 256, n_models), dim3(256), 0, stream, m, w, wimg, (int)RT_IMG_STRIDE);
     return hipGetLastError();
 }
 
@@ -3943,26 +3971,28 @@ hipError_t rt_launch_forward(const DevModel& m, const float* wimg, const float* 
 
 // the three-wavefronts-per-tile forward solve of the latency points; tapes (optional) in tile16's formats
 hipError_t rt_launch_forward_split(const DevModel& m, const float* wimg, const float* x0, const float* bcs, const float* save_times,
-                                   int n_save, int substeps, float* sol, float* t16_tape, float* t16_ztape, int n_col, bool rich, bool use_helper, bool want_split, hipStream_t stream) {
+                                   int n_save, int substeps, float* sol, float* t16_tape, float* t16_ztape, int n_col, bool rich, bool use_helper, bool want_split, hipStream_t stream,
+                                   const RtEns& ens) {
     const size_t lds = (((size_t)RT_IMG_FLOATS + 3) & ~(size_t)3) * sizeof(float) + 2 * 384 * 16;
     const dim3 grid((n_col + 15) / 16), block(192);
     const size_t ldsh = lds + 384 * 16;
-    const dim3 blockh(256);
+    const dim3 gridh((n_col + 15) / 16, ens.n_models), blockh(256);       // ensembles: grid.y = model (the four-wave kernels only)
     if (m.nst != 4 && !(m.rkc && use_helper)) return hipErrorInvalidValue;      // RKC2 lives in the four-wave kernels only
+    if (ens.n_models != 1 && !use_helper) return hipErrorInvalidValue;
     // layers 1 and 2 on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT; the four-wave kernels, RK4 and RKC2)
     const bool split = want_split && use_helper;
     const size_t ldss = ((size_t)RT_SIMG2_WORDS + ((RT_IMG_FLOATS - RT_W3C + 3) & ~3)) * sizeof(float) + 3 * 384 * 16;
-    if (split) hipLaunchKernelGGL(rt_pack_split_ns_kernel, dim3(41), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_SIMG2_OFF);
+    if (split) hipLaunchKernelGGL(rt_pack_split_ns_kernel, dim3(41, ens.n_models), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_SIMG2_OFF, (int)ens.wimg);
 #define RT_FWDS(A)                                                                                                                              \
     do {                                                                                                                                        \
-        if (split && rich && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, true, true>), grid, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-        else if (split && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, true, true>), grid, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-        else if (split && rich) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, false, true>), grid, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-        else if (split) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, false, true>), grid, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-        else if (use_helper && rich && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, true>), grid, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-        else if (use_helper && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, true>), grid, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-        else if (use_helper && rich) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true>), grid, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-        else if (use_helper) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false>), grid, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
+        if (split && rich && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, true, true>), gridh, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
+        else if (split && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, true, true>), gridh, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
+        else if (split && rich) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, false, true>), gridh, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
+        else if (split) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, false, true>), gridh, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
+        else if (use_helper && rich && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, true>), gridh, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
+        else if (use_helper && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, true>), gridh, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
+        else if (use_helper && rich) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true>), gridh, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
+        else if (use_helper) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false>), gridh, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
         else if (rich) hipLaunchKernelGGL((rt16s_forward_kernel<A, true>), grid, block, lds, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
         else hipLaunchKernelGGL((rt16s_forward_kernel<A, false>), grid, block, lds, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
     } while (0)
@@ -3983,29 +4013,31 @@ bool rt_adjoint_split_has_bf16(const DevModel& m, bool use_helper) { return use_
 
 hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const float* save_times, int n_save, int substeps, const float* sol,
                                    const float* truth, const float* t16_tape, const float* t16_ztape, const LossWeights& lw, float* slab,
-                                   int n_col, float* dwtape, bool rich, bool use_helper, bool want_split, hipStream_t stream) {
+                                   int n_col, float* dwtape, bool rich, bool use_helper, bool want_split, hipStream_t stream,
+                                   const RtEns& ens) {
     // the record formats this kernel reads and writes are tile16's for exactly this shape
     if (!rt_supported(m) || dwtape_row_floats(m) * CT != RT16S_REC || t16_ztape_col_floats(m) * CT != RT16S_ZREC || (m.nst != 4 && !(m.rkc && use_helper)))
         return hipErrorInvalidValue;
     const size_t lds = (((size_t)RT_IMG_FLOATS + 3) & ~(size_t)3) * sizeof(float) + 2 * (3 * 6 * 64) * 16 + 3 * RT16S_STG * sizeof(float);
     const dim3 grid((n_col + 15) / 16), block(192);
     const size_t ldsh = (((size_t)RT_IMG_FLOATS + 3) & ~(size_t)3) * sizeof(float) + (3 * 6 * 64 + 3 * 2 * 64) * 16 + 3 * RT16S_STG * sizeof(float);
-    const dim3 blockh(256);
+    const dim3 gridh((n_col + 15) / 16, ens.n_models), blockh(256);       // ensembles: grid.y = model (the four-wave kernels only)
+    if (ens.n_models != 1 && !use_helper) return hipErrorInvalidValue;
     // COLNDE_MATRIX_BF16X3_EXACT: the W1^T products on the bf16 pipe (four-wave kernels, RK4 and RKC2); LDS: the fp32 image from W2 on, exchange, staging, the h / m planes
     const bool split = want_split && rt_adjoint_split_has_bf16(m, use_helper);
     const size_t ldss = ((((size_t)RT_IMG_FLOATS - RT_W2C) + 3) & ~(size_t)3) * sizeof(float) + (3 * 6 * 64 + 3 * 2 * 64) * 16 + 3 * RT16S_STG * sizeof(float) +
                         (size_t)RT_NSA_HM_WORDS * 4;
-    if (split) hipLaunchKernelGGL(rt_pack_split_nsadj_kernel, dim3(36), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_NSA_OFF);
+    if (split) hipLaunchKernelGGL(rt_pack_split_nsadj_kernel, dim3(36, ens.n_models), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_NSA_OFF, (int)ens.wimg);
 #define RT_ADJS(A)                                                                                                                              \
     do {                                                                                                                                        \
-        if (split && rich && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, true, true>), grid, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-        else if (split && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, true, true>), grid, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-        else if (split && rich) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, false, true>), grid, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-        else if (split) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, false, true>), grid, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-        else if (use_helper && rich && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, true>), grid, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-        else if (use_helper && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, true>), grid, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-        else if (use_helper && rich) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true>), grid, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-        else if (use_helper) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false>), grid, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
+        if (split && rich && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, true, true>), gridh, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
+        else if (split && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, true, true>), gridh, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
+        else if (split && rich) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, false, true>), gridh, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
+        else if (split) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, false, true>), gridh, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
+        else if (use_helper && rich && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, true>), gridh, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
+        else if (use_helper && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, true>), gridh, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
+        else if (use_helper && rich) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true>), gridh, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
+        else if (use_helper) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false>), gridh, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
         else if (rich) hipLaunchKernelGGL((rt16s_adjoint_kernel<A, true>), grid, block, lds, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
         else hipLaunchKernelGGL((rt16s_adjoint_kernel<A, false>), grid, block, lds, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
     } while (0)

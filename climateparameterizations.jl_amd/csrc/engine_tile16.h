@@ -43,8 +43,9 @@ hipError_t launch_rhs(const DevModel& m, const PackInfo& pk, const float* w, con
 hipError_t launch_forward(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* x0,
                           const float* bcs, const float* save_times, int n_save, int substeps, float* sol, float* tape,
                           int n_col, int nthreads, bool wlds, size_t lds_bytes, hipStream_t stream, float* ztape = nullptr);
+// n_models > 1 (ensembles): grid.y = model, sol [K] sol_mstride floats apart, partial [K][n_blocks][8]; truth shared
 hipError_t launch_loss(const DevModel& m, const float* sol, const float* truth, int n_save, int n_col, float* partial,
-                       int n_blocks, hipStream_t stream);
+                       int n_blocks, hipStream_t stream, int n_models = 1, size_t sol_mstride = 0);
 hipError_t launch_adjoint(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* wb,
                           const TileDesc* tiles, const int* bias_zoff, const int* bias_goff, const float* bcs,
                           const float* save_times, int n_save, int substeps, const float* sol, const float* truth,
@@ -57,8 +58,9 @@ static inline int dwtape_ns4(const DevModel& m) { return (m.ns + 3) & ~3; }
 static inline int dwtape_act4(const DevModel& m) { return (m.act_total + 3) & ~3; }
 static inline size_t dwtape_row_floats(const DevModel& m) { return (size_t)dwtape_ns4(m) + (size_t)2 * m.n_nets * dwtape_act4(m); }
 bool dw_gemm_lds_fits(int row_floats, int n_macros);     // the LDS-staged dW kernel applies (else the L2-streaming one)
+// n_models > 1 (ensembles): grid.y = model, its records tape_mstride and its slab rows slab_mstride floats after the previous model's
 hipError_t launch_dw_gemm(const float* dwtape, size_t n_records, int row_floats, const DwMacro* macros, int n_macros, int n_slices,
-                          float* slab_rows, int slab_stride, hipStream_t stream);
+                          float* slab_rows, int slab_stride, hipStream_t stream, int n_models = 1, size_t tape_mstride = 0, size_t slab_mstride = 0);
 // dW GEMM on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT; the plan is built with the tapes whenever the records fit LDS): the blocks are
 // dealt to passes by layer so that a pass's operand features (split ONCE per record into LDS planes) and its accumulators fit one workgroup
 struct DwSeg { int src, len, dst; };                                  // floats of a record row [src, src + len) -> compact features [dst, dst + len)
@@ -67,9 +69,10 @@ struct DwSplitPlan { std::vector<DwPassDesc> passes; DwMacro* d_macros = nullptr
 bool dw_split_build(const std::vector<DwMacro>& mac, const std::vector<int>& matrix_of, int row_floats, DwSplitPlan& plan);
 void dw_split_free(DwSplitPlan& plan);
 hipError_t launch_dw_gemm_split(const float* dwtape, size_t n_records, int row_floats, const DwSplitPlan& plan, int n_slices,
-                                float* slab_rows, int slab_stride, hipStream_t stream);
+                                float* slab_rows, int slab_stride, hipStream_t stream, int n_models = 1, size_t tape_mstride = 0, size_t slab_mstride = 0);
+// n_models > 1 (ensembles): grid.y = model, slab slab_mstride and out out_mstride floats apart per model
 hipError_t launch_reduce(const float* slab, int n_tiles, int n_params, int stride, const LossWeights& lw, float* out,
-                         hipStream_t stream);
+                         hipStream_t stream, int n_models = 1, size_t slab_mstride = 0, int out_mstride = 0);
 hipError_t launch_infer(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* T,
                         const float* top_flux, float inv_dz, float* out, int n_col, int nthreads, size_t lds_bytes,
                         hipStream_t stream);

@@ -1156,7 +1156,9 @@ __device__ __forceinline__ void block_reduce_sums(float* sums, int nq, float* re
 }
 
 __global__ void loss_kernel(DevModel m, const float* __restrict__ sol, const float* __restrict__ truth, int n_save,
-                            int n_col, float* __restrict__ partial /* [gridDim.x][8] */) {
+                            int n_col, float* __restrict__ partial /* [gridDim.x][8] */, size_t sol_mstride) {
+    sol += (size_t)blockIdx.y * sol_mstride;              // ensembles: blockIdx.y = model (its solution and partial rows; truth shared)
+    partial += (size_t)blockIdx.y * gridDim.x * 8;
     __shared__ float red[16 * 8];
     const int tid = threadIdx.x, nth = blockDim.x;
     float sums[6] = {0, 0, 0, 0, 0, 0};
@@ -1536,7 +1538,9 @@ typedef float dwf32x16 __attribute__((ext_vector_type(16)));
 
 __global__ void __launch_bounds__(256)
 dw_gemm_kernel(const float* __restrict__ dwtape, size_t n_records, int R, const DwMacro* __restrict__ macros, int n_macros,
-               int n_groups, int n_slices, float* __restrict__ slab_rows, int stride) {
+               int n_groups, int n_slices, float* __restrict__ slab_rows, int stride, size_t tape_mstride, size_t slab_mstride) {
+    dwtape += (size_t)blockIdx.y * tape_mstride;          // ensembles: blockIdx.y = model (its delta tape and slab rows); grid.y = 1: one model
+    slab_rows += (size_t)blockIdx.y * slab_mstride;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int L = blockIdx.x, xcd = L & 7, k = L >> 3;
     const int group = k % n_groups, slice = (k / n_groups) * 8 + xcd;
@@ -1594,7 +1598,9 @@ dw_gemm_kernel(const float* __restrict__ dwtape, size_t n_records, int R, const 
 template <int MAXM, int NW, int RPB>
 __global__ void __launch_bounds__(64 * NW)
 dw_gemm_lds_kernel(const float* __restrict__ dwtape, size_t n_records, int R, const DwMacro* __restrict__ macros, int n_macros,
-                   int n_slices, float* __restrict__ slab_rows, int stride) {
+                   int n_slices, float* __restrict__ slab_rows, int stride, size_t tape_mstride, size_t slab_mstride) {
+    dwtape += (size_t)blockIdx.y * tape_mstride;          // ensembles: blockIdx.y = model (its delta tape and slab rows); grid.y = 1: one model
+    slab_rows += (size_t)blockIdx.y * slab_mstride;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int slice = blockIdx.x;
     const int rec_floats = CT * R;                       // multiple of 4 (checked by the host)
@@ -1692,7 +1698,9 @@ typedef float dws_f32x2 __attribute__((ext_vector_type(2)));
 template <int MAXM, int NIT>
 __global__ void __launch_bounds__(512)
 dw_gemm_split_kernel(const float* __restrict__ dwtape, size_t n_records, int R, const DwMacro* __restrict__ macros, DwPassDesc ps,
-                     int n_slices, float* __restrict__ slab_rows, int stride) {
+                     int n_slices, float* __restrict__ slab_rows, int stride, size_t tape_mstride, size_t slab_mstride) {
+    dwtape += (size_t)blockIdx.y * tape_mstride;          // ensembles: blockIdx.y = model (its delta tape and slab rows); grid.y = 1: one model
+    slab_rows += (size_t)blockIdx.y * slab_mstride;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int slice = blockIdx.x;
     const size_t per = (n_records + n_slices - 1) / n_slices;
@@ -1950,11 +1958,11 @@ void dw_split_free(DwSplitPlan& plan) {
 }
 
 hipError_t launch_dw_gemm_split(const float* dwtape, size_t n_records, int row_floats, const DwSplitPlan& plan, int n_slices,
-                                float* slab_rows, int slab_stride, hipStream_t stream) {
+                                float* slab_rows, int slab_stride, hipStream_t stream, int n_models, size_t tape_mstride, size_t slab_mstride) {
     if (n_records == 0 || n_slices < 1 || plan.passes.empty()) return hipErrorInvalidValue;
     for (const DwPassDesc& pd : plan.passes) {
         const size_t lds = (size_t)2 * 3 * (pd.Fc + 64) * 2 * 16;
-#define DWS_LAUNCH(M, N) hipLaunchKernelGGL((dw_gemm_split_kernel<M, N>), dim3(n_slices), dim3(512), lds, stream, dwtape, n_records, row_floats, plan.d_macros, pd, n_slices, slab_rows, slab_stride)
+#define DWS_LAUNCH(M, N) hipLaunchKernelGGL((dw_gemm_split_kernel<M, N>), dim3(n_slices, n_models), dim3(512), lds, stream, dwtape, n_records, row_floats, plan.d_macros, pd, n_slices, slab_rows, slab_stride, tape_mstride, slab_mstride)
         if (pd.maxm <= 1) { if (pd.nit <= 1) DWS_LAUNCH(1, 1); else DWS_LAUNCH(1, 2); }
         else { if (pd.nit <= 1) DWS_LAUNCH(2, 1); else DWS_LAUNCH(2, 2); }
 #undef DWS_LAUNCH
@@ -1978,12 +1986,12 @@ static int dw_gemm_rpb(int row_floats) {
 }
 
 hipError_t launch_dw_gemm(const float* dwtape, size_t n_records, int row_floats, const DwMacro* macros, int n_macros, int n_slices,
-                          float* slab_rows, int slab_stride, hipStream_t stream) {
+                          float* slab_rows, int slab_stride, hipStream_t stream, int n_models, size_t tape_mstride, size_t slab_mstride) {
     if (dw_gemm_lds_fits(row_floats, n_macros)) {
         if (n_records == 0 || n_slices < 1) return hipErrorInvalidValue;
         const int maxm = (n_macros + DW_NW - 1) / DW_NW, rpb = dw_gemm_rpb(row_floats);
         const size_t lds = (size_t)2 * rpb * CT * row_floats * sizeof(float);
-#define DW_LAUNCH(M, P) hipLaunchKernelGGL((dw_gemm_lds_kernel<M, DW_NW, P>), dim3(n_slices), dim3(64 * DW_NW), lds, stream, dwtape, n_records, row_floats, macros, n_macros, n_slices, slab_rows, slab_stride)
+#define DW_LAUNCH(M, P) hipLaunchKernelGGL((dw_gemm_lds_kernel<M, DW_NW, P>), dim3(n_slices, n_models), dim3(64 * DW_NW), lds, stream, dwtape, n_records, row_floats, macros, n_macros, n_slices, slab_rows, slab_stride, tape_mstride, slab_mstride)
         if (maxm == 1) { if (rpb == 4) DW_LAUNCH(1, 4); else if (rpb == 2) DW_LAUNCH(1, 2); else DW_LAUNCH(1, 1); }
         else if (maxm == 2) { if (rpb == 4) DW_LAUNCH(2, 4); else if (rpb == 2) DW_LAUNCH(2, 2); else DW_LAUNCH(2, 1); }
         else { if (rpb == 4) DW_LAUNCH(3, 4); else if (rpb == 2) DW_LAUNCH(3, 2); else DW_LAUNCH(3, 1); }
@@ -1993,15 +2001,17 @@ hipError_t launch_dw_gemm(const float* dwtape, size_t n_records, int row_floats,
     if (n_records == 0 || n_macros < 1 || n_slices < 8 || (n_slices & 7)) return hipErrorInvalidValue;
     const int n_groups = (n_macros + 3) / 4;
     const int grid = n_groups * n_slices;          // = 8 * n_groups * (n_slices / 8): every (group, slice) pair once
-    hipLaunchKernelGGL(dw_gemm_kernel, dim3(grid), dim3(256), 0, stream, dwtape, n_records, row_floats, macros, n_macros, n_groups,
-                       n_slices, slab_rows, slab_stride);
+    hipLaunchKernelGGL(dw_gemm_kernel, dim3(grid, n_models), dim3(256), 0, stream, dwtape, n_records, row_floats, macros, n_macros, n_groups,
+                       n_slices, slab_rows, slab_stride, tape_mstride, slab_mstride);
     return hipGetLastError();
 }
 
 // grad[p] = Σ_rows slab[row][p] in a fixed order (deterministic): 64 parameters x 16 row lanes per workgroup, lane ry sums
 // rows ry, ry + 16, ..., then the 16 partial sums are added in order; the 6 raw sums become scaled mean terms
 __global__ void __launch_bounds__(1024) reduce_kernel(const float* __restrict__ slab, int n_tiles, int n_params, int stride, LossWeights lw,
-                                                      float* __restrict__ out /* [n_params + 8] */) {
+                                                      float* __restrict__ out /* [n_params + 8] */, size_t slab_mstride, int out_mstride) {
+    slab += (size_t)blockIdx.y * slab_mstride;            // ensembles: blockIdx.y = model; grid.y = 1: one model
+    out += (size_t)blockIdx.y * out_mstride;
     __shared__ float part[16][65];
     const int px = threadIdx.x & 63, ry = threadIdx.x >> 6;
     const int p = blockIdx.x * 64 + px;
@@ -2019,7 +2029,8 @@ __global__ void __launch_bounds__(1024) reduce_kernel(const float* __restrict__ 
     }
 }
 
-__global__ void finish_loss_kernel(float* __restrict__ out8) {
+__global__ void finish_loss_kernel(float* __restrict__ out8, int out_mstride) {
+    out8 += (size_t)blockIdx.x * out_mstride;             // ensembles: one workgroup per model
     if (threadIdx.x == 0) {
         float t = 0.0f;
         for (int q = 0; q < 6; q++) t += out8[q];
@@ -2156,8 +2167,8 @@ hipError_t launch_forward(const DevModel& m, const PackInfo& pk, const float* w,
 }
 
 hipError_t launch_loss(const DevModel& m, const float* sol, const float* truth, int n_save, int n_col, float* partial,
-                       int n_blocks, hipStream_t stream) {
-    hipLaunchKernelGGL(loss_kernel, dim3(n_blocks), dim3(256), 0, stream, m, sol, truth, n_save, n_col, partial);
+                       int n_blocks, hipStream_t stream, int n_models, size_t sol_mstride) {
+    hipLaunchKernelGGL(loss_kernel, dim3(n_blocks, n_models), dim3(256), 0, stream, m, sol, truth, n_save, n_col, partial, sol_mstride);
     return hipGetLastError();
 }
 
@@ -2214,9 +2225,10 @@ hipError_t launch_adjoint(const DevModel& m, const PackInfo& pk, const float* w,
 }
 
 hipError_t launch_reduce(const float* slab, int n_tiles, int n_params, int stride, const LossWeights& lw, float* out,
-                         hipStream_t stream) {
-    hipLaunchKernelGGL(reduce_kernel, dim3((n_params + 6 + 63) / 64), dim3(1024), 0, stream, slab, n_tiles, n_params, stride, lw, out);
-    hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(64), 0, stream, out + n_params);
+                         hipStream_t stream, int n_models, size_t slab_mstride, int out_mstride) {
+    hipLaunchKernelGGL(reduce_kernel, dim3((n_params + 6 + 63) / 64, n_models), dim3(1024), 0, stream, slab, n_tiles, n_params, stride, lw, out,
+                       slab_mstride, out_mstride);
+    hipLaunchKernelGGL(finish_loss_kernel, dim3(n_models), dim3(64), 0, stream, out + n_params, out_mstride);
     return hipGetLastError();
 }
 

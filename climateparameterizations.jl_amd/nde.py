@@ -469,3 +469,110 @@ class ColumnNDE:
         _lib.check(self._L.colnde_zscore_stats_dev(self._h, x.data_ptr(), x.numel(), ms.data_ptr()))
         _lib.check(self._L.colnde_scale_dev(self._h, x.data_ptr(), x.numel(), ms.data_ptr(), out.data_ptr()))
         return out, ms
+
+
+PHYSICS_KEYS = ("nu0", "nu_minus", "dRi", "Ric", "Pr")     # colnde_create_ensemble's physics row (mpp_parameters order)
+
+
+def check_ensemble_arrays(n_models: int, n_params: int, weights=None, physics=None, etas=None):
+    """Shape checks of an ensemble's per-model arrays (no GPU needed): weights [K, n_params], physics [K, 5] (PHYSICS_KEYS), etas [K]."""
+    K = int(n_models)
+    if K < 1:
+        raise ValueError("n_models must be >= 1, got %d" % K)
+    for name, a, shape in (("weights", weights, (K, n_params)), ("physics", physics, (K, 5)), ("etas", etas, (K,))):
+        if a is not None and tuple(a.shape) != shape:
+            raise ValueError("%s: expected shape %s for %d models, got %s" % (name, shape, K, tuple(a.shape)))
+
+
+class ColumnNDEEnsemble(ColumnNDE):
+    """K models of ONE architecture on the same columns (`colnde_create_ensemble`): own weights, own Pacanowski-Philander constants, own ADAM rate —
+    the sweep of wind_mixing/train_NDE_args.jl (one model per process there) with every kernel launched once for all K models.
+    physics: [K, 5] = (nu0, nu_minus, dRi, Ric, Pr) per model, or None (cfg's constants for all).  The problem (`set_problem`) and the loss
+    scalings are shared.  NumPy inputs go through the host entry points, torch device tensors through the `_dev` twins on torch's current stream.
+    The single-model calls of `ColumnNDE` (rhs, flux, error_estimate, ...) are refused by the library on this handle."""
+
+    def __init__(self, cfg: NDEConfig, n_columns: int, n_models: int, physics=None, device: int = 0, matrix_arithmetic="bf16x3_exact"):
+        cfg.validate()
+        check_ensemble_arrays(n_models, cfg.n_params, physics=None if physics is None else np.asarray(physics))
+        self.cfg = cfg
+        self.n_columns = int(n_columns)
+        self.n_models = int(n_models)
+        self.device = int(device)
+        self._h = ctypes.c_void_p()
+        L = _lib.lib()
+        c, keep = to_c_config(cfg, n_columns, device, 0, matrix_arithmetic)
+        ph = None if physics is None else _f32(physics, (self.n_models, 5))
+        _lib.check(L.colnde_create_ensemble(ctypes.byref(c), self.n_models, _ptr(ph), ctypes.byref(self._h)))
+        self._L = L
+        self.n_params = L.colnde_n_params(self._h)
+        assert self.n_params == cfg.n_params and L.colnde_n_models(self._h) == self.n_models
+        self.n_columns_total = self.n_columns
+        self.engine = L.colnde_engine(self._h)
+
+    def set_physics(self, physics):
+        ph = np.asarray(physics)
+        check_ensemble_arrays(self.n_models, self.n_params, physics=ph)
+        _lib.check(self._L.colnde_ensemble_set_physics(self._h, _ptr(_f32(ph))))
+
+    def _weights_dev(self, weights):
+        """torch device weights [K, P] as given; NumPy weights copied to the device (the ensemble calls are device-pointer calls)."""
+        import torch
+        if _is_torch(weights):
+            self._chk_dev(weights, (self.n_models, self.n_params))
+            return weights, True
+        w = _f32(weights, (self.n_models, self.n_params))
+        return torch.from_numpy(w).to(torch.device("cuda", self.device)), False
+
+    def forward(self, weights, out=None):
+        """sol [K, n_columns, n_save, n_state]: a torch tensor for torch weights, NumPy for NumPy weights."""
+        import torch
+        c = self.cfg
+        w, is_t = self._weights_dev(weights)
+        shape = (self.n_models, self.n_columns, c.n_save, c.n_state)
+        sol = out if out is not None else torch.empty(shape, dtype=torch.float32, device=w.device)
+        self._chk_dev(sol, shape)
+        self.use_torch_stream()
+        _lib.check(self._L.colnde_ensemble_forward_dev(self._h, w.data_ptr(), sol.data_ptr()))
+        return sol if is_t else sol.cpu().numpy()
+
+    def loss(self, weights, scalings: Sequence[float]):
+        """[K, 8] = [scaled terms(6); total; 0] per model."""
+        import torch
+        sc = (ctypes.c_float * 6)(*[float(s) for s in scalings])
+        w, is_t = self._weights_dev(weights)
+        out = torch.empty((self.n_models, 8), dtype=torch.float32, device=w.device)
+        self.use_torch_stream()
+        _lib.check(self._L.colnde_ensemble_loss_dev(self._h, w.data_ptr(), sc, out.data_ptr()))
+        return out if is_t else out.cpu().numpy()
+
+    def loss_grad(self, weights, scalings: Sequence[float], out=None):
+        """[K, n_params + 8]: per model the row `colnde_loss_grad_dev` writes — [grad; scaled terms(6); total; 0]."""
+        sc = (ctypes.c_float * 6)(*[float(s) for s in scalings])
+        shape = (self.n_models, self.n_params + 8)
+        if _is_torch(weights):
+            import torch
+            self._chk_dev(weights, (self.n_models, self.n_params))
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=weights.device)
+            self._chk_dev(out, shape)
+            self.use_torch_stream()
+            _lib.check(self._L.colnde_ensemble_loss_grad_dev(self._h, weights.data_ptr(), sc, out.data_ptr()))
+            return out
+        w = _f32(weights, (self.n_models, self.n_params))
+        res = np.empty(shape, dtype=np.float32)
+        _lib.check(self._L.colnde_ensemble_loss_grad(self._h, _ptr(w), sc, _ptr(res)))
+        return res
+
+    def adam_step(self, weights, result, m, v, etas, beta=(0.9, 0.999), eps: float = 1e-8, beta_t=None):
+        """Flux ADAM for every model (in place): weights, m, v [K, P]; the gradient read from `result` [K, P + 8] (loss_grad's buffer); etas [K]."""
+        import torch
+        K, P = self.n_models, self.n_params
+        for t in (weights, m, v):
+            self._chk_dev(t, (K, P))
+        self._chk_dev(result, (K, P + 8))
+        self._chk_dev(etas, (K,))
+        bt = beta if beta_t is None else beta_t
+        self.use_torch_stream()
+        _lib.check(self._L.colnde_ensemble_adam_step_dev(self._h, weights.data_ptr(), result.data_ptr(), m.data_ptr(), v.data_ptr(), etas.data_ptr(),
+                                                         float(beta[0]), float(beta[1]), float(eps), float(bt[0]), float(bt[1])))
+        return weights

@@ -68,6 +68,7 @@ class WindMixingNDE:
         self.BCs = np.ascontiguousarray(BCs, dtype=np.float32)
         self.engine = ColumnNDE(cfg, self.n_simulations, device=device, matrix_arithmetic=matrix_arithmetic)
         self.engine.set_problem(uvT0, self.BCs, uvT_trains)
+        self.uvT0, self.uvT_trains = uvT0, uvT_trains          # (train_NDE_ensemble hands the same problem to an ensemble handle)
         self._rhs_engine = None
         # determine_loss_scalings (NDE_training.jl:256-288)
         if training_fractions is None:
@@ -264,6 +265,63 @@ def train_NDE_device(problem: WindMixingNDE, weights, optimizers: Sequence[ADAM]
     H = torch.stack(hist).cpu().numpy() if hist else np.zeros((0, 7), np.float32)
     history = [dict(total=float(r[6]), **{k: float(r[i]) for i, k in enumerate(LOSS_KEYS)}) for r in H]
     return TrainResult(theta.cpu().numpy(), history)
+
+
+def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: int = 1, maxiters: int = 500, beta=(0.9, 0.999),
+                       eps: float = 1e-8) -> List[TrainResult]:
+    """`train_NDE_device`'s loop (NDE_training.jl:340-372: ADAM, per-solve state reset, save_best) for K models at once — the sweep of
+    wind_mixing/train_NDE_args.jl, which trains one model per process with its own ADAM rate (ARGS[2], :143) and Pacanowski-Philander constants
+    (ARGS[3], :175).  weights [K, n_params], physics [K, 5] = (nu0, nu_minus, dRi, Ric, Pr) per model or None (the problem's constants), etas [K].
+    One `colnde_ensemble_loss_grad_dev` and one `colnde_ensemble_adam_step_dev` per iteration for all models, on the problem's simulations and
+    loss scalings; `save_best` per model (torch.where over rows).  Returns one TrainResult per model."""
+    import torch
+    from .nde import ColumnNDEEnsemble, check_ensemble_arrays
+    W = np.ascontiguousarray(weights, dtype=np.float32)
+    ph = None if physics is None else np.ascontiguousarray(physics, dtype=np.float32)
+    et = np.ascontiguousarray(etas, dtype=np.float32)
+    K = W.shape[0] if W.ndim == 2 else 0
+    check_ensemble_arrays(K, problem.cfg.n_params, W, ph, et)
+    eng = problem.engine
+    ens = ColumnNDEEnsemble(problem.cfg, problem.n_simulations, K, physics=ph, device=eng.device, matrix_arithmetic=eng.matrix_arithmetic)
+    try:
+        dev = torch.device("cuda", eng.device)
+        t = lambda a: a if a is None or _is_torch_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32))
+        x0, bcs, truth = (t(a).to(dev).contiguous() for a in (problem.uvT0, problem.BCs, problem.uvT_trains))
+        ens.set_problem(x0, bcs, truth)
+        n = ens.n_params
+        theta = torch.as_tensor(W).to(dev).contiguous()
+        eta_d = torch.as_tensor(et).to(dev).contiguous()
+        out = torch.empty((K, n + 8), dtype=torch.float32, device=dev)
+        sc = problem.loss_scalings.copy()
+        if not problem.cfg.train_gradient:
+            sc[3:] = 0.0
+        hist = []
+        for _ in range(epochs):
+            m = torch.zeros((K, n), dtype=torch.float32, device=dev)
+            v = torch.zeros((K, n), dtype=torch.float32, device=dev)
+            bt = [beta[0], beta[1]]                                  # a fresh ADAM state per solve (ADAM.reset)
+            best = torch.full((K,), float("inf"), dtype=torch.float32, device=dev)
+            best_theta = theta.clone()
+            for _ in range(maxiters):
+                ens.loss_grad(theta, sc, out=out)
+                total = out[:, n + 6]
+                hist.append(out[:, n:n + 7].clone())
+                ens.adam_step(theta, out, m, v, eta_d, beta, eps, beta_t=tuple(bt))
+                bt[0] *= beta[0]
+                bt[1] *= beta[1]
+                better = total < best
+                best = torch.where(better, total, best)
+                best_theta = torch.where(better[:, None], theta, best_theta)      # min_θ = copy(θ) AFTER update, per model
+            theta = best_theta.clone()
+        H = torch.stack(hist).cpu().numpy() if hist else np.zeros((0, K, 7), np.float32)
+        th = theta.cpu().numpy()
+    finally:
+        ens.close()
+    return [TrainResult(th[k], [dict(total=float(r[k, 6]), **{q: float(r[k, i]) for i, q in enumerate(LOSS_KEYS)}) for r in H]) for k in range(K)]
+
+
+def _is_torch_tensor(x):
+    return type(x).__module__.startswith("torch")
 
 
 def train_NN(engine: ColumnNDE, NN_type: str, weights, profiles, BCs, fluxes, optimizers: Sequence[ADAM], train_epochs: Sequence[int],

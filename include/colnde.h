@@ -336,6 +336,41 @@ int colnde_plan(const colnde_handle* h, int info[8]);
  * that one of them shaped the handle.  buf may be NULL; returns the number of bytes the full line needs (including the terminating 0), or -1. */
 int colnde_describe(const colnde_handle* h, char* buf, int capacity);
 
+/* ---- ensembles: K models of ONE architecture trained side by side on one GPU ----------------------------------------------------------------------
+ * The reference's production driver is a sweep: wind_mixing/train_NDE_args.jl takes the activation (ARGS[1]), the ADAM rate (ARGS[2], :143) and the
+ * Pacanowski-Philander constants (ARGS[3], the train_parameters Dict at :175) on its command line and trains ONE model per process, at the small shape of
+ * wind_mixing/train_NDE.jl:138-141 (8 to 18 simulations).  An ensemble handle holds K such models of one architecture (cfg) on the same columns, each
+ * with its own weights, its own five constants and its own ADAM rate; every kernel of a training iteration runs once for all K models (model index in
+ * the launch grid).  Shared by all models: the problem (colnde_set_problem[_dev]: x0, bcs, truth), the loss scalings and the sub-step count.
+ * Accepted: the configurations on which engine AUTO runs the four-wave net-split kernels — Nz = 32, three 96-50-20-31 nets, training RHS, no smoothing,
+ * RK4 or RKC2, engine AUTO, substeps >= 1, at most 8,192 columns per model; everything else (free convection / fc32, wide networks, inplace_variant,
+ * a forced engine, substeps = 0) is refused with the reason.  The shared sub-step count must meet colnde_min_substeps for EVERY model's constants
+ * (COLNDE_ALLOW_UNSTABLE_DT=1 overrides); RKC2 with rkc_stages = 0 runs the largest automatic stage count over the models.  The tapes of all models are
+ * allocated at creation: a handle whose tapes do not fit is refused with the bytes it needs.  Handle-level calls that accept an ensemble: set_problem[_dev],
+ * set_stream, set_matrix_arithmetic, set_profiling / kernel_time / reset_kernel_times, plan, describe (adds models=K and the bytes per model), n_params,
+ * destroy.  Every call that takes ONE weight vector refuses an ensemble handle. */
+
+/* Create: physics [n_models][5] = nu0, nu_minus, dRi, Ric, Pr per model (mpp_parameters order; the train_parameters of train_NDE_args.jl:175), host
+ * memory; NULL = cfg's constants for every model.  A physics array needs modified_pacanowski_philander = 1. */
+int colnde_create_ensemble(const colnde_config* cfg, int n_models, const float* physics, colnde_handle** out);
+/* number of models: 1 for colnde_create handles, K for an ensemble */
+int colnde_n_models(const colnde_handle* h);
+/* new constants for every model (host [n_models][5]), checked against the stability bound like colnde_create_ensemble */
+int colnde_ensemble_set_physics(colnde_handle* h, const float* physics);
+/* solve(...) of every model (NDE_training.jl:291,403): d_weights [K][n_params], d_sol [K][n_col][n_save][n_state]; device memory, handle's stream */
+int colnde_ensemble_forward_dev(colnde_handle* h, const float* d_weights, float* d_sol);
+/* loss_NDE (NDE_training.jl:290-323) of every model: d_out8 [K][8] = [scaled terms(6); total; 0] per model */
+int colnde_ensemble_loss_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out8);
+/* loss_gradient_NDE of every model (NDE_training.jl:327-333): d_out [K][n_params + 8], each row exactly what colnde_loss_grad_dev writes for one model.
+ * A model whose solve leaves the stable regime gets a non-finite row; the other rows are unaffected. */
+int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
+/* the same with host arrays: weights [K][n_params], out [K][n_params + 8]; synchronises the stream */
+int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float* out);
+/* Flux.Optimise.ADAM (as colnde_adam_step_dev; NDE_training.jl:340-372) for every model: d_weights, d_m, d_v [K][n_params], the gradient read as the first
+ * n_params floats of each [n_params + 8] row of d_result (the buffer of colnde_ensemble_loss_grad_dev), d_eta [K] per-model rates (train_NDE_args.jl:143) */
+int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_result, float* d_m, float* d_v, const float* d_eta,
+                                  float beta1, float beta2, float eps, float beta1_t, float beta2_t);
+
 /* ---- measurement: HIP-event timing of the handle's kernels on its stream.
  * which: 0 = forward solve kernel, 1 = adjoint kernel, 2 = gradient reduce, 3 = rhs, 4 = inference,
  * 5 = streaming dW1 GEMM (regtile engine only), 6 = convective adjustment, 7 = ADAM step, 8 = implicit diffusion.

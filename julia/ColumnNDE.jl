@@ -358,4 +358,56 @@ function pretrain_flux!(h::Handle, flux_type, dθ::Ptr{Float32}, dm::Ptr{Float32
     loss[], βᵗ
 end
 
+# ---- ensembles: K models of one architecture side by side — the sweep of wind_mixing/train_NDE_args.jl (activation ARGS[1], ADAM rate ARGS[2]
+# at :143, Pacanowski-Philander constants ARGS[3] in the train_parameters Dict at :175), which trains one model per process
+
+"K models of `cfg`'s architecture on the same columns; physics: K x 5 matrix of (ν₀, ν₋, ΔRi, Riᶜ, Pr) per model (row k = model k), or `nothing`"
+function EnsembleHandle(cfg::Config, save_times::Vector{Float32}, n_models::Integer, physics=nothing)
+    cfg.n_save = length(save_times)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    ph = physics === nothing ? C_NULL : Matrix{Float32}(permutedims(physics))       # C order [K][5]
+    GC.@preserve save_times ph begin
+        cfg.save_times = pointer(save_times)
+        check(ccall((:colnde_create_ensemble, libcolnde), Cint, (Ref{Config}, Cint, Ptr{Float32}, Ref{Ptr{Cvoid}}),
+                    cfg, n_models, ph === C_NULL ? Ptr{Float32}(C_NULL) : pointer(ph), out))
+    end
+    h = Handle(out[], ccall((:colnde_n_params, libcolnde), Cint, (Ptr{Cvoid},), out[]),
+               3cfg.Nz, cfg.n_save, cfg.n_columns, 3)
+    finalizer(x -> ccall((:colnde_destroy, libcolnde), Cvoid, (Ptr{Cvoid},), x.ptr), h)
+end
+
+n_models(h::Handle) = Int(ccall((:colnde_n_models, libcolnde), Cint, (Ptr{Cvoid},), h.ptr))
+
+"new (ν₀, ν₋, ΔRi, Riᶜ, Pr) for every model: K x 5"
+function set_physics!(h::Handle, physics::AbstractMatrix)
+    ph = Matrix{Float32}(permutedims(physics))
+    check(ccall((:colnde_ensemble_set_physics, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}), h.ptr, ph))
+    h
+end
+
+"∇loss of every model: weights n_params x K (column k = model k); returns the (n_params + 8) x K result [∇θ; scaled terms(6); total; 0] per column"
+function ensemble_∇loss(h::Handle, weights::AbstractMatrix{Float32}, loss_scalings::NamedTuple)
+    sc = Float32[loss_scalings[k] for k in KEYS]
+    out = zeros(Float32, h.n_params + 8, size(weights, 2))
+    check(ccall((:colnde_ensemble_loss_grad, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                h.ptr, Matrix{Float32}(weights), sc, out))
+    out
+end
+
+"device-pointer twins (handle's stream, not synchronised): solve, loss ([8] per model), loss + gradient ([n_params + 8] per model)"
+ensemble_forward_dev!(h::Handle, dθ::Ptr{Float32}, dsol::Ptr{Float32}) =
+    check(ccall((:colnde_ensemble_forward_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, dsol))
+ensemble_loss_dev!(h::Handle, dθ::Ptr{Float32}, sc::Vector{Float32}, dout::Ptr{Float32}) =
+    check(ccall((:colnde_ensemble_loss_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, sc, dout))
+ensemble_loss_grad_dev!(h::Handle, dθ::Ptr{Float32}, sc::Vector{Float32}, dout::Ptr{Float32}) =
+    check(ccall((:colnde_ensemble_loss_grad_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, sc, dout))
+
+"ADAM for every model on device pointers: θ, m, v n_params x K, the gradient read from the loss-gradient result, η one rate per model (device)"
+function ensemble_adam_step!(h::Handle, dθ::Ptr{Float32}, dresult::Ptr{Float32}, dm::Ptr{Float32}, dv::Ptr{Float32}, dη::Ptr{Float32}, β, ϵ, βᵗ)
+    check(ccall((:colnde_ensemble_adam_step_dev, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Cfloat, Cfloat, Cfloat),
+        h.ptr, dθ, dresult, dm, dv, dη, β[1], β[2], ϵ, βᵗ[1], βᵗ[2]))
+    βᵗ .* β
+end
+
 end # module
