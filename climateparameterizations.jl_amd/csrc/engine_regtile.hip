@@ -18,6 +18,7 @@
 // Reference arithmetic: wind_mixing/src/NDE_training.jl:46-165 (NDE, predict_flux, predict_NDE).
 #include <cstdlib>
 #include "engine_regtile.h"
+#include "kernel_select.h"
 #include "split_bf16.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -3737,6 +3738,28 @@ bool rt_supported(const DevModel& m) {
 
 size_t rt_forward_lds_bytes() { return (size_t)RT_IMG_FLOATS * sizeof(float); }
 size_t rt_adjoint_lds_bytes() { return ((size_t)((RT_IMG_FLOATS + 3) & ~3) + RT_WAVES * (3072 + RT_TB)) * sizeof(float); }
+// ... of the other kernels, in the order their heads carve rt_smem up
+static constexpr size_t rt_pad4(size_t floats) { return (floats + 3) & ~(size_t)3; }
+static constexpr size_t RT_IMG_BYTES = rt_pad4(RT_IMG_FLOATS) * sizeof(float);       // the fp32 weight image, padded to 16 bytes
+static constexpr size_t RT16S_FWD_XCH = 3 * 2 * 64 * 16;                             // one exchange buffer of the net-split forward: [3 variables][2 tiles][64 lanes] x 16 bytes
+static constexpr size_t RT16S_ADJ_XCH = 3 * 6 * 64 * 16;                             // ... of the net-split adjoint (the nets' parts of the state adjoint): [3 nets][6 tiles][64 lanes] x 16 bytes
+static constexpr size_t RT16S_ADJ_STG = 3 * RT16S_STG * sizeof(float);               // the three net waves' record staging areas
+// rt16_forward_kernel; SPLIT: the bf16 operand planes and the fp32 biases
+static size_t rt16_forward_lds_bytes(bool split) { return split ? ((size_t)RT_SIMG_WORDS + (RT_IMG_FLOATS - RT_B1C)) * sizeof(float) : rt_forward_lds_bytes(); }
+// rt16s_forward_kernel: image, two exchange buffers
+static size_t rt16s_forward_lds_bytes() { return RT_IMG_BYTES + 2 * RT16S_FWD_XCH; }
+// rt16sh_forward_kernel: a third exchange buffer; SPLIT: the bf16 planes of layers 1 and 2 and the fp32 image from W3 on in the image's place
+static size_t rt16sh_forward_lds_bytes(bool split) {
+    return (split ? ((size_t)RT_SIMG2_WORDS + rt_pad4(RT_IMG_FLOATS - RT_W3C)) * sizeof(float) : RT_IMG_BYTES) + 3 * RT16S_FWD_XCH;
+}
+// rt16s_adjoint_kernel: image, two exchange buffers, staging
+static size_t rt16s_adjoint_lds_bytes() { return RT_IMG_BYTES + 2 * RT16S_ADJ_XCH + RT16S_ADJ_STG; }
+// rt16sh_adjoint_kernel: image, one exchange buffer, the helper's dO, staging; SPLIT: the fp32 image from W2 on, and the h / m planes of W1^T behind the staging
+static size_t rt16sh_adjoint_lds_bytes(bool split) {
+    const size_t rest = RT16S_ADJ_XCH + 3 * 2 * 64 * 16 + RT16S_ADJ_STG;
+    return split ? rt_pad4(RT_IMG_FLOATS - RT_W2C) * sizeof(float) + rest + (size_t)RT_NSA_HM_WORDS * 4 : RT_IMG_BYTES + rest;
+}
+static size_t rt_dw1_lds_bytes() { return RT_WAVES * RT_DW1_LDS * sizeof(float); }
 size_t rt_tape_floats(int n_col, int n_steps) { return (size_t)((n_col + RT_COLS - 1) / RT_COLS) * n_steps * 4 * 3072; }
 size_t rt_tape2_floats(int n_col, int n_steps) { return (size_t)((n_col + RT_COLS - 1) / RT_COLS) * n_steps * 4 * RT_TAPE2; }
 size_t rt_split_rich_record_floats() { return RT16S_RREC; }
@@ -3748,170 +3771,83 @@ int rt_dw1_waves(int n_col, int n_steps) {
     return (int)((w + RT_WAVES - 1) / RT_WAVES) * RT_WAVES;
 }
 
+// ---- kernel selection (kernel_select.h).  ONE selector per kernel family names its instantiations: the launchers call it with
+// the run's flags, rt_set_attributes() with every value of them, so whatever can be launched has had its dynamic-LDS limit raised.
+// nullptr: there is no such kernel.  To add an instantiation, add it to its family's selector (and, for a new flag, to the loop below).
+using RtForwardFn = decltype(&rt_forward_kernel<COLNDE_ACT_RELU>);
+using Rt16ForwardFn = decltype(&rt16_forward_kernel<COLNDE_ACT_RELU, false>);
+using Rt16sForwardFn = decltype(&rt16s_forward_kernel<COLNDE_ACT_RELU, false>);
+using Rt16shForwardFn = decltype(&rt16sh_forward_kernel<COLNDE_ACT_RELU, false>);
+using Rt16sAdjointFn = decltype(&rt16s_adjoint_kernel<COLNDE_ACT_RELU, false>);
+using Rt16shAdjointFn = decltype(&rt16sh_adjoint_kernel<COLNDE_ACT_RELU, false>);
+using RtAdjointFn = decltype(&rt_adjoint_kernel<COLNDE_ACT_RELU, false>);
+
+static RtForwardFn rt_forward_pick(int act) {
+    RtForwardFn k = nullptr;
+    with_act(act, [&](auto A) { k = rt_forward_kernel<decltype(A)::value>; });
+    return k;
+}
+static Rt16ForwardFn rt16_forward_pick(int act, bool split) {
+    Rt16ForwardFn k = nullptr;
+    with_act(act, [&](auto A) { with_bools([&](auto S) { k = rt16_forward_kernel<decltype(A)::value, decltype(S)::value>; }, split); });
+    return k;
+}
+static Rt16sForwardFn rt16s_forward_pick(int act, bool rich) {
+    Rt16sForwardFn k = nullptr;
+    with_act(act, [&](auto A) { with_bools([&](auto R) { k = rt16s_forward_kernel<decltype(A)::value, decltype(R)::value>; }, rich); });
+    return k;
+}
+static Rt16shForwardFn rt16sh_forward_pick(int act, bool rich, bool rkc, bool split) {
+    Rt16shForwardFn k = nullptr;
+    with_act(act, [&](auto A) {
+        with_bools([&](auto R, auto K, auto S) { k = rt16sh_forward_kernel<decltype(A)::value, decltype(R)::value, decltype(K)::value, decltype(S)::value>; }, rich, rkc, split);
+    });
+    return k;
+}
+static Rt16sAdjointFn rt16s_adjoint_pick(int act, bool rich) {
+    Rt16sAdjointFn k = nullptr;
+    with_act(act, [&](auto A) { with_bools([&](auto R) { k = rt16s_adjoint_kernel<decltype(A)::value, decltype(R)::value>; }, rich); });
+    return k;
+}
+static Rt16shAdjointFn rt16sh_adjoint_pick(int act, bool rich, bool rkc, bool split) {
+    Rt16shAdjointFn k = nullptr;
+    with_act(act, [&](auto A) {
+        with_bools([&](auto R, auto K, auto S) { k = rt16sh_adjoint_kernel<decltype(A)::value, decltype(R)::value, decltype(K)::value, decltype(S)::value>; }, rich, rkc, split);
+    });
+    return k;
+}
+static RtAdjointFn rt_adjoint_pick(int act, bool ztape, bool split) {
+    RtAdjointFn k = nullptr;
+    with_act(act, [&](auto A) {
+        with_bools([&](auto Z, auto S) {
+            if constexpr (decltype(Z)::value || !decltype(S)::value) k = rt_adjoint_kernel<decltype(A)::value, decltype(Z)::value, decltype(S)::value>;      // the split kernel reads the Z1 tape
+        }, ztape, split);
+    });
+    return k;
+}
+static auto rt_dw1_pick(bool split) { return split ? rt_dw1_split_kernel : rt_dw1_kernel; }
+
 hipError_t rt_set_attributes() {
-    hipError_t e;
-    const int v = 160 * 1024;
-#define RT_SETATTR(K) if ((e = hipFuncSetAttribute((const void*)(K), hipFuncAttributeMaxDynamicSharedMemorySize, v)) != hipSuccess) return e
-    RT_SETATTR(rt_forward_kernel<COLNDE_ACT_IDENTITY>);
-    RT_SETATTR(rt_forward_kernel<COLNDE_ACT_RELU>);
-    RT_SETATTR(rt_forward_kernel<COLNDE_ACT_MISH>);
-    RT_SETATTR(rt_forward_kernel<COLNDE_ACT_SWISH>);
-    RT_SETATTR(rt_forward_kernel<COLNDE_ACT_TANH>);
-    RT_SETATTR(rt_forward_kernel<COLNDE_ACT_LEAKYRELU>);
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_IDENTITY, false>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_IDENTITY, true>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_RELU, false>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_RELU, true>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_MISH, false>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_MISH, true>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_SWISH, false>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_SWISH, true>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_TANH, false>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_TANH, true>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_LEAKYRELU, false>));
-    RT_SETATTR((rt16_forward_kernel<COLNDE_ACT_LEAKYRELU, true>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_IDENTITY, false>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_IDENTITY, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_IDENTITY, false>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_IDENTITY, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_IDENTITY, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_IDENTITY, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_IDENTITY, false, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_IDENTITY, true, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_IDENTITY, false, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_IDENTITY, true, true, true>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_RELU, false>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_RELU, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_RELU, false>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_RELU, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_RELU, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_RELU, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_RELU, false, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_RELU, true, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_RELU, false, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_RELU, true, true, true>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_MISH, false>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_MISH, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_MISH, false>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_MISH, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_MISH, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_MISH, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_MISH, false, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_MISH, true, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_MISH, false, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_MISH, true, true, true>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_SWISH, false>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_SWISH, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_SWISH, false>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_SWISH, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_SWISH, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_SWISH, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_SWISH, false, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_SWISH, true, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_SWISH, false, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_SWISH, true, true, true>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_TANH, false>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_TANH, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_TANH, false>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_TANH, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_TANH, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_TANH, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_TANH, false, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_TANH, true, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_TANH, false, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_TANH, true, true, true>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_LEAKYRELU, false>));
-    RT_SETATTR((rt16s_forward_kernel<COLNDE_ACT_LEAKYRELU, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_LEAKYRELU, false>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_LEAKYRELU, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_LEAKYRELU, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_LEAKYRELU, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_LEAKYRELU, false, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_LEAKYRELU, true, false, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_LEAKYRELU, false, true, true>));
-    RT_SETATTR((rt16sh_forward_kernel<COLNDE_ACT_LEAKYRELU, true, true, true>));
-    RT_SETATTR(rt_dw1_kernel);
-    RT_SETATTR(rt_dw1_split_kernel);
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_IDENTITY, false>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_IDENTITY, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_IDENTITY, false>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_IDENTITY, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_IDENTITY, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_IDENTITY, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_IDENTITY, false, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_IDENTITY, true, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_IDENTITY, false, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_IDENTITY, true, true, true>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_RELU, false>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_RELU, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_RELU, false>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_RELU, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_RELU, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_RELU, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_RELU, false, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_RELU, true, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_RELU, false, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_RELU, true, true, true>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_MISH, false>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_MISH, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_MISH, false>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_MISH, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_MISH, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_MISH, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_MISH, false, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_MISH, true, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_MISH, false, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_MISH, true, true, true>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_SWISH, false>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_SWISH, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_SWISH, false>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_SWISH, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_SWISH, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_SWISH, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_SWISH, false, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_SWISH, true, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_SWISH, false, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_SWISH, true, true, true>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_TANH, false>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_TANH, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_TANH, false>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_TANH, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_TANH, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_TANH, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_TANH, false, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_TANH, true, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_TANH, false, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_TANH, true, true, true>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_LEAKYRELU, false>));
-    RT_SETATTR((rt16s_adjoint_kernel<COLNDE_ACT_LEAKYRELU, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_LEAKYRELU, false>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_LEAKYRELU, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_LEAKYRELU, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_LEAKYRELU, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_LEAKYRELU, false, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_LEAKYRELU, true, false, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_LEAKYRELU, false, true, true>));
-    RT_SETATTR((rt16sh_adjoint_kernel<COLNDE_ACT_LEAKYRELU, true, true, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_IDENTITY, false>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_RELU, false>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_MISH, false>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_SWISH, false>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_TANH, false>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_LEAKYRELU, false>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_IDENTITY, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_IDENTITY, true, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_RELU, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_RELU, true, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_MISH, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_MISH, true, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_SWISH, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_SWISH, true, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_TANH, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_TANH, true, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_LEAKYRELU, true>));
-    RT_SETATTR((rt_adjoint_kernel<COLNDE_ACT_LEAKYRELU, true, true>));
-#undef RT_SETATTR
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    const size_t v = 160 * 1024;
+    auto set = [&](auto* k) { if (k && e == hipSuccess) e = set_max_lds(k, v); };
+    for_each_act([&](auto A) {
+        set(rt_forward_pick(A));
+        for (int a = 0; a < 2; a++) {
+            set(rt16_forward_pick(A, a));
+            set(rt16s_forward_pick(A, a));
+            set(rt16s_adjoint_pick(A, a));
+            for (int b = 0; b < 2; b++) {
+                set(rt_adjoint_pick(A, a, b));
+                for (int c = 0; c < 2; c++) {
+                    set(rt16sh_forward_pick(A, a, b, c));
+                    set(rt16sh_adjoint_pick(A, a, b, c));
+                }
+            }
+        }
+    });
+    for (int split = 0; split < 2; split++) set(rt_dw1_pick(split));
+    return e;
 }
 
 hipError_t rt_launch_pack(const DevModel& m, const float* w, float* wimg, hipStream_t stream, int n_models) {
@@ -3928,22 +3864,13 @@ bool rt_forward_is32() {
 hipError_t rt_launch_forward(const DevModel& m, const float* wimg, const float* x0, const float* bcs,
                              const float* save_times, int n_save, int substeps, float* sol, float* tape, float* tapez,
                              int n_col, bool fwd32, bool split, hipStream_t stream) {
-    const size_t lds = rt_forward_lds_bytes();
     // COLNDE_RT_FWD=32 selects the one-wave-per-SIMD 32-column kernel (A/B aid); default: 16-column tiles, two waves per SIMD
     if (fwd32) {
         const int n_wtiles = (n_col + RT_COLS - 1) / RT_COLS;
         const dim3 grid((n_wtiles + RT_WAVES - 1) / RT_WAVES), block(64 * RT_WAVES);
-#define RT_FWD(A) hipLaunchKernelGGL(rt_forward_kernel<A>, grid, block, lds, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, tape, n_col)
-        switch (m.acts[0]) {
-            case COLNDE_ACT_IDENTITY: RT_FWD(COLNDE_ACT_IDENTITY); break;
-            case COLNDE_ACT_RELU: RT_FWD(COLNDE_ACT_RELU); break;
-            case COLNDE_ACT_MISH: RT_FWD(COLNDE_ACT_MISH); break;
-            case COLNDE_ACT_SWISH: RT_FWD(COLNDE_ACT_SWISH); break;
-            case COLNDE_ACT_TANH: RT_FWD(COLNDE_ACT_TANH); break;
-            case COLNDE_ACT_LEAKYRELU: RT_FWD(COLNDE_ACT_LEAKYRELU); break;
-            default: return hipErrorInvalidValue;
-        }
-#undef RT_FWD
+        const auto k = rt_forward_pick(m.acts[0]);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, grid, block, rt_forward_lds_bytes(), stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, tape, n_col);
     } else {
         const int n_wt16 = 2 * ((n_col + RT_COLS - 1) / RT_COLS);
         // small problems spread over the CUs first (one wavefront per workgroup up to 256 tiles), then fill the SIMDs
@@ -3951,20 +3878,10 @@ hipError_t rt_launch_forward(const DevModel& m, const float* wimg, const float* 
         wpw = wpw < 1 ? 1 : (wpw > RT16_WAVES ? RT16_WAVES : wpw);
         const dim3 grid((n_wt16 + wpw - 1) / wpw), block(64 * wpw);
         // split: the nets on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT)
-        const size_t lds_split = ((size_t)RT_SIMG_WORDS + (RT_IMG_FLOATS - RT_B1C)) * sizeof(float);
         if (split) hipLaunchKernelGGL(rt_pack_split_kernel, dim3(48), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_SIMG_OFF);
-#define RT_FWD(A) do { if (split) hipLaunchKernelGGL((rt16_forward_kernel<A, true>), grid, block, lds_split, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, tape, tapez, n_col); \
-                       else hipLaunchKernelGGL((rt16_forward_kernel<A, false>), grid, block, lds, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, tape, tapez, n_col); } while (0)
-        switch (m.acts[0]) {
-            case COLNDE_ACT_IDENTITY: RT_FWD(COLNDE_ACT_IDENTITY); break;
-            case COLNDE_ACT_RELU: RT_FWD(COLNDE_ACT_RELU); break;
-            case COLNDE_ACT_MISH: RT_FWD(COLNDE_ACT_MISH); break;
-            case COLNDE_ACT_SWISH: RT_FWD(COLNDE_ACT_SWISH); break;
-            case COLNDE_ACT_TANH: RT_FWD(COLNDE_ACT_TANH); break;
-            case COLNDE_ACT_LEAKYRELU: RT_FWD(COLNDE_ACT_LEAKYRELU); break;
-            default: return hipErrorInvalidValue;
-        }
-#undef RT_FWD
+        const auto k = rt16_forward_pick(m.acts[0], split);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, grid, block, rt16_forward_lds_bytes(split), stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, tape, tapez, n_col);
     }
     return hipGetLastError();
 }
@@ -3973,39 +3890,22 @@ hipError_t rt_launch_forward(const DevModel& m, const float* wimg, const float* 
 hipError_t rt_launch_forward_split(const DevModel& m, const float* wimg, const float* x0, const float* bcs, const float* save_times,
                                    int n_save, int substeps, float* sol, float* t16_tape, float* t16_ztape, int n_col, bool rich, bool use_helper, bool want_split, hipStream_t stream,
                                    const RtEns& ens) {
-    const size_t lds = (((size_t)RT_IMG_FLOATS + 3) & ~(size_t)3) * sizeof(float) + 2 * 384 * 16;
     const dim3 grid((n_col + 15) / 16), block(192);
-    const size_t ldsh = lds + 384 * 16;
     const dim3 gridh((n_col + 15) / 16, ens.n_models), blockh(256);       // ensembles: grid.y = model (the four-wave kernels only)
     if (m.nst != 4 && !(m.rkc && use_helper)) return hipErrorInvalidValue;      // RKC2 lives in the four-wave kernels only
     if (ens.n_models != 1 && !use_helper) return hipErrorInvalidValue;
     // layers 1 and 2 on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT; the four-wave kernels, RK4 and RKC2)
     const bool split = want_split && use_helper;
-    const size_t ldss = ((size_t)RT_SIMG2_WORDS + ((RT_IMG_FLOATS - RT_W3C + 3) & ~3)) * sizeof(float) + 3 * 384 * 16;
     if (split) hipLaunchKernelGGL(rt_pack_split_ns_kernel, dim3(41, ens.n_models), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_SIMG2_OFF, (int)ens.wimg);
-#define RT_FWDS(A)                                                                                                                              \
-    do {                                                                                                                                        \
-        if (split && rich && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, true, true>), gridh, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
-        else if (split && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, true, true>), gridh, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
-        else if (split && rich) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, false, true>), gridh, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
-        else if (split) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, false, true>), gridh, blockh, ldss, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
-        else if (use_helper && rich && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true, true>), gridh, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
-        else if (use_helper && m.rkc) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false, true>), gridh, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
-        else if (use_helper && rich) hipLaunchKernelGGL((rt16sh_forward_kernel<A, true>), gridh, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
-        else if (use_helper) hipLaunchKernelGGL((rt16sh_forward_kernel<A, false>), gridh, blockh, ldsh, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens); \
-        else if (rich) hipLaunchKernelGGL((rt16s_forward_kernel<A, true>), grid, block, lds, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-        else hipLaunchKernelGGL((rt16s_forward_kernel<A, false>), grid, block, lds, stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col); \
-    } while (0)
-    switch (m.acts[0]) {
-        case COLNDE_ACT_IDENTITY: RT_FWDS(COLNDE_ACT_IDENTITY); break;
-        case COLNDE_ACT_RELU: RT_FWDS(COLNDE_ACT_RELU); break;
-        case COLNDE_ACT_MISH: RT_FWDS(COLNDE_ACT_MISH); break;
-        case COLNDE_ACT_SWISH: RT_FWDS(COLNDE_ACT_SWISH); break;
-        case COLNDE_ACT_TANH: RT_FWDS(COLNDE_ACT_TANH); break;
-        case COLNDE_ACT_LEAKYRELU: RT_FWDS(COLNDE_ACT_LEAKYRELU); break;
-        default: return hipErrorInvalidValue;
+    if (use_helper) {
+        const auto k = rt16sh_forward_pick(m.acts[0], rich, m.rkc != nullptr, split);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, gridh, blockh, rt16sh_forward_lds_bytes(split), stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens);
+    } else {
+        const auto k = rt16s_forward_pick(m.acts[0], rich);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, grid, block, rt16s_forward_lds_bytes(), stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col);
     }
-#undef RT_FWDS
     return hipGetLastError();
 }
 
@@ -4018,39 +3918,21 @@ hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const f
     // the record formats this kernel reads and writes are tile16's for exactly this shape
     if (!rt_supported(m) || dwtape_row_floats(m) * CT != RT16S_REC || t16_ztape_col_floats(m) * CT != RT16S_ZREC || (m.nst != 4 && !(m.rkc && use_helper)))
         return hipErrorInvalidValue;
-    const size_t lds = (((size_t)RT_IMG_FLOATS + 3) & ~(size_t)3) * sizeof(float) + 2 * (3 * 6 * 64) * 16 + 3 * RT16S_STG * sizeof(float);
     const dim3 grid((n_col + 15) / 16), block(192);
-    const size_t ldsh = (((size_t)RT_IMG_FLOATS + 3) & ~(size_t)3) * sizeof(float) + (3 * 6 * 64 + 3 * 2 * 64) * 16 + 3 * RT16S_STG * sizeof(float);
     const dim3 gridh((n_col + 15) / 16, ens.n_models), blockh(256);       // ensembles: grid.y = model (the four-wave kernels only)
     if (ens.n_models != 1 && !use_helper) return hipErrorInvalidValue;
-    // COLNDE_MATRIX_BF16X3_EXACT: the W1^T products on the bf16 pipe (four-wave kernels, RK4 and RKC2); LDS: the fp32 image from W2 on, exchange, staging, the h / m planes
+    // COLNDE_MATRIX_BF16X3_EXACT: the W1^T products on the bf16 pipe (four-wave kernels, RK4 and RKC2)
     const bool split = want_split && rt_adjoint_split_has_bf16(m, use_helper);
-    const size_t ldss = ((((size_t)RT_IMG_FLOATS - RT_W2C) + 3) & ~(size_t)3) * sizeof(float) + (3 * 6 * 64 + 3 * 2 * 64) * 16 + 3 * RT16S_STG * sizeof(float) +
-                        (size_t)RT_NSA_HM_WORDS * 4;
     if (split) hipLaunchKernelGGL(rt_pack_split_nsadj_kernel, dim3(36, ens.n_models), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_NSA_OFF, (int)ens.wimg);
-#define RT_ADJS(A)                                                                                                                              \
-    do {                                                                                                                                        \
-        if (split && rich && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, true, true>), gridh, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
-        else if (split && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, true, true>), gridh, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
-        else if (split && rich) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, false, true>), gridh, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
-        else if (split) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, false, true>), gridh, blockh, ldss, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
-        else if (use_helper && rich && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true, true>), gridh, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
-        else if (use_helper && m.rkc) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false, true>), gridh, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
-        else if (use_helper && rich) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, true>), gridh, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
-        else if (use_helper) hipLaunchKernelGGL((rt16sh_adjoint_kernel<A, false>), gridh, blockh, ldsh, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens); \
-        else if (rich) hipLaunchKernelGGL((rt16s_adjoint_kernel<A, true>), grid, block, lds, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-        else hipLaunchKernelGGL((rt16s_adjoint_kernel<A, false>), grid, block, lds, stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape); \
-    } while (0)
-    switch (m.acts[0]) {
-        case COLNDE_ACT_IDENTITY: RT_ADJS(COLNDE_ACT_IDENTITY); break;
-        case COLNDE_ACT_RELU: RT_ADJS(COLNDE_ACT_RELU); break;
-        case COLNDE_ACT_MISH: RT_ADJS(COLNDE_ACT_MISH); break;
-        case COLNDE_ACT_SWISH: RT_ADJS(COLNDE_ACT_SWISH); break;
-        case COLNDE_ACT_TANH: RT_ADJS(COLNDE_ACT_TANH); break;
-        case COLNDE_ACT_LEAKYRELU: RT_ADJS(COLNDE_ACT_LEAKYRELU); break;
-        default: return hipErrorInvalidValue;
+    if (use_helper) {
+        const auto k = rt16sh_adjoint_pick(m.acts[0], rich, m.rkc != nullptr, split);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, gridh, blockh, rt16sh_adjoint_lds_bytes(split), stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens);
+    } else {
+        const auto k = rt16s_adjoint_pick(m.acts[0], rich);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, grid, block, rt16s_adjoint_lds_bytes(), stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape);
     }
-#undef RT_ADJS
     return hipGetLastError();
 }
 
@@ -4059,29 +3941,12 @@ hipError_t rt_launch_adjoint(const DevModel& m, const float* wimg, const float* 
                              const float* tapez, const LossWeights& lw, float* slab, int n_col, bool want_split, hipStream_t stream) {
     const int n_wtiles = rt_n_wtiles(n_col);
     const dim3 grid((n_wtiles + RT_WAVES - 1) / RT_WAVES), block(64 * RT_WAVES);
-    const size_t lds = rt_adjoint_lds_bytes();
     // with the Z1 tape: the W1^T products on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT)
     const bool split = want_split && tapez;
     if (split) hipLaunchKernelGGL(rt_pack_split_adj_kernel, dim3(30), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_ASIMG_OFF);
-#define RT_ADJ(A)                                                                                                             \
-    do {                                                                                                                      \
-        if (split) hipLaunchKernelGGL((rt_adjoint_kernel<A, true, true>), grid, block, lds, stream, m, wimg, bcs, save_times, n_save, \
-                                      substeps, sol, truth, tape, tape2, tapez, lw, slab, n_col);                      \
-        else if (tapez) hipLaunchKernelGGL((rt_adjoint_kernel<A, true>), grid, block, lds, stream, m, wimg, bcs, save_times, n_save, \
-                                      substeps, sol, truth, tape, tape2, tapez, lw, slab, n_col);                      \
-        else hipLaunchKernelGGL((rt_adjoint_kernel<A, false>), grid, block, lds, stream, m, wimg, bcs, save_times, n_save,    \
-                                substeps, sol, truth, tape, tape2, tapez, lw, slab, n_col);                            \
-    } while (0)
-    switch (m.acts[0]) {
-        case COLNDE_ACT_IDENTITY: RT_ADJ(COLNDE_ACT_IDENTITY); break;
-        case COLNDE_ACT_RELU: RT_ADJ(COLNDE_ACT_RELU); break;
-        case COLNDE_ACT_MISH: RT_ADJ(COLNDE_ACT_MISH); break;
-        case COLNDE_ACT_SWISH: RT_ADJ(COLNDE_ACT_SWISH); break;
-        case COLNDE_ACT_TANH: RT_ADJ(COLNDE_ACT_TANH); break;
-        case COLNDE_ACT_LEAKYRELU: RT_ADJ(COLNDE_ACT_LEAKYRELU); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef RT_ADJ
+    const auto k = rt_adjoint_pick(m.acts[0], tapez != nullptr, split);
+    if (!k) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, grid, block, rt_adjoint_lds_bytes(), stream, m, wimg, bcs, save_times, n_save, substeps, sol, truth, tape, tape2, tapez, lw, slab, n_col);
     return hipGetLastError();
 }
 
@@ -4089,12 +3954,8 @@ hipError_t rt_launch_dw1(const DevModel& m, const float* tape, const float* tape
                          bool split, hipStream_t stream) {
     const long items = (long)rt_n_wtiles(n_col) * n_steps * 4;
     const int waves = rt_dw1_waves(n_col, n_steps);
-    if (split)      // dW1 on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT)
-        hipLaunchKernelGGL(rt_dw1_split_kernel, dim3(waves / RT_WAVES), dim3(64 * RT_WAVES), RT_WAVES * RT_DW1_LDS * sizeof(float), stream, m,
-                           tape, tape2, items, slab_rows);
-    else
-        hipLaunchKernelGGL(rt_dw1_kernel, dim3(waves / RT_WAVES), dim3(64 * RT_WAVES), RT_WAVES * RT_DW1_LDS * sizeof(float), stream, m, tape,
-                           tape2, items, slab_rows);
+    // split: dW1 on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT)
+    hipLaunchKernelGGL(rt_dw1_pick(split), dim3(waves / RT_WAVES), dim3(64 * RT_WAVES), rt_dw1_lds_bytes(), stream, m, tape, tape2, items, slab_rows);
     return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 #include "colnde_dev.h"
 #include <cstdlib>
 #include "engine_tile16.h"
+#include "kernel_select.h"
 #include "split_bf16.h"
 #include <algorithm>
 
@@ -1957,15 +1958,22 @@ void dw_split_free(DwSplitPlan& plan) {
     plan.passes.clear();
 }
 
+// the instantiations of the two LDS-staged dW kernels: launched from, and their dynamic-LDS limit raised through, these tables
+using DwSplitFn = decltype(&dw_gemm_split_kernel<1, 1>);
+static const DwSplitFn kDwSplitKernels[2][2] = {{dw_gemm_split_kernel<1, 1>, dw_gemm_split_kernel<1, 2>},      // [maxm > 1][nit > 1]
+                                                {dw_gemm_split_kernel<2, 1>, dw_gemm_split_kernel<2, 2>}};
+using DwLdsFn = decltype(&dw_gemm_lds_kernel<1, DW_NW, 1>);
+static const DwLdsFn kDwLdsKernels[3][3] = {{dw_gemm_lds_kernel<1, DW_NW, 1>, dw_gemm_lds_kernel<1, DW_NW, 2>, dw_gemm_lds_kernel<1, DW_NW, 4>},   // [maxm - 1][log2 rpb]
+                                            {dw_gemm_lds_kernel<2, DW_NW, 1>, dw_gemm_lds_kernel<2, DW_NW, 2>, dw_gemm_lds_kernel<2, DW_NW, 4>},
+                                            {dw_gemm_lds_kernel<3, DW_NW, 1>, dw_gemm_lds_kernel<3, DW_NW, 2>, dw_gemm_lds_kernel<3, DW_NW, 4>}};
+
 hipError_t launch_dw_gemm_split(const float* dwtape, size_t n_records, int row_floats, const DwSplitPlan& plan, int n_slices,
                                 float* slab_rows, int slab_stride, hipStream_t stream, int n_models, size_t tape_mstride, size_t slab_mstride) {
     if (n_records == 0 || n_slices < 1 || plan.passes.empty()) return hipErrorInvalidValue;
     for (const DwPassDesc& pd : plan.passes) {
         const size_t lds = (size_t)2 * 3 * (pd.Fc + 64) * 2 * 16;
-#define DWS_LAUNCH(M, N) hipLaunchKernelGGL((dw_gemm_split_kernel<M, N>), dim3(n_slices, n_models), dim3(512), lds, stream, dwtape, n_records, row_floats, plan.d_macros, pd, n_slices, slab_rows, slab_stride, tape_mstride, slab_mstride)
-        if (pd.maxm <= 1) { if (pd.nit <= 1) DWS_LAUNCH(1, 1); else DWS_LAUNCH(1, 2); }
-        else { if (pd.nit <= 1) DWS_LAUNCH(2, 1); else DWS_LAUNCH(2, 2); }
-#undef DWS_LAUNCH
+        const auto k = kDwSplitKernels[pd.maxm > 1][pd.nit > 1];
+        hipLaunchKernelGGL(k, dim3(n_slices, n_models), dim3(512), lds, stream, dwtape, n_records, row_floats, plan.d_macros, pd, n_slices, slab_rows, slab_stride, tape_mstride, slab_mstride);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -1991,11 +1999,8 @@ hipError_t launch_dw_gemm(const float* dwtape, size_t n_records, int row_floats,
         if (n_records == 0 || n_slices < 1) return hipErrorInvalidValue;
         const int maxm = (n_macros + DW_NW - 1) / DW_NW, rpb = dw_gemm_rpb(row_floats);
         const size_t lds = (size_t)2 * rpb * CT * row_floats * sizeof(float);
-#define DW_LAUNCH(M, P) hipLaunchKernelGGL((dw_gemm_lds_kernel<M, DW_NW, P>), dim3(n_slices, n_models), dim3(64 * DW_NW), lds, stream, dwtape, n_records, row_floats, macros, n_macros, n_slices, slab_rows, slab_stride, tape_mstride, slab_mstride)
-        if (maxm == 1) { if (rpb == 4) DW_LAUNCH(1, 4); else if (rpb == 2) DW_LAUNCH(1, 2); else DW_LAUNCH(1, 1); }
-        else if (maxm == 2) { if (rpb == 4) DW_LAUNCH(2, 4); else if (rpb == 2) DW_LAUNCH(2, 2); else DW_LAUNCH(2, 1); }
-        else { if (rpb == 4) DW_LAUNCH(3, 4); else if (rpb == 2) DW_LAUNCH(3, 2); else DW_LAUNCH(3, 1); }
-#undef DW_LAUNCH
+        const auto k = kDwLdsKernels[maxm == 1 ? 0 : maxm == 2 ? 1 : 2][rpb == 4 ? 2 : rpb == 2 ? 1 : 0];
+        hipLaunchKernelGGL(k, dim3(n_slices, n_models), dim3(64 * DW_NW), lds, stream, dwtape, n_records, row_floats, macros, n_macros, n_slices, slab_rows, slab_stride, tape_mstride, slab_mstride);
         return hipGetLastError();
     }
     if (n_records == 0 || n_macros < 1 || n_slices < 8 || (n_slices & 7)) return hipErrorInvalidValue;
@@ -2079,22 +2084,41 @@ __global__ void __launch_bounds__(256) infer_kernel(DevModel m, PackInfo pk, con
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers (declared in engine_tile16.h)
 // ------------------------------------------------------------------------------------------------
-#define LAUNCH_ADJ_K(MT, NT, MR, WL, TD, ...)                                                                                   \
-    do {                                                                                                                        \
-        if (m.rkc)                                                                                                              \
-            hipLaunchKernelGGL((adjoint_kernel<MT, NT, MR, WL, TD, true>), dim3(n_tiles), dim3(NT), lds_bytes, stream, m, pk, w, wf, \
-                               wb, tiles, bias_zoff, bias_goff, bcs, save_times, n_save, substeps, sol, truth, tape, lw, slab,  \
-                               n_col, __VA_ARGS__);                                                                             \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((adjoint_kernel<MT, NT, MR, WL, TD, false>), dim3(n_tiles), dim3(NT), lds_bytes, stream, m, pk, w, wf, \
-                               wb, tiles, bias_zoff, bias_goff, bcs, save_times, n_save, substeps, sol, truth, tape, lw, slab,  \
-                               n_col, __VA_ARGS__);                                                                             \
-    } while (0)
-#define LAUNCH_ADJ(MT, NT, MR, WL) LAUNCH_ADJ_K(MT, NT, MR, WL, false, (float*)nullptr, (const float*)nullptr)
+// Kernel selection (kernel_select.h): per kernel family ONE table or selector names the instantiations; the launcher
+// takes its kernel from it and set_kernel_attributes() walks it, so whatever can be launched has had its dynamic-LDS limit raised.
+// To add an instantiation, add it there.
+//
+// adjoint_kernel: a geometry (threads, dW tiles per wave, state items per thread, weights in LDS) and its kernels, [0] RK4, [1] RKC2
+using AdjointFn = decltype(&adjoint_kernel<16, 512, 3, true>);
+struct AdjointInst { AdjointGeom g; AdjointFn k[2]; };
+template <int MT, int NT, int MR, bool WL, bool TD = false, bool AG = false>
+static constexpr AdjointInst adj_inst() {
+    return {{NT, MT, MR, WL}, {adjoint_kernel<MT, NT, MR, WL, TD, false, AG>, adjoint_kernel<MT, NT, MR, WL, TD, true, AG>}};
+}
+// in-kernel dW: the host picks the first that fits (pick_adjoint_geom)
+static const AdjointInst kGeoms[] = {adj_inst<16, 512, 3, true>(), adj_inst<32, 256, 6, true>(), adj_inst<32, 256, 6, false>(),
+                                     adj_inst<32, 256, 12, false>(), adj_inst<32, 512, 6, false>(), adj_inst<48, 512, 3, false>()};
+// taped dW (launch_adjoint chooses); the last: rows in global memory (DevModel::ag)
+enum { TAPED_1024_WLDS, TAPED_1024, TAPED_512_R3, TAPED_512_R6, TAPED_AG };
+static const AdjointInst kTapedGeoms[] = {adj_inst<1, 1024, 2, true, true>(), adj_inst<1, 1024, 2, false, true>(), adj_inst<1, 512, 3, false, true>(),
+                                          adj_inst<1, 512, 6, false, true>(), adj_inst<1, 1024, 2, false, true, true>()};
+static_assert(sizeof(kTapedGeoms) / sizeof(kTapedGeoms[0]) == TAPED_AG + 1, "one entry per TAPED_* index");
 
-// (threads, dW tiles per wave, state items per thread, weights in LDS) instantiations; the host picks the first that fits
-static const AdjointGeom kGeoms[] = {{512, 16, 3, 1}, {256, 32, 6, 1}, {256, 32, 6, 0}, {256, 32, 12, 0},
-                                     {512, 32, 6, 0}, {512, 48, 3, 0}};
+// forward_kernel<WLDS, NTH, RKC, AG>; nullptr: no such kernel (AG, rows in global memory: weights streamed from L2, 256 or 1,024 threads)
+using ForwardFn = decltype(&forward_kernel<false, 256>);
+static ForwardFn forward_pick(bool wlds, int nthreads, bool rkc, bool ag) {
+    ForwardFn k = nullptr;
+    with_bools([&](auto WL, auto RK, auto AG) {
+        constexpr bool wl = decltype(WL)::value, rk = decltype(RK)::value, g = decltype(AG)::value;
+        if constexpr (!(wl && g)) {
+            if (nthreads == 256) k = forward_kernel<wl, 256, rk, g>;
+            if (nthreads == 1024) k = forward_kernel<wl, 1024, rk, g>;
+            if constexpr (!g) if (nthreads == 512) k = forward_kernel<wl, 512, rk, g>;
+        }
+    }, wlds, rkc, ag);
+    return k;
+}
+static auto rhs_pick(bool ag) { return ag ? rhs_kernel<true> : rhs_kernel<false>; }
 
 size_t lds_floats_adjoint_geom(const DevModel& m, const AdjointGeom& g) {
     return MODEL_FLOATS + lds_floats_adjoint(m) + (g.wlds ? (size_t)((m.n_params + 3) & ~3) + 128 : 0);
@@ -2103,7 +2127,8 @@ size_t lds_floats_adjoint_geom(const DevModel& m, const AdjointGeom& g) {
 bool pick_adjoint_geom(const DevModel& m, AdjointGeom* geo, int force) {
     const size_t cap = 160 * 1024;
     int idx = 0;
-    for (const AdjointGeom& g : kGeoms) {
+    for (const AdjointInst& inst : kGeoms) {
+        const AdjointGeom& g = inst.g;
         const int nwaves = g.nthreads / 64;
         const bool fits = m.n_tiles <= g.maxt * nwaves && CT * m.ns <= g.maxr * g.nthreads && m.n_bias <= MAXB * g.nthreads &&
                           lds_floats_adjoint_geom(m, g) * sizeof(float) <= cap;
@@ -2130,8 +2155,7 @@ hipError_t launch_pack_planes(const DevModel& m, const float* w, unsigned* sf, u
 
 hipError_t launch_rhs(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* x,
                       const float* bcs, float t, float* dx, int n_col, int nthreads, size_t lds_bytes, hipStream_t stream, float* flux) {
-    if (m.ag) hipLaunchKernelGGL((rhs_kernel<true>), dim3((n_col + CT - 1) / CT), dim3(nthreads), lds_bytes, stream, m, pk, w, wf, x, bcs, t, dx, flux, n_col);
-    else hipLaunchKernelGGL((rhs_kernel<false>), dim3((n_col + CT - 1) / CT), dim3(nthreads), lds_bytes, stream, m, pk, w, wf, x, bcs, t, dx, flux, n_col);
+    hipLaunchKernelGGL(rhs_pick(m.ag != nullptr), dim3((n_col + CT - 1) / CT), dim3(nthreads), lds_bytes, stream, m, pk, w, wf, x, bcs, t, dx, flux, n_col);
     return hipGetLastError();
 }
 
@@ -2139,30 +2163,11 @@ hipError_t launch_forward(const DevModel& m, const PackInfo& pk, const float* w,
                           const float* bcs, const float* save_times, int n_save, int substeps, float* sol, float* tape,
                           int n_col, int nthreads, bool wlds, size_t lds_bytes, hipStream_t stream, float* ztape) {
     const dim3 grid((n_col + CT - 1) / CT);
-#define LAUNCH_FWD(WL, NT)                                                                                                  \
-    do {                                                                                                                    \
-        if (m.rkc)                                                                                                          \
-            hipLaunchKernelGGL((forward_kernel<WL, NT, true>), grid, dim3(NT), lds_bytes, stream, m, pk, w, wf, x0, bcs,    \
-                               save_times, n_save, substeps, sol, tape, n_col, ztape);                                      \
-        else                                                                                                                \
-            hipLaunchKernelGGL((forward_kernel<WL, NT, false>), grid, dim3(NT), lds_bytes, stream, m, pk, w, wf, x0, bcs,   \
-                               save_times, n_save, substeps, sol, tape, n_col, ztape);                                      \
-    } while (0)
-    if (m.ag) {        // rows in global memory (wide networks): weights streamed from L2; 1,024 threads (four waves per SIMD hide the row loads) or 256
-        if (wlds || (nthreads != 256 && nthreads != 1024)) return hipErrorInvalidValue;
-#define LAUNCH_FWD_AG(NT, RK) hipLaunchKernelGGL((forward_kernel<false, NT, RK, true>), grid, dim3(NT), lds_bytes, stream, m, pk, w, wf, x0, bcs, save_times, n_save, substeps, sol, tape, n_col, ztape)
-        if (nthreads == 1024) { if (m.rkc) LAUNCH_FWD_AG(1024, true); else LAUNCH_FWD_AG(1024, false); }
-        else { if (m.rkc) LAUNCH_FWD_AG(256, true); else LAUNCH_FWD_AG(256, false); }
-#undef LAUNCH_FWD_AG
-        return hipGetLastError();
-    }
-    if (wlds && nthreads == 512) LAUNCH_FWD(true, 512);
-    else if (wlds && nthreads == 256) LAUNCH_FWD(true, 256);
-    else if (!wlds && nthreads == 512) LAUNCH_FWD(false, 512);
-    else if (!wlds && nthreads == 256) LAUNCH_FWD(false, 256);
-    else if (wlds && nthreads == 1024) LAUNCH_FWD(true, 1024);
-    else if (!wlds && nthreads == 1024) LAUNCH_FWD(false, 1024);
-    else return hipErrorInvalidValue;
+    // rows in global memory (wide networks): weights streamed from L2; 1,024 threads (four waves per SIMD hide the row loads) or 256
+    if (m.ag && (wlds || (nthreads != 256 && nthreads != 1024))) return hipErrorInvalidValue;
+    const auto k = forward_pick(wlds, nthreads, m.rkc != nullptr, m.ag != nullptr);
+    if (!k) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, grid, dim3(nthreads), lds_bytes, stream, m, pk, w, wf, x0, bcs, save_times, n_save, substeps, sol, tape, n_col, ztape);
     return hipGetLastError();
 }
 
@@ -2178,16 +2183,15 @@ hipError_t launch_adjoint(const DevModel& m, const PackInfo& pk, const float* w,
                           const float* tape, const LossWeights& lw, float* slab, int n_col, const AdjointGeom& geo,
                           size_t lds_bytes, hipStream_t stream, float* dwtape, const float* ztape) {
     const int n_tiles = (n_col + CT - 1) / CT;
+    auto launch = [&](const AdjointInst& a, size_t lds, float* dwt, const float* zt) {
+        hipLaunchKernelGGL(a.k[m.rkc != nullptr], dim3(n_tiles), dim3(a.g.nthreads), lds, stream, m, pk, w, wf, wb, tiles, bias_zoff, bias_goff, bcs, save_times,
+                           n_save, substeps, sol, truth, tape, lw, slab, n_col, dwt, zt);
+        return hipGetLastError();
+    };
     if (dwtape && m.ag) {
         // rows in global memory (wide networks): the Z tape is required (no A array), 1,024 threads (n_bias <= MAXB * 1,024, CT * ns <= 2 * 1,024: checked by the host)
         if (!ztape || CT * m.ns > 2 * 1024 || m.n_bias > MAXB * 1024) return hipErrorInvalidValue;
-        if (m.rkc)
-            hipLaunchKernelGGL((adjoint_kernel<1, 1024, 2, false, true, true, true>), dim3(n_tiles), dim3(1024), lds_bytes, stream, m, pk, w, wf, wb, tiles, bias_zoff,
-                               bias_goff, bcs, save_times, n_save, substeps, sol, truth, tape, lw, slab, n_col, dwtape, ztape);
-        else
-            hipLaunchKernelGGL((adjoint_kernel<1, 1024, 2, false, true, false, true>), dim3(n_tiles), dim3(1024), lds_bytes, stream, m, pk, w, wf, wb, tiles, bias_zoff,
-                               bias_goff, bcs, save_times, n_save, substeps, sol, truth, tape, lw, slab, n_col, dwtape, ztape);
-        return hipGetLastError();
+        return launch(kTapedGeoms[TAPED_AG], lds_bytes, dwtape, ztape);
     }
     if (dwtape) {
         // Two 512-thread workgroups per CU (128 registers each) when two fit in the LDS: one's GEMMs then cover the other's tape
@@ -2200,28 +2204,15 @@ hipError_t launch_adjoint(const DevModel& m, const PackInfo& pk, const float* w,
         const size_t wl_bytes = ((size_t)((m.n_params + 3) & ~3) + 128) * sizeof(float);
         const char* ew = getenv("COLNDE_T16_TAPE_WLDS");
         const bool wlds_ok = nth_env == 1024 && CT * m.ns <= 2 * 1024 && lds_bytes + wl_bytes <= 160 * 1024;
-        if (wlds_ok && (ew ? atoi(ew) != 0 : n_tiles <= 256)) {
-            const size_t lds_save = lds_bytes;
-            lds_bytes += wl_bytes;
-            LAUNCH_ADJ_K(1, 1024, 2, true, true, dwtape, ztape);
-            lds_bytes = lds_save;
-        } else if (nth_env == 1024 && CT * m.ns <= 2 * 1024)
-            LAUNCH_ADJ_K(1, 1024, 2, false, true, dwtape, ztape);
-        else if (CT * m.ns <= 3 * 512)
-            LAUNCH_ADJ_K(1, 512, 3, false, true, dwtape, ztape);
-        else if (CT * m.ns <= 6 * 512)
-            LAUNCH_ADJ_K(1, 512, 6, false, true, dwtape, ztape);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
+        if (wlds_ok && (ew ? atoi(ew) != 0 : n_tiles <= 256)) return launch(kTapedGeoms[TAPED_1024_WLDS], lds_bytes + wl_bytes, dwtape, ztape);
+        if (nth_env == 1024 && CT * m.ns <= 2 * 1024) return launch(kTapedGeoms[TAPED_1024], lds_bytes, dwtape, ztape);
+        if (CT * m.ns <= 3 * 512) return launch(kTapedGeoms[TAPED_512_R3], lds_bytes, dwtape, ztape);
+        if (CT * m.ns <= 6 * 512) return launch(kTapedGeoms[TAPED_512_R6], lds_bytes, dwtape, ztape);
+        return hipErrorInvalidValue;
     }
-    if (geo.nthreads == 512 && geo.maxt == 16 && geo.maxr == 3 && geo.wlds) LAUNCH_ADJ(16, 512, 3, true);
-    else if (geo.nthreads == 256 && geo.maxt == 32 && geo.maxr == 6 && geo.wlds) LAUNCH_ADJ(32, 256, 6, true);
-    else if (geo.nthreads == 256 && geo.maxt == 32 && geo.maxr == 6) LAUNCH_ADJ(32, 256, 6, false);
-    else if (geo.nthreads == 256 && geo.maxt == 32 && geo.maxr == 12) LAUNCH_ADJ(32, 256, 12, false);
-    else if (geo.nthreads == 512 && geo.maxt == 32 && geo.maxr == 6) LAUNCH_ADJ(32, 512, 6, false);
-    else if (geo.nthreads == 512 && geo.maxt == 48 && geo.maxr == 3) LAUNCH_ADJ(48, 512, 3, false);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    for (const AdjointInst& a : kGeoms)
+        if (a.g.nthreads == geo.nthreads && a.g.maxt == geo.maxt && a.g.maxr == geo.maxr && !a.g.wlds == !geo.wlds) return launch(a, lds_bytes, nullptr, nullptr);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_reduce(const float* slab, int n_tiles, int n_params, int stride, const LossWeights& lw, float* out,
@@ -2253,55 +2244,18 @@ hipError_t debug_read_stamps(unsigned long long* out16) {
 }
 
 hipError_t set_kernel_attributes(size_t max_lds_bytes) {
-    hipError_t e;
-    const int v = (int)max_lds_bytes;
-#define SETATTR(K) if ((e = hipFuncSetAttribute((const void*)(K), hipFuncAttributeMaxDynamicSharedMemorySize, v)) != hipSuccess) return e
-    SETATTR((rhs_kernel<false>));
-    SETATTR((rhs_kernel<true>));
-    SETATTR((forward_kernel<false, 256, false, true>));
-    SETATTR((forward_kernel<false, 256, true, true>));
-    SETATTR((forward_kernel<false, 1024, false, true>));
-    SETATTR((forward_kernel<false, 1024, true, true>));
-    SETATTR((adjoint_kernel<1, 1024, 2, false, true, false, true>));
-    SETATTR((adjoint_kernel<1, 1024, 2, false, true, true, true>));
-    SETATTR(infer_kernel);
-    SETATTR((forward_kernel<true, 512>));
-    SETATTR((forward_kernel<true, 256>));
-    SETATTR((forward_kernel<false, 512>));
-    SETATTR((forward_kernel<false, 256>));
-    SETATTR((forward_kernel<true, 1024>));
-    SETATTR((forward_kernel<false, 1024>));
-    SETATTR((adjoint_kernel<16, 512, 3, true>));
-    SETATTR((adjoint_kernel<32, 256, 6, true>));
-    SETATTR((adjoint_kernel<32, 256, 6, false>));
-    SETATTR((adjoint_kernel<32, 256, 12, false>));
-    SETATTR((adjoint_kernel<32, 512, 6, false>));
-    SETATTR((adjoint_kernel<48, 512, 3, false>));
-    SETATTR((adjoint_kernel<1, 512, 3, false, true>));
-    SETATTR((adjoint_kernel<1, 512, 6, false, true>));
-    SETATTR((adjoint_kernel<1, 1024, 2, false, true>));
-    // the RKC2 instantiations
-    SETATTR((forward_kernel<true, 512, true>));
-    SETATTR((forward_kernel<true, 256, true>));
-    SETATTR((forward_kernel<false, 512, true>));
-    SETATTR((forward_kernel<false, 256, true>));
-    SETATTR((forward_kernel<true, 1024, true>));
-    SETATTR((forward_kernel<false, 1024, true>));
-    SETATTR((adjoint_kernel<16, 512, 3, true, false, true>));
-    SETATTR((adjoint_kernel<32, 256, 6, true, false, true>));
-    SETATTR((adjoint_kernel<32, 256, 6, false, false, true>));
-    SETATTR((adjoint_kernel<32, 256, 12, false, false, true>));
-    SETATTR((adjoint_kernel<32, 512, 6, false, false, true>));
-    SETATTR((adjoint_kernel<48, 512, 3, false, false, true>));
-    SETATTR((adjoint_kernel<1, 512, 3, false, true, true>));
-    SETATTR((adjoint_kernel<1, 512, 6, false, true, true>));
-    SETATTR((adjoint_kernel<1, 1024, 2, false, true, true>));
-    SETATTR((adjoint_kernel<1, 1024, 2, true, true, false>));
-    SETATTR((adjoint_kernel<1, 1024, 2, true, true, true>));
-    SETATTR((dw_gemm_split_kernel<1, 1>)); SETATTR((dw_gemm_split_kernel<1, 2>)); SETATTR((dw_gemm_split_kernel<2, 1>)); SETATTR((dw_gemm_split_kernel<2, 2>));
-    SETATTR((dw_gemm_lds_kernel<1, DW_NW, 1>)); SETATTR((dw_gemm_lds_kernel<1, DW_NW, 2>)); SETATTR((dw_gemm_lds_kernel<1, DW_NW, 4>));
-    SETATTR((dw_gemm_lds_kernel<2, DW_NW, 1>)); SETATTR((dw_gemm_lds_kernel<2, DW_NW, 2>)); SETATTR((dw_gemm_lds_kernel<2, DW_NW, 4>));
-    SETATTR((dw_gemm_lds_kernel<3, DW_NW, 1>)); SETATTR((dw_gemm_lds_kernel<3, DW_NW, 2>)); SETATTR((dw_gemm_lds_kernel<3, DW_NW, 4>));
-#undef SETATTR
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    auto set = [&](auto* k) { if (k && e == hipSuccess) e = set_max_lds(k, max_lds_bytes); };
+    set(infer_kernel);
+    for (int ag = 0; ag < 2; ag++) set(rhs_pick(ag));
+    for (int rkc = 0; rkc < 2; rkc++) {
+        for (const AdjointInst& a : kGeoms) set(a.k[rkc]);
+        for (const AdjointInst& a : kTapedGeoms) set(a.k[rkc]);
+        for (int nthreads : {256, 512, 1024})
+            for (int wlds = 0; wlds < 2; wlds++)
+                for (int ag = 0; ag < 2; ag++) set(forward_pick(wlds, nthreads, rkc, ag));
+    }
+    for (const auto& row : kDwSplitKernels) for (auto k : row) set(k);
+    for (const auto& row : kDwLdsKernels) for (auto k : row) set(k);
+    return e;
 }
