@@ -57,8 +57,8 @@ typedef float f32x2v __attribute__((ext_vector_type(2)));
 #endif                        // 32-column stage, +19 GB at the bench size) and the adjoint drops its layer-2 recomputation (75 of its 336 f32 MFMAs per stage).  Measured SLOWER: forward
                               // 27.5 -> 29.4-30.0 ms, adjoint 56.2 -> 61.9 ms (Z2 fetched one net ahead: scratch 536 -> 684 B) / 64.5 ms (fetched at the net's top: 668 B and the
                               // latency exposed) — the recomputation's MFMAs ride under the vector phases, its replacement's registers do not exist (profiles/r05_ab_adjoint_variants.log)
-#define RT_TAPEZ_HALF (21 * 256)
-#define RT_Z2OFF ((RT_ZRICH ? 2 : 1) * RT_TAPEZ_HALF)   // floats per (tile, step, stage) of the layer-1 tape: 3 nets x 7 groups x 64 lanes x 4 (RT_ZRICH: values, then derivatives)
+#define RT_TAPEZ_HALF (20 * 256)
+#define RT_Z2OFF ((RT_ZRICH ? 2 : 1) * RT_TAPEZ_HALF)   // floats per (tile, step, stage) of the layer-1 tape: the forward kernel's 10 tiles x 2 lane pairs x 64 lanes x 4 (RT_ZRICH: values, then derivatives)
 #define RT_TAPEZ (RT_Z2OFF + (RT_Z2TAPE ? 9 * 256 : 0)) // ... and of the whole pre-activation record (layer 2 behind layer 1: net n's register r < 10 = features 2r, 2r+1 is element r & 3 of group 3n + (r >> 2))
 #define RT_TAPE2 (20 * 256)   // ... of the layer-1 delta tape: 20 groups x 64 lanes x 4, the three nets' 25 registers stacked (G = 25 n + g)
 
@@ -950,30 +950,32 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
     };
     inject(0, false);
 
-    // taped layer-1 pre-activations of net n at (step, stage): registers G' < 25 of Z (padding registers untouched)
+    // taped layer-1 pre-activations of net n at (step, stage): registers G' < 25 of Z (padding registers untouched).  The record is the forward kernel's
+    // ten layer-1 tiles as they left its accumulators: group (t, c), lane, element e = stacked quad Q = 4 t + e (net Q / 13, qq = Q % 13), feature 4 qq + h + 2 c,
+    // i.e. register G' = 2 qq + c of this lane.  Net n's 13 quads lie in four tiles; a tile shared with a neighbouring net is fetched by both (its other
+    // elements are dropped here, not kept: the registers do not exist).  Eight 16-byte loads, each one contiguous KiB per wave; every index is compile-time.
     // (RT_ZRICH: Z receives the taped activation values and Dz their derivatives; nothing is left to evaluate)
     auto load_z1 = [&](int step, int st, int n, f32x16 (&Z)[2], f32x16 (&Dz)[2]) {
         size_t rec = (size_t)step * 4 + st;
-#ifdef RT_ABL_Z1_CACHED   // (ablation probe, results wrong: every stage reads the tile's FIRST Z1 record — the loads stay, the 50.7 GB of HBM reads go; VERDICT r4 task 4a)
+#ifdef RT_ABL_Z1_CACHED   // (ablation probe, results wrong: every stage reads the tile's FIRST Z1 record — the loads stay, the 48.3 GB of HBM reads go; VERDICT r4 task 4a)
         { int z_ = 0; asm volatile("" : "+v"(z_)); rec = (size_t)z_; }      // (opaque, so that the loads are not hoisted out of the time loop)
 #endif
-        const float* srcz = tpz + rec * RT_TAPEZ + n * 7 * 256;
+        const float* srcz = tpz + rec * RT_TAPEZ;
+        auto fill = [&](const float* src, f32x16 (&T)[2]) {
 #pragma unroll
-        for (int grp = 0; grp < 7; grp++) {
-            const f32x4v v = RT_TAPE_LOAD4(srcz + grp * 256);
+            for (int t = (13 * n) >> 2; t <= (13 * n + 12) >> 2; t++)
 #pragma unroll
-            for (int e = 0; e < 4; e++)
-                if (4 * grp + e < 25) Z[grp >> 2][(grp & 3) * 4 + e] = v[e];
-        }
-        if (RT_ZRICH) {
+                for (int c = 0; c < 2; c++) {
+                    const f32x4v v = RT_TAPE_LOAD4(src + (2 * t + c) * 256);
 #pragma unroll
-            for (int grp = 0; grp < 7; grp++) {
-                const f32x4v v = RT_TAPE_LOAD4(srcz + RT_TAPEZ_HALF + grp * 256);
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (4 * grp + e < 25) Dz[grp >> 2][(grp & 3) * 4 + e] = v[e];
-            }
-        }
+                    for (int e = 0; e < 4; e++) {
+                        const int G = 2 * (4 * t + e - 13 * n) + c;
+                        if ((4 * t + e) / 13 == n && G < 25) T[G >> 4][G & 15] = v[e];
+                    }
+                }
+        };
+        fill(srcz, Z);
+        if (RT_ZRICH) fill(srcz + RT_TAPEZ_HALF, Dz);
     };
 
     // taped layer-2 pre-activations of net n (RT_Z2TAPE): registers r < 10 of Z (the rest zero)
@@ -1642,38 +1644,12 @@ __device__ __forceinline__ f32x4t rt16_chain_fill(const float* wl, f32x4t acc, A
     return acc;
 }
 
-// Z1 tape store of layer-1 tile tt of the 16-column forward kernels (the adjoint's per-net register-image format: feature f = 4 qq + g of net n is element
-// 2 (qq & 1) + (g >> 1) of group qq >> 1 at lane32 = j + 16 half + 32 (g & 1)).  Round 5 A/B (-DRT_Z1_DWORD=0): 16-byte stores instead of dword stores.  The lanes g and g ^ 2
-// (= lane ^ 32) hold the two halves of every group; two v_permlane32_swap per FOUR consecutive qq hand lanes g < 2 the complete group qq0 >> 1 and lanes
-// g >= 2 the complete next group, so a net's twelve quads leave with three 16-byte stores per lane (all 64 lanes storing) instead of twelve dword stores;
-// quad 12 (features 48, 49: lanes g < 2) keeps its dword store.  A chunk of four quads may straddle two tiles: the pre-activations wait in zpre (compile-time indices).
-// MEASURED SLOWER: forward 28.0 -> 31.7 ms (bit-identical tapes; 39 dword stores become 9 16-byte stores + 3 dword stores + 18 swaps per lane and stage, but the swaps and the
-// waiting pre-activations cost the 128-register kernel more than the store instructions did) — the dword stores stay.
-#ifndef RT_Z1_DWORD
-#define RT_Z1_DWORD 1         // 1: dword stores (shipped); 0: the 16-byte variant (A/B build)
-#endif
-__device__ __forceinline__ void rt16_tape_z1(float* oz /* tz + record offset (lane part and (g >> 1) folded in) */, float (&zpre)[40], const f32x4t z, int tt, int g) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int Q = 4 * tt + r, qq = Q % 13, net = Q / 13;
-        if (Q >= 39) continue;
-        if (RT_Z1_DWORD) {
-            if (qq < 12 || g < 2) oz[(net * 7 + (qq >> 1)) * 256 + ((2 * qq) & 3)] = z[r];
-            continue;
-        }
-        zpre[Q] = z[r];
-        if (qq == 12) {
-            if (g < 2) oz[(net * 7 + 6) * 256] = z[r];
-        } else if ((qq & 3) == 3) {
-            const int Q0 = Q - 3;
-            const auto s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(zpre[Q0]), __float_as_uint(zpre[Q0 + 2]), false, false);
-            const auto s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(zpre[Q0 + 1]), __float_as_uint(zpre[Q0 + 3]), false, false);
-            const f32x4v v = {__uint_as_float(s02[0]), __uint_as_float(s02[1]), __uint_as_float(s13[0]), __uint_as_float(s13[1])};
-            *reinterpret_cast<f32x4v*>(oz - (g >> 1) + (net * 7 + ((qq - 3) >> 1) + (g >> 1)) * 256) = v;
-        }
-    }
-}
-
+// Z1 tape of the 16-column forward kernels: layer-1 tile tt leaves as it sits in the accumulators, one 16-byte store per lane (a wave instruction writes four
+// complete 256-byte runs, no address or mask arithmetic).  Record of one (32-column tile, step, stage): [t = 0..9][c = 0..1][64 lanes][4]; group (t, c), lane
+// j + 16 half + 32 h, element e = the pre-activation of stacked quad Q = 4 t + e (net Q / 13, qq = Q % 13), feature 4 qq + g with g = h + 2 c, column j + 16 half:
+// A1[t] of forward lane (j, g).  The adjoint's loads do the renaming into its per-net registers (load_z1).  Slot Q = 39 and the qq = 12, g >= 2 slots hold what the
+// padding rows produce (finite, never read).  (The earlier record in the adjoint's per-net register-image format took 39 dword stores per lane and stage, each wave
+// store filling 8 of every 16 bytes; assembling that format's 16-byte groups with v_permlane32_swap was measured slower still: forward 28.0 -> 31.7 ms, round 5.)
 template <int ACT, bool SPLIT = false>
 __global__ void __launch_bounds__(512)
 rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ x0, const float* __restrict__ bcs,
@@ -1743,9 +1719,8 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
 #endif
     // 32-column register image: group (q*4 + 2 tau + (g>>1)), lane32 = j + 16 half + 32 (g & 1)
     float* tp = tape ? tape + (size_t)tile32 * n_steps * 4 * 3072 + ((g >> 1) * 64 + j + 16 * half + 32 * (g & 1)) * 4 : nullptr;
-    // layer-1 pre-activations, taped in the adjoint kernel's per-net register-image format (same as the delta tape): feature
-    // f = 4 qq + g of net n is element (2qq & 3) + (g >> 1) of group qq >> 1, lane32 = j + 16 half + 32 (g & 1)
-    float* tz = tapez ? tapez + (size_t)tile32 * n_steps * 4 * RT_TAPEZ + (j + 16 * half + 32 * (g & 1)) * 4 + (g >> 1) : nullptr;
+    // layer-1 pre-activations, taped as whole accumulator tiles: tile t is group 2 t + (g >> 1), lane32 = j + 16 half + 32 (g & 1) (as the stage tape above)
+    float* tz = tapez ? tapez + (size_t)tile32 * n_steps * 4 * RT_TAPEZ + ((g >> 1) * 64 + j + 16 * half + 32 * (g & 1)) * 4 : nullptr;
     const float Nz = 32.0f;
     struct { float cU, sU, cV, sV, cB, sB, kE, oE, cE, nA, nB, f0, f1, f2; } pc;
     {
@@ -1780,7 +1755,6 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                 RT_STAMP(0);
                 // ---- three MLPs -------------------------------------------------------------------------------------
                 f32x4t A1[10];
-                float zpre[40];             // layer-1 pre-activations waiting for their 16-byte tape store (rt16_tape_z1): at most one tile's worth is live
                 // operand addresses stay (lane base + immediate): left loop-invariant, all ~150 of them are computed outside the time loop and spilled
                 int lz = lane;
                 if constexpr (SPLIT) asm volatile("" : "+v"(lz));
@@ -1805,7 +1779,8 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                             const int nx = q * 10 + t + 1;                                        // the group after (q, t) in this order
                             if (nx < 30) Apf = rt16_ldA(simg, 3 * (nx % 10) + nx / 10, lz);
                             auto finish = [&](int tt) {        // tile tt is complete: tape store, activation
-                                if (tz && !RT_ZRICH) rt16_tape_z1(tz + ((size_t)step * 4 + st) * RT_TAPEZ, zpre, A1[tt], tt, g);
+                                float* oz = tz ? tz + ((size_t)step * 4 + st) * RT_TAPEZ + 2 * tt * 256 : nullptr;
+                                if (tz && !RT_ZRICH) *reinterpret_cast<f32x4v*>(oz) = A1[tt];
                                 // (side-effect-free arithmetic is not ordered against the scheduling fences when the block is linearised: the empty
                                 //  asm statements pin the activation's inputs below the products' issue point and its results above the closing fence)
 #pragma unroll
@@ -1815,16 +1790,8 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                                     f32x2v a0, d0, a1, d1;
                                     rt_act_pair4<ACT>((f32x2v){A1[tt][0], A1[tt][1]}, (f32x2v){A1[tt][2], A1[tt][3]}, a0, d0, a1, d1);
                                     A1[tt] = (f32x4t){a0.x, a0.y, a1.x, a1.y};
-                                    const float dd[4] = {d0.x, d0.y, d1.x, d1.y};
-                                    float* oz = tz + ((size_t)step * 4 + st) * RT_TAPEZ;
-#pragma unroll
-                                    for (int r = 0; r < 4; r++) {
-                                        const int Q = 4 * tt + r, qq = Q % 13;
-                                        if (Q < 39 && (qq < 12 || g < 2)) {
-                                            oz[((Q / 13) * 7 + (qq >> 1)) * 256 + ((2 * qq) & 3)] = A1[tt][r];
-                                            oz[RT_TAPEZ_HALF + ((Q / 13) * 7 + (qq >> 1)) * 256 + ((2 * qq) & 3)] = dd[r];
-                                        }
-                                    }
+                                    *reinterpret_cast<f32x4v*>(oz) = A1[tt];
+                                    *reinterpret_cast<f32x4v*>(oz + RT_TAPEZ_HALF) = (f32x4v){d0.x, d0.y, d1.x, d1.y};
                                 } else
                                 A1[tt] = rt_act4<ACT>(A1[tt]);
 #pragma unroll
@@ -1853,23 +1820,16 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                     }
                 } else {
                 auto finish1 = [&](int tt) {          // tile tt of layer 1 is complete: Z1 tape store, activation (pinned: see rt16_chain_fill)
-                    if (tz && !RT_ZRICH) rt16_tape_z1(tz + ((size_t)step * 4 + st) * RT_TAPEZ, zpre, A1[tt], tt, g);
+                    float* oz = tz ? tz + ((size_t)step * 4 + st) * RT_TAPEZ + 2 * tt * 256 : nullptr;
+                    if (tz && !RT_ZRICH) *reinterpret_cast<f32x4v*>(oz) = A1[tt];
 #pragma unroll
                     for (int r = 0; r < 4; r++) asm volatile("" : "+v"(A1[tt][r]));
                     if (RT_ZRICH && tz) {
                         f32x2v a0, d0, a1, d1;
                         rt_act_pair4<ACT>((f32x2v){A1[tt][0], A1[tt][1]}, (f32x2v){A1[tt][2], A1[tt][3]}, a0, d0, a1, d1);
                         A1[tt] = (f32x4t){a0.x, a0.y, a1.x, a1.y};
-                        const float dd[4] = {d0.x, d0.y, d1.x, d1.y};
-                        float* oz = tz + ((size_t)step * 4 + st) * RT_TAPEZ;
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int Q = 4 * tt + r, qq = Q % 13;
-                            if (Q < 39 && (qq < 12 || g < 2)) {
-                                oz[((Q / 13) * 7 + (qq >> 1)) * 256 + ((2 * qq) & 3)] = A1[tt][r];
-                                oz[RT_TAPEZ_HALF + ((Q / 13) * 7 + (qq >> 1)) * 256 + ((2 * qq) & 3)] = dd[r];
-                            }
-                        }
+                        *reinterpret_cast<f32x4v*>(oz) = A1[tt];
+                        *reinterpret_cast<f32x4v*>(oz + RT_TAPEZ_HALF) = (f32x4v){d0.x, d0.y, d1.x, d1.y};
                     } else
                     A1[tt] = rt_act4<ACT>(A1[tt]);
 #pragma unroll
@@ -1933,7 +1893,8 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                         }
                         if (RT_Z2TAPE && tz) {
                             // layer-2 pre-activations in the adjoint's register-image format: feature f = 4 Q2 + g of net n is element (2 Q2 & 3) + (g >> 1) of group 3 n + (Q2 >> 1)
-                            float* oz = tz + ((size_t)step * 4 + st) * RT_TAPEZ + RT_Z2OFF;
+                            // (tz carries the Z1 record's lane part, group (g >> 1) included: taken back here, where g >> 1 selects the element instead)
+                            float* oz = tz + ((size_t)step * 4 + st) * RT_TAPEZ + RT_Z2OFF - (g >> 1) * 255;
 #pragma unroll
                             for (int r = 0; r < 4; r++) {
                                 const int Q2 = 4 * u + r;

@@ -53,8 +53,7 @@ if sq_csv:
     out["sq"] = sq
 out["correction"] = ("gfx950: FETCH_SIZE doubled (MI355X_MICROARCH.md HBM section); cross-check on known byte counts: rt16_forward WRITE_SIZE = stage "
                      "tape 28.99 GB + Z1 tape + sol 3.64 GB; rt_dw1 2*FETCH_SIZE = stage tape 28.99 GB + delta tape 48.32 GB (20 groups since r02b)")
-out["source"] = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_* (separate passes, --kernel-trace only) -- python3 bench.py --steps 1 --warmup 1 "
-                 "--no-cpu-baseline --no-configs (%s)" % tag)
+out["source"] = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_* (separate passes, no API tracing) -- python3 bench.py --steps 1 --warmup 1 (%s)" % tag)
 json.dump(out, open(os.path.join(ROOT, "profiles", "traffic.json"), "w"), indent=1)
 for k, v in out["per_kernel"].items():
     print("%-14s %8.2f GB per launch" % (k, v["hbm_bytes"] / 1e9))
