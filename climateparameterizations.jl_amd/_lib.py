@@ -76,6 +76,13 @@ SYMBOLS = [
     ("colnde_ensemble_loss_grad_dev", ctypes.c_int, [_V, _V, _F, _V]),
     ("colnde_ensemble_loss_grad", ctypes.c_int, [_V, _V, _F, _V]),
     ("colnde_ensemble_adam_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V] + [ctypes.c_float] * 5),
+    ("colnde_closure_min_substeps", ctypes.c_int, [_V, _F]),
+    ("colnde_create_closure", ctypes.c_int, [_V, ctypes.c_int, ctypes.POINTER(_V)]),
+    ("colnde_closure_forward_dev", ctypes.c_int, [_V, _V, _V]),
+    ("colnde_closure_loss_dev", ctypes.c_int, [_V, _V, _F, _V]),
+    ("colnde_closure_loss_grad_dev", ctypes.c_int, [_V, _V, _F, _V]),
+    ("colnde_closure_forward", ctypes.c_int, [_V, _V, _V]),
+    ("colnde_closure_loss_grad", ctypes.c_int, [_V, _V, _F, _V]),
     ("colnde_set_profiling", ctypes.c_int, [_V, ctypes.c_int]),
     ("colnde_kernel_time", ctypes.c_int, [_V, ctypes.c_int, _F, ctypes.POINTER(ctypes.c_int)]),
     ("colnde_reset_kernel_times", ctypes.c_int, [_V]),

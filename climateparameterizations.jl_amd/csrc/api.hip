@@ -14,6 +14,7 @@
 #include "engine_regtile.h"
 #include "engine_fc.h"
 #include "column_ops.h"
+#include "engine_closure.h"
 
 static thread_local std::string g_err;
 
@@ -30,6 +31,9 @@ static int fail(const char* fmt, ...) {
 // Entry points that take ONE weight vector refuse an ensemble handle (colnde_create_ensemble)
 #define SINGLE_MODEL_ONLY(h)                                                                                                              \
     do {                                                                                                                                  \
+        if ((h) && (h)->closure)                                                                                                          \
+            return fail("%s takes a weight vector, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", \
+                        __func__, (h)->n_models);                                                                                         \
         if ((h) && (h)->ensemble)                                                                                                         \
             return fail("%s takes one weight vector, but this handle holds an ensemble of %d models: use colnde_ensemble_* (include/colnde.h)", \
                         __func__, (h)->n_models);                                                                                         \
@@ -121,6 +125,11 @@ struct colnde_handle {
     RtEns ens;                      // per-model strides of the buffers a model owns
     size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)
     int ens_rkc_stages = 0;         // RKC2, automatic stage count: the largest any model needs (refresh_rkc)
+    // closure-only model (colnde_create_closure): n_models constant sets of the Pacanowski-Philander closure, no networks (engine_closure.hip)
+    bool closure = false;
+    ClosureModel cm = {};
+    float *d_cl_tape = nullptr, *d_cl_rows = nullptr, *d_cl_params = nullptr;
+    size_t cl_tape_bytes = 0;
     std::vector<PendingEvent> pending;
     double ms[K_COUNT] = {};
     int launches[K_COUNT] = {};
@@ -620,7 +629,8 @@ extern "C" void colnde_destroy(colnde_handle* h) {
     drain_events(h);
     void* ptrs[] = {h->d_rt_tapez, h->d_rt_tape, h->d_rt_tape2, h->d_rt_slab, h->d_wimg, h->d_w, h->d_wf, h->d_wb, h->d_x0, h->d_bcs, h->d_truth, h->d_sol, h->d_tape, h->d_slab, h->d_out,
                     h->d_times, h->d_partial, h->d_tmp_a, h->d_tmp_b, h->d_tmp_c, h->d_tiles, h->d_bias_zoff, h->d_bias_goff, h->d_dwtape, h->d_macros, h->d_t16_ztape, h->d_rkc, h->d_ag, h->d_sf, h->d_sb,
-                    h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_masks, h->d_fc_switch, h->d_fc_lam, h->d_fc_simgf, h->d_fc_simgb, h->d_phys};
+                    h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_masks, h->d_fc_switch, h->d_fc_lam, h->d_fc_simgf, h->d_fc_simgb, h->d_phys,
+                    h->d_cl_tape, h->d_cl_rows, h->d_cl_params};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     dw_split_free(h->dw_split);
@@ -647,7 +657,7 @@ extern "C" int colnde_set_matrix_arithmetic(colnde_handle* h, int ma) {
 extern "C" int colnde_matrix_arithmetic(const colnde_handle* h) { return h ? h->cfg.matrix_arithmetic : -1; }
 
 extern "C" int colnde_set_global_columns(colnde_handle* h, int64_t n) {
-    SINGLE_MODEL_ONLY(h);
+    if (!(h && h->closure)) SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (n < h->n_col) return fail("global column count %lld < local %d", (long long)n, h->n_col);
     h->n_col_total = n;
@@ -1625,6 +1635,7 @@ extern "C" int colnde_n_models(const colnde_handle* h) { return h ? h->n_models 
 
 static int ensemble_only(const colnde_handle* h) {
     if (!h) return fail("null handle");
+    if (h->closure) return fail("colnde_ensemble_* take weight vectors, but this is a closure handle (no networks): use colnde_closure_* (include/colnde.h)");
     if (!h->ensemble) return fail("not an ensemble handle: colnde_ensemble_* take the handles of colnde_create_ensemble (colnde_create: the single-model calls)");
     return 0;
 }
@@ -2282,6 +2293,21 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
     if (colnde_plan(h, info)) return -1;
     std::string s;
     char t[256];
+    if (h->closure) {
+        snprintf(t, sizeof t, "engine=closure sets=%d columns=%d Nz=%d stepper=rk4 substeps=%d tape=step_start_states tape_bytes=%zu gradient=exact discrete adjoint",
+                 h->n_models, h->n_col, h->m.Nz, h->cfg.substeps, h->cl_tape_bytes);
+        s = t;
+        const char* e = getenv("COLNDE_ALLOW_UNSTABLE_DT");
+        s += " | env";
+        if (e && *e) { s += " COLNDE_ALLOW_UNSTABLE_DT="; s += e; } else s += " (none set)";
+        const int need = (int)s.size() + 1;
+        if (buf && capacity > 0) {
+            const int n = need <= capacity ? need - 1 : capacity - 1;
+            memcpy(buf, s.data(), n);
+            buf[n] = 0;
+        }
+        return need;
+    }
     const char* eng = info[0] == COLNDE_ENGINE_MFMA ? "regtile" : info[0] == COLNDE_ENGINE_FC32 ? "fc32" : ((info[6] & 1) ? "tile16+net-split" : "tile16");
     char why[96] = "";
     if (h->auto_substeps) snprintf(why, sizeof why, "(stability bound; pending: the first solve chooses from reltol=%g)", h->cfg.reltol);
@@ -2339,5 +2365,221 @@ extern "C" int colnde_debug_stamps(colnde_handle* h, unsigned long long* out16) 
         return 0;
     }
     HIPCHK(debug_read_stamps(out16));
+    return 0;
+}
+
+// ---- closure-only model: calibrating the five Pacanowski-Philander constants (colnde_create_closure) ------------------------------------------------
+// The reference fits nu0, nu_minus, dRi, Ric, Pr to the LES profiles before any network is trained (optimise_modified_pacanowski_philander,
+// wind_mixing/src/diffusivity_parameter_optimisation.jl:35-231): the same column ODE without the MLPs (DE, :1-33), the same six-term loss (:150-163).
+// A closure handle holds K constant sets on the same columns; every kernel (engine_closure.hip) runs once for all K.
+
+// cfg as the closure model reads it: wind mixing, MPP, one placeholder Dense layer so that validate() has a network to look at
+static colnde_config closure_config(const colnde_config* cfg, const float* params) {
+    colnde_config c = *cfg;
+    c.n_layers = 1;
+    c.layer_sizes[0] = 3 * c.Nz;
+    c.layer_sizes[1] = c.Nz - 1;
+    c.activations[0] = COLNDE_ACT_IDENTITY;
+    if (params) { c.nu0 = params[0]; c.nu_minus = params[1]; c.dRi = params[2]; c.Ric = params[3]; c.Pr = params[4]; }
+    return c;
+}
+
+static int closure_refusals(const colnde_config* cfg) {
+    if (!cfg) return fail("null config");
+    if (cfg->model != COLNDE_MODEL_WIND_MIXING) return fail("the closure model is the wind-mixing column without networks: model = %d is refused", cfg->model);
+    if (!cfg->modified_pacanowski_philander) return fail("the closure model IS the modified Pacanowski-Philander closure: modified_pacanowski_philander must be 1");
+    if (cfg->convective_adjustment) return fail("closure model: convective_adjustment is not part of DE (diffusivity_parameter_optimisation.jl:1-33)");
+    if (cfg->smooth_NN) return fail("closure model: smooth_NN filters network outputs, and there are none");
+    if (cfg->smooth_Ri) return fail("closure model: smooth_Ri is not part of DE (diffusivity_parameter_optimisation.jl:1-33)");
+    if (cfg->diurnal) return fail("closure model: diurnal forcing is not supported (DE takes constant boundary fluxes)");
+    if (cfg->inplace_variant) return fail("closure model: inplace_variant (the NDE! evaluation arithmetic) is not supported");
+    if (cfg->stepper != COLNDE_STEPPER_RK4) return fail("closure model: classical RK4 only (RKC2 is not supported)");
+    if (cfg->substeps == 0) return fail("closure model: substeps = 0 (chosen from reltol) is not supported: the tape is sized at creation — pass substeps >= "
+                                        "colnde_closure_min_substeps of the constants you start from");
+    if (cfg->engine != COLNDE_ENGINE_AUTO) return fail("closure model: engine forced to %d, but the closure kernels are an engine of their own (use COLNDE_ENGINE_AUTO)", cfg->engine);
+    if (cfg->Nz > CLOSURE_MAX_NZ) return fail("closure model: Nz = %d outside 4..%d (a lane per level)", cfg->Nz, CLOSURE_MAX_NZ);
+    return 0;
+}
+
+extern "C" int colnde_closure_min_substeps(const colnde_config* cfg, const float params[5]) {
+    if (!cfg || !params) { fail("null argument"); return -1; }
+    for (int q = 0; q < 5; q++)
+        if (!std::isfinite(params[q])) { fail("params[%d] = %g is not finite", q, params[q]); return -1; }
+    if (!(params[2] > 0.0f) || !(params[4] > 0.0f)) { fail("dRi = %g and Pr = %g must be > 0", params[2], params[4]); return -1; }
+    colnde_config c = closure_config(cfg, params);
+    c.model = COLNDE_MODEL_WIND_MIXING;
+    c.modified_pacanowski_philander = 1;
+    c.convective_adjustment = 0;
+    c.inplace_variant = 0;
+    c.stepper = COLNDE_STEPPER_RK4;
+    return colnde_min_substeps(&c);
+}
+
+extern "C" int colnde_create_closure(const colnde_config* cfg, int n_sets, colnde_handle** out) {
+    if (!out) return fail("null out pointer");
+    *out = nullptr;
+    if (closure_refusals(cfg)) return 1;
+    const colnde_config cc = closure_config(cfg, nullptr);
+    if (validate(&cc)) return 1;
+    if (n_sets < 1) return fail("n_sets = %d must be >= 1", n_sets);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail("no HIP device visible: colnde has no CPU fallback (the product path is the gfx950 HIP engine)");
+    if (cc.device < 0 || cc.device >= ndev) return fail("device %d not in 0..%d", cc.device, ndev - 1);
+    HIPCHK(hipSetDevice(cc.device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, cc.device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail("device %d is %s; this library is built for gfx950 (MI355X) only", cc.device, prop.gcnArchName);
+
+    colnde_handle* h = new (std::nothrow) colnde_handle();
+    if (!h) return fail("out of host memory");
+    h->cfg = cc;
+    h->save_times.assign(cc.save_times, cc.save_times + cc.n_save);
+    h->cfg.save_times = h->save_times.data();
+    h->device = cc.device;
+    h->n_col = cc.n_columns;
+    h->n_col_total = cc.n_columns;
+    h->closure = true;
+    h->n_models = n_sets;
+    PackInfo pk;
+    build_model(&cc, &h->m, &pk);            // scalings and the physics prefactors; the network fields are not used
+    h->m.n_params = CLOSURE_N_PARAMS;
+    h->m.n_nets = 0;
+    h->m.nst = 4;
+    ClosureModel& cm = h->cm;
+    cm.Nz = cc.Nz; cm.n_save = cc.n_save; cm.substeps = cc.substeps; cm.n_col = cc.n_columns; cm.n_sets = n_sets;
+    for (int k = 0; k < 3; k++) { cm.cs[k] = h->m.cs[k]; cm.A[k] = h->m.A[k]; cm.s0[k] = h->m.s0[k]; }
+    cm.B = h->m.B; cm.cor_u = h->m.cor_u; cm.cor_v = h->m.cor_v; cm.sig_u = h->m.sig_u; cm.sig_v = h->m.sig_v; cm.mu_u = h->m.mu_u; cm.mu_v = h->m.mu_v;
+    cm.eps = h->m.eps;
+    // the tape of all sets, the solutions and the partial rows are allocated here: a handle that does not fit is refused with the bytes it needs
+    const size_t K = (size_t)n_sets, ns = (size_t)h->m.ns;
+    const size_t b_tape = K * closure_tape_floats(cm) * sizeof(float), b_sol = K * h->n_col * cc.n_save * ns * sizeof(float),
+                 b_rows = K * h->n_col * CLOSURE_ROW * sizeof(float), b_small = K * (CLOSURE_N_PARAMS + CLOSURE_N_PARAMS + 8) * sizeof(float),
+                 b_problem = (size_t)h->n_col * (ns * (1 + cc.n_save) + 6) * sizeof(float);
+    const size_t need = b_tape + b_sol + b_rows + b_small + b_problem;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { delete h; return fail("hipMemGetInfo failed"); }
+    const size_t margin = (size_t)1 << 30;
+    if (need + margin > free_b) {
+        delete h;
+        return fail("a closure handle of %d sets x %d columns needs %zu bytes of device memory (%zu of them the step-start tape: %d save intervals x %d substeps x "
+                    "%zu floats per column and set); %zu bytes are free (1 GB kept in reserve): use fewer sets per handle",
+                    n_sets, cc.n_columns, need, b_tape, cc.n_save - 1, cc.substeps, ns, free_b);
+    }
+    h->cl_tape_bytes = b_tape;
+    hipError_t e = hipMalloc((void**)&h->d_cl_tape, b_tape);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_sol, b_sol);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_cl_rows, b_rows);
+    if (e == hipSuccess) e = hipMemset(h->d_cl_rows, 0, b_rows);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_cl_params, K * CLOSURE_N_PARAMS * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_out, K * (CLOSURE_N_PARAMS + 8) * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_x0, (size_t)h->n_col * ns * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_bcs, (size_t)h->n_col * 6 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_times, cc.n_save * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->d_times, h->save_times.data(), sizeof(float) * cc.n_save, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        colnde_destroy(h);
+        return fail("allocating the closure handle's buffers (%zu bytes, %zu of them tape) failed: %s", need, b_tape, hipGetErrorString(e));
+    }
+    *out = h;
+    return 0;
+}
+
+static int closure_only(const colnde_handle* h) {
+    if (!h) return fail("null handle");
+    if (!h->closure) return fail("not a closure handle: colnde_closure_* take the handles of colnde_create_closure");
+    return 0;
+}
+
+// host-side stability check of every set (the _dev calls cannot see the values)
+static int closure_check_sets(const colnde_handle* h, const float* params) {
+    const char* e = getenv("COLNDE_ALLOW_UNSTABLE_DT");
+    const bool allow = e && atoi(e) != 0;
+    for (int k = 0; k < h->n_models; k++) {
+        const float* r = params + (size_t)CLOSURE_N_PARAMS * k;
+        const int ms = colnde_closure_min_substeps(&h->cfg, r);
+        if (ms < 0) return fail("set %d: %s", k, std::string(g_err).c_str());
+        if (h->cfg.substeps < ms && !allow)
+            return fail("set %d (nu0 = %g, nu_minus = %g, Pr = %g) needs substeps >= %d for a stable RK4 step (colnde_closure_min_substeps), but the handle runs "
+                        "substeps = %d (COLNDE_ALLOW_UNSTABLE_DT=1 overrides)", k, r[0], r[1], r[4], ms, h->cfg.substeps);
+    }
+    return 0;
+}
+
+static int closure_forward_impl(colnde_handle* h, const float* d_params, float* d_sol, bool with_tape, bool with_loss) {
+    if (!h->have_problem) return fail("colnde_set_problem has not been called");
+    Timed tm(h, K_FORWARD);
+    hipError_t e = closure_launch_forward(h->cm, d_params, h->d_x0, h->d_bcs, h->d_times, d_sol, with_tape ? h->d_cl_tape : nullptr,
+                                          with_loss ? h->d_truth : nullptr, with_loss ? h->d_cl_rows : nullptr, h->stream);
+    if (e != hipSuccess) return fail("closure forward launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_closure_forward_dev(colnde_handle* h, const float* d_params, float* d_sol) {
+    if (closure_only(h)) return 1;
+    if (!d_params) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    return closure_forward_impl(h, d_params, d_sol ? d_sol : h->d_sol, false, false);
+}
+
+extern "C" int colnde_closure_loss_dev(colnde_handle* h, const float* d_params, const float scalings[6], float* d_out8) {
+    if (closure_only(h)) return 1;
+    if (!d_params || !scalings || !d_out8) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    HIPCHK(hipSetDevice(h->device));
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    if (closure_forward_impl(h, d_params, h->d_sol, false, true)) return 1;
+    Timed tm(h, K_REDUCE);
+    hipError_t e = closure_launch_reduce(h->cm, h->d_cl_rows, lw, false, d_out8, h->stream);
+    if (e != hipSuccess) return fail("closure reduce launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_closure_loss_grad_dev(colnde_handle* h, const float* d_params, const float scalings[6], float* d_out) {
+    if (closure_only(h)) return 1;
+    if (!d_params || !scalings || !d_out) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    HIPCHK(hipSetDevice(h->device));
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    if (closure_forward_impl(h, d_params, h->d_sol, true, true)) return 1;
+    {
+        Timed tm(h, K_ADJOINT);
+        hipError_t e = closure_launch_adjoint(h->cm, d_params, h->d_bcs, h->d_times, h->d_sol, h->d_truth, h->d_cl_tape, lw, h->d_cl_rows, h->stream);
+        if (e != hipSuccess) return fail("closure adjoint launch failed: %s", hipGetErrorString(e));
+    }
+    Timed tm(h, K_REDUCE);
+    hipError_t e = closure_launch_reduce(h->cm, h->d_cl_rows, lw, true, d_out, h->stream);
+    if (e != hipSuccess) return fail("closure reduce launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_closure_forward(colnde_handle* h, const float* params, float* sol) {
+    if (closure_only(h)) return 1;
+    if (!params) return fail("null pointer argument");
+    if (closure_check_sets(h, params)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t K = (size_t)h->n_models;
+    HIPCHK(hipMemcpyAsync(h->d_cl_params, params, sizeof(float) * K * CLOSURE_N_PARAMS, hipMemcpyHostToDevice, h->stream));
+    if (closure_forward_impl(h, h->d_cl_params, h->d_sol, false, false)) return 1;
+    if (sol)
+        HIPCHK(hipMemcpyAsync(sol, h->d_sol, sizeof(float) * K * h->n_col * h->cfg.n_save * h->m.ns, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int colnde_closure_loss_grad(colnde_handle* h, const float* params, const float scalings[6], float* out) {
+    if (closure_only(h)) return 1;
+    if (!params || !scalings || !out) return fail("null pointer argument");
+    if (closure_check_sets(h, params)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t K = (size_t)h->n_models;
+    HIPCHK(hipMemcpyAsync(h->d_cl_params, params, sizeof(float) * K * CLOSURE_N_PARAMS, hipMemcpyHostToDevice, h->stream));
+    if (colnde_closure_loss_grad_dev(h, h->d_cl_params, scalings, h->d_out)) return 1;
+    HIPCHK(hipMemcpyAsync(out, h->d_out, sizeof(float) * K * (CLOSURE_N_PARAMS + 8), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }

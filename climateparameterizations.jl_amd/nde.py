@@ -576,3 +576,113 @@ class ColumnNDEEnsemble(ColumnNDE):
         _lib.check(self._L.colnde_ensemble_adam_step_dev(self._h, weights.data_ptr(), result.data_ptr(), m.data_ptr(), v.data_ptr(), etas.data_ptr(),
                                                          float(beta[0]), float(beta[1]), float(eps), float(bt[0]), float(bt[1])))
         return weights
+
+
+CLOSURE_N_PARAMS = 5
+
+
+def check_closure_arrays(n_sets: int, params=None, out=None):
+    """Shape and type checks of a closure handle's per-set arrays (no GPU needed): params [K, 5] (PHYSICS_KEYS order), out [K, 13].  NumPy arrays are
+    converted to float32 by the callers; a torch tensor must already be a contiguous float32 device tensor (the `_dev` calls read it in place)."""
+    K = int(n_sets)
+    if K < 1:
+        raise ValueError("n_sets must be >= 1, got %d" % K)
+    for name, a, shape in (("params", params, (K, CLOSURE_N_PARAMS)), ("out", out, (K, CLOSURE_N_PARAMS + 8))):
+        if a is None:
+            continue
+        if tuple(a.shape) != shape:
+            raise ValueError("%s: expected shape %s for %d sets, got %s" % (name, shape, K, tuple(a.shape)))
+        if _is_torch(a):
+            import torch
+            if a.dtype != torch.float32 or not a.is_contiguous() or not a.is_cuda:
+                raise ValueError("%s: expected a contiguous float32 device tensor, got %s on %s" % (name, a.dtype, a.device))
+
+
+def closure_min_substeps(cfg: NDEConfig, params) -> int:
+    """`colnde_closure_min_substeps`: the RK4 stability bound for the five constants (nu0, nu_minus, dRi, Ric, Pr); no GPU needed."""
+    c, keep = to_c_config(cfg, 1, 0, 0)
+    p = (ctypes.c_float * 5)(*[float(x) for x in params])
+    n = _lib.lib().colnde_closure_min_substeps(ctypes.byref(c), p)
+    if n < 0:
+        raise _lib.ColndeError(_lib.lib().colnde_last_error().decode("utf-8", "replace"))
+    return int(n)
+
+
+class ClosureColumns(ColumnNDE):
+    """The column model WITHOUT networks (`colnde_create_closure`): K sets of the five Pacanowski-Philander constants solved, scored and differentiated
+    side by side — `DE` / `loss_mpp` of wind_mixing/src/diffusivity_parameter_optimisation.jl.  params: [K, 5] = (nu0, nu_minus, dRi, Ric, Pr) per set.
+    NumPy inputs go through the host entry points (which check every set's stability bound), torch device tensors through the `_dev` twins on torch's
+    current stream.  The calls of `ColumnNDE` that take a weight vector are refused by the library on this handle."""
+
+    def __init__(self, cfg: NDEConfig, n_columns: int, n_sets: int = 1, device: int = 0):
+        check_closure_arrays(n_sets)
+        self.cfg = cfg
+        self.n_columns = int(n_columns)
+        self.n_sets = self.n_models = int(n_sets)
+        self.device = int(device)
+        self._h = ctypes.c_void_p()
+        L = _lib.lib()
+        c, keep = to_c_config(cfg, n_columns, device, 0)
+        _lib.check(L.colnde_create_closure(ctypes.byref(c), self.n_sets, ctypes.byref(self._h)))
+        self._L = L
+        self.n_params = L.colnde_n_params(self._h)
+        assert self.n_params == CLOSURE_N_PARAMS and L.colnde_n_models(self._h) == self.n_sets
+        self.n_columns_total = self.n_columns
+        self.engine = "closure"
+
+    def _params_dev(self, params):
+        import torch
+        check_closure_arrays(self.n_sets, params=params if _is_torch(params) else np.asarray(params))
+        if _is_torch(params):
+            self._chk_dev(params, (self.n_sets, CLOSURE_N_PARAMS))
+            return params, True
+        p = _f32(params, (self.n_sets, CLOSURE_N_PARAMS))
+        return torch.from_numpy(p).to(torch.device("cuda", self.device)), False
+
+    def forward(self, params, out=None):
+        """sol [K, n_columns, n_save, 3 Nz]: a torch tensor for torch params, NumPy for NumPy params."""
+        c = self.cfg
+        shape = (self.n_sets, self.n_columns, c.n_save, c.n_state)
+        if _is_torch(params):
+            import torch
+            p, _ = self._params_dev(params)
+            sol = out if out is not None else torch.empty(shape, dtype=torch.float32, device=p.device)
+            self._chk_dev(sol, shape)
+            self.use_torch_stream()
+            _lib.check(self._L.colnde_closure_forward_dev(self._h, p.data_ptr(), sol.data_ptr()))
+            return sol
+        check_closure_arrays(self.n_sets, params=np.asarray(params))
+        p = _f32(params, (self.n_sets, CLOSURE_N_PARAMS))
+        sol = np.empty(shape, dtype=np.float32)
+        _lib.check(self._L.colnde_closure_forward(self._h, _ptr(p), _ptr(sol)))
+        return sol
+
+    def loss(self, params, scalings: Sequence[float]):
+        """[K, 8] = [scaled terms(6); total; 0] per set."""
+        import torch
+        sc = (ctypes.c_float * 6)(*[float(s) for s in scalings])
+        p, is_t = self._params_dev(params)
+        out = torch.empty((self.n_sets, 8), dtype=torch.float32, device=p.device)
+        self.use_torch_stream()
+        _lib.check(self._L.colnde_closure_loss_dev(self._h, p.data_ptr(), sc, out.data_ptr()))
+        return out if is_t else out.cpu().numpy()
+
+    def loss_grad(self, params, scalings: Sequence[float], out=None):
+        """[K, 13]: per set [dL/dnu0, dL/dnu_minus, dL/ddRi, dL/dRic, dL/dPr; scaled terms(6); total; 0]."""
+        sc = (ctypes.c_float * 6)(*[float(s) for s in scalings])
+        shape = (self.n_sets, CLOSURE_N_PARAMS + 8)
+        if _is_torch(params):
+            import torch
+            p, _ = self._params_dev(params)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=p.device)
+            check_closure_arrays(self.n_sets, out=out)
+            self._chk_dev(out, shape)
+            self.use_torch_stream()
+            _lib.check(self._L.colnde_closure_loss_grad_dev(self._h, p.data_ptr(), sc, out.data_ptr()))
+            return out
+        check_closure_arrays(self.n_sets, params=np.asarray(params))
+        p = _f32(params, (self.n_sets, CLOSURE_N_PARAMS))
+        res = np.empty(shape, dtype=np.float32)
+        _lib.check(self._L.colnde_closure_loss_grad(self._h, _ptr(p), sc, _ptr(res)))
+        return res

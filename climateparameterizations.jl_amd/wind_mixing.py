@@ -375,3 +375,103 @@ def modified_pacanowski_philander_step(engine: ColumnNDE, u, v, T, dt: float, dz
     hb = None if halo_bottom is None else np.asarray(halo_bottom, np.float32).reshape(3, -1)
     uo, vo, To = engine.implicit_diffusion(u2, v2, T2, dt, dz, params, convective_adjustment, hb)
     return uo.reshape(shape), vo.reshape(shape), To.reshape(shape)
+
+
+# ---- calibrating the closure itself (wind_mixing/src/diffusivity_parameter_optimisation.jl) ---------------------------------------------------
+MPP_KEYS = ("nu0", "nu_minus", "dRi", "Ric", "Pr")
+
+
+@dataclass
+class MPPOptimisationResult:
+    parameters: np.ndarray        # [K, 5] fitted constants per start (MPP_KEYS order)
+    losses: np.ndarray            # [n_iterations, K]: total loss BEFORE each update
+    terms: np.ndarray             # [n_iterations, K, 6]: the scaled terms (LOSS_KEYS order)
+    best: int                     # the start whose final loss is least
+    loss_scalings: np.ndarray
+    final_losses: np.ndarray      # [K]: total loss at the returned parameters
+
+
+def _problem_arrays(problem):
+    """(cfg, x0, bcs, truth) of a synthetic.ColumnProblem-like object or of a WindMixingNDE."""
+    get = lambda *names: next((getattr(problem, n) for n in names if getattr(problem, n, None) is not None), None)
+    x0, bcs, truth = get("x0", "uvT0"), get("bcs", "BCs"), get("truth", "uvT_trains")
+    if x0 is None or bcs is None or truth is None:
+        raise ValueError("the problem needs initial profiles, boundary conditions and training trajectories (x0 / bcs / truth)")
+    return problem.cfg, x0, bcs, truth
+
+
+def optimise_modified_pacanowski_philander(problem, optimizers: Sequence[ADAM], maxiters: int, nu0: float = 1e-4, nu_minus: float = 1e-1,
+                                           dRi: float = 0.1, Ric: float = 0.25, Pr: float = 1.0, train_gradient: bool = True,
+                                           gradient_scaling: float = 5e-3, training_fractions: Optional[dict] = None, starts=None,
+                                           cb: Optional[Callable] = None, s_min: float = 1e-3, device: int = 0) -> MPPOptimisationResult:
+    """`optimise_modified_pacanowski_philander` (diffusivity_parameter_optimisation.jl:35-231) on the closure engine: fits (nu0, nu_minus, dRi, Ric, Pr)
+    to the problem's trajectories by ADAM on the exact discrete gradient.
+
+    As in the reference the optimiser works on the SCALED parameters s = p / p_initial, starting from ones (:44-48, :72-73); dL/ds = p_initial * dL/dp is
+    one elementwise op on the result rows, and the update is Flux ADAM (`colnde_adam_step_dev`) on the 5 K vector, one optimiser after the other (:205-227),
+    each with a fresh state.  Loss scalings: (1, 1, 1, g, g, g) with g = gradient_scaling, or from `training_fractions` through `calculate_loss_scalings`
+    after one forward solve at the initial constants (:114-148; with several starts: the first start's solve).  train_gradient=False zeroes the three
+    gradient terms (loss_mpp, :150-163).
+
+    The reference hands the box lb = 0, ub = 10 in scaled units to the optimisation problem (:197).  Here the scaled parameters are clamped to [s_min, 10]
+    after every update.  The lower edge s_min = 1e-3 is THIS PROJECT'S, not the reference's: dRi = 0 and Pr = 0 are singular (y = (Ri - Ric) / dRi, nu / Pr),
+    so the box cannot be closed at 0.
+
+    starts: [K, 5] initial constant sets fitted side by side (multi-start), every kernel launched once for all K; default: the single set of the keywords.
+    The handle's sub-step count is cfg.substeps raised, if need be, to `colnde_closure_min_substeps` of every initial set with nu0 and nu_minus doubled and
+    Pr no larger than 1 (room for the fit to move; the far corner of the box, 10 x the diffusivities at Pr -> 0, would be needlessly pessimistic).  A set that
+    still leaves the stable regime shows up as a non-finite loss in its own row only.
+
+    cb(parameters [K, 5], total [K], terms [K, 6], optimizer_index, iteration): what the reference's callback logs (:209-223).  Returns MPPOptimisationResult."""
+    import torch
+    from .nde import ClosureColumns, closure_min_substeps
+    cfg, x0, bcs, truth = _problem_arrays(problem)
+    p0 = np.array([[nu0, nu_minus, dRi, Ric, Pr]] if starts is None else starts, dtype=np.float64)
+    if p0.ndim != 2 or p0.shape[1] != 5:
+        raise ValueError("starts: expected shape [K, 5] = (nu0, nu_minus, dRi, Ric, Pr) per start, got %s" % (p0.shape,))
+    if not (p0 > 0).all():
+        raise ValueError("the initial constants must be positive (they scale the optimised parameters)")
+    K = p0.shape[0]
+    need = max(closure_min_substeps(cfg, (2 * r[0], 2 * r[1], r[2], r[3], min(r[4], 1.0))) for r in p0)
+    if need > cfg.substeps:
+        cfg = cfg.with_(substeps=need)
+    eng = ClosureColumns(cfg, len(x0), K, device=device)
+    try:
+        dev = torch.device("cuda", device)
+        t = lambda a: (a if _is_torch_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32))).to(dev).contiguous()
+        eng.set_problem(t(x0), t(bcs), t(truth))
+        p_init = torch.as_tensor(p0.astype(np.float32)).to(dev).contiguous()
+        if training_fractions is None:
+            g = gradient_scaling if train_gradient else 0.0
+            sc = np.array([1, 1, 1, g, g, g], dtype=np.float64)
+        else:
+            terms0 = eng.loss(p_init, [1, 1, 1, 1, 1, 1] if train_gradient else [1, 1, 1, 0, 0, 0])[0, :6].cpu().numpy()
+            sc = calculate_loss_scalings(terms0, training_fractions, train_gradient)
+        if not train_gradient:
+            sc[3:] = 0.0
+        s = torch.ones((K, 5), dtype=torch.float32, device=dev)
+        out = torch.empty((K, 13), dtype=torch.float32, device=dev)
+        hist = []
+        for oi, opt in enumerate(optimizers):
+            m, v = torch.zeros_like(s), torch.zeros_like(s)
+            bt = [opt.beta[0], opt.beta[1]]
+            for it in range(maxiters):
+                p = (s * p_init).contiguous()
+                eng.loss_grad(p, sc, out=out)
+                hist.append(out[:, 5:12].clone())
+                if cb is not None:
+                    o = out.cpu().numpy()
+                    cb(p.cpu().numpy(), o[:, 11], o[:, 5:11], oi, it)
+                gs = (out[:, :5] * p_init).contiguous()                    # dL/ds = p_initial * dL/dp
+                eng.adam_step(s.view(-1), gs.view(-1), m.view(-1), v.view(-1), opt.eta, opt.beta, opt.eps, beta_t=tuple(bt))
+                bt[0] *= opt.beta[0]
+                bt[1] *= opt.beta[1]
+                s.clamp_(float(s_min), 10.0)
+        p = (s * p_init).contiguous()
+        final = eng.loss(p, sc)[:, 6].cpu().numpy()
+        H = torch.stack(hist).cpu().numpy() if hist else np.zeros((0, K, 7), np.float32)
+        params = p.cpu().numpy()
+    finally:
+        eng.close()
+    best = int(np.nanargmin(final)) if np.isfinite(final).any() else 0
+    return MPPOptimisationResult(params, H[:, :, 6], H[:, :, :6], best, sc, final)

@@ -371,6 +371,41 @@ int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const floa
 int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_result, float* d_m, float* d_v, const float* d_eta,
                                   float beta1, float beta2, float eps, float beta1_t, float beta2_t);
 
+/* ---- closure-only model: fitting the five Pacanowski-Philander constants before any network is trained ------------------------------------------------
+ * optimise_modified_pacanowski_philander (wind_mixing/src/diffusivity_parameter_optimisation.jl:35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl
+ * and ..._args.jl) integrates the column ODE WITHOUT the MLPs — DE(x, p, t), :1-33: eps on all three face gradients, nu on interior faces only, boundary faces
+ * -(BC - scaling(0)), nu/Pr for T, Coriolis terms — and differentiates the six-term loss (loss_mpp, :150-163) with respect to nu0, nu_minus, dRi, Ric, Pr; the
+ * fitted constants are the train_parameters of train_NDE_args.jl:175.  That is the wind-mixing RHS with modified_pacanowski_philander = zero_weights = 1 and every
+ * network output zero.  A closure handle is a handle kind of its own: K constant sets on the same columns, every kernel launched once for all K (classical RK4,
+ * `substeps` per save interval, float32; a wavefront per (set, column), a lane per level; exact discrete adjoint from a tape of step-start states; fixed-order
+ * reductions — two launches on the same inputs give the same bits, and row k of a K-set launch equals a one-set launch of set k).
+ * Handle-level calls that accept a closure handle: set_problem[_dev], set_stream, set_global_columns, set_profiling / kernel_time (which = 0, 1, 2) /
+ * reset_kernel_times, describe ("engine=closure sets=K ... tape_bytes=..."), n_params (5), n_models (K), destroy, and colnde_adam_step_dev (any device vector).
+ * Every call that takes a weight vector refuses a closure handle. */
+
+/* The stability bound of colnde_min_substeps for these five constants (params = nu0, nu_minus, dRi, Ric, Pr): D = tau (nu0 + nu_minus) max(1, 1/Pr) / H^2,
+ * whatever cfg's own constants and network fields say.  Returns -1 on an invalid configuration or a non-positive dRi or Pr.  No GPU needed. */
+int colnde_closure_min_substeps(const colnde_config* cfg, const float params[5]);
+/* Create: cfg.model = wind mixing with modified_pacanowski_philander = 1, 4 <= Nz <= 64; layer_sizes, n_layers and activations are ignored, and so are cfg's own
+ * five constants (every solve call brings its sets).  Refused, each with its reason: convective_adjustment, smooth_NN, smooth_Ri, diurnal, inplace_variant, RKC2,
+ * substeps = 0, a forced engine.  The tape (n_sets x n_columns x (n_save - 1) x substeps x 3 Nz floats) is allocated here: a handle that does not fit is refused
+ * with the bytes it needs. */
+int colnde_create_closure(const colnde_config* cfg, int n_sets, colnde_handle** out);
+/* solve(ODEProblem(DE, ...)) of every set (diffusivity_parameter_optimisation.jl:165-170): d_params [K][5] = nu0, nu_minus, dRi, Ric, Pr per set,
+ * d_sol [K][n_col][n_save][3 Nz] (NULL: keep in the handle); device memory, handle's stream, not synchronised */
+int colnde_closure_forward_dev(colnde_handle* h, const float* d_params, float* d_sol);
+/* loss_mpp of every set (:150-163): d_out8 [K][8] = [scaled terms(6); total; 0] */
+int colnde_closure_loss_dev(colnde_handle* h, const float* d_params, const float scalings[6], float* d_out8);
+/* ... and its gradient with respect to the five constants (replaces the AD of OptimizationFunction(loss_mpp, ...), :192-197): d_out [K][13], each row
+ * [dL/dnu0, dL/dnu_minus, dL/ddRi, dL/dRic, dL/dPr; 6 scaled terms; total; 0] — the n_params + 8 layout of colnde_loss_grad_dev, normalised by the global
+ * column count in the same way, so a sharded caller all-reduces it unchanged.  The _dev calls cannot see the values: a set that leaves the stable regime
+ * yields a non-finite row and leaves every other row untouched. */
+int colnde_closure_loss_grad_dev(colnde_handle* h, const float* d_params, const float scalings[6], float* d_out);
+/* the same with host arrays (params [K][5], sol / out as above); they check every set against colnde_closure_min_substeps and refuse, naming the set,
+ * unless COLNDE_ALLOW_UNSTABLE_DT=1; synchronise the stream */
+int colnde_closure_forward(colnde_handle* h, const float* params, float* sol);
+int colnde_closure_loss_grad(colnde_handle* h, const float* params, const float scalings[6], float* out);
+
 /* ---- measurement: HIP-event timing of the handle's kernels on its stream.
  * which: 0 = forward solve kernel, 1 = adjoint kernel, 2 = gradient reduce, 3 = rhs, 4 = inference,
  * 5 = streaming dW1 GEMM (regtile engine only), 6 = convective adjustment, 7 = ADAM step, 8 = implicit diffusion.

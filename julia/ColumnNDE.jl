@@ -410,4 +410,85 @@ function ensemble_adam_step!(h::Handle, dθ::Ptr{Float32}, dresult::Ptr{Float32}
     βᵗ .* β
 end
 
+# ---- the closure without networks: fitting (ν₀, ν₋, ΔRi, Riᶜ, Pr) — wind_mixing/src/diffusivity_parameter_optimisation.jl (DE :1-33,
+# optimise_modified_pacanowski_philander :35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl and ..._args.jl)
+
+"RK4 stability bound for the constants `p = [ν₀, ν₋, ΔRi, Riᶜ, Pr]` (no GPU needed); -1: invalid configuration, ΔRi ≤ 0 or Pr ≤ 0"
+function closure_min_substeps(cfg::Config, save_times::Vector{Float32}, p::Vector{Float32})
+    cfg.n_save = length(save_times)
+    GC.@preserve save_times begin
+        cfg.save_times = pointer(save_times)
+        ccall((:colnde_closure_min_substeps, libcolnde), Cint, (Ref{Config}, Ptr{Float32}), cfg, p)
+    end
+end
+
+"K constant sets on the same columns (the column model WITHOUT the MLPs); cfg's layer fields and its own five constants are ignored"
+function ClosureHandle(cfg::Config, save_times::Vector{Float32}, n_sets::Integer=1)
+    cfg.n_save = length(save_times)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve save_times begin
+        cfg.save_times = pointer(save_times)
+        check(ccall((:colnde_create_closure, libcolnde), Cint, (Ref{Config}, Cint, Ref{Ptr{Cvoid}}), cfg, n_sets, out))
+    end
+    h = Handle(out[], 5, 3cfg.Nz, cfg.n_save, cfg.n_columns, 0)
+    finalizer(x -> ccall((:colnde_destroy, libcolnde), Cvoid, (Ptr{Cvoid},), x.ptr), h)
+end
+
+"solve(prob_NDEs[i], ...; p=unscaled_parameters) for every simulation and set (:119,:152): parameters 5 x K; returns 3Nz x Nt x n_sim x K"
+function closure_solve(h::Handle, parameters::AbstractMatrix{Float32})
+    K = size(parameters, 2)
+    sol = zeros(Float32, h.n_state, h.n_save, h.n_columns, K)
+    check(ccall((:colnde_closure_forward, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, Matrix{Float32}(parameters), sol))
+    sol
+end
+
+"loss_gradient_mpp and its gradient (:165-197): parameters 5 x K; returns 13 x K = [∂L/∂ν₀, ∂ν₋, ∂ΔRi, ∂Riᶜ, ∂Pr; scaled terms(6); total; 0] per column"
+function closure_∇loss(h::Handle, parameters::AbstractMatrix{Float32}, loss_scalings::NamedTuple)
+    sc = Float32[loss_scalings[k] for k in KEYS]
+    out = zeros(Float32, 13, size(parameters, 2))
+    check(ccall((:colnde_closure_loss_grad, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                h.ptr, Matrix{Float32}(parameters), sc, out))
+    out
+end
+
+"device-pointer twins (handle's stream, not synchronised): dp [5 x K], dsol, dout8 [8 x K], dout [13 x K]"
+closure_forward_dev!(h::Handle, dp::Ptr{Float32}, dsol::Ptr{Float32}) =
+    check(ccall((:colnde_closure_forward_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, dp, dsol))
+closure_loss_dev!(h::Handle, dp::Ptr{Float32}, sc::Vector{Float32}, dout8::Ptr{Float32}) =
+    check(ccall((:colnde_closure_loss_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), h.ptr, dp, sc, dout8))
+closure_loss_grad_dev!(h::Handle, dp::Ptr{Float32}, sc::Vector{Float32}, dout::Ptr{Float32}) =
+    check(ccall((:colnde_closure_loss_grad_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), h.ptr, dp, sc, dout))
+
+"""
+optimise_modified_pacanowski_philander (diffusivity_parameter_optimisation.jl:35-231) on a ClosureHandle that already holds the problem
+(`set_problem!`: uvT₀s, BCs, uvT_trains — what the reference builds from train_files, tsteps and n_simulations at :39-108).  `optimizers`: Flux ADAM
+objects (fields eta, beta); the scaled parameters s = p ./ p_initial start from ones (:44-48,:72-73), ∂L/∂s = p_initial .* ∂L/∂p, Flux's ADAM rule on the
+host (5 K numbers), then clamp to [s_min, 10]: the reference's box is lb = 0, ub = 10 (:197); the lower edge s_min = 1f-3 is this project's, because
+ΔRi = 0 and Pr = 0 are singular.  `starts`: 5 x K initial sets fitted side by side.  Returns (parameters 5 x K, losses iterations x K).
+"""
+function optimise_modified_pacanowski_philander(h::Handle, optimizers, maxiters; ν₀=1f-4, ν₋=1f-1, ΔRi=0.1f0, Riᶜ=0.25f0, Pr=1f0,
+                                                train_gradient=true, gradient_scaling=5f-3, loss_scalings=nothing, starts=nothing, s_min=1f-3,
+                                                cb=(args...) -> false)
+    p₀ = starts === nothing ? reshape(Float32[ν₀, ν₋, ΔRi, Riᶜ, Pr], 5, 1) : Matrix{Float32}(starts)
+    g = train_gradient ? Float32(gradient_scaling) : 0f0
+    sc = loss_scalings === nothing ? (u=1f0, v=1f0, T=1f0, ∂u∂z=g, ∂v∂z=g, ∂T∂z=g) : loss_scalings
+    s = ones(Float32, size(p₀))
+    losses = Matrix{Float32}(undef, 0, size(p₀, 2))
+    for (i, opt) in enumerate(optimizers)
+        m, v, βᵗ = zero(s), zero(s), Float32[opt.beta[1], opt.beta[2]]
+        for iter in 1:maxiters
+            out = closure_∇loss(h, s .* p₀, sc)
+            losses = vcat(losses, out[12:12, :])
+            cb(s .* p₀, out[12, :], out[6:11, :], i, iter)
+            ∇s = out[1:5, :] .* p₀
+            m .= opt.beta[1] .* m .+ (1 - opt.beta[1]) .* ∇s
+            v .= opt.beta[2] .* v .+ (1 - opt.beta[2]) .* ∇s .^ 2
+            s .-= opt.eta .* m ./ (1 - βᵗ[1]) ./ (sqrt.(v ./ (1 - βᵗ[2])) .+ 1f-8)
+            βᵗ .*= Float32[opt.beta[1], opt.beta[2]]
+            clamp!(s, s_min, 10f0)
+        end
+    end
+    s .* p₀, losses
+end
+
 end # module
