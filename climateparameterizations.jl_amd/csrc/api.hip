@@ -15,6 +15,7 @@
 #include "engine_fc.h"
 #include "column_ops.h"
 #include "engine_closure.h"
+#include "engine_wm_infer.h"
 
 static thread_local std::string g_err;
 
@@ -2151,6 +2152,122 @@ extern "C" int colnde_implicit_diffusion(colnde_handle* h, const float* u, const
     return rc;
 }
 
+// ---- wind-mixing embedded inference (wind_mixing/src/NDE_oceananigans.jl:288-329, :380-405; engine_wm_infer.hip) ----------------------
+// the handles the kernels cover; fn names the entry point in the refusal
+static bool wm_infer_covers(const colnde_handle* h) {
+    const colnde_config& c = h->cfg;
+    return !h->closure && !h->ensemble && c.model == COLNDE_MODEL_WIND_MIXING && !c.smooth_NN && c.Nz == WM_NZ && c.n_layers == 3 && c.layer_sizes[0] == 3 * WM_NZ &&
+           c.layer_sizes[1] == WM_H1 && c.layer_sizes[2] == WM_H2 && c.layer_sizes[3] == WM_NZ - 1 && c.activations[2] == COLNDE_ACT_IDENTITY;
+}
+static int wm_infer_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, int n_columns) {
+    if (!h) return fail("null handle");
+    const colnde_config& c = h->cfg;
+    if (c.model != COLNDE_MODEL_WIND_MIXING)
+        return fail("%s needs a wind-mixing handle (three flux networks on [u; v; T]); a free-convection handle has colnde_infer_forcing", fn);
+    if (c.smooth_NN)
+        return fail("%s: the embedding has no smoothing filter (NDE_oceananigans.jl:288-329 apply the networks unfiltered), so a handle with smooth_NN is refused", fn);
+    if (!wm_infer_covers(h)) {
+        std::string shape;
+        for (int l = 0; l <= c.n_layers; l++) shape += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
+        return fail("%s covers Nz = 32 with three 96-50-20-31 networks and an identity output layer; this handle has Nz = %d, networks %s, output activation %d", fn,
+                    c.Nz, shape.c_str(), c.activations[c.n_layers - 1]);
+    }
+    for (int i = 0; i < n_ptrs; i++)
+        if (!ptrs[i]) return fail("null pointer argument");
+    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
+    return 0;
+}
+static void wm_infer_args(const colnde_handle* h, WmInferArgs* a) {
+    for (int i = 0; i < 6; i++) { a->mu[i] = h->cfg.mu[i]; a->sigma[i] = h->cfg.sigma[i]; }
+    a->act1 = h->cfg.activations[0];
+    a->act2 = h->cfg.activations[1];
+}
+
+extern "C" int colnde_wm_infer_dz_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                                           const float* d_top_flux, float Lz, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[8] = {d_weights, d_u, d_v, d_T, d_top_flux, d_dz_uw, d_dz_vw, d_dz_wT};
+    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    WmInferArgs a = {};
+    wm_infer_args(h, &a);
+    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.Lz = Lz;
+    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT; a.n_col = n_columns; a.fused = false;
+    Timed tm(h, K_INFER);
+    hipError_t e = launch_wm_infer(a, h->stream);
+    if (e != hipSuccess) return fail("wm_infer launch failed: %s (the state and output arrays must be 16-byte aligned)", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_wm_embedded_step_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                                           const float* d_top_flux, const float* d_halo_bottom, float Lz, float dt, const float params[7],
+                                           int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out,
+                                           float* d_T_out, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[8] = {d_weights, d_u, d_v, d_T, d_top_flux, d_dz_uw, d_dz_vw, d_dz_wT};
+    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
+    if (impl_diff_check(h, d_u, d_v, d_T, d_u_out, d_v_out, d_T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    WmInferArgs a = {};
+    wm_infer_args(h, &a);
+    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.Lz = Lz;
+    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT; a.n_col = n_columns; a.fused = true;
+    a.halo_bottom = d_halo_bottom;
+    a.mpp = mpp_params(params, dt, Lz / (float)WM_NZ, convective_adjustment);
+    a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
+    Timed tm(h, K_INFER);
+    hipError_t e = launch_wm_infer(a, h->stream);
+    if (e != hipSuccess) return fail("wm_embedded_step launch failed: %s (the state and output arrays must be 16-byte aligned)", hipGetErrorString(e));
+    return 0;
+}
+
+// host arrays: one scratch of [u | v | T | dz_uw | dz_vw | dz_wT | top(3 n) | halo(3 n)], the step in place on its first three blocks
+static int wm_infer_host(colnde_handle* h, const char* fn, bool fused, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                         const float* halo_bottom, float Lz, float dt, const float* params, int ca, float* dz_uw, float* dz_vw, float* dz_wT, float* u_out,
+                         float* v_out, float* T_out, int n_columns) {
+    const void* const ptrs[8] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT};
+    if (wm_infer_check(h, fn, ptrs, 8, Lz, n_columns)) return 1;
+    if (fused && impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nf = (size_t)n_columns * WM_NZ, nh = (size_t)n_columns;
+    float* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, (6 * nf + 6 * nh) * sizeof(float)));
+    int rc = 1;
+    do {
+        const float* srcs[3] = {u, v, T};
+        bool ok = hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        for (int f = 0; f < 3 && ok; f++) ok = hipMemcpyAsync(d + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(d + 6 * nf, top_flux, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok && fused && halo_bottom) ok = hipMemcpyAsync(d + 6 * nf + 3 * nh, halo_bottom, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (!ok) { fail("%s: host-to-device copy failed", fn); break; }
+        if (fused) {
+            if (colnde_wm_embedded_step_dev(h, h->d_w, d, d + nf, d + 2 * nf, d + 6 * nf, halo_bottom ? d + 6 * nf + 3 * nh : nullptr, Lz, dt, params, ca,
+                                            d + 3 * nf, d + 4 * nf, d + 5 * nf, d, d + nf, d + 2 * nf, n_columns)) break;
+        } else if (colnde_wm_infer_dz_flux_dev(h, h->d_w, d, d + nf, d + 2 * nf, d + 6 * nf, Lz, d + 3 * nf, d + 4 * nf, d + 5 * nf, n_columns)) break;
+        float* dsts[6] = {u_out, v_out, T_out, dz_uw, dz_vw, dz_wT};
+        for (int f = fused ? 0 : 3; f < 6 && ok; f++) ok = hipMemcpyAsync(dsts[f], d + f * nf, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("%s: device-to-host copy failed", fn); break; }
+        rc = 0;
+    } while (0);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int colnde_wm_infer_dz_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux, float Lz,
+                                       float* dz_uw, float* dz_vw, float* dz_wT, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    return wm_infer_host(h, __func__, false, weights, u, v, T, top_flux, nullptr, Lz, 0.0f, nullptr, 0, dz_uw, dz_vw, dz_wT, nullptr, nullptr, nullptr, n_columns);
+}
+
+extern "C" int colnde_wm_embedded_step(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                                       const float* halo_bottom, float Lz, float dt, const float params[7], int convective_adjustment, float* dz_uw,
+                                       float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    return wm_infer_host(h, __func__, true, weights, u, v, T, top_flux, halo_bottom, Lz, dt, params, convective_adjustment, dz_uw, dz_vw, dz_wT, u_out, v_out,
+                         T_out, n_columns);
+}
+
 extern "C" int colnde_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_grad, float* d_m, float* d_v, float eta,
                                     float beta1, float beta2, float eps, float beta1_t, float beta2_t, int n) {
     if (!h) return fail("null handle");
@@ -2320,6 +2437,7 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
     snprintf(t, sizeof t, " matrix_arithmetic=%s forward=%s adjoint=%s dw=%s", h->cfg.matrix_arithmetic == COLNDE_MATRIX_BF16X3_EXACT ? "bf16x3_exact" : "f32_mfma",
              (info[7] & 2) ? "bf16x3" : "f32", (info[7] & 4) ? "bf16x3" : "f32", (info[7] & 8) ? "bf16x3" : "f32");
     s += t;
+    if (wm_infer_covers(h)) s += " wm_infer=f32";      // colnde_wm_infer_dz_flux / colnde_wm_embedded_step: the f32 matrix pipe under either arithmetic
     if (info[1]) { snprintf(t, sizeof t, " block=%dx%d", info[1], info[2]); s += t; } else s += " block=(not planned yet)";
     if (info[0] == COLNDE_ENGINE_MFMA) { snprintf(t, sizeof t, " z1_tape=%d", info[3]); s += t; }
     if (info[0] == COLNDE_ENGINE_FC32) { snprintf(t, sizeof t, " time_segments=%d tile_width=%d dw_slices=%d", info[3], h->fc_cw, info[5]); s += t; }

@@ -1,5 +1,6 @@
 // column_ops.hip — gfx950 kernels for the steps either side of the NDE hot path.
 #include "column_ops.h"
+#include "mpp_sweep.h"
 
 // ------------------------------------------------------------------------------------------------
 // convective_adjustment!(model, Δt, K): free_convection/double_gyre_nn.jl:27-62 (3-D), free_convection/src/oceananigans_nn.jl:13-40
@@ -281,17 +282,6 @@ hipError_t launch_zscore_scale(const float* x, long count, const float* mu_sigma
 // system goes first: its sweep forms the face diffusivities from the still-unmodified u, v and keeps c·ν for the velocity sweep.
 // ------------------------------------------------------------------------------------------------
 typedef float co_f32x4 __attribute__((ext_vector_type(4)));
-struct MppParams { float nu0, nu_minus, inv_dRi, Ric, inv_Pr, galpha_dz, c; int ca; };
-
-// c·ν and c·νT of face k (1 <= k < Nz) from the level differences across it (du, dv, dT = upper − lower)
-__device__ __forceinline__ void mpp_face(const MppParams& P, float du, float dv, float dT, float& kv, float& kT) {
-    const float Ri = P.galpha_dz * dT / (du * du + dv * dv);
-    const float x = (Ri - P.Ric) * P.inv_dRi;
-    const float nu = P.nu0 + P.nu_minus * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x));
-    kv = P.c * nu;
-    kT = P.ca ? (Ri > 0.0f ? kv * P.inv_Pr : P.c) : kv * P.inv_Pr;
-}
-
 template <int NZ>
 __global__ void __launch_bounds__(64) mpp_diffusion_kernel(const float* u, const float* v, const float* T,
                                                            const float* __restrict__ halo_bottom, MppParams P, float* uo, float* vo, float* To, int n_col) {
@@ -332,61 +322,7 @@ __global__ void __launch_bounds__(64) mpp_diffusion_kernel(const float* u, const
     __syncthreads();
     if (lane < ncol) {
         float* tu = cs_smem + lane * LD;
-        float* tv = tu + FS;
-        float* tT = tv + FS;
-        float kvs[NZ], cp[NZ];
-        // face 0: ν = 0; νT under convective adjustment from the Richardson number the halo cells give (absent: zero-gradient fill,
-        // 0/0 = NaN, `NaN > 0` false: νT = 1 — what the reference computes for a flux-bounded field)
-        float u_lo = tu[0], v_lo = tv[0], T_lo = tT[0];
-        const float T_bottom = T_lo;
-        float kT_k = 0.0f;
-        kvs[0] = 0.0f;
-        if (P.ca) {
-            const size_t c = (size_t)col0 + lane;
-            const float du = halo_bottom ? u_lo - halo_bottom[c] : 0.0f;
-            const float dv = halo_bottom ? v_lo - halo_bottom[(size_t)n_col + c] : 0.0f;
-            const float dT = halo_bottom ? T_lo - halo_bottom[2 * (size_t)n_col + c] : 0.0f;
-            const float Ri0 = P.galpha_dz * dT / (du * du + dv * dv);
-            kT_k = Ri0 > 0.0f ? 0.0f : P.c;
-        }
-        // ---- T system, forming the faces one ahead of the elimination
-        float xT = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NZ; k++) {
-            float kT_n = 0.0f;
-            const float T_k = T_lo;
-            if (k + 1 < NZ) {
-                const float u_hi = tu[k + 1], v_hi = tv[k + 1], T_hi = tT[k + 1];
-                mpp_face(P, u_hi - u_lo, v_hi - v_lo, T_hi - T_lo, kvs[k + 1], kT_n);
-                u_lo = u_hi; v_lo = v_hi; T_lo = T_hi;
-            }
-            const float a = -kT_k, b = 1.0f + kT_k + kT_n;
-            const float inv = 1.0f / (k == 0 ? b : b - a * cp[k - 1]);
-            cp[k] = -kT_n * inv;
-            xT = (k == 0 ? T_k : T_k - a * xT) * inv;
-            tT[k] = xT;
-            kT_k = kT_n;
-        }
-#pragma unroll
-        for (int k = NZ - 2; k >= 0; k--) { xT = tT[k] - cp[k] * xT; tT[k] = xT; }
-        tT[0] = T_bottom;
-        // ---- velocity system, two right-hand sides
-        float xu = 0.0f, xv = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NZ; k++) {
-            const float kn = k + 1 < NZ ? kvs[k + 1] : 0.0f;
-            const float a = -kvs[k], b = 1.0f + kvs[k] + kn;
-            const float inv = 1.0f / (k == 0 ? b : b - a * cp[k - 1]);
-            cp[k] = -kn * inv;
-            xu = (k == 0 ? tu[k] : tu[k] - a * xu) * inv;
-            xv = (k == 0 ? tv[k] : tv[k] - a * xv) * inv;
-            tu[k] = xu; tv[k] = xv;
-        }
-#pragma unroll
-        for (int k = NZ - 2; k >= 0; k--) {
-            xu = tu[k] - cp[k] * xu; tu[k] = xu;
-            xv = tv[k] - cp[k] * xv; tv[k] = xv;
-        }
+        mpp_column_step<NZ>(P, tu, tu + FS, tu + 2 * FS, halo_bottom, (size_t)col0 + lane, n_col);
     }
     __syncthreads();
     if (ncol == 64) {
@@ -461,11 +397,7 @@ hipError_t launch_mpp_diffusion(const float* u, const float* v, const float* T, 
                                 const float params[7], int convective_adjustment, float* uo, float* vo, float* To, int Nz, int n_col,
                                 hipStream_t stream) {
     if (Nz < 2 || Nz > 128 || n_col < 1) return hipErrorInvalidValue;
-    MppParams P;
-    P.nu0 = params[0]; P.nu_minus = params[1]; P.inv_dRi = 1.0f / params[2]; P.Ric = params[3]; P.inv_Pr = 1.0f / params[4];
-    P.galpha_dz = params[5] * params[6] * dz;       // ∂z b / ((∂z u)² + (∂z v)²) = gα ΔT Δz / (Δu² + Δv²)
-    P.c = dt / (dz * dz);
-    P.ca = convective_adjustment ? 1 : 0;
+    const MppParams P = mpp_params(params, dt, dz, convective_adjustment);
     const dim3 grid((n_col + 63) / 64), block(64);
     const bool aligned = (((uintptr_t)u | (uintptr_t)v | (uintptr_t)T | (uintptr_t)uo | (uintptr_t)vo | (uintptr_t)To) & 15) == 0;
     // in-place use is allowed field by field (uo == u etc.); any other overlap between the six arrays is the caller's error

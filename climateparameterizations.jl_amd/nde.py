@@ -34,6 +34,52 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _span(a):
+    """(address, bytes) of a numpy array or a torch tensor."""
+    if _is_torch(a):
+        return a.data_ptr(), a.numel() * a.element_size()
+    return a.ctypes.data, a.nbytes
+
+
+def check_wm_embed_arrays(Nz: int, n: int, state, top_flux, halo_bottom=None, dz_out=None, out=None):
+    """Shape and alias rules of `wm_infer_dz_flux` / `wm_embedded_step` (no GPU needed): state = (u, v, T) each [n, Nz], top_flux [3, n],
+    halo_bottom [3, n] or None, dz_out = three [n, Nz] arrays that overlap NOTHING, out = three [n, Nz] arrays each of which may be
+    exactly its own input (in place) and overlaps nothing else."""
+    names = ("u", "v", "T")
+    if len(state) != 3:
+        raise ValueError("state must be (u, v, T)")
+    for nm, a in zip(names, state):
+        if tuple(a.shape) != (n, Nz):
+            raise ValueError("%s: expected shape %s, got %s" % (nm, (n, Nz), tuple(a.shape)))
+    if tuple(top_flux.shape) != (3, n):
+        raise ValueError("top_flux: expected shape %s (uw, vw, wT at the top face), got %s" % ((3, n), tuple(top_flux.shape)))
+    if halo_bottom is not None and tuple(halo_bottom.shape) != (3, n):
+        raise ValueError("halo_bottom: expected shape %s, got %s" % ((3, n), tuple(halo_bottom.shape)))
+    inputs = [(nm, a) for nm, a in zip(names, state)] + [("top_flux", top_flux)] + ([("halo_bottom", halo_bottom)] if halo_bottom is not None else [])
+    outputs = []
+    for label, arrs, tags in (("dz_out", dz_out, ("dz_uw", "dz_vw", "dz_wT")), ("out", out, ("u_out", "v_out", "T_out"))):
+        if arrs is None:
+            continue
+        if len(arrs) != 3:
+            raise ValueError("%s must be three arrays" % label)
+        for tg, a in zip(tags, arrs):
+            if tuple(a.shape) != (n, Nz):
+                raise ValueError("%s: expected shape %s, got %s" % (tg, (n, Nz), tuple(a.shape)))
+            outputs.append((tg, a))
+
+    def overlap(a, b):
+        (pa, na), (pb, nb) = _span(a), _span(b)
+        return pa < pb + nb and pb < pa + na
+    own = {"u_out": "u", "v_out": "v", "T_out": "T"}
+    for i, (to, o) in enumerate(outputs):
+        for ti, a in inputs:
+            if overlap(o, a) and not (own.get(to) == ti and _span(o) == _span(a)):
+                raise ValueError("%s overlaps %s: the dz arrays may alias nothing, an output only its own input (in place)" % (to, ti))
+        for tj, b in outputs[i + 1:]:
+            if overlap(o, b):
+                raise ValueError("%s overlaps %s" % (to, tj))
+
+
 def min_substeps(cfg: NDEConfig) -> int:
     """`colnde_min_substeps`: the least RK4 sub-steps per save interval inside the diffusive stability bound (no GPU needed)."""
     c, keep = to_c_config(cfg, 1, 0, 0)
@@ -431,6 +477,69 @@ class ColumnNDE:
         _lib.check(self._L.colnde_implicit_diffusion(self._h, _ptr(u), _ptr(v), _ptr(T), _ptr(hb), float(dt), float(dz), pr,
                                                      int(bool(convective_adjustment)), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), n))
         return res
+
+    def wm_infer_dz_flux(self, weights, u, v, T, top_flux, Lz: float, dz_out=None):
+        """`NN_uw_forcing`, `NN_vw_forcing`, `NN_wT_forcing` (wind_mixing/src/NDE_oceananigans.jl:288-329) as `progress_neural_network`
+        stores them (:393-400): (∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN), each [n][Nz] = +∂z(flux); the forcing is its negative.  u, v, T [n][Nz]
+        in the ocean model's units (k = 0 deepest), top_flux [3][n] = uw, vw, wT at the top face.  numpy arrays or device tensors
+        (`dz_out`: three device tensors that alias nothing)."""
+        return self._wm_embed(weights, u, v, T, top_flux, Lz, dz_out, None)
+
+    def wm_embedded_step(self, weights, u, v, T, top_flux, Lz: float, dt: float, params, convective_adjustment: bool = False, halo_bottom=None,
+                         dz_out=None, out=None):
+        """`progress_neural_network` (wind_mixing/src/NDE_oceananigans.jl:380-405) in one launch: the three ∂z arrays of the state AS
+        GIVEN, then `modified_pacanowski_philander!` on that state (Δz = Lz/Nz; params, halo_bottom as `implicit_diffusion`).
+        Returns ((∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN), (u′, v′, T′)); `out` tensors may be their own inputs (in place)."""
+        return self._wm_embed(weights, u, v, T, top_flux, Lz, dz_out, (float(dt), params, bool(convective_adjustment), halo_bottom, out))
+
+    def _wm_embed(self, weights, u, v, T, top_flux, Lz, dz_out, step):
+        Nz = self.cfg.Nz
+        dt, params, ca, halo_bottom, out = step if step is not None else (0.0, None, False, None, None)
+        pr = (ctypes.c_float * 7)(*[float(x) for x in params]) if step is not None else None
+        if _is_torch(T):
+            import torch
+            n = T.shape[0]
+            check_wm_embed_arrays(Nz, n, (u, v, T), top_flux, halo_bottom, dz_out, out)
+            for a in (u, v, T):
+                self._chk_dev(a, (n, Nz))
+            self._chk_dev(top_flux, (3, n))
+            self._chk_dev(weights, (self.n_params,))
+            if halo_bottom is not None:
+                self._chk_dev(halo_bottom, (3, n))
+            if dz_out is None:
+                dz_out = tuple(torch.empty_like(T) for _ in range(3))
+            if step is not None and out is None:
+                out = tuple(torch.empty_like(T) for _ in range(3))
+            for a in tuple(dz_out) + (tuple(out) if step is not None else ()):
+                self._chk_dev(a, (n, Nz))
+            self.use_torch_stream()
+            if step is None:
+                _lib.check(self._L.colnde_wm_infer_dz_flux_dev(self._h, weights.data_ptr(), u.data_ptr(), v.data_ptr(), T.data_ptr(), top_flux.data_ptr(),
+                                                               float(Lz), dz_out[0].data_ptr(), dz_out[1].data_ptr(), dz_out[2].data_ptr(), n))
+                return tuple(dz_out)
+            _lib.check(self._L.colnde_wm_embedded_step_dev(
+                self._h, weights.data_ptr(), u.data_ptr(), v.data_ptr(), T.data_ptr(), top_flux.data_ptr(),
+                halo_bottom.data_ptr() if halo_bottom is not None else None, float(Lz), dt, pr, int(ca), dz_out[0].data_ptr(), dz_out[1].data_ptr(),
+                dz_out[2].data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), n))
+            return tuple(dz_out), tuple(out)
+        if dz_out is not None or out is not None:
+            raise ValueError("dz_out / out are for device tensors; host arrays are returned")
+        T = _f32(T)
+        n = T.shape[0]
+        u, v, T = _f32(u), _f32(v), _f32(T)
+        top_flux = _f32(top_flux)
+        hb = _f32(halo_bottom) if halo_bottom is not None else None
+        check_wm_embed_arrays(Nz, n, (u, v, T), top_flux, hb)
+        w = _f32(weights, (self.n_params,))
+        dz = tuple(np.empty_like(T) for _ in range(3))
+        if step is None:
+            _lib.check(self._L.colnde_wm_infer_dz_flux(self._h, _ptr(w), _ptr(u), _ptr(v), _ptr(T), _ptr(top_flux), float(Lz), _ptr(dz[0]), _ptr(dz[1]),
+                                                       _ptr(dz[2]), n))
+            return dz
+        res = tuple(np.empty_like(T) for _ in range(3))
+        _lib.check(self._L.colnde_wm_embedded_step(self._h, _ptr(w), _ptr(u), _ptr(v), _ptr(T), _ptr(top_flux), _ptr(hb), float(Lz), dt, pr, int(ca),
+                                                   _ptr(dz[0]), _ptr(dz[1]), _ptr(dz[2]), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), n))
+        return dz, res
 
     def adam_step(self, weights, grad, m, v, eta: float, beta=(0.9, 0.999), eps: float = 1e-8, beta_t=None):
         """One fused `Flux.Optimise.ADAM` apply!/update! on device vectors (in place).  beta_t = running powers (β₁ᵗ, β₂ᵗ)."""

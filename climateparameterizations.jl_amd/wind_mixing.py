@@ -353,6 +353,43 @@ def train_NN(engine: ColumnNDE, NN_type: str, weights, profiles, BCs, fluxes, op
     return theta.cpu().numpy(), hist
 
 
+def _named(d, *names):
+    for nm in names:
+        if isinstance(d, dict) and nm in d:
+            return float(d[nm])
+        if not isinstance(d, dict) and hasattr(d, nm):
+            return float(getattr(d, nm))
+    raise KeyError(names[0])
+
+
+def NN_forcings(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz: float):
+    """`NN_uw_forcing`, `NN_vw_forcing`, `NN_wT_forcing` (wind_mixing/src/NDE_oceananigans.jl:288-329) as the ocean model applies them
+    (`- p.∂z_uw_NN[k]`, :333, :338, :343): the three forcings [n, Nz] (or [Nz]) of `interior(u)`, `interior(v)`, `interior(T)` in the
+    model's units.  top_fluxes = (uw_flux, vw_flux, wT_flux) at the top face: scalars or [n] arrays ([3, n]); a diurnal wT_flux(t) is
+    passed as its value at t."""
+    u, v, T = (np.asarray(a, dtype=np.float32) for a in (u, v, T))
+    shape = T.shape
+    u2, v2, T2 = (a.reshape(-1, shape[-1]) for a in (u, v, T))
+    top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_fluxes, np.float32).reshape(3, -1), (3, T2.shape[0])))
+    return tuple(-d.reshape(shape) for d in engine.wm_infer_dz_flux(weights, u2, v2, T2, top, Lz))
+
+
+def progress_neural_network(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz: float, dt: float, p: dict, constants,
+                            convective_adjustment: bool = False, halo_bottom=None):
+    """One iteration of `progress_neural_network` (wind_mixing/src/NDE_oceananigans.jl:380-405): the stored `∂z_uw_NN`, `∂z_vw_NN`,
+    `∂z_wT_NN` of the state as given, then `modified_pacanowski_philander!` on it.  `p`, `constants`, halo_bottom as
+    `modified_pacanowski_philander_step`; top_fluxes as `NN_forcings`.  Returns ((∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN), (u′, v′, T′))."""
+    params = (_named(p, "ν₀", "nu0"), _named(p, "ν₋", "nu_minus"), _named(p, "ΔRi", "dRi"), _named(p, "Riᶜ", "Ric"), _named(p, "Pr"),
+              _named(constants, "α", "alpha"), _named(constants, "g"))
+    u, v, T = (np.asarray(a, dtype=np.float32) for a in (u, v, T))
+    shape = T.shape
+    u2, v2, T2 = (a.reshape(-1, shape[-1]) for a in (u, v, T))
+    top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_fluxes, np.float32).reshape(3, -1), (3, T2.shape[0])))
+    hb = None if halo_bottom is None else np.asarray(halo_bottom, np.float32).reshape(3, -1)
+    dz, st = engine.wm_embedded_step(weights, u2, v2, T2, top, Lz, dt, params, convective_adjustment, hb)
+    return tuple(d.reshape(shape) for d in dz), tuple(a.reshape(shape) for a in st)
+
+
 def modified_pacanowski_philander_step(engine: ColumnNDE, u, v, T, dt: float, dz: float, p: dict, constants, convective_adjustment: bool = False,
                                        halo_bottom=None):
     """`modified_pacanowski_philander!(model, constants, Δt, p, convective_adjustment)` (wind_mixing/src/NDE_oceananigans.jl:61-101;

@@ -269,6 +269,36 @@ int colnde_implicit_diffusion_dev(colnde_handle* h, const float* d_u, const floa
                                   float dt, float dz, const float params[7], int convective_adjustment, float* d_u_out, float* d_v_out,
                                   float* d_T_out, int n_columns);
 
+/* NN_uw_forcing / NN_vw_forcing / NN_wT_forcing (wind_mixing/src/NDE_oceananigans.jl:288-329) as progress_neural_network stores them every
+ * iteration of the 1-D embedding (:393-400): the three trained flux networks on an ocean column's u, v, T.  Per column, with
+ * x = [(u−μ_u)/σ_u; (v−μ_v)/σ_v; (T−μ_T)/σ_T] and y = net_k(x) (Nz−1 values):
+ *   uw, vw (:288-304): a = σ y + μ, interior faces a .− (σ a[1] + μ) — the reference applies inv(scaling) a SECOND time to the already
+ *           unscaled first element (`uw .- inv(uw_scaling).(uw[1])`, sic); this is NOT the inv(scaling)(0) of training and is mirrored as written;
+ *   wT (:315-329): interior faces σ_wT (y .− y[1]), so the first interior face is exactly 0;
+ *   faces [0; interior; top_flux] (:220-224), output in cell k = (F[k+1] − F[k])/Δz (:193-218), Δz = Lz/Nz.
+ * u, v, T: [n_col][Nz] in the ocean model's units, k = 0 deepest (as colnde_implicit_diffusion); top_flux: [3][n_col] = uw, vw, wT at the
+ * top face in physical units (a diurnal wT_flux(t), :323-329, is passed as its value at t); outputs each [n_col][Nz] = +∂z(flux) — the
+ * forcing is its negative (:333, :338, :343) — and may alias nothing.  n_columns is independent of the handle's own column count.  All
+ * state and output arrays 16-byte aligned.  No smoothing filter and none of the training `conditions` enter: a handle with smooth_NN is
+ * refused, the other flags do not matter.  Single-model wind-mixing handles with Nz = 32 and three 96-50-20-31 networks (any hidden
+ * activation, identity output) only; anything else is refused with the reason.  The dense chains run on the f32 matrix pipe under either
+ * matrix_arithmetic (colnde_describe: wm_infer=f32); timed under colnde_kernel_time slot 4. */
+int colnde_wm_infer_dz_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                                const float* d_top_flux, float Lz, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, int n_columns);
+int colnde_wm_infer_dz_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                            float Lz, float* dz_uw, float* dz_vw, float* dz_wT, int n_columns);   /* host arrays; synchronises */
+
+/* progress_neural_network (wind_mixing/src/NDE_oceananigans.jl:380-405) in one launch: the three ∂z arrays above from the state AS GIVEN,
+ * then modified_pacanowski_philander! (:61-101; colnde_implicit_diffusion with dz = Lz/Nz) on that state.  halo_bottom, params and
+ * convective_adjustment as colnde_implicit_diffusion; u_out, v_out, T_out may each alias its own input, the ∂z arrays nothing. */
+int colnde_wm_embedded_step_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                                const float* d_top_flux, const float* d_halo_bottom, float Lz, float dt, const float params[7],
+                                int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out,
+                                float* d_T_out, int n_columns);
+int colnde_wm_embedded_step(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                            const float* halo_bottom, float Lz, float dt, const float params[7], int convective_adjustment, float* dz_uw,
+                            float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, int n_columns);
+
 /* Flux.Optimise.ADAM apply! + update! (Flux 0.11.6 src/optimise/optimisers.jl; used at wind_mixing/src/NDE_training.jl:340-372,
  * free_convection/src/training.jl:71) on device vectors of n floats: m ← β₁m + (1-β₁)g, v ← β₂v + (1-β₂)g²,
  * w ← w - η·m/(1-β₁ᵗ)/(√(v/(1-β₂ᵗ)) + ϵ).  beta1_t / beta2_t are the running powers the optimiser state carries (β₁, β₂ on the

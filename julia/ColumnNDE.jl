@@ -338,6 +338,31 @@ function modified_pacanowski_philander!(h::Handle, u::Matrix{Float32}, v::Matrix
     nothing
 end
 
+"NN_uw_forcing, NN_vw_forcing, NN_wT_forcing (wind_mixing/src/NDE_oceananigans.jl:288-329) of every column: u, v, T as (Nz, n_columns)
+matrices in the ocean model's units, top_fluxes (n_columns, 3) column-major = C-order [3][n_columns] (uw, vw, wT at the top face; a diurnal
+wT_flux(t) as its value at t).  Returns the three forcings −∂z(flux) (:333, :338, :343)"
+function NN_forcings(h::Handle, θ::Vector{Float32}, u::Matrix{Float32}, v::Matrix{Float32}, T::Matrix{Float32}, top_fluxes::Matrix{Float32}, Lz)
+    ∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN = similar(T), similar(T), similar(T)
+    check(ccall((:colnde_wm_infer_dz_flux, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint),
+        h.ptr, θ, u, v, T, top_fluxes, Lz, ∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN, size(T, 2)))
+    (-∂z_uw_NN, -∂z_vw_NN, -∂z_wT_NN)
+end
+
+"progress_neural_network(simulation) — wind_mixing/src/NDE_oceananigans.jl:380-405: fills ∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN from the state as
+given, then modified_pacanowski_philander! on u, v, T in place (Δz = Lz/Nz); `p`, `constants`, halo_bottom as modified_pacanowski_philander!"
+function progress_neural_network(h::Handle, θ::Vector{Float32}, u::Matrix{Float32}, v::Matrix{Float32}, T::Matrix{Float32},
+                                 top_fluxes::Matrix{Float32}, Lz, constants, Δt, p, convective_adjustment,
+                                 ∂z_uw_NN::Matrix{Float32}, ∂z_vw_NN::Matrix{Float32}, ∂z_wT_NN::Matrix{Float32}; halo_bottom=nothing)
+    params = Float32[p["ν₀"], p["ν₋"], p["ΔRi"], p["Riᶜ"], p["Pr"], constants.α, constants.g]
+    hb = halo_bottom === nothing ? C_NULL : pointer(halo_bottom)
+    GC.@preserve halo_bottom check(ccall((:colnde_wm_embedded_step, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Ptr{Float32}, Cint,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint),
+        h.ptr, θ, u, v, T, top_fluxes, hb, Lz, Δt, params, convective_adjustment ? 1 : 0, ∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN, u, v, T, size(T, 2)))
+    nothing
+end
+
 "Flux.Optimise.ADAM apply!/update! on device pointers (θ, ∇, m, v resident on the GPU); βᵗ = running powers kept by the caller"
 function adam_step!(h::Handle, dθ::Ptr{Float32}, dg::Ptr{Float32}, dm::Ptr{Float32}, dv::Ptr{Float32}, η, β, ϵ, βᵗ, n)
     check(ccall((:colnde_adam_step_dev, libcolnde), Cint,
