@@ -57,6 +57,10 @@ SYMBOLS = [
     ("colnde_wm_infer_dz_flux_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, _V, _V, _V, ctypes.c_int]),
     ("colnde_wm_embedded_step", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _F, ctypes.c_int, _V, _V, _V, _V, _V, _V, ctypes.c_int]),
     ("colnde_wm_embedded_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _F, ctypes.c_int, _V, _V, _V, _V, _V, _V, ctypes.c_int]),
+    ("colnde_fc_embedded_step", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, ctypes.c_float, _V, _V, _V, ctypes.c_int]),
+    ("colnde_fc_embedded_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, ctypes.c_float, _V, _V, _V, ctypes.c_int]),
+    ("colnde_fc_diagnose_wT", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _V, ctypes.c_int]),
+    ("colnde_fc_diagnose_wT_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _V, ctypes.c_int]),
     ("colnde_adam_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V] + [ctypes.c_float] * 6 + [ctypes.c_int]),
     ("colnde_pretrain_flux_dev", ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V, _V, _V, _V, ctypes.c_int] + [ctypes.c_float] * 5 +
      [ctypes.POINTER(ctypes.c_double), ctypes.c_int, _F]),

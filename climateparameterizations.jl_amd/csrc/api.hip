@@ -16,6 +16,7 @@
 #include "column_ops.h"
 #include "engine_closure.h"
 #include "engine_wm_infer.h"
+#include "engine_fc_embed.h"
 
 static thread_local std::string g_err;
 
@@ -49,7 +50,7 @@ extern "C" int colnde_internal_set_error(const char* msg) { g_err = msg ? msg : 
         if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1 = 5, K_CONVADJ = 6, K_ADAM = 7, K_IMPLDIFF = 8, K_COUNT = 9 };
+enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1 = 5, K_CONVADJ = 6, K_ADAM = 7, K_IMPLDIFF = 8, K_FCEMBED = 9, K_COUNT = 10 };
 
 struct PendingEvent { hipEvent_t a, b; int which; };
 
@@ -76,6 +77,7 @@ struct colnde_handle {
     bool sp_fwd = true, sp_adj = true, sp_dw = true;   // matrix arithmetic of the forward-solve / adjoint / weight-gradient kernels: exact three-way bf16 split (true) or
                                                       // f32 MFMA — cfg.matrix_arithmetic with the test overrides COLNDE_{FWD,ADJ,DW}_SPLIT (resolve_arithmetic)
     bool use_fc = false;            // 32-column free-convection engine (engine_fc.hip: Nz = 32 | 64, the reference's relu network, RK4)
+    bool fce_ready = false;         // colnde_fc_embedded_step / colnde_fc_diagnose_wT: images allocated, LDS limits raised (first call)
     float *d_fc_imgf = nullptr, *d_fc_imgb = nullptr, *d_fc_bias = nullptr;
     unsigned int *d_fc_simgf = nullptr, *d_fc_simgb = nullptr;   // the split operand images (COLNDE_MATRIX_BF16X3_EXACT; 32-column tiles)
     unsigned int* d_fc_masks = nullptr;
@@ -2268,6 +2270,136 @@ extern "C" int colnde_wm_embedded_step(colnde_handle* h, const float* weights, c
                          T_out, n_columns);
 }
 
+// ---- free-convection embedded step (free_convection/src/oceananigans_nn.jl:100-118, :153-165; engine_fc_embed.hip) ----------------------
+// the handles the kernels cover: the network shapes of fc32 (fc_supported), whatever engine and stepper the handle trains with
+static bool fce_covers(const colnde_handle* h) {
+    const DevModel& m = h->m;
+    return !h->closure && !h->ensemble && !h->ag_rows && (m.model == COLNDE_MODEL_FREE_CONVECTION || m.model == COLNDE_MODEL_CONV_ADJ_NDE) &&
+           (m.Nz == 32 || m.Nz == 64) && m.n_layers == 3 && m.n_nets == 1 && m.sizes[0] == m.Nz && m.sizes[1] == 4 * m.Nz && m.sizes[2] == 4 * m.Nz &&
+           m.sizes[3] == m.Nz - 1 && m.acts[0] == COLNDE_ACT_RELU && m.acts[1] == COLNDE_ACT_RELU && m.acts[2] == COLNDE_ACT_IDENTITY;
+}
+static int fce_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, float K, int n_columns) {
+    if (!h) return fail("null handle");
+    const colnde_config& c = h->cfg;
+    if (c.model == COLNDE_MODEL_WIND_MIXING)
+        return fail("%s needs a free-convection handle (one network on T); a wind-mixing handle has colnde_wm_embedded_step", fn);
+    if (h->ag_rows) return fail("%s: this handle's network keeps its activation rows in global memory (a wide network); the embedded step covers the fc32 shapes only", fn);
+    if (c.Nz != 32 && c.Nz != 64) return fail("%s covers Nz = 32 or 64 (this handle has Nz = %d)", fn, c.Nz);
+    if (!fce_covers(h)) {
+        std::string shape;
+        for (int l = 0; l <= c.n_layers; l++) shape += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
+        return fail("%s covers the fc32 network Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1); this handle has Nz = %d and network %s", fn, c.Nz,
+                    shape.c_str());
+    }
+    for (int i = 0; i < n_ptrs; i++)
+        if (!ptrs[i]) return fail("null pointer argument");
+    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
+    if (!(K >= 0.0f)) return fail("K >= 0 required");
+    return 0;
+}
+// first call on a handle: the operand images (a handle on another engine has none yet) and the kernels' LDS limits
+static int fce_prepare(colnde_handle* h) {
+    HIPCHK(hipSetDevice(h->device));
+    if (h->fce_ready) return 0;
+    if (!h->d_fc_imgf) HIPCHK(hipMalloc((void**)&h->d_fc_imgf, fc_image_floats(h->m.Nz) * sizeof(float)));
+    if (!h->d_fc_imgb) HIPCHK(hipMalloc((void**)&h->d_fc_imgb, fc_image_floats(h->m.Nz) * sizeof(float)));
+    if (!h->d_fc_bias) HIPCHK(hipMalloc((void**)&h->d_fc_bias, fc_bias_floats(h->m.Nz) * sizeof(float)));
+    hipError_t e = fce_set_kernel_attributes();
+    if (e != hipSuccess) return fail("hipFuncSetAttribute (fc_embed) failed: %s", hipGetErrorString(e));
+    h->fce_ready = true;
+    return 0;
+}
+static int fce_launch(colnde_handle* h, const char* fn, bool step, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
+                      const float* d_halo_top, float Lz, float dt, float K, float* d_dz_wT, float* d_T_out, float* d_wT_faces, int n_columns) {
+    if (fce_prepare(h)) return 1;
+    FcEmbedArgs a = {};
+    a.cw = fc_tile_width(n_columns);                         // (the images are packed per call: this call's own tile width, as colnde_infer_forcing)
+    hipError_t e = fc_launch_pack(h->m, a.cw, d_weights, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, nullptr, nullptr, h->stream);
+    if (e != hipSuccess) return fail("fc32 pack launch failed: %s", hipGetErrorString(e));
+    a.imgf = h->d_fc_imgf; a.bias = h->d_fc_bias; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top;
+    a.Lz = Lz; a.dt = dt; a.K = K; a.dz_wT = d_dz_wT; a.T_out = d_T_out; a.wT_faces = d_wT_faces; a.n_col = n_columns; a.step = step;
+    Timed tm(h, K_FCEMBED);
+    e = launch_fc_embed(h->m, a, h->stream);
+    if (e != hipSuccess) return fail("%s launch failed: %s (T and the output arrays must be 16-byte aligned)", fn, hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_fc_embedded_step_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
+                                           const float* d_halo_top, float Lz, float dt, float K, float* d_dz_wT, float* d_T_out, float* d_wT_faces,
+                                           int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[5] = {d_weights, d_T, d_top_flux, d_dz_wT, d_T_out};
+    if (fce_check(h, __func__, ptrs, 5, Lz, K, n_columns)) return 1;
+    if (!(dt > 0.0f)) return fail("dt > 0 required");
+    // Measured (profiles/fc_embed_rate.json): without the diagnosis the fused kernel is slower than the two launches it replaces at
+    // 65,536 columns (one lane per column sweeps while the other waves of the workgroup wait), so that is what this call issues — the same bits,
+    // timed under slots 4 and 6.  With wT_faces the one launch beats the three it replaces at every size measured and is kept.
+    // COLNDE_FC_EMBED_FUSED=1 forces the fused kernel (tools/fc_embed_rate.py measures it that way).
+    const char* ef = getenv("COLNDE_FC_EMBED_FUSED");
+    if (!d_wT_faces && !(ef && atoi(ef) != 0)) {
+        if (((uintptr_t)d_T | (uintptr_t)d_dz_wT | (uintptr_t)d_T_out) & 15) return fail("%s: T and the output arrays must be 16-byte aligned", __func__);
+        if (colnde_infer_dz_wT_dev(h, d_weights, d_T, d_top_flux, Lz, d_dz_wT, n_columns)) return 1;
+        return colnde_convective_adjustment_dev(h, d_T, d_halo_bottom, d_halo_top, dt, Lz / (float)h->m.Nz, K, d_T_out, n_columns);
+    }
+    return fce_launch(h, __func__, true, d_weights, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, K, d_dz_wT, d_T_out, d_wT_faces, n_columns);
+}
+
+extern "C" int colnde_fc_diagnose_wT_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
+                                         const float* d_halo_top, float Lz, float K, float* d_wT_faces, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[4] = {d_weights, d_T, d_top_flux, d_wT_faces};
+    if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
+    return fce_launch(h, __func__, false, d_weights, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, 0.0f, K, nullptr, nullptr, d_wT_faces, n_columns);
+}
+
+// host arrays: one scratch of [T (stepped in place) | dz_wT | wT_faces | top | halo_bottom | halo_top]
+static int fce_host(colnde_handle* h, const char* fn, bool step, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
+                    const float* halo_top, float Lz, float dt, float K, float* dz_wT, float* T_out, float* wT_faces, int n_columns) {
+    HIPCHK(hipSetDevice(h->device));
+    const size_t Nz = (size_t)h->m.Nz, nf = (size_t)n_columns * Nz, nfc = ((size_t)n_columns * (Nz + 1) + 3) / 4 * 4, nh = (size_t)n_columns;
+    float* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, (2 * nf + nfc + 3 * nh) * sizeof(float)));
+    float *d_dz = d + nf, *d_faces = d + 2 * nf, *d_top = d_faces + nfc, *d_hb = d_top + nh, *d_ht = d_hb + nh;
+    int rc = 1;
+    do {
+        bool ok = hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(d, T, nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(d_top, top_flux, nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok && halo_bottom) ok = hipMemcpyAsync(d_hb, halo_bottom, nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok && halo_top) ok = hipMemcpyAsync(d_ht, halo_top, nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (!ok) { fail("%s: host-to-device copy failed", fn); break; }
+        if (step) {
+            if (colnde_fc_embedded_step_dev(h, h->d_w, d, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, dt, K, d_dz, d,
+                                            wT_faces ? d_faces : nullptr, n_columns)) break;
+            ok = hipMemcpyAsync(dz_wT, d_dz, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess &&
+                 hipMemcpyAsync(T_out, d, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        } else if (colnde_fc_diagnose_wT_dev(h, h->d_w, d, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, K, d_faces, n_columns)) break;
+        if (ok && wT_faces) ok = hipMemcpyAsync(wT_faces, d_faces, (size_t)n_columns * (Nz + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("%s: device-to-host copy failed", fn); break; }
+        rc = 0;
+    } while (0);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int colnde_fc_embedded_step(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
+                                       const float* halo_top, float Lz, float dt, float K, float* dz_wT, float* T_out, float* wT_faces, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[5] = {weights, T, top_flux, dz_wT, T_out};
+    if (fce_check(h, __func__, ptrs, 5, Lz, K, n_columns)) return 1;
+    if (!(dt > 0.0f)) return fail("dt > 0 required");
+    return fce_host(h, __func__, true, weights, T, top_flux, halo_bottom, halo_top, Lz, dt, K, dz_wT, T_out, wT_faces, n_columns);
+}
+
+extern "C" int colnde_fc_diagnose_wT(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
+                                     const float* halo_top, float Lz, float K, float* wT_faces, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[4] = {weights, T, top_flux, wT_faces};
+    if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
+    return fce_host(h, __func__, false, weights, T, top_flux, halo_bottom, halo_top, Lz, 0.0f, K, nullptr, nullptr, wT_faces, n_columns);
+}
+
 extern "C" int colnde_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_grad, float* d_m, float* d_v, float eta,
                                     float beta1, float beta2, float eps, float beta1_t, float beta2_t, int n) {
     if (!h) return fail("null handle");
@@ -2400,7 +2532,7 @@ extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
 // Every environment variable some part of the library reads (api.hip, engine_*.hip): the list colnde_describe reports from.
 static const char* const COLNDE_ENV_SWITCHES[] = {
     "COLNDE_FWD_SPLIT", "COLNDE_ADJ_SPLIT", "COLNDE_DW_SPLIT", "COLNDE_ADJ_GEOM", "COLNDE_FWD_WLDS", "COLNDE_FWD_THREADS", "COLNDE_T16_FWD_HELPER",
-    "COLNDE_T16_ADJ_HELPER", "COLNDE_T16_FWD_SPLIT", "COLNDE_T16_ADJ_SPLIT", "COLNDE_FC", "COLNDE_FC_CW", "COLNDE_FC_BLOCK", "COLNDE_FC_SEG",
+    "COLNDE_T16_ADJ_HELPER", "COLNDE_T16_FWD_SPLIT", "COLNDE_T16_ADJ_SPLIT", "COLNDE_FC", "COLNDE_FC_CW", "COLNDE_FC_EMBED_FUSED", "COLNDE_FC_BLOCK", "COLNDE_FC_SEG",
     "COLNDE_RT_ZTAPE", "COLNDE_RT_BLOCK", "COLNDE_RT_FWD", "COLNDE_ALLOW_UNSTABLE_DT", "COLNDE_T16_DWTAPE", "COLNDE_T16_ZTAPE", "COLNDE_T16_SPLIT_RICH",
     "COLNDE_T16_BLOCK", "COLNDE_T16_DWLDS", "COLNDE_T16_TAPE_THREADS", "COLNDE_T16_TAPE_WLDS"};
 
@@ -2438,6 +2570,7 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
              (info[7] & 2) ? "bf16x3" : "f32", (info[7] & 4) ? "bf16x3" : "f32", (info[7] & 8) ? "bf16x3" : "f32");
     s += t;
     if (wm_infer_covers(h)) s += " wm_infer=f32";      // colnde_wm_infer_dz_flux / colnde_wm_embedded_step: the f32 matrix pipe under either arithmetic
+    if (fce_covers(h)) s += " fc_embed=f32";      // colnde_fc_embedded_step / colnde_fc_diagnose_wT: likewise
     if (info[1]) { snprintf(t, sizeof t, " block=%dx%d", info[1], info[2]); s += t; } else s += " block=(not planned yet)";
     if (info[0] == COLNDE_ENGINE_MFMA) { snprintf(t, sizeof t, " z1_tape=%d", info[3]); s += t; }
     if (info[0] == COLNDE_ENGINE_FC32) { snprintf(t, sizeof t, " time_segments=%d tile_width=%d dw_slices=%d", info[3], h->fc_cw, info[5]); s += t; }

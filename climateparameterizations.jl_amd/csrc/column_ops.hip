@@ -46,34 +46,8 @@ __global__ void __launch_bounds__(64) convadj_kernel(const float* T, const float
     __syncthreads();
     if (lane < ncol) {
         float* t = cs_smem + lane * LD;
-        float x[NZ], cp[NZ];
-#pragma unroll
-        for (int k = 0; k < NZ; k++) x[k] = t[k];
-        const float ck = c * K;
-        // κ of cell k as c·κ_k: statically unstable where T[k+1] - T[k-1] < 0; the halo cells are the caller's (they carry
-        // the field's boundary conditions) or, absent, the nearest interior value (zero-gradient fill)
-        const float below = halo_bottom ? halo_bottom[col0 + lane] : x[0];
-        const float above = halo_top ? halo_top[col0 + lane] : x[NZ - 1];
-        float kk[NZ];
-#pragma unroll
-        for (int k = 0; k < NZ; k++) kk[k] = ((k + 1 < NZ ? x[k + 1] : above) - (k > 0 ? x[k - 1] : below)) < 0.0f ? ck : 0.0f;
-        // forward elimination
-        float inv = 1.0f / (1.0f + kk[0] + kk[1]);
-        cp[0] = -kk[1] * inv;
-        x[0] = x[0] * inv;
-#pragma unroll
-        for (int k = 1; k < NZ; k++) {
-            const float a = -kk[k];
-            const float b = 1.0f + kk[k] + (k < NZ - 1 ? kk[k + 1] : 0.0f);
-            inv = 1.0f / (b - a * cp[k - 1]);
-            cp[k] = (k < NZ - 1 ? -kk[k + 1] : 0.0f) * inv;
-            x[k] = (x[k] - a * x[k - 1]) * inv;
-        }
-        // back substitution
-#pragma unroll
-        for (int k = NZ - 2; k >= 0; k--) x[k] -= cp[k] * x[k + 1];
-#pragma unroll
-        for (int k = 0; k < NZ; k++) t[k] = x[k];
+        const int ca_i = col0 + lane;
+#include "convadj_sweep.inc"
     }
     __syncthreads();
     ca_f32x4* dst = reinterpret_cast<ca_f32x4*>(out + (size_t)col0 * NZ);

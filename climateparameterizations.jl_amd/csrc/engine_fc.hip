@@ -30,123 +30,9 @@
 #include <type_traits>
 #include "engine_fc.h"
 #include "split_bf16.h"
-
-typedef float fc16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32;
+#include "fc_chain.h"
 
 extern __shared__ float fc_smem[];
-
-#ifndef FC_PF
-#define FC_PF 8                                    // ring depth in groups of four MFMAs: 8 x 256 cycles of cover
-#endif
-#ifndef FC_NT
-#define FC_NT 0                                    // tape traffic with the non-temporal cache policy: measured SLOWER (A/B on one box, 16,384 columns:
-#endif                                             // Nz = 32 forward 26.8 vs 16.7 ms, adjoint 25.4 vs 17.6; Nz = 64 61.0 vs 53.9 and 61.0 vs 54.0) — an
-                                                   // nt store is acknowledged late, and every wait for a ring load (vmcnt is in order) waits behind it
-#if FC_NT
-#define FC_STORE(v, p) __builtin_nontemporal_store(v, p)
-#define FC_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define FC_STORE(v, p) (*(p) = (v))
-#define FC_LOAD(p) (*(p))
-#endif
-#define FC_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-// The group addresses of a stage are loop-invariant: left alone, the optimiser computes all ~100 of them once, outside the time loop, and
-// keeps them in (spilled) registers.  An opaque zero added to the wave-uniform bases at the top of every stage keeps them what they should
-// be: a scalar base, a compile-time offset and the lane.  (The pointers themselves stay kernel-argument-derived: laundering THEM loses the global
-// address space and turns every load into a flat_load, which counts against lgkmcnt as well.)
-#define FC_OPAQUE_ZERO(z) asm volatile("" : "+s"(z))
-
-// CW = columns per workgroup tile = N of the MFMA: 32 (v_mfma_f32_32x32x2_f32, the throughput shape) or 16 (v_mfma_f32_16x16x4_f32: half the
-// matrix work per stage for problems that cannot fill 32-column tiles on every CU — the latency sizes, up to 4,096 columns).  Everything else is the
-// same code: lane = (column n = lane % CW, k/row quad hq = lane / CW); a group is four MFMAs over KG = 256/CW consecutive k; an accumulator holds
-// NQ = CW²/256 quads of four consecutive output rows: rows 8q + 4hq + e (CW = 32) or 4hq + e (CW = 16) of the row tile, column n.
-template <int NZ, int CW = 32>
-struct Fc {
-    static_assert(CW == 32 || CW == 16, "tile width");
-    static constexpr int H = 4 * NZ, NO = NZ - 1;
-    static constexpr int LDX = NZ + 4, LDH = H + 4;              // LDS row strides: 16-byte aligned rows, stride/4 odd => conflict-free ds_read_b128
-    static constexpr int KG = 256 / CW, NQ = CW * CW / 256, ACCN = 4 * NQ;   // k per group; accumulator quads (4 / 1); accumulator floats
-    static constexpr int MT = H / CW, JH = MT / 4;               // row tiles of a hidden layer; jobs per wave
-    static constexpr int S_IN = NZ / KG, S_H = H / KG;           // groups per chain: K = NZ, K = 4 NZ
-    static constexpr int MT3 = NZ / CW, KS3 = MT3 >= 4 ? 1 : 4 / MT3, G3 = S_H / KS3;   // narrow layer (M = NZ): row tiles, K splits, groups per job
-    static_assert(MT3 * KS3 == 4 && JH >= 1, "four jobs of the narrow layer, one per wave");
-    static constexpr int F1 = 0, F1_SZ = MT * S_IN * 256;
-    static constexpr int F2 = F1 + F1_SZ, F2_SZ = MT * S_H * 256;
-    static constexpr int F3 = F2 + F2_SZ, F3_SZ = MT3 * S_H * 256;
-    static constexpr int IMG = F3 + F3_SZ;                       // floats per operand image (forward and backward alike)
-    static constexpr int BIAS = 2 * H + NZ;
-    static constexpr int P = JH * S_IN + JH * S_H + G3;          // groups per stage and wave
-    static constexpr int ACT4 = 2 * H + NZ;                      // dwtape_act4: (2H + NZ - 1) rounded up to 4
-    static constexpr int R = NZ + 2 * ACT4;                      // floats per column of a delta-tape record (dwtape_row_floats)
-    static constexpr int OWN = CW * NZ / 256;                    // state items (column, level) per thread
-    static_assert(P % FC_PF == 0, "the ring must close over one stage");
-    // ---- COLNDE_MATRIX_BF16X3_EXACT on the 16-column tiles (round 4; the 32-column tiles have their own kernels, engine_fc_split.hip): the same sections
-    // on v_mfma_f32_16x16x32_bf16 from exact three-way operand splits (split_bf16.h).  The A operand is pre-split: per (16-row tile, 32-deep k-block) three
-    // planes (h, m, l) of [64 lanes][8 bf16], lane (m = lane % 16, kq = lane / 16) holding k = 32 kb + 8 kq + i.  A wave's stream is contiguous per
-    // section, k-block outer, its row tiles (jobs) inner, planes innermost: the B operand (8 consecutive floats of the column's activation row, split
-    // in registers: 44 vector instructions) is shared by the wave's jobs.  Unit below: one SLOT = one plane fragment (64 lanes x 16 bytes).
-    static constexpr int KB_IN = NZ / 32, KB_H = H / 32, KB3 = KB_H / KS3;          // k-blocks per chain: K = NZ, K = 4 NZ, the narrow layer's K part
-    static constexpr int SF1 = 0, SF1_SZ = MT * KB_IN * 3 * 256;                    // u32 words
-    static constexpr int SF2 = SF1 + SF1_SZ, SF2_SZ = MT * KB_H * 3 * 256;
-    static constexpr int SF3 = SF2 + SF2_SZ, SF3_SZ = MT3 * KB_H * 3 * 256;
-    static constexpr int SIMG = SF3 + SF3_SZ;                                       // words per split operand image (1.5 x IMG: engine_fc_split's size)
-    static constexpr int PS0 = JH * 3 * KB_IN, PS1 = JH * 3 * KB_H, PS2 = 3 * KB3, PS = PS0 + PS1 + PS2;   // slots per stage and wave
-    static constexpr int PFS = 12;                                                  // ring depth in slots
-    static_assert(CW != 16 || (PS % PFS == 0 && KB_IN >= 1), "the split ring must close over one stage");
-    typedef float acc_t __attribute__((ext_vector_type(ACCN)));
-    // first row (within the row tile) of accumulator quad q for this lane's hq
-    __device__ static constexpr int qrow(int q, int hq) { return (CW == 32 ? 8 * q : 0) + 4 * hq; }
-};
-
-// stream position -> layer section (0: K = NZ hidden, 1: K = 4NZ hidden, 2: the narrow layer) and offset in float4 units from the wave's base
-template <int NZ, int CW> __host__ __device__ constexpr int fc_sec(int p) {
-    p %= Fc<NZ, CW>::P;
-    return p < Fc<NZ, CW>::JH * Fc<NZ, CW>::S_IN ? 0 : (p < Fc<NZ, CW>::JH * (Fc<NZ, CW>::S_IN + Fc<NZ, CW>::S_H) ? 1 : 2);
-}
-template <int NZ, int CW> __host__ __device__ constexpr int fc_off(int p) {
-    using S = Fc<NZ, CW>;
-    p %= S::P;
-    if (p < S::JH * S::S_IN) return (4 * (p / S::S_IN) * S::S_IN + p % S::S_IN) * 64;
-    p -= S::JH * S::S_IN;
-    if (p < S::JH * S::S_H) return (4 * (p / S::S_H) * S::S_H + p % S::S_H) * 64;
-    return (p - S::JH * S::S_H) * 64;
-}
-
-// One section of the wave's stream: NJ jobs (output row tiles) of NG groups each, starting at stream position P0.  Per group: four
-// MFMAs fed by one ring slot (A: four k-steps of this lane's weight row) and one 16-byte LDS read (B: the same four k of column n);
-// the slot is refilled with the group FC_PF positions ahead — possibly the next layer's or the next stage's.
-template <int NZ, int CW, int P0, int NJ, int NG, class Epi>
-__device__ __forceinline__ void fc_section(f32x4 (&ring)[FC_PF], const f32x4* const (&base)[3], int lane, const float* brow, Epi&& epi) {
-    using S = Fc<NZ, CW>;
-#pragma unroll
-    for (int j = 0; j < NJ; j++) {
-        typename S::acc_t acc = (typename S::acc_t)(0.0f);
-        f32x4 b[2];
-        b[0] = *reinterpret_cast<const f32x4*>(brow);
-#pragma unroll
-        for (int g = 0; g < NG; g++) {
-            const int p = P0 + j * NG + g;
-            if (g + 1 < NG) b[(g + 1) & 1] = *reinterpret_cast<const f32x4*>(brow + S::KG * (g + 1));
-            const f32x4 a = ring[p % FC_PF];
-            ring[p % FC_PF] = (base[fc_sec<NZ, CW>(p + FC_PF)] + fc_off<NZ, CW>(p + FC_PF))[lane];
-            const f32x4 bv = b[g & 1];
-            if constexpr (CW == 32) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bv.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bv.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bv.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bv.w, acc, 0, 0, 0);
-            } else {
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bv.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, bv.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, bv.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, bv.w, acc, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        epi(j, acc);
-    }
-}
 
 // slot position of the split stream (16-column tiles) -> section, and offset in 16-byte units from the wave's base of that section
 template <int NZ> __host__ __device__ constexpr int fc16s_sec(int p) {
@@ -360,12 +246,6 @@ __global__ void __launch_bounds__(256) fc_pack_split16_kernel(FcOffsets o, const
         (fwd ? simgf : simgb)[e] = word;
     }
 }
-
-// state items owned by a thread: item it = tid + 256 r  ->  (column it / NZ, level it % NZ)
-#define FC_OWNER_INDEX()                                                   \
-    int oc[S::OWN];                                                        \
-    const int oi = tid & (NZ - 1);                                         \
-    _Pragma("unroll") for (int r = 0; r < S::OWN; r++) oc[r] = (tid + 256 * r) / NZ
 
 // ------------------------------------------------------------------------------------------------
 // forward solve (and, TAPE, the forward half of the tapes)
@@ -624,45 +504,15 @@ fc_infer_kernel(const float* __restrict__ imgf, const float* __restrict__ bias, 
 #pragma unroll
         for (int r = 0; r < S::OWN; r++) {
             const int col = min(col0 + oc[r], n_col - 1);
-            X[oc[r] * S::LDX + oi] = ((19.65f + T[(size_t)col * NZ + oi] / 20.0f) - mu_T) * inv_sig_T;
+            X[oc[r] * S::LDX + oi] = fc_infer_scale(T[(size_t)col * NZ + oi], mu_T, inv_sig_T);
             tf[r] = top_flux[col];
         }
         FC_BARRIER();
-        auto hidden = [&](int l, float* dstrows, int j, const typename S::acc_t& acc) {
-            const int mt = w + 4 * j;
-#pragma unroll
-            for (int q = 0; q < S::NQ; q++) {
-                const int f = mt * CW + S::qrow(q, h);
-                const f32x4 bq = *reinterpret_cast<const f32x4*>(BL + (l - 1) * S::H + f);
-                f32x4 a;
-#pragma unroll
-                for (int e = 0; e < 4; e++) a[e] = fmaxf(acc[4 * q + e] + bq[e], 0.0f);
-                *reinterpret_cast<f32x4*>(dstrows + n * S::LDH + f) = a;
-            }
-        };
-        fc_section<NZ, CW, 0, S::JH, S::S_IN>(ring, sb, lane, X + n * S::LDX + 4 * h, [&](int j, const typename S::acc_t& acc) { hidden(1, A1, j, acc); });
-        FC_BARRIER();
-        fc_section<NZ, CW, S::JH * S::S_IN, S::JH, S::S_H>(ring, sb, lane, A1 + n * S::LDH + 4 * h, [&](int j, const typename S::acc_t& acc) { hidden(2, A2, j, acc); });
-        FC_BARRIER();
-        fc_section<NZ, CW, S::JH * (S::S_IN + S::S_H), 1, S::G3>(ring, sb, lane, A2 + n * S::LDH + (w / S::MT3) * S::G3 * S::KG + 4 * h,
-            [&](int, const typename S::acc_t& acc) {
-                float* pr = PART + ((w / S::MT3) * CW + n) * NZ + (w % S::MT3) * CW;
-#pragma unroll
-                for (int q = 0; q < S::NQ; q++) {
-                    const f32x4 v = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-                    *reinterpret_cast<f32x4*>(pr + S::qrow(q, h)) = v;
-                }
-            });
-        FC_BARRIER();
+#include "fc_infer_chain.inc"
 #pragma unroll
         for (int r = 0; r < S::OWN; r++) {
-            float o = b3v;
-#pragma unroll
-            for (int ks = 0; ks < S::KS3; ks++) o += PART[(ks * CW + oc[r]) * NZ + oi];
-            const float wT = sig_wT * o + mu_wT;                                   // face oi + 1
-            const float below = __shfl_up(wT, 1);                                  // face oi
-            const float lo = oi == 0 ? 0.0f : below;
-            const float hi = oi == NZ - 1 ? tf[r] : wT;
+            float lo, hi;
+            fc_infer_faces<NZ, CW>(PART, oc[r], oi, b3v, sig_wT, mu_wT, tf[r], lo, hi);
             if (col0 + oc[r] < n_col) out[(size_t)(col0 + oc[r]) * NZ + oi] = -(hi - lo) * inv_dz;
         }
         FC_BARRIER();                                                               // PART (= A1's rows) is rewritten by the next tile's first layer

@@ -8,6 +8,7 @@
     nde_loss()  and the Flux.train! loop                                  free_convection/src/training.jl:44-74
     compute_neural_network_forcing!                                       free_convection/double_gyre_nn.jl:149-168
     convective_adjustment!(model, Δt, K)                                  free_convection/double_gyre_nn.jl:27-62, src/oceananigans_nn.jl:13-40
+    progress_neural_network(simulation), diagnose_wT_NN(model)            free_convection/src/oceananigans_nn.jl:153-165, :100-118
 
 The Oceananigans `FieldDataset` wrangling and DataDeps download stay outside (network + foreign types).
 """
@@ -129,6 +130,33 @@ def convective_adjustment(engine: ColumnNDE, T_interior, dt: float, K: float, dz
     hb = None if halo_bottom is None else np.asarray(halo_bottom, np.float32).reshape(-1)
     ht = None if halo_top is None else np.asarray(halo_top, np.float32).reshape(-1)
     return engine.convective_adjustment(T2, dt, dz, K, hb, ht).reshape(shape)
+
+
+def _embed_args(T, top_flux, halos):
+    T = np.asarray(T, dtype=np.float32)
+    shape = T.shape
+    T2 = T.reshape(-1, shape[-1])
+    top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_flux, np.float32).reshape(-1), (T2.shape[0],)))
+    if halos is not None:
+        halos = tuple(None if a is None else np.asarray(a, np.float32).reshape(-1) for a in halos)
+    return T2, shape, top, halos
+
+
+def progress_neural_network(engine: ColumnNDE, weights, T, top_flux, Lz: float, dt: float, K: float, halos=None):
+    """One iteration of `progress_neural_network` (src/oceananigans_nn.jl:153-165; per column of double_gyre_nn.jl:211-234): the stored
+    `∂z_wT_NN` of T as given (:159-160), then `convective_adjustment!(model, Δt, K)` (:162), in one launch.  T [..., Nz] (k = 0 deepest,
+    the units `compute_neural_network_dz_wT` takes), top_flux a scalar or one value per column, halos = None or (halo_bottom, halo_top) as
+    `convective_adjustment`.  Returns (∂z_wT_NN, Tⁿ⁺¹) in T's shape; the forcing the ocean model applies is −∂z_wT_NN (:132)."""
+    T2, shape, top, halos = _embed_args(T, top_flux, halos)
+    dz_wT, T_new = engine.fc_embedded_step(weights, T2, top, Lz, dt, K, halos)
+    return dz_wT.reshape(shape), T_new.reshape(shape)
+
+
+def diagnose_wT_NN(engine: ColumnNDE, weights, T, top_flux, Lz: float, K: float, halos=None):
+    """`diagnose_wT_NN(model)` (src/oceananigans_nn.jl:100-118): the total face flux wT_NN − κ ∂T/∂z on the Nz + 1 faces, κ = K where the
+    face gradient is negative (the end faces from the halo cells).  Arguments as `progress_neural_network`; returns [..., Nz + 1]."""
+    T2, shape, top, halos = _embed_args(T, top_flux, halos)
+    return engine.fc_diagnose_wT(weights, T2, top, Lz, K, halos).reshape(shape[:-1] + (shape[-1] + 1,))
 
 
 def train_neural_differential_equation_device(nde: FreeConvectionNDE, weights, opt: ADAM, epochs: int, process_group=None, comm=None):

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .config import MATRIX_ARITHMETIC_NAMES, NDEConfig, matrix_arithmetic_id, to_c_config
 
-KERNEL_IDS = {"forward": 0, "adjoint": 1, "reduce": 2, "rhs": 3, "infer": 4, "dw1": 5, "convadj": 6, "adam": 7, "impldiff": 8}
+KERNEL_IDS = {"forward": 0, "adjoint": 1, "reduce": 2, "rhs": 3, "infer": 4, "dw1": 5, "convadj": 6, "adam": 7, "impldiff": 8, "fc_embed": 9}
 ENGINE_AUTO, ENGINE_TILE16, ENGINE_REGTILE, ENGINE_FC32 = 0, 1, 2, 3
 
 
@@ -75,6 +75,41 @@ def check_wm_embed_arrays(Nz: int, n: int, state, top_flux, halo_bottom=None, dz
         for ti, a in inputs:
             if overlap(o, a) and not (own.get(to) == ti and _span(o) == _span(a)):
                 raise ValueError("%s overlaps %s: the dz arrays may alias nothing, an output only its own input (in place)" % (to, ti))
+        for tj, b in outputs[i + 1:]:
+            if overlap(o, b):
+                raise ValueError("%s overlaps %s" % (to, tj))
+
+
+def check_fc_embed_arrays(Nz: int, n: int, T, top_flux, halos=None, dz_out=None, T_out=None, faces_out=None):
+    """Shape and alias rules of `fc_embedded_step` / `fc_diagnose_wT` (no GPU needed): T [n, Nz], top_flux [n], halos = None or
+    (halo_bottom, halo_top), each [n] or None; dz_out [n, Nz] and faces_out [n, Nz + 1] overlap nothing, T_out [n, Nz] may be exactly T
+    (in place) and overlaps nothing else."""
+    if tuple(T.shape) != (n, Nz):
+        raise ValueError("T: expected shape %s, got %s" % ((n, Nz), tuple(T.shape)))
+    if tuple(top_flux.shape) != (n,):
+        raise ValueError("top_flux: expected shape %s, got %s" % ((n,), tuple(top_flux.shape)))
+    if halos is not None and len(halos) != 2:
+        raise ValueError("halos must be (halo_bottom, halo_top); either may be None")
+    inputs = [("T", T), ("top_flux", top_flux)]
+    for nm, a in zip(("halo_bottom", "halo_top"), halos if halos is not None else ()):
+        if a is not None:
+            if tuple(a.shape) != (n,):
+                raise ValueError("%s: expected shape %s, got %s" % (nm, (n,), tuple(a.shape)))
+            inputs.append((nm, a))
+    outputs = []
+    for nm, a, shape in (("dz_out", dz_out, (n, Nz)), ("T_out", T_out, (n, Nz)), ("faces_out", faces_out, (n, Nz + 1))):
+        if a is not None:
+            if tuple(a.shape) != shape:
+                raise ValueError("%s: expected shape %s, got %s" % (nm, shape, tuple(a.shape)))
+            outputs.append((nm, a))
+
+    def overlap(a, b):
+        (pa, na), (pb, nb) = _span(a), _span(b)
+        return pa < pb + nb and pb < pa + na
+    for i, (to, o) in enumerate(outputs):
+        for ti, a in inputs:
+            if overlap(o, a) and not (to == "T_out" and ti == "T" and _span(o) == _span(a)):
+                raise ValueError("%s overlaps %s: only T_out may alias an input, and only T itself (in place)" % (to, ti))
         for tj, b in outputs[i + 1:]:
             if overlap(o, b):
                 raise ValueError("%s overlaps %s" % (to, tj))
@@ -540,6 +575,69 @@ class ColumnNDE:
         _lib.check(self._L.colnde_wm_embedded_step(self._h, _ptr(w), _ptr(u), _ptr(v), _ptr(T), _ptr(top_flux), _ptr(hb), float(Lz), dt, pr, int(ca),
                                                    _ptr(dz[0]), _ptr(dz[1]), _ptr(dz[2]), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), n))
         return dz, res
+
+    def fc_embedded_step(self, weights, T, top_flux, Lz: float, dt: float, K: float, halos=None, diagnose: bool = False, dz_out=None, T_out=None,
+                         faces_out=None):
+        """`progress_neural_network` of the free-convection embedding (free_convection/src/oceananigans_nn.jl:153-165) in one launch: the
+        stored ∂z_wT_NN of T AS GIVEN, then `convective_adjustment!(model, Δt, K)` on it (Δz = Lz/Nz), and with `diagnose` (or `faces_out`)
+        `diagnose_wT_NN` (:100-118) of the state as given.  T [n][Nz] in the units `infer_dz_wT` takes, top_flux [n], halos = None or
+        (halo_bottom, halo_top).  numpy arrays or device tensors (`dz_out`, `T_out`, `faces_out`: device tensors; `T_out` may be `T`).
+        Returns (∂z_wT_NN, T′) or (∂z_wT_NN, T′, wT_faces [n][Nz+1])."""
+        return self._fc_embed(weights, T, top_flux, Lz, float(dt), K, halos, bool(diagnose) or faces_out is not None, dz_out, T_out, faces_out)
+
+    def fc_diagnose_wT(self, weights, T, top_flux, Lz: float, K: float, halos=None, faces_out=None):
+        """`diagnose_wT_NN` (free_convection/src/oceananigans_nn.jl:100-118): wT_NN − κ ∂T/∂z on the Nz + 1 faces, κ = K where the face
+        gradient is negative; [n][Nz+1].  Arguments as `fc_embedded_step`."""
+        return self._fc_embed(weights, T, top_flux, Lz, None, K, halos, True, None, None, faces_out)
+
+    def _fc_embed(self, weights, T, top_flux, Lz, dt, K, halos, diag, dz_out, T_out, faces_out):
+        Nz = self.cfg.Nz
+        step = dt is not None
+        hb, ht = halos if halos is not None else (None, None)
+        if _is_torch(T):
+            import torch
+            n = T.shape[0]
+            check_fc_embed_arrays(Nz, n, T, top_flux, halos, dz_out, T_out, faces_out)
+            self._chk_dev(T, (n, Nz))
+            self._chk_dev(top_flux, (n,))
+            self._chk_dev(weights, (self.n_params,))
+            for hl in (hb, ht):
+                if hl is not None:
+                    self._chk_dev(hl, (n,))
+            if step and dz_out is None:
+                dz_out = torch.empty_like(T)
+            if step and T_out is None:
+                T_out = torch.empty_like(T)
+            if diag and faces_out is None:
+                faces_out = torch.empty((n, Nz + 1), dtype=T.dtype, device=T.device)
+            for a, shape in ((dz_out, (n, Nz)), (T_out, (n, Nz)), (faces_out, (n, Nz + 1))):
+                if a is not None:
+                    self._chk_dev(a, shape)
+            self.use_torch_stream()
+            P = lambda a: a.data_ptr() if a is not None else None
+            if step:
+                _lib.check(self._L.colnde_fc_embedded_step_dev(self._h, P(weights), P(T), P(top_flux), P(hb), P(ht), float(Lz), dt, float(K), P(dz_out),
+                                                               P(T_out), P(faces_out) if diag else None, n))
+                return (dz_out, T_out, faces_out) if diag else (dz_out, T_out)
+            _lib.check(self._L.colnde_fc_diagnose_wT_dev(self._h, P(weights), P(T), P(top_flux), P(hb), P(ht), float(Lz), float(K), P(faces_out), n))
+            return faces_out
+        if dz_out is not None or T_out is not None or faces_out is not None:
+            raise ValueError("dz_out / T_out / faces_out are for device tensors; host arrays are returned")
+        T = _f32(T)
+        n = T.shape[0]
+        top_flux = _f32(top_flux)
+        hb = _f32(hb) if hb is not None else None
+        ht = _f32(ht) if ht is not None else None
+        check_fc_embed_arrays(Nz, n, T, top_flux, None if halos is None else (hb, ht))
+        w = _f32(weights, (self.n_params,))
+        faces = np.empty((n, Nz + 1), np.float32) if diag else None
+        if step:
+            dz, res = np.empty_like(T), np.empty_like(T)
+            _lib.check(self._L.colnde_fc_embedded_step(self._h, _ptr(w), _ptr(T), _ptr(top_flux), _ptr(hb), _ptr(ht), float(Lz), dt, float(K), _ptr(dz),
+                                                       _ptr(res), _ptr(faces), n))
+            return (dz, res, faces) if diag else (dz, res)
+        _lib.check(self._L.colnde_fc_diagnose_wT(self._h, _ptr(w), _ptr(T), _ptr(top_flux), _ptr(hb), _ptr(ht), float(Lz), float(K), _ptr(faces), n))
+        return faces
 
     def adam_step(self, weights, grad, m, v, eta: float, beta=(0.9, 0.999), eps: float = 1e-8, beta_t=None):
         """One fused `Flux.Optimise.ADAM` apply!/update! on device vectors (in place).  beta_t = running powers (β₁ᵗ, β₂ᵗ)."""

@@ -299,6 +299,36 @@ int colnde_wm_embedded_step(colnde_handle* h, const float* weights, const float*
                             const float* halo_bottom, float Lz, float dt, const float params[7], int convective_adjustment, float* dz_uw,
                             float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, int n_columns);
 
+/* The free-convection embedding's per-iteration work and its diagnosed flux (free_convection/src/oceananigans_nn.jl; the same over 96 x 96 columns
+ * in free_convection/double_gyre_nn.jl:211-234), per column, on T [Nz] AS GIVEN (k = 0 deepest, the units colnde_infer_dz_wT takes), dz = Lz/Nz,
+ * c = dt/dz²:
+ *   1. forcing (progress_neural_network :159-160 with neural_network_forcing :120-126): y = NN((T̃−μ_T)/σ_T) as colnde_infer_dz_wT evaluates it
+ *      (Nz−1 values), faces F = [0; σ_wT y + μ_wT; top_flux] (:95), stored ∂z_wT_NN[k] = (F[k+1] − F[k])/dz (:86-93) — BEFORE the adjustment;
+ *   2. convective_adjustment!(model, Δt, K) (:162, :13-40): exactly colnde_convective_adjustment above — κ_k = K where the centred ∂T/∂z of cell k
+ *      is negative, 0 elsewhere, halo cells as given or, NULL, the zero-gradient fill, one backward-Euler step T′ = L \ T;
+ *   3. diagnose_wT_NN (:100-118): g_f = ∂T/∂z on the Nz+1 faces (:107; the end faces from the halo cells, same NULL rule), κ_f = g_f < 0 ? K : 0
+ *      (:110-113; NaN < 0 is false, as in Julia), wT_faces = F − κ_f g_f (:115-117), F the faces of 1.
+ * colnde_fc_embedded_step: 1 and 2 (progress_neural_network, :153-165) and, when wT_faces is not NULL, 3 of the state as given, in ONE launch that
+ * reads T once; colnde_fc_diagnose_wT: 3 alone.  T, dz_wT, T_out: [n_col][Nz]; top_flux, halo_bottom, halo_top: [n_col]; wT_faces: [n_col][Nz+1].
+ * T, dz_wT, T_out and wT_faces 16-byte aligned.  T_out may alias T; no other aliasing.  n_columns is independent of the handle's own column
+ * count.  The ∂z_wT_NN bits are colnde_infer_dz_wT_dev's and the T′ bits colnde_convective_adjustment_dev's (the same device code).  Refused, with
+ * the reason in colnde_last_error: wind-mixing, ensemble and closure handles, networks other than the fc32 shape Dense(Nz,4Nz,relu),
+ * Dense(4Nz,4Nz,relu), Dense(4Nz,Nz−1), networks with activation rows in global memory, Nz other than 32 or 64; the handle's engine and stepper do
+ * not matter.  The dense chains run on the f32 matrix pipe under either matrix_arithmetic (colnde_describe: fc_embed=f32); timed under
+ * colnde_kernel_time slot 9.  Launches: colnde_fc_diagnose_wT one; colnde_fc_embedded_step one when wT_faces is given and, when it is NULL,
+ * the two of colnde_infer_dz_wT_dev and colnde_convective_adjustment_dev (slots 4 and 6) — measured faster than the fused kernel from 65,536
+ * columns on (COLNDE_FC_EMBED_FUSED=1 forces the fused kernel); the results are the same bits either way. */
+int colnde_fc_embedded_step_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
+                                const float* d_halo_top, float Lz, float dt, float K, float* d_dz_wT, float* d_T_out, float* d_wT_faces /* nullable */,
+                                int n_columns);
+int colnde_fc_embedded_step(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
+                            const float* halo_top, float Lz, float dt, float K, float* dz_wT, float* T_out, float* wT_faces /* nullable */,
+                            int n_columns);   /* host arrays; synchronises */
+int colnde_fc_diagnose_wT_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
+                              const float* d_halo_top, float Lz, float K, float* d_wT_faces, int n_columns);
+int colnde_fc_diagnose_wT(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
+                          const float* halo_top, float Lz, float K, float* wT_faces, int n_columns);   /* host arrays; synchronises */
+
 /* Flux.Optimise.ADAM apply! + update! (Flux 0.11.6 src/optimise/optimisers.jl; used at wind_mixing/src/NDE_training.jl:340-372,
  * free_convection/src/training.jl:71) on device vectors of n floats: m ← β₁m + (1-β₁)g, v ← β₂v + (1-β₂)g²,
  * w ← w - η·m/(1-β₁ᵗ)/(√(v/(1-β₂ᵗ)) + ϵ).  beta1_t / beta2_t are the running powers the optimiser state carries (β₁, β₂ on the
@@ -438,7 +468,8 @@ int colnde_closure_loss_grad(colnde_handle* h, const float* params, const float 
 
 /* ---- measurement: HIP-event timing of the handle's kernels on its stream.
  * which: 0 = forward solve kernel, 1 = adjoint kernel, 2 = gradient reduce, 3 = rhs, 4 = inference,
- * 5 = streaming dW1 GEMM (regtile engine only), 6 = convective adjustment, 7 = ADAM step, 8 = implicit diffusion.
+ * 5 = streaming dW1 GEMM (regtile engine only), 6 = convective adjustment, 7 = ADAM step, 8 = implicit diffusion,
+ * 9 = free-convection embedded step / diagnose_wT.
  * Returns accumulated milliseconds and launch count since the last reset (synchronises the stream). */
 int colnde_set_profiling(colnde_handle* h, int enabled);
 int colnde_kernel_time(colnde_handle* h, int which, float* ms_total, int* n_launches);

@@ -324,6 +324,32 @@ function convective_adjustment!(h::Handle, T::Matrix{Float32}, Δt, Δz, K; halo
     T
 end
 
+"progress_neural_network(simulation) of the free-convection embedding — free_convection/src/oceananigans_nn.jl:153-165, per column of
+double_gyre_nn.jl:211-234 — for ALL columns in one call: fills ∂z_wT_NN from T as given (:159-160), then convective_adjustment!(model, Δt, K)
+on T in place (:162; Δz = Lz/Nz).  T (Nz, n_columns) column-major, surface_flux one value per column, halos as convective_adjustment!;
+wT_faces (Nz+1, n_columns), when given, receives diagnose_wT_NN (:100-118) of the state as given"
+function progress_neural_network!(h::Handle, θ::Vector{Float32}, T::Matrix{Float32}, surface_flux::Vector{Float32}, Lz, Δt, K,
+                                  ∂z_wT_NN::Matrix{Float32}; halo_bottom=nothing, halo_top=nothing, wT_faces=nothing)
+    hb = halo_bottom === nothing ? C_NULL : pointer(halo_bottom); ht = halo_top === nothing ? C_NULL : pointer(halo_top)
+    fc = wT_faces === nothing ? C_NULL : pointer(wT_faces)
+    GC.@preserve halo_bottom halo_top wT_faces check(ccall((:colnde_fc_embedded_step, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Cfloat, Ptr{Float32}, Ptr{Float32},
+         Ptr{Float32}, Cint),
+        h.ptr, θ, T, surface_flux, hb, ht, Lz, Δt, K, ∂z_wT_NN, T, fc, size(T, 2)))
+    nothing
+end
+
+"diagnose_wT_NN(model) — free_convection/src/oceananigans_nn.jl:100-118 — for all columns in one call: wT_NN .- κ .* ∂T∂z on the Nz+1 faces,
+κ = K where the face gradient is negative; returns (Nz+1, n_columns)"
+function diagnose_wT_NN(h::Handle, θ::Vector{Float32}, T::Matrix{Float32}, surface_flux::Vector{Float32}, Lz, K; halo_bottom=nothing, halo_top=nothing)
+    hb = halo_bottom === nothing ? C_NULL : pointer(halo_bottom); ht = halo_top === nothing ? C_NULL : pointer(halo_top)
+    wT = Matrix{Float32}(undef, size(T, 1) + 1, size(T, 2))
+    GC.@preserve halo_bottom halo_top check(ccall((:colnde_fc_diagnose_wT, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Ptr{Float32}, Cint),
+        h.ptr, θ, T, surface_flux, hb, ht, Lz, K, wT, size(T, 2)))
+    wT
+end
+
 "modified_pacanowski_philander!(model, constants, Δt, p, convective_adjustment) — wind_mixing/src/NDE_oceananigans.jl:61-101: u, v, T are
 `interior(model.velocities.u)[:]` … as (Nz, n_columns) column-major matrices (= C-order [column][level]), updated in place; `p` is the
 reference's diffusivity dictionary, `constants` its NamedTuple; halo_bottom (n_columns, 3) column-major = C-order [3][n_columns] or nothing"
