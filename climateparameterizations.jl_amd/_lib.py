@@ -57,6 +57,12 @@ SYMBOLS = [
     ("colnde_wm_infer_dz_flux_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, _V, _V, _V, ctypes.c_int]),
     ("colnde_wm_embedded_step", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _F, ctypes.c_int, _V, _V, _V, _V, _V, _V, ctypes.c_int]),
     ("colnde_wm_embedded_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _F, ctypes.c_int, _V, _V, _V, _V, _V, _V, ctypes.c_int]),
+    ("colnde_wm_diagnose_flux", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, _F, ctypes.c_int, _V, _V, _V, ctypes.c_int]),
+    ("colnde_wm_diagnose_flux_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, _F, ctypes.c_int, _V, _V, _V, ctypes.c_int]),
+    ("colnde_wm_embedded_step_flux", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _F, ctypes.c_int] + [_V] * 9 + [ctypes.c_int]),
+    ("colnde_wm_embedded_step_flux_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _F, ctypes.c_int] + [_V] * 9 + [ctypes.c_int]),
+    ("colnde_mpp_diagnose_flux", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, _F, ctypes.c_int, _V, _V, _V, ctypes.c_int]),
+    ("colnde_mpp_diagnose_flux_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, _F, ctypes.c_int, _V, _V, _V, ctypes.c_int]),
     ("colnde_fc_embedded_step", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, ctypes.c_float, _V, _V, _V, ctypes.c_int]),
     ("colnde_fc_embedded_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, ctypes.c_float, _V, _V, _V, ctypes.c_int]),
     ("colnde_fc_diagnose_wT", ctypes.c_int, [_V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _V, ctypes.c_int]),

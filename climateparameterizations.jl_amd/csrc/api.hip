@@ -50,7 +50,7 @@ extern "C" int colnde_internal_set_error(const char* msg) { g_err = msg ? msg : 
         if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1 = 5, K_CONVADJ = 6, K_ADAM = 7, K_IMPLDIFF = 8, K_FCEMBED = 9, K_COUNT = 10 };
+enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1 = 5, K_CONVADJ = 6, K_ADAM = 7, K_IMPLDIFF = 8, K_FCEMBED = 9, K_FLUXDIAG = 10, K_COUNT = 11 };
 
 struct PendingEvent { hipEvent_t a, b; int which; };
 
@@ -2270,6 +2270,177 @@ extern "C" int colnde_wm_embedded_step(colnde_handle* h, const float* weights, c
                          T_out, n_columns);
 }
 
+// ---- the saved-state flux diagnoses of the wind-mixing embedding (NDE_oceananigans.jl:157-191, :226-286) ---------------------------------
+static int wm_diag_launch(colnde_handle* h, const char* fn, bool fused, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                          const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt, const float params[7], int ca,
+                          float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT,
+                          int n_columns) {
+    WmInferArgs a = {};
+    wm_infer_args(h, &a);
+    const float dz = Lz / (float)WM_NZ;
+    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.Lz = Lz; a.n_col = n_columns;
+    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT; a.fused = fused;
+    a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top;
+    a.mpp = mpp_params(params, fused ? dt : dz * dz, dz, ca);          // (the diagnosis alone takes no step: c is not read)
+    a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
+    a.diag = true; a.uw = d_uw; a.vw = d_vw; a.wT = d_wT;
+    Timed tm(h, K_FLUXDIAG);
+    hipError_t e = launch_wm_infer(a, h->stream);
+    if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", fn, hipGetErrorString(e));
+    return 0;
+}
+static int wm_diag_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, const float params[7], int n_columns) {
+    if (wm_infer_check(h, fn, ptrs, n_ptrs, Lz, n_columns)) return 1;
+    if (!params) return fail("null pointer argument");
+    if (!(params[2] != 0.0f) || !(params[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
+    for (int i = 0; i < n_ptrs; i++)
+        if ((uintptr_t)ptrs[i] & 15) return fail("%s: the state and output arrays must be 16-byte aligned", fn);
+    return 0;
+}
+
+extern "C" int colnde_wm_diagnose_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                                           const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, const float params[7],
+                                           int convective_adjustment, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[8] = {d_u, d_v, d_T, d_uw, d_vw, d_wT, d_weights, d_top_flux};
+    if (wm_diag_check(h, __func__, ptrs, 6, Lz, params, n_columns)) return 1;
+    if (!d_weights || !d_top_flux) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    return wm_diag_launch(h, __func__, false, d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, 0.0f, params, convective_adjustment, nullptr,
+                          nullptr, nullptr, nullptr, nullptr, nullptr, d_uw, d_vw, d_wT, n_columns);
+}
+
+extern "C" int colnde_wm_embedded_step_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                                                const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt,
+                                                const float params[7], int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT,
+                                                float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[12] = {d_u, d_v, d_T, d_dz_uw, d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT};
+    if (wm_diag_check(h, __func__, ptrs, 12, Lz, params, n_columns)) return 1;
+    if (!d_weights || !d_top_flux) return fail("null pointer argument");
+    if (impl_diff_check(h, d_u, d_v, d_T, d_u_out, d_v_out, d_T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    // One launch, by measurement (profiles/wm_diag_rate.json): it beats colnde_wm_embedded_step_dev + colnde_wm_diagnose_flux_dev by far more than
+    // the spread at 9,216, 65,536 and 1,048,576 columns.
+    return wm_diag_launch(h, __func__, true, d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, params, convective_adjustment, d_dz_uw,
+                          d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT, n_columns);
+}
+
+// host arrays: one scratch of [u | v | T | dz_uw | dz_vw | dz_wT | faces(3 x n x 33, padded) | top(3 n) | halo_bottom(3 n) | halo_top(3 n)]
+static int wm_diag_host(colnde_handle* h, const char* fn, bool step, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                        const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params, int ca, float* dz_uw, float* dz_vw, float* dz_wT,
+                        float* u_out, float* v_out, float* T_out, float* uw, float* vw, float* wT, int n_columns) {
+    HIPCHK(hipSetDevice(h->device));
+    const size_t nf = (size_t)n_columns * WM_NZ, nfc = ((size_t)n_columns * (WM_NZ + 1) + 3) / 4 * 4, nh = ((size_t)n_columns + 3) / 4 * 4, nc = (size_t)n_columns;
+    float* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, (6 * nf + 3 * nfc + 9 * nh) * sizeof(float)));
+    float *d_f = d + 6 * nf, *d_top = d_f + 3 * nfc, *d_hb = d_top + 3 * nh, *d_ht = d_hb + 3 * nh;
+    int rc = 1;
+    do {
+        const float* srcs[3] = {u, v, T};
+        bool ok = hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        for (int f = 0; f < 3 && ok; f++) ok = hipMemcpyAsync(d + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(d_top, top_flux, 3 * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok && halo_bottom) ok = hipMemcpyAsync(d_hb, halo_bottom, 3 * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok && halo_top) ok = hipMemcpyAsync(d_ht, halo_top, 3 * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (!ok) { fail("%s: host-to-device copy failed", fn); break; }
+        if (step) {
+            if (colnde_wm_embedded_step_flux_dev(h, h->d_w, d, d + nf, d + 2 * nf, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, dt, params, ca,
+                                                 d + 3 * nf, d + 4 * nf, d + 5 * nf, d, d + nf, d + 2 * nf, d_f, d_f + nfc, d_f + 2 * nfc, n_columns)) break;
+            float* dsts[6] = {u_out, v_out, T_out, dz_uw, dz_vw, dz_wT};
+            for (int f = 0; f < 6 && ok; f++) ok = hipMemcpyAsync(dsts[f], d + f * nf, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        } else if (colnde_wm_diagnose_flux_dev(h, h->d_w, d, d + nf, d + 2 * nf, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, params, ca,
+                                               d_f, d_f + nfc, d_f + 2 * nfc, n_columns)) break;
+        float* fd[3] = {uw, vw, wT};
+        for (int f = 0; f < 3 && ok; f++)
+            ok = hipMemcpyAsync(fd[f], d_f + f * nfc, nc * (WM_NZ + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("%s: device-to-host copy failed", fn); break; }
+        rc = 0;
+    } while (0);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int colnde_wm_diagnose_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                                       const float* halo_bottom, const float* halo_top, float Lz, const float params[7], int convective_adjustment, float* uw,
+                                       float* vw, float* wT, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[8] = {weights, u, v, T, top_flux, uw, vw, wT};
+    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
+    if (!params) return fail("null pointer argument");
+    return wm_diag_host(h, __func__, false, weights, u, v, T, top_flux, halo_bottom, halo_top, Lz, 0.0f, params, convective_adjustment, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, uw, vw, wT, n_columns);
+}
+
+extern "C" int colnde_wm_embedded_step_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                                            const float* halo_bottom, const float* halo_top, float Lz, float dt, const float params[7],
+                                            int convective_adjustment, float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out,
+                                            float* uw, float* vw, float* wT, int n_columns) {
+    SINGLE_MODEL_ONLY(h);
+    const void* const ptrs[11] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT, uw, vw, wT};
+    if (wm_infer_check(h, __func__, ptrs, 11, Lz, n_columns)) return 1;
+    if (impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
+    return wm_diag_host(h, __func__, true, weights, u, v, T, top_flux, halo_bottom, halo_top, Lz, dt, params, convective_adjustment, dz_uw, dz_vw, dz_wT, u_out,
+                        v_out, T_out, uw, vw, wT, n_columns);
+}
+
+// diagnose_baseline_flux_uw / _vw / _wT (:157-191; column_ops.hip): no networks, any handle kind
+static int mpp_diag_check(colnde_handle* h, const void* const* ptrs, int n_ptrs, float dz, const float params[7], int n_columns) {
+    if (!h) return fail("null handle");
+    for (int i = 0; i < n_ptrs; i++)
+        if (!ptrs[i]) return fail("null pointer argument");
+    if (!params) return fail("null pointer argument");
+    if (n_columns < 1) return fail("n_columns must be >= 1");
+    if (!(dz > 0.0f)) return fail("dz > 0 required");
+    if (!(params[2] != 0.0f) || !(params[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
+    if (h->m.Nz < 2 || h->m.Nz > 128) return fail("the flux diagnosis supports 2 <= Nz <= 128 (Nz = %d)", h->m.Nz);
+    return 0;
+}
+
+extern "C" int colnde_mpp_diagnose_flux_dev(colnde_handle* h, const float* d_u, const float* d_v, const float* d_T, const float* d_top_flux,
+                                            const float* d_halo_bottom, float dz, const float params[7], int convective_adjustment, float* d_uw, float* d_vw,
+                                            float* d_wT, int n_columns) {
+    const void* const ptrs[7] = {d_u, d_v, d_T, d_top_flux, d_uw, d_vw, d_wT};
+    if (mpp_diag_check(h, ptrs, 7, dz, params, n_columns)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    Timed tm(h, K_FLUXDIAG);
+    hipError_t e = launch_mpp_diagnose_flux(d_u, d_v, d_T, d_top_flux, d_halo_bottom, dz, params, convective_adjustment, d_uw, d_vw, d_wT, h->m.Nz, n_columns,
+                                            h->stream);
+    if (e != hipSuccess) return fail("mpp_diagnose_flux launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_mpp_diagnose_flux(colnde_handle* h, const float* u, const float* v, const float* T, const float* top_flux, const float* halo_bottom,
+                                        float dz, const float params[7], int convective_adjustment, float* uw, float* vw, float* wT, int n_columns) {
+    const void* const ptrs[7] = {u, v, T, top_flux, uw, vw, wT};
+    if (mpp_diag_check(h, ptrs, 7, dz, params, n_columns)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t Nz = (size_t)h->m.Nz, nf = (size_t)n_columns * Nz, nfc = ((size_t)n_columns * (Nz + 1) + 3) / 4 * 4, nh = (size_t)n_columns;
+    float* d = nullptr;       // [faces(3, padded to 16 bytes) | u | v | T | top(3 n) | halo(3 n)]
+    HIPCHK(hipMalloc((void**)&d, (3 * nfc + 3 * nf + 6 * nh) * sizeof(float)));
+    float *d_s = d + 3 * nfc, *d_top = d_s + 3 * nf, *d_hb = d_top + 3 * nh;
+    int rc = 1;
+    do {
+        const float* srcs[3] = {u, v, T};
+        bool ok = true;
+        for (int f = 0; f < 3 && ok; f++) ok = hipMemcpyAsync(d_s + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(d_top, top_flux, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok && halo_bottom) ok = hipMemcpyAsync(d_hb, halo_bottom, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (!ok) { fail("mpp_diagnose_flux: host-to-device copy failed"); break; }
+        if (colnde_mpp_diagnose_flux_dev(h, d_s, d_s + nf, d_s + 2 * nf, d_top, halo_bottom ? d_hb : nullptr, dz, params, convective_adjustment, d, d + nfc,
+                                         d + 2 * nfc, n_columns)) break;
+        float* fd[3] = {uw, vw, wT};
+        for (int f = 0; f < 3 && ok; f++)
+            ok = hipMemcpyAsync(fd[f], d + f * nfc, (size_t)n_columns * (Nz + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("mpp_diagnose_flux: device-to-host copy failed"); break; }
+        rc = 0;
+    } while (0);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
 // ---- free-convection embedded step (free_convection/src/oceananigans_nn.jl:100-118, :153-165; engine_fc_embed.hip) ----------------------
 // the handles the kernels cover: the network shapes of fc32 (fc_supported), whatever engine and stepper the handle trains with
 static bool fce_covers(const colnde_handle* h) {
@@ -2569,7 +2740,7 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
     snprintf(t, sizeof t, " matrix_arithmetic=%s forward=%s adjoint=%s dw=%s", h->cfg.matrix_arithmetic == COLNDE_MATRIX_BF16X3_EXACT ? "bf16x3_exact" : "f32_mfma",
              (info[7] & 2) ? "bf16x3" : "f32", (info[7] & 4) ? "bf16x3" : "f32", (info[7] & 8) ? "bf16x3" : "f32");
     s += t;
-    if (wm_infer_covers(h)) s += " wm_infer=f32";      // colnde_wm_infer_dz_flux / colnde_wm_embedded_step: the f32 matrix pipe under either arithmetic
+    if (wm_infer_covers(h)) s += " wm_infer=f32";      // colnde_wm_infer_dz_flux / colnde_wm_embedded_step[_flux] / colnde_wm_diagnose_flux: the f32 matrix pipe under either arithmetic
     if (fce_covers(h)) s += " fc_embed=f32";      // colnde_fc_embedded_step / colnde_fc_diagnose_wT: likewise
     if (info[1]) { snprintf(t, sizeof t, " block=%dx%d", info[1], info[2]); s += t; } else s += " block=(not planned yet)";
     if (info[0] == COLNDE_ENGINE_MFMA) { snprintf(t, sizeof t, " z1_tape=%d", info[3]); s += t; }

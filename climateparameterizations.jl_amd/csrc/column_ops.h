@@ -11,6 +11,11 @@ hipError_t launch_convective_adjustment(const float* T, const float* halo_bottom
 hipError_t launch_mpp_diffusion(const float* u, const float* v, const float* T, const float* halo_bottom, float dt, float dz,
                                 const float params[7], int convective_adjustment, float* uo, float* vo, float* To, int Nz, int n_col,
                                 hipStream_t stream);
+// diagnose_baseline_flux_uw / _vw / _wT (:157-191): uw, vw, wT [n_col][Nz+1] = −ν ∂z u, −ν ∂z v, −νT ∂z T on the faces, the top face replaced by
+// top_flux [3][n_col]; halo_bottom, params as above.  The outputs alias nothing.  2 <= Nz <= 128.
+hipError_t launch_mpp_diagnose_flux(const float* u, const float* v, const float* T, const float* top_flux, const float* halo_bottom, float dz,
+                                    const float params[7], int convective_adjustment, float* uw, float* vw, float* wT, int Nz, int n_col,
+                                    hipStream_t stream);
 hipError_t launch_adam_step(float* w, const float* grad, float* m, float* v, float eta, float beta1, float beta2, float eps,
                             float beta1_t, float beta2_t, int n, hipStream_t stream);
 hipError_t launch_adam_ensemble(float* w, const float* grad, int grad_stride, float* m, float* v, const float* eta, float beta1, float beta2,

@@ -341,7 +341,7 @@ __global__ void __launch_bounds__(64) mpp_diffusion_generic_kernel(const float* 
         const float Ri0 = P.galpha_dz * dT / (du * du + dv * dv);
         kT[0] = Ri0 > 0.0f ? 0.0f : P.c;
     }
-    for (int k = 1; k < Nz; k++) mpp_face(P, pu[k] - pu[k - 1], pv[k] - pv[k - 1], pT[k] - pT[k - 1], kv[k], kT[k]);
+    for (int k = 1; k < Nz; k++) mpp_face(P, P.c, pu[k] - pu[k - 1], pv[k] - pv[k - 1], pT[k] - pT[k - 1], kv[k], kT[k]);
     const float T_bottom = pT[0];
     // T
     for (int k = 0; k < Nz; k++) {
@@ -381,6 +381,95 @@ hipError_t launch_mpp_diffusion(const float* u, const float* v, const float* T, 
     else if (aligned && Nz == 64) MPP_LAUNCH(64);
     else hipLaunchKernelGGL(mpp_diffusion_generic_kernel, grid, block, 0, stream, u, v, T, halo_bottom, P, uo, vo, To, Nz, n_col);
 #undef MPP_LAUNCH
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// diagnose_baseline_flux_uw / _vw / _wT (wind_mixing/src/NDE_oceananigans.jl:157-191): what the diffusivity-only model saves with every state.
+// Per column, on the Nz+1 faces (face 0 the bottom):  uw = −ν ∂z u,  vw = −ν ∂z v,  wT = −νT ∂z T  with the ν, νT of
+// modified_pacanowski_philander_diffusivity above (mpp_sweep.h: the same face function as the step, c = 1) and the (Center, Center, Face)
+// gradients (φ[f] − φ[f−1])/Δz — face 0 from the halo cells below (absent: zero-gradient fill) —, then the top face REPLACED by the given top
+// flux (`uw[end] = uw_flux`, :163, :173, :185-187), so no halo above is read.
+//
+// HBM-bound: 3·4·Nz bytes in, 3·4·(Nz+1) out per column.  One wave per workgroup stages 64 columns of the three fields in LDS rows of Nz+1
+// floats with coalesced loads; a lane walks its column upwards and overwrites slot k of each row with face k AFTER reading level k (the
+// padding slot takes face Nz), which leaves in LDS the exact image of the workgroup's contiguous, 16-byte-aligned span of each output
+// (64 (Nz+1) floats): it goes out as coalesced 16-byte pieces.  NZT = 0: Nz at run time (any 2 <= Nz <= 128).
+// ------------------------------------------------------------------------------------------------
+template <int NZT>
+__global__ void __launch_bounds__(64) mpp_diagnose_flux_kernel(const float* __restrict__ u, const float* __restrict__ v, const float* __restrict__ T,
+                                                               const float* __restrict__ top, const float* __restrict__ halo_bottom, MppParams P, float dz,
+                                                               float* __restrict__ uw, float* __restrict__ vw, float* __restrict__ wT, int Nz_rt, int n_col,
+                                                               int vec_in, int vec_out) {
+    extern __shared__ __attribute__((aligned(16))) float dg_smem[];
+    const int Nz = NZT ? NZT : Nz_rt, LD = Nz + 1, FS = 64 * LD;
+    const int lane = threadIdx.x;
+    const size_t col0 = (size_t)blockIdx.x * 64;
+    const int ncol = (int)min((size_t)64, (size_t)n_col - col0);
+    const float* srcs[3] = {u, v, T};
+    float* dsts[3] = {uw, vw, wT};
+    for (int f = 0; f < 3; f++) {
+        const float* s = srcs[f] + col0 * Nz;
+        float* d = dg_smem + f * FS;
+        if (vec_in) {                               // Nz % 4 == 0: the four floats of a piece lie in one row
+            for (int e = 4 * lane; e < ncol * Nz; e += 256) {
+                const co_f32x4 q = __builtin_nontemporal_load(reinterpret_cast<const co_f32x4*>(s + e));
+                float* t = d + e + e / Nz;
+                t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.w;
+            }
+        } else {
+            for (int e = lane; e < ncol * Nz; e += 64) d[e + e / Nz] = s[e];
+        }
+    }
+    __syncthreads();
+    if (lane < ncol) {
+        const size_t col = col0 + lane;
+        float* tu = dg_smem + lane * LD;
+        float* tv = tu + FS;
+        float* tT = tu + 2 * FS;
+        float u_lo = tu[0], v_lo = tv[0], T_lo = tT[0];
+        float a, b, c;
+        mpp_face_nu_grad(P, dz, true, halo_bottom ? u_lo - halo_bottom[col] : 0.0f, halo_bottom ? v_lo - halo_bottom[(size_t)n_col + col] : 0.0f,
+                         halo_bottom ? T_lo - halo_bottom[2 * (size_t)n_col + col] : 0.0f, a, b, c);
+        tu[0] = -a; tv[0] = -b; tT[0] = -c;
+#pragma unroll 8
+        for (int k = 1; k < Nz; k++) {
+            const float u_hi = tu[k], v_hi = tv[k], T_hi = tT[k];
+            mpp_face_nu_grad(P, dz, false, u_hi - u_lo, v_hi - v_lo, T_hi - T_lo, a, b, c);
+            tu[k] = -a; tv[k] = -b; tT[k] = -c;
+            u_lo = u_hi; v_lo = v_hi; T_lo = T_hi;
+        }
+        tu[Nz] = top[col]; tv[Nz] = top[(size_t)n_col + col]; tT[Nz] = top[2 * (size_t)n_col + col];
+    }
+    __syncthreads();
+    const int cnt = ncol * LD, nv = vec_out ? cnt / 4 : 0;
+    for (int f = 0; f < 3; f++) {
+        float* o = dsts[f] + col0 * LD;
+        const float* d = dg_smem + f * FS;
+        for (int i = lane; i < nv; i += 64) __builtin_nontemporal_store(*reinterpret_cast<const co_f32x4*>(d + 4 * i), reinterpret_cast<co_f32x4*>(o + 4 * i));
+        for (int e = 4 * nv + lane; e < cnt; e += 64) o[e] = d[e];
+    }
+}
+
+hipError_t launch_mpp_diagnose_flux(const float* u, const float* v, const float* T, const float* top_flux, const float* halo_bottom, float dz,
+                                    const float params[7], int convective_adjustment, float* uw, float* vw, float* wT, int Nz, int n_col,
+                                    hipStream_t stream) {
+    if (Nz < 2 || Nz > 128 || n_col < 1) return hipErrorInvalidValue;
+    const MppParams P = mpp_params(params, dz * dz, dz, convective_adjustment);          // (c = 1: the diagnosis takes no step)
+    const dim3 grid((n_col + 63) / 64), block(64);
+    const size_t lds = 3 * 64 * (size_t)(Nz + 1) * sizeof(float);
+    const int vec_in = Nz % 4 == 0 && (((uintptr_t)u | (uintptr_t)v | (uintptr_t)T) & 15) == 0;
+    const int vec_out = (((uintptr_t)uw | (uintptr_t)vw | (uintptr_t)wT) & 15) == 0;
+#define DG_LAUNCH(N) hipLaunchKernelGGL(mpp_diagnose_flux_kernel<N>, grid, block, lds, stream, u, v, T, top_flux, halo_bottom, P, dz, uw, vw, wT, Nz, n_col, vec_in, vec_out)
+    if (Nz == 16) DG_LAUNCH(16);
+    else if (Nz == 32) DG_LAUNCH(32);
+    else if (Nz == 64) DG_LAUNCH(64);
+    else {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mpp_diagnose_flux_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        DG_LAUNCH(0);
+    }
+#undef DG_LAUNCH
     return hipGetLastError();
 }
 

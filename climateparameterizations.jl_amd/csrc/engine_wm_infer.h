@@ -1,5 +1,6 @@
 // engine_wm_infer.h — embedded inference of the trained wind-mixing NDE (wind_mixing/src/NDE_oceananigans.jl:288-329, :380-405):
-// the three flux networks evaluated on an ocean column's u, v, T, optionally fused with the implicit diffusion step of that state.
+// the three flux networks evaluated on an ocean column's u, v, T, optionally fused with the implicit diffusion step of that state and / or
+// with the diagnosis of the total face fluxes diagnose_NN_flux_uw / _vw / _wT (:226-286).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mpp_sweep.h"
@@ -24,6 +25,11 @@ struct WmInferArgs {
     const float* halo_bottom;             // [3][n_col] or null
     MppParams mpp;
     float *u_out, *v_out, *T_out;
+    // flux diagnosis (diag = true): uw, vw, wT [n_col][33] of the state as given; mpp (its step is not used unless fused) and halo_bottom as
+    // above, halo_top [3][n_col] or null.  diag without fused writes no d/dz arrays (dz_* unused).
+    bool diag;
+    const float* halo_top;
+    float *uw, *vw, *wT;
 };
 
 // every pointer of the state and the outputs must be 16-byte aligned (hipErrorInvalidValue otherwise)

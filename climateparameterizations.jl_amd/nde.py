@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .config import MATRIX_ARITHMETIC_NAMES, NDEConfig, matrix_arithmetic_id, to_c_config
 
-KERNEL_IDS = {"forward": 0, "adjoint": 1, "reduce": 2, "rhs": 3, "infer": 4, "dw1": 5, "convadj": 6, "adam": 7, "impldiff": 8, "fc_embed": 9}
+KERNEL_IDS = {"forward": 0, "adjoint": 1, "reduce": 2, "rhs": 3, "infer": 4, "dw1": 5, "convadj": 6, "adam": 7, "impldiff": 8, "fc_embed": 9, "flux_diag": 10}
 ENGINE_AUTO, ENGINE_TILE16, ENGINE_REGTILE, ENGINE_FC32 = 0, 1, 2, 3
 
 
@@ -78,6 +78,36 @@ def check_wm_embed_arrays(Nz: int, n: int, state, top_flux, halo_bottom=None, dz
         for tj, b in outputs[i + 1:]:
             if overlap(o, b):
                 raise ValueError("%s overlaps %s" % (to, tj))
+
+
+def check_wm_diag_arrays(Nz: int, n: int, state, top_flux, halos=None, faces_out=None, dz_out=None, out=None):
+    """Shape and alias rules of `wm_diagnose_flux` / `wm_embedded_step_flux` / `mpp_diagnose_flux` (no GPU needed): those of
+    `check_wm_embed_arrays` for state, top_flux, dz_out and out; halos = None or (halo_bottom, halo_top), each [3, n] or None; faces_out =
+    three [n, Nz + 1] arrays (uw, vw, wT) that overlap nothing."""
+    if halos is not None and len(halos) != 2:
+        raise ValueError("halos must be (halo_bottom, halo_top); either may be None")
+    hb, ht = halos if halos is not None else (None, None)
+    check_wm_embed_arrays(Nz, n, state, top_flux, hb, dz_out, out)
+    if ht is not None and tuple(ht.shape) != (3, n):
+        raise ValueError("halo_top: expected shape %s, got %s" % ((3, n), tuple(ht.shape)))
+    if faces_out is None:
+        return
+    if len(faces_out) != 3:
+        raise ValueError("faces_out must be three arrays (uw, vw, wT)")
+    tags = ("uw", "vw", "wT")
+    for tg, a in zip(tags, faces_out):
+        if tuple(a.shape) != (n, Nz + 1):
+            raise ValueError("%s: expected shape %s, got %s" % (tg, (n, Nz + 1), tuple(a.shape)))
+
+    def overlap(a, b):
+        (pa, na), (pb, nb) = _span(a), _span(b)
+        return pa < pb + nb and pb < pa + na
+    others = list(zip(("u", "v", "T"), state)) + [("top_flux", top_flux)] + [(nm, a) for nm, a in (("halo_bottom", hb), ("halo_top", ht)) if a is not None]
+    others += list(zip(("dz_uw", "dz_vw", "dz_wT"), dz_out or ())) + list(zip(("u_out", "v_out", "T_out"), out or ()))
+    for i, (tg, a) in enumerate(zip(tags, faces_out)):
+        for nm, b in others + list(zip(tags[i + 1:], faces_out[i + 1:])):
+            if overlap(a, b):
+                raise ValueError("%s overlaps %s: the face arrays may alias nothing" % (tg, nm))
 
 
 def check_fc_embed_arrays(Nz: int, n: int, T, top_flux, halos=None, dz_out=None, T_out=None, faces_out=None):
@@ -575,6 +605,114 @@ class ColumnNDE:
         _lib.check(self._L.colnde_wm_embedded_step(self._h, _ptr(w), _ptr(u), _ptr(v), _ptr(T), _ptr(top_flux), _ptr(hb), float(Lz), dt, pr, int(ca),
                                                    _ptr(dz[0]), _ptr(dz[1]), _ptr(dz[2]), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), n))
         return dz, res
+
+    def wm_diagnose_flux(self, weights, u, v, T, top_flux, Lz: float, params, convective_adjustment: bool = False, halos=None, faces_out=None):
+        """`diagnose_NN_flux_uw`, `_vw`, `_wT` (wind_mixing/src/NDE_oceananigans.jl:226-286): the total fluxes (uw, vw, wT), each [n][Nz+1]
+        (face 0 the bottom), of the state as given: [0; inv(scaling).(NN) .- inv(scaling)(0); top] − ν ∂z φ with the diffusivities of
+        `implicit_diffusion` (params, convective_adjustment as there; Δz = Lz/Nz).  halos = None or (halo_bottom, halo_top), each [3][n] or
+        None (zero-gradient fill).  numpy arrays or device tensors (`faces_out`: three device tensors that alias nothing)."""
+        return self._wm_diag(weights, u, v, T, top_flux, Lz, None, params, convective_adjustment, halos, faces_out, None, None)
+
+    def wm_embedded_step_flux(self, weights, u, v, T, top_flux, Lz: float, dt: float, params, convective_adjustment: bool = False, halos=None,
+                              dz_out=None, out=None, faces_out=None):
+        """`wm_embedded_step` and `wm_diagnose_flux` of the same state as given in one call (one read of the state): returns
+        ((∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN), (u′, v′, T′), (uw, vw, wT)).  The step reads halos[0] only; `out` tensors may be their own inputs."""
+        return self._wm_diag(weights, u, v, T, top_flux, Lz, float(dt), params, convective_adjustment, halos, faces_out, dz_out, out)
+
+    def _wm_diag(self, weights, u, v, T, top_flux, Lz, dt, params, ca, halos, faces_out, dz_out, out):
+        Nz = self.cfg.Nz
+        step = dt is not None
+        pr = (ctypes.c_float * 7)(*[float(x) for x in params])
+        if halos is not None and len(halos) != 2:
+            raise ValueError("halos must be (halo_bottom, halo_top); either may be None")
+        hb, ht = halos if halos is not None else (None, None)
+        if _is_torch(T):
+            import torch
+            n = T.shape[0]
+            check_wm_diag_arrays(Nz, n, (u, v, T), top_flux, halos, faces_out, dz_out, out)
+            for a in (u, v, T):
+                self._chk_dev(a, (n, Nz))
+            self._chk_dev(top_flux, (3, n))
+            self._chk_dev(weights, (self.n_params,))
+            for hl in (hb, ht):
+                if hl is not None:
+                    self._chk_dev(hl, (3, n))
+            if faces_out is None:
+                faces_out = tuple(torch.empty((n, Nz + 1), dtype=T.dtype, device=T.device) for _ in range(3))
+            if step and dz_out is None:
+                dz_out = tuple(torch.empty_like(T) for _ in range(3))
+            if step and out is None:
+                out = tuple(torch.empty_like(T) for _ in range(3))
+            for a in faces_out:
+                self._chk_dev(a, (n, Nz + 1))
+            for a in (tuple(dz_out) + tuple(out)) if step else ():
+                self._chk_dev(a, (n, Nz))
+            self.use_torch_stream()
+            P = lambda a: a.data_ptr() if a is not None else None
+            if not step:
+                _lib.check(self._L.colnde_wm_diagnose_flux_dev(self._h, P(weights), P(u), P(v), P(T), P(top_flux), P(hb), P(ht), float(Lz), pr, int(bool(ca)),
+                                                               P(faces_out[0]), P(faces_out[1]), P(faces_out[2]), n))
+                return tuple(faces_out)
+            _lib.check(self._L.colnde_wm_embedded_step_flux_dev(
+                self._h, P(weights), P(u), P(v), P(T), P(top_flux), P(hb), P(ht), float(Lz), dt, pr, int(bool(ca)), P(dz_out[0]), P(dz_out[1]), P(dz_out[2]),
+                P(out[0]), P(out[1]), P(out[2]), P(faces_out[0]), P(faces_out[1]), P(faces_out[2]), n))
+            return tuple(dz_out), tuple(out), tuple(faces_out)
+        if dz_out is not None or out is not None or faces_out is not None:
+            raise ValueError("dz_out / out / faces_out are for device tensors; host arrays are returned")
+        T = _f32(T)
+        n = T.shape[0]
+        u, v, T, top_flux = _f32(u), _f32(v), _f32(T), _f32(top_flux)
+        hb = _f32(hb) if hb is not None else None
+        ht = _f32(ht) if ht is not None else None
+        check_wm_diag_arrays(Nz, n, (u, v, T), top_flux, None if halos is None else (hb, ht))
+        w = _f32(weights, (self.n_params,))
+        faces = tuple(np.empty((n, Nz + 1), np.float32) for _ in range(3))
+        if not step:
+            _lib.check(self._L.colnde_wm_diagnose_flux(self._h, _ptr(w), _ptr(u), _ptr(v), _ptr(T), _ptr(top_flux), _ptr(hb), _ptr(ht), float(Lz), pr,
+                                                       int(bool(ca)), _ptr(faces[0]), _ptr(faces[1]), _ptr(faces[2]), n))
+            return faces
+        dz, res = tuple(np.empty_like(T) for _ in range(3)), tuple(np.empty_like(T) for _ in range(3))
+        _lib.check(self._L.colnde_wm_embedded_step_flux(self._h, _ptr(w), _ptr(u), _ptr(v), _ptr(T), _ptr(top_flux), _ptr(hb), _ptr(ht), float(Lz), dt, pr,
+                                                        int(bool(ca)), _ptr(dz[0]), _ptr(dz[1]), _ptr(dz[2]), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]),
+                                                        _ptr(faces[0]), _ptr(faces[1]), _ptr(faces[2]), n))
+        return dz, res, faces
+
+    def mpp_diagnose_flux(self, u, v, T, top_flux, dz: float, params, convective_adjustment: bool = False, halo_bottom=None, faces_out=None):
+        """`diagnose_baseline_flux_uw`, `_vw`, `_wT` (wind_mixing/src/NDE_oceananigans.jl:157-191): (uw, vw, wT), each [n][Nz+1], of the
+        diffusivity-only model: −ν ∂z u, −ν ∂z v, −νT ∂z T with the top face replaced by top_flux [3][n].  params, halo_bottom as
+        `implicit_diffusion`; no networks, any Nz.  numpy arrays or device tensors."""
+        Nz = self.cfg.Nz
+        pr = (ctypes.c_float * 7)(*[float(x) for x in params])
+        if _is_torch(T):
+            import torch
+            n = T.shape[0]
+            check_wm_diag_arrays(Nz, n, (u, v, T), top_flux, (halo_bottom, None), faces_out)
+            for a in (u, v, T):
+                self._chk_dev(a, (n, Nz))
+            self._chk_dev(top_flux, (3, n))
+            if halo_bottom is not None:
+                self._chk_dev(halo_bottom, (3, n))
+            if faces_out is None:
+                faces_out = tuple(torch.empty((n, Nz + 1), dtype=T.dtype, device=T.device) for _ in range(3))
+            for a in faces_out:
+                self._chk_dev(a, (n, Nz + 1))
+            self.use_torch_stream()
+            _lib.check(self._L.colnde_mpp_diagnose_flux_dev(self._h, u.data_ptr(), v.data_ptr(), T.data_ptr(), top_flux.data_ptr(),
+                                                            halo_bottom.data_ptr() if halo_bottom is not None else None, float(dz), pr,
+                                                            int(bool(convective_adjustment)), faces_out[0].data_ptr(), faces_out[1].data_ptr(),
+                                                            faces_out[2].data_ptr(), n))
+            return tuple(faces_out)
+        if faces_out is not None:
+            raise ValueError("faces_out is for device tensors; host arrays are returned")
+        T = _f32(T)
+        n = T.shape[0]
+        u, v, T, top_flux = _f32(u), _f32(v), _f32(T), _f32(top_flux)
+        hb = _f32(halo_bottom) if halo_bottom is not None else None
+        check_wm_diag_arrays(Nz, n, (u, v, T), top_flux, (hb, None))
+        faces = tuple(np.empty((n, Nz + 1), np.float32) for _ in range(3))
+        _lib.check(self._L.colnde_mpp_diagnose_flux(self._h, _ptr(u), _ptr(v), _ptr(T), _ptr(top_flux), _ptr(hb), float(dz), pr,
+                                                    int(bool(convective_adjustment)), _ptr(faces[0]), _ptr(faces[1]), _ptr(faces[2]), n))
+        return faces
 
     def fc_embedded_step(self, weights, T, top_flux, Lz: float, dt: float, K: float, halos=None, diagnose: bool = False, dz_out=None, T_out=None,
                          faces_out=None):

@@ -390,6 +390,44 @@ def progress_neural_network(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz:
     return tuple(d.reshape(shape) for d in dz), tuple(a.reshape(shape) for a in st)
 
 
+def _mpp_tuple(p, constants):
+    return (_named(p, "ν₀", "nu0"), _named(p, "ν₋", "nu_minus"), _named(p, "ΔRi", "dRi"), _named(p, "Riᶜ", "Ric"), _named(p, "Pr"),
+            _named(constants, "α", "alpha"), _named(constants, "g"))
+
+
+def _diag_args(u, v, T, top_fluxes, halos):
+    u, v, T = (np.asarray(a, dtype=np.float32) for a in (u, v, T))
+    shape = T.shape
+    u2, v2, T2 = (np.ascontiguousarray(a.reshape(-1, shape[-1])) for a in (u, v, T))
+    n = T2.shape[0]
+    top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_fluxes, np.float32).reshape(3, -1), (3, n)))
+    if halos is not None:
+        if len(halos) != 2:
+            raise ValueError("halos must be (halo_bottom, halo_top); either may be None")
+        halos = tuple(None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32).reshape(3, -1), (3, n))) for a in halos)
+    return shape[:-1] + (shape[-1] + 1,), u2, v2, T2, top, halos
+
+
+def diagnose_NN_flux(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz: float, p: dict, constants, convective_adjustment: bool = False, halos=None):
+    """`diagnose_NN_flux_uw`, `diagnose_NN_flux_vw`, `diagnose_NN_flux_wT` (wind_mixing/src/NDE_oceananigans.jl:226-286): the total fluxes
+    (uw, vw, wT) on the Nz + 1 faces ([n, Nz + 1], or [Nz + 1] for one column) that the embedding saves with a state.  `p`, `constants` as
+    `modified_pacanowski_philander_step`; top_fluxes as `NN_forcings`; halos = None or (halo_bottom, halo_top): the u, v, T halo cells
+    below and above the column, each [3, n] (or [3]) or None (zero-gradient fill)."""
+    shape, u2, v2, T2, top, halos = _diag_args(u, v, T, top_fluxes, halos)
+    faces = engine.wm_diagnose_flux(weights, u2, v2, T2, top, Lz, _mpp_tuple(p, constants), convective_adjustment, halos)
+    return tuple(f.reshape(shape) for f in faces)
+
+
+def diagnose_baseline_flux(engine: ColumnNDE, u, v, T, top_fluxes, Lz: float, p: dict, constants, convective_adjustment: bool = False, halos=None):
+    """`diagnose_baseline_flux_uw`, `_vw`, `_wT` (wind_mixing/src/NDE_oceananigans.jl:157-191): the same for the diffusivity-only model,
+    (uw, vw, wT) = (−ν ∂z u, −ν ∂z v, −νT ∂z T) with the top face replaced by the top flux.  Arguments as `diagnose_NN_flux` without the
+    weights; of halos only halo_bottom is read (the one face that would see halo_top is replaced)."""
+    shape, u2, v2, T2, top, halos = _diag_args(u, v, T, top_fluxes, halos)
+    faces = engine.mpp_diagnose_flux(u2, v2, T2, top, float(Lz) / T2.shape[1], _mpp_tuple(p, constants), convective_adjustment,
+                                     None if halos is None else halos[0])
+    return tuple(f.reshape(shape) for f in faces)
+
+
 def modified_pacanowski_philander_step(engine: ColumnNDE, u, v, T, dt: float, dz: float, p: dict, constants, convective_adjustment: bool = False,
                                        halo_bottom=None):
     """`modified_pacanowski_philander!(model, constants, Δt, p, convective_adjustment)` (wind_mixing/src/NDE_oceananigans.jl:61-101;

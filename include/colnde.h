@@ -299,6 +299,53 @@ int colnde_wm_embedded_step(colnde_handle* h, const float* weights, const float*
                             const float* halo_bottom, float Lz, float dt, const float params[7], int convective_adjustment, float* dz_uw,
                             float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, int n_columns);
 
+/* What the wind-mixing embedding saves with every state: the TOTAL fluxes uw, vw, wT on the Nz+1 faces (face 0 the bottom), read back as `uw`, `vw`,
+ * `wT` by solve_oceananigans_modified_pacanowski_philander_nn and the comparison scripts.  Per column, on u, v, T [Nz] AS GIVEN (ocean units,
+ * k = 0 deepest), dz = Lz/Nz:
+ *   gradients  g_φ[f] = (φ[f] − φ[f−1])/dz on the Nz+1 faces ((Center, Center, Face) ∂z; :159, :232); the two end faces read the halo cells:
+ *              halo_bottom [3][n_col] (u, v, T below k = 0, as colnde_implicit_diffusion) and halo_top [3][n_col] (above k = Nz−1), either NULL =
+ *              the zero-gradient fill;
+ *   diffusivities of modified_pacanowski_philander_diffusivity (:17-58), exactly those of colnde_implicit_diffusion: ν[f] = ν₀ + ν₋ tanh_step((Ri_f −
+ *              Riᶜ)/ΔRi) on faces 1..Nz−1, 0 on both end faces; νT = ν/Pr, or under convective_adjustment Ri_f > 0 ? ν/Pr : 1 on EVERY face, the
+ *              ends included (their Ri from the halo cells; with the fill it is 0/0 = NaN and `NaN > 0` is false, as in Julia: νT = 1);
+ *   colnde_wm_diagnose_flux — diagnose_NN_flux_uw / _vw / _wT (wind_mixing/src/NDE_oceananigans.jl:226-286): NN faces F = [0; inv(scaling).(y) .−
+ *              inv(scaling)(0); top_flux] (:235, :253, :274-276 with enforce_fluxes_* :220-224), y the net's 31 outputs on the scaled [u; v; T] as
+ *              colnde_wm_infer_dz_flux evaluates them, each operation of (σ y + μ) − (σ·0 + μ) rounded to float32 — NOT the forcing chain's
+ *              convention, which subtracts inv(scaling) of the already unscaled first element (:292, :301), so the ∂z arrays do not integrate to
+ *              these faces;  uw = F_uw − ν g_u,  vw = F_vw − ν g_v,  wT = F_wT − νT g_T;
+ *   colnde_mpp_diagnose_flux — diagnose_baseline_flux_uw / _vw / _wT (:157-191), the diffusivity-only model: uw = −ν g_u, vw = −ν g_v, wT = −νT g_T,
+ *              then the top face REPLACED by top_flux (`uw[end] = uw_flux`), so no halo above is read and the call has no halo_top.  No networks:
+ *              any handle kind, every Nz colnde_implicit_diffusion accepts (the handle's Nz), dz given; 16-byte alignment is used when present,
+ *              not required;
+ *   colnde_wm_embedded_step_flux — colnde_wm_embedded_step and colnde_wm_diagnose_flux of the SAME state as given in one call: the ∂z arrays and
+ *              u′, v′, T′ are the bits of colnde_wm_embedded_step_dev, the faces the bits of colnde_wm_diagnose_flux_dev.  One launch that reads
+ *              the state once (measured against the two launches in DESIGN §4j and kept).
+ * u, v, T, the ∂z arrays, u_out, v_out, T_out: [n_col][Nz]; top_flux, halo_bottom, halo_top: [3][n_col]; uw, vw, wT: [n_col][Nz+1]; params = {nu0,
+ * nu_minus, dRi, Ric, Pr, alpha, g}.  The wm calls need every state and output base pointer 16-byte aligned (a row of Nz+1 floats is not: only
+ * the base).  u_out, v_out, T_out may each alias its own input; the ∂z arrays and the faces alias nothing.  n_columns is independent of the handle's
+ * own column count.  The wm calls refuse, with the reason in colnde_last_error, what colnde_wm_infer_dz_flux refuses: anything but a single-model
+ * wind-mixing handle with Nz = 32 and three 96-50-20-31 networks, and a handle with smooth_NN; also a misaligned pointer.  They run on the f32
+ * matrix pipe under either matrix_arithmetic (colnde_describe: wm_infer=f32).  All six are timed under colnde_kernel_time slot 10. */
+int colnde_wm_diagnose_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T, const float* d_top_flux,
+                                const float* d_halo_bottom /* nullable */, const float* d_halo_top /* nullable */, float Lz, const float params[7],
+                                int convective_adjustment, float* d_uw, float* d_vw, float* d_wT, int n_columns);
+int colnde_wm_diagnose_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                            const float* halo_bottom, const float* halo_top, float Lz, const float params[7], int convective_adjustment, float* uw,
+                            float* vw, float* wT, int n_columns);   /* host arrays; synchronises */
+int colnde_wm_embedded_step_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                                     const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt,
+                                     const float params[7], int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out,
+                                     float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns);
+int colnde_wm_embedded_step_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                                 const float* halo_bottom, const float* halo_top, float Lz, float dt, const float params[7], int convective_adjustment,
+                                 float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, float* uw, float* vw, float* wT,
+                                 int n_columns);   /* host arrays; synchronises */
+int colnde_mpp_diagnose_flux_dev(colnde_handle* h, const float* d_u, const float* d_v, const float* d_T, const float* d_top_flux,
+                                 const float* d_halo_bottom /* nullable */, float dz, const float params[7], int convective_adjustment, float* d_uw,
+                                 float* d_vw, float* d_wT, int n_columns);
+int colnde_mpp_diagnose_flux(colnde_handle* h, const float* u, const float* v, const float* T, const float* top_flux, const float* halo_bottom, float dz,
+                             const float params[7], int convective_adjustment, float* uw, float* vw, float* wT, int n_columns);   /* host arrays */
+
 /* The free-convection embedding's per-iteration work and its diagnosed flux (free_convection/src/oceananigans_nn.jl; the same over 96 x 96 columns
  * in free_convection/double_gyre_nn.jl:211-234), per column, on T [Nz] AS GIVEN (k = 0 deepest, the units colnde_infer_dz_wT takes), dz = Lz/Nz,
  * c = dt/dz²:
@@ -469,7 +516,8 @@ int colnde_closure_loss_grad(colnde_handle* h, const float* params, const float 
 /* ---- measurement: HIP-event timing of the handle's kernels on its stream.
  * which: 0 = forward solve kernel, 1 = adjoint kernel, 2 = gradient reduce, 3 = rhs, 4 = inference,
  * 5 = streaming dW1 GEMM (regtile engine only), 6 = convective adjustment, 7 = ADAM step, 8 = implicit diffusion,
- * 9 = free-convection embedded step / diagnose_wT.
+ * 9 = free-convection embedded step / diagnose_wT, 10 = wind-mixing flux diagnoses (colnde_wm_diagnose_flux, colnde_wm_embedded_step_flux,
+ * colnde_mpp_diagnose_flux).
  * Returns accumulated milliseconds and launch count since the last reset (synchronises the stream). */
 int colnde_set_profiling(colnde_handle* h, int enabled);
 int colnde_kernel_time(colnde_handle* h, int which, float* ms_total, int* n_launches);

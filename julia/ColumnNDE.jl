@@ -389,6 +389,51 @@ function progress_neural_network(h::Handle, θ::Vector{Float32}, u::Matrix{Float
     nothing
 end
 
+"diagnose_NN_flux_uw, diagnose_NN_flux_vw, diagnose_NN_flux_wT (wind_mixing/src/NDE_oceananigans.jl:226-286) of every column: the total
+fluxes the embedding saves with a state, each (Nz+1, n_columns); arguments as NN_forcings and modified_pacanowski_philander!, halo_top like
+halo_bottom (the cells above the column)"
+function diagnose_NN_flux(h::Handle, θ::Vector{Float32}, u::Matrix{Float32}, v::Matrix{Float32}, T::Matrix{Float32}, top_fluxes::Matrix{Float32},
+                          Lz, constants, p, convective_adjustment; halo_bottom=nothing, halo_top=nothing)
+    params = Float32[p["ν₀"], p["ν₋"], p["ΔRi"], p["Riᶜ"], p["Pr"], constants.α, constants.g]
+    hb = halo_bottom === nothing ? C_NULL : pointer(halo_bottom); ht = halo_top === nothing ? C_NULL : pointer(halo_top)
+    uw, vw, wT = (Matrix{Float32}(undef, size(T, 1) + 1, size(T, 2)) for _ in 1:3)
+    GC.@preserve halo_bottom halo_top check(ccall((:colnde_wm_diagnose_flux, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Ptr{Float32}, Cint,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint),
+        h.ptr, θ, u, v, T, top_fluxes, hb, ht, Lz, params, convective_adjustment ? 1 : 0, uw, vw, wT, size(T, 2)))
+    (uw, vw, wT)
+end
+
+"progress_neural_network and diagnose_NN_flux_* of the same state in one call: as progress_neural_network, and returns (uw, vw, wT) of the
+state as given (before the step)"
+function progress_neural_network_flux(h::Handle, θ::Vector{Float32}, u::Matrix{Float32}, v::Matrix{Float32}, T::Matrix{Float32},
+                                      top_fluxes::Matrix{Float32}, Lz, constants, Δt, p, convective_adjustment,
+                                      ∂z_uw_NN::Matrix{Float32}, ∂z_vw_NN::Matrix{Float32}, ∂z_wT_NN::Matrix{Float32}; halo_bottom=nothing, halo_top=nothing)
+    params = Float32[p["ν₀"], p["ν₋"], p["ΔRi"], p["Riᶜ"], p["Pr"], constants.α, constants.g]
+    hb = halo_bottom === nothing ? C_NULL : pointer(halo_bottom); ht = halo_top === nothing ? C_NULL : pointer(halo_top)
+    uw, vw, wT = (Matrix{Float32}(undef, size(T, 1) + 1, size(T, 2)) for _ in 1:3)
+    GC.@preserve halo_bottom halo_top check(ccall((:colnde_wm_embedded_step_flux, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Ptr{Float32}, Cint,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint),
+        h.ptr, θ, u, v, T, top_fluxes, hb, ht, Lz, Δt, params, convective_adjustment ? 1 : 0, ∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN, u, v, T, uw, vw, wT,
+        size(T, 2)))
+    (uw, vw, wT)
+end
+
+"diagnose_baseline_flux_uw, _vw, _wT (wind_mixing/src/NDE_oceananigans.jl:157-191): (−ν ∂z u, −ν ∂z v, −νT ∂z T) on the faces with the top
+face replaced by the top flux, each (Nz+1, n_columns); no networks"
+function diagnose_baseline_flux(h::Handle, u::Matrix{Float32}, v::Matrix{Float32}, T::Matrix{Float32}, top_fluxes::Matrix{Float32}, Δz, constants, p,
+                                convective_adjustment; halo_bottom=nothing)
+    params = Float32[p["ν₀"], p["ν₋"], p["ΔRi"], p["Riᶜ"], p["Pr"], constants.α, constants.g]
+    hb = halo_bottom === nothing ? C_NULL : pointer(halo_bottom)
+    uw, vw, wT = (Matrix{Float32}(undef, size(T, 1) + 1, size(T, 2)) for _ in 1:3)
+    GC.@preserve halo_bottom check(ccall((:colnde_mpp_diagnose_flux, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Ptr{Float32}, Cint,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint),
+        h.ptr, u, v, T, top_fluxes, hb, Δz, params, convective_adjustment ? 1 : 0, uw, vw, wT, size(T, 2)))
+    (uw, vw, wT)
+end
+
 "Flux.Optimise.ADAM apply!/update! on device pointers (θ, ∇, m, v resident on the GPU); βᵗ = running powers kept by the caller"
 function adam_step!(h::Handle, dθ::Ptr{Float32}, dg::Ptr{Float32}, dm::Ptr{Float32}, dv::Ptr{Float32}, η, β, ϵ, βᵗ, n)
     check(ccall((:colnde_adam_step_dev, libcolnde), Cint,
