@@ -125,6 +125,9 @@ struct colnde_handle {
     int n_models = 1;
     std::vector<RtPhys> phys_host;  // per-model closure constants (closure_constants), and their device copy
     RtPhys* d_phys = nullptr;
+    std::vector<float> phys_raw;    // ... as given: [n_models][5] {nu0, nu_minus, dRi, Ric, Pr} (empty: cfg's constants for every model)
+    MppParams* d_wm_ens_mpp = nullptr;          // colnde_ensemble_wm_embedded: the per-model sweep constants on the device, and what they hold
+    std::vector<MppParams> wm_ens_mpp_host;
     RtEns ens;                      // per-model strides of the buffers a model owns
     size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)
     int ens_rkc_stages = 0;         // RKC2, automatic stage count: the largest any model needs (refresh_rkc)
@@ -632,7 +635,7 @@ extern "C" void colnde_destroy(colnde_handle* h) {
     drain_events(h);
     void* ptrs[] = {h->d_rt_tapez, h->d_rt_tape, h->d_rt_tape2, h->d_rt_slab, h->d_wimg, h->d_w, h->d_wf, h->d_wb, h->d_x0, h->d_bcs, h->d_truth, h->d_sol, h->d_tape, h->d_slab, h->d_out,
                     h->d_times, h->d_partial, h->d_tmp_a, h->d_tmp_b, h->d_tmp_c, h->d_tiles, h->d_bias_zoff, h->d_bias_goff, h->d_dwtape, h->d_macros, h->d_t16_ztape, h->d_rkc, h->d_ag, h->d_sf, h->d_sb,
-                    h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_masks, h->d_fc_switch, h->d_fc_lam, h->d_fc_simgf, h->d_fc_simgb, h->d_phys,
+                    h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_masks, h->d_fc_switch, h->d_fc_lam, h->d_fc_simgf, h->d_fc_simgb, h->d_phys, h->d_wm_ens_mpp,
                     h->d_cl_tape, h->d_cl_rows, h->d_cl_params};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -1504,6 +1507,8 @@ static int ens_upload_physics(colnde_handle* h, const float* physics) {
     HIPCHK(hipMemcpyAsync(h->d_phys, ph.data(), ph.size() * sizeof(RtPhys), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->phys_host.swap(ph);
+    if (physics) h->phys_raw.assign(physics, physics + (size_t)5 * h->n_models);
+    else h->phys_raw.clear();
     return 0;
 }
 
@@ -2385,6 +2390,147 @@ extern "C" int colnde_wm_embedded_step_flux(colnde_handle* h, const float* weigh
                         v_out, T_out, uw, vw, wT, n_columns);
 }
 
+// ---- the K models of an ensemble in the embedding at once (engine_wm_infer.hip: wm_infer_ens_kernel) -------------------------------
+// {nu0, nu_minus, dRi, Ric, Pr, alpha, g} of model k as the handle holds them (colnde_create_ensemble / colnde_ensemble_set_physics; cfg.alpha, cfg.g)
+static void wm_ens_model_params(const colnde_handle* h, int k, float out[7]) {
+    const colnde_config c = model_config(&h->cfg, h->phys_raw.empty() ? nullptr : h->phys_raw.data(), k);
+    out[0] = c.nu0; out[1] = c.nu_minus; out[2] = c.dRi; out[3] = c.Ric; out[4] = c.Pr; out[5] = c.alpha; out[6] = c.g;
+}
+
+// everything the call refuses that does not depend on where the arrays live; host: the host twin's arrays (no alignment rule of their own)
+static int wm_ens_check(colnde_handle* h, const char* fn, const float* weights, const float* u, const float* v, const float* T, const float* top_flux, float Lz,
+                        float dt, const float* params, const float* dz_uw, const float* dz_vw, const float* dz_wT, const float* u_out, const float* v_out,
+                        const float* T_out, const float* uw, const float* vw, const float* wT, int n_columns, bool host) {
+    if (!h) return fail("null handle");
+    if (h->closure)
+        return fail("%s takes K weight vectors, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", fn,
+                    h->n_models);
+    const colnde_config& c = h->cfg;
+    if (c.model != COLNDE_MODEL_WIND_MIXING)
+        return fail("%s needs a wind-mixing handle (three flux networks on [u; v; T]); a free-convection handle has colnde_infer_forcing", fn);
+    if (c.smooth_NN)
+        return fail("%s: the embedding has no smoothing filter (NDE_oceananigans.jl:288-329 apply the networks unfiltered), so a handle with smooth_NN is refused", fn);
+    if (!(c.Nz == WM_NZ && c.n_layers == 3 && c.layer_sizes[0] == 3 * WM_NZ && c.layer_sizes[1] == WM_H1 && c.layer_sizes[2] == WM_H2 &&
+          c.layer_sizes[3] == WM_NZ - 1 && c.activations[2] == COLNDE_ACT_IDENTITY)) {
+        std::string shape;
+        for (int l = 0; l <= c.n_layers; l++) shape += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
+        return fail("%s covers Nz = 32 with three 96-50-20-31 networks and an identity output layer; this handle has Nz = %d, networks %s, output activation %d", fn,
+                    c.Nz, shape.c_str(), c.activations[c.n_layers - 1]);
+    }
+    if (!weights || !u || !v || !T || !top_flux || !dz_uw || !dz_vw || !dz_wT) return fail("null pointer argument");
+    const int n_step = (u_out != nullptr) + (v_out != nullptr) + (T_out != nullptr), n_flux = (uw != nullptr) + (vw != nullptr) + (wT != nullptr);
+    if (n_step != 0 && n_step != 3)
+        return fail("%s: u_out, v_out, T_out are one output group — all three given (the implicit step is taken) or all three NULL (no step); %d of 3 given", fn, n_step);
+    if (n_flux != 0 && n_flux != 3)
+        return fail("%s: uw, vw, wT are one output group — all three given (the face diagnosis) or all three NULL; %d of 3 given", fn, n_flux);
+    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
+    if (n_step && !(dt > 0.0f)) return fail("%s: dt > 0 required when a step is asked for (u_out, v_out, T_out given); dt = %g", fn, dt);
+    for (int k = 0; k < h->n_models; k++) {
+        float own[7];
+        const float* p = params ? params + (size_t)7 * k : own;
+        if (!params) wm_ens_model_params(h, k, own);
+        if (n_step && (!(p[0] >= 0.0f) || !(p[1] >= 0.0f))) return fail("nu0 >= 0 and nu_minus >= 0 required (the tridiagonal must stay diagonally dominant)");
+        if (!(p[2] != 0.0f) || !(p[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
+    }
+    if (!host) {
+        const void* const ptrs[12] = {u, v, T, dz_uw, dz_vw, dz_wT, u_out, v_out, T_out, uw, vw, wT};
+        for (const void* p : ptrs)
+            if ((uintptr_t)p & 15) return fail("%s: the state and output arrays must be 16-byte aligned", fn);
+    }
+    return 0;
+}
+
+// the device array [K] of the sweeps' constants: uploaded when it differs from what the device holds (an embedding calls with the same constants every iteration)
+static int wm_ens_upload_mpp(colnde_handle* h, const float* params, bool step, float dt, float dz, int ca) {
+    const size_t K = (size_t)h->n_models;
+    std::vector<MppParams> P(K);
+    for (size_t k = 0; k < K; k++) {
+        float own[7];
+        const float* p = params ? params + 7 * k : own;
+        if (!params) wm_ens_model_params(h, (int)k, own);
+        P[k] = mpp_params(p, step ? dt : dz * dz, dz, ca);            // (without a step c is not read: 1, as the single-model diagnosis passes it)
+    }
+    if (h->d_wm_ens_mpp && h->wm_ens_mpp_host.size() == K && !memcmp(h->wm_ens_mpp_host.data(), P.data(), K * sizeof(MppParams))) return 0;
+    if (!h->d_wm_ens_mpp) HIPCHK(hipMalloc((void**)&h->d_wm_ens_mpp, K * sizeof(MppParams)));
+    // (kernels in flight on the stream may still read the previous table: the copy is ordered on the stream and completed before returning)
+    h->wm_ens_mpp_host.clear();
+    HIPCHK(hipMemcpyAsync(h->d_wm_ens_mpp, P.data(), K * sizeof(MppParams), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->wm_ens_mpp_host.swap(P);
+    return 0;
+}
+
+static int wm_ens_grid_cap() {
+    const char* e = getenv("COLNDE_WM_ENS_GRID");      // test override: at most this many workgroups (several models per workgroup at small K)
+    return e && *e ? std::max(0, atoi(e)) : 0;
+}
+
+extern "C" int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+                                               const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt,
+                                               const float* params, int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT,
+                                               float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
+    if (wm_ens_check(h, __func__, d_weights, d_u, d_v, d_T, d_top_flux, Lz, dt, params, d_dz_uw, d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT,
+                     n_columns, false))
+        return 1;
+    HIPCHK(hipSetDevice(h->device));
+    const bool step = d_u_out != nullptr;
+    if (wm_ens_upload_mpp(h, params, step, dt, Lz / (float)WM_NZ, convective_adjustment)) return 1;
+    WmEnsArgs a = {};
+    for (int i = 0; i < 6; i++) { a.mu[i] = h->cfg.mu[i]; a.sigma[i] = h->cfg.sigma[i]; }
+    a.act1 = h->cfg.activations[0];
+    a.act2 = h->cfg.activations[1];
+    a.n_models = h->n_models; a.weights = d_weights; a.w_stride = (size_t)h->m.n_params;
+    a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top; a.Lz = Lz; a.mpp = h->d_wm_ens_mpp;
+    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT;
+    a.fused = step; a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
+    a.diag = d_uw != nullptr; a.uw = d_uw; a.vw = d_vw; a.wT = d_wT;
+    a.n_col = n_columns;
+    a.grid_cap = wm_ens_grid_cap();
+    // One launch at every size, by measurement (profiles/wm_ens_embed_rate.json)
+    Timed tm(h, K_FLUXDIAG);
+    hipError_t e = launch_wm_infer_ens(a, h->stream);
+    if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", __func__, hipGetErrorString(e));
+    return 0;
+}
+
+// host arrays: one scratch of [u | v | T | dz_uw | dz_vw | dz_wT | faces(3 x K n 33, padded) | top(3 n) | halo_bottom(K 3 n) | halo_top(K 3 n)], the step in place
+extern "C" int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
+                                           const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params, int convective_adjustment,
+                                           float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, float* uw, float* vw, float* wT,
+                                           int n_columns) {
+    if (wm_ens_check(h, __func__, weights, u, v, T, top_flux, Lz, dt, params, dz_uw, dz_vw, dz_wT, u_out, v_out, T_out, uw, vw, wT, n_columns, true)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t K = (size_t)h->n_models, nc = (size_t)n_columns, nf = K * nc * WM_NZ, nfa = K * nc * (WM_NZ + 1), nfc = (nfa + 3) / 4 * 4,
+                 nt = (3 * nc + 3) / 4 * 4, nh = (3 * K * nc + 3) / 4 * 4;
+    const bool step = u_out != nullptr, flux = uw != nullptr;
+    float* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, (6 * nf + 3 * nfc + nt + 2 * nh) * sizeof(float)));
+    float *d_f = d + 6 * nf, *d_top = d_f + 3 * nfc, *d_hb = d_top + nt, *d_ht = d_hb + nh;
+    int rc = 1;
+    do {
+        const float* srcs[3] = {u, v, T};
+        bool ok = hipMemcpyAsync(h->d_w, weights, sizeof(float) * K * h->m.n_params, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        for (int f = 0; f < 3 && ok; f++) ok = hipMemcpyAsync(d + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok) ok = hipMemcpyAsync(d_top, top_flux, 3 * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok && halo_bottom) ok = hipMemcpyAsync(d_hb, halo_bottom, 3 * K * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (ok && halo_top) ok = hipMemcpyAsync(d_ht, halo_top, 3 * K * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+        if (!ok) { fail("%s: host-to-device copy failed", __func__); break; }
+        if (colnde_ensemble_wm_embedded_dev(h, h->d_w, d, d + nf, d + 2 * nf, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, dt, params,
+                                            convective_adjustment, d + 3 * nf, d + 4 * nf, d + 5 * nf, step ? d : nullptr, step ? d + nf : nullptr,
+                                            step ? d + 2 * nf : nullptr, flux ? d_f : nullptr, flux ? d_f + nfc : nullptr, flux ? d_f + 2 * nfc : nullptr, n_columns))
+            break;
+        float* dsts[6] = {u_out, v_out, T_out, dz_uw, dz_vw, dz_wT};
+        for (int f = step ? 0 : 3; f < 6 && ok; f++) ok = hipMemcpyAsync(dsts[f], d + f * nf, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        float* fd[3] = {uw, vw, wT};
+        for (int f = 0; f < 3 && ok && flux; f++) ok = hipMemcpyAsync(fd[f], d_f + f * nfc, nfa * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("%s: device-to-host copy failed", __func__); break; }
+        rc = 0;
+    } while (0);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
 // diagnose_baseline_flux_uw / _vw / _wT (:157-191; column_ops.hip): no networks, any handle kind
 static int mpp_diag_check(colnde_handle* h, const void* const* ptrs, int n_ptrs, float dz, const float params[7], int n_columns) {
     if (!h) return fail("null handle");
@@ -2703,7 +2849,7 @@ extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
 // Every environment variable some part of the library reads (api.hip, engine_*.hip): the list colnde_describe reports from.
 static const char* const COLNDE_ENV_SWITCHES[] = {
     "COLNDE_FWD_SPLIT", "COLNDE_ADJ_SPLIT", "COLNDE_DW_SPLIT", "COLNDE_ADJ_GEOM", "COLNDE_FWD_WLDS", "COLNDE_FWD_THREADS", "COLNDE_T16_FWD_HELPER",
-    "COLNDE_T16_ADJ_HELPER", "COLNDE_T16_FWD_SPLIT", "COLNDE_T16_ADJ_SPLIT", "COLNDE_FC", "COLNDE_FC_CW", "COLNDE_FC_EMBED_FUSED", "COLNDE_FC_BLOCK", "COLNDE_FC_SEG",
+    "COLNDE_T16_ADJ_HELPER", "COLNDE_T16_FWD_SPLIT", "COLNDE_T16_ADJ_SPLIT", "COLNDE_FC", "COLNDE_FC_CW", "COLNDE_FC_EMBED_FUSED", "COLNDE_FC_BLOCK", "COLNDE_FC_SEG", "COLNDE_WM_ENS_GRID",
     "COLNDE_RT_ZTAPE", "COLNDE_RT_BLOCK", "COLNDE_RT_FWD", "COLNDE_ALLOW_UNSTABLE_DT", "COLNDE_T16_DWTAPE", "COLNDE_T16_ZTAPE", "COLNDE_T16_SPLIT_RICH",
     "COLNDE_T16_BLOCK", "COLNDE_T16_DWLDS", "COLNDE_T16_TAPE_THREADS", "COLNDE_T16_TAPE_WLDS"};
 

@@ -34,3 +34,43 @@ struct WmInferArgs {
 
 // every pointer of the state and the outputs must be 16-byte aligned (hipErrorInvalidValue otherwise)
 hipError_t launch_wm_infer(const WmInferArgs& a, hipStream_t stream);
+
+// ---- the K models of an ensemble in ONE launch (wm_infer_ens_kernel): each model its own weights, state, halos and constants ----------------------
+// The work list is model-major: item = model * n_groups + group, n_groups = ceil(n_col / 128) groups of four 32-column tiles per model, W = K n_groups
+// items.  Workgroup b of `grid` walks the contiguous items [b W / grid, (b + 1) W / grid): below the grid size in models a model's groups are shared
+// by several workgroups, above it a workgroup walks several models and re-copies the weight image at every model boundary.
+inline int wm_ens_groups(int n_col) { return ((n_col + 31) / 32 + 3) / 4; }
+__host__ __device__ inline void wm_ens_range(int b, int grid, long long W, long long* first, long long* last) {
+    *first = (long long)b * W / grid;
+    *last = (long long)(b + 1) * W / grid;
+}
+// workgroups of the launch: one per item up to one per CU, capped by grid_cap when it is positive (COLNDE_WM_ENS_GRID)
+inline int wm_ens_grid(int n_models, int n_col, int n_cu, int grid_cap) {
+    const long long W = (long long)n_models * wm_ens_groups(n_col);
+    long long g = W < (long long)n_cu ? W : (long long)n_cu;
+    if (grid_cap > 0 && g > grid_cap) g = grid_cap;
+    return (int)(g < 1 ? 1 : g);
+}
+
+struct WmEnsArgs {
+    int n_models;
+    const float* weights;                 // [K][w_stride]: model k's [3 WM_NET] first in its row
+    size_t w_stride;
+    float mu[6], sigma[6];
+    int act1, act2;
+    const float *u, *v, *T;               // [K][n_col][32]
+    const float* top_flux;                // [3][n_col], shared by the models
+    const float *halo_bottom, *halo_top;  // [K][3][n_col] or null
+    float Lz;
+    const MppParams* mpp;                 // DEVICE array [K]
+    float *dz_uw, *dz_vw, *dz_wT;         // [K][n_col][32], always written
+    bool fused;
+    float *u_out, *v_out, *T_out;         // fused: [K][n_col][32], each may alias its own input
+    bool diag;
+    float *uw, *vw, *wT;                  // diag: [K][n_col][33] (a model's rows need no alignment of their own: only the base pointers do)
+    int n_col;
+    int grid_cap;                         // > 0: at most this many workgroups
+};
+
+// every base pointer of the state and the outputs must be 16-byte aligned (hipErrorInvalidValue otherwise)
+hipError_t launch_wm_infer_ens(const WmEnsArgs& a, hipStream_t stream);

@@ -8,7 +8,7 @@ for device memory, streams and torch.distributed only).  The reference-named clo
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -829,6 +829,43 @@ def check_ensemble_arrays(n_models: int, n_params: int, weights=None, physics=No
             raise ValueError("%s: expected shape %s for %d models, got %s" % (name, shape, K, tuple(a.shape)))
 
 
+class WmEnsembleEmbedded(NamedTuple):
+    """What `ColumnNDEEnsemble.wm_embedded` returns: dz = (∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN), each [K, n, Nz]; state = (u′, v′, T′), each [K, n, Nz], or
+    None (step=False); faces = (uw, vw, wT), each [K, n, Nz + 1], or None (flux=False)."""
+    dz: tuple
+    state: Optional[tuple]
+    faces: Optional[tuple]
+
+
+def check_wm_ens_embed_arrays(n_models: int, n_params: int, Nz: int, weights, state, top_flux, dt=None, params=None, halo_bottom=None, halo_top=None,
+                              step: bool = True):
+    """Shape and argument rules of `ColumnNDEEnsemble.wm_embedded` (no GPU needed), raised before any library call: weights [K, n_params]; state =
+    (u, v, T), each [K, n, Nz]; top_flux [3, n], shared by the models; halo_bottom, halo_top [K, 3, n] or None; params [K, 7] or None; step=True
+    needs dt > 0.  Per model the rules are those of `check_wm_diag_arrays`.  Returns n."""
+    K = int(n_models)
+    check_ensemble_arrays(K, n_params, weights=weights)
+    if len(state) != 3:
+        raise ValueError("state must be (u, v, T)")
+    T = state[2]
+    if len(T.shape) != 3 or T.shape[0] != K:
+        raise ValueError("T: expected shape (%d, n, %d) for %d models, got %s" % (K, Nz, K, tuple(T.shape)))
+    n = int(T.shape[1])
+    for nm, a in zip(("u", "v", "T"), state):
+        if tuple(a.shape) != (K, n, Nz):
+            raise ValueError("%s: expected shape %s for %d models, got %s" % (nm, (K, n, Nz), K, tuple(a.shape)))
+    for nm, a in (("halo_bottom", halo_bottom), ("halo_top", halo_top)):
+        if a is not None and tuple(a.shape) != (K, 3, n):
+            raise ValueError("%s: expected shape %s for %d models, got %s" % (nm, (K, 3, n), K, tuple(a.shape)))
+    for k in range(K):
+        check_wm_diag_arrays(Nz, n, tuple(a[k] for a in state), top_flux,
+                             (None if halo_bottom is None else halo_bottom[k], None if halo_top is None else halo_top[k]))
+    if params is not None and tuple(np.shape(params)) != (K, 7):
+        raise ValueError("params: expected shape %s (nu0, nu_minus, dRi, Ric, Pr, alpha, g per model), got %s" % ((K, 7), tuple(np.shape(params))))
+    if step and (dt is None or not float(dt) > 0.0):
+        raise ValueError("step=True takes the implicit step and needs dt > 0, got dt = %r (step=False: the ∂z arrays and the faces of the state as given)" % (dt,))
+    return n
+
+
 class ColumnNDEEnsemble(ColumnNDE):
     """K models of ONE architecture on the same columns (`colnde_create_ensemble`): own weights, own Pacanowski-Philander constants, own ADAM rate —
     the sweep of wind_mixing/train_NDE_args.jl (one model per process there) with every kernel launched once for all K models.
@@ -921,6 +958,49 @@ class ColumnNDEEnsemble(ColumnNDE):
         _lib.check(self._L.colnde_ensemble_adam_step_dev(self._h, weights.data_ptr(), result.data_ptr(), m.data_ptr(), v.data_ptr(), etas.data_ptr(),
                                                          float(beta[0]), float(beta[1]), float(eps), float(bt[0]), float(bt[1])))
         return weights
+
+
+    def wm_embedded(self, weights, u, v, T, top_flux, Lz: float, dt=None, params=None, convective_adjustment: bool = False, halo_bottom=None,
+                    halo_top=None, step: bool = True, flux: bool = True) -> WmEnsembleEmbedded:
+        """One embedded iteration of ALL K models in one launch (`colnde_ensemble_wm_embedded`): per model what `wm_embedded_step_flux` (step and
+        flux), `wm_embedded_step` (step), `wm_diagnose_flux` and `wm_infer_dz_flux` (flux; the ∂z arrays are always returned) give for that model's
+        weights, state and constants, bit for bit.  weights [K, n_params]; u, v, T [K, n, Nz], each model its own state; top_flux [3, n], shared;
+        halo_bottom, halo_top [K, 3, n] or None; params [K, 7] = (nu0, nu_minus, dRi, Ric, Pr, alpha, g) per model, or None: the handle's physics
+        with cfg.alpha, cfg.g.  numpy arrays or torch device tensors (all of one kind)."""
+        Nz, K = self.cfg.Nz, self.n_models
+        n = check_wm_ens_embed_arrays(K, self.n_params, Nz, weights, (u, v, T), top_flux, dt, params, halo_bottom, halo_top, step)
+        pr = None if params is None else (ctypes.c_float * (7 * K))(*[float(x) for x in np.asarray(params, dtype=np.float64).reshape(-1)])
+        dtv = float(dt) if step else 0.0
+        ca = int(bool(convective_adjustment))
+        if _is_torch(T):
+            import torch
+            self._chk_dev(weights, (K, self.n_params))
+            for a in (u, v, T):
+                self._chk_dev(a, (K, n, Nz))
+            self._chk_dev(top_flux, (3, n))
+            for a in (halo_bottom, halo_top):
+                if a is not None:
+                    self._chk_dev(a, (K, 3, n))
+            dz = tuple(torch.empty_like(T) for _ in range(3))
+            st = tuple(torch.empty_like(T) for _ in range(3)) if step else None
+            fc = tuple(torch.empty((K, n, Nz + 1), dtype=T.dtype, device=T.device) for _ in range(3)) if flux else None
+            self.use_torch_stream()
+            P = lambda a: a.data_ptr() if a is not None else None
+            fn = self._L.colnde_ensemble_wm_embedded_dev
+        else:
+            weights = _f32(weights, (K, self.n_params))
+            u, v, T, top_flux = _f32(u), _f32(v), _f32(T), _f32(top_flux)
+            halo_bottom = _f32(halo_bottom) if halo_bottom is not None else None
+            halo_top = _f32(halo_top) if halo_top is not None else None
+            dz = tuple(np.empty_like(T) for _ in range(3))
+            st = tuple(np.empty_like(T) for _ in range(3)) if step else None
+            fc = tuple(np.empty((K, n, Nz + 1), np.float32) for _ in range(3)) if flux else None
+            P = _ptr
+            fn = self._L.colnde_ensemble_wm_embedded
+        s3, f3 = st or (None,) * 3, fc or (None,) * 3
+        _lib.check(fn(self._h, P(weights), P(u), P(v), P(T), P(top_flux), P(halo_bottom), P(halo_top), float(Lz), dtv, pr, ca, P(dz[0]), P(dz[1]), P(dz[2]),
+                      P(s3[0]), P(s3[1]), P(s3[2]), P(f3[0]), P(f3[1]), P(f3[2]), n))
+        return WmEnsembleEmbedded(dz, st, fc)
 
 
 CLOSURE_N_PARAMS = 5

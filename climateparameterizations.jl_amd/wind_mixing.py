@@ -390,6 +390,32 @@ def progress_neural_network(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz:
     return tuple(d.reshape(shape) for d in dz), tuple(a.reshape(shape) for a in st)
 
 
+def ensemble_progress_neural_network(ens, weights, state, top_fluxes, Lz: float, dt: float, p=None, constants=None, convective_adjustment: bool = False,
+                                     halo_bottom=None, halo_top=None, flux: bool = False):
+    """`progress_neural_network` for the K models of a `ColumnNDEEnsemble` in one launch: state = (u, v, T), each [K, n, Nz] (or [K, Nz] for one
+    column per model), every model on its own state; top_fluxes [3] or [3, n], shared by the models.  `p`: a sequence of K parameter dicts (as
+    `progress_neural_network`'s `p`) with `constants` one dict for all, or None: the ensemble's own physics.  halo_bottom / halo_top [K, 3, n]
+    or None.  Returns ((∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN), (u′, v′, T′)) shaped like the state — and, with flux=True, also (uw, vw, wT) of the state
+    as given ([.., Nz + 1]).  Row k is `progress_neural_network` of model k, bit for bit."""
+    K = ens.n_models
+    u, v, T = (np.asarray(a, dtype=np.float32) for a in state)
+    shape = T.shape
+    u3, v3, T3 = (np.ascontiguousarray(a.reshape(K, -1, shape[-1])) for a in (u, v, T))
+    n = T3.shape[1]
+    top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_fluxes, np.float32).reshape(3, -1), (3, n)))
+    halos = [None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape(K, 3, -1)) for a in (halo_bottom, halo_top)]
+    params = None
+    if p is not None:
+        if len(p) != K or constants is None:
+            raise ValueError("p must hold one parameter dict per model (%d) and constants must be given with it" % K)
+        params = np.array([_mpp_tuple(pk, constants) for pk in p], dtype=np.float32)
+    r = ens.wm_embedded(weights, u3, v3, T3, top, Lz, dt, params, convective_adjustment, halos[0], halos[1], step=True, flux=flux)
+    out = tuple(d.reshape(shape) for d in r.dz), tuple(a.reshape(shape) for a in r.state)
+    if flux:
+        out += (tuple(f.reshape(shape[:-1] + (shape[-1] + 1,)) for f in r.faces),)
+    return out
+
+
 def _mpp_tuple(p, constants):
     return (_named(p, "ν₀", "nu0"), _named(p, "ν₋", "nu_minus"), _named(p, "ΔRi", "dRi"), _named(p, "Riᶜ", "Ric"), _named(p, "Pr"),
             _named(constants, "α", "alpha"), _named(constants, "g"))

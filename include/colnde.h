@@ -478,6 +478,30 @@ int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const floa
 int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_result, float* d_m, float* d_v, const float* d_eta,
                                   float beta1, float beta2, float eps, float beta1_t, float beta2_t);
 
+/* All K models of an ensemble in the embedding ocean column at once — one iteration of progress_neural_network (wind_mixing/src/NDE_oceananigans.jl:380-405) and / or
+ * the saved-state diagnoses diagnose_NN_flux_uw / _vw / _wT (:226-286) for every model, each on its OWN column state with its own weights and its own constants: how
+ * NDE_profile_oceananigans / solve_oceananigans_modified_pacanowski_philander_nn judge the members of a sweep.  One launch for all K.
+ *   d_weights [K][n_params] (the ensemble's layout); u, v, T and every [..][Nz] output [K][n_col][32]; the faces [K][n_col][33]; top_flux [3][n_col], SHARED by the
+ *   models (they are driven by the same surface fluxes, as the ensemble shares bcs); halo_bottom, halo_top [K][3][n_col] or NULL; params HOST memory [K][7] =
+ *   {nu0, nu_minus, dRi, Ric, Pr, alpha, g} per model, or NULL: the handle's current per-model physics (colnde_create_ensemble / colnde_ensemble_set_physics)
+ *   followed by cfg.alpha, cfg.g.
+ *   The ∂z arrays are always written.  d_u_out, d_v_out, d_T_out: all three given — the implicit step is taken, dt > 0 required, each may alias its own input —
+ *   or all three NULL (no step, dt ignored).  d_uw, d_vw, d_wT: all three given — the face diagnosis of the state AS GIVEN — or all three NULL.
+ * Row k of every output is, bit for bit, what the single-model call of the same output groups (colnde_wm_embedded_step_flux, colnde_wm_diagnose_flux,
+ * colnde_wm_embedded_step, colnde_wm_infer_dz_flux) writes for model k's weights, state, halos and params.  Accepts an ensemble handle; a single-model handle is
+ * K = 1.  Refuses, with the reason in colnde_last_error, what those calls refuse (shape, smooth_NN, null, the 16-byte alignment of every state and output BASE
+ * pointer, dRi != 0, Pr > 0) and a closure handle, a half-given output group, dt <= 0 with a step.  Timed under colnde_kernel_time slot 10.
+ * COLNDE_WM_ENS_GRID=<n> (a test override) caps the workgroups of this launch and of no other. */
+int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
+        const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt, const float* params,
+        int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out, float* d_T_out,
+        float* d_uw, float* d_vw, float* d_wT, int n_columns);
+/* the same with host arrays (no alignment rule); synchronises the stream */
+int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T,
+        const float* top_flux, const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params,
+        int convective_adjustment, float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out,
+        float* uw, float* vw, float* wT, int n_columns);
+
 /* ---- closure-only model: fitting the five Pacanowski-Philander constants before any network is trained ------------------------------------------------
  * optimise_modified_pacanowski_philander (wind_mixing/src/diffusivity_parameter_optimisation.jl:35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl
  * and ..._args.jl) integrates the column ODE WITHOUT the MLPs — DE(x, p, t), :1-33: eps on all three face gradients, nu on interior faces only, boundary faces
@@ -517,7 +541,7 @@ int colnde_closure_loss_grad(colnde_handle* h, const float* params, const float 
  * which: 0 = forward solve kernel, 1 = adjoint kernel, 2 = gradient reduce, 3 = rhs, 4 = inference,
  * 5 = streaming dW1 GEMM (regtile engine only), 6 = convective adjustment, 7 = ADAM step, 8 = implicit diffusion,
  * 9 = free-convection embedded step / diagnose_wT, 10 = wind-mixing flux diagnoses (colnde_wm_diagnose_flux, colnde_wm_embedded_step_flux,
- * colnde_mpp_diagnose_flux).
+ * colnde_mpp_diagnose_flux, colnde_ensemble_wm_embedded).
  * Returns accumulated milliseconds and launch count since the last reset (synchronises the stream). */
 int colnde_set_profiling(colnde_handle* h, int enabled);
 int colnde_kernel_time(colnde_handle* h, int which, float* ms_total, int* n_launches);

@@ -420,6 +420,26 @@ function progress_neural_network_flux(h::Handle, θ::Vector{Float32}, u::Matrix{
     (uw, vw, wT)
 end
 
+"progress_neural_network and diagnose_NN_flux_* for ALL K models of an ensemble handle in one launch (colnde_ensemble_wm_embedded): θ (n_params, K);
+u, v, T and the ∂z arrays (Nz, n_columns, K), every model on its own state, stepped in place; top_fluxes (n_columns, 3), shared by the models;
+`ps`: a vector of K parameter dictionaries, or nothing (the ensemble's own physics with the handle's α, g); halo_bottom, halo_top (n_columns, 3, K)
+or nothing.  Returns (uw, vw, wT) of the states as given, each (Nz+1, n_columns, K).  Slice k is progress_neural_network_flux of model k, bit for bit."
+function ensemble_progress_neural_network_flux(h::Handle, θ::Matrix{Float32}, u::Array{Float32,3}, v::Array{Float32,3}, T::Array{Float32,3},
+                                               top_fluxes::Matrix{Float32}, Lz, constants, Δt, ps, convective_adjustment,
+                                               ∂z_uw_NN::Array{Float32,3}, ∂z_vw_NN::Array{Float32,3}, ∂z_wT_NN::Array{Float32,3};
+                                               halo_bottom=nothing, halo_top=nothing)
+    params = ps === nothing ? nothing : reduce(vcat, [Float32[p["ν₀"], p["ν₋"], p["ΔRi"], p["Riᶜ"], p["Pr"], constants.α, constants.g] for p in ps])
+    pp = params === nothing ? C_NULL : pointer(params)
+    hb = halo_bottom === nothing ? C_NULL : pointer(halo_bottom); ht = halo_top === nothing ? C_NULL : pointer(halo_top)
+    uw, vw, wT = (Array{Float32,3}(undef, size(T, 1) + 1, size(T, 2), size(T, 3)) for _ in 1:3)
+    GC.@preserve params halo_bottom halo_top check(ccall((:colnde_ensemble_wm_embedded, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Ptr{Float32}, Cint,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint),
+        h.ptr, θ, u, v, T, top_fluxes, hb, ht, Lz, Δt, pp, convective_adjustment ? 1 : 0, ∂z_uw_NN, ∂z_vw_NN, ∂z_wT_NN, u, v, T, uw, vw, wT,
+        size(T, 2)))
+    (uw, vw, wT)
+end
+
 "diagnose_baseline_flux_uw, _vw, _wT (wind_mixing/src/NDE_oceananigans.jl:157-191): (−ν ∂z u, −ν ∂z v, −νT ∂z T) on the faces with the top
 face replaced by the top flux, each (Nz+1, n_columns); no networks"
 function diagnose_baseline_flux(h::Handle, u::Matrix{Float32}, v::Matrix{Float32}, T::Matrix{Float32}, top_fluxes::Matrix{Float32}, Δz, constants, p,
