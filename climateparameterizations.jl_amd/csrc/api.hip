@@ -10,17 +10,11 @@
 #include <string>
 #include <vector>
 
-#include "engine_tile16.h"
-#include "engine_regtile.h"
-#include "engine_fc.h"
-#include "column_ops.h"
-#include "engine_closure.h"
-#include "engine_wm_infer.h"
-#include "engine_fc_embed.h"
+#include "api_internal.h"
 
 static thread_local std::string g_err;
 
-static int fail(const char* fmt, ...) {
+int fail(const char* fmt, ...) {
     char buf[1024];
     va_list ap;
     va_start(ap, fmt);
@@ -30,116 +24,8 @@ static int fail(const char* fmt, ...) {
     return 1;
 }
 
-// Entry points that take ONE weight vector refuse an ensemble handle (colnde_create_ensemble)
-#define SINGLE_MODEL_ONLY(h)                                                                                                              \
-    do {                                                                                                                                  \
-        if ((h) && (h)->closure)                                                                                                          \
-            return fail("%s takes a weight vector, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", \
-                        __func__, (h)->n_models);                                                                                         \
-        if ((h) && (h)->ensemble)                                                                                                         \
-            return fail("%s takes one weight vector, but this handle holds an ensemble of %d models: use colnde_ensemble_* (include/colnde.h)", \
-                        __func__, (h)->n_models);                                                                                         \
-    } while (0)
-
 // shared with comm.hip (not part of the public header)
 extern "C" int colnde_internal_set_error(const char* msg) { g_err = msg ? msg : "error"; return 1; }
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1 = 5, K_CONVADJ = 6, K_ADAM = 7, K_IMPLDIFF = 8, K_FCEMBED = 9, K_FLUXDIAG = 10, K_COUNT = 11 };
-
-struct PendingEvent { hipEvent_t a, b; int which; };
-
-struct colnde_handle {
-    colnde_config cfg;
-    std::vector<float> save_times;
-    DevModel m;
-    PackInfo pk;
-    AdjointGeom geo;
-    bool geo_ok = false;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int n_col = 0, n_tiles = 0;
-    int64_t n_col_total = 0;
-    size_t lds_fwd = 0, lds_adj = 0, lds_fwd_solve = 0;
-    int fwd_threads = 256;
-    bool fwd_wlds = false;
-    bool adj_helper = true;         // ... and in the adjoint: a helper wave carries λ, x̄ and the physics pullback for the three net waves
-    bool fwd_helper = true;         // ... four waves per tile: a helper wave evaluates the Richardson-number closure for the three net waves
-    bool split_rich = false;        // ... with the rich tape (activations, derivatives, physics coefficients) in place of the pre-activation tape
-    bool adj_split = false;         // ... and the gradient by rt16s_adjoint_kernel + tile16's dW GEMM
-    bool fwd_split = false;         // forward solves by the net-split kernels (rt16sh_forward_kernel: three net waves + a helper wave per tile)
-    bool use_rt = false;            // register-resident tile engine (static 96-50-20-31 wind-mixing shape)
-    bool sp_fwd = true, sp_adj = true, sp_dw = true;   // matrix arithmetic of the forward-solve / adjoint / weight-gradient kernels: exact three-way bf16 split (true) or
-                                                      // f32 MFMA — cfg.matrix_arithmetic with the test overrides COLNDE_{FWD,ADJ,DW}_SPLIT (resolve_arithmetic)
-    bool use_fc = false;            // 32-column free-convection engine (engine_fc.hip: Nz = 32 | 64, the reference's relu network, RK4)
-    bool fce_ready = false;         // colnde_fc_embedded_step / colnde_fc_diagnose_wT: images allocated, LDS limits raised (first call)
-    float *d_fc_imgf = nullptr, *d_fc_imgb = nullptr, *d_fc_bias = nullptr;
-    unsigned int *d_fc_simgf = nullptr, *d_fc_simgb = nullptr;   // the split operand images (COLNDE_MATRIX_BF16X3_EXACT; 32-column tiles)
-    unsigned int* d_fc_masks = nullptr;
-    unsigned long long* d_fc_switch = nullptr;   // ConvectiveAdjustmentNDE: the taped switch patterns
-    int fc_block = 0, fc_nblocks = 0, fc_rows = 0;   // gradient path: columns per pass (multiple of 32), passes, slab rows
-    int fc_seg = 0, fc_nseg = 0;                      // ... save intervals per time segment of the tapes, segments (1: the tapes hold the whole axis)
-    int fc_cw = 32;                                   // columns per workgroup tile: 32, or 16 for problems of at most 4,096 columns (fc_tile_width)
-    float* d_fc_lam = nullptr;                        // λ handed from one time segment to the one before it
-    float* d_wimg = nullptr;
-    float *d_rt_tape = nullptr, *d_rt_tape2 = nullptr, *d_rt_slab = nullptr, *d_rt_tapez = nullptr;
-    bool rt_fwd32 = false;         // COLNDE_RT_FWD=32 at creation: the 32-column forward kernel (no Z1 tape)
-    bool rt_ztape = false;         // layer-1 pre-activations taped by the forward kernel instead of recomputed by the adjoint
-    int rt_rows = 0;
-    int rt_block = 0;              // columns per pass of the gradient path (multiple of 32): the tapes hold one block at a time
-    int rt_nblocks = 0;
-    float *d_w = nullptr, *d_wf = nullptr, *d_wb = nullptr, *d_x0 = nullptr, *d_bcs = nullptr, *d_truth = nullptr,
-          *d_sol = nullptr, *d_tape = nullptr, *d_slab = nullptr, *d_out = nullptr, *d_times = nullptr,
-          *d_partial = nullptr, *d_tmp_a = nullptr, *d_tmp_b = nullptr, *d_tmp_c = nullptr;
-    size_t tmp_cols = 0;
-    TileDesc* d_tiles = nullptr;
-    // tile16 taped-dW mode (networks whose weight-gradient tiles overflow the register file)
-    int t16_dwtape = -1;            // -1 undecided, 0 off, 1 on
-    float* d_dwtape = nullptr;
-    float* d_t16_ztape = nullptr;   // taped mode: hidden pre-activations written by the forward kernel (the adjoint skips its forward GEMMs)
-    DwMacro* d_macros = nullptr;
-    DwSplitPlan dw_split;                       // the dW GEMM on the bf16 pipe (exact operand splitting), built with the tapes' plan whenever the records fit LDS; used when sp_dw
-    int n_macros = 0, dw_slices = 0, t16_rows = 0;
-    int t16_block = 0, t16_nblocks = 0;   // taped mode: columns per pass (multiple of 16) — the tapes hold one block
-    int *d_bias_zoff = nullptr, *d_bias_goff = nullptr;
-    bool have_problem = false, have_truth = false;
-    bool prof = false;
-    int min_substeps = 1;           // least RK4 sub-steps per save interval inside the diffusive stability bound
-    bool auto_substeps = false;     // cfg.substeps = 0 at creation: the first solve call chooses the sub-step count from cfg.reltol (choose_substeps)
-    float last_estimate = -1.0f;    // ... and the error estimate it settled on
-    unsigned* d_sf = nullptr;       // DevModel::sf / sb: bf16 plane images of the dense chains (networks with rows in global memory, BF16X3_EXACT)
-    unsigned* d_sb = nullptr;
-    float* d_ag = nullptr;          // DevModel::ag: per-tile activation / delta rows in global memory (networks whose rows do not fit the LDS)
-    size_t ag_tiles = 0;            // ... tiles it holds
-    std::vector<float> rkc_host;    // host copy of the RKC2 coefficient table in use (refresh_rkc)
-    bool ag_rows = false;           // the tile16 kernels keep the activation rows in global memory (DevModel::ag)
-    bool substeps_chosen = false;   // the count in use came out of choose_substeps_impl (colnde_describe says so, with the estimate)
-    float* d_rkc = nullptr;         // RKC2 coefficient table (DevModel::rkc)
-    // ensembles (colnde_create_ensemble): n_models models of this configuration in one launch per kernel (blockIdx.y = model)
-    bool ensemble = false;
-    int n_models = 1;
-    std::vector<RtPhys> phys_host;  // per-model closure constants (closure_constants), and their device copy
-    RtPhys* d_phys = nullptr;
-    std::vector<float> phys_raw;    // ... as given: [n_models][5] {nu0, nu_minus, dRi, Ric, Pr} (empty: cfg's constants for every model)
-    MppParams* d_wm_ens_mpp = nullptr;          // colnde_ensemble_wm_embedded: the per-model sweep constants on the device, and what they hold
-    std::vector<MppParams> wm_ens_mpp_host;
-    RtEns ens;                      // per-model strides of the buffers a model owns
-    size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)
-    int ens_rkc_stages = 0;         // RKC2, automatic stage count: the largest any model needs (refresh_rkc)
-    // closure-only model (colnde_create_closure): n_models constant sets of the Pacanowski-Philander closure, no networks (engine_closure.hip)
-    bool closure = false;
-    ClosureModel cm = {};
-    float *d_cl_tape = nullptr, *d_cl_rows = nullptr, *d_cl_params = nullptr;
-    size_t cl_tape_bytes = 0;
-    std::vector<PendingEvent> pending;
-    double ms[K_COUNT] = {};
-    int launches[K_COUNT] = {};
-};
 
 extern "C" const char* colnde_last_error(void) { return g_err.c_str(); }
 extern "C" int colnde_version(void) { return COLNDE_VERSION; }
@@ -380,7 +266,7 @@ static void resolve_arithmetic(colnde_handle* h) {
 }
 
 // DevModel::ag for `tiles` workgroups (zero-filled once: the pad slots behind a layer's last feature are never written and must read as zero)
-static int ensure_ag(colnde_handle* h, size_t tiles) {
+int ensure_ag(colnde_handle* h, size_t tiles) {
     if (!h->ag_rows || h->ag_tiles >= tiles) return 0;
     (void)hipStreamSynchronize(h->stream);
     if (h->d_ag) { (void)hipFree(h->d_ag); h->d_ag = nullptr; h->m.ag = nullptr; h->ag_tiles = 0; }
@@ -616,7 +502,7 @@ extern "C" int colnde_create(const colnde_config* cfg, colnde_handle** out) {
     return 0;
 }
 
-static void drain_events(colnde_handle* h) {
+void drain_events(colnde_handle* h) {
     for (PendingEvent& p : h->pending) {
         float ms = 0.0f;
         if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
@@ -671,24 +557,6 @@ extern "C" int colnde_set_global_columns(colnde_handle* h, int64_t n) {
 }
 
 // ---- profiling -----------------------------------------------------------------------------------------
-struct Timed {
-    colnde_handle* h;
-    PendingEvent p;
-    bool on;
-    Timed(colnde_handle* h_, int which) : h(h_), on(h_->prof) {
-        if (!on) return;
-        p.which = which;
-        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(p.a, h->stream);
-    }
-    ~Timed() {
-        if (!on) return;
-        (void)hipEventRecord(p.b, h->stream);
-        h->pending.push_back(p);
-        if (h->pending.size() > 2048) drain_events(h);
-    }
-};
-
 extern "C" int colnde_set_profiling(colnde_handle* h, int enabled) {
     if (!h) return fail("null handle");
     h->prof = enabled != 0;
@@ -735,7 +603,7 @@ extern "C" int colnde_set_problem_dev(colnde_handle* h, const float* x0, const f
     return set_problem_impl(h, x0, bcs, truth, hipMemcpyDeviceToDevice);
 }
 
-static int pack(colnde_handle* h, const float* d_weights) {
+int pack(colnde_handle* h, const float* d_weights) {
     hipError_t e = launch_pack(h->m, h->pk, d_weights, h->d_wf, h->d_wb, h->stream);
     if (e != hipSuccess) return fail("pack_weights launch failed: %s", hipGetErrorString(e));
     if (h->d_sf && (h->m.sf || h->m.sb)) {
@@ -775,7 +643,7 @@ extern "C" int colnde_rhs_dev(colnde_handle* h, const float* d_x, const float* d
     return 0;
 }
 
-static int ensure_tmp(colnde_handle* h, size_t n_columns) {
+int ensure_tmp(colnde_handle* h, size_t n_columns) {
     if (h->tmp_cols >= n_columns) return 0;
     for (float** p : {&h->d_tmp_a, &h->d_tmp_b, &h->d_tmp_c})
         if (*p) { (void)hipFree(*p); *p = nullptr; }
@@ -1463,7 +1331,7 @@ extern "C" int colnde_loss_grad(colnde_handle* h, const float* weights, const fl
 // its packed weights, solution, tapes and slab rows (RtEns strides) and its closure constants (RtPhys); x0, bcs and truth are shared.
 
 // the configuration of model k: cfg with row k of physics ([K][5]: nu0, nu_minus, dRi, Ric, Pr)
-static colnde_config model_config(const colnde_config* cfg, const float* physics, int k) {
+colnde_config model_config(const colnde_config* cfg, const float* physics, int k) {
     colnde_config c = *cfg;
     if (physics) {
         const float* r = physics + (size_t)5 * k;
@@ -1943,27 +1811,15 @@ extern "C" int colnde_flux(colnde_handle* h, const float* x, const float* weight
     HIPCHK(hipSetDevice(h->device));
     if (ensure_tmp(h, (size_t)n_columns)) return 1;
     const DevModel& m = h->m;
-    const size_t nfl = (size_t)n_columns * m.n_nets * (m.Nz + 1);
+    HostStage st(h, "flux");
     float* d_fl = nullptr;
-    HIPCHK(hipMalloc((void**)&d_fl, nfl * sizeof(float)));
-    int rc = 1;
-    do {
-        if (hipMemcpyAsync(h->d_w, weights, sizeof(float) * m.n_params, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipMemcpyAsync(h->d_tmp_a, x, sizeof(float) * (size_t)n_columns * m.ns, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipMemcpyAsync(h->d_tmp_b, bcs, sizeof(float) * (size_t)n_columns * m.n_bc, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
-            fail("flux: host-to-device copy failed");
-            break;
-        }
-        if (colnde_flux_dev(h, h->d_tmp_a, h->d_w, h->d_tmp_b, t, d_fl, n_columns)) break;
-        if (hipMemcpyAsync(flux, d_fl, nfl * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
-            fail("flux: device-to-host copy failed");
-            break;
-        }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d_fl);
-    return rc;
+    st.to(h->d_w, weights, (size_t)m.n_params);
+    st.to(h->d_tmp_a, x, (size_t)n_columns * m.ns);
+    st.to(h->d_tmp_b, bcs, (size_t)n_columns * m.n_bc);
+    st.out(&d_fl, flux, (size_t)n_columns * m.n_nets * (m.Nz + 1));
+    if (st.upload()) return 1;
+    if (colnde_flux_dev(h, h->d_tmp_a, h->d_w, h->d_tmp_b, t, d_fl, n_columns)) return 1;
+    return st.download();
 }
 
 extern "C" int colnde_loss_per_tstep_dev(colnde_handle* h, const float* d_weights, float* d_out) {
@@ -1983,738 +1839,13 @@ extern "C" int colnde_loss_per_tstep(colnde_handle* h, const float* weights, flo
     if (!h) return fail("null handle");
     if (!weights || !out) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
-    const size_t n = (size_t)h->n_col * 6 * h->cfg.n_save;
+    HostStage st(h, "loss_per_tstep");
     float* d_o = nullptr;
-    HIPCHK(hipMalloc((void**)&d_o, n * sizeof(float)));
-    int rc = 1;
-    do {
-        if (hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream) != hipSuccess) { fail("loss_per_tstep: host-to-device copy failed"); break; }
-        if (colnde_loss_per_tstep_dev(h, h->d_w, d_o)) break;
-        if (hipMemcpyAsync(out, d_o, n * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
-            fail("loss_per_tstep: device-to-host copy failed");
-            break;
-        }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d_o);
-    return rc;
-}
-
-// ---- embedded inference --------------------------------------------------------------------------------
-// sign = +1: the forcing -dz(wT); -1: +dz(wT), what the reference stores in params.∂z_wT_NN (double_gyre_nn.jl:165)
-static int infer_impl(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, float Lz, float* d_out, int n_columns, float sign);
-extern "C" int colnde_infer_forcing_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux,
-                                        float Lz, float* d_out, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    return infer_impl(h, d_weights, d_T, d_top_flux, Lz, d_out, n_columns, 1.0f);
-}
-extern "C" int colnde_infer_dz_wT_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux,
-                                      float Lz, float* d_out, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    return infer_impl(h, d_weights, d_T, d_top_flux, Lz, d_out, n_columns, -1.0f);
-}
-static int infer_impl(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, float Lz, float* d_out, int n_columns, float sign) {
-    if (!h) return fail("null handle");
-    if (!d_weights || !d_T || !d_top_flux || !d_out) return fail("null pointer argument");
-    if (h->m.model == COLNDE_MODEL_WIND_MIXING) return fail("infer_forcing needs a single T-only network (free-convection model)");
-    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
-    HIPCHK(hipSetDevice(h->device));
-    if (h->use_fc && h->m.model == COLNDE_MODEL_FREE_CONVECTION) {
-        // the reference's forcing network IS the fc32 shape (32-128-128-31 in double_gyre_nn.jl): the 32-column engine's sections, one evaluation
-        const int cw = fc_tile_width(n_columns);                 // (the images are packed per call: this call's own tile width)
-        hipError_t ef = fc_launch_pack(h->m, cw, d_weights, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, nullptr, nullptr, h->stream);
-        if (ef != hipSuccess) return fail("fc32 pack launch failed: %s", hipGetErrorString(ef));
-        Timed tm(h, K_INFER);
-        ef = fc_launch_infer(h->m, cw, h->d_fc_imgf, h->d_fc_bias, d_T, d_top_flux, sign * (float)h->m.Nz / Lz, d_out, n_columns, h->stream);
-        if (ef != hipSuccess) return fail("fc32 infer launch failed: %s", hipGetErrorString(ef));
-        return 0;
-    }
-    if (pack(h, d_weights)) return 1;
-    Timed tm(h, K_INFER);
-    hipError_t e = launch_infer(h->m, h->pk, d_weights, h->d_wf, d_T, d_top_flux, sign * (float)h->m.Nz / Lz, d_out, n_columns, 256,
-                                h->lds_fwd, h->stream);
-    if (e != hipSuccess) return fail("infer launch failed: %s", hipGetErrorString(e));
-    return 0;
-}
-
-static int infer_host(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz, float* out, int n_columns, float sign);
-extern "C" int colnde_infer_forcing(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz,
-                                    float* out, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    return infer_host(h, weights, T, top_flux, Lz, out, n_columns, 1.0f);
-}
-extern "C" int colnde_infer_dz_wT(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz,
-                                  float* out, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    return infer_host(h, weights, T, top_flux, Lz, out, n_columns, -1.0f);
-}
-static int infer_host(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz, float* out, int n_columns, float sign) {
-    if (!h) return fail("null handle");
-    if (!weights || !T || !top_flux || !out) return fail("null pointer argument");
-    if (n_columns < 1) return fail("n_columns must be >= 1");
-    HIPCHK(hipSetDevice(h->device));
-    if (ensure_tmp(h, (size_t)n_columns)) return 1;
-    const int Nz = h->m.Nz;
-    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_tmp_a, T, sizeof(float) * (size_t)n_columns * Nz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_tmp_b, top_flux, sizeof(float) * (size_t)n_columns, hipMemcpyHostToDevice, h->stream));
-    if (infer_impl(h, h->d_w, h->d_tmp_a, h->d_tmp_b, Lz, h->d_tmp_c, n_columns, sign)) return 1;
-    HIPCHK(hipMemcpyAsync(out, h->d_tmp_c, sizeof(float) * (size_t)n_columns * Nz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// ---- the steps either side of the hot path ---------------------------------------------------
-extern "C" int colnde_convective_adjustment_dev(colnde_handle* h, const float* d_T, const float* d_halo_bottom,
-                                                const float* d_halo_top, float dt, float dz, float K, float* d_out, int n_columns) {
-    if (!h) return fail("null handle");
-    if (!d_T || !d_out) return fail("null pointer argument");
-    if (n_columns < 1) return fail("n_columns must be >= 1");
-    if (!(dt > 0.0f) || !(dz > 0.0f) || !(K >= 0.0f)) return fail("dt > 0, dz > 0 and K >= 0 required");
-    if (h->m.Nz < 2 || h->m.Nz > 128) return fail("convective adjustment supports 2 <= Nz <= 128 (Nz = %d)", h->m.Nz);
-    HIPCHK(hipSetDevice(h->device));
-    Timed tm(h, K_CONVADJ);
-    hipError_t e = launch_convective_adjustment(d_T, d_halo_bottom, d_halo_top, dt / (dz * dz), K, d_out, h->m.Nz, n_columns, h->stream);
-    if (e != hipSuccess) return fail("convective adjustment launch failed: %s", hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int colnde_convective_adjustment(colnde_handle* h, const float* T, const float* halo_bottom, const float* halo_top,
-                                            float dt, float dz, float K, float* out, int n_columns) {
-    if (!h) return fail("null handle");
-    if (!T || !out) return fail("null pointer argument");
-    if (n_columns < 1) return fail("n_columns must be >= 1");
-    HIPCHK(hipSetDevice(h->device));
-    if (ensure_tmp(h, (size_t)n_columns)) return 1;
-    const int Nz = h->m.Nz;
-    HIPCHK(hipMemcpyAsync(h->d_tmp_a, T, sizeof(float) * (size_t)n_columns * Nz, hipMemcpyHostToDevice, h->stream));
-    float* d_hb = nullptr;
-    float* d_ht = nullptr;
-    if (halo_bottom) {
-        d_hb = h->d_tmp_b;
-        HIPCHK(hipMemcpyAsync(d_hb, halo_bottom, sizeof(float) * (size_t)n_columns, hipMemcpyHostToDevice, h->stream));
-    }
-    if (halo_top) {
-        d_ht = h->d_tmp_b + n_columns;
-        HIPCHK(hipMemcpyAsync(d_ht, halo_top, sizeof(float) * (size_t)n_columns, hipMemcpyHostToDevice, h->stream));
-    }
-    if (colnde_convective_adjustment_dev(h, h->d_tmp_a, d_hb, d_ht, dt, dz, K, h->d_tmp_c, n_columns)) return 1;
-    HIPCHK(hipMemcpyAsync(out, h->d_tmp_c, sizeof(float) * (size_t)n_columns * Nz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// modified_pacanowski_philander! (wind_mixing/src/NDE_oceananigans.jl:61-101): one implicit diffusion step of u, v, T per column
-static int impl_diff_check(colnde_handle* h, const void* a, const void* b, const void* c, const void* d, const void* e, const void* f,
-                           float dt, float dz, const float params[7], int n_columns) {
-    if (!h) return fail("null handle");
-    if (!a || !b || !c || !d || !e || !f || !params) return fail("null pointer argument");
-    if (n_columns < 1) return fail("n_columns must be >= 1");
-    if (!(dt > 0.0f) || !(dz > 0.0f)) return fail("dt > 0 and dz > 0 required");
-    if (!(params[0] >= 0.0f) || !(params[1] >= 0.0f)) return fail("nu0 >= 0 and nu_minus >= 0 required (the tridiagonal must stay diagonally dominant)");
-    if (!(params[2] != 0.0f) || !(params[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
-    if (h->m.Nz < 2 || h->m.Nz > 128) return fail("implicit diffusion supports 2 <= Nz <= 128 (Nz = %d)", h->m.Nz);
-    return 0;
-}
-
-extern "C" int colnde_implicit_diffusion_dev(colnde_handle* h, const float* d_u, const float* d_v, const float* d_T,
-                                             const float* d_halo_bottom, float dt, float dz, const float params[7],
-                                             int convective_adjustment, float* d_u_out, float* d_v_out, float* d_T_out, int n_columns) {
-    if (impl_diff_check(h, d_u, d_v, d_T, d_u_out, d_v_out, d_T_out, dt, dz, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    Timed tm(h, K_IMPLDIFF);
-    hipError_t e = launch_mpp_diffusion(d_u, d_v, d_T, d_halo_bottom, dt, dz, params, convective_adjustment, d_u_out, d_v_out, d_T_out,
-                                        h->m.Nz, n_columns, h->stream);
-    if (e != hipSuccess) return fail("implicit diffusion launch failed: %s", hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int colnde_implicit_diffusion(colnde_handle* h, const float* u, const float* v, const float* T, const float* halo_bottom,
-                                         float dt, float dz, const float params[7], int convective_adjustment, float* u_out,
-                                         float* v_out, float* T_out, int n_columns) {
-    if (impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, dz, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t nf = (size_t)n_columns * h->m.Nz, nh = (size_t)n_columns;
-    float* d = nullptr;       // [u | v | T | halo(3 n_col)]: a scratch of its own — the handle's are sized for its own state vector
-    HIPCHK(hipMalloc((void**)&d, (3 * nf + 3 * nh) * sizeof(float)));
-    int rc = 1;
-    do {
-        const float* srcs[3] = {u, v, T};
-        bool ok = true;
-        for (int f = 0; f < 3 && ok; f++)
-            ok = hipMemcpyAsync(d + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && halo_bottom) ok = hipMemcpyAsync(d + 3 * nf, halo_bottom, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (!ok) { fail("implicit diffusion: host-to-device copy failed"); break; }
-        if (colnde_implicit_diffusion_dev(h, d, d + nf, d + 2 * nf, halo_bottom ? d + 3 * nf : nullptr, dt, dz, params,
-                                          convective_adjustment, d, d + nf, d + 2 * nf, n_columns)) break;
-        float* dsts[3] = {u_out, v_out, T_out};
-        for (int f = 0; f < 3 && ok; f++)
-            ok = hipMemcpyAsync(dsts[f], d + f * nf, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("implicit diffusion: device-to-host copy failed"); break; }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-// ---- wind-mixing embedded inference (wind_mixing/src/NDE_oceananigans.jl:288-329, :380-405; engine_wm_infer.hip) ----------------------
-// the handles the kernels cover; fn names the entry point in the refusal
-static bool wm_infer_covers(const colnde_handle* h) {
-    const colnde_config& c = h->cfg;
-    return !h->closure && !h->ensemble && c.model == COLNDE_MODEL_WIND_MIXING && !c.smooth_NN && c.Nz == WM_NZ && c.n_layers == 3 && c.layer_sizes[0] == 3 * WM_NZ &&
-           c.layer_sizes[1] == WM_H1 && c.layer_sizes[2] == WM_H2 && c.layer_sizes[3] == WM_NZ - 1 && c.activations[2] == COLNDE_ACT_IDENTITY;
-}
-static int wm_infer_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, int n_columns) {
-    if (!h) return fail("null handle");
-    const colnde_config& c = h->cfg;
-    if (c.model != COLNDE_MODEL_WIND_MIXING)
-        return fail("%s needs a wind-mixing handle (three flux networks on [u; v; T]); a free-convection handle has colnde_infer_forcing", fn);
-    if (c.smooth_NN)
-        return fail("%s: the embedding has no smoothing filter (NDE_oceananigans.jl:288-329 apply the networks unfiltered), so a handle with smooth_NN is refused", fn);
-    if (!wm_infer_covers(h)) {
-        std::string shape;
-        for (int l = 0; l <= c.n_layers; l++) shape += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
-        return fail("%s covers Nz = 32 with three 96-50-20-31 networks and an identity output layer; this handle has Nz = %d, networks %s, output activation %d", fn,
-                    c.Nz, shape.c_str(), c.activations[c.n_layers - 1]);
-    }
-    for (int i = 0; i < n_ptrs; i++)
-        if (!ptrs[i]) return fail("null pointer argument");
-    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
-    return 0;
-}
-static void wm_infer_args(const colnde_handle* h, WmInferArgs* a) {
-    for (int i = 0; i < 6; i++) { a->mu[i] = h->cfg.mu[i]; a->sigma[i] = h->cfg.sigma[i]; }
-    a->act1 = h->cfg.activations[0];
-    a->act2 = h->cfg.activations[1];
-}
-
-extern "C" int colnde_wm_infer_dz_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
-                                           const float* d_top_flux, float Lz, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[8] = {d_weights, d_u, d_v, d_T, d_top_flux, d_dz_uw, d_dz_vw, d_dz_wT};
-    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    WmInferArgs a = {};
-    wm_infer_args(h, &a);
-    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.Lz = Lz;
-    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT; a.n_col = n_columns; a.fused = false;
-    Timed tm(h, K_INFER);
-    hipError_t e = launch_wm_infer(a, h->stream);
-    if (e != hipSuccess) return fail("wm_infer launch failed: %s (the state and output arrays must be 16-byte aligned)", hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int colnde_wm_embedded_step_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
-                                           const float* d_top_flux, const float* d_halo_bottom, float Lz, float dt, const float params[7],
-                                           int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out,
-                                           float* d_T_out, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[8] = {d_weights, d_u, d_v, d_T, d_top_flux, d_dz_uw, d_dz_vw, d_dz_wT};
-    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
-    if (impl_diff_check(h, d_u, d_v, d_T, d_u_out, d_v_out, d_T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    WmInferArgs a = {};
-    wm_infer_args(h, &a);
-    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.Lz = Lz;
-    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT; a.n_col = n_columns; a.fused = true;
-    a.halo_bottom = d_halo_bottom;
-    a.mpp = mpp_params(params, dt, Lz / (float)WM_NZ, convective_adjustment);
-    a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
-    Timed tm(h, K_INFER);
-    hipError_t e = launch_wm_infer(a, h->stream);
-    if (e != hipSuccess) return fail("wm_embedded_step launch failed: %s (the state and output arrays must be 16-byte aligned)", hipGetErrorString(e));
-    return 0;
-}
-
-// host arrays: one scratch of [u | v | T | dz_uw | dz_vw | dz_wT | top(3 n) | halo(3 n)], the step in place on its first three blocks
-static int wm_infer_host(colnde_handle* h, const char* fn, bool fused, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
-                         const float* halo_bottom, float Lz, float dt, const float* params, int ca, float* dz_uw, float* dz_vw, float* dz_wT, float* u_out,
-                         float* v_out, float* T_out, int n_columns) {
-    const void* const ptrs[8] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT};
-    if (wm_infer_check(h, fn, ptrs, 8, Lz, n_columns)) return 1;
-    if (fused && impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t nf = (size_t)n_columns * WM_NZ, nh = (size_t)n_columns;
-    float* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (6 * nf + 6 * nh) * sizeof(float)));
-    int rc = 1;
-    do {
-        const float* srcs[3] = {u, v, T};
-        bool ok = hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        for (int f = 0; f < 3 && ok; f++) ok = hipMemcpyAsync(d + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok) ok = hipMemcpyAsync(d + 6 * nf, top_flux, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && fused && halo_bottom) ok = hipMemcpyAsync(d + 6 * nf + 3 * nh, halo_bottom, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (!ok) { fail("%s: host-to-device copy failed", fn); break; }
-        if (fused) {
-            if (colnde_wm_embedded_step_dev(h, h->d_w, d, d + nf, d + 2 * nf, d + 6 * nf, halo_bottom ? d + 6 * nf + 3 * nh : nullptr, Lz, dt, params, ca,
-                                            d + 3 * nf, d + 4 * nf, d + 5 * nf, d, d + nf, d + 2 * nf, n_columns)) break;
-        } else if (colnde_wm_infer_dz_flux_dev(h, h->d_w, d, d + nf, d + 2 * nf, d + 6 * nf, Lz, d + 3 * nf, d + 4 * nf, d + 5 * nf, n_columns)) break;
-        float* dsts[6] = {u_out, v_out, T_out, dz_uw, dz_vw, dz_wT};
-        for (int f = fused ? 0 : 3; f < 6 && ok; f++) ok = hipMemcpyAsync(dsts[f], d + f * nf, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("%s: device-to-host copy failed", fn); break; }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-extern "C" int colnde_wm_infer_dz_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux, float Lz,
-                                       float* dz_uw, float* dz_vw, float* dz_wT, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    return wm_infer_host(h, __func__, false, weights, u, v, T, top_flux, nullptr, Lz, 0.0f, nullptr, 0, dz_uw, dz_vw, dz_wT, nullptr, nullptr, nullptr, n_columns);
-}
-
-extern "C" int colnde_wm_embedded_step(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
-                                       const float* halo_bottom, float Lz, float dt, const float params[7], int convective_adjustment, float* dz_uw,
-                                       float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    return wm_infer_host(h, __func__, true, weights, u, v, T, top_flux, halo_bottom, Lz, dt, params, convective_adjustment, dz_uw, dz_vw, dz_wT, u_out, v_out,
-                         T_out, n_columns);
-}
-
-// ---- the saved-state flux diagnoses of the wind-mixing embedding (NDE_oceananigans.jl:157-191, :226-286) ---------------------------------
-static int wm_diag_launch(colnde_handle* h, const char* fn, bool fused, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
-                          const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt, const float params[7], int ca,
-                          float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT,
-                          int n_columns) {
-    WmInferArgs a = {};
-    wm_infer_args(h, &a);
-    const float dz = Lz / (float)WM_NZ;
-    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.Lz = Lz; a.n_col = n_columns;
-    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT; a.fused = fused;
-    a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top;
-    a.mpp = mpp_params(params, fused ? dt : dz * dz, dz, ca);          // (the diagnosis alone takes no step: c is not read)
-    a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
-    a.diag = true; a.uw = d_uw; a.vw = d_vw; a.wT = d_wT;
-    Timed tm(h, K_FLUXDIAG);
-    hipError_t e = launch_wm_infer(a, h->stream);
-    if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", fn, hipGetErrorString(e));
-    return 0;
-}
-static int wm_diag_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, const float params[7], int n_columns) {
-    if (wm_infer_check(h, fn, ptrs, n_ptrs, Lz, n_columns)) return 1;
-    if (!params) return fail("null pointer argument");
-    if (!(params[2] != 0.0f) || !(params[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
-    for (int i = 0; i < n_ptrs; i++)
-        if ((uintptr_t)ptrs[i] & 15) return fail("%s: the state and output arrays must be 16-byte aligned", fn);
-    return 0;
-}
-
-extern "C" int colnde_wm_diagnose_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
-                                           const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, const float params[7],
-                                           int convective_adjustment, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[8] = {d_u, d_v, d_T, d_uw, d_vw, d_wT, d_weights, d_top_flux};
-    if (wm_diag_check(h, __func__, ptrs, 6, Lz, params, n_columns)) return 1;
-    if (!d_weights || !d_top_flux) return fail("null pointer argument");
-    HIPCHK(hipSetDevice(h->device));
-    return wm_diag_launch(h, __func__, false, d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, 0.0f, params, convective_adjustment, nullptr,
-                          nullptr, nullptr, nullptr, nullptr, nullptr, d_uw, d_vw, d_wT, n_columns);
-}
-
-extern "C" int colnde_wm_embedded_step_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
-                                                const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt,
-                                                const float params[7], int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT,
-                                                float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[12] = {d_u, d_v, d_T, d_dz_uw, d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT};
-    if (wm_diag_check(h, __func__, ptrs, 12, Lz, params, n_columns)) return 1;
-    if (!d_weights || !d_top_flux) return fail("null pointer argument");
-    if (impl_diff_check(h, d_u, d_v, d_T, d_u_out, d_v_out, d_T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    // One launch, by measurement (profiles/wm_diag_rate.json): it beats colnde_wm_embedded_step_dev + colnde_wm_diagnose_flux_dev by far more than
-    // the spread at 9,216, 65,536 and 1,048,576 columns.
-    return wm_diag_launch(h, __func__, true, d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, params, convective_adjustment, d_dz_uw,
-                          d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT, n_columns);
-}
-
-// host arrays: one scratch of [u | v | T | dz_uw | dz_vw | dz_wT | faces(3 x n x 33, padded) | top(3 n) | halo_bottom(3 n) | halo_top(3 n)]
-static int wm_diag_host(colnde_handle* h, const char* fn, bool step, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
-                        const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params, int ca, float* dz_uw, float* dz_vw, float* dz_wT,
-                        float* u_out, float* v_out, float* T_out, float* uw, float* vw, float* wT, int n_columns) {
-    HIPCHK(hipSetDevice(h->device));
-    const size_t nf = (size_t)n_columns * WM_NZ, nfc = ((size_t)n_columns * (WM_NZ + 1) + 3) / 4 * 4, nh = ((size_t)n_columns + 3) / 4 * 4, nc = (size_t)n_columns;
-    float* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (6 * nf + 3 * nfc + 9 * nh) * sizeof(float)));
-    float *d_f = d + 6 * nf, *d_top = d_f + 3 * nfc, *d_hb = d_top + 3 * nh, *d_ht = d_hb + 3 * nh;
-    int rc = 1;
-    do {
-        const float* srcs[3] = {u, v, T};
-        bool ok = hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        for (int f = 0; f < 3 && ok; f++) ok = hipMemcpyAsync(d + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok) ok = hipMemcpyAsync(d_top, top_flux, 3 * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && halo_bottom) ok = hipMemcpyAsync(d_hb, halo_bottom, 3 * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && halo_top) ok = hipMemcpyAsync(d_ht, halo_top, 3 * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (!ok) { fail("%s: host-to-device copy failed", fn); break; }
-        if (step) {
-            if (colnde_wm_embedded_step_flux_dev(h, h->d_w, d, d + nf, d + 2 * nf, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, dt, params, ca,
-                                                 d + 3 * nf, d + 4 * nf, d + 5 * nf, d, d + nf, d + 2 * nf, d_f, d_f + nfc, d_f + 2 * nfc, n_columns)) break;
-            float* dsts[6] = {u_out, v_out, T_out, dz_uw, dz_vw, dz_wT};
-            for (int f = 0; f < 6 && ok; f++) ok = hipMemcpyAsync(dsts[f], d + f * nf, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        } else if (colnde_wm_diagnose_flux_dev(h, h->d_w, d, d + nf, d + 2 * nf, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, params, ca,
-                                               d_f, d_f + nfc, d_f + 2 * nfc, n_columns)) break;
-        float* fd[3] = {uw, vw, wT};
-        for (int f = 0; f < 3 && ok; f++)
-            ok = hipMemcpyAsync(fd[f], d_f + f * nfc, nc * (WM_NZ + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("%s: device-to-host copy failed", fn); break; }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-extern "C" int colnde_wm_diagnose_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
-                                       const float* halo_bottom, const float* halo_top, float Lz, const float params[7], int convective_adjustment, float* uw,
-                                       float* vw, float* wT, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[8] = {weights, u, v, T, top_flux, uw, vw, wT};
-    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
-    if (!params) return fail("null pointer argument");
-    return wm_diag_host(h, __func__, false, weights, u, v, T, top_flux, halo_bottom, halo_top, Lz, 0.0f, params, convective_adjustment, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, uw, vw, wT, n_columns);
-}
-
-extern "C" int colnde_wm_embedded_step_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
-                                            const float* halo_bottom, const float* halo_top, float Lz, float dt, const float params[7],
-                                            int convective_adjustment, float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out,
-                                            float* uw, float* vw, float* wT, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[11] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT, uw, vw, wT};
-    if (wm_infer_check(h, __func__, ptrs, 11, Lz, n_columns)) return 1;
-    if (impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
-    return wm_diag_host(h, __func__, true, weights, u, v, T, top_flux, halo_bottom, halo_top, Lz, dt, params, convective_adjustment, dz_uw, dz_vw, dz_wT, u_out,
-                        v_out, T_out, uw, vw, wT, n_columns);
-}
-
-// ---- the K models of an ensemble in the embedding at once (engine_wm_infer.hip: wm_infer_ens_kernel) -------------------------------
-// {nu0, nu_minus, dRi, Ric, Pr, alpha, g} of model k as the handle holds them (colnde_create_ensemble / colnde_ensemble_set_physics; cfg.alpha, cfg.g)
-static void wm_ens_model_params(const colnde_handle* h, int k, float out[7]) {
-    const colnde_config c = model_config(&h->cfg, h->phys_raw.empty() ? nullptr : h->phys_raw.data(), k);
-    out[0] = c.nu0; out[1] = c.nu_minus; out[2] = c.dRi; out[3] = c.Ric; out[4] = c.Pr; out[5] = c.alpha; out[6] = c.g;
-}
-
-// everything the call refuses that does not depend on where the arrays live; host: the host twin's arrays (no alignment rule of their own)
-static int wm_ens_check(colnde_handle* h, const char* fn, const float* weights, const float* u, const float* v, const float* T, const float* top_flux, float Lz,
-                        float dt, const float* params, const float* dz_uw, const float* dz_vw, const float* dz_wT, const float* u_out, const float* v_out,
-                        const float* T_out, const float* uw, const float* vw, const float* wT, int n_columns, bool host) {
-    if (!h) return fail("null handle");
-    if (h->closure)
-        return fail("%s takes K weight vectors, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", fn,
-                    h->n_models);
-    const colnde_config& c = h->cfg;
-    if (c.model != COLNDE_MODEL_WIND_MIXING)
-        return fail("%s needs a wind-mixing handle (three flux networks on [u; v; T]); a free-convection handle has colnde_infer_forcing", fn);
-    if (c.smooth_NN)
-        return fail("%s: the embedding has no smoothing filter (NDE_oceananigans.jl:288-329 apply the networks unfiltered), so a handle with smooth_NN is refused", fn);
-    if (!(c.Nz == WM_NZ && c.n_layers == 3 && c.layer_sizes[0] == 3 * WM_NZ && c.layer_sizes[1] == WM_H1 && c.layer_sizes[2] == WM_H2 &&
-          c.layer_sizes[3] == WM_NZ - 1 && c.activations[2] == COLNDE_ACT_IDENTITY)) {
-        std::string shape;
-        for (int l = 0; l <= c.n_layers; l++) shape += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
-        return fail("%s covers Nz = 32 with three 96-50-20-31 networks and an identity output layer; this handle has Nz = %d, networks %s, output activation %d", fn,
-                    c.Nz, shape.c_str(), c.activations[c.n_layers - 1]);
-    }
-    if (!weights || !u || !v || !T || !top_flux || !dz_uw || !dz_vw || !dz_wT) return fail("null pointer argument");
-    const int n_step = (u_out != nullptr) + (v_out != nullptr) + (T_out != nullptr), n_flux = (uw != nullptr) + (vw != nullptr) + (wT != nullptr);
-    if (n_step != 0 && n_step != 3)
-        return fail("%s: u_out, v_out, T_out are one output group — all three given (the implicit step is taken) or all three NULL (no step); %d of 3 given", fn, n_step);
-    if (n_flux != 0 && n_flux != 3)
-        return fail("%s: uw, vw, wT are one output group — all three given (the face diagnosis) or all three NULL; %d of 3 given", fn, n_flux);
-    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
-    if (n_step && !(dt > 0.0f)) return fail("%s: dt > 0 required when a step is asked for (u_out, v_out, T_out given); dt = %g", fn, dt);
-    for (int k = 0; k < h->n_models; k++) {
-        float own[7];
-        const float* p = params ? params + (size_t)7 * k : own;
-        if (!params) wm_ens_model_params(h, k, own);
-        if (n_step && (!(p[0] >= 0.0f) || !(p[1] >= 0.0f))) return fail("nu0 >= 0 and nu_minus >= 0 required (the tridiagonal must stay diagonally dominant)");
-        if (!(p[2] != 0.0f) || !(p[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
-    }
-    if (!host) {
-        const void* const ptrs[12] = {u, v, T, dz_uw, dz_vw, dz_wT, u_out, v_out, T_out, uw, vw, wT};
-        for (const void* p : ptrs)
-            if ((uintptr_t)p & 15) return fail("%s: the state and output arrays must be 16-byte aligned", fn);
-    }
-    return 0;
-}
-
-// the device array [K] of the sweeps' constants: uploaded when it differs from what the device holds (an embedding calls with the same constants every iteration)
-static int wm_ens_upload_mpp(colnde_handle* h, const float* params, bool step, float dt, float dz, int ca) {
-    const size_t K = (size_t)h->n_models;
-    std::vector<MppParams> P(K);
-    for (size_t k = 0; k < K; k++) {
-        float own[7];
-        const float* p = params ? params + 7 * k : own;
-        if (!params) wm_ens_model_params(h, (int)k, own);
-        P[k] = mpp_params(p, step ? dt : dz * dz, dz, ca);            // (without a step c is not read: 1, as the single-model diagnosis passes it)
-    }
-    if (h->d_wm_ens_mpp && h->wm_ens_mpp_host.size() == K && !memcmp(h->wm_ens_mpp_host.data(), P.data(), K * sizeof(MppParams))) return 0;
-    if (!h->d_wm_ens_mpp) HIPCHK(hipMalloc((void**)&h->d_wm_ens_mpp, K * sizeof(MppParams)));
-    // (kernels in flight on the stream may still read the previous table: the copy is ordered on the stream and completed before returning)
-    h->wm_ens_mpp_host.clear();
-    HIPCHK(hipMemcpyAsync(h->d_wm_ens_mpp, P.data(), K * sizeof(MppParams), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->wm_ens_mpp_host.swap(P);
-    return 0;
-}
-
-static int wm_ens_grid_cap() {
-    const char* e = getenv("COLNDE_WM_ENS_GRID");      // test override: at most this many workgroups (several models per workgroup at small K)
-    return e && *e ? std::max(0, atoi(e)) : 0;
-}
-
-extern "C" int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
-                                               const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt,
-                                               const float* params, int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT,
-                                               float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
-    if (wm_ens_check(h, __func__, d_weights, d_u, d_v, d_T, d_top_flux, Lz, dt, params, d_dz_uw, d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT,
-                     n_columns, false))
-        return 1;
-    HIPCHK(hipSetDevice(h->device));
-    const bool step = d_u_out != nullptr;
-    if (wm_ens_upload_mpp(h, params, step, dt, Lz / (float)WM_NZ, convective_adjustment)) return 1;
-    WmEnsArgs a = {};
-    for (int i = 0; i < 6; i++) { a.mu[i] = h->cfg.mu[i]; a.sigma[i] = h->cfg.sigma[i]; }
-    a.act1 = h->cfg.activations[0];
-    a.act2 = h->cfg.activations[1];
-    a.n_models = h->n_models; a.weights = d_weights; a.w_stride = (size_t)h->m.n_params;
-    a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top; a.Lz = Lz; a.mpp = h->d_wm_ens_mpp;
-    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT;
-    a.fused = step; a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
-    a.diag = d_uw != nullptr; a.uw = d_uw; a.vw = d_vw; a.wT = d_wT;
-    a.n_col = n_columns;
-    a.grid_cap = wm_ens_grid_cap();
-    // One launch at every size, by measurement (profiles/wm_ens_embed_rate.json)
-    Timed tm(h, K_FLUXDIAG);
-    hipError_t e = launch_wm_infer_ens(a, h->stream);
-    if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", __func__, hipGetErrorString(e));
-    return 0;
-}
-
-// host arrays: one scratch of [u | v | T | dz_uw | dz_vw | dz_wT | faces(3 x K n 33, padded) | top(3 n) | halo_bottom(K 3 n) | halo_top(K 3 n)], the step in place
-extern "C" int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
-                                           const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params, int convective_adjustment,
-                                           float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, float* uw, float* vw, float* wT,
-                                           int n_columns) {
-    if (wm_ens_check(h, __func__, weights, u, v, T, top_flux, Lz, dt, params, dz_uw, dz_vw, dz_wT, u_out, v_out, T_out, uw, vw, wT, n_columns, true)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t K = (size_t)h->n_models, nc = (size_t)n_columns, nf = K * nc * WM_NZ, nfa = K * nc * (WM_NZ + 1), nfc = (nfa + 3) / 4 * 4,
-                 nt = (3 * nc + 3) / 4 * 4, nh = (3 * K * nc + 3) / 4 * 4;
-    const bool step = u_out != nullptr, flux = uw != nullptr;
-    float* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (6 * nf + 3 * nfc + nt + 2 * nh) * sizeof(float)));
-    float *d_f = d + 6 * nf, *d_top = d_f + 3 * nfc, *d_hb = d_top + nt, *d_ht = d_hb + nh;
-    int rc = 1;
-    do {
-        const float* srcs[3] = {u, v, T};
-        bool ok = hipMemcpyAsync(h->d_w, weights, sizeof(float) * K * h->m.n_params, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        for (int f = 0; f < 3 && ok; f++) ok = hipMemcpyAsync(d + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok) ok = hipMemcpyAsync(d_top, top_flux, 3 * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && halo_bottom) ok = hipMemcpyAsync(d_hb, halo_bottom, 3 * K * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && halo_top) ok = hipMemcpyAsync(d_ht, halo_top, 3 * K * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (!ok) { fail("%s: host-to-device copy failed", __func__); break; }
-        if (colnde_ensemble_wm_embedded_dev(h, h->d_w, d, d + nf, d + 2 * nf, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, dt, params,
-                                            convective_adjustment, d + 3 * nf, d + 4 * nf, d + 5 * nf, step ? d : nullptr, step ? d + nf : nullptr,
-                                            step ? d + 2 * nf : nullptr, flux ? d_f : nullptr, flux ? d_f + nfc : nullptr, flux ? d_f + 2 * nfc : nullptr, n_columns))
-            break;
-        float* dsts[6] = {u_out, v_out, T_out, dz_uw, dz_vw, dz_wT};
-        for (int f = step ? 0 : 3; f < 6 && ok; f++) ok = hipMemcpyAsync(dsts[f], d + f * nf, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        float* fd[3] = {uw, vw, wT};
-        for (int f = 0; f < 3 && ok && flux; f++) ok = hipMemcpyAsync(fd[f], d_f + f * nfc, nfa * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("%s: device-to-host copy failed", __func__); break; }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-// diagnose_baseline_flux_uw / _vw / _wT (:157-191; column_ops.hip): no networks, any handle kind
-static int mpp_diag_check(colnde_handle* h, const void* const* ptrs, int n_ptrs, float dz, const float params[7], int n_columns) {
-    if (!h) return fail("null handle");
-    for (int i = 0; i < n_ptrs; i++)
-        if (!ptrs[i]) return fail("null pointer argument");
-    if (!params) return fail("null pointer argument");
-    if (n_columns < 1) return fail("n_columns must be >= 1");
-    if (!(dz > 0.0f)) return fail("dz > 0 required");
-    if (!(params[2] != 0.0f) || !(params[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
-    if (h->m.Nz < 2 || h->m.Nz > 128) return fail("the flux diagnosis supports 2 <= Nz <= 128 (Nz = %d)", h->m.Nz);
-    return 0;
-}
-
-extern "C" int colnde_mpp_diagnose_flux_dev(colnde_handle* h, const float* d_u, const float* d_v, const float* d_T, const float* d_top_flux,
-                                            const float* d_halo_bottom, float dz, const float params[7], int convective_adjustment, float* d_uw, float* d_vw,
-                                            float* d_wT, int n_columns) {
-    const void* const ptrs[7] = {d_u, d_v, d_T, d_top_flux, d_uw, d_vw, d_wT};
-    if (mpp_diag_check(h, ptrs, 7, dz, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    Timed tm(h, K_FLUXDIAG);
-    hipError_t e = launch_mpp_diagnose_flux(d_u, d_v, d_T, d_top_flux, d_halo_bottom, dz, params, convective_adjustment, d_uw, d_vw, d_wT, h->m.Nz, n_columns,
-                                            h->stream);
-    if (e != hipSuccess) return fail("mpp_diagnose_flux launch failed: %s", hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int colnde_mpp_diagnose_flux(colnde_handle* h, const float* u, const float* v, const float* T, const float* top_flux, const float* halo_bottom,
-                                        float dz, const float params[7], int convective_adjustment, float* uw, float* vw, float* wT, int n_columns) {
-    const void* const ptrs[7] = {u, v, T, top_flux, uw, vw, wT};
-    if (mpp_diag_check(h, ptrs, 7, dz, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t Nz = (size_t)h->m.Nz, nf = (size_t)n_columns * Nz, nfc = ((size_t)n_columns * (Nz + 1) + 3) / 4 * 4, nh = (size_t)n_columns;
-    float* d = nullptr;       // [faces(3, padded to 16 bytes) | u | v | T | top(3 n) | halo(3 n)]
-    HIPCHK(hipMalloc((void**)&d, (3 * nfc + 3 * nf + 6 * nh) * sizeof(float)));
-    float *d_s = d + 3 * nfc, *d_top = d_s + 3 * nf, *d_hb = d_top + 3 * nh;
-    int rc = 1;
-    do {
-        const float* srcs[3] = {u, v, T};
-        bool ok = true;
-        for (int f = 0; f < 3 && ok; f++) ok = hipMemcpyAsync(d_s + f * nf, srcs[f], nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok) ok = hipMemcpyAsync(d_top, top_flux, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && halo_bottom) ok = hipMemcpyAsync(d_hb, halo_bottom, 3 * nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (!ok) { fail("mpp_diagnose_flux: host-to-device copy failed"); break; }
-        if (colnde_mpp_diagnose_flux_dev(h, d_s, d_s + nf, d_s + 2 * nf, d_top, halo_bottom ? d_hb : nullptr, dz, params, convective_adjustment, d, d + nfc,
-                                         d + 2 * nfc, n_columns)) break;
-        float* fd[3] = {uw, vw, wT};
-        for (int f = 0; f < 3 && ok; f++)
-            ok = hipMemcpyAsync(fd[f], d + f * nfc, (size_t)n_columns * (Nz + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("mpp_diagnose_flux: device-to-host copy failed"); break; }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-// ---- free-convection embedded step (free_convection/src/oceananigans_nn.jl:100-118, :153-165; engine_fc_embed.hip) ----------------------
-// the handles the kernels cover: the network shapes of fc32 (fc_supported), whatever engine and stepper the handle trains with
-static bool fce_covers(const colnde_handle* h) {
-    const DevModel& m = h->m;
-    return !h->closure && !h->ensemble && !h->ag_rows && (m.model == COLNDE_MODEL_FREE_CONVECTION || m.model == COLNDE_MODEL_CONV_ADJ_NDE) &&
-           (m.Nz == 32 || m.Nz == 64) && m.n_layers == 3 && m.n_nets == 1 && m.sizes[0] == m.Nz && m.sizes[1] == 4 * m.Nz && m.sizes[2] == 4 * m.Nz &&
-           m.sizes[3] == m.Nz - 1 && m.acts[0] == COLNDE_ACT_RELU && m.acts[1] == COLNDE_ACT_RELU && m.acts[2] == COLNDE_ACT_IDENTITY;
-}
-static int fce_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, float K, int n_columns) {
-    if (!h) return fail("null handle");
-    const colnde_config& c = h->cfg;
-    if (c.model == COLNDE_MODEL_WIND_MIXING)
-        return fail("%s needs a free-convection handle (one network on T); a wind-mixing handle has colnde_wm_embedded_step", fn);
-    if (h->ag_rows) return fail("%s: this handle's network keeps its activation rows in global memory (a wide network); the embedded step covers the fc32 shapes only", fn);
-    if (c.Nz != 32 && c.Nz != 64) return fail("%s covers Nz = 32 or 64 (this handle has Nz = %d)", fn, c.Nz);
-    if (!fce_covers(h)) {
-        std::string shape;
-        for (int l = 0; l <= c.n_layers; l++) shape += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
-        return fail("%s covers the fc32 network Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1); this handle has Nz = %d and network %s", fn, c.Nz,
-                    shape.c_str());
-    }
-    for (int i = 0; i < n_ptrs; i++)
-        if (!ptrs[i]) return fail("null pointer argument");
-    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
-    if (!(K >= 0.0f)) return fail("K >= 0 required");
-    return 0;
-}
-// first call on a handle: the operand images (a handle on another engine has none yet) and the kernels' LDS limits
-static int fce_prepare(colnde_handle* h) {
-    HIPCHK(hipSetDevice(h->device));
-    if (h->fce_ready) return 0;
-    if (!h->d_fc_imgf) HIPCHK(hipMalloc((void**)&h->d_fc_imgf, fc_image_floats(h->m.Nz) * sizeof(float)));
-    if (!h->d_fc_imgb) HIPCHK(hipMalloc((void**)&h->d_fc_imgb, fc_image_floats(h->m.Nz) * sizeof(float)));
-    if (!h->d_fc_bias) HIPCHK(hipMalloc((void**)&h->d_fc_bias, fc_bias_floats(h->m.Nz) * sizeof(float)));
-    hipError_t e = fce_set_kernel_attributes();
-    if (e != hipSuccess) return fail("hipFuncSetAttribute (fc_embed) failed: %s", hipGetErrorString(e));
-    h->fce_ready = true;
-    return 0;
-}
-static int fce_launch(colnde_handle* h, const char* fn, bool step, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
-                      const float* d_halo_top, float Lz, float dt, float K, float* d_dz_wT, float* d_T_out, float* d_wT_faces, int n_columns) {
-    if (fce_prepare(h)) return 1;
-    FcEmbedArgs a = {};
-    a.cw = fc_tile_width(n_columns);                         // (the images are packed per call: this call's own tile width, as colnde_infer_forcing)
-    hipError_t e = fc_launch_pack(h->m, a.cw, d_weights, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, nullptr, nullptr, h->stream);
-    if (e != hipSuccess) return fail("fc32 pack launch failed: %s", hipGetErrorString(e));
-    a.imgf = h->d_fc_imgf; a.bias = h->d_fc_bias; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top;
-    a.Lz = Lz; a.dt = dt; a.K = K; a.dz_wT = d_dz_wT; a.T_out = d_T_out; a.wT_faces = d_wT_faces; a.n_col = n_columns; a.step = step;
-    Timed tm(h, K_FCEMBED);
-    e = launch_fc_embed(h->m, a, h->stream);
-    if (e != hipSuccess) return fail("%s launch failed: %s (T and the output arrays must be 16-byte aligned)", fn, hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int colnde_fc_embedded_step_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
-                                           const float* d_halo_top, float Lz, float dt, float K, float* d_dz_wT, float* d_T_out, float* d_wT_faces,
-                                           int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[5] = {d_weights, d_T, d_top_flux, d_dz_wT, d_T_out};
-    if (fce_check(h, __func__, ptrs, 5, Lz, K, n_columns)) return 1;
-    if (!(dt > 0.0f)) return fail("dt > 0 required");
-    // Measured (profiles/fc_embed_rate.json): without the diagnosis the fused kernel is slower than the two launches it replaces at
-    // 65,536 columns (one lane per column sweeps while the other waves of the workgroup wait), so that is what this call issues — the same bits,
-    // timed under slots 4 and 6.  With wT_faces the one launch beats the three it replaces at every size measured and is kept.
-    // COLNDE_FC_EMBED_FUSED=1 forces the fused kernel (tools/fc_embed_rate.py measures it that way).
-    const char* ef = getenv("COLNDE_FC_EMBED_FUSED");
-    if (!d_wT_faces && !(ef && atoi(ef) != 0)) {
-        if (((uintptr_t)d_T | (uintptr_t)d_dz_wT | (uintptr_t)d_T_out) & 15) return fail("%s: T and the output arrays must be 16-byte aligned", __func__);
-        if (colnde_infer_dz_wT_dev(h, d_weights, d_T, d_top_flux, Lz, d_dz_wT, n_columns)) return 1;
-        return colnde_convective_adjustment_dev(h, d_T, d_halo_bottom, d_halo_top, dt, Lz / (float)h->m.Nz, K, d_T_out, n_columns);
-    }
-    return fce_launch(h, __func__, true, d_weights, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, K, d_dz_wT, d_T_out, d_wT_faces, n_columns);
-}
-
-extern "C" int colnde_fc_diagnose_wT_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
-                                         const float* d_halo_top, float Lz, float K, float* d_wT_faces, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[4] = {d_weights, d_T, d_top_flux, d_wT_faces};
-    if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
-    return fce_launch(h, __func__, false, d_weights, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, 0.0f, K, nullptr, nullptr, d_wT_faces, n_columns);
-}
-
-// host arrays: one scratch of [T (stepped in place) | dz_wT | wT_faces | top | halo_bottom | halo_top]
-static int fce_host(colnde_handle* h, const char* fn, bool step, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
-                    const float* halo_top, float Lz, float dt, float K, float* dz_wT, float* T_out, float* wT_faces, int n_columns) {
-    HIPCHK(hipSetDevice(h->device));
-    const size_t Nz = (size_t)h->m.Nz, nf = (size_t)n_columns * Nz, nfc = ((size_t)n_columns * (Nz + 1) + 3) / 4 * 4, nh = (size_t)n_columns;
-    float* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (2 * nf + nfc + 3 * nh) * sizeof(float)));
-    float *d_dz = d + nf, *d_faces = d + 2 * nf, *d_top = d_faces + nfc, *d_hb = d_top + nh, *d_ht = d_hb + nh;
-    int rc = 1;
-    do {
-        bool ok = hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok) ok = hipMemcpyAsync(d, T, nf * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok) ok = hipMemcpyAsync(d_top, top_flux, nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && halo_bottom) ok = hipMemcpyAsync(d_hb, halo_bottom, nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (ok && halo_top) ok = hipMemcpyAsync(d_ht, halo_top, nh * sizeof(float), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        if (!ok) { fail("%s: host-to-device copy failed", fn); break; }
-        if (step) {
-            if (colnde_fc_embedded_step_dev(h, h->d_w, d, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, dt, K, d_dz, d,
-                                            wT_faces ? d_faces : nullptr, n_columns)) break;
-            ok = hipMemcpyAsync(dz_wT, d_dz, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess &&
-                 hipMemcpyAsync(T_out, d, nf * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        } else if (colnde_fc_diagnose_wT_dev(h, h->d_w, d, d_top, halo_bottom ? d_hb : nullptr, halo_top ? d_ht : nullptr, Lz, K, d_faces, n_columns)) break;
-        if (ok && wT_faces) ok = hipMemcpyAsync(wT_faces, d_faces, (size_t)n_columns * (Nz + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-        if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) { fail("%s: device-to-host copy failed", fn); break; }
-        rc = 0;
-    } while (0);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-extern "C" int colnde_fc_embedded_step(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
-                                       const float* halo_top, float Lz, float dt, float K, float* dz_wT, float* T_out, float* wT_faces, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[5] = {weights, T, top_flux, dz_wT, T_out};
-    if (fce_check(h, __func__, ptrs, 5, Lz, K, n_columns)) return 1;
-    if (!(dt > 0.0f)) return fail("dt > 0 required");
-    return fce_host(h, __func__, true, weights, T, top_flux, halo_bottom, halo_top, Lz, dt, K, dz_wT, T_out, wT_faces, n_columns);
-}
-
-extern "C" int colnde_fc_diagnose_wT(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
-                                     const float* halo_top, float Lz, float K, float* wT_faces, int n_columns) {
-    SINGLE_MODEL_ONLY(h);
-    const void* const ptrs[4] = {weights, T, top_flux, wT_faces};
-    if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
-    return fce_host(h, __func__, false, weights, T, top_flux, halo_bottom, halo_top, Lz, 0.0f, K, nullptr, nullptr, wT_faces, n_columns);
+    st.to(h->d_w, weights, (size_t)h->m.n_params);
+    st.out(&d_o, out, (size_t)h->n_col * 6 * h->cfg.n_save);
+    if (st.upload()) return 1;
+    if (colnde_loss_per_tstep_dev(h, h->d_w, d_o)) return 1;
+    return st.download();
 }
 
 extern "C" int colnde_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_grad, float* d_m, float* d_v, float eta,
@@ -2846,7 +1977,7 @@ extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
     return 0;
 }
 
-// Every environment variable some part of the library reads (api.hip, engine_*.hip): the list colnde_describe reports from.
+// Every environment variable some part of the library reads (api.hip, api_embed.hip, engine_*.hip): the list colnde_describe reports from.
 static const char* const COLNDE_ENV_SWITCHES[] = {
     "COLNDE_FWD_SPLIT", "COLNDE_ADJ_SPLIT", "COLNDE_DW_SPLIT", "COLNDE_ADJ_GEOM", "COLNDE_FWD_WLDS", "COLNDE_FWD_THREADS", "COLNDE_T16_FWD_HELPER",
     "COLNDE_T16_ADJ_HELPER", "COLNDE_T16_FWD_SPLIT", "COLNDE_T16_ADJ_SPLIT", "COLNDE_FC", "COLNDE_FC_CW", "COLNDE_FC_EMBED_FUSED", "COLNDE_FC_BLOCK", "COLNDE_FC_SEG", "COLNDE_WM_ENS_GRID",

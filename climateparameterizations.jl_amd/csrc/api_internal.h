@@ -1,0 +1,218 @@
+// api_internal.h — what the translation units of the C ABI share (api.hip, api_embed.hip): the handle, the error and timing plumbing, and the
+// staging of host arrays through one device scratch.  Not part of the public header; nothing here is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "engine_tile16.h"
+#include "engine_regtile.h"
+#include "engine_fc.h"
+#include "column_ops.h"
+#include "engine_closure.h"
+#include "engine_wm_infer.h"
+#include "engine_fc_embed.h"
+
+#pragma GCC visibility push(hidden)
+
+struct colnde_handle;
+
+// ---- defined once, in api.hip ------------------------------------------------------------------------------
+int fail(const char* fmt, ...);   // stores the thread-local message of colnde_last_error, returns 1
+int pack(colnde_handle* h, const float* d_weights);
+int ensure_tmp(colnde_handle* h, size_t n_columns);
+int ensure_ag(colnde_handle* h, size_t tiles);
+void drain_events(colnde_handle* h);
+colnde_config model_config(const colnde_config* cfg, const float* physics, int k);
+// ---- defined in api_embed.hip: the handles the embedding's kernels cover (colnde_describe reports them) ------
+bool wm_infer_covers(const colnde_handle* h);
+bool fce_covers(const colnde_handle* h);
+
+// Entry points that take ONE weight vector refuse an ensemble handle (colnde_create_ensemble)
+#define SINGLE_MODEL_ONLY(h)                                                                                                              \
+    do {                                                                                                                                  \
+        if ((h) && (h)->closure)                                                                                                          \
+            return fail("%s takes a weight vector, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", \
+                        __func__, (h)->n_models);                                                                                         \
+        if ((h) && (h)->ensemble)                                                                                                         \
+            return fail("%s takes one weight vector, but this handle holds an ensemble of %d models: use colnde_ensemble_* (include/colnde.h)", \
+                        __func__, (h)->n_models);                                                                                         \
+    } while (0)
+
+#define HIPCHK(expr)                                                                              \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+// the timing slots of colnde_kernel_time
+enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1 = 5, K_CONVADJ = 6, K_ADAM = 7, K_IMPLDIFF = 8, K_FCEMBED = 9, K_FLUXDIAG = 10, K_COUNT = 11 };
+
+struct PendingEvent { hipEvent_t a, b; int which; };
+
+struct colnde_handle {
+    colnde_config cfg;
+    std::vector<float> save_times;
+    DevModel m;
+    PackInfo pk;
+    AdjointGeom geo;
+    bool geo_ok = false;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int n_col = 0, n_tiles = 0;
+    int64_t n_col_total = 0;
+    size_t lds_fwd = 0, lds_adj = 0, lds_fwd_solve = 0;
+    int fwd_threads = 256;
+    bool fwd_wlds = false;
+    bool adj_helper = true;         // ... and in the adjoint: a helper wave carries λ, x̄ and the physics pullback for the three net waves
+    bool fwd_helper = true;         // ... four waves per tile: a helper wave evaluates the Richardson-number closure for the three net waves
+    bool split_rich = false;        // ... with the rich tape (activations, derivatives, physics coefficients) in place of the pre-activation tape
+    bool adj_split = false;         // ... and the gradient by rt16s_adjoint_kernel + tile16's dW GEMM
+    bool fwd_split = false;         // forward solves by the net-split kernels (rt16sh_forward_kernel: three net waves + a helper wave per tile)
+    bool use_rt = false;            // register-resident tile engine (static 96-50-20-31 wind-mixing shape)
+    bool sp_fwd = true, sp_adj = true, sp_dw = true;   // matrix arithmetic of the forward-solve / adjoint / weight-gradient kernels: exact three-way bf16 split (true) or
+                                                      // f32 MFMA — cfg.matrix_arithmetic with the test overrides COLNDE_{FWD,ADJ,DW}_SPLIT (resolve_arithmetic)
+    bool use_fc = false;            // 32-column free-convection engine (engine_fc.hip: Nz = 32 | 64, the reference's relu network, RK4)
+    bool fce_ready = false;         // colnde_fc_embedded_step / colnde_fc_diagnose_wT: images allocated, LDS limits raised (first call)
+    float *d_fc_imgf = nullptr, *d_fc_imgb = nullptr, *d_fc_bias = nullptr;
+    unsigned int *d_fc_simgf = nullptr, *d_fc_simgb = nullptr;   // the split operand images (COLNDE_MATRIX_BF16X3_EXACT; 32-column tiles)
+    unsigned int* d_fc_masks = nullptr;
+    unsigned long long* d_fc_switch = nullptr;   // ConvectiveAdjustmentNDE: the taped switch patterns
+    int fc_block = 0, fc_nblocks = 0, fc_rows = 0;   // gradient path: columns per pass (multiple of 32), passes, slab rows
+    int fc_seg = 0, fc_nseg = 0;                      // ... save intervals per time segment of the tapes, segments (1: the tapes hold the whole axis)
+    int fc_cw = 32;                                   // columns per workgroup tile: 32, or 16 for problems of at most 4,096 columns (fc_tile_width)
+    float* d_fc_lam = nullptr;                        // λ handed from one time segment to the one before it
+    float* d_wimg = nullptr;
+    float *d_rt_tape = nullptr, *d_rt_tape2 = nullptr, *d_rt_slab = nullptr, *d_rt_tapez = nullptr;
+    bool rt_fwd32 = false;         // COLNDE_RT_FWD=32 at creation: the 32-column forward kernel (no Z1 tape)
+    bool rt_ztape = false;         // layer-1 pre-activations taped by the forward kernel instead of recomputed by the adjoint
+    int rt_rows = 0;
+    int rt_block = 0;              // columns per pass of the gradient path (multiple of 32): the tapes hold one block at a time
+    int rt_nblocks = 0;
+    float *d_w = nullptr, *d_wf = nullptr, *d_wb = nullptr, *d_x0 = nullptr, *d_bcs = nullptr, *d_truth = nullptr,
+          *d_sol = nullptr, *d_tape = nullptr, *d_slab = nullptr, *d_out = nullptr, *d_times = nullptr,
+          *d_partial = nullptr, *d_tmp_a = nullptr, *d_tmp_b = nullptr, *d_tmp_c = nullptr;
+    size_t tmp_cols = 0;
+    TileDesc* d_tiles = nullptr;
+    // tile16 taped-dW mode (networks whose weight-gradient tiles overflow the register file)
+    int t16_dwtape = -1;            // -1 undecided, 0 off, 1 on
+    float* d_dwtape = nullptr;
+    float* d_t16_ztape = nullptr;   // taped mode: hidden pre-activations written by the forward kernel (the adjoint skips its forward GEMMs)
+    DwMacro* d_macros = nullptr;
+    DwSplitPlan dw_split;                       // the dW GEMM on the bf16 pipe (exact operand splitting), built with the tapes' plan whenever the records fit LDS; used when sp_dw
+    int n_macros = 0, dw_slices = 0, t16_rows = 0;
+    int t16_block = 0, t16_nblocks = 0;   // taped mode: columns per pass (multiple of 16) — the tapes hold one block
+    int *d_bias_zoff = nullptr, *d_bias_goff = nullptr;
+    bool have_problem = false, have_truth = false;
+    bool prof = false;
+    int min_substeps = 1;           // least RK4 sub-steps per save interval inside the diffusive stability bound
+    bool auto_substeps = false;     // cfg.substeps = 0 at creation: the first solve call chooses the sub-step count from cfg.reltol (choose_substeps)
+    float last_estimate = -1.0f;    // ... and the error estimate it settled on
+    unsigned* d_sf = nullptr;       // DevModel::sf / sb: bf16 plane images of the dense chains (networks with rows in global memory, BF16X3_EXACT)
+    unsigned* d_sb = nullptr;
+    float* d_ag = nullptr;          // DevModel::ag: per-tile activation / delta rows in global memory (networks whose rows do not fit the LDS)
+    size_t ag_tiles = 0;            // ... tiles it holds
+    std::vector<float> rkc_host;    // host copy of the RKC2 coefficient table in use (refresh_rkc)
+    bool ag_rows = false;           // the tile16 kernels keep the activation rows in global memory (DevModel::ag)
+    bool substeps_chosen = false;   // the count in use came out of choose_substeps_impl (colnde_describe says so, with the estimate)
+    float* d_rkc = nullptr;         // RKC2 coefficient table (DevModel::rkc)
+    // ensembles (colnde_create_ensemble): n_models models of this configuration in one launch per kernel (blockIdx.y = model)
+    bool ensemble = false;
+    int n_models = 1;
+    std::vector<RtPhys> phys_host;  // per-model closure constants (closure_constants), and their device copy
+    RtPhys* d_phys = nullptr;
+    std::vector<float> phys_raw;    // ... as given: [n_models][5] {nu0, nu_minus, dRi, Ric, Pr} (empty: cfg's constants for every model)
+    MppParams* d_wm_ens_mpp = nullptr;          // colnde_ensemble_wm_embedded: the per-model sweep constants on the device, and what they hold
+    std::vector<MppParams> wm_ens_mpp_host;
+    RtEns ens;                      // per-model strides of the buffers a model owns
+    size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)
+    int ens_rkc_stages = 0;         // RKC2, automatic stage count: the largest any model needs (refresh_rkc)
+    // closure-only model (colnde_create_closure): n_models constant sets of the Pacanowski-Philander closure, no networks (engine_closure.hip)
+    bool closure = false;
+    ClosureModel cm = {};
+    float *d_cl_tape = nullptr, *d_cl_rows = nullptr, *d_cl_params = nullptr;
+    size_t cl_tape_bytes = 0;
+    std::vector<PendingEvent> pending;
+    double ms[K_COUNT] = {};
+    int launches[K_COUNT] = {};
+};
+
+// times the launches of its scope into slot `which` when the handle profiles (colnde_set_profiling)
+struct Timed {
+    colnde_handle* h;
+    PendingEvent p;
+    bool on;
+    Timed(colnde_handle* h_, int which) : h(h_), on(h_->prof) {
+        if (!on) return;
+        p.which = which;
+        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) { on = false; return; }
+        (void)hipEventRecord(p.a, h->stream);
+    }
+    ~Timed() {
+        if (!on) return;
+        (void)hipEventRecord(p.b, h->stream);
+        h->pending.push_back(p);
+        if (h->pending.size() > 2048) drain_events(h);
+    }
+};
+
+// ---- host-array twins: one device scratch per call --------------------------------------------------------
+// A twin declares its arrays in the order they are copied, calls upload(), its _dev form on the device pointers it was given, and download():
+//     HostStage st(h, "label");  st.to(h->d_w, weights, n);  st.in(&d_x, x, nx);  st.out(&d_y, y, ny);
+//     if (st.upload()) return 1;  if (..._dev(h, h->d_w, d_x, d_y)) return 1;  return st.download();
+// One hipMalloc holds every block, each on a 16-byte boundary (what the kernels ask of their arrays).  An array whose host pointer is null takes
+// no room and its device pointer is null.  The first copy that fails leaves "<label>: host-to-device copy failed" / "<label>: device-to-host copy
+// failed"; a failing _dev call keeps its own message.  However the twin returns, the stream is synchronised and the scratch freed.
+class HostStage {
+    struct Block { float *fixed, **d_src, **d_dst; const float* src; float* dst; size_t n, off; };
+    colnde_handle* h_;
+    const char* label_;
+    std::vector<Block> blocks_;
+    size_t total_ = 0;          // floats
+    float* base_ = nullptr;
+
+    void add(float** d_src, float** d_dst, const float* src, float* dst, size_t n) {
+        if (d_src) *d_src = nullptr;
+        if (d_dst) *d_dst = nullptr;
+        if (!src && !dst) return;
+        blocks_.push_back({nullptr, d_src, d_dst, src, dst, n, total_});
+        total_ += (n + 3) / 4 * 4;
+    }
+
+  public:
+    HostStage(colnde_handle* h, const char* label) : h_(h), label_(label) {}
+    HostStage(const HostStage&) = delete;
+    HostStage& operator=(const HostStage&) = delete;
+    ~HostStage() {
+        if (!base_) return;
+        (void)hipStreamSynchronize(h_->stream);
+        (void)hipFree(base_);
+    }
+    // an input that goes to a buffer the handle owns (the weights to h->d_w), in order with the others
+    void to(float* d_dst, const float* src, size_t n) { blocks_.push_back({d_dst, nullptr, nullptr, src, nullptr, n, 0}); }
+    void in(float** d, const float* src, size_t n) { add(d, nullptr, src, nullptr, n); }
+    void out(float** d, float* dst, size_t n) { add(nullptr, d, nullptr, dst, n); }
+    // one block, uploaded from src and downloaded to dst: the call works in place on it.  *d_dst is null without dst (input only).
+    void inout(float** d_src, float** d_dst, const float* src, float* dst, size_t n) { add(d_src, d_dst, src, dst, n); }
+
+    int upload() {
+        HIPCHK(hipMalloc((void**)&base_, total_ * sizeof(float)));
+        bool ok = true;
+        for (const Block& b : blocks_) {
+            float* d = b.fixed ? b.fixed : base_ + b.off;
+            if (b.d_src && b.src) *b.d_src = d;
+            if (b.d_dst && b.dst) *b.d_dst = d;
+            if (ok && b.src) ok = hipMemcpyAsync(d, b.src, b.n * sizeof(float), hipMemcpyHostToDevice, h_->stream) == hipSuccess;
+        }
+        return ok ? 0 : fail("%s: host-to-device copy failed", label_);
+    }
+    int download() {
+        bool ok = true;
+        for (const Block& b : blocks_)
+            if (ok && b.dst) ok = hipMemcpyAsync(b.dst, base_ + b.off, b.n * sizeof(float), hipMemcpyDeviceToHost, h_->stream) == hipSuccess;
+        return ok && hipStreamSynchronize(h_->stream) == hipSuccess ? 0 : fail("%s: device-to-host copy failed", label_);
+    }
+};
+
+#pragma GCC visibility pop
