@@ -1917,6 +1917,9 @@ extern "C" int colnde_pretrain_flux_dev(colnde_handle* h, int flux_type, float* 
     if (h->m.smooth_NN || h->m.smooth_Ri) return fail("flux pre-training does not cover the smoothing options");
     if (h->m.inplace) return fail("flux pre-training uses the training arithmetic (inplace_variant = 0)");
     if (!(beta_t[0] < 1.0 && beta_t[1] < 1.0)) return fail("running powers beta^t must be < 1");
+    if (pretrain_lds_bytes(h->m) > PRETRAIN_LDS_CAP)
+        return fail("network too large for flux pre-training: its one workgroup needs %zu B of LDS for the activations, pre-activations and deltas (> %zu)",
+                    pretrain_lds_bytes(h->m), PRETRAIN_LDS_CAP);
     HIPCHK(hipSetDevice(h->device));
     float* d_loss = nullptr;
     HIPCHK(hipMalloc((void**)&d_loss, sizeof(float) + 2 * sizeof(double) + 8));

@@ -76,7 +76,13 @@ hipError_t launch_reduce(const float* slab, int n_tiles, int n_params, int strid
 hipError_t launch_infer(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* T,
                         const float* top_flux, float inv_dz, float* out, int n_col, int nthreads, size_t lds_bytes,
                         hipStream_t stream);
-// flux-MLP pre-training (train_NN): one pass over the data set, one ADAM update per sample (update = 0: mean-loss evaluation only)
+// flux-MLP pre-training (train_NN): one pass over the data set, one ADAM update per sample (update = 0: mean-loss evaluation only).
+// pretrain_lds_bytes: the dynamic LDS of pretrain_kernel's carving (x, three activation-sized arrays, three face vectors, the reduction
+// slots); launch_pretrain refuses above PRETRAIN_LDS_CAP, and set_kernel_attributes raises the kernel's limit to it.
+#define PRETRAIN_LDS_CAP ((size_t)160 * 1024)
+static inline size_t pretrain_lds_bytes(const DevModel& m) {
+    return (size_t)(((m.ns + 3) & ~3) + 3 * (m.act_total + 4) + 3 * (m.Nz + 4) + 64) * sizeof(float);
+}
 hipError_t launch_pretrain(const DevModel& m, int flux_type, float* theta, float* mom, float* vel, const float* X, const float* BC,
                            const float* Y, const int* order, int n_samples, float gs, float eta, float b1, float b2, float eps,
                            double bt1, double bt2, int update, float* loss_out, double* bt_out, hipStream_t stream);

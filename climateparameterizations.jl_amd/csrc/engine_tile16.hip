@@ -897,8 +897,8 @@ pretrain_kernel(DevModel m, int flux_type, float* __restrict__ theta, float* __r
 hipError_t launch_pretrain(const DevModel& m, int flux_type, float* theta, float* mom, float* vel, const float* X, const float* BC,
                            const float* Y, const int* order, int n_samples, float gs, float eta, float b1, float b2, float eps,
                            double bt1, double bt2, int update, float* loss_out, double* bt_out, hipStream_t stream) {
-    const size_t lds = (size_t)(((m.ns + 3) & ~3) + 3 * (m.act_total + 4) + 3 * (m.Nz + 4) + 64) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = pretrain_lds_bytes(m);
+    if (lds > PRETRAIN_LDS_CAP) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pretrain_kernel, dim3(1), dim3(512), lds, stream, m, flux_type, theta, mom, vel, X, BC, Y, order, n_samples, gs, eta,
                        b1, b2, eps, bt1, bt2, update, loss_out, bt_out);
     return hipGetLastError();
@@ -2247,6 +2247,7 @@ hipError_t set_kernel_attributes(size_t max_lds_bytes) {
     hipError_t e = hipSuccess;
     auto set = [&](auto* k) { if (k && e == hipSuccess) e = set_max_lds(k, max_lds_bytes); };
     set(infer_kernel);
+    set(pretrain_kernel);        // (deep or wide nets: above the 64 KB a kernel may take without the attribute)
     for (int ag = 0; ag < 2; ag++) set(rhs_pick(ag));
     for (int rkc = 0; rkc < 2; rkc++) {
         for (const AdjointInst& a : kGeoms) set(a.k[rkc]);

@@ -258,6 +258,8 @@ class ColumnNDE:
         self._chk_dev(bcs, (n, self.cfg.n_bc))
         self._chk_dev(fluxes, (n, self.cfg.Nz + 1))
         if update:
+            if m is None or v is None:
+                raise ValueError("the ADAM moments m and v are needed when update=True")
             self._chk_dev(m, (self.n_params,))
             self._chk_dev(v, (self.n_params,))
         import torch

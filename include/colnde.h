@@ -389,10 +389,18 @@ int colnde_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_grad
  *   NN_flux = face vector of net `flux_type` (0 = uw, 1 = vw, 2 = wT; T-only models: 2) for the sample's profile and BCs, as the
  *             handle's conditions say (MPP / convective adjustment / zero_weights; the smoothing options are not covered);
  *   loss    = mse(NN_flux, flux) + gradient_scaling * mse(D^c flux, D^c NN_flux).
- * d_theta / d_m / d_v: the handle's full weight vector and its ADAM moments (n_params floats; only the net trained is touched);
- * d_profiles [n][n_state], d_bcs [n][n_bc], d_flux [n][Nz+1] scaled fluxes on faces, d_order [n] sample order (NULL: 0..n-1);
- * beta_t[2]: the optimiser's running powers (host, updated in place).  update = 0: no update, *mean_loss = mean loss at the given
- * weights (`total_loss(training_data)`, :234-236); update != 0: *mean_loss = mean of each sample's loss just before its update.
+ * d_theta / d_m / d_v: the handle's full weight vector and its ADAM moments (n_params floats).  Only the block of the net trained is
+ * read or written, in all three: the blocks of the other nets keep their bits in d_theta, d_m and d_v.
+ * d_profiles [n][n_state], d_bcs [n][n_bc], d_flux [n][Nz+1] scaled fluxes on faces, d_order [n] sample order (NULL: 0..n-1; an index may
+ * repeat: the sample is then visited again, with the weights its earlier visits left);
+ * beta_t[2]: the optimiser's running powers (host, doubles; updated in place, so a pass may be split into several calls that carry d_m,
+ * d_v and beta_t along: same bits as the one call).
+ * update = 0: d_theta is not written, d_m / d_v are not read (either may be NULL), beta_t is not advanced, and *mean_loss = mean loss at
+ * the given weights (`total_loss(training_data)`, :234-236).  update != 0: *mean_loss = mean over the pass of each sample's loss just
+ * BEFORE its own update (the weights as the samples ahead of it in the order left them).
+ * Refused (non-zero, colnde_last_error says why; nothing is written): the smoothing options, inplace_variant, a flux_type other than 2 on a
+ * T-only model, update != 0 without moments, beta_t >= 1, n_samples < 1, ensemble and closure handles, and a network whose activations do
+ * not fit the one workgroup's LDS (the message states the bytes needed).
  * Synchronises the handle's stream. */
 int colnde_pretrain_flux_dev(colnde_handle* h, int flux_type, float* d_theta, float* d_m, float* d_v, const float* d_profiles,
                              const float* d_bcs, const float* d_flux, const int32_t* d_order, int n_samples, float gradient_scaling,
