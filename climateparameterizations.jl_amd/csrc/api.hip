@@ -1509,6 +1509,255 @@ extern "C" int colnde_create_ensemble(const colnde_config* cfg, int n_models, co
 
 extern "C" int colnde_n_models(const colnde_handle* h) { return h ? h->n_models : -1; }
 
+static int ensemble_only(const colnde_handle* h);
+
+// ---- free-convection ensembles (colnde_create_fc_ensemble) ------------------------------------------------------------------------------------------
+// The reference trains the free-convection NDE on 3 to 9 simulations (train_free_convection_nde.jl, --training-simulations): one 16-column workgroup.  Its
+// sweep (one process per seed / optimiser rate / penalty setting) and the judging of a run (compute_nde_solution_history, testing.jl:1-32: the network of
+// EVERY epoch re-solved on every simulation) are both "many networks, same few columns".  Here the 16-column fc32 kernels carry the model index in
+// blockIdx.y (FcEns: the strides of what a model owns), tile16's dW GEMM, the reductions and the ADAM step already do; row k of every result is, bit for
+// bit, what a colnde_create handle computes for model k's weights (under the same COLNDE_FC_SEG: the segment count orders the gradient's sums).
+
+// Decided from the configuration and the environment alone, before any device work
+static int fc_ens_refusals(const colnde_config* cfg, int n_models) {
+    if (n_models < 1 || n_models > 65535) return fail("n_models = %d outside 1..65535", n_models);
+    if (cfg->model == COLNDE_MODEL_WIND_MIXING)
+        return fail("colnde_create_fc_ensemble covers the free-convection models (FreeConvectionNDE, ConvectiveAdjustmentNDE): a wind-mixing ensemble is colnde_create_ensemble's");
+    if (cfg->engine != COLNDE_ENGINE_AUTO && cfg->engine != COLNDE_ENGINE_FC32)
+        return fail("free-convection ensembles run the fc32 kernels (engine AUTO or FC32): engine forced to %d has no model index", cfg->engine);
+    {
+        DevModel dm;
+        PackInfo pk;
+        build_model(cfg, &dm, &pk);
+        if (!fc_supported(dm, cfg->stepper))
+            return fail("free-convection ensembles cover the fc32 shape only: FreeConvectionNDE (RK4) or ConvectiveAdjustmentNDE (RK4, RKC2) with Dense(Nz,4Nz,relu), "
+                        "Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1), Nz = 32 or 64 (Nz = %d, %d layers here); other networks run one handle per model", cfg->Nz, cfg->n_layers);
+    }
+    if (cfg->substeps == 0)
+        return fail("substeps = 0 (chosen from reltol by the first solve) is not supported: the models share one sub-step count, and the tapes are sized at "
+                    "creation — choose it with a single handle (colnde_choose_substeps) and pass it");
+    {
+        const int ms = colnde_min_substeps(cfg);
+        const char* e = getenv("COLNDE_ALLOW_UNSTABLE_DT");
+        if (ms < 0) return 1;
+        if (cfg->substeps < ms && !(e && atoi(e) != 0))
+            return fail("substeps = %d is below colnde_min_substeps = %d: the step leaves the stepper's stability region (lambda = -%.4g; COLNDE_ALLOW_UNSTABLE_DT=1 overrides)",
+                        cfg->substeps, ms, stiff_lambda(cfg));
+    }
+    if (cfg->n_columns > 4096)
+        return fail("%d columns per model: free-convection ensembles cover the 16-column tiles (at most 4,096 columns per model, fc_tile_width); above it the 32-column "
+                    "kernels run one handle per model", cfg->n_columns);
+    // the switches that send a single handle to kernels without a model index
+    {
+        const char* e = getenv("COLNDE_FC");
+        if (e && *e && atoi(e) == 0) return fail("COLNDE_FC=0 sends free convection to the tile16 engine, which has no model index here: free-convection ensembles refuse it");
+        e = getenv("COLNDE_FC_CW");
+        if (e && atoi(e) == 32) return fail("COLNDE_FC_CW=32 selects the 32-column kernels, which have no model index: free-convection ensembles refuse it");
+        if (getenv("COLNDE_FC_BLOCK")) return fail("COLNDE_FC_BLOCK: free-convection ensembles hold one block of columns per model (the column-block loop has no model index)");
+    }
+    return 0;
+}
+
+// The tapes of all K models, planned once at creation by fc_plan_tapes' rules on a per-model budget of (free memory - margin) / K: one block of all columns
+// (column blocks do not occur at <= 4,096 columns), the whole time axis when it fits and time segments otherwise (COLNDE_FC_SEG=<intervals> forces), the
+// slice count a single handle of this size plans.  Refused with the bytes it needs when not even one save interval per segment fits.
+static int fc_ens_plan_tapes(colnde_handle* h) {
+    const DevModel& m = h->m;
+    const size_t K = (size_t)h->n_models;
+    const int n_iv = h->cfg.n_save - 1, cw = h->fc_cw;
+    const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
+    if (R != fc_record_row_floats(m.Nz)) return fail("fc32: record layout mismatch (%zu vs %zu floats per column)", R, fc_record_row_floats(m.Nz));
+    const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE;
+    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0));
+    const int n32 = (h->n_col + 31) / 32 * 32;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t margin = (size_t)3 << 30;
+    const size_t budget = (free_b > margin ? free_b - margin : 0) / K;
+    // what a model owns beside the tapes: λ between segments and the slab rows ([tile][segment] + [segment][<= 512 slices] rows of n_params + 8 floats)
+    auto rest_bytes = [&](int sg) {
+        const size_t nsg = ((size_t)n_iv + sg - 1) / sg;
+        return ((size_t)(n32 / cw) + 512) * nsg * P8 * sizeof(float) + (size_t)n32 * m.Nz * sizeof(float);
+    };
+    int seg = n_iv;
+    while (seg > 1 && per_col_iv * (size_t)n32 * seg + rest_bytes(seg) > budget) seg--;
+    const char* es = getenv("COLNDE_FC_SEG");
+    if (es && atoi(es) >= 1) seg = std::min(n_iv, atoi(es));
+    const size_t need = per_col_iv * (size_t)n32 * seg + rest_bytes(seg);
+    if (need > budget)
+        return fail("a free-convection ensemble of %d models needs %zu bytes of device memory for its tapes and slab rows (%zu per model with %d save interval(s) per "
+                    "time segment, %d substeps x %d stages); %zu bytes are free (3 GB kept in reserve): use fewer models per handle",
+                    h->n_models, K * need, need, seg, h->cfg.substeps, m.nst, free_b);
+    h->fc_block = n32;
+    h->fc_nblocks = 1;
+    h->fc_seg = seg;
+    h->fc_nseg = (n_iv + seg - 1) / seg;
+    const size_t tiles_b = (size_t)n32 / cw;
+    const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;
+    const size_t n_rec = tiles_b * (cw / 16) * stage_recs;
+    std::vector<DwMacro> mac;
+    build_dw_macros(h, n_rec, mac);                          // the slice count a single handle of this size plans: same reduction order
+    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw_slices;
+    FcEns& en = h->fens;
+    en.dwtape = n_rec * CT * R;
+    en.masks = tiles_b * stage_recs * fc_mask_words();
+    en.swtape = ca ? tiles_b * stage_recs * fc_switch_words(cw) : 0;
+    en.lam = (size_t)n32 * m.Nz;
+    en.slab = (size_t)h->fc_rows * P8;
+    hipError_t e = hipMalloc((void**)&h->d_dwtape, K * en.dwtape * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_fc_masks, K * en.masks * sizeof(unsigned int));
+    if (e == hipSuccess && ca) e = hipMalloc((void**)&h->d_fc_switch, K * en.swtape * sizeof(unsigned long long));
+    if (e == hipSuccess && h->fc_nseg > 1) e = hipMalloc((void**)&h->d_fc_lam, K * en.lam * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_macros, mac.size() * sizeof(DwMacro));
+    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_slab, K * en.slab * sizeof(float));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("allocating the free-convection ensemble's tapes (%zu bytes, %zu per model) failed: %s", K * need, need, hipGetErrorString(e));
+    }
+    h->ens.slab = en.slab;
+    h->ens_model_bytes = (en.dwtape + en.slab + (h->fc_nseg > 1 ? en.lam : 0)) * sizeof(float) + en.masks * sizeof(unsigned int) + en.swtape * sizeof(unsigned long long);
+    return 0;
+}
+
+extern "C" int colnde_create_fc_ensemble(const colnde_config* cfg, int n_models, colnde_handle** out) {
+    if (!out) return fail("null out pointer");
+    *out = nullptr;
+    if (validate(cfg)) return 1;
+    if (fc_ens_refusals(cfg, n_models)) return 1;
+    colnde_handle* h = nullptr;
+    if (colnde_create(cfg, &h)) return 1;
+    if (!h->use_fc || h->fc_cw != 16 || !fc_split_supported(16)) {
+        colnde_destroy(h);
+        return fail("this configuration does not run the 16-column fc32 kernels: free-convection ensembles refuse it");
+    }
+    h->ensemble = true;
+    h->n_models = n_models;
+    const size_t K = (size_t)n_models, P = (size_t)h->m.n_params;
+    const int Nz = h->m.Nz;
+    FcEns& en = h->fens;
+    en.n_models = n_models;
+    en.w = P;
+    en.img = fc_image_floats(Nz);
+    en.simg = fc_split_image_words(Nz);
+    en.bias = (fc_bias_floats(Nz) + 3) / 4 * 4;
+    en.sol = (size_t)h->n_col * h->cfg.n_save * h->m.ns;
+    h->ens.sol = en.sol;
+    h->ens.n_models = n_models;
+    auto realloc_ = [&](void** p, size_t bytes) {
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+        if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return true;
+    };
+    if (!realloc_((void**)&h->d_w, K * P * sizeof(float)) || !realloc_((void**)&h->d_out, K * (P + 8) * sizeof(float)) ||
+        !realloc_((void**)&h->d_partial, K * 256 * 8 * sizeof(float)) || !realloc_((void**)&h->d_sol, K * en.sol * sizeof(float)) ||
+        !realloc_((void**)&h->d_fc_imgf, K * en.img * sizeof(float)) || !realloc_((void**)&h->d_fc_imgb, K * en.img * sizeof(float)) ||
+        !realloc_((void**)&h->d_fc_bias, K * en.bias * sizeof(float)) || !realloc_((void**)&h->d_fc_simgf, K * en.simg * sizeof(unsigned int)) ||
+        !realloc_((void**)&h->d_fc_simgb, K * en.simg * sizeof(unsigned int))) {
+        colnde_destroy(h);
+        return fail("allocating the free-convection ensemble's per-model buffers (%d models) failed", n_models);
+    }
+    if (fc_ens_plan_tapes(h)) { colnde_destroy(h); return 1; }
+    h->ens_model_bytes += (2 * en.img + en.bias + en.sol) * sizeof(float) + 2 * en.simg * sizeof(unsigned int);
+    *out = h;
+    return 0;
+}
+
+static int fc_ens_pack(colnde_handle* h, const float* d_weights) {
+    hipError_t e = fc_launch_pack(h->m, h->fc_cw, d_weights, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_simgf, h->d_fc_simgb, h->stream, &h->fens);
+    if (e != hipSuccess) return fail("fc32 ensemble pack launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// all models over the save intervals [iv0, iv1): from the shared x0 (iv0 = 0) or from every model's own saved state at save point iv0
+static int fc_ens_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int iv0, int iv1, int tape_iv0) {
+    const size_t ns = h->m.ns;
+    FcEns en = h->fens;
+    en.x0 = iv0 == 0 ? 0 : en.sol;
+    const float* init = iv0 == 0 ? h->d_x0 : d_sol + (size_t)iv0 * ns;
+    const size_t stride = iv0 == 0 ? ns : (size_t)h->cfg.n_save * ns;
+    Timed tm(h, K_FORWARD);
+    hipError_t e = fc_launch_forward(h->m, h->fc_cw, h->d_fc_imgf, h->sp_fwd ? h->d_fc_simgf : nullptr, h->d_fc_bias, init, stride, h->d_bcs, h->d_times, h->cfg.n_save,
+                                     iv0, iv1, tape_iv0, h->cfg.substeps, d_sol, with_tape ? h->d_dwtape : nullptr, with_tape ? h->d_fc_masks : nullptr,
+                                     with_tape ? h->d_fc_switch : nullptr, h->n_col, h->stream, &en);
+    if (e != hipSuccess) return fail("fc32 ensemble forward launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+static int fc_ens_forward(colnde_handle* h, const float* d_weights, float* d_sol) {
+    if (fc_ens_pack(h, d_weights)) return 1;
+    return fc_ens_forward_range(h, d_sol, false, 0, h->cfg.n_save - 1, 0);
+}
+
+// colnde_loss_grad_dev's fc32 branch for all K models: the same launches in the same order, each once for every model; the models march through the
+// time segments together (the tape-less pass first, then segment by segment from the end), λ carried per model.
+static int fc_ens_loss_grad(colnde_handle* h, const float* d_weights, const LossWeights& lw, float* d_out) {
+    if (!h->have_problem) return fail("colnde_set_problem has not been called");
+    if (check_stability(h)) return 1;
+    const int K = h->n_models, stride = h->m.n_params + 8, cw = h->fc_cw;
+    const FcEns& en = h->fens;
+    if (fc_ens_pack(h, d_weights)) return 1;
+    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * en.slab * sizeof(float), h->stream));
+    const int n_wg = (h->n_col + cw - 1) / cw, n_iv = h->cfg.n_save - 1, nseg = h->fc_nseg;
+    const size_t gemm_rows0 = (size_t)n_wg * nseg;                          // a model's slab: [segment][tile] adjoint rows, then [segment][slice] GEMM rows
+    const size_t tiles_b = (size_t)n_wg;
+    hipError_t e;
+    if (nseg > 1 && fc_ens_forward_range(h, h->d_sol, true, 0, n_iv, (nseg - 1) * h->fc_seg)) return 1;
+    for (int sg = nseg - 1; sg >= 0; sg--) {
+        const int iv0 = sg * h->fc_seg, iv1 = std::min(n_iv, iv0 + h->fc_seg);
+        if (!(nseg > 1 && sg == nseg - 1) && fc_ens_forward_range(h, h->d_sol, true, iv0, iv1, iv0)) return 1;
+        {
+            Timed tm(h, K_ADJOINT);
+            e = fc_launch_adjoint(h->m, cw, h->d_fc_imgb, h->sp_adj ? h->d_fc_simgb : nullptr, h->d_times, h->cfg.n_save, iv0, iv1, h->cfg.substeps, h->d_sol, h->d_truth,
+                                  h->d_dwtape, h->d_fc_masks, h->d_fc_switch, lw.w[2], nseg > 1 ? h->d_fc_lam : nullptr, h->d_slab + (size_t)sg * n_wg * stride,
+                                  h->n_col, h->stream, &en);
+            if (e != hipSuccess) return fail("fc32 ensemble adjoint launch failed: %s", hipGetErrorString(e));
+        }
+        {
+            Timed tm(h, K_DW1);
+            const size_t n_rec = tiles_b * (cw / 16) * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst;
+            float* rows = h->d_slab + (gemm_rows0 + (size_t)sg * h->dw_slices) * stride;
+            e = (h->sp_dw && !h->dw_split.passes.empty())
+                ? launch_dw_gemm_split(h->d_dwtape, n_rec, (int)dwtape_row_floats(h->m), h->dw_split, h->dw_slices, rows, stride, h->stream, K, en.dwtape, en.slab)
+                : launch_dw_gemm(h->d_dwtape, n_rec, (int)dwtape_row_floats(h->m), h->d_macros, h->n_macros, h->dw_slices, rows, stride, h->stream, K, en.dwtape, en.slab);
+            if (e != hipSuccess) return fail("ensemble dW GEMM launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    {
+        Timed tm(h, K_REDUCE);
+        e = launch_reduce(h->d_slab, h->fc_rows, h->m.n_params, stride, lw, d_out, h->stream, K, en.slab, stride);
+        if (e != hipSuccess) return fail("ensemble reduce launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+static int fc_ensemble_only(const colnde_handle* h, const char* fn) {
+    if (ensemble_only(h)) return 1;
+    if (!h->use_fc) return fail("%s takes the handles of colnde_create_fc_ensemble: this ensemble holds wind-mixing models", fn);
+    return 0;
+}
+
+extern "C" int colnde_ensemble_column_loss_dev(colnde_handle* h, const float* d_sol, float* d_out) {
+    if (fc_ensemble_only(h, __func__)) return 1;
+    if (!d_sol || !d_out) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    HIPCHK(hipSetDevice(h->device));
+    Timed tm(h, K_REDUCE);
+    hipError_t e = launch_column_loss(d_sol, h->d_truth, h->m.Nz, (long)h->n_col * h->cfg.n_save, h->n_models, d_out, h->stream);
+    if (e != hipSuccess) return fail("column loss launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_causal_penalty_dev(colnde_handle* h, const float* d_weights, const float* d_coeff, float* d_result) {
+    if (fc_ensemble_only(h, __func__)) return 1;
+    if (!d_weights || !d_coeff || !d_result) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    Timed tm(h, K_REDUCE);
+    hipError_t e = launch_causal_penalty(d_weights, d_coeff, d_result, h->m.Nz, h->m.w_off[0], h->m.n_params, h->n_models, h->stream);
+    if (e != hipSuccess) return fail("causal penalty launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
 static int ensemble_only(const colnde_handle* h) {
     if (!h) return fail("null handle");
     if (h->closure) return fail("colnde_ensemble_* take weight vectors, but this is a closure handle (no networks): use colnde_closure_* (include/colnde.h)");
@@ -1518,6 +1767,8 @@ static int ensemble_only(const colnde_handle* h) {
 
 extern "C" int colnde_ensemble_set_physics(colnde_handle* h, const float* physics) {
     if (ensemble_only(h)) return 1;
+    if (h->use_fc)
+        return fail("colnde_ensemble_set_physics: a free-convection ensemble has no closure constants to vary (its models differ in their weights and ADAM rates only)");
     if (!physics) return fail("null physics array");
     if (!h->cfg.modified_pacanowski_philander)
         return fail("a physics array needs modified_pacanowski_philander = 1: without the Richardson-number closure the five constants are unused");
@@ -1536,6 +1787,7 @@ extern "C" int colnde_ensemble_set_physics(colnde_handle* h, const float* physic
 static int ens_forward(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape) {
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
     if (check_stability(h)) return 1;
+    if (h->use_fc) return fc_ens_forward(h, d_weights, d_sol);
     RtEns ens = h->ens;
     ens.sol = (size_t)h->n_col * h->cfg.n_save * h->m.ns;
     Timed tm(h, K_FORWARD);
@@ -1578,6 +1830,7 @@ extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_we
     const int K = h->n_models, stride = h->m.n_params + 8;
     LossWeights lw;
     loss_weights(h, scalings, &lw);
+    if (h->use_fc) return fc_ens_loss_grad(h, d_weights, lw, d_out);
     HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->ens.slab * sizeof(float), h->stream));
     if (ens_forward(h, d_weights, h->d_sol, true)) return 1;
     hipError_t e;

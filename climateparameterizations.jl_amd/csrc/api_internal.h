@@ -126,6 +126,7 @@ struct colnde_handle {
     MppParams* d_wm_ens_mpp = nullptr;          // colnde_ensemble_wm_embedded: the per-model sweep constants on the device, and what they hold
     std::vector<MppParams> wm_ens_mpp_host;
     RtEns ens;                      // per-model strides of the buffers a model owns
+    FcEns fens;                     // ... of a free-convection ensemble (colnde_create_fc_ensemble): the fc32 kernels' strides
     size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)
     int ens_rkc_stages = 0;         // RKC2, automatic stage count: the largest any model needs (refresh_rkc)
     // closure-only model (colnde_create_closure): n_models constant sets of the Pacanowski-Philander closure, no networks (engine_closure.hip)

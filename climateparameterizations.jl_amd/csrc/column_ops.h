@@ -31,3 +31,8 @@ hipError_t launch_loss_per_tstep(const float* sol, const float* truth, int n_col
 // out[0] = max over the n_rows rows of rms_i((a_i - b_i) / (floor + |b_i|)) over the `row` floats of a row (+inf if any entry is not finite);
 // partial: scratch of >= 1024 floats
 hipError_t launch_rel_diff_max(const float* a, const float* b, long n_rows, int row, float floor, float* partial, float* out, hipStream_t stream);
+// Free-convection ensembles.  out[k][c][n] = mean over Nz (32 | 64) levels of (sol[k][c][n][:] - truth[c][n][:])^2; rows_per_model = n_col * n_save
+hipError_t launch_column_loss(const float* sol, const float* truth, int Nz, long rows_per_model, int n_models, float* out, hipStream_t stream);
+// result[k][n_params + 6] += coeff[k] * sum_{r < q} W1_k[r, q]^2, result[k][index of W1[r, q]] += 2 coeff[k] W1_k[r, q] (W1: 4 Nz x Nz at w1_off,
+// column-major); w [K][n_params], result [K][n_params + 8]; coeff[k] = 0 leaves row k untouched
+hipError_t launch_causal_penalty(const float* w, const float* coeff, float* result, int Nz, int w1_off, int n_params, int n_models, hipStream_t stream);

@@ -544,3 +544,74 @@ hipError_t launch_rel_diff_max(const float* a, const float* b, long n_rows, int 
     hipLaunchKernelGGL(rel_diff_finish_kernel, dim3(1), dim3(64), 0, stream, partial, blocks, out);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// Free-convection ensembles (colnde_create_fc_ensemble): judging K networks on the same simulations.
+// ------------------------------------------------------------------------------------------------
+// out[k][c][n] = mean over the Nz levels of (sol[k][c][n][:] - truth[c][n][:])^2 — Flux.mse(true, nde, agg = x -> mean(x, dims=1)) of
+// free_convection/src/testing.jl:83 for every model, simulation and save point.  A lane per level, NZ lanes per row (two rows per wavefront at
+// Nz = 32); the sum is a shuffle tree over the row's lanes, always in the same order: two launches give the same bits.  Bandwidth-bound: sol is read once.
+template <int NZ>
+__global__ void __launch_bounds__(256) column_loss_kernel(const float* __restrict__ sol, const float* __restrict__ truth, long rows_per_model, long n_rows,
+                                                          float* __restrict__ out) {
+    const int lvl = threadIdx.x & (NZ - 1);
+    const long row = (long)blockIdx.x * (256 / NZ) + threadIdx.x / NZ;           // (model, simulation, save point)
+    float v = 0.0f;
+    if (row < n_rows) {
+        const float d = sol[row * NZ + lvl] - truth[(row % rows_per_model) * NZ + lvl];
+        v = d * d;
+    }
+#pragma unroll
+    for (int off = NZ / 2; off > 0; off >>= 1) v += __shfl_down(v, off, NZ);
+    if (lvl == 0 && row < n_rows) out[row] = v * (1.0f / (float)NZ);
+}
+
+hipError_t launch_column_loss(const float* sol, const float* truth, int Nz, long rows_per_model, int n_models, float* out, hipStream_t stream) {
+    if ((Nz != 32 && Nz != 64) || rows_per_model < 1 || n_models < 1) return hipErrorInvalidValue;
+    const long n_rows = rows_per_model * n_models, per_block = 256 / Nz, blocks = (n_rows + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+    if (Nz == 64) hipLaunchKernelGGL((column_loss_kernel<64>), dim3((unsigned)blocks), dim3(256), 0, stream, sol, truth, rows_per_model, n_rows, out);
+    else hipLaunchKernelGGL((column_loss_kernel<32>), dim3((unsigned)blocks), dim3(256), 0, stream, sol, truth, rows_per_model, n_rows, out);
+    return hipGetLastError();
+}
+
+// The soft spatial-causality penalty of train_free_convection_nde.jl:186-197 for every model: c_k sum_{r < q} W1_k[r, q]^2 over the strict upper triangle of
+// the first Dense weight (4 Nz x Nz, W1[r, q] at w1_off + q * 4 Nz + r: Flux.destructure's column-major order), added to the total of the model's result
+// row, and its gradient 2 c_k W1_k[r, q] added to the row's gradient entries.  One workgroup per model; thread t owns the masked entries e = t, t + 256, ...
+// of the triangle's column-by-column enumeration and the partial sums meet in a fixed tree, so the value is bit-reproducible.  c_k = 0: the row is not
+// touched at all (not even rewritten).  Plain vector loads and stores; every entry has one owner, so nothing is atomic.
+__global__ void __launch_bounds__(256) causal_penalty_kernel(const float* __restrict__ w, const float* __restrict__ coeff, float* __restrict__ result,
+                                                             int Nz, int w1_off, int n_params) {
+    __shared__ float part[256];
+    const size_t k = blockIdx.x;
+    const float c = coeff[k];
+    if (c == 0.0f) return;                                           // (uniform over the workgroup)
+    const float* W = w + k * (size_t)n_params + w1_off;
+    float* row = result + k * ((size_t)n_params + 8);
+    const int H = 4 * Nz, n_mask = Nz * (Nz - 1) / 2;
+    float s = 0.0f;
+    for (int e = threadIdx.x; e < n_mask; e += 256) {
+        // column q holds the q entries r = 0 .. q - 1; entries of columns < q: q (q - 1) / 2
+        int q = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)e)) * 0.5f);
+        while (q * (q - 1) / 2 > e) q--;
+        while ((q + 1) * q / 2 <= e) q++;
+        const int r = e - q * (q - 1) / 2;
+        const int idx = q * H + r;
+        const float v = W[idx];
+        s += v * v;
+        row[w1_off + idx] += 2.0f * c * v;
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) row[n_params + 6] += c * part[0];
+}
+
+hipError_t launch_causal_penalty(const float* w, const float* coeff, float* result, int Nz, int w1_off, int n_params, int n_models, hipStream_t stream) {
+    if (Nz < 2 || n_models < 1 || w1_off < 0 || w1_off + 4 * Nz * Nz > n_params) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(causal_penalty_kernel, dim3(n_models), dim3(256), 0, stream, w, coeff, result, Nz, w1_off, n_params);
+    return hipGetLastError();
+}

@@ -19,8 +19,16 @@ int fc_tile_width(int n_col);
 // SPLIT instantiations of engine_fc.hip's; the two orders differ, the size does not)
 size_t fc_split_image_words(int Nz);
 bool fc_split_supported(int cw);
+// Ensembles (colnde_create_fc_ensemble): K networks of the shape on the SAME columns, the model index in blockIdx.y of the 16-column kernels.  What a
+// model owns lies at a fixed stride from model 0's, in elements of the array's type; x0 is 0 (the shared initial state) or `sol` (a time segment
+// restarting from the model's own saved state).  x0 at iv_begin = 0, bcs, truth, the save times and the RKC2 table are shared.  Passed by value.
+struct FcEns {
+    size_t w = 0, img = 0, simg = 0, bias = 0, x0 = 0, sol = 0, dwtape = 0, masks = 0, swtape = 0, lam = 0, slab = 0;
+    int n_models = 1;
+};
+// ens != null (cw = 16, both image kinds given): the images of all ens->n_models models, weights ens->w floats apart
 hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf, float* imgb, float* bias, unsigned int* simgf, unsigned int* simgb,
-                          hipStream_t stream);
+                          hipStream_t stream, const FcEns* ens = nullptr);
 // Save intervals [iv_begin, iv_end) from x0 (column stride x0_stride floats).  dwtape == nullptr: plain forward solve.  Otherwise, from interval
 // tape_iv0 on (iv_begin <= tape_iv0 < iv_end; records numbered from its first step), the stage inputs
 // and hidden activations go into the records [tile32][step of this launch][stage][cw/16 records of 16 columns][R], the relu bits into masks [..][512] and
@@ -28,13 +36,13 @@ hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf
 // simgf != null (and cw == 32): the split kernels (v_mfma_f32_32x32x16_bf16 on exact three-way operand splits) instead of the f32-MFMA ones
 hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const unsigned int* simgf, const float* bias, const float* x0, size_t x0_stride,
                              const float* bcs, const float* save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps, float* sol,
-                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream);
+                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens = nullptr);
 // slab: one row of n_params + 8 floats per tile (bias gradients and the squared-error sum; the weight gradients are the dW GEMM's).
 // lam_io [columns padded to 32][Nz]: carries λ between the time segments of a segmented gradient pass (null when one launch covers the axis).
 hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const unsigned int* simgb, const float* save_times, int n_save, int iv_begin, int iv_end,
                              int substeps,
                              const float* sol, const float* truth, float* dwtape, const unsigned int* masks, const unsigned long long* swtape,
-                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream);
+                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens = nullptr);
 // compute_neural_network_forcing! (double_gyre_nn.jl:149-168): T [n_col][Nz] model units, top_flux [n_col], out = -dz(wT) on cell centres
 hipError_t fc_launch_infer(const DevModel& m, int cw, const float* imgf, const float* bias, const float* T, const float* top_flux, float inv_dz,
                            float* out, int n_col, hipStream_t stream);

@@ -160,10 +160,18 @@ struct FcStream {
 // ------------------------------------------------------------------------------------------------
 struct FcOffsets { int w[3], b[3]; };
 
-template <int NZ, int CW>
+// ENS (ensembles, 16-column tiles): blockIdx.y = model; the model's weights and images lie en.w / en.img / en.bias floats from model 0's.
+template <int NZ, int CW, bool ENS = false>
 __global__ void __launch_bounds__(256) fc_pack_kernel(FcOffsets o, const float* __restrict__ w, float* __restrict__ imgf, float* __restrict__ imgb,
-                                                      float* __restrict__ bias) {
+                                                      float* __restrict__ bias, FcEns en) {
     using S = Fc<NZ, CW>;
+    if constexpr (ENS) {
+        const size_t k = blockIdx.y;
+        w += k * en.w;
+        imgf += k * en.img;
+        imgb += k * en.img;
+        bias += k * en.bias;
+    }
     const int total = 2 * S::IMG + S::BIAS;
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
         if (idx >= 2 * S::IMG) {
@@ -202,9 +210,16 @@ __global__ void __launch_bounds__(256) fc_pack_kernel(FcOffsets o, const float* 
 // three bf16 (x = h + m + l by truncation: split_bf16.h), laid out as each WAVE streams them — image[section][wave][k-block][job][plane][lane][8 bf16]:
 // lane (m = lane % 16, kq = lane / 16), element i <-> k = 32 kb + 8 kq + i of row 16 (wave + 4 job) + m (sections 0, 1); section 2: row tile
 // wave % MT3, k-blocks (wave / MT3) KB3 + g.
-template <int NZ>
-__global__ void __launch_bounds__(256) fc_pack_split16_kernel(FcOffsets o, const float* __restrict__ w, u32* __restrict__ simgf, u32* __restrict__ simgb) {
+template <int NZ, bool ENS = false>
+__global__ void __launch_bounds__(256) fc_pack_split16_kernel(FcOffsets o, const float* __restrict__ w, u32* __restrict__ simgf, u32* __restrict__ simgb,
+                                                              FcEns en) {
     using S = Fc<NZ, 16>;
+    if constexpr (ENS) {
+        const size_t k = blockIdx.y;
+        w += k * en.w;
+        simgf += k * en.simg;
+        simgb += k * en.simg;
+    }
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < 2 * S::SIMG; idx += gridDim.x * 256) {
         const bool fwd = idx < S::SIMG;
         const int e = fwd ? idx : idx - S::SIMG;
@@ -255,12 +270,29 @@ __global__ void __launch_bounds__(256) fc_pack_split16_kernel(FcOffsets o, const
 // ------------------------------------------------------------------------------------------------
 typedef unsigned long long u64;
 
-template <int NZ, int CW, bool TAPE, bool CA, bool RKC, bool SPLIT = false>
+//   ENS: an ensemble (colnde_create_fc_ensemble; 16-column tiles) — blockIdx.y = model.  What a model owns (operand image, biases, solution, the three
+//        tapes; x0 when it is a saved state of the model's own solution) is offset ONCE, here in the prologue, by the strides of `en`: scalar arithmetic on
+//        kernel arguments, no vector load is added before the stage loop.  The single-handle instantiations (ENS = false) never read `en`.
+template <int NZ, int CW, bool TAPE, bool CA, bool RKC, bool SPLIT = false, bool ENS = false>
 __global__ void __launch_bounds__(256, 2)
 fc_forward_kernel(const void* __restrict__ imgf, const float* __restrict__ bias, const float* __restrict__ x0, size_t x0_stride,
                   const float* __restrict__ bcs, const float* __restrict__ save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps, float CN,
                   float caKN, int nst, const float* __restrict__ rkc, float* __restrict__ sol, float* __restrict__ dwtape, u32* __restrict__ masks,
-                  u64* __restrict__ swtape, int n_col) {
+                  u64* __restrict__ swtape, int n_col, FcEns en) {
+    static_assert(!ENS || CW == 16, "ensembles run the 16-column tiles");
+    if constexpr (ENS) {
+        const size_t k = blockIdx.y;
+        if constexpr (SPLIT) imgf = reinterpret_cast<const u32*>(imgf) + k * en.simg;
+        else imgf = reinterpret_cast<const float*>(imgf) + k * en.img;
+        bias += k * en.bias;
+        x0 += k * en.x0;
+        if (sol) sol += k * en.sol;
+        if constexpr (TAPE) {
+            dwtape += k * en.dwtape;
+            masks += k * en.masks;
+            if constexpr (CA) swtape += k * en.swtape;
+        }
+    }
     // Save intervals [iv_begin, iv_end) of the time axis, starting from x0 (column stride x0_stride: the initial state, or — a time SEGMENT
     // of the gradient path — the state the tape-less pass saved at save point iv_begin; restarting there is exact: the saved state IS xn).
     // Only the intervals from tape_iv0 on are taped (the records are numbered from its first step): the tape-less pass of a time-segmented
@@ -527,12 +559,25 @@ fc_infer_kernel(const float* __restrict__ imgf, const float* __restrict__ bias, 
 // ------------------------------------------------------------------------------------------------
 struct FcGrad { int b[3]; int n_params; };
 
-template <int NZ, int CW, bool CA, bool RKC, bool SPLIT = false>
+// ENS: as in fc_forward_kernel — blockIdx.y = model; image, solution, tapes, λ hand-over and slab rows are the model's own, the truth is shared.
+template <int NZ, int CW, bool CA, bool RKC, bool SPLIT = false, bool ENS = false>
 __global__ void __launch_bounds__(256, 2)
 fc_adjoint_kernel(const void* __restrict__ imgb, const float* __restrict__ save_times, int n_save, int iv_begin, int iv_end, int substeps, float CN,
                   float caKN, int nst, const float* __restrict__ rkc, const float* __restrict__ sol, const float* __restrict__ truth,
                   float* __restrict__ dwtape, const u32* __restrict__ masks, const u64* __restrict__ swtape, float w_loss, float* __restrict__ lam_io,
-                  float* __restrict__ slab, FcGrad go, int n_col) {
+                  float* __restrict__ slab, FcGrad go, int n_col, FcEns en) {
+    static_assert(!ENS || CW == 16, "ensembles run the 16-column tiles");
+    if constexpr (ENS) {
+        const size_t k = blockIdx.y;
+        if constexpr (SPLIT) imgb = reinterpret_cast<const u32*>(imgb) + k * en.simg;
+        else imgb = reinterpret_cast<const float*>(imgb) + k * en.img;
+        sol += k * en.sol;
+        dwtape += k * en.dwtape;
+        masks += k * en.masks;
+        if constexpr (CA) swtape += k * en.swtape;
+        if (lam_io) lam_io += k * en.lam;
+        slab += k * en.slab;
+    }
     // Save intervals [iv_begin, iv_end), backwards.  lam_io [columns][NZ] (or null: one launch covers the axis) carries λ from one time
     // segment to the one before it: read unless this is the last segment of the axis, written unless it is the first.
     using S = Fc<NZ, CW>;
@@ -803,6 +848,17 @@ hipError_t fc_set_kernel_attributes() {
     FC_FOR_EACH_ADJ16(FC_ATTR_AS)
 #undef FC_ATTR_FS
 #undef FC_ATTR_AS
+    // ... and the ensemble instantiations of the 16-column kernels, both arithmetics
+#define FC_ATTR_FE(N, W, T, C, K)                                                                                                                                        \
+    if ((e = hipFuncSetAttribute((const void*)(fc_forward_kernel<N, W, T, C, K, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_fwd<N, W>())) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)(fc_forward_kernel<N, W, T, C, K, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_fwd<N, W>())) != hipSuccess) return e;
+#define FC_ATTR_AE(N, W, C, K)                                                                                                                                           \
+    if ((e = hipFuncSetAttribute((const void*)(fc_adjoint_kernel<N, W, C, K, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_adj<N, W>())) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)(fc_adjoint_kernel<N, W, C, K, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_adj<N, W>())) != hipSuccess) return e;
+    FC_FOR_EACH_FWD16(FC_ATTR_FE)
+    FC_FOR_EACH_ADJ16(FC_ATTR_AE)
+#undef FC_ATTR_FE
+#undef FC_ATTR_AE
 #undef FC_ATTR_F
 #undef FC_ATTR_A
 #undef FC_ATTR_I
@@ -817,18 +873,30 @@ int fc_tile_width(int n_col) {
 }
 
 hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf, float* imgb, float* bias, unsigned int* simgf, unsigned int* simgb,
-                          hipStream_t stream) {
+                          hipStream_t stream, const FcEns* ens) {
     FcOffsets o;
     for (int l = 0; l < 3; l++) { o.w[l] = m.w_off[l]; o.b[l] = m.b_off[l]; }
+    if (ens) {                                             // every model's images in one launch each (16-column tiles only)
+        if (cw != 16 || ens->n_models < 1 || ens->n_models > 65535 || !simgf || !simgb) return hipErrorInvalidValue;
+        const unsigned K = (unsigned)ens->n_models;
+        if (m.Nz == 64) {
+            hipLaunchKernelGGL((fc_pack_split16_kernel<64, true>), dim3(256, K), dim3(256), 0, stream, o, w, simgf, simgb, *ens);
+            hipLaunchKernelGGL((fc_pack_kernel<64, 16, true>), dim3(256, K), dim3(256), 0, stream, o, w, imgf, imgb, bias, *ens);
+        } else {
+            hipLaunchKernelGGL((fc_pack_split16_kernel<32, true>), dim3(128, K), dim3(256), 0, stream, o, w, simgf, simgb, *ens);
+            hipLaunchKernelGGL((fc_pack_kernel<32, 16, true>), dim3(128, K), dim3(256), 0, stream, o, w, imgf, imgb, bias, *ens);
+        }
+        return hipGetLastError();
+    }
     if (simgf && simgb && cw == 32) {                      // the split images of COLNDE_MATRIX_BF16X3_EXACT beside the f32 ones (the biases are shared)
         const hipError_t es = fcs_launch_pack(m, w, simgf, simgb, stream);
         if (es != hipSuccess) return es;
     } else if (simgf && simgb && cw == 16) {               // ... in the 16-column kernels' stream order (same size)
-        if (m.Nz == 64) hipLaunchKernelGGL((fc_pack_split16_kernel<64>), dim3(256), dim3(256), 0, stream, o, w, simgf, simgb);
-        else hipLaunchKernelGGL((fc_pack_split16_kernel<32>), dim3(128), dim3(256), 0, stream, o, w, simgf, simgb);
+        if (m.Nz == 64) hipLaunchKernelGGL((fc_pack_split16_kernel<64>), dim3(256), dim3(256), 0, stream, o, w, simgf, simgb, FcEns());
+        else hipLaunchKernelGGL((fc_pack_split16_kernel<32>), dim3(128), dim3(256), 0, stream, o, w, simgf, simgb, FcEns());
     }
     bool launched = false;
-#define FC_PACK(N, W, X) if (!launched && m.Nz == N && cw == W) { hipLaunchKernelGGL((fc_pack_kernel<N, W>), dim3(N == 64 ? 256 : 128), dim3(256), 0, stream, o, w, imgf, imgb, bias); launched = true; }
+#define FC_PACK(N, W, X) if (!launched && m.Nz == N && cw == W) { hipLaunchKernelGGL((fc_pack_kernel<N, W>), dim3(N == 64 ? 256 : 128), dim3(256), 0, stream, o, w, imgf, imgb, bias, FcEns()); launched = true; }
     FC_FOR_EACH_SHAPE(FC_PACK, 0)
 #undef FC_PACK
     return launched ? hipGetLastError() : hipErrorInvalidValue;
@@ -848,8 +916,29 @@ hipError_t fc_launch_infer(const DevModel& m, int cw, const float* imgf, const f
 
 hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const unsigned int* simgf, const float* bias, const float* x0, size_t x0_stride,
                              const float* bcs, const float* save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps, float* sol,
-                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream) {
+                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens) {
     if (n_col < 1 || iv_begin < 0 || iv_end > n_save - 1 || iv_begin >= iv_end || tape_iv0 < iv_begin || tape_iv0 >= iv_end) return hipErrorInvalidValue;
+    if (ens) {                                              // all models in one launch: the ENS instantiations of the 16-column kernels, grid.y = model
+        if (cw != 16 || ens->n_models < 1 || ens->n_models > 65535) return hipErrorInvalidValue;
+        const dim3 grid((n_col + 15) / 16, ens->n_models), block(256);
+        const float CN = m.C_fc * (float)m.Nz, caKN = m.ca_K * (float)m.Nz;
+        const bool tape = dwtape != nullptr, ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE, rk = m.rkc != nullptr, split = simgf != nullptr;
+        if ((tape && (!masks || (ca && !swtape))) || (rk && !ca)) return hipErrorInvalidValue;
+        bool launched = false;
+#define FC_FWDE(N, W, T, C, K)                                                                                                                       \
+    if (!launched && m.Nz == N && tape == T && ca == C && rk == K) {                                                                                 \
+        if (split)                                                                                                                                   \
+            hipLaunchKernelGGL((fc_forward_kernel<N, W, T, C, K, true, true>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)simgf, bias, x0, x0_stride, bcs,    \
+                               save_times, n_save, iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, *ens); \
+        else                                                                                                                                         \
+            hipLaunchKernelGGL((fc_forward_kernel<N, W, T, C, K, false, true>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)imgf, bias, x0, x0_stride, bcs,    \
+                               save_times, n_save, iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, *ens); \
+        launched = true;                                                                                                                             \
+    }
+        FC_FOR_EACH_FWD16(FC_FWDE)
+#undef FC_FWDE
+        return launched ? hipGetLastError() : hipErrorInvalidValue;
+    }
     if (simgf && cw == 32) {                                // COLNDE_MATRIX_BF16X3_EXACT: the same solve on the bf16 pipe (engine_fc_split.hip)
         if (dwtape && (!masks || (m.model == COLNDE_MODEL_CONV_ADJ_NDE && !swtape))) return hipErrorInvalidValue;
         if (m.rkc && m.model != COLNDE_MODEL_CONV_ADJ_NDE) return hipErrorInvalidValue;
@@ -865,7 +954,7 @@ hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const
 #define FC_FWDS(N, W, T, C, K)                                                                                                                       \
     if (!launched && m.Nz == N && tape == T && ca == C && rk == K) {                                                                                 \
         hipLaunchKernelGGL((fc_forward_kernel<N, W, T, C, K, true>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)simgf, bias, x0, x0_stride, bcs, save_times, n_save, \
-                           iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col);                         \
+                           iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, FcEns());                \
         launched = true;                                                                                                                             \
     }
         FC_FOR_EACH_FWD16(FC_FWDS)
@@ -875,7 +964,7 @@ hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const
 #define FC_FWD(N, W, T, C, K)                                                                                                                        \
     if (!launched && m.Nz == N && cw == W && tape == T && ca == C && rk == K) {                                                                      \
         hipLaunchKernelGGL((fc_forward_kernel<N, W, T, C, K>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)imgf, bias, x0, x0_stride, bcs, save_times, n_save, \
-                           iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col);                         \
+                           iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, FcEns());                \
         launched = true;                                                                                                                             \
     }
     FC_FOR_EACH_FWD(FC_FWD)
@@ -885,9 +974,33 @@ hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const
 
 hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const unsigned int* simgb, const float* save_times, int n_save, int iv_begin, int iv_end,
                              int substeps, const float* sol, const float* truth, float* dwtape, const unsigned int* masks, const unsigned long long* swtape,
-                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream) {
+                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens) {
     if (n_col < 1 || !dwtape || !masks || iv_begin < 0 || iv_end > n_save - 1 || iv_begin >= iv_end) return hipErrorInvalidValue;
     if ((iv_begin > 0 || iv_end < n_save - 1) && !lam_io) return hipErrorInvalidValue;
+    if (ens) {
+        if (cw != 16 || ens->n_models < 1 || ens->n_models > 65535) return hipErrorInvalidValue;
+        const dim3 grid((n_col + 15) / 16, ens->n_models), block(256);
+        const float CN = m.C_fc * (float)m.Nz, caKN = m.ca_K * (float)m.Nz;
+        const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE, rk = m.rkc != nullptr, split = simgb != nullptr;
+        if ((ca && !swtape) || (rk && !ca)) return hipErrorInvalidValue;
+        FcGrad go;
+        for (int l = 0; l < 3; l++) go.b[l] = m.b_off[l];
+        go.n_params = m.n_params;
+        bool launched = false;
+#define FC_ADJE(N, W, C, K)                                                                                                                          \
+    if (!launched && m.Nz == N && ca == C && rk == K) {                                                                                              \
+        if (split)                                                                                                                                   \
+            hipLaunchKernelGGL((fc_adjoint_kernel<N, W, C, K, true, true>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)simgb, save_times, n_save, iv_begin,  \
+                               iv_end, substeps, CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, *ens); \
+        else                                                                                                                                         \
+            hipLaunchKernelGGL((fc_adjoint_kernel<N, W, C, K, false, true>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)imgb, save_times, n_save, iv_begin,  \
+                               iv_end, substeps, CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, *ens); \
+        launched = true;                                                                                                                             \
+    }
+        FC_FOR_EACH_ADJ16(FC_ADJE)
+#undef FC_ADJE
+        return launched ? hipGetLastError() : hipErrorInvalidValue;
+    }
     if (simgb && cw == 32) {
         if ((m.model == COLNDE_MODEL_CONV_ADJ_NDE && !swtape) || (m.rkc && m.model != COLNDE_MODEL_CONV_ADJ_NDE)) return hipErrorInvalidValue;
         return fcs_launch_adjoint(m, simgb, save_times, n_save, iv_begin, iv_end, substeps, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, n_col, stream);
@@ -904,7 +1017,7 @@ hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const
 #define FC_ADJS(N, W, C, K)                                                                                                                          \
     if (!launched && m.Nz == N && ca == C && rk == K) {                                                                                              \
         hipLaunchKernelGGL((fc_adjoint_kernel<N, W, C, K, true>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)simgb, save_times, n_save, iv_begin, iv_end, substeps, \
-                           CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col);                              \
+                           CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, FcEns());                     \
         launched = true;                                                                                                                             \
     }
         FC_FOR_EACH_ADJ16(FC_ADJS)
@@ -914,7 +1027,7 @@ hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const
 #define FC_ADJ(N, W, C, K)                                                                                                                           \
     if (!launched && m.Nz == N && cw == W && ca == C && rk == K) {                                                                                   \
         hipLaunchKernelGGL((fc_adjoint_kernel<N, W, C, K>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)imgb, save_times, n_save, iv_begin, iv_end, substeps, \
-                           CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col);                              \
+                           CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, FcEns());                     \
         launched = true;                                                                                                                             \
     }
     FC_FOR_EACH_ADJ(FC_ADJ)

@@ -13,7 +13,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .config import MATRIX_ARITHMETIC_NAMES, NDEConfig, matrix_arithmetic_id, to_c_config
+from .config import CONVECTIVE_ADJUSTMENT_NDE, FREE_CONVECTION, MATRIX_ARITHMETIC_NAMES, NDEConfig, matrix_arithmetic_id, to_c_config
 
 KERNEL_IDS = {"forward": 0, "adjoint": 1, "reduce": 2, "rhs": 3, "infer": 4, "dw1": 5, "convadj": 6, "adam": 7, "impldiff": 8, "fc_embed": 9, "flux_diag": 10}
 ENGINE_AUTO, ENGINE_TILE16, ENGINE_REGTILE, ENGINE_FC32 = 0, 1, 2, 3
@@ -1006,6 +1006,87 @@ class ColumnNDEEnsemble(ColumnNDE):
 
 
 CLOSURE_N_PARAMS = 5
+
+
+FC_ENSEMBLE_MAX_COLUMNS = 4096      # the size up to which a single handle runs 16-column tiles (fc_tile_width)
+
+
+def check_fc_ensemble_arrays(cfg: NDEConfig, n_columns: int, n_models: int, weights=None, etas=None, coeff=None, sol=None, result=None):
+    """Shape rules of `FreeConvectionEnsemble` (no GPU needed), raised before any library call: a free-convection config of the fc32 shape
+    Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1) with Nz = 32 or 64, 1 <= n_columns <= 4096, n_models >= 1; weights [K, n_params],
+    etas and coeff [K], sol [K, n_columns, n_save, Nz], result [K, n_params + 8]."""
+    if cfg.model not in (FREE_CONVECTION, CONVECTIVE_ADJUSTMENT_NDE):
+        raise ValueError("FreeConvectionEnsemble needs a free-convection config (FreeConvectionNDE or ConvectiveAdjustmentNDE); wind mixing: ColumnNDEEnsemble")
+    Nz = cfg.Nz
+    if Nz not in (32, 64) or tuple(cfg.layer_sizes) != (Nz, 4 * Nz, 4 * Nz, Nz - 1) or tuple(cfg.activations) != ("relu", "relu", "identity"):
+        raise ValueError("FreeConvectionEnsemble covers Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1) with Nz = 32 or 64; got Nz = %d, layers %s, "
+                         "activations %s" % (Nz, tuple(cfg.layer_sizes), tuple(cfg.activations)))
+    if not 1 <= int(n_columns) <= FC_ENSEMBLE_MAX_COLUMNS:
+        raise ValueError("n_columns = %d outside 1..%d (the 16-column tiles)" % (int(n_columns), FC_ENSEMBLE_MAX_COLUMNS))
+    K = int(n_models)
+    check_ensemble_arrays(K, cfg.n_params, weights=weights, etas=etas)
+    for name, a, shape in (("coeff", coeff, (K,)), ("sol", sol, (K, int(n_columns), cfg.n_save, Nz)), ("result", result, (K, cfg.n_params + 8))):
+        if a is not None and tuple(a.shape) != shape:
+            raise ValueError("%s: expected shape %s for %d models, got %s" % (name, shape, K, tuple(a.shape)))
+
+
+class FreeConvectionEnsemble(ColumnNDEEnsemble):
+    """K free-convection networks of the fc32 shape on the same simulations (`colnde_create_fc_ensemble`): the sweep of
+    free_convection/train_free_convection_nde.jl (one process per seed / optimiser rate / penalty setting there) and the judging of a training run
+    (free_convection/src/testing.jl: the network of every epoch on every simulation), every kernel launched once for all K.  `forward`, `loss`,
+    `loss_grad` and `adam_step` are `ColumnNDEEnsemble`'s, with its NumPy / torch rules; row k holds the bits a `ColumnNDE` handle computes for
+    model k's weights.  There are no constants to vary: `set_physics` and `wm_embedded` are refused."""
+
+    def __init__(self, cfg: NDEConfig, n_columns: int, n_models: int, device: int = 0, engine: int = 0, matrix_arithmetic="bf16x3_exact"):
+        cfg.validate()
+        check_fc_ensemble_arrays(cfg, n_columns, n_models)
+        self.cfg = cfg
+        self.n_columns = int(n_columns)
+        self.n_models = int(n_models)
+        self.device = int(device)
+        self._h = ctypes.c_void_p()
+        L = _lib.lib()
+        c, keep = to_c_config(cfg, n_columns, device, engine, matrix_arithmetic)
+        _lib.check(L.colnde_create_fc_ensemble(ctypes.byref(c), self.n_models, ctypes.byref(self._h)))
+        self._L = L
+        self.n_params = L.colnde_n_params(self._h)
+        assert self.n_params == cfg.n_params and L.colnde_n_models(self._h) == self.n_models
+        self.n_columns_total = self.n_columns
+        self.engine = L.colnde_engine(self._h)
+
+    def column_loss(self, sol):
+        """[K, n_columns, n_save]: the mean over the levels of (sol - truth)^2 per model, simulation and save point, scaled units —
+        `Flux.mse(true, nde, agg = x -> mean(x, dims=1))` (testing.jl:83).  sol: `forward`'s output (torch on the device, or NumPy)."""
+        import torch
+        check_fc_ensemble_arrays(self.cfg, self.n_columns, self.n_models, sol=sol)
+        is_t = _is_torch(sol)
+        s = sol if is_t else torch.from_numpy(_f32(sol)).to(torch.device("cuda", self.device))
+        self._chk_dev(s, tuple(sol.shape))
+        out = torch.empty(tuple(sol.shape[:3]), dtype=torch.float32, device=s.device)
+        self.use_torch_stream()
+        _lib.check(self._L.colnde_ensemble_column_loss_dev(self._h, s.data_ptr(), out.data_ptr()))
+        return out if is_t else out.cpu().numpy()
+
+    def causal_penalty(self, weights, coeff, result):
+        """The soft spatial-causality penalty (train_free_convection_nde.jl:186-197) added to `result` [K, n_params + 8] (loss_grad's buffer):
+        total += c_k sum_{r<q} W1_k[r, q]^2, gradient += 2 c_k W1_k[r, q]; coeff [K].  Torch device tensors are updated in place; NumPy arrays
+        are copied to the device and the updated result is returned."""
+        import torch
+        check_fc_ensemble_arrays(self.cfg, self.n_columns, self.n_models, weights=weights, coeff=coeff, result=result)
+        if _is_torch(result):
+            for t, shape in ((weights, (self.n_models, self.n_params)), (coeff, (self.n_models,)), (result, (self.n_models, self.n_params + 8))):
+                self._chk_dev(t, shape)
+            self.use_torch_stream()
+            _lib.check(self._L.colnde_ensemble_causal_penalty_dev(self._h, weights.data_ptr(), coeff.data_ptr(), result.data_ptr()))
+            return result
+        dev = torch.device("cuda", self.device)
+        w, c, r = (torch.from_numpy(_f32(a)).to(dev) for a in (weights, coeff, result))
+        self.use_torch_stream()
+        _lib.check(self._L.colnde_ensemble_causal_penalty_dev(self._h, w.data_ptr(), c.data_ptr(), r.data_ptr()))
+        return r.cpu().numpy()
+
+    def set_physics(self, physics):
+        _lib.check(self._L.colnde_ensemble_set_physics(self._h, _ptr(_f32(np.asarray(physics)))))
 
 
 def check_closure_arrays(n_sets: int, params=None, out=None):

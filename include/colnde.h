@@ -486,6 +486,33 @@ int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const floa
 int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_result, float* d_m, float* d_v, const float* d_eta,
                                   float beta1, float beta2, float eps, float beta1_t, float beta2_t);
 
+/* ---- free-convection ensembles: K networks of the fc32 shape on the same simulations ---------------------------------------------------------------
+ * The reference trains the free-convection NDE on 3 to 9 simulations (free_convection/train_free_convection_nde.jl, --training-simulations), sweeps that
+ * driver over seeds, optimiser rates and `--spatial_causality soft`, and judges a run by re-solving the network of EVERY epoch on every simulation
+ * (compute_nde_solution_history, free_convection/src/testing.jl:1-32).  A free-convection ensemble handle holds K networks Dense(Nz,4Nz,relu),
+ * Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1), Nz = 32 or 64, of FreeConvectionNDE (RK4) or ConvectiveAdjustmentNDE (RK4, RKC2) on the same columns; the 16-column
+ * fc32 kernels carry the model index in the launch grid.  Shared: x0, the [bottom, top] fluxes, truth, the save times, the sub-step count, the RKC2 table.
+ * Owned by a model: operand images, biases, solution, tapes, lambda between time segments, slab rows.
+ * It is accepted by colnde_ensemble_forward_dev, _loss_dev, _loss_grad_dev, _loss_grad and _adam_step_dev with their layouts ([K][n_params] weights,
+ * [K][n_params + 8] result rows), and by the handle-level calls a wind-mixing ensemble accepts (describe adds models=K, the bytes per model and
+ * time_segments).  Row k of every result holds the bits a colnde_create handle computes for model k's weights, under either matrix arithmetic (and the same
+ * COLNDE_FC_SEG: the segment count orders the gradient's sums).  colnde_ensemble_set_physics (no constants to vary), colnde_ensemble_wm_embedded and every
+ * single-model call refuse it.
+ * Refused at creation, before any device work, each with its reason: a wind-mixing model, another network shape or Nz, an engine other than AUTO or FC32,
+ * substeps = 0, substeps < colnde_min_substeps, n_models outside 1..65535, more than 4,096 columns per model (above it a single handle runs 32-column
+ * tiles), COLNDE_FC=0, COLNDE_FC_CW=32, COLNDE_FC_BLOCK.  Then "no HIP device ... no CPU fallback", and tapes that do not fit, with the bytes needed: all K
+ * models' tapes are planned here on a per-model budget of (free memory - 3 GB) / K, the whole time axis when it fits, time segments otherwise. */
+int colnde_create_fc_ensemble(const colnde_config* cfg, int n_models, colnde_handle** out);
+/* out[k][c][n] = mean over the Nz levels of (sol[k][c][n][:] - truth[c][n][:])^2, scaled units:
+ * Flux.mse(true, nde, agg = x -> mean(x, dims=1)) of testing.jl:83 for every model and simulation (plot_epoch_loss, animate_nde_loss: testing.jl:34-105).
+ * d_sol: [K][n_col][n_save][Nz], the layout of colnde_ensemble_forward_dev.  Fixed-order sums: bit-reproducible. */
+int colnde_ensemble_column_loss_dev(colnde_handle* h, const float* d_sol, float* d_out /* [K][n_col][n_save] */);
+/* result[k][n_params + 6] += c_k * sum_{r < q} W1_k[r, q]^2 ;  result[k][index of W1[r, q]] += 2 c_k W1_k[r, q]
+ * W1 = the first Dense weight (4Nz x Nz, column-major as Flux.destructure lays it out), r < q the mask of
+ * train_free_convection_nde.jl:193; c_k = 1 is the reference's penalty, 0 leaves row k's bits alone.
+ * d_result: the buffer of colnde_ensemble_loss_grad_dev, updated in place. */
+int colnde_ensemble_causal_penalty_dev(colnde_handle* h, const float* d_weights, const float* d_coeff /* [K] */, float* d_result);
+
 /* All K models of an ensemble in the embedding ocean column at once — one iteration of progress_neural_network (wind_mixing/src/NDE_oceananigans.jl:380-405) and / or
  * the saved-state diagnoses diagnose_NN_flux_uw / _vw / _wT (:226-286) for every model, each on its OWN column state with its own weights and its own constants: how
  * NDE_profile_oceananigans / solve_oceananigans_modified_pacanowski_philander_nn judge the members of a sweep.  One launch for all K.

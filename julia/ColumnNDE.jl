@@ -526,6 +526,32 @@ function ensemble_adam_step!(h::Handle, dθ::Ptr{Float32}, dresult::Ptr{Float32}
     βᵗ .* β
 end
 
+# ---- free-convection ensembles: K networks of the fc32 shape on the same simulations — the sweep of free_convection/train_free_convection_nde.jl
+# (seed, optimiser rate, --spatial_causality soft) and the judging of a run (free_convection/src/testing.jl: the network of every epoch re-solved)
+
+"K networks Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1) (Nz = 32 | 64) of FreeConvectionNDE / ConvectiveAdjustmentNDE on the same columns;
+accepted by the `ensemble_*` calls above (row k = the bits a single handle computes for model k), refused by `set_physics!` and the single-model calls"
+function FreeConvectionEnsembleHandle(cfg::Config, save_times::Vector{Float32}, n_models::Integer)
+    cfg.n_save = length(save_times)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve save_times begin
+        cfg.save_times = pointer(save_times)
+        check(ccall((:colnde_create_fc_ensemble, libcolnde), Cint, (Ref{Config}, Cint, Ref{Ptr{Cvoid}}), cfg, n_models, out))
+    end
+    h = Handle(out[], ccall((:colnde_n_params, libcolnde), Cint, (Ptr{Cvoid},), out[]), cfg.Nz, cfg.n_save, cfg.n_columns, 1)
+    finalizer(x -> ccall((:colnde_destroy, libcolnde), Cvoid, (Ptr{Cvoid},), x.ptr), h)
+end
+
+"dout[n, c, k] = mean over the levels of (sol - truth)² per save point n, simulation c and model k, scaled units: Flux.mse(true, nde, agg = x -> mean(x, dims=1))
+of testing.jl:83 (plot_epoch_loss, animate_nde_loss); dsol is `ensemble_forward_dev!`'s output.  Device pointers, handle's stream."
+ensemble_column_loss_dev!(h::Handle, dsol::Ptr{Float32}, dout::Ptr{Float32}) =
+    check(ccall((:colnde_ensemble_column_loss_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, dsol, dout))
+
+"the soft spatial-causality penalty of train_free_convection_nde.jl:186-197 added in place to the loss-gradient result: total += cₖ sum(abs2, W1ₖ[mask]),
+gradient += 2 cₖ W1ₖ[mask]; dcoeff one coefficient per model (1: the reference's penalty, 0: row k untouched).  Device pointers, handle's stream."
+ensemble_causal_penalty_dev!(h::Handle, dθ::Ptr{Float32}, dcoeff::Ptr{Float32}, dresult::Ptr{Float32}) =
+    check(ccall((:colnde_ensemble_causal_penalty_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, dcoeff, dresult))
+
 # ---- the closure without networks: fitting (ν₀, ν₋, ΔRi, Riᶜ, Pr) — wind_mixing/src/diffusivity_parameter_optimisation.jl (DE :1-33,
 # optimise_modified_pacanowski_philander :35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl and ..._args.jl)
 
