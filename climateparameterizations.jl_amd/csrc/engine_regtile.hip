@@ -607,9 +607,31 @@ __device__ __forceinline__ void rt_act_pair(float z, float& a, float& d) {
     }
 }
 
+// The SCALAR twin of rt_act4's packed mish form (rt_act4<ACT, false>): four values side by side, each through exactly the operations the packed
+// form compiles to — v_fma_f32 where the shipped ISA has v_pk_fma_f32 (q = e (e + 2) + 2, beside the separately rounded n = e (e + 2)), separately
+// rounded v_mul_f32 / v_add_f32 where it has v_pk_mul_f32 / v_pk_add_f32 — so the results are the same bits (tools/probe/pk_beside_mfma.hip,
+// tests/test_gpu_regtile_bits.py).  Contraction is off in here: the one fused operation is spelled out, nothing else may fuse.
+__device__ __forceinline__ f32x4v rt_mish4_scalar(f32x4v z) {
+#pragma clang fp contract(off)
+    float e[4], s[4], n[4], r[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) e[i] = __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(z[i], -3.0e38f, 20.0f) * 1.4426950408889634f);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        s[i] = e[i] + 2.0f;
+        n[i] = e[i] * s[i];
+        r[i] = __builtin_amdgcn_rcpf(fmaf(e[i], s[i], 2.0f));
+    }
+    return (f32x4v){z[0] * (n[0] * r[0]), z[1] * (n[1] * r[1]), z[2] * (n[2] * r[2]), z[3] * (n[3] * r[3])};
+}
+
 // Two activation value/derivative pairs at once on packed f32 arithmetic (v_pk_mul / v_pk_add / v_pk_fma: two lanes' worth of the same
-// instruction per issue slot).  With one wave per SIMD every vector instruction of these phases is exposed, and scalar v_fma runs the
-// vector unit at half its rate: 13 packed + 6 scalar (clamp, exp, rcp) instructions for two pairs instead of 34.
+// instruction per issue slot): 13 packed + 6 scalar (clamp, exp, rcp) instructions for two pairs instead of 34.  That pays where the wave has the
+// SIMD's vector issue to itself — the adjoint (one wave per SIMD), whose pairs sit in vector-only phases or are a small part of what its W1^T
+// products overlap (scalar twins measured there: neutral under the products, +1.5 ms in the vector-only phases) — and alone on a SIMD the packed
+// sequence is the faster one (59 against 83 ticks per pair).  It does NOT hold beside another wave's MFMAs: there a packed instruction waits far
+// longer for issue than the two scalar ones it replaces (452 against 141 ticks per pair beside v_mfma_f32_16x16x32_bf16:
+// tools/probe/pk_beside_mfma.hip), which is why the two-waves-per-SIMD forward kernel on bf16 MFMAs uses rt_mish4_scalar.
 template <int ACT>
 __device__ __forceinline__ void rt_act_pair2(f32x2v z, f32x2v& a, f32x2v& d) {
     if (ACT == COLNDE_ACT_MISH) {
@@ -638,8 +660,9 @@ __device__ __forceinline__ void rt_act_pair2(f32x2v z, f32x2v& a, f32x2v& d) {
 }
 
 // activation VALUE only (forward kernels), four elements on packed arithmetic
-template <int ACT>
+template <int ACT, bool PK = true>
 __device__ __forceinline__ f32x4v rt_act4(f32x4v z) {
+    if (ACT == COLNDE_ACT_MISH && !PK) return rt_mish4_scalar(z);
     if (ACT == COLNDE_ACT_MISH) {
         f32x2v z0 = {z[0], z[1]}, z1 = {z[2], z[3]}, c0, c1, e0, e1, r0, r1;
         c0.x = __builtin_amdgcn_fmed3f(z0.x, -3.0e38f, 20.0f); c0.y = __builtin_amdgcn_fmed3f(z0.y, -3.0e38f, 20.0f);
@@ -1793,7 +1816,7 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                                     *reinterpret_cast<f32x4v*>(oz) = A1[tt];
                                     *reinterpret_cast<f32x4v*>(oz + RT_TAPEZ_HALF) = (f32x4v){d0.x, d0.y, d1.x, d1.y};
                                 } else
-                                A1[tt] = rt_act4<ACT>(A1[tt]);
+                                A1[tt] = rt_act4<ACT, false>(A1[tt]);       // scalar f32: this filler issues beside the partner wave's bf16 MFMAs (see rt_mish4_scalar)
 #pragma unroll
                                 for (int r = 0; r < 4; r++) asm volatile("" : "+v"(A1[tt][r]));
                             };
@@ -1901,7 +1924,9 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                                 if (Q2 < 5) oz[(3 * n + (Q2 >> 1)) * 256 + ((2 * Q2) & 3)] = acc[r];
                             }
                         }
-                        A2[u] = rt_act4<ACT>(acc);
+                        // (SPLIT: the four values of tile 0 on scalar f32, as layer 1; tile 1 has ONE live value, which the compiler evaluates on scalar instructions from
+                        //  either form — its packed source form is kept, because there the split below contracts its residual onto the last product, and the bits hang on it)
+                        A2[u] = SPLIT && u == 0 ? rt_act4<ACT, false>(acc) : rt_act4<ACT>(acc);
                     }
                     Bf3 GB;
                     if constexpr (SPLIT) {
@@ -1935,9 +1960,29 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                         Ud = shift_down16(Xs[0], lane, 0.0f); Vd = shift_down16(Xs[1], lane, 0.0f); Td = shift_down16(Xs[2], lane, 0.0f);
                     }
                     if (m.mpp) {
-                        // the Richardson-number closure on pairs of adjacent levels (packed f32 arithmetic: two levels per issue slot);
-                        // uniform factors folded (see rt_physics_vjp): d = level difference, a = σ (Nz d + ε), Ri = B (Nz d_T + ε) / S2,
-                        // tanh via exp2, ν = nB + nA tanh, diffusive flux = -(c Nz) ν d
+                        // the Richardson-number closure; uniform factors folded (see rt_physics_vjp): d = level difference, a = σ (Nz d + ε),
+                        // Ri = B (Nz d_T + ε) / S2, tanh via exp2, ν = nB + nA tanh, diffusive flux = -(c Nz) ν d.  On f32 MFMAs: pairs of adjacent levels
+                        // on packed f32 arithmetic (two levels per issue slot).  On bf16 MFMAs (SPLIT): the same operations level by level on scalar f32
+                        // — v_fma_f32 where the packed form compiles to v_pk_fma_f32, contraction off so that nothing else fuses: the same bits — because
+                        // beside the partner wave's bf16 MFMAs the packed instructions are the dearer ones
+                        if constexpr (SPLIT) {
+#pragma unroll
+                            for (int tau = 0; tau < 2; tau++)
+#pragma unroll
+                                for (int r = 0; r < 4; r++) {
+#pragma clang fp contract(off)
+                                    const float dU = Xs[0].t[tau][r] - Ud.t[tau][r], dV = Xs[1].t[tau][r] - Vd.t[tau][r], dT = Xs[2].t[tau][r] - Td.t[tau][r];
+                                    const float a1 = fmaf(dU, pc.cU, pc.sU), a2 = fmaf(dV, pc.cV, pc.sV);
+                                    const float rS = __builtin_amdgcn_rcpf(fmaf(a1, a1, a2 * a2));        // (the shipped packed form: v_pk_mul a2 a2, then v_pk_fma a1 a1)
+                                    const float arg = fmaf(fmaf(dT, pc.cB, pc.sB) * rS, pc.kE, pc.oE);
+                                    const float e = __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(arg, -pc.cE, pc.cE));
+                                    const float rc = __builtin_amdgcn_rcpf(e + 1.0f);
+                                    const float nu = fmaf(fmaf(rc, -2.0f, 1.0f), pc.nA, pc.nB);
+                                    F[0].t[tau][r] = fmaf(nu * dU, pc.f0, O[0].t[tau][r]);
+                                    F[1].t[tau][r] = fmaf(nu * dV, pc.f1, O[1].t[tau][r]);
+                                    F[2].t[tau][r] = fmaf(nu * dT, pc.f2, O[2].t[tau][r]);
+                                }
+                        } else
 #pragma unroll
                         for (int tau = 0; tau < 2; tau++)
 #pragma unroll
