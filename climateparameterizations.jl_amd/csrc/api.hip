@@ -522,14 +522,17 @@ extern "C" void colnde_destroy(colnde_handle* h) {
     void* ptrs[] = {h->d_rt_tapez, h->d_rt_tape, h->d_rt_tape2, h->d_rt_slab, h->d_wimg, h->d_w, h->d_wf, h->d_wb, h->d_x0, h->d_bcs, h->d_truth, h->d_sol, h->d_tape, h->d_slab, h->d_out,
                     h->d_times, h->d_partial, h->d_tmp_a, h->d_tmp_b, h->d_tmp_c, h->d_tiles, h->d_bias_zoff, h->d_bias_goff, h->d_dwtape, h->d_macros, h->d_t16_ztape, h->d_rkc, h->d_ag, h->d_sf, h->d_sb,
                     h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_masks, h->d_fc_switch, h->d_fc_lam, h->d_fc_simgf, h->d_fc_simgb, h->d_phys, h->d_wm_ens_mpp,
-                    h->d_cl_tape, h->d_cl_rows, h->d_cl_params};
+                    h->d_cl_tape, h->d_cl_rows, h->d_cl_params, h->conv.d_wpad, h->conv.d_gpad, h->conv.d_ctape, h->conv.d_cslab};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     dw_split_free(h->dw_split);
     delete h;
 }
 
-extern "C" int colnde_n_params(const colnde_handle* h) { return h ? h->m.n_params : -1; }
+// parameters of the vector the caller passes: the model's, except behind a conv filter (the handle's internal vector pads W1)
+static int user_params(const colnde_handle* h) { return h->conv.c ? h->conv.n_params : h->m.n_params; }
+extern "C" int colnde_n_params(const colnde_handle* h) { return h ? user_params(h) : -1; }
+extern "C" int colnde_conv_filter(const colnde_handle* h) { return h ? h->conv.c : -1; }
 extern "C" int colnde_engine(const colnde_handle* h) { return h ? (h->use_rt ? COLNDE_ENGINE_MFMA : (h->use_fc ? COLNDE_ENGINE_FC32 : COLNDE_ENGINE_GENERIC)) : -1; }
 
 extern "C" int colnde_set_stream(colnde_handle* h, void* s) {
@@ -550,6 +553,7 @@ extern "C" int colnde_matrix_arithmetic(const colnde_handle* h) { return h ? h->
 
 extern "C" int colnde_set_global_columns(colnde_handle* h, int64_t n) {
     if (!(h && h->closure)) SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (n < h->n_col) return fail("global column count %lld < local %d", (long long)n, h->n_col);
     h->n_col_total = n;
@@ -631,6 +635,7 @@ static void loss_weights(const colnde_handle* h, const float scalings[6], LossWe
 extern "C" int colnde_rhs_dev(colnde_handle* h, const float* d_x, const float* d_weights, const float* d_bcs, float t,
                               float* d_dx, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_x || !d_weights || !d_bcs || !d_dx) return fail("null pointer argument");
     if (n_columns < 1) return fail("n_columns must be >= 1");
@@ -658,6 +663,7 @@ int ensure_tmp(colnde_handle* h, size_t n_columns) {
 extern "C" int colnde_rhs(colnde_handle* h, const float* x, const float* weights, const float* bcs, float t, float* dx,
                           int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (!x || !weights || !bcs || !dx) return fail("null pointer argument");
     if (n_columns < 1) return fail("n_columns must be >= 1");
@@ -764,8 +770,29 @@ static int t16_forward_range(colnde_handle* h, const float* d_weights, float* d_
 
 // fc32 forward solve of columns [c0, c0 + nc) (c0 a multiple of 32) over the save intervals [iv0, iv1); with_tape: into the handle's records and
 // bits.  iv0 > 0 restarts from the state a previous (tape-less) pass saved in d_sol at save point iv0 — exact: the saved state is the stepper's.
+// The conv handle's kernels take the filter from the head of the user's vector and the conv tape from the handle
+static FcConv fc_conv_args(const colnde_handle* h) {
+    FcConv cv;
+    cv.c = h->conv.c;
+    cv.wb = h->conv.d_user;
+    cv.ctape = h->conv.d_ctape;
+    return cv;
+}
+
+// The vector the fc32 engine packs: the caller's, or — behind a conv filter — its dense part with W1 padded to 4Nz x Nz (one small kernel on the stream)
+static int fc_engine_weights(colnde_handle* h, const float* d_weights, const float** d_engine) {
+    *d_engine = d_weights;
+    if (!h->conv.c) return 0;
+    h->conv.d_user = d_weights;
+    hipError_t e = launch_fc_conv_pad(d_weights, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->m.n_params, h->conv.d_wpad, h->stream);
+    if (e != hipSuccess) return fail("conv weight padding launch failed: %s", hipGetErrorString(e));
+    *d_engine = h->conv.d_wpad;
+    return 0;
+}
+
 static int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int nc, int iv0 = 0, int iv1 = -1, int tape_iv0 = -1) {
     const size_t ns = h->m.ns;
+    const FcConv cv = fc_conv_args(h);
     if (iv1 < 0) iv1 = h->cfg.n_save - 1;
     if (tape_iv0 < 0) tape_iv0 = iv0;                // (a later tape_iv0: the tape-less pass of a segmented gradient tapes its last segment on the way)
     const float* init = iv0 == 0 ? h->d_x0 + (size_t)c0 * ns : d_sol + ((size_t)c0 * h->cfg.n_save + iv0) * ns;
@@ -774,7 +801,7 @@ static int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int 
     hipError_t e = fc_launch_forward(h->m, h->fc_cw, h->d_fc_imgf, (h->sp_fwd && fc_split_supported(h->fc_cw)) ? h->d_fc_simgf : nullptr, h->d_fc_bias, init, stride, h->d_bcs + (size_t)c0 * h->m.n_bc, h->d_times, h->cfg.n_save,
                                      iv0, iv1, tape_iv0, h->cfg.substeps, d_sol ? d_sol + (size_t)c0 * h->cfg.n_save * ns : nullptr,
                                      with_tape ? h->d_dwtape : nullptr, with_tape ? h->d_fc_masks : nullptr, with_tape ? h->d_fc_switch : nullptr, nc,
-                                     h->stream);
+                                     h->stream, nullptr, h->conv.c ? &cv : nullptr);
     if (e != hipSuccess) return fail("fc32 forward launch failed: %s", hipGetErrorString(e));
     return 0;
 }
@@ -822,7 +849,9 @@ static int forward_impl(colnde_handle* h, const float* d_weights, float* d_sol, 
         return rt_forward_range(h, d_sol, false, 0, h->n_col);
     }
     if (h->use_fc) {
-        hipError_t e = fc_launch_pack(h->m, h->fc_cw, d_weights, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_simgf, h->d_fc_simgb, h->stream);
+        const float* d_we = nullptr;
+        if (fc_engine_weights(h, d_weights, &d_we)) return 1;
+        hipError_t e = fc_launch_pack(h->m, h->fc_cw, d_we, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_simgf, h->d_fc_simgb, h->stream);
         if (e != hipSuccess) return fail("fc32 pack launch failed: %s", hipGetErrorString(e));
         return fc_forward_range(h, d_sol, false, 0, h->n_col);
     }
@@ -844,7 +873,7 @@ extern "C" int colnde_forward(colnde_handle* h, const float* weights, float* sol
     if (!h) return fail("null handle");
     if (!weights) return fail("null weights");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * user_params(h), hipMemcpyHostToDevice, h->stream));
     if (forward_impl(h, h->d_w, h->d_sol, false)) return 1;
     if (sol)
         HIPCHK(hipMemcpyAsync(sol, h->d_sol, sizeof(float) * (size_t)h->n_col * h->cfg.n_save * h->m.ns, hipMemcpyDeviceToHost, h->stream));
@@ -874,7 +903,7 @@ extern "C" int colnde_loss(colnde_handle* h, const float* weights, const float s
     if (!h) return fail("null handle");
     if (!weights || !scalings || !terms || !total) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * user_params(h), hipMemcpyHostToDevice, h->stream));
     if (colnde_loss_dev(h, h->d_w, scalings, h->d_out)) return 1;
     float o[8];
     HIPCHK(hipMemcpyAsync(o, h->d_out, sizeof(o), hipMemcpyDeviceToHost, h->stream));
@@ -941,7 +970,8 @@ static int fc_plan_tapes(colnde_handle* h) {
     const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE;
     // bytes of tape per column and save interval
     const int cw = h->fc_cw;
-    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0));
+    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0) +
+                                                                 (h->conv.c ? fc_conv_tape_floats(m.Nz) / 16 * sizeof(float) : 0));      // (conv handles: the conv tape)
     const int n32 = (h->n_col + 31) / 32 * 32;
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -995,12 +1025,18 @@ static int fc_plan_tapes(colnde_handle* h) {
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_fc_masks, tiles_b * stage_recs * fc_mask_words() * sizeof(unsigned int));
     if (e == hipSuccess && ca) e = hipMalloc((void**)&h->d_fc_switch, tiles_b * stage_recs * fc_switch_words(cw) * sizeof(unsigned long long));
     if (e == hipSuccess && h->fc_nseg > 1) e = hipMalloc((void**)&h->d_fc_lam, (size_t)n32 * m.Nz * sizeof(float));
+    if (e == hipSuccess && h->conv.c) {
+        h->conv.cslab_rows = h->fc_nblocks * h->fc_nseg * FC_CONV_GRAD_MAX_SLICES;
+        e = hipMalloc((void**)&h->conv.d_ctape, n_rec * fc_conv_tape_floats(m.Nz) * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->conv.d_cslab, (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS * sizeof(float));
+    }
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_macros, mac.size() * sizeof(DwMacro));
     if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
     if (e == hipSuccess && !h->d_slab) e = hipMalloc((void**)&h->d_slab, (size_t)h->fc_rows * stride * sizeof(float));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        for (void** p : {(void**)&h->d_dwtape, (void**)&h->d_fc_masks, (void**)&h->d_fc_switch, (void**)&h->d_fc_lam, (void**)&h->d_macros})
+        for (void** p : {(void**)&h->d_dwtape, (void**)&h->d_fc_masks, (void**)&h->d_fc_switch, (void**)&h->d_fc_lam, (void**)&h->d_macros, (void**)&h->conv.d_ctape,
+                         (void**)&h->conv.d_cslab})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         return fail("fc32: hipMalloc of the tapes (%zu bytes for %d columns x %d save intervals) failed: %s", (size_t)block * per_col_iv * seg, block, seg,
                     hipGetErrorString(e));
@@ -1188,9 +1224,13 @@ extern "C" int colnde_loss_grad_dev(colnde_handle* h, const float* d_weights, co
         LossWeights lw;
         loss_weights(h, scalings, &lw);
         const size_t ns = h->m.ns;
-        hipError_t e = fc_launch_pack(h->m, h->fc_cw, d_weights, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_simgf, h->d_fc_simgb, h->stream);
+        const float* d_we = nullptr;
+        if (fc_engine_weights(h, d_weights, &d_we)) return 1;
+        const FcConv cv = fc_conv_args(h);                                  // (after the plan: the conv tape exists)
+        hipError_t e = fc_launch_pack(h->m, h->fc_cw, d_we, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, h->d_fc_simgf, h->d_fc_simgb, h->stream);
         if (e != hipSuccess) return fail("fc32 pack launch failed: %s", hipGetErrorString(e));
         HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)h->fc_rows * stride * sizeof(float), h->stream));
+        if (h->conv.c) HIPCHK(hipMemsetAsync(h->conv.d_cslab, 0, (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS * sizeof(float), h->stream));
         const int cw = h->fc_cw;
         const int n_wg = (h->n_col + cw - 1) / cw, n_iv = h->cfg.n_save - 1, nseg = h->fc_nseg;
         const size_t gemm_rows0 = (size_t)n_wg * nseg;                      // slab: [tile][segment] adjoint rows, then [block][segment][slice] GEMM rows
@@ -1209,7 +1249,7 @@ extern "C" int colnde_loss_grad_dev(colnde_handle* h, const float* d_weights, co
                     e = fc_launch_adjoint(h->m, h->fc_cw, h->d_fc_imgb, (h->sp_adj && fc_split_supported(h->fc_cw)) ? h->d_fc_simgb : nullptr, h->d_times, h->cfg.n_save, iv0, iv1, h->cfg.substeps, h->d_sol + (size_t)c0 * h->cfg.n_save * ns,
                                           h->d_truth + (size_t)c0 * h->cfg.n_save * ns, h->d_dwtape, h->d_fc_masks, h->d_fc_switch, lw.w[2],
                                           nseg > 1 ? h->d_fc_lam + (size_t)c0 * h->m.Nz : nullptr,
-                                          h->d_slab + ((size_t)sg * n_wg + (size_t)(c0 / cw)) * stride, nc, h->stream);
+                                          h->d_slab + ((size_t)sg * n_wg + (size_t)(c0 / cw)) * stride, nc, h->stream, nullptr, h->conv.c ? &cv : nullptr);
                     if (e != hipSuccess) return fail("fc32 adjoint launch failed: %s", hipGetErrorString(e));
                 }
                 {
@@ -1221,13 +1261,23 @@ extern "C" int colnde_loss_grad_dev(colnde_handle* h, const float* d_weights, co
                     e = launch_dw_gemm(h->d_dwtape, tiles_b * (cw / 16) * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst, (int)dwtape_row_floats(h->m), h->d_macros,
                                        h->n_macros, h->dw_slices, h->d_slab + (gemm_rows0 + ((size_t)b * nseg + sg) * h->dw_slices) * stride, stride, h->stream);
                     if (e != hipSuccess) return fail("dW GEMM launch failed: %s", hipGetErrorString(e));
+                    if (h->conv.c) {                                        // the filter's c + 1 entries, from the conv tape of the same records
+                        e = launch_fc_conv_grad(h->conv.d_ctape, (long)(tiles_b * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst) * 16, h->m.Nz, h->conv.c,
+                                                h->conv.d_cslab + ((size_t)b * nseg + sg) * FC_CONV_GRAD_MAX_SLICES * FC_CONV_GRAD_SLOTS, h->stream);
+                        if (e != hipSuccess) return fail("conv filter gradient launch failed: %s", hipGetErrorString(e));
+                    }
                 }
             }
         }
         {
             Timed tm(h, K_REDUCE);
-            e = launch_reduce(h->d_slab, h->fc_rows, h->m.n_params, stride, lw, d_out, h->stream);
+            e = launch_reduce(h->d_slab, h->fc_rows, h->m.n_params, stride, lw, h->conv.c ? h->conv.d_gpad : d_out, h->stream);
             if (e != hipSuccess) return fail("reduce launch failed: %s", hipGetErrorString(e));
+            if (h->conv.c) {                                                // the user's layout: filter entries in front, W1's padded columns dropped
+                e = launch_fc_conv_fold(h->conv.d_gpad, h->conv.d_cslab, h->conv.cslab_rows, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->conv.n_params + 8, d_out,
+                                        h->stream);
+                if (e != hipSuccess) return fail("conv gradient fold launch failed: %s", hipGetErrorString(e));
+            }
         }
         return 0;
     }
@@ -1311,7 +1361,7 @@ extern "C" int colnde_loss_grad(colnde_handle* h, const float* weights, const fl
     if (!h) return fail("null handle");
     if (!weights || !scalings || !terms || !total || !grad) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
-    const int np = h->m.n_params;
+    const int np = user_params(h);
     HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * np, hipMemcpyHostToDevice, h->stream));
     if (colnde_loss_grad_dev(h, h->d_w, scalings, h->d_out)) return 1;
     float o[8];
@@ -1558,6 +1608,77 @@ static int fc_ens_refusals(const colnde_config* cfg, int n_models) {
     return 0;
 }
 
+// ---- the --conv network (train_free_convection_nde.jl:110-122): a handle of its own on the 16-column fc32 kernels -------------------------------------
+// Decided from the configuration and the environment alone, before any device work
+static int conv_refusals(const colnde_config* cfg, int c) {
+    if (c < 2 || c > FC_CONV_MAX)
+        return fail("conv_filter = %d outside 2..%d (the reference builds the plain three-Dense chain for --conv <= 1: colnde_create; the taps are an unrolled loop of %d)", c,
+                    FC_CONV_MAX, FC_CONV_MAX);
+    if (cfg->model == COLNDE_MODEL_WIND_MIXING)
+        return fail("colnde_create_conv covers the free-convection models (FreeConvectionNDE, ConvectiveAdjustmentNDE): the wind-mixing driver has no --conv network");
+    {
+        DevModel dm;
+        PackInfo pk;
+        build_model(cfg, &dm, &pk);
+        if (!fc_supported(dm, COLNDE_STEPPER_RK4))
+            return fail("colnde_create_conv takes the plain fc32 configuration, layer_sizes = (Nz, 4Nz, 4Nz, Nz-1) with relu, relu, identity and Nz = 32 or 64 (Nz = %d, %d "
+                        "layers here): conv_filter says that the first Dense takes Nz - c + 1 inputs behind the filter", cfg->Nz, cfg->n_layers);
+    }
+    if (cfg->engine != COLNDE_ENGINE_AUTO && cfg->engine != COLNDE_ENGINE_FC32)
+        return fail("the conv network runs the fc32 kernels (engine AUTO or FC32): engine forced to %d has no filter", cfg->engine);
+    if (cfg->model == COLNDE_MODEL_FREE_CONVECTION && cfg->stepper == COLNDE_STEPPER_RKC2)
+        return fail("FreeConvectionNDE under RKC2: fc32 has no such kernel (RKC2 covers ConvectiveAdjustmentNDE; FreeConvectionNDE runs RK4)");
+    if (cfg->substeps == 0)
+        return fail("substeps = 0 (chosen from reltol by the first solve) is not supported on a conv handle: the error estimate does not cover the filter — choose the count "
+                    "and pass it");
+    {
+        const int ms = colnde_min_substeps(cfg);
+        const char* e = getenv("COLNDE_ALLOW_UNSTABLE_DT");
+        if (ms < 0) return 1;
+        if (cfg->substeps < ms && !(e && atoi(e) != 0))
+            return fail("substeps = %d is below colnde_min_substeps = %d: the step leaves the stepper's stability region (lambda = -%.4g; COLNDE_ALLOW_UNSTABLE_DT=1 overrides)",
+                        cfg->substeps, ms, stiff_lambda(cfg));
+    }
+    if (cfg->n_columns > 4096)
+        return fail("%d columns: the conv network covers the 16-column tiles (at most 4,096 columns, fc_tile_width); the 32-column kernels have no filter", cfg->n_columns);
+    {
+        const char* e = getenv("COLNDE_FC");
+        if (e && *e && atoi(e) == 0) return fail("COLNDE_FC=0 sends free convection to the tile16 engine, which has no filter: conv handles refuse it");
+        e = getenv("COLNDE_FC_CW");
+        if (e && atoi(e) == 32) return fail("COLNDE_FC_CW=32 selects the 32-column kernels, which have no filter: conv handles refuse it");
+        if (getenv("COLNDE_FC_BLOCK")) return fail("COLNDE_FC_BLOCK: conv handles hold one block of columns (at most 4,096)");
+    }
+    return 0;
+}
+
+extern "C" int colnde_create_conv(const colnde_config* cfg, int conv_filter, colnde_handle** out) {
+    if (!out) return fail("null out pointer");
+    *out = nullptr;
+    if (validate(cfg)) return 1;
+    if (conv_refusals(cfg, conv_filter)) return 1;
+    colnde_handle* h = nullptr;
+    if (colnde_create(cfg, &h)) return 1;
+    if (!h->use_fc || h->fc_cw != 16) {
+        colnde_destroy(h);
+        return fail("colnde_create_conv: the configuration did not select the 16-column fc32 kernels");
+    }
+    const DevModel& m = h->m;
+    const int H = 4 * m.Nz, M = m.Nz - conv_filter + 1;
+    h->conv.w1_end = m.w_off[0] + H * M;
+    h->conv.n_zero = H * (conv_filter - 1);
+    h->conv.n_params = conv_filter + 1 + m.n_params - h->conv.n_zero;
+    hipError_t e = m.w_off[0] == 0 ? hipMalloc((void**)&h->conv.d_wpad, (size_t)m.n_params * sizeof(float)) : hipErrorInvalidValue;
+    if (e == hipSuccess) e = hipMalloc((void**)&h->conv.d_gpad, ((size_t)m.n_params + 8) * sizeof(float));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        colnde_destroy(h);
+        return fail("colnde_create_conv: allocating the padded weight and gradient vectors failed: %s", hipGetErrorString(e));
+    }
+    h->conv.c = conv_filter;
+    *out = h;
+    return 0;
+}
+
 // The tapes of all K models, planned once at creation by fc_plan_tapes' rules on a per-model budget of (free memory - margin) / K: one block of all columns
 // (column blocks do not occur at <= 4,096 columns), the whole time axis when it fits and time segments otherwise (COLNDE_FC_SEG=<intervals> forces), the
 // slice count a single handle of this size plans.  Refused with the bytes it needs when not even one save interval per segment fits.
@@ -1761,6 +1882,7 @@ extern "C" int colnde_ensemble_causal_penalty_dev(colnde_handle* h, const float*
 static int ensemble_only(const colnde_handle* h) {
     if (!h) return fail("null handle");
     if (h->closure) return fail("colnde_ensemble_* take weight vectors, but this is a closure handle (no networks): use colnde_closure_* (include/colnde.h)");
+    if (h->conv.c) return fail("colnde_ensemble_* do not cover the convolutional first layer of a colnde_create_conv handle (conv=%d): ensembles of conv networks are out of scope", h->conv.c);
     if (!h->ensemble) return fail("not an ensemble handle: colnde_ensemble_* take the handles of colnde_create_ensemble (colnde_create: the single-model calls)");
     return 0;
 }
@@ -1928,6 +2050,7 @@ static float norm_floor(float reltol) { return 1e-6f / (reltol > 0.0f ? reltol :
 
 extern "C" int colnde_error_estimate_dev(colnde_handle* h, const float* d_weights, float* max_rel_err) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_weights || !max_rel_err) return fail("null pointer argument");
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
@@ -1949,6 +2072,7 @@ extern "C" int colnde_error_estimate_dev(colnde_handle* h, const float* d_weight
 
 extern "C" int colnde_error_estimate(colnde_handle* h, const float* weights, float* max_rel_err) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (!weights || !max_rel_err) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
@@ -2006,6 +2130,7 @@ static int choose_substeps_impl(colnde_handle* h, const float* d_weights, float 
 
 extern "C" int colnde_choose_substeps(colnde_handle* h, const float* weights, float reltol, int* substeps, float* estimate) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (!weights) return fail("null weights");
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
@@ -2044,6 +2169,7 @@ extern "C" int colnde_set_substeps(colnde_handle* h, int substeps) {
 // ---- flux diagnostics: predict_flux and loss_per_tstep ---------------------------------------------------------------------------------
 extern "C" int colnde_flux_dev(colnde_handle* h, const float* d_x, const float* d_weights, const float* d_bcs, float t, float* d_flux, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_x || !d_weights || !d_bcs || !d_flux) return fail("null pointer argument");
     if (n_columns < 1) return fail("n_columns must be >= 1");
@@ -2058,6 +2184,7 @@ extern "C" int colnde_flux_dev(colnde_handle* h, const float* d_x, const float* 
 
 extern "C" int colnde_flux(colnde_handle* h, const float* x, const float* weights, const float* bcs, float t, float* flux, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (!x || !weights || !bcs || !flux) return fail("null pointer argument");
     if (n_columns < 1) return fail("n_columns must be >= 1");
@@ -2094,7 +2221,7 @@ extern "C" int colnde_loss_per_tstep(colnde_handle* h, const float* weights, flo
     HIPCHK(hipSetDevice(h->device));
     HostStage st(h, "loss_per_tstep");
     float* d_o = nullptr;
-    st.to(h->d_w, weights, (size_t)h->m.n_params);
+    st.to(h->d_w, weights, (size_t)user_params(h));
     st.out(&d_o, out, (size_t)h->n_col * 6 * h->cfg.n_save);
     if (st.upload()) return 1;
     if (colnde_loss_per_tstep_dev(h, h->d_w, d_o)) return 1;
@@ -2151,6 +2278,7 @@ extern "C" int colnde_scale_dev(colnde_handle* h, const float* d_x, int64_t coun
 extern "C" int colnde_comm_allreduce_dev(colnde_comm* c, float* d_buf, int64_t n, int op, void* hip_stream);
 extern "C" int colnde_allreduce_result_dev(colnde_handle* h, colnde_comm* comm, float* d_out) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h || !comm || !d_out) return fail("null argument");
     return colnde_comm_allreduce_dev(comm, d_out, (int64_t)h->m.n_params + 8, 0, (void*)h->stream);
 }
@@ -2161,6 +2289,7 @@ extern "C" int colnde_pretrain_flux_dev(colnde_handle* h, int flux_type, float* 
                                         float gradient_scaling, float eta, float beta1, float beta2, float eps, double beta_t[2],
                                         int update, float* mean_loss) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     if (!h) return fail("null handle");
     if (!d_theta || !d_profiles || !d_bcs || !d_flux || !beta_t || !mean_loss) return fail("null pointer argument");
     if (update && (!d_m || !d_v)) return fail("the ADAM moments are needed when update != 0");
@@ -2219,6 +2348,7 @@ extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
         info[3] = h->fc_nseg > 1 ? h->fc_nseg : 0;       // fc32: time segments of the tapes (0: the tapes hold the whole axis)
         info[4] = h->d_dwtape ? 1 : 0;
         info[5] = h->d_dwtape ? h->dw_slices : 0;
+        info[6] = h->conv.c;
     } else if (h->use_rt) {
         info[1] = h->rt_block;
         info[2] = h->rt_nblocks;
@@ -2262,19 +2392,21 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
         return need;
     }
     const char* eng = info[0] == COLNDE_ENGINE_MFMA ? "regtile" : info[0] == COLNDE_ENGINE_FC32 ? "fc32" : ((info[6] & 1) ? "tile16+net-split" : "tile16");
+    if (info[0] == COLNDE_ENGINE_FC32) info[6] = 0;                  // (fc32: the filter length of a conv handle, reported below; the bits are tile16's)
     char why[96] = "";
     if (h->auto_substeps) snprintf(why, sizeof why, "(stability bound; pending: the first solve chooses from reltol=%g)", h->cfg.reltol);
     else if (h->substeps_chosen) snprintf(why, sizeof why, "(chosen from reltol, estimate=%.3g)", h->last_estimate);
     snprintf(t, sizeof t, "engine=%s columns=%d stepper=%s substeps=%d%s", eng, h->cfg.n_columns, h->cfg.stepper == COLNDE_STEPPER_RKC2 ? "rkc2" : "rk4",
              h->cfg.substeps, why);
     s += t;
+    if (h->conv.c) { snprintf(t, sizeof t, " conv=%d n_params=%d", h->conv.c, h->conv.n_params); s += t; }
     if (h->ensemble) { snprintf(t, sizeof t, " models=%d tape_bytes_per_model=%zu", h->n_models, h->ens_model_bytes); s += t; }
     if (h->cfg.stepper == COLNDE_STEPPER_RKC2) { snprintf(t, sizeof t, " rkc_stages=%d%s", h->m.nst, h->cfg.rkc_stages ? "" : "(automatic)"); s += t; }
     snprintf(t, sizeof t, " matrix_arithmetic=%s forward=%s adjoint=%s dw=%s", h->cfg.matrix_arithmetic == COLNDE_MATRIX_BF16X3_EXACT ? "bf16x3_exact" : "f32_mfma",
              (info[7] & 2) ? "bf16x3" : "f32", (info[7] & 4) ? "bf16x3" : "f32", (info[7] & 8) ? "bf16x3" : "f32");
     s += t;
     if (wm_infer_covers(h)) s += " wm_infer=f32";      // colnde_wm_infer_dz_flux / colnde_wm_embedded_step[_flux] / colnde_wm_diagnose_flux: the f32 matrix pipe under either arithmetic
-    if (fce_covers(h)) s += " fc_embed=f32";      // colnde_fc_embedded_step / colnde_fc_diagnose_wT: likewise
+    if (!h->conv.c && fce_covers(h)) s += " fc_embed=f32";      // colnde_fc_embedded_step / colnde_fc_diagnose_wT: likewise
     if (info[1]) { snprintf(t, sizeof t, " block=%dx%d", info[1], info[2]); s += t; } else s += " block=(not planned yet)";
     if (info[0] == COLNDE_ENGINE_MFMA) { snprintf(t, sizeof t, " z1_tape=%d", info[3]); s += t; }
     if (info[0] == COLNDE_ENGINE_FC32) { snprintf(t, sizeof t, " time_segments=%d tile_width=%d dw_slices=%d", info[3], h->fc_cw, info[5]); s += t; }
@@ -2444,6 +2576,7 @@ extern "C" int colnde_create_closure(const colnde_config* cfg, int n_sets, colnd
 
 static int closure_only(const colnde_handle* h) {
     if (!h) return fail("null handle");
+    if (h->conv.c) return fail("colnde_closure_* take the handles of colnde_create_closure: this is a colnde_create_conv handle (conv=%d)", h->conv.c);
     if (!h->closure) return fail("not a closure handle: colnde_closure_* take the handles of colnde_create_closure");
     return 0;
 }

@@ -15,11 +15,13 @@ static int infer_impl(colnde_handle* h, const float* d_weights, const float* d_T
 extern "C" int colnde_infer_forcing_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux,
                                         float Lz, float* d_out, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     return infer_impl(h, d_weights, d_T, d_top_flux, Lz, d_out, n_columns, 1.0f);
 }
 extern "C" int colnde_infer_dz_wT_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux,
                                       float Lz, float* d_out, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     return infer_impl(h, d_weights, d_T, d_top_flux, Lz, d_out, n_columns, -1.0f);
 }
 static int infer_impl(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, float Lz, float* d_out, int n_columns, float sign) {
@@ -50,11 +52,13 @@ static int infer_host(colnde_handle* h, const float* weights, const float* T, co
 extern "C" int colnde_infer_forcing(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz,
                                     float* out, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     return infer_host(h, weights, T, top_flux, Lz, out, n_columns, 1.0f);
 }
 extern "C" int colnde_infer_dz_wT(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz,
                                   float* out, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     return infer_host(h, weights, T, top_flux, Lz, out, n_columns, -1.0f);
 }
 static int infer_host(colnde_handle* h, const float* weights, const float* T, const float* top_flux, float Lz, float* out, int n_columns, float sign) {
@@ -214,6 +218,7 @@ static int wm_launch(colnde_handle* h, int slot, const char* what, const float* 
 extern "C" int colnde_wm_infer_dz_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
                                            const float* d_top_flux, float Lz, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[8] = {d_weights, d_u, d_v, d_T, d_top_flux, d_dz_uw, d_dz_vw, d_dz_wT};
     if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
     HIPCHK(hipSetDevice(h->device));
@@ -226,6 +231,7 @@ extern "C" int colnde_wm_embedded_step_dev(colnde_handle* h, const float* d_weig
                                            int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out,
                                            float* d_T_out, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[8] = {d_weights, d_u, d_v, d_T, d_top_flux, d_dz_uw, d_dz_vw, d_dz_wT};
     if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
     if (impl_diff_check(h, d_u, d_v, d_T, d_u_out, d_v_out, d_T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
@@ -248,6 +254,7 @@ extern "C" int colnde_wm_diagnose_flux_dev(colnde_handle* h, const float* d_weig
                                            const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, const float params[7],
                                            int convective_adjustment, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[8] = {d_u, d_v, d_T, d_uw, d_vw, d_wT, d_weights, d_top_flux};
     if (wm_diag_check(h, __func__, ptrs, 6, Lz, params, n_columns)) return 1;
     if (!d_weights || !d_top_flux) return fail("null pointer argument");
@@ -261,6 +268,7 @@ extern "C" int colnde_wm_embedded_step_flux_dev(colnde_handle* h, const float* d
                                                 const float params[7], int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT,
                                                 float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[12] = {d_u, d_v, d_T, d_dz_uw, d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT};
     if (wm_diag_check(h, __func__, ptrs, 12, Lz, params, n_columns)) return 1;
     if (!d_weights || !d_top_flux) return fail("null pointer argument");
@@ -306,6 +314,7 @@ static int wm_host(colnde_handle* h, const char* fn, const float* weights, const
 extern "C" int colnde_wm_infer_dz_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux, float Lz,
                                        float* dz_uw, float* dz_vw, float* dz_wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[8] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT};
     if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
     return wm_host(h, __func__, weights, u, v, T, top_flux, nullptr, nullptr, Lz, 0.0f, nullptr, 0, dz_uw, dz_vw, dz_wT, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -316,6 +325,7 @@ extern "C" int colnde_wm_embedded_step(colnde_handle* h, const float* weights, c
                                        const float* halo_bottom, float Lz, float dt, const float params[7], int convective_adjustment, float* dz_uw,
                                        float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[8] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT};
     if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
     if (impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
@@ -327,6 +337,7 @@ extern "C" int colnde_wm_diagnose_flux(colnde_handle* h, const float* weights, c
                                        const float* halo_bottom, const float* halo_top, float Lz, const float params[7], int convective_adjustment, float* uw,
                                        float* vw, float* wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[8] = {weights, u, v, T, top_flux, uw, vw, wT};
     if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
     if (!params) return fail("null pointer argument");
@@ -339,6 +350,7 @@ extern "C" int colnde_wm_embedded_step_flux(colnde_handle* h, const float* weigh
                                             int convective_adjustment, float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out,
                                             float* uw, float* vw, float* wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[11] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT, uw, vw, wT};
     if (wm_infer_check(h, __func__, ptrs, 11, Lz, n_columns)) return 1;
     if (impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
@@ -564,6 +576,7 @@ extern "C" int colnde_fc_embedded_step_dev(colnde_handle* h, const float* d_weig
                                            const float* d_halo_top, float Lz, float dt, float K, float* d_dz_wT, float* d_T_out, float* d_wT_faces,
                                            int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[5] = {d_weights, d_T, d_top_flux, d_dz_wT, d_T_out};
     if (fce_check(h, __func__, ptrs, 5, Lz, K, n_columns)) return 1;
     if (!(dt > 0.0f)) return fail("dt > 0 required");
@@ -583,6 +596,7 @@ extern "C" int colnde_fc_embedded_step_dev(colnde_handle* h, const float* d_weig
 extern "C" int colnde_fc_diagnose_wT_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
                                          const float* d_halo_top, float Lz, float K, float* d_wT_faces, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[4] = {d_weights, d_T, d_top_flux, d_wT_faces};
     if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
     return fce_launch(h, __func__, false, d_weights, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, 0.0f, K, nullptr, nullptr, d_wT_faces, n_columns);
@@ -612,6 +626,7 @@ static int fce_host(colnde_handle* h, const char* fn, const float* weights, cons
 extern "C" int colnde_fc_embedded_step(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
                                        const float* halo_top, float Lz, float dt, float K, float* dz_wT, float* T_out, float* wT_faces, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[5] = {weights, T, top_flux, dz_wT, T_out};
     if (fce_check(h, __func__, ptrs, 5, Lz, K, n_columns)) return 1;
     if (!(dt > 0.0f)) return fail("dt > 0 required");
@@ -621,6 +636,7 @@ extern "C" int colnde_fc_embedded_step(colnde_handle* h, const float* weights, c
 extern "C" int colnde_fc_diagnose_wT(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
                                      const float* halo_top, float Lz, float K, float* wT_faces, int n_columns) {
     SINGLE_MODEL_ONLY(h);
+    PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[4] = {weights, T, top_flux, wT_faces};
     if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
     return fce_host(h, __func__, weights, T, top_flux, halo_bottom, halo_top, Lz, 0.0f, K, nullptr, nullptr, wT_faces, n_columns);

@@ -40,6 +40,14 @@ bool fce_covers(const colnde_handle* h);
                         __func__, (h)->n_models);                                                                                         \
     } while (0)
 
+// Entry points outside the conv handle's list (include/colnde.h, colnde_create_conv) refuse it: the network they would evaluate has no filter
+#define PLAIN_NETWORK_ONLY(h)                                                                                                             \
+    do {                                                                                                                                  \
+        if ((h) && (h)->conv.c)                                                                                                           \
+            return fail("%s does not cover the convolutional first layer of a colnde_create_conv handle (conv=%d): conv handles solve, "  \
+                        "differentiate and train (forward, loss, loss_grad, loss_per_tstep, adam_step)", __func__, (h)->conv.c);          \
+    } while (0)
+
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
         hipError_t e_ = (expr);                                                                   \
@@ -51,8 +59,22 @@ enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1
 
 struct PendingEvent { hipEvent_t a, b; int which; };
 
+// colnde_create_conv: the filter in front of the plain fc32 network the handle holds in `m`
+struct ConvBlock {
+    int c = 0;                      // taps (0: not a conv handle)
+    int n_params = 0;               // the user's parameter count: c + 1 + (plain count) - 4Nz (c - 1)
+    int w1_end = 0, n_zero = 0;     // padded vector: W1's 4Nz M user entries end here, followed by 4Nz (c - 1) zeros
+    const float* d_user = nullptr;  // the user's vector of the call in flight (the filter leads it)
+    float* d_wpad = nullptr;        // [m.n_params] the padded vector the engine packs
+    float* d_gpad = nullptr;        // [m.n_params + 8] the padded result of the reduction, folded into the user's layout
+    float* d_ctape = nullptr;       // [record][16][2 Nz] stage inputs and filter cotangents (planned with the other tapes)
+    float* d_cslab = nullptr;       // [block][segment][FC_CONV_GRAD_MAX_SLICES][FC_CONV_GRAD_SLOTS] the filter gradient's partial sums
+    int cslab_rows = 0;
+};
+
 struct colnde_handle {
     colnde_config cfg;
+    ConvBlock conv;
     std::vector<float> save_times;
     DevModel m;
     PackInfo pk;

@@ -615,3 +615,94 @@ hipError_t launch_causal_penalty(const float* w, const float* coeff, float* resu
     hipLaunchKernelGGL(causal_penalty_kernel, dim3(n_models), dim3(256), 0, stream, w, coeff, result, Nz, w1_off, n_params);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// The --conv network of the free-convection driver (train_free_convection_nde.jl:110-122; colnde_create_conv): Conv((c, 1), 1 => 1, relu) in front of
+// the three Dense layers.  The fc32 kernels run the dense chain on W1 padded with zero columns to 4Nz x Nz; these three kernels are what surrounds them.
+//   theta  = [w (c); b; vec(W1) (4Nz x M, column-major, M = Nz - c + 1); b1; W2; b2; W3; b3]        the user's vector (Flux.params order)
+//   padded = [vec(W1), 4Nz (c - 1) zeros; b1; ...]                                                  the plain network's vector the engine packs
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) fc_conv_pad_kernel(const float* __restrict__ theta, int c, int w1_end, int n_zero, int n_pad, float* __restrict__ padded) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_pad) return;
+    padded[p] = p < w1_end ? theta[c + 1 + p] : (p < w1_end + n_zero ? 0.0f : theta[c + 1 + p - n_zero]);
+}
+
+// The filter's gradient from the conv tape [row = (record, column)][x (Nz) | z̄ (Nz)]: slot d of a workgroup's output row is the sum over its rows and
+// levels of z̄[i] x[i + d] (= ∂/∂w[c - d], 1-based), slot FC_CG_SLOTS - 1 the sum of z̄ (= ∂/∂b).  Lane = level (Nz = 32: two rows per wave); x[i + d]
+// comes from the lane d above — within the row wherever z̄[i] can be non-zero (i < M).  Every sum in a fixed order: a thread over its rows, then one
+// thread per slot over the 256 partial sums.
+#define FC_CG_TAPS 8                               // = FC_CONV_MAX (engine_fc.h)
+#define FC_CG_SLOTS (FC_CG_TAPS + 1)
+template <int NZ>
+__global__ void __launch_bounds__(256) fc_conv_grad_kernel(const float* __restrict__ ctape, long n_rows, long rows_per_wg, int c, float* __restrict__ out) {
+    __shared__ float scr[FC_CG_SLOTS][256];
+    constexpr int RPB = 256 / NZ;                   // rows in flight per workgroup
+    const int tid = threadIdx.x, i = tid & (NZ - 1), rs = tid / NZ;
+    const long r0 = (long)blockIdx.x * rows_per_wg, r1 = r0 + rows_per_wg < n_rows ? r0 + rows_per_wg : n_rows;
+    float acc[FC_CG_SLOTS];
+#pragma unroll
+    for (int k = 0; k < FC_CG_SLOTS; k++) acc[k] = 0.0f;
+    for (long base = r0; base < r1; base += RPB) {  // (uniform trip count: the shifts below need every lane)
+        const long row = base + rs;
+        const bool ok = row < r1;
+        const float x = ok ? ctape[row * (2 * NZ) + i] : 0.0f;
+        const float z = ok ? ctape[row * (2 * NZ) + NZ + i] : 0.0f;
+#pragma unroll
+        for (int d = 0; d < FC_CG_TAPS; d++)
+            if (d < c) acc[d] = fmaf(z, __shfl_down(x, d), acc[d]);
+        acc[FC_CG_SLOTS - 1] += z;
+    }
+#pragma unroll
+    for (int k = 0; k < FC_CG_SLOTS; k++) scr[k][tid] = acc[k];
+    __syncthreads();
+    if (tid < FC_CG_SLOTS) {
+        float s = 0.0f;
+        for (int t = 0; t < 256; t++) s += scr[tid][t];
+        out[(size_t)blockIdx.x * FC_CG_SLOTS + tid] = s;
+    }
+}
+
+// The user's result [c + 1 filter entries; the padded gradient without W1's padded columns (exactly zero: their input is); 8 loss slots]: the filter
+// entries are the sums over the rows of the filter slab, in row order.
+__global__ void __launch_bounds__(256) fc_conv_fold_kernel(const float* __restrict__ gpad, const float* __restrict__ cslab, int n_rows, int c, int w1_end,
+                                                            int n_zero, int n_out, float* __restrict__ out) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_out) return;
+    if (idx <= c) {
+        const int slot = idx < c ? c - 1 - idx : FC_CG_SLOTS - 1;
+        float s = 0.0f;
+        for (int r = 0; r < n_rows; r++) s += cslab[(size_t)r * FC_CG_SLOTS + slot];
+        out[idx] = s;
+        return;
+    }
+    const int q = idx - (c + 1);
+    out[idx] = gpad[q < w1_end ? q : q + n_zero];
+}
+
+hipError_t launch_fc_conv_pad(const float* theta, int c, int w1_end, int n_zero, int n_pad, float* padded, hipStream_t stream) {
+    if (c < 2 || c > FC_CG_TAPS || w1_end < 1 || n_zero < 1 || n_pad < w1_end + n_zero) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fc_conv_pad_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, stream, theta, c, w1_end, n_zero, n_pad, padded);
+    return hipGetLastError();
+}
+
+int fc_conv_grad_slices(long n_rows) {
+    const long s = (n_rows + 255) / 256;            // at least 256 rows per workgroup
+    return (int)(s < 1 ? 1 : (s > FC_CONV_GRAD_MAX_SLICES ? FC_CONV_GRAD_MAX_SLICES : s));
+}
+
+hipError_t launch_fc_conv_grad(const float* ctape, long n_rows, int Nz, int c, float* slab_rows, hipStream_t stream) {
+    if (n_rows < 1 || c < 2 || c > FC_CG_TAPS || (Nz != 32 && Nz != 64)) return hipErrorInvalidValue;
+    const int n_wg = fc_conv_grad_slices(n_rows);
+    const int rpb = 256 / Nz;
+    const long per = ((n_rows + n_wg - 1) / n_wg + rpb - 1) / rpb * rpb;
+    if (Nz == 64) hipLaunchKernelGGL(fc_conv_grad_kernel<64>, dim3(n_wg), dim3(256), 0, stream, ctape, n_rows, per, c, slab_rows);
+    else hipLaunchKernelGGL(fc_conv_grad_kernel<32>, dim3(n_wg), dim3(256), 0, stream, ctape, n_rows, per, c, slab_rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_fc_conv_fold(const float* gpad, const float* cslab, int n_rows, int c, int w1_end, int n_zero, int n_out, float* out, hipStream_t stream) {
+    if (n_rows < 1 || c < 2 || c > FC_CG_TAPS || n_out <= c + 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fc_conv_fold_kernel, dim3((n_out + 255) / 256), dim3(256), 0, stream, gpad, cslab, n_rows, c, w1_end, n_zero, n_out, out);
+    return hipGetLastError();
+}

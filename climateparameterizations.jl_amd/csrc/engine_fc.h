@@ -26,6 +26,19 @@ struct FcEns {
     size_t w = 0, img = 0, simg = 0, bias = 0, x0 = 0, sol = 0, dwtape = 0, masks = 0, swtape = 0, lam = 0, slab = 0;
     int n_models = 1;
 };
+// The reference's --conv network (train_free_convection_nde.jl:110-122): Conv((c, 1), 1 => 1, relu) in front of the three Dense layers, on the 16-column
+// kernels (colnde_create_conv).  The filter is applied where the stage input goes to LDS: y[i] = relu(b + sum_d w[c-1-d] x[i+d]) (NNlib's conv flips the
+// kernel), i < M = Nz - c + 1, zero above; the dense chain runs on W1 padded with zero columns to 4Nz x Nz, so images, dW GEMM and reducers are the plain
+// network's.  wb: the c taps and the bias, as they lead the user's parameter vector.  ctape [record][16 columns][2 Nz]: the stage input x (forward
+// kernel) and the cotangent of the filter's pre-activation (adjoint kernel), record index as in the delta tape; fc_launch_conv_grad contracts the two.
+// Passed by value to the CONV kernels only.
+#define FC_CONV_MAX 8                    // taps: an unrolled loop in the kernels
+struct FcConv {
+    int c = 0;
+    const float* wb = nullptr;
+    float* ctape = nullptr;
+};
+static inline size_t fc_conv_tape_floats(int Nz) { return (size_t)16 * 2 * Nz; }       // per record (16-column tile and stage)
 // ens != null (cw = 16, both image kinds given): the images of all ens->n_models models, weights ens->w floats apart
 hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf, float* imgb, float* bias, unsigned int* simgf, unsigned int* simgb,
                           hipStream_t stream, const FcEns* ens = nullptr);
@@ -36,13 +49,15 @@ hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf
 // simgf != null (and cw == 32): the split kernels (v_mfma_f32_32x32x16_bf16 on exact three-way operand splits) instead of the f32-MFMA ones
 hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const unsigned int* simgf, const float* bias, const float* x0, size_t x0_stride,
                              const float* bcs, const float* save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps, float* sol,
-                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens = nullptr);
+                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens = nullptr,
+                             const FcConv* conv = nullptr);
 // slab: one row of n_params + 8 floats per tile (bias gradients and the squared-error sum; the weight gradients are the dW GEMM's).
 // lam_io [columns padded to 32][Nz]: carries λ between the time segments of a segmented gradient pass (null when one launch covers the axis).
 hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const unsigned int* simgb, const float* save_times, int n_save, int iv_begin, int iv_end,
                              int substeps,
                              const float* sol, const float* truth, float* dwtape, const unsigned int* masks, const unsigned long long* swtape,
-                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens = nullptr);
+                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens = nullptr,
+                             const FcConv* conv = nullptr);
 // compute_neural_network_forcing! (double_gyre_nn.jl:149-168): T [n_col][Nz] model units, top_flux [n_col], out = -dz(wT) on cell centres
 hipError_t fc_launch_infer(const DevModel& m, int cw, const float* imgf, const float* bias, const float* T, const float* top_flux, float inv_dz,
                            float* out, int n_col, hipStream_t stream);

@@ -273,227 +273,48 @@ typedef unsigned long long u64;
 //   ENS: an ensemble (colnde_create_fc_ensemble; 16-column tiles) — blockIdx.y = model.  What a model owns (operand image, biases, solution, the three
 //        tapes; x0 when it is a saved state of the model's own solution) is offset ONCE, here in the prologue, by the strides of `en`: scalar arithmetic on
 //        kernel arguments, no vector load is added before the stage loop.  The single-handle instantiations (ENS = false) never read `en`.
+//   CONV: the --conv network (FcConv, engine_fc.h) — the filter is applied where the stage input goes to LDS.  The kernel's text is ONE body
+//        (fc_forward_body.inc) behind two entry points: fc_forward_kernel (name and arguments as they were; CONV = false) and fc_forward_conv_kernel, which
+//        adds the FcConv argument.  A template flag on fc_forward_kernel itself would rename every existing instantiation and lengthen its argument block.
+// the filter's pre-activation for this lane's level from the column's levels in the lanes above (d = 0: the lane's own): ONE instruction sequence for the
+// forward kernel and for the adjoint's recomputation, so that both see the same bits and the same sign
+__device__ __forceinline__ float fc_conv_pre(float x, const float (&cw)[FC_CONV_MAX], float cb, int c) {
+    float pre = cb;
+#pragma unroll
+    for (int d = 0; d < FC_CONV_MAX; d++)
+        if (d < c) pre = fmaf(cw[d], __shfl_down(x, d), pre);                   // taps in a fixed order: w[c], w[c-1], ..., w[1]
+    return pre;
+}
+// cw[d] = w[c - d] (1-based: the tap that multiplies x[i + d]), zero beyond the filter; cb = b
+__device__ __forceinline__ void fc_conv_load(const FcConv& cv, float (&cw)[FC_CONV_MAX], float& cb) {
+#pragma unroll
+    for (int d = 0; d < FC_CONV_MAX; d++) cw[d] = d < cv.c ? cv.wb[cv.c - 1 - d] : 0.0f;
+    cb = cv.wb[cv.c];
+#pragma unroll
+    for (int d = 0; d < FC_CONV_MAX; d++) asm volatile("" :: "v"(cw[d]));
+    asm volatile("" :: "v"(cb));
+}
+
 template <int NZ, int CW, bool TAPE, bool CA, bool RKC, bool SPLIT = false, bool ENS = false>
 __global__ void __launch_bounds__(256, 2)
 fc_forward_kernel(const void* __restrict__ imgf, const float* __restrict__ bias, const float* __restrict__ x0, size_t x0_stride,
                   const float* __restrict__ bcs, const float* __restrict__ save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps, float CN,
                   float caKN, int nst, const float* __restrict__ rkc, float* __restrict__ sol, float* __restrict__ dwtape, u32* __restrict__ masks,
                   u64* __restrict__ swtape, int n_col, FcEns en) {
-    static_assert(!ENS || CW == 16, "ensembles run the 16-column tiles");
-    if constexpr (ENS) {
-        const size_t k = blockIdx.y;
-        if constexpr (SPLIT) imgf = reinterpret_cast<const u32*>(imgf) + k * en.simg;
-        else imgf = reinterpret_cast<const float*>(imgf) + k * en.img;
-        bias += k * en.bias;
-        x0 += k * en.x0;
-        if (sol) sol += k * en.sol;
-        if constexpr (TAPE) {
-            dwtape += k * en.dwtape;
-            masks += k * en.masks;
-            if constexpr (CA) swtape += k * en.swtape;
-        }
-    }
-    // Save intervals [iv_begin, iv_end) of the time axis, starting from x0 (column stride x0_stride: the initial state, or — a time SEGMENT
-    // of the gradient path — the state the tape-less pass saved at save point iv_begin; restarting there is exact: the saved state IS xn).
-    // Only the intervals from tape_iv0 on are taped (the records are numbered from its first step): the tape-less pass of a time-segmented
-    // gradient tapes its LAST segment on the way, which that segment's own pass would otherwise have to repeat.
-    using S = Fc<NZ, CW>;
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & (CW - 1), h = lane / CW;               // column of the tile; k / row quad
-    float* X = fc_smem;                          // [32][LDX]   stage input
-    float* A1 = X + CW * S::LDX;                 // [32][LDH]   relu(W1 x + b1)
-    float* A2 = A1 + CW * S::LDH;                // [32][LDH]   relu(W2 a1 + b2)
-    float* PART = A1;                            // [KS3][32][NZ] partial sums of the last layer (a1 is dead by then)
-    float* BL = A2 + CW * S::LDH;                // [2H + NZ] biases (a global load in an epilogue would be waited for with vmcnt(0): the ring too)
-    for (int q = tid; q < S::BIAS; q += 256) BL[q] = bias[q];
-    const int col0 = blockIdx.x * CW;
-    FC_OWNER_INDEX();
-
-    typedef FcStream<NZ, CW, SPLIT> Stream;
-    Stream strm;
-    strm.init(imgf, w, lane);
-
-    float xn[S::OWN], vst[S::OWN], kv[S::OWN], bcb[S::OWN], bct[S::OWN];
-#pragma unroll
-    for (int r = 0; r < S::OWN; r++) {
-        const int col = min(col0 + oc[r], n_col - 1);
-        xn[r] = x0[(size_t)col * x0_stride + oi];
-        bcb[r] = bcs[(size_t)col * 2];
-        bct[r] = bcs[(size_t)col * 2 + 1];
-        kv[r] = 0.0f;
-        if (sol && iv_begin == 0 && col0 + oc[r] < n_col) sol[((size_t)(col0 + oc[r]) * n_save) * NZ + oi] = xn[r];
-    }
-    const float b3v = oi < S::NO ? bias[2 * S::H + oi] : 0.0f;
-    // every load issued so far is consumed HERE: a register still "in flight" at the loop header makes the wait-count pass put a
-    // vmcnt(0) at the top of every stage, which would drain the prefetch ring each time
-#pragma unroll
-    for (int r = 0; r < S::OWN; r++) asm volatile("" :: "v"(xn[r]), "v"(bcb[r]), "v"(bct[r]));
-    asm volatile("" :: "v"(b3v));
-    const int n_steps = (iv_end - tape_iv0) * substeps;          // taped steps (and, x nst, records per tile) of this launch
-    const int step_t0 = (tape_iv0 - iv_begin) * substeps;         // first taped step
-
-    // one right-hand-side evaluation: stage input vst[] (owner layout) -> kv[]; qi = record index step * nst + st
-    auto rhs = [&](int qs) {
-        const int qi = qs - step_t0 * nst;
-        const bool tp = TAPE && qi >= 0;                              // wave-uniform
-        int zero = 0;
-        FC_OPAQUE_ZERO(zero);
-        const typename Stream::slot_t* const sb[3] = {strm.base[0] + zero, strm.base[1] + zero, strm.base[2] + zero};
-        const size_t ri = (size_t)blockIdx.x * n_steps * nst + qi;
-        float* rec = tp ? dwtape + ri * ((size_t)CW * S::R) : nullptr;
-        u32* mrec = tp ? masks + ri * 512 + w * 64 + lane : nullptr;
-        // ---- stage input (owner layout) -> LDS rows, tape
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) {
-            X[oc[r] * S::LDX + oi] = vst[r];
-            if (tp) FC_STORE(vst[r], rec + (size_t)oc[r] * S::R + oi);
-        }
-        FC_BARRIER();
-        // ---- hidden layers: z = W a + b on 32x32x2 MFMA, relu, rows to LDS (next layer's B operand) and to the tape
-        auto hidden = [&](int l /* 1, 2 */, float* dstrows, int j, const typename S::acc_t& acc) {
-            const int mt = w + 4 * j;
-            u32 bits = 0;
-#pragma unroll
-            for (int q = 0; q < S::NQ; q++) {
-                const int f = mt * CW + S::qrow(q, h);
-                const f32x4 bq = *reinterpret_cast<const f32x4*>(BL + (l - 1) * S::H + f);
-                f32x4 a;
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const float z = acc[4 * q + e] + bq[e];
-                    a[e] = fmaxf(z, 0.0f);
-                    bits |= (z > 0.0f ? 1u : 0u) << (4 * q + e);
-                }
-                *reinterpret_cast<f32x4*>(dstrows + n * S::LDH + f) = a;
-                if (tp) FC_STORE(a, reinterpret_cast<f32x4*>(rec + (size_t)n * S::R + NZ + (l - 1) * S::H + f));
-            }
-            return bits;
-        };
-        {
-            u32 mb = 0;
-            strm.template section<0>(sb, lane, h, w, X + n * S::LDX,
-                                     [&](int j, const typename S::acc_t& acc) { mb |= hidden(1, A1, j, acc) << (S::ACCN * j); });
-            if (tp) FC_STORE(mb, mrec);
-        }
-        FC_BARRIER();
-        {
-            u32 mb = 0;
-            strm.template section<1>(sb, lane, h, w, A1 + n * S::LDH,
-                                     [&](int j, const typename S::acc_t& acc) { mb |= hidden(2, A2, j, acc) << (S::ACCN * j); });
-            if (tp) FC_STORE(mb, mrec + 256);
-        }
-        FC_BARRIER();
-        // ---- output layer: row tile w % MT3, K part w / MT3; partial sums to LDS
-        strm.template section<2>(sb, lane, h, w, A2 + n * S::LDH,
-            [&](int, const typename S::acc_t& acc) {
-                float* pr = PART + ((w / S::MT3) * CW + n) * NZ + (w % S::MT3) * CW;
-#pragma unroll
-                for (int q = 0; q < S::NQ; q++) {
-                    const f32x4 v = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-                    *reinterpret_cast<f32x4*>(pr + S::qrow(q, h)) = v;
-                }
-            });
-        FC_BARRIER();
-        // ---- physics: faces F = [b; NN(T); t] (free_convection_nde.jl:29-38) [- min(0, K dT/dz) on the interior faces,
-        //      convective_adjustment_nde.jl:43-47], dT = -C Nz (F[i+1] - F[i])
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) {
-            float o = b3v;
-#pragma unroll
-            for (int ks = 0; ks < S::KS3; ks++) o += PART[(ks * CW + oc[r]) * NZ + oi];
-            const float olo = __shfl_up(o, 1);                                // NN output of face i (lane i - 1 holds it)
-            float wlo = oi == 0 ? bcb[r] : olo;
-            float whi = oi == NZ - 1 ? bct[r] : o;
-            if (CA) {
-                const float vlo = __shfl_up(vst[r], 1), vhi = __shfl_down(vst[r], 1);
-                const float glo = (vst[r] - vlo) * (float)NZ, ghi = (vhi - vst[r]) * (float)NZ;     // dT/dz on faces i and i + 1
-                const bool on = oi >= 1 && glo < 0.0f;
-                if (oi >= 1) wlo -= fminf(0.0f, caKN * (vst[r] - vlo));
-                if (oi <= NZ - 2) whi -= fminf(0.0f, caKN * (vhi - vst[r]));
-                (void)ghi;
-                if (tp) {
-                    // the switch pattern of the stage, one bit per face, for the pullback
-                    const u64 bal = __ballot(on);
-                    const u64 mine = NZ == 64 ? bal : (lane < 32 ? (bal & 0xffffffffull) : (bal >> 32));
-                    if (oi == 0) swtape[ri * CW + oc[r]] = mine;
-                }
-            }
-            kv[r] = -CN * (whi - wlo);
-        }
-    };
-
-    int step = 0;
-    if constexpr (!RKC) {
-        float ac[S::OWN];
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) ac[r] = 0.0f;
-        for (int iv = iv_begin; iv < iv_end; iv++) {
-            const float dt = (save_times[iv + 1] - save_times[iv]) / (float)substeps;
-            for (int s = 0; s < substeps; s++, step++) {
-#pragma nounroll
-                for (int st = 0; st < 4; st++) {
-                    const float ca = st == 0 ? 0.0f : (st == 3 ? 1.0f : 0.5f);            // stage abscissa
-                    const float cbp = st == 1 ? 1.0f / 6.0f : 1.0f / 3.0f;                 // RK4 weight of k_{st-1}
-#pragma unroll
-                    for (int r = 0; r < S::OWN; r++) {
-                        float v = xn[r];
-                        if (st > 0) {
-                            ac[r] += cbp * kv[r];
-                            v += ca * dt * kv[r];
-                        }
-                        vst[r] = v;
-                    }
-                    rhs(step * 4 + st);
-                }
-                const bool save = s == substeps - 1;
-#pragma unroll
-                for (int r = 0; r < S::OWN; r++) {
-                    ac[r] += (1.0f / 6.0f) * kv[r];
-                    xn[r] += dt * ac[r];
-                    ac[r] = 0.0f;
-                    if (save && sol && col0 + oc[r] < n_col) sol[((size_t)(col0 + oc[r]) * n_save + iv + 1) * NZ + oi] = xn[r];
-                }
-            }
-        }
-    } else {
-        // Y_0 = xn, d_j = Y_j - Y_0 (increments: float32 stays accurate), F_0 = f0; stage st evaluates F_st = f(Y_st); Y_s ends the step
-        const float* mu_t = rkc, *nu_t = rkc + RKC_LD, *mut_t = rkc + 2 * RKC_LD, *gat_t = rkc + 3 * RKC_LD;
-        float ym1[S::OWN], ym2[S::OWN], f0[S::OWN];
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) { ym1[r] = 0.0f; ym2[r] = 0.0f; f0[r] = 0.0f; }
-        for (int iv = iv_begin; iv < iv_end; iv++) {
-            const float dt = (save_times[iv + 1] - save_times[iv]) / (float)substeps;
-            for (int s = 0; s < substeps; s++, step++) {
-#pragma nounroll
-                for (int st = 0; st <= nst; st++) {      // st = nst: only the final combination Y_s
-                    const float cmu = mu_t[st], cnu = nu_t[st], cmt = mut_t[st] * dt, cga = gat_t[st] * dt;
-                    const bool last = st == nst;
-                    const bool save = last && s == substeps - 1;
-#pragma unroll
-                    for (int r = 0; r < S::OWN; r++) {
-                        float dj = 0.0f;
-                        if (st == 1) {
-                            f0[r] = kv[r];
-                            dj = cmt * f0[r];
-                        } else if (st >= 2) {
-                            dj = cmu * ym1[r] + cnu * ym2[r] + cmt * kv[r] + cga * f0[r];
-                        }
-                        const float v = xn[r] + dj;
-                        ym2[r] = st == 0 ? 0.0f : ym1[r];
-                        ym1[r] = dj;
-                        if (last) {
-                            xn[r] = v;
-                            if (save && sol && col0 + oc[r] < n_col) sol[((size_t)(col0 + oc[r]) * n_save + iv + 1) * NZ + oi] = v;
-                        } else {
-                            vst[r] = v;
-                        }
-                    }
-                    if (last) break;
-                    rhs(step * nst + st);
-                }
-            }
-        }
-    }
+    constexpr bool CONV = false;
+    const FcConv cv = FcConv();
+#include "fc_forward_body.inc"
+}
+template <int NZ, bool TAPE, bool CA, bool RKC, bool SPLIT>
+__global__ void __launch_bounds__(256, 2)
+fc_forward_conv_kernel(const void* __restrict__ imgf, const float* __restrict__ bias, const float* __restrict__ x0, size_t x0_stride,
+                       const float* __restrict__ bcs, const float* __restrict__ save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps,
+                       float CN, float caKN, int nst, const float* __restrict__ rkc, float* __restrict__ sol, float* __restrict__ dwtape,
+                       u32* __restrict__ masks, u64* __restrict__ swtape, int n_col, FcConv cv) {
+    constexpr int CW = 16;
+    constexpr bool ENS = false, CONV = true;
+    const FcEns en = FcEns();
+#include "fc_forward_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -560,246 +381,29 @@ fc_infer_kernel(const float* __restrict__ imgf, const float* __restrict__ bias, 
 struct FcGrad { int b[3]; int n_params; };
 
 // ENS: as in fc_forward_kernel — blockIdx.y = model; image, solution, tapes, λ hand-over and slab rows are the model's own, the truth is shared.
+// CONV: as in the forward kernel, one body (fc_adjoint_body.inc) behind fc_adjoint_kernel (unchanged) and fc_adjoint_conv_kernel.  At the end of the pullback the filter's
+// pre-activation is recomputed from the taped stage input (fc_conv_pre: the forward's bits), its cotangent goes to the second half of the conv-tape record
+// (the filter's gradient is fc_conv_grad_kernel's: no accumulator rides along here) and x̄ = physics part + the filter's transpose applied to it.
 template <int NZ, int CW, bool CA, bool RKC, bool SPLIT = false, bool ENS = false>
 __global__ void __launch_bounds__(256, 2)
 fc_adjoint_kernel(const void* __restrict__ imgb, const float* __restrict__ save_times, int n_save, int iv_begin, int iv_end, int substeps, float CN,
                   float caKN, int nst, const float* __restrict__ rkc, const float* __restrict__ sol, const float* __restrict__ truth,
                   float* __restrict__ dwtape, const u32* __restrict__ masks, const u64* __restrict__ swtape, float w_loss, float* __restrict__ lam_io,
                   float* __restrict__ slab, FcGrad go, int n_col, FcEns en) {
-    static_assert(!ENS || CW == 16, "ensembles run the 16-column tiles");
-    if constexpr (ENS) {
-        const size_t k = blockIdx.y;
-        if constexpr (SPLIT) imgb = reinterpret_cast<const u32*>(imgb) + k * en.simg;
-        else imgb = reinterpret_cast<const float*>(imgb) + k * en.img;
-        sol += k * en.sol;
-        dwtape += k * en.dwtape;
-        masks += k * en.masks;
-        if constexpr (CA) swtape += k * en.swtape;
-        if (lam_io) lam_io += k * en.lam;
-        slab += k * en.slab;
-    }
-    // Save intervals [iv_begin, iv_end), backwards.  lam_io [columns][NZ] (or null: one launch covers the axis) carries λ from one time
-    // segment to the one before it: read unless this is the last segment of the axis, written unless it is the first.
-    using S = Fc<NZ, CW>;
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & (CW - 1), h = lane / CW;               // column of the tile; k / row quad
-    float* DZ2 = fc_smem;                        // [32][LDH]
-    float* DZ1 = DZ2 + CW * S::LDH;              // [32][LDH]
-    float* DZ3 = DZ1;                            // [32][LDX]   dead before dz1 is written
-    float* XBP = DZ2;                            // [KS3][32][NZ] partial sums of W1ᵀ dz1 (dz2 is dead by then)
-    const int col0 = blockIdx.x * CW;
-    FC_OWNER_INDEX();
-
-    typedef FcStream<NZ, CW, SPLIT> Stream;
-    Stream strm;
-    strm.init(imgb, w, lane);
-
-    float lam[S::OWN], xb[S::OWN], kb[S::OWN], db3[S::OWN];
-    u32 swp = 0;                                 // switch bits of this thread's items: bit 2r = face oi, bit 2r + 1 = face oi + 1 of item r
-    float db2 = 0.0f, db1 = 0.0f;                // bias gradients of hidden unit tid (< H): column sums of the dz rows, taken from LDS
-    float sumsq = 0.0f;
-#pragma unroll
-    for (int r = 0; r < S::OWN; r++) {
-        lam[r] = 0.0f; xb[r] = 0.0f; db3[r] = 0.0f; kb[r] = 0.0f;
-        if (lam_io && iv_end < n_save - 1) lam[r] = lam_io[(size_t)(col0 + oc[r]) * NZ + oi];
-        if (iv_begin == 0 && col0 + oc[r] < n_col) {                // save point 0 enters the loss value only
-            const size_t q = ((size_t)(col0 + oc[r]) * n_save) * NZ + oi;
-            const float d = sol[q] - truth[q];
-            sumsq += d * d;
-        }
-    }
-    const int n_steps = (iv_end - iv_begin) * substeps;          // steps (and, x nst, records per tile) of this launch
-
-    // pullback of one right-hand-side evaluation: stage cotangent kb[] (owner layout) -> xb[] = J(Y)ᵀ kb; qi = record index
-    auto pull = [&](int qi) {
-        int zero = 0;
-        FC_OPAQUE_ZERO(zero);
-        const typename Stream::slot_t* const sb[3] = {strm.base[0] + zero, strm.base[1] + zero, strm.base[2] + zero};
-        const size_t ri = (size_t)blockIdx.x * n_steps * nst + qi;
-        float* rec = dwtape + ri * ((size_t)CW * S::R);
-        const u32* mrec = masks + ri * 512 + w * 64 + lane;
-        const u32 m1 = FC_LOAD(mrec), m2 = FC_LOAD(mrec + 256);
-        // ---- physics pullback: dz3[i] = C Nz (k̄[i+1] - k̄[i]) on the Nz-1 interior faces; CA: x̄ += Dᶠᵀ(switch ∘ (-K) ∘ that)
-        float xph[S::OWN];
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) {
-            const float kn = __shfl_down(kb[r], 1);
-            const float dz = oi < S::NO ? CN * (kn - kb[r]) : 0.0f;                 // face i + 1
-            xph[r] = 0.0f;
-            if (CA) {
-                const float dlo = __shfl_up(dz, 1);                                 // face i
-                const float ghi = (oi < S::NO && ((swp >> (2 * r + 1)) & 1u)) ? -dz * caKN : 0.0f;
-                const float glo = (oi >= 1 && ((swp >> (2 * r)) & 1u)) ? -dlo * caKN : 0.0f;
-                xph[r] = glo - ghi;
-            }
-            DZ3[oc[r] * S::LDX + oi] = dz;
-            FC_STORE(dz, rec + (size_t)oc[r] * S::R + NZ + S::ACT4 + 2 * S::H + oi);
-            db3[r] += dz;
-        }
-        FC_BARRIER();
-        auto hidden = [&](int l /* 2, 1: layer whose dz this is */, float* dstrows, u32 bits, int j, const typename S::acc_t& acc) {
-            const int mt = w + 4 * j;
-#pragma unroll
-            for (int q = 0; q < S::NQ; q++) {
-                f32x4 d;
-#pragma unroll
-                for (int e = 0; e < 4; e++) d[e] = ((bits >> (S::ACCN * j + 4 * q + e)) & 1u) ? acc[4 * q + e] : 0.0f;
-                const int f = mt * CW + S::qrow(q, h);
-                *reinterpret_cast<f32x4*>(dstrows + n * S::LDH + f) = d;
-                FC_STORE(d, reinterpret_cast<f32x4*>(rec + (size_t)n * S::R + NZ + S::ACT4 + (l - 1) * S::H + f));
-            }
-        };
-        // ---- dz2 = relu'(z2) ∘ W3ᵀ dz3
-        strm.template section<0>(sb, lane, h, w, DZ3 + n * S::LDX,
-                                          [&](int j, const typename S::acc_t& acc) { hidden(2, DZ2, m2, j, acc); });
-        FC_BARRIER();
-        // bias gradients: hidden unit tid's column sum of the finished dz rows, straight from LDS (16 accumulator registers per row tile
-        // and layer — 64 at Nz = 64 — would otherwise ride along in every lane)
-        auto colsum = [&](const float* rows) {
-            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-#pragma unroll
-            for (int c = 0; c < CW; c += 4) {
-                a0 += rows[(c + 0) * S::LDH + tid];
-                a1 += rows[(c + 1) * S::LDH + tid];
-                a2 += rows[(c + 2) * S::LDH + tid];
-                a3 += rows[(c + 3) * S::LDH + tid];
-            }
-            return (a0 + a1) + (a2 + a3);
-        };
-        if (S::H == 256 || tid < S::H) db2 += colsum(DZ2);
-        // ---- dz1 = relu'(z1) ∘ W2ᵀ dz2
-        strm.template section<1>(sb, lane, h, w, DZ2 + n * S::LDH,
-                                                       [&](int j, const typename S::acc_t& acc) { hidden(1, DZ1, m1, j, acc); });
-        FC_BARRIER();
-        if (S::H == 256 || tid < S::H) db1 += colsum(DZ1);
-        // ---- x̄ = W1ᵀ dz1: row tile w % MT3, K part w / MT3
-        strm.template section<2>(sb, lane, h, w, DZ1 + n * S::LDH,
-            [&](int, const typename S::acc_t& acc) {
-                float* pr = XBP + ((w / S::MT3) * CW + n) * NZ + (w % S::MT3) * CW;
-#pragma unroll
-                for (int q = 0; q < S::NQ; q++) {
-                    const f32x4 v = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-                    *reinterpret_cast<f32x4*>(pr + S::qrow(q, h)) = v;
-                }
-            });
-        FC_BARRIER();
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) {
-            float v = xph[r];
-#pragma unroll
-            for (int ks = 0; ks < S::KS3; ks++) v += XBP[(ks * CW + oc[r]) * NZ + oi];
-            xb[r] = v;
-        }
-        // (the next evaluation writes DZ3 = DZ1's rows: every wave's reads of DZ1 ended before the barrier above; XBP = DZ2's rows
-        //  are next written two barriers from here)
-    };
-    auto load_switch = [&](int qi) {
-        if (CA) {
-            const size_t ri = (size_t)blockIdx.x * n_steps * nst + qi;
-            swp = 0;
-#pragma unroll
-            for (int r = 0; r < S::OWN; r++) swp |= (u32)((swtape[ri * CW + oc[r]] >> oi) & 3ull) << (2 * r);
-        }
-    };
-
-    const float* mu_t = rkc, *nu_t = rkc + RKC_LD, *mut_t = rkc + 2 * RKC_LD, *gat_t = rkc + 3 * RKC_LD, *kap_t = rkc + 5 * RKC_LD;
-    float xbs[S::OWN], yb1[S::OWN], yb2[S::OWN], yb0[S::OWN], f0b[S::OWN];
-#pragma unroll
-    for (int r = 0; r < S::OWN; r++) { xbs[r] = 0.0f; yb1[r] = 0.0f; yb2[r] = 0.0f; yb0[r] = 0.0f; f0b[r] = 0.0f; }
-    for (int iv = iv_end - 1; iv >= iv_begin; iv--) {
-        const float dt = (save_times[iv + 1] - save_times[iv]) / (float)substeps;
-        // λ += ∂loss/∂sol[:, iv+1]   (nde_loss = Flux.mse over every (level, save point, simulation): training.jl:55-62)
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++)
-            if (col0 + oc[r] < n_col) {
-                const size_t q = ((size_t)(col0 + oc[r]) * n_save + iv + 1) * NZ + oi;
-                const float d = sol[q] - truth[q];
-                sumsq += d * d;
-                lam[r] += 2.0f * w_loss * d;
-            }
-        for (int s = substeps - 1; s >= 0; s--) {
-            const int step = (iv - iv_begin) * substeps + s;
-            if constexpr (!RKC) {
-#pragma unroll
-                for (int r = 0; r < S::OWN; r++) xbs[r] = 0.0f;
-#pragma nounroll
-                for (int st = 3; st >= 0; st--) {
-                    // k̄4 = dt/6 λ; k̄3 = dt/3 λ + dt x̄4; k̄2 = dt/3 λ + dt/2 x̄3; k̄1 = dt/6 λ + dt/2 x̄2
-                    const float cwl = (st == 0 || st == 3) ? dt / 6.0f : dt / 3.0f;
-                    const float cwx = st == 3 ? 0.0f : (st == 2 ? dt : 0.5f * dt);
-#pragma unroll
-                    for (int r = 0; r < S::OWN; r++) kb[r] = cwl * lam[r] + cwx * xb[r];
-                    load_switch(step * 4 + st);                 // RK4: every stage's own pattern (the exact discrete adjoint)
-                    pull(step * 4 + st);
-#pragma unroll
-                    for (int r = 0; r < S::OWN; r++) xbs[r] += xb[r];
-                }
-#pragma unroll
-                for (int r = 0; r < S::OWN; r++) lam[r] += xbs[r];
-            } else {
-                load_switch(step * nst + nst - 1);              // one switch pattern per step: that of Y_{s-1}
-#pragma nounroll
-                for (int st = nst - 1; st >= 0; st--) {
-                    // stage input Y_st feeds Y_j, j = st + 1, through mu~_j h F_st
-                    const float cmu = mu_t[st + 1], cnu = nu_t[st + 1], cmt = mut_t[st + 1] * dt, cga = gat_t[st + 1] * dt, ck0 = kap_t[st + 1];
-#pragma unroll
-                    for (int r = 0; r < S::OWN; r++) {
-                        // lam = cotangent of Y_j, complete once the previous iteration's pullback (xb: J(Y_j)ᵀ F̄_j) is added
-                        if (st < nst - 1) {
-                            const float yj = yb1[r] + xb[r];
-                            yb1[r] = yb2[r];
-                            yb2[r] = 0.0f;
-                            lam[r] = yj;
-                        }
-                        if (st >= 1) {
-                            yb0[r] += ck0 * lam[r];
-                            yb1[r] += cmu * lam[r];
-                            yb2[r] += cnu * lam[r];
-                            f0b[r] += cga * lam[r];
-                            kb[r] = cmt * lam[r];
-                        } else {
-                            // Y_1 = Y_0 + mu~_1 h F_0: lam holds Ȳ_1, yb1 the nu_2 part of Ȳ_0
-                            yb0[r] += lam[r] + yb1[r];
-                            kb[r] = f0b[r] + cmt * lam[r];
-                            yb1[r] = 0.0f;
-                            f0b[r] = 0.0f;
-                        }
-                    }
-                    pull(step * nst + st);
-                }
-                // λ_n = Ȳ_0 + J(Y_0)ᵀ F̄_0
-#pragma unroll
-                for (int r = 0; r < S::OWN; r++) {
-                    lam[r] = yb0[r] + xb[r];
-                    yb0[r] = 0.0f;
-                }
-            }
-        }
-    }
-    if (lam_io && iv_begin > 0)
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) lam_io[(size_t)(col0 + oc[r]) * NZ + oi] = lam[r];
-    // ---- flush: bias gradients and the loss sum into this workgroup's slab row (weight gradients come from the dW GEMM)
-    FC_BARRIER();
-    float* out = slab + (size_t)blockIdx.x * (go.n_params + 8);
-    float* scr = fc_smem;                                            // [4][NZ] + [4]
-    {
-        float s3 = 0.0f;
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) s3 += db3[r];              // this thread's columns, level oi
-        if (NZ == 32) s3 += __shfl_down(s3, 32);                     // the wave's second column group
-        if (lane < NZ) scr[w * NZ + lane] = s3;
-        float v = sumsq;
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-        if (lane == 0) scr[4 * NZ + w] = v;
-    }
-    FC_BARRIER();
-    if (tid < S::NO) out[go.b[2] + tid] = (scr[tid] + scr[NZ + tid]) + (scr[2 * NZ + tid] + scr[3 * NZ + tid]);
-    if (tid == 0) out[go.n_params + 2] = (scr[4 * NZ] + scr[4 * NZ + 1]) + (scr[4 * NZ + 2] + scr[4 * NZ + 3]);
-    if (tid < S::H) {
-        out[go.b[0] + tid] = db1;
-        out[go.b[1] + tid] = db2;
-    }
+    constexpr bool CONV = false;
+    const FcConv cv = FcConv();
+#include "fc_adjoint_body.inc"
+}
+template <int NZ, bool CA, bool RKC, bool SPLIT>
+__global__ void __launch_bounds__(256, 2)
+fc_adjoint_conv_kernel(const void* __restrict__ imgb, const float* __restrict__ save_times, int n_save, int iv_begin, int iv_end, int substeps, float CN,
+                       float caKN, int nst, const float* __restrict__ rkc, const float* __restrict__ sol, const float* __restrict__ truth,
+                       float* __restrict__ dwtape, const u32* __restrict__ masks, const u64* __restrict__ swtape, float w_loss, float* __restrict__ lam_io,
+                       float* __restrict__ slab, FcGrad go, int n_col, FcConv cv) {
+    constexpr int CW = 16;
+    constexpr bool ENS = false, CONV = true;
+    const FcEns en = FcEns();
+#include "fc_adjoint_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -859,6 +463,17 @@ hipError_t fc_set_kernel_attributes() {
     FC_FOR_EACH_ADJ16(FC_ATTR_AE)
 #undef FC_ATTR_FE
 #undef FC_ATTR_AE
+    // ... and the conv network's entry points (16-column tiles, both arithmetics)
+#define FC_ATTR_FC(N, W, T, C, K)                                                                                                                                        \
+    if ((e = hipFuncSetAttribute((const void*)(fc_forward_conv_kernel<N, T, C, K, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_fwd<N, W>())) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)(fc_forward_conv_kernel<N, T, C, K, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_fwd<N, W>())) != hipSuccess) return e;
+#define FC_ATTR_AC(N, W, C, K)                                                                                                                                           \
+    if ((e = hipFuncSetAttribute((const void*)(fc_adjoint_conv_kernel<N, C, K, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_adj<N, W>())) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)(fc_adjoint_conv_kernel<N, C, K, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_adj<N, W>())) != hipSuccess) return e;
+    FC_FOR_EACH_FWD16(FC_ATTR_FC)
+    FC_FOR_EACH_ADJ16(FC_ATTR_AC)
+#undef FC_ATTR_FC
+#undef FC_ATTR_AC
 #undef FC_ATTR_F
 #undef FC_ATTR_A
 #undef FC_ATTR_I
@@ -916,8 +531,29 @@ hipError_t fc_launch_infer(const DevModel& m, int cw, const float* imgf, const f
 
 hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const unsigned int* simgf, const float* bias, const float* x0, size_t x0_stride,
                              const float* bcs, const float* save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps, float* sol,
-                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens) {
+                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens, const FcConv* conv) {
     if (n_col < 1 || iv_begin < 0 || iv_end > n_save - 1 || iv_begin >= iv_end || tape_iv0 < iv_begin || tape_iv0 >= iv_end) return hipErrorInvalidValue;
+    if (conv) {                                             // the --conv network: the CONV entry points of the 16-column kernels, either arithmetic
+        if (ens || cw != 16 || conv->c < 2 || conv->c > FC_CONV_MAX || !conv->wb || (dwtape && !conv->ctape)) return hipErrorInvalidValue;
+        const dim3 grid((n_col + 15) / 16), block(256);
+        const float CN = m.C_fc * (float)m.Nz, caKN = m.ca_K * (float)m.Nz;
+        const bool tape = dwtape != nullptr, ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE, rk = m.rkc != nullptr, split = simgf != nullptr;
+        if ((tape && (!masks || (ca && !swtape))) || (rk && !ca)) return hipErrorInvalidValue;
+        bool launched = false;
+#define FC_FWDC(N, W, T, C, K)                                                                                                                       \
+    if (!launched && m.Nz == N && tape == T && ca == C && rk == K) {                                                                                 \
+        if (split)                                                                                                                                   \
+            hipLaunchKernelGGL((fc_forward_conv_kernel<N, T, C, K, true>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)simgf, bias, x0, x0_stride, bcs,       \
+                               save_times, n_save, iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, *conv); \
+        else                                                                                                                                         \
+            hipLaunchKernelGGL((fc_forward_conv_kernel<N, T, C, K, false>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)imgf, bias, x0, x0_stride, bcs,       \
+                               save_times, n_save, iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, *conv); \
+        launched = true;                                                                                                                             \
+    }
+        FC_FOR_EACH_FWD16(FC_FWDC)
+#undef FC_FWDC
+        return launched ? hipGetLastError() : hipErrorInvalidValue;
+    }
     if (ens) {                                              // all models in one launch: the ENS instantiations of the 16-column kernels, grid.y = model
         if (cw != 16 || ens->n_models < 1 || ens->n_models > 65535) return hipErrorInvalidValue;
         const dim3 grid((n_col + 15) / 16, ens->n_models), block(256);
@@ -974,9 +610,33 @@ hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const
 
 hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const unsigned int* simgb, const float* save_times, int n_save, int iv_begin, int iv_end,
                              int substeps, const float* sol, const float* truth, float* dwtape, const unsigned int* masks, const unsigned long long* swtape,
-                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens) {
+                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens, const FcConv* conv) {
     if (n_col < 1 || !dwtape || !masks || iv_begin < 0 || iv_end > n_save - 1 || iv_begin >= iv_end) return hipErrorInvalidValue;
     if ((iv_begin > 0 || iv_end < n_save - 1) && !lam_io) return hipErrorInvalidValue;
+    if (conv) {
+        if (ens || cw != 16 || conv->c < 2 || conv->c > FC_CONV_MAX || !conv->wb || !conv->ctape) return hipErrorInvalidValue;
+        const dim3 grid((n_col + 15) / 16), block(256);
+        const float CN = m.C_fc * (float)m.Nz, caKN = m.ca_K * (float)m.Nz;
+        const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE, rk = m.rkc != nullptr, split = simgb != nullptr;
+        if ((ca && !swtape) || (rk && !ca)) return hipErrorInvalidValue;
+        FcGrad go;
+        for (int l = 0; l < 3; l++) go.b[l] = m.b_off[l];
+        go.n_params = m.n_params;
+        bool launched = false;
+#define FC_ADJC(N, W, C, K)                                                                                                                          \
+    if (!launched && m.Nz == N && ca == C && rk == K) {                                                                                              \
+        if (split)                                                                                                                                   \
+            hipLaunchKernelGGL((fc_adjoint_conv_kernel<N, C, K, true>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)simgb, save_times, n_save, iv_begin,      \
+                               iv_end, substeps, CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, *conv); \
+        else                                                                                                                                         \
+            hipLaunchKernelGGL((fc_adjoint_conv_kernel<N, C, K, false>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)imgb, save_times, n_save, iv_begin,      \
+                               iv_end, substeps, CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, *conv); \
+        launched = true;                                                                                                                             \
+    }
+        FC_FOR_EACH_ADJ16(FC_ADJC)
+#undef FC_ADJC
+        return launched ? hipGetLastError() : hipErrorInvalidValue;
+    }
     if (ens) {
         if (cw != 16 || ens->n_models < 1 || ens->n_models > 65535) return hipErrorInvalidValue;
         const dim3 grid((n_col + 15) / 16, ens->n_models), block(256);

@@ -23,20 +23,67 @@ from .flux_compat import ADAM
 from .nde import ColumnNDE
 
 
+# ---- the `--conv c` network (train_free_convection_nde.jl:50-53, 110-122): pure NumPy, no GPU ------------------------------------------------------
+#   Chain(reshape, Conv((c, 1), 1 => 1, relu), reshape, Dense(M, 4Nz, relu), Dense(4Nz, 4Nz, relu), Dense(4Nz, Nz-1)),   M = Nz - c + 1
+#   θ = [w (c); b (1); vec(W1) (4Nz x M, column-major); b1; vec(W2); b2; vec(W3); b3]      (Flux.params order)
+#   y[i] = relu(b + Σ_k w[k] x[i + c - k])  (NNlib's conv flips the kernel) = relu(b + Σ_j T[i, j] x[j]) with the Toeplitz T[i, i + d] = w[c - d]
+
+def conv_n_params(Nz: int, c: int) -> int:
+    M = Nz - c + 1
+    return c + 1 + 4 * Nz * M + 4 * Nz + 16 * Nz * Nz + 4 * Nz + 4 * Nz * (Nz - 1) + Nz - 1
+
+
+def conv_dense_layer_sizes(Nz: int, c: int):
+    """The four-layer dense network `conv_to_dense` writes: relu, relu, relu, identity."""
+    return (Nz, Nz - c + 1, 4 * Nz, 4 * Nz, Nz - 1)
+
+
+def conv_to_dense(theta, Nz: int, c: int):
+    """θ of the `--conv c` network -> θ of the equivalent four-layer dense network `conv_dense_layer_sizes(Nz, c)` whose first layer is the
+    M x Nz Toeplitz matrix of the filter with the bias b on every row (Flux.destructure order: vec(W0) column-major, b0, then the rest)."""
+    theta = np.asarray(theta)
+    if theta.shape != (conv_n_params(Nz, c),):
+        raise ValueError("theta: expected %d entries for Nz = %d, conv = %d, got %s" % (conv_n_params(Nz, c), Nz, c, theta.shape))
+    M = Nz - c + 1
+    W0 = np.zeros((M, Nz), dtype=theta.dtype)
+    i = np.arange(M)
+    for d in range(c):
+        W0[i, i + d] = theta[c - 1 - d]
+    b0 = np.full(M, theta[c], dtype=theta.dtype)
+    return np.concatenate([W0.reshape(-1, order="F"), b0, theta[c + 1:]])
+
+
+def conv_grad_from_dense(g, Nz: int, c: int):
+    """The gradient with respect to the dense θ of `conv_to_dense` folded back onto the `--conv` θ: ∂W0 summed along its diagonals, ∂b0 over its
+    entries, the rest appended."""
+    g = np.asarray(g)
+    M = Nz - c + 1
+    if g.shape != (M * Nz + M + conv_n_params(Nz, c) - (c + 1),):
+        raise ValueError("g: expected the gradient of the %s network, got %s" % (conv_dense_layer_sizes(Nz, c), g.shape))
+    G0 = g[:M * Nz].reshape((M, Nz), order="F")
+    i = np.arange(M)
+    gw = np.array([G0[i, i + (c - 1 - k)].sum() for k in range(c)], dtype=g.dtype)
+    gb = np.array([g[M * Nz:M * Nz + M].sum()], dtype=g.dtype)
+    return np.concatenate([gw, gb, g[M * Nz + M:]])
+
+
 class FreeConvectionNDE:
     """One NDE per simulation in the reference (`ndes[id]`); here all simulations are columns of one handle."""
 
     def __init__(self, cfg: NDEConfig, T0, nde_params, true_sols=None, device: int = 0,
-                 causal_penalty: Optional[Callable] = None):
+                 causal_penalty: Optional[Callable] = None, conv: int = 0, matrix_arithmetic="bf16x3_exact"):
         """`causal_penalty`: the optional term of `nde_loss` (training.jl:44,57-58: `Flux.mse(...) + causal_penalty(NN)`), a
-        function of the weights alone; here a callable θ -> (value, ∂value/∂θ) since there is no Zygote to differentiate it."""
+        function of the weights alone; here a callable θ -> (value, ∂value/∂θ) since there is no Zygote to differentiate it.
+        `conv` = c > 1: the driver's `--conv c` network; cfg stays the plain (Nz, 4Nz, 4Nz, Nz-1) configuration and the weights are the
+        `conv_n_params(Nz, c)` entries of Flux.params(NN).  solve_nde, nde_loss, nde_loss_and_grad and both training loops work unchanged."""
         if cfg.model not in (FREE_CONVECTION, CONVECTIVE_ADJUSTMENT_NDE):
             raise ValueError("need a free-convection config")
         self.cfg = cfg
+        self.conv = int(conv)
         self.causal_penalty = causal_penalty
         T0 = np.ascontiguousarray(T0, dtype=np.float32)
         self.n_simulations = T0.shape[0]
-        self.engine = ColumnNDE(cfg, self.n_simulations, device=device)
+        self.engine = ColumnNDE(cfg, self.n_simulations, device=device, conv=self.conv, matrix_arithmetic=matrix_arithmetic)
         self.engine.set_problem(T0, np.ascontiguousarray(nde_params, dtype=np.float32), true_sols)
 
     def dTdt(self, T, p, t=0.0):

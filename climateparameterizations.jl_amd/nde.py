@@ -164,20 +164,30 @@ def rkc_stages(cfg: NDEConfig) -> int:
 
 
 class ColumnNDE:
-    def __init__(self, cfg: NDEConfig, n_columns: int, device: int = 0, engine: int = 0, matrix_arithmetic="bf16x3_exact"):
+    def __init__(self, cfg: NDEConfig, n_columns: int, device: int = 0, engine: int = 0, matrix_arithmetic="bf16x3_exact", conv: int = 0):
         """matrix_arithmetic: "bf16x3_exact" (default: f32 products as six bf16 MFMA products of exact three-way operand splits, f32 accumulation,
-        wherever the engine has a split kernel) or "f32_mfma" (v_mfma_f32_* throughout) — include/colnde.h COLNDE_MATRIX_*."""
+        wherever the engine has a split kernel) or "f32_mfma" (v_mfma_f32_* throughout) — include/colnde.h COLNDE_MATRIX_*.
+        conv = c > 1: the free-convection driver's `--conv c` network (`colnde_create_conv`) — cfg is the plain fc32 configuration, the first
+        Dense takes Nz - c + 1 inputs behind a c-tap filter, and the weight vector has `free_convection.conv_n_params(Nz, c)` entries."""
         cfg.validate()
         self.cfg = cfg
         self.n_columns = int(n_columns)
         self.device = int(device)
+        self.conv = int(conv)
         self._h = ctypes.c_void_p()
         L = _lib.lib()
         c, keep = to_c_config(cfg, n_columns, device, engine, matrix_arithmetic)
-        _lib.check(L.colnde_create(ctypes.byref(c), ctypes.byref(self._h)))
+        if self.conv:
+            _lib.check(L.colnde_create_conv(ctypes.byref(c), self.conv, ctypes.byref(self._h)))
+        else:
+            _lib.check(L.colnde_create(ctypes.byref(c), ctypes.byref(self._h)))
         self._L = L
         self.n_params = L.colnde_n_params(self._h)
-        assert self.n_params == cfg.n_params
+        if self.conv:
+            assert L.colnde_conv_filter(self._h) == self.conv
+            assert self.n_params == self.conv + 1 + cfg.n_params - 4 * cfg.Nz * (self.conv - 1)
+        else:
+            assert self.n_params == cfg.n_params
         self.n_columns_total = self.n_columns
         self.engine = L.colnde_engine(self._h)      # engine actually selected (ENGINE_TILE16 or ENGINE_REGTILE)
 
@@ -234,7 +244,9 @@ class ColumnNDE:
         _lib.check(self._L.colnde_plan(self._h, info))
         return dict(engine=info[0], block_columns=info[1], n_blocks=info[2], z1_taped=bool(info[3]) and info[0] == ENGINE_REGTILE,
                     time_segments=info[3] if info[0] == ENGINE_FC32 else 0,
-                    dw_taped=bool(info[4]), dw_slices=info[5], split_forward=bool(info[6] & 1), split_adjoint=bool(info[6] & 2), split_rich_tape=bool(info[6] & 4),
+                    conv=info[6] if info[0] == ENGINE_FC32 else 0,       # fc32: the filter length of a conv handle; tile16: the net-split bits
+                    dw_taped=bool(info[4]), dw_slices=info[5], split_forward=bool(info[6] & 1) and info[0] != ENGINE_FC32,
+                    split_adjoint=bool(info[6] & 2) and info[0] != ENGINE_FC32, split_rich_tape=bool(info[6] & 4) and info[0] != ENGINE_FC32,
                     approximate_gradient=bool(info[7] & 1),
                     # which kernel families run the exact three-way bf16 split (the others: f32 MFMA)
                     bf16x3_forward=bool(info[7] & 2), bf16x3_adjoint=bool(info[7] & 4), bf16x3_dw=bool(info[7] & 8),

@@ -140,6 +140,30 @@ def free_convection_problem(n_columns: int, Nz: int = 32, n_save: int = 129, sub
     return ColumnProblem(cfg, x0, bcs.astype(np.float32), w, w_truth)
 
 
+def free_convection_conv_problem(n_columns: int, conv: int, Nz: int = 32, n_save: int = 129, substeps: int = 4, convective_adjustment: bool = False,
+                                 seed: int = SEED, weight_divisor: float = 1e2, t_end: float = 1.0) -> ColumnProblem:
+    """The `--conv c` network of train_free_convection_nde.jl:110-122 on `free_convection_problem`'s columns: cfg is the plain fc32 configuration
+    (what `ColumnNDE(cfg, n, conv=c)` takes), the weights are θ = [w (c); b; W1 (4Nz x M); b1; W2; b2; W3; b3], M = Nz - c + 1.  Filter taps
+    U(-1, 1) sqrt(6 / (c + 1)), b = 0.05 (both relu branches of the filter are exercised); the dense layers from `make_weights`."""
+    from dataclasses import replace
+    p = free_convection_problem(n_columns, Nz=Nz, n_save=n_save, substeps=substeps, convective_adjustment=convective_adjustment, seed=seed,
+                                weight_divisor=weight_divisor, t_end=t_end)
+    M = Nz - conv + 1
+    dense_cfg = replace(p.cfg, layer_sizes=(M, 4 * Nz, 4 * Nz, Nz - 1))
+    r = _rng(seed, 7)
+    filt = (r.uniform(-1.0, 1.0, size=conv) * np.sqrt(6.0 / (conv + 1))).astype(np.float32)
+
+    def theta(rw):
+        return np.concatenate([filt, np.float32([0.05]), make_weights(rw, dense_cfg, weight_divisor)]).astype(np.float32)
+
+    rw = _rng(seed, 8)
+    w = theta(rw)
+    w_truth = w.copy()
+    w_truth[conv + 1:] = perturb_weights(rw, w[conv + 1:])
+    w_truth[:conv] = (filt * np.float32(0.8)).astype(np.float32)
+    return ColumnProblem(p.cfg, p.x0, p.bcs, w, w_truth)
+
+
 def inference_problem(nx: int, ny: int, Nz: int = 32, seed: int = SEED):
     """double_gyre_nn.jl:149-168 — a T field of nx×ny columns, a relaxation surface flux, the wT MLP 32-128-128-31."""
     cfg = NDEConfig(model=FREE_CONVECTION, Nz=Nz, layer_sizes=(Nz, 4 * Nz, 4 * Nz, Nz - 1),

@@ -436,7 +436,7 @@ int  colnde_allreduce_result_dev(colnde_handle* h, colnde_comm* comm, float* d_o
 /* How the handle runs its gradient path (filled in by the first colnde_loss_grad[_dev]; zeros before that):
  * info[0] engine (COLNDE_ENGINE_*), [1] columns per block of the gradient path (the tapes hold one block), [2] number of blocks, [3] regtile: layer-1
  * pre-activations taped (1) or recomputed (0); fc32: number of time segments the tapes are cut into (0: they hold the whole axis), [4] tile16: weight gradients taped (1) or accumulated in registers (0),
- * [5] tile16 taped mode: K-slices of the dW GEMM, [6] net-split kernels of the latency points (per 16-column tile one wavefront per flux net
+ * [5] tile16 taped mode: K-slices of the dW GEMM, [6] fc32: the filter length c of a conv handle (colnde_create_conv; 0 otherwise); tile16: net-split kernels of the latency points (per 16-column tile one wavefront per flux net
  * plus a helper wavefront): bit 0 = forward solve, bit 1 = adjoint, bit 2 = with the rich tape (activations, their derivatives and the physics-pullback
  * coefficients taped by the forward kernel: blocks of at most 2,048 columns), [7] bit 0 = the gradient is the one-switch-pattern
  * RKC2 pullback, an approximation of the discrete adjoint (see COLNDE_STEPPER_RKC2); 0 = exact discrete adjoint of the stepper;
@@ -536,6 +536,31 @@ int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weights, const fl
         const float* top_flux, const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params,
         int convective_adjustment, float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out,
         float* uw, float* vw, float* wT, int n_columns);
+
+/* ---- the free-convection driver's --conv network (train_free_convection_nde.jl:50-53, 110-122) ----------------------------------------------------------
+ * With --conv c > 1 the reference trains
+ *     Chain(reshape, Conv((c, 1), 1 => 1, relu), reshape, Dense(Nz-c+1, 4Nz, relu), Dense(4Nz, 4Nz, relu), Dense(4Nz, Nz-1))
+ * A conv handle runs FreeConvectionNDE (RK4) and ConvectiveAdjustmentNDE (RK4, RKC2) with that network on the fc32 engine's 16-column kernels, Nz = 32 | 64,
+ * either matrix arithmetic.  The filter is applied inside the kernels where the stage input is written to LDS; the dense chain is the plain network's with
+ * W1 padded by zero columns, so the operand images, the weight-gradient GEMM and the reductions are unchanged.
+ *   Arithmetic (x the stage input, level 1 = bottom; M = Nz - c + 1; NNlib's conv flips the kernel):
+ *       y[i] = relu(b + sum_{k=1..c} w[k] x[i + c - k]),  i = 1..M;     y feeds Dense(M, 4Nz, relu); the physics reads x.
+ *   Parameter vector (Flux.params order; colnde_n_params):
+ *       theta = [w (c); b (1); vec(W1) (4Nz x M, column-major); b1; vec(W2); b2; vec(W3); b3]
+ * cfg is the PLAIN fc32 configuration — layer_sizes = (Nz, 4Nz, 4Nz, Nz-1), relu, relu, identity — and conv_filter = c says that the first Dense takes M
+ * inputs behind a c-tap filter.  Calls that work on a conv handle: set_problem[_dev], forward[_dev], loss[_dev], loss_grad[_dev] (n_params gradient floats,
+ * the filter's c + 1 first, then the 8 loss slots), loss_per_tstep[_dev], adam_step_dev, set_stream, set_substeps / substeps, set_matrix_arithmetic /
+ * matrix_arithmetic, n_params, engine, conv_filter, plan (info[6] = c), describe ("conv=c"), profiling and kernel times (the filter-gradient kernel is timed
+ * with the dW GEMM, slot 5), destroy; the array utilities that read no network (coarse_grain, zscore_stats, scale, convective_adjustment, implicit_diffusion,
+ * mpp_diagnose_flux).  Every other call refuses a conv handle with a sentence naming the call: rhs, flux, error_estimate, choose_substeps, infer_*, the embedded
+ * steps and diagnoses, pretrain_flux, set_global_columns and allreduce_result (multi-GPU results), the ensemble and closure calls.
+ * Refused here, before any device work, each with its reason: conv_filter outside 2..8, a wind-mixing model, another network shape or Nz, an engine other than
+ * AUTO or FC32, FreeConvectionNDE under RKC2, substeps = 0, substeps < colnde_min_substeps, more than 4,096 columns, COLNDE_FC=0, COLNDE_FC_CW=32,
+ * COLNDE_FC_BLOCK.  Then "no HIP device ... no CPU fallback".  The tapes are planned by the first colnde_loss_grad (colnde_set_substeps works until then); tapes
+ * that do not fit are refused there with the bytes needed. */
+int colnde_create_conv(const colnde_config* cfg, int conv_filter, colnde_handle** out);
+/* c of a conv handle, 0 for every other handle (-1: null) */
+int colnde_conv_filter(const colnde_handle* h);
 
 /* ---- closure-only model: fitting the five Pacanowski-Philander constants before any network is trained ------------------------------------------------
  * optimise_modified_pacanowski_philander (wind_mixing/src/diffusivity_parameter_optimisation.jl:35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl

@@ -542,6 +542,25 @@ function FreeConvectionEnsembleHandle(cfg::Config, save_times::Vector{Float32}, 
     finalizer(x -> ccall((:colnde_destroy, libcolnde), Cvoid, (Ptr{Cvoid},), x.ptr), h)
 end
 
+"The free-convection driver's `--conv c` network (train_free_convection_nde.jl:110-122: Conv((c, 1), 1 => 1, relu) in front of Dense(Nz-c+1, 4Nz, relu),
+Dense(4Nz, 4Nz, relu), Dense(4Nz, Nz-1)) on the fc32 kernels.  `cfg` is the PLAIN fc32 configuration (layer sizes Nz, 4Nz, 4Nz, Nz-1); the weight vector
+is `vcat(vec.(Flux.params(NN))...)` of the conv chain: [w (c); b; vec(W1); b1; vec(W2); b2; vec(W3); b3], `h.n_params` entries.  Works with
+set_problem!, forward!, loss, loss_grad!, loss_per_tstep and the device ADAM step; every other call refuses the handle by name."
+function ConvHandle(cfg::Config, save_times::Vector{Float32}, conv::Integer)
+    cfg.n_save = length(save_times)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve save_times begin
+        cfg.save_times = pointer(save_times)
+        check(ccall((:colnde_create_conv, libcolnde), Cint, (Ref{Config}, Cint, Ref{Ptr{Cvoid}}), cfg, conv, out))
+    end
+    h = Handle(out[], ccall((:colnde_n_params, libcolnde), Cint, (Ptr{Cvoid},), out[]), cfg.Nz, cfg.n_save, cfg.n_columns, 1)
+    finalizer(x -> ccall((:colnde_destroy, libcolnde), Cvoid, (Ptr{Cvoid},), x.ptr), h)
+end
+const create_conv = ConvHandle
+
+"c of a conv handle, 0 for every other handle"
+conv_filter(h::Handle) = Int(ccall((:colnde_conv_filter, libcolnde), Cint, (Ptr{Cvoid},), h.ptr))
+
 "dout[n, c, k] = mean over the levels of (sol - truth)² per save point n, simulation c and model k, scaled units: Flux.mse(true, nde, agg = x -> mean(x, dims=1))
 of testing.jl:83 (plot_epoch_loss, animate_nde_loss); dsol is `ensemble_forward_dev!`'s output.  Device pointers, handle's stream."
 ensemble_column_loss_dev!(h::Handle, dsol::Ptr{Float32}, dout::Ptr{Float32}) =
