@@ -1,12 +1,5 @@
 // api_embed.hip — the embedding's part of the C ABI (include/colnde.h): inference, the steps either side of it, the wind-mixing and free-convection
 // embedded steps and the saved-state flux diagnoses.  Host code only; the kernels are column_ops.hip, engine_wm_infer.hip, engine_fc_embed.hip.
-#include <hip/hip_runtime.h>
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "api_internal.h"
 
 // ---- embedded inference --------------------------------------------------------------------------------
@@ -408,7 +401,7 @@ static int wm_ens_upload_mpp(colnde_handle* h, const float* params, bool step, f
         P[k] = mpp_params(p, step ? dt : dz * dz, dz, ca);            // (without a step c is not read: 1, as the single-model diagnosis passes it)
     }
     if (h->d_wm_ens_mpp && h->wm_ens_mpp_host.size() == K && !memcmp(h->wm_ens_mpp_host.data(), P.data(), K * sizeof(MppParams))) return 0;
-    if (!h->d_wm_ens_mpp) HIPCHK(hipMalloc((void**)&h->d_wm_ens_mpp, K * sizeof(MppParams)));
+    if (!h->d_wm_ens_mpp) HIPCHK(h->mem.alloc(&h->d_wm_ens_mpp, K));
     // (kernels in flight on the stream may still read the previous table: the copy is ordered on the stream and completed before returning)
     h->wm_ens_mpp_host.clear();
     HIPCHK(hipMemcpyAsync(h->d_wm_ens_mpp, P.data(), K * sizeof(MppParams), hipMemcpyHostToDevice, h->stream));
@@ -418,7 +411,7 @@ static int wm_ens_upload_mpp(colnde_handle* h, const float* params, bool step, f
 }
 
 static int wm_ens_grid_cap() {
-    const char* e = getenv("COLNDE_WM_ENS_GRID");      // test override: at most this many workgroups (several models per workgroup at small K)
+    const char* e = env_get(ENV_WM_ENS_GRID);      // test override: at most this many workgroups (several models per workgroup at small K)
     return e && *e ? std::max(0, atoi(e)) : 0;
 }
 
@@ -549,9 +542,9 @@ static int fce_check(colnde_handle* h, const char* fn, const void* const* ptrs, 
 static int fce_prepare(colnde_handle* h) {
     HIPCHK(hipSetDevice(h->device));
     if (h->fce_ready) return 0;
-    if (!h->d_fc_imgf) HIPCHK(hipMalloc((void**)&h->d_fc_imgf, fc_image_floats(h->m.Nz) * sizeof(float)));
-    if (!h->d_fc_imgb) HIPCHK(hipMalloc((void**)&h->d_fc_imgb, fc_image_floats(h->m.Nz) * sizeof(float)));
-    if (!h->d_fc_bias) HIPCHK(hipMalloc((void**)&h->d_fc_bias, fc_bias_floats(h->m.Nz) * sizeof(float)));
+    if (!h->d_fc_imgf) HIPCHK(h->mem.alloc(&h->d_fc_imgf, fc_image_floats(h->m.Nz)));
+    if (!h->d_fc_imgb) HIPCHK(h->mem.alloc(&h->d_fc_imgb, fc_image_floats(h->m.Nz)));
+    if (!h->d_fc_bias) HIPCHK(h->mem.alloc(&h->d_fc_bias, fc_bias_floats(h->m.Nz)));
     hipError_t e = fce_set_kernel_attributes();
     if (e != hipSuccess) return fail("hipFuncSetAttribute (fc_embed) failed: %s", hipGetErrorString(e));
     h->fce_ready = true;
@@ -584,7 +577,7 @@ extern "C" int colnde_fc_embedded_step_dev(colnde_handle* h, const float* d_weig
     // 65,536 columns (one lane per column sweeps while the other waves of the workgroup wait), so that is what this call issues — the same bits,
     // timed under slots 4 and 6.  With wT_faces the one launch beats the three it replaces at every size measured and is kept.
     // COLNDE_FC_EMBED_FUSED=1 forces the fused kernel (tools/fc_embed_rate.py measures it that way).
-    const char* ef = getenv("COLNDE_FC_EMBED_FUSED");
+    const char* ef = env_get(ENV_FC_EMBED_FUSED);
     if (!d_wT_faces && !(ef && atoi(ef) != 0)) {
         if (((uintptr_t)d_T | (uintptr_t)d_dz_wT | (uintptr_t)d_T_out) & 15) return fail("%s: T and the output arrays must be 16-byte aligned", __func__);
         if (colnde_infer_dz_wT_dev(h, d_weights, d_T, d_top_flux, Lz, d_dz_wT, n_columns)) return 1;

@@ -1,0 +1,534 @@
+// api_ensemble.hip — handles built on colnde_create: wind-mixing and free-convection ensembles, the conv network; the colnde_ensemble_* entry points.
+#include "api_internal.h"
+#include "tape_plan.h"
+
+// ---- ensembles: K models of one architecture side by side (colnde_create_ensemble) ---------------------------------------------------------------
+// The reference's sweep (wind_mixing/train_NDE_args.jl: activation, ADAM rate and Pacanowski-Philander constants per process) trains many small
+// models of ONE architecture on the same simulations.  Here every kernel of a training iteration runs once for all K models with the model index in
+// blockIdx.y: the net-split pair (rt16sh_*), the weight packers, tile16's dW GEMM, the loss and gradient reductions and the ADAM step.  A model owns
+// its packed weights, solution, tapes and slab rows (RtEns strides) and its closure constants (RtPhys); x0, bcs and truth are shared.
+
+// the configuration of model k: cfg with row k of physics ([K][5]: nu0, nu_minus, dRi, Ric, Pr)
+colnde_config model_config(const colnde_config* cfg, const float* physics, int k) {
+    colnde_config c = *cfg;
+    if (physics) {
+        const float* r = physics + (size_t)5 * k;
+        c.nu0 = r[0]; c.nu_minus = r[1]; c.dRi = r[2]; c.Ric = r[3]; c.Pr = r[4];
+    }
+    return c;
+}
+
+// The shared sub-step count against every model's stability bound; RKC2 with automatic stages: the largest stage count any model needs.
+// *min_sub / *stages: the ensemble's bound and stage count (stages = 0 for RK4).
+static int ens_stability(const colnde_config* cfg, int K, const float* physics, int* min_sub, int* stages) {
+    *min_sub = 1;
+    *stages = 0;
+    for (int k = 0; k < K; k++) {
+        const colnde_config c = model_config(cfg, physics, k);
+        if (physics) {
+            const float* r = physics + (size_t)5 * k;
+            for (int q = 0; q < 5; q++)
+                if (!std::isfinite(r[q])) return fail("physics[%d][%d] = %g is not finite", k, q, r[q]);
+            if (!(c.dRi > 0.0f) || !(c.Pr > 0.0f)) return fail("physics[%d]: dRi = %g and Pr = %g must be > 0", k, c.dRi, c.Pr);
+        }
+        const int ms = colnde_min_substeps(&c);
+        if (ms < 0) return 1;
+        *min_sub = std::max(*min_sub, ms);
+        if (cfg->stepper == COLNDE_STEPPER_RKC2 && !cfg->rkc_stages) *stages = std::max(*stages, colnde_rkc_stages(&c));
+        if (cfg->substeps < ms && !allow_unstable())
+            return fail("model %d (nu0 = %g, nu_minus = %g, Pr = %g) needs substeps >= %d for a stable step (colnde_min_substeps; lambda = -%.4g), but the "
+                        "ensemble shares substeps = %d (COLNDE_ALLOW_UNSTABLE_DT=1 overrides)", k, c.nu0, c.nu_minus, c.Pr, ms, stiff_lambda(&c), cfg->substeps);
+    }
+    return 0;
+}
+
+static int ens_upload_physics(colnde_handle* h, const float* physics) {
+    std::vector<RtPhys> ph((size_t)h->n_models);
+    for (int k = 0; k < h->n_models; k++) {
+        const colnde_config c = model_config(&h->cfg, physics, k);
+        ph[k] = closure_constants(c.nu0, c.nu_minus, c.dRi, c.Ric, c.Pr);
+    }
+    // (kernels in flight on the stream may still read the previous table: the copy is ordered on the stream and completed before returning)
+    HIPCHK(hipMemcpyAsync(h->d_phys, ph.data(), ph.size() * sizeof(RtPhys), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->phys_host.swap(ph);
+    if (physics) h->phys_raw.assign(physics, physics + (size_t)5 * h->n_models);
+    else h->phys_raw.clear();
+    return 0;
+}
+
+// The tapes of all K models, planned once at creation: tile16's taped-dW formats for ONE block of all columns per model (the net-split pair has no
+// column-block loop across models), the rich tape while the K models' 16-column tiles number at most 128 (2,048 columns in flight: the single
+// handle's crossover, which counts concurrent tiles whoever owns them).  Refused with the bytes it needs when it does not fit.
+static int ens_plan_tapes(colnde_handle* h) {
+    const DevModel& m = h->m;
+    const int K = h->n_models;
+    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
+    const size_t n_rec = (size_t)h->n_tiles * n_steps * m.nst;
+    const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
+    std::vector<DwMacro> mac;
+    build_dw_macros(h, n_rec, mac);                          // the slice count a single handle of this size plans: same reduction order
+    h->t16_rows = h->n_tiles + h->dw_slices;
+    const size_t f_tape = n_rec * CT * m.ns, f_dw = n_rec * CT * R, f_rich = n_rec * rt_split_rich_record_floats(),
+                 f_plain = n_rec * CT * t16_ztape_col_floats(m), f_slab = (size_t)h->t16_rows * P8,
+                 f_sol = (size_t)h->n_col * h->cfg.n_save * m.ns, f_img = RT_IMG_STRIDE;
+    const char* er = env_get(ENV_T16_SPLIT_RICH);
+    const bool forced = er != nullptr;
+    bool rich = forced ? atoi(er) != 0 : (size_t)K * h->n_tiles <= 128;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t budget = hbm_budget(free_b, ((size_t)3 << 30) + (size_t)K * (P8 * 2 + 256 * 8) * sizeof(float));
+    auto per_model = [&](bool r) { return (f_tape + f_dw + (r ? f_rich : f_plain) + f_slab + f_sol + f_img) * sizeof(float); };
+    if (rich && !forced && (size_t)K * per_model(true) > budget) rich = false;       // the automatic rich tape gives way to the plain one, as for one handle
+    const size_t need = per_model(rich);
+    if ((size_t)K * need > budget)
+        return fail("an ensemble of %d models needs %zu bytes of device memory for its tapes, slab rows and solutions (%zu per model, %s tape, "
+                    "%d substeps x %d stages x %d save intervals); %zu bytes are free (3 GB kept in reserve): use fewer models per handle",
+                    K, (size_t)K * need, need, rich ? "rich" : "plain", h->cfg.substeps, m.nst, h->cfg.n_save - 1, free_b);
+    const size_t f_z = rich ? f_rich : f_plain;
+    const size_t mark = h->mem.mark();
+    hipError_t e = h->mem.alloc(&h->d_dwtape, (size_t)K * f_dw);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_tape, (size_t)K * f_tape);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_t16_ztape, (size_t)K * f_z);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_slab, (size_t)K * f_slab);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
+    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h->mem.rollback(mark);
+        return fail("allocating the ensemble's tapes (%zu bytes, %zu per model) failed: %s", (size_t)K * need, need, hipGetErrorString(e));
+    }
+    h->t16_dwtape = 1;
+    h->t16_block = h->n_tiles * CT;
+    h->t16_nblocks = 1;
+    h->split_rich = rich;
+    h->ens.wimg = f_img;
+    h->ens.sol = f_sol;
+    h->ens.tape = f_tape;
+    h->ens.ztape = f_z;
+    h->ens.dwtape = f_dw;
+    h->ens.slab = f_slab;
+    h->ens.n_models = K;
+    h->ens.phys = h->d_phys;
+    h->ens_model_bytes = need;
+    return 0;
+}
+
+extern "C" int colnde_create_ensemble(const colnde_config* cfg, int n_models, const float* physics, colnde_handle** out) {
+    if (!out) return fail("null out pointer");
+    *out = nullptr;
+    if (validate(cfg)) return 1;
+    if (n_models < 1 || n_models > 65535) return fail("n_models = %d outside 1..65535", n_models);
+    // only the configurations on which AUTO runs the four-wave net-split pair: those kernels carry the model index
+    if (cfg->model != COLNDE_MODEL_WIND_MIXING)
+        return fail("ensembles cover the wind-mixing NDE on the net-split kernels: the free-convection models (fc32 / tile16) run one handle per model");
+    if (cfg->inplace_variant) return fail("ensembles train on the training RHS: inplace_variant (the NDE! evaluation RHS) is not supported");
+    if (cfg->engine != COLNDE_ENGINE_AUTO)
+        return fail("ensembles run the net-split kernels engine AUTO selects: engine forced to %d is not supported (those engines have no model index)", cfg->engine);
+    if (cfg->substeps == 0)
+        return fail("substeps = 0 (chosen from reltol by the first solve) is not supported: the models share one sub-step count, and the tapes are sized at "
+                    "creation — choose it with a single handle (colnde_choose_substeps) and pass it");
+    if (cfg->n_columns > 8192)
+        return fail("%d columns per model: ensembles cover the net-split range (at most 8,192 columns per model); above it regtile runs one handle per model",
+                    cfg->n_columns);
+    {
+        DevModel dm;
+        PackInfo pk;
+        build_model(cfg, &dm, &pk);
+        if (!rt_supported(dm))
+            return fail("ensembles cover the net-split shape only (Nz = 32, three 96-50-20-31 nets, one hidden activation, training RHS, no smoothing): "
+                        "wide networks and other architectures run one handle per model");
+    }
+    if (physics && !cfg->modified_pacanowski_philander)
+        return fail("a physics array needs modified_pacanowski_philander = 1: without the Richardson-number closure the five constants are unused (pass NULL)");
+    // the environment switches that send a single handle down paths without a model index
+    for (EnvSwitch sw : {ENV_T16_FWD_HELPER, ENV_T16_ADJ_HELPER, ENV_T16_FWD_SPLIT, ENV_T16_ADJ_SPLIT, ENV_T16_ZTAPE, ENV_T16_DWTAPE}) {
+        const char* e = env_get(sw);
+        if (e && *e && atoi(e) == 0)
+            return fail("%s=0 selects kernels without a model index (the three-wave or tile16 kernels, or no delta / pre-activation tape): ensembles refuse it", env_name(sw));
+    }
+    if (env_get(ENV_T16_BLOCK)) return fail("COLNDE_T16_BLOCK: ensembles hold one block of columns per model (the column-block loop has no model index)");
+    int min_sub = 1, stages = 0;
+    if (ens_stability(cfg, n_models, physics, &min_sub, &stages)) return 1;
+    colnde_handle* h = nullptr;
+    if (colnde_create(cfg, &h)) return 1;
+    if (h->use_rt || h->use_fc || h->ag_rows || !h->fwd_split || !h->adj_split || !h->fwd_helper || !h->adj_helper) {
+        colnde_destroy(h);
+        return fail("this configuration does not run the four-wave net-split pair under engine AUTO: ensembles refuse it");
+    }
+    h->ensemble = true;
+    h->n_models = n_models;
+    h->min_substeps = min_sub;
+    if (stages > 0 && stages != h->m.nst) {
+        h->ens_rkc_stages = stages;
+        if (refresh_rkc(h)) { colnde_destroy(h); return 1; }
+    } else if (stages > 0) {
+        h->ens_rkc_stages = stages;
+    }
+    const size_t K = (size_t)n_models, P = (size_t)h->m.n_params;
+    DevPool& mem = h->mem;
+    if (mem.resize(&h->d_w, K * P) || mem.resize(&h->d_out, K * (P + 8)) || mem.resize(&h->d_partial, K * 256 * 8) ||
+        mem.resize(&h->d_sol, K * h->n_col * h->cfg.n_save * h->m.ns) || mem.resize(&h->d_wimg, K * RT_IMG_STRIDE) || mem.alloc(&h->d_phys, K)) {
+        colnde_destroy(h);
+        return fail("allocating the ensemble's per-model buffers (%d models) failed", n_models);
+    }
+    if (ens_upload_physics(h, physics) || ens_plan_tapes(h)) { colnde_destroy(h); return 1; }
+    *out = h;
+    return 0;
+}
+
+extern "C" int colnde_n_models(const colnde_handle* h) { return h ? h->n_models : -1; }
+
+// ---- free-convection ensembles (colnde_create_fc_ensemble) ------------------------------------------------------------------------------------------
+// The reference trains the free-convection NDE on 3 to 9 simulations (train_free_convection_nde.jl, --training-simulations): one 16-column workgroup.  Its
+// sweep (one process per seed / optimiser rate / penalty setting) and the judging of a run (compute_nde_solution_history, testing.jl:1-32: the network of
+// EVERY epoch re-solved on every simulation) are both "many networks, same few columns".  Here the 16-column fc32 kernels carry the model index in
+// blockIdx.y (FcEns: the strides of what a model owns), tile16's dW GEMM, the reductions and the ADAM step already do; row k of every result is, bit for
+// bit, what a colnde_create handle computes for model k's weights (under the same COLNDE_FC_SEG: the segment count orders the gradient's sums).
+
+// Decided from the configuration and the environment alone, before any device work
+static int fc_ens_refusals(const colnde_config* cfg, int n_models) {
+    if (n_models < 1 || n_models > 65535) return fail("n_models = %d outside 1..65535", n_models);
+    if (cfg->model == COLNDE_MODEL_WIND_MIXING)
+        return fail("colnde_create_fc_ensemble covers the free-convection models (FreeConvectionNDE, ConvectiveAdjustmentNDE): a wind-mixing ensemble is colnde_create_ensemble's");
+    if (cfg->engine != COLNDE_ENGINE_AUTO && cfg->engine != COLNDE_ENGINE_FC32)
+        return fail("free-convection ensembles run the fc32 kernels (engine AUTO or FC32): engine forced to %d has no model index", cfg->engine);
+    {
+        DevModel dm;
+        PackInfo pk;
+        build_model(cfg, &dm, &pk);
+        if (!fc_supported(dm, cfg->stepper))
+            return fail("free-convection ensembles cover the fc32 shape only: FreeConvectionNDE (RK4) or ConvectiveAdjustmentNDE (RK4, RKC2) with Dense(Nz,4Nz,relu), "
+                        "Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1), Nz = 32 or 64 (Nz = %d, %d layers here); other networks run one handle per model", cfg->Nz, cfg->n_layers);
+    }
+    if (cfg->substeps == 0)
+        return fail("substeps = 0 (chosen from reltol by the first solve) is not supported: the models share one sub-step count, and the tapes are sized at "
+                    "creation — choose it with a single handle (colnde_choose_substeps) and pass it");
+    if (refuse_unstable_substeps(cfg)) return 1;
+    if (cfg->n_columns > 4096)
+        return fail("%d columns per model: free-convection ensembles cover the 16-column tiles (at most 4,096 columns per model, fc_tile_width); above it the 32-column "
+                    "kernels run one handle per model", cfg->n_columns);
+    // the switches that send a single handle to kernels without a model index
+    {
+        const char* e = env_get(ENV_FC);
+        if (e && *e && atoi(e) == 0) return fail("COLNDE_FC=0 sends free convection to the tile16 engine, which has no model index here: free-convection ensembles refuse it");
+        e = env_get(ENV_FC_CW);
+        if (e && atoi(e) == 32) return fail("COLNDE_FC_CW=32 selects the 32-column kernels, which have no model index: free-convection ensembles refuse it");
+        if (env_get(ENV_FC_BLOCK)) return fail("COLNDE_FC_BLOCK: free-convection ensembles hold one block of columns per model (the column-block loop has no model index)");
+    }
+    return 0;
+}
+
+// ---- the --conv network (train_free_convection_nde.jl:110-122): a handle of its own on the 16-column fc32 kernels -------------------------------------
+// Decided from the configuration and the environment alone, before any device work
+static int conv_refusals(const colnde_config* cfg, int c) {
+    if (c < 2 || c > FC_CONV_MAX)
+        return fail("conv_filter = %d outside 2..%d (the reference builds the plain three-Dense chain for --conv <= 1: colnde_create; the taps are an unrolled loop of %d)", c,
+                    FC_CONV_MAX, FC_CONV_MAX);
+    if (cfg->model == COLNDE_MODEL_WIND_MIXING)
+        return fail("colnde_create_conv covers the free-convection models (FreeConvectionNDE, ConvectiveAdjustmentNDE): the wind-mixing driver has no --conv network");
+    {
+        DevModel dm;
+        PackInfo pk;
+        build_model(cfg, &dm, &pk);
+        if (!fc_supported(dm, COLNDE_STEPPER_RK4))
+            return fail("colnde_create_conv takes the plain fc32 configuration, layer_sizes = (Nz, 4Nz, 4Nz, Nz-1) with relu, relu, identity and Nz = 32 or 64 (Nz = %d, %d "
+                        "layers here): conv_filter says that the first Dense takes Nz - c + 1 inputs behind the filter", cfg->Nz, cfg->n_layers);
+    }
+    if (cfg->engine != COLNDE_ENGINE_AUTO && cfg->engine != COLNDE_ENGINE_FC32)
+        return fail("the conv network runs the fc32 kernels (engine AUTO or FC32): engine forced to %d has no filter", cfg->engine);
+    if (cfg->model == COLNDE_MODEL_FREE_CONVECTION && cfg->stepper == COLNDE_STEPPER_RKC2)
+        return fail("FreeConvectionNDE under RKC2: fc32 has no such kernel (RKC2 covers ConvectiveAdjustmentNDE; FreeConvectionNDE runs RK4)");
+    if (cfg->substeps == 0)
+        return fail("substeps = 0 (chosen from reltol by the first solve) is not supported on a conv handle: the error estimate does not cover the filter — choose the count "
+                    "and pass it");
+    if (refuse_unstable_substeps(cfg)) return 1;
+    if (cfg->n_columns > 4096)
+        return fail("%d columns: the conv network covers the 16-column tiles (at most 4,096 columns, fc_tile_width); the 32-column kernels have no filter", cfg->n_columns);
+    {
+        const char* e = env_get(ENV_FC);
+        if (e && *e && atoi(e) == 0) return fail("COLNDE_FC=0 sends free convection to the tile16 engine, which has no filter: conv handles refuse it");
+        e = env_get(ENV_FC_CW);
+        if (e && atoi(e) == 32) return fail("COLNDE_FC_CW=32 selects the 32-column kernels, which have no filter: conv handles refuse it");
+        if (env_get(ENV_FC_BLOCK)) return fail("COLNDE_FC_BLOCK: conv handles hold one block of columns (at most 4,096)");
+    }
+    return 0;
+}
+
+extern "C" int colnde_create_conv(const colnde_config* cfg, int conv_filter, colnde_handle** out) {
+    if (!out) return fail("null out pointer");
+    *out = nullptr;
+    if (validate(cfg)) return 1;
+    if (conv_refusals(cfg, conv_filter)) return 1;
+    colnde_handle* h = nullptr;
+    if (colnde_create(cfg, &h)) return 1;
+    if (!h->use_fc || h->fc_cw != 16) {
+        colnde_destroy(h);
+        return fail("colnde_create_conv: the configuration did not select the 16-column fc32 kernels");
+    }
+    const DevModel& m = h->m;
+    const int H = 4 * m.Nz, M = m.Nz - conv_filter + 1;
+    h->conv.w1_end = m.w_off[0] + H * M;
+    h->conv.n_zero = H * (conv_filter - 1);
+    h->conv.n_params = conv_filter + 1 + m.n_params - h->conv.n_zero;
+    hipError_t e = m.w_off[0] == 0 ? h->mem.alloc(&h->conv.d_wpad, (size_t)m.n_params) : hipErrorInvalidValue;
+    if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_gpad, (size_t)m.n_params + 8);
+    if (e != hipSuccess) {
+        colnde_destroy(h);
+        return fail("colnde_create_conv: allocating the padded weight and gradient vectors failed: %s", hipGetErrorString(e));
+    }
+    h->conv.c = conv_filter;
+    *out = h;
+    return 0;
+}
+
+// The tapes of all K models, planned once at creation by fc_plan_tapes' rules on a per-model budget of (free memory - margin) / K: one block of all columns
+// (column blocks do not occur at <= 4,096 columns), the whole time axis when it fits and time segments otherwise (COLNDE_FC_SEG=<intervals> forces), the
+// slice count a single handle of this size plans.  Refused with the bytes it needs when not even one save interval per segment fits.
+static int fc_ens_plan_tapes(colnde_handle* h) {
+    const DevModel& m = h->m;
+    const size_t K = (size_t)h->n_models;
+    const int n_iv = h->cfg.n_save - 1, cw = h->fc_cw;
+    const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
+    if (R != fc_record_row_floats(m.Nz)) return fail("fc32: record layout mismatch (%zu vs %zu floats per column)", R, fc_record_row_floats(m.Nz));
+    const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE;
+    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0));
+    const int n32 = (h->n_col + 31) / 32 * 32;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t budget = hbm_budget(free_b, (size_t)3 << 30) / K;
+    int seg = plan_fc_ens_seg(n32, n_iv, cw, m.Nz, per_col_iv, budget, m.n_params);
+    const char* es = env_get(ENV_FC_SEG);
+    if (es && atoi(es) >= 1) seg = std::min(n_iv, atoi(es));
+    const size_t need = fc_ens_model_bytes(n32, n_iv, cw, m.Nz, per_col_iv, m.n_params, seg);
+    if (need > budget)
+        return fail("a free-convection ensemble of %d models needs %zu bytes of device memory for its tapes and slab rows (%zu per model with %d save interval(s) per "
+                    "time segment, %d substeps x %d stages); %zu bytes are free (3 GB kept in reserve): use fewer models per handle",
+                    h->n_models, K * need, need, seg, h->cfg.substeps, m.nst, free_b);
+    h->fc_block = n32;
+    h->fc_nblocks = 1;
+    h->fc_seg = seg;
+    h->fc_nseg = (n_iv + seg - 1) / seg;
+    const size_t tiles_b = (size_t)n32 / cw;
+    const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;
+    const size_t n_rec = tiles_b * (cw / 16) * stage_recs;
+    std::vector<DwMacro> mac;
+    build_dw_macros(h, n_rec, mac);                          // the slice count a single handle of this size plans: same reduction order
+    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw_slices;
+    FcEns& en = h->fens;
+    en.dwtape = n_rec * CT * R;
+    en.masks = tiles_b * stage_recs * fc_mask_words();
+    en.swtape = ca ? tiles_b * stage_recs * fc_switch_words(cw) : 0;
+    en.lam = (size_t)n32 * m.Nz;
+    en.slab = (size_t)h->fc_rows * P8;
+    const size_t mark = h->mem.mark();
+    hipError_t e = h->mem.alloc(&h->d_dwtape, K * en.dwtape);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_fc_masks, K * en.masks);
+    if (e == hipSuccess && ca) e = h->mem.alloc(&h->d_fc_switch, K * en.swtape);
+    if (e == hipSuccess && h->fc_nseg > 1) e = h->mem.alloc(&h->d_fc_lam, K * en.lam);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
+    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_slab, K * en.slab);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h->mem.rollback(mark);
+        return fail("allocating the free-convection ensemble's tapes (%zu bytes, %zu per model) failed: %s", K * need, need, hipGetErrorString(e));
+    }
+    h->ens.slab = en.slab;
+    h->ens_model_bytes = (en.dwtape + en.slab + (h->fc_nseg > 1 ? en.lam : 0)) * sizeof(float) + en.masks * sizeof(unsigned int) + en.swtape * sizeof(unsigned long long);
+    return 0;
+}
+
+extern "C" int colnde_create_fc_ensemble(const colnde_config* cfg, int n_models, colnde_handle** out) {
+    if (!out) return fail("null out pointer");
+    *out = nullptr;
+    if (validate(cfg)) return 1;
+    if (fc_ens_refusals(cfg, n_models)) return 1;
+    colnde_handle* h = nullptr;
+    if (colnde_create(cfg, &h)) return 1;
+    if (!h->use_fc || h->fc_cw != 16 || !fc_split_supported(16)) {
+        colnde_destroy(h);
+        return fail("this configuration does not run the 16-column fc32 kernels: free-convection ensembles refuse it");
+    }
+    h->ensemble = true;
+    h->n_models = n_models;
+    const size_t K = (size_t)n_models, P = (size_t)h->m.n_params;
+    const int Nz = h->m.Nz;
+    FcEns& en = h->fens;
+    en.n_models = n_models;
+    en.w = P;
+    en.img = fc_image_floats(Nz);
+    en.simg = fc_split_image_words(Nz);
+    en.bias = (fc_bias_floats(Nz) + 3) / 4 * 4;
+    en.sol = (size_t)h->n_col * h->cfg.n_save * h->m.ns;
+    h->ens.sol = en.sol;
+    h->ens.n_models = n_models;
+    DevPool& mem = h->mem;
+    if (mem.resize(&h->d_w, K * P) || mem.resize(&h->d_out, K * (P + 8)) || mem.resize(&h->d_partial, K * 256 * 8) || mem.resize(&h->d_sol, K * en.sol) ||
+        mem.resize(&h->d_fc_imgf, K * en.img) || mem.resize(&h->d_fc_imgb, K * en.img) || mem.resize(&h->d_fc_bias, K * en.bias) ||
+        mem.resize(&h->d_fc_simgf, K * en.simg) || mem.resize(&h->d_fc_simgb, K * en.simg)) {
+        colnde_destroy(h);
+        return fail("allocating the free-convection ensemble's per-model buffers (%d models) failed", n_models);
+    }
+    if (fc_ens_plan_tapes(h)) { colnde_destroy(h); return 1; }
+    h->ens_model_bytes += (2 * en.img + en.bias + en.sol) * sizeof(float) + 2 * en.simg * sizeof(unsigned int);
+    *out = h;
+    return 0;
+}
+
+static int ensemble_only(const colnde_handle* h) {
+    if (!h) return fail("null handle");
+    if (h->closure) return fail("colnde_ensemble_* take weight vectors, but this is a closure handle (no networks): use colnde_closure_* (include/colnde.h)");
+    if (h->conv.c) return fail("colnde_ensemble_* do not cover the convolutional first layer of a colnde_create_conv handle (conv=%d): ensembles of conv networks are out of scope", h->conv.c);
+    if (!h->ensemble) return fail("not an ensemble handle: colnde_ensemble_* take the handles of colnde_create_ensemble (colnde_create: the single-model calls)");
+    return 0;
+}
+
+static int fc_ensemble_only(const colnde_handle* h, const char* fn) {
+    if (ensemble_only(h)) return 1;
+    if (!h->use_fc) return fail("%s takes the handles of colnde_create_fc_ensemble: this ensemble holds wind-mixing models", fn);
+    return 0;
+}
+
+extern "C" int colnde_ensemble_column_loss_dev(colnde_handle* h, const float* d_sol, float* d_out) {
+    if (fc_ensemble_only(h, __func__)) return 1;
+    if (!d_sol || !d_out) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    HIPCHK(hipSetDevice(h->device));
+    Timed tm(h, K_REDUCE);
+    hipError_t e = launch_column_loss(d_sol, h->d_truth, h->m.Nz, (long)h->n_col * h->cfg.n_save, h->n_models, d_out, h->stream);
+    if (e != hipSuccess) return fail("column loss launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_causal_penalty_dev(colnde_handle* h, const float* d_weights, const float* d_coeff, float* d_result) {
+    if (fc_ensemble_only(h, __func__)) return 1;
+    if (!d_weights || !d_coeff || !d_result) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    Timed tm(h, K_REDUCE);
+    hipError_t e = launch_causal_penalty(d_weights, d_coeff, d_result, h->m.Nz, h->m.w_off[0], h->m.n_params, h->n_models, h->stream);
+    if (e != hipSuccess) return fail("causal penalty launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_set_physics(colnde_handle* h, const float* physics) {
+    if (ensemble_only(h)) return 1;
+    if (h->use_fc)
+        return fail("colnde_ensemble_set_physics: a free-convection ensemble has no closure constants to vary (its models differ in their weights and ADAM rates only)");
+    if (!physics) return fail("null physics array");
+    if (!h->cfg.modified_pacanowski_philander)
+        return fail("a physics array needs modified_pacanowski_philander = 1: without the Richardson-number closure the five constants are unused");
+    HIPCHK(hipSetDevice(h->device));
+    int min_sub = 1, stages = 0;
+    if (ens_stability(&h->cfg, h->n_models, physics, &min_sub, &stages)) return 1;
+    // the tapes hold the stage count planned at creation
+    if (stages > h->m.nst)
+        return fail("the new constants need %d RKC2 stages per step, the ensemble's tapes were planned for %d: create a new ensemble", stages, h->m.nst);
+    if (ens_upload_physics(h, physics)) return 1;
+    h->min_substeps = min_sub;
+    return 0;
+}
+
+// forward solve of all K models (with_tape: into the ensemble's tapes)
+static int ens_forward(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape) {
+    if (!h->have_problem) return fail("colnde_set_problem has not been called");
+    if (check_stability(h)) return 1;
+    if (h->use_fc) return fc_pack(h, d_weights) ? 1 : fc_forward_range(h, d_sol, false, 0, h->n_col);
+    RtEns ens = h->ens;
+    ens.sol = (size_t)h->n_col * h->cfg.n_save * h->m.ns;
+    Timed tm(h, K_FORWARD);
+    hipError_t e = rt_launch_pack(h->m, d_weights, h->d_wimg, h->stream, h->n_models);
+    if (e == hipSuccess)
+        e = rt_launch_forward_split(h->m, h->d_wimg, h->d_x0, h->d_bcs, h->d_times, h->cfg.n_save, h->cfg.substeps, d_sol,
+                                    with_tape ? h->d_tape : nullptr, with_tape ? h->d_t16_ztape : nullptr, h->n_col, with_tape && h->split_rich,
+                                    true, h->sp_fwd, h->stream, ens);
+    if (e != hipSuccess) return fail("ensemble forward launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_forward_dev(colnde_handle* h, const float* d_weights, float* d_sol) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !d_sol) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    return ens_forward(h, d_weights, d_sol, false);
+}
+
+extern "C" int colnde_ensemble_loss_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out8) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !scalings || !d_out8) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    HIPCHK(hipSetDevice(h->device));
+    if (ens_forward(h, d_weights, h->d_sol, false)) return 1;
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    const int nblk = 256;
+    hipError_t e = launch_loss(h->m, h->d_sol, h->d_truth, h->cfg.n_save, h->n_col, h->d_partial, nblk, h->stream, h->n_models, h->ens.sol);
+    if (e == hipSuccess) e = launch_reduce(h->d_partial, nblk, 0, 8, lw, d_out8, h->stream, h->n_models, (size_t)nblk * 8, 8);
+    if (e != hipSuccess) return fail("ensemble loss launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !scalings || !d_out) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->use_fc) {                 // fc32: the single handle's gradient path with the models' strides (api_grad.hip)
+        if (!h->have_problem) return fail("colnde_set_problem has not been called");
+        return check_stability(h) ? 1 : fc_loss_grad(h, d_weights, scalings, d_out);
+    }
+    const int K = h->n_models, stride = h->m.n_params + 8;
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->ens.slab * sizeof(float), h->stream));
+    if (ens_forward(h, d_weights, h->d_sol, true)) return 1;
+    hipError_t e;
+    {
+        Timed tm(h, K_ADJOINT);
+        e = rt_launch_adjoint_split(h->m, h->d_wimg, h->d_times, h->cfg.n_save, h->cfg.substeps, h->d_sol, h->d_truth, h->d_tape, h->d_t16_ztape, lw,
+                                    h->d_slab, h->n_col, h->d_dwtape, h->split_rich, true, h->sp_adj, h->stream, h->ens);
+        if (e != hipSuccess) return fail("ensemble adjoint launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        Timed tm(h, K_DW1);
+        const size_t n_rec = (size_t)h->n_tiles * (h->cfg.n_save - 1) * h->cfg.substeps * h->m.nst;
+        float* rows = h->d_slab + (size_t)h->n_tiles * stride;
+        e = (h->sp_dw && !h->dw_split.passes.empty())
+            ? launch_dw_gemm_split(h->d_dwtape, n_rec, (int)dwtape_row_floats(h->m), h->dw_split, h->dw_slices, rows, stride, h->stream, K, h->ens.dwtape, h->ens.slab)
+            : launch_dw_gemm(h->d_dwtape, n_rec, (int)dwtape_row_floats(h->m), h->d_macros, h->n_macros, h->dw_slices, rows, stride, h->stream, K, h->ens.dwtape,
+                             h->ens.slab);
+        if (e != hipSuccess) return fail("ensemble dW GEMM launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        Timed tm(h, K_REDUCE);
+        e = launch_reduce(h->d_slab, h->t16_rows, h->m.n_params, stride, lw, d_out, h->stream, K, h->ens.slab, stride);
+        if (e != hipSuccess) return fail("ensemble reduce launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+extern "C" int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float* out) {
+    if (ensemble_only(h)) return 1;
+    if (!weights || !scalings || !out) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t K = (size_t)h->n_models, P = (size_t)h->m.n_params;
+    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * K * P, hipMemcpyHostToDevice, h->stream));
+    if (colnde_ensemble_loss_grad_dev(h, h->d_w, scalings, h->d_out)) return 1;
+    HIPCHK(hipMemcpyAsync(out, h->d_out, sizeof(float) * K * (P + 8), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_result, float* d_m, float* d_v, const float* d_eta,
+                                             float beta1, float beta2, float eps, float beta1_t, float beta2_t) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !d_result || !d_m || !d_v || !d_eta) return fail("null pointer argument");
+    if (!(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f)) return fail("0 <= beta < 1 required");
+    if (!(beta1_t < 1.0f && beta2_t < 1.0f)) return fail("running powers beta^t must be < 1");
+    HIPCHK(hipSetDevice(h->device));
+    Timed tm(h, K_ADAM);
+    hipError_t e = launch_adam_ensemble(d_weights, d_result, h->m.n_params + 8, d_m, d_v, d_eta, beta1, beta2, eps, beta1_t, beta2_t, h->m.n_params,
+                                        h->n_models, h->stream);
+    if (e != hipSuccess) return fail("ensemble ADAM launch failed: %s", hipGetErrorString(e));
+    return 0;
+}

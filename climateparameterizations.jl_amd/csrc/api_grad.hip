@@ -1,0 +1,479 @@
+// api_grad.hip — loss and gradient of a single handle: the tape planners of the three engines and colnde_loss_grad[_dev].
+#include "api_internal.h"
+#include "tape_plan.h"
+
+// Sizes the regtile engine's tapes.  They hold ONE block of columns; a problem whose tapes exceed the free HBM (many columns, or a
+// long horizon: 1,153 frames need 4x the bytes per column of the 2-day suite) runs its gradient path block after block into the same
+// buffers.  COLNDE_RT_BLOCK=<columns> forces a block size (testing aid).
+static int rt_plan_tapes(colnde_handle* h) {
+    if (h->d_rt_tape) return 0;
+    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
+    const char* ez = env_get(ENV_RT_ZTAPE);
+    bool want_z = !h->rt_fwd32 && !(ez && atoi(ez) == 0);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t budget = hbm_budget(free_b, (size_t)2 << 30);
+    const size_t per_col_x = (size_t)n_steps * 4 * 96 * sizeof(float), per_col_2 = (size_t)n_steps * 4 * ((21 * 256) / 32) * sizeof(float);
+    const size_t per_col_z = rt_tapez_floats(32, n_steps) / 32 * sizeof(float);      // (twice per_col_2 in the A/B build that tapes activation pairs)
+    const int n32 = ((h->n_col + 31) / 32) * 32;
+    int block = 0;
+    for (int pass = 0; pass < 2 && block == 0; pass++) {
+        const size_t per_col = per_col_x + per_col_2 + (want_z ? per_col_z : 0);
+        block = plan_column_block(n32, budget / per_col, 1024, 1024);
+        if (block == 0) want_z = false;          // not even 1,024 columns with the Z1 tape: try without it
+    }
+    const char* eb = env_get(ENV_RT_BLOCK);
+    if (eb && atoi(eb) >= 32) block = std::min(n32, (atoi(eb) / 32) * 32);
+    if (block == 0) return fail("the stage tapes of even 1,024 columns (%zu bytes per column) do not fit in %zu free bytes of HBM",
+                                per_col_x + per_col_2, free_b);
+    const size_t n1 = rt_tape_floats(block, n_steps), n2 = rt_tape2_floats(block, n_steps);
+    const size_t mark = h->mem.mark();
+    hipError_t e = h->mem.alloc(&h->d_rt_tape, n1);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_rt_tape2, n2);
+    h->rt_ztape = want_z;                        // the Z1 tape is optional: dropped when its allocation fails
+    if (e == hipSuccess && want_z && h->mem.alloc(&h->d_rt_tapez, rt_tapez_floats(block, n_steps)) != hipSuccess) h->rt_ztape = false;
+    if (e != hipSuccess) {
+        h->mem.rollback(mark);                   // leave no half-built state behind
+        return fail("hipMalloc of the %zu-byte stage tapes failed: %s", (n1 + n2) * sizeof(float), hipGetErrorString(e));
+    }
+    h->rt_block = block;
+    h->rt_nblocks = (n32 + block - 1) / block;
+    return 0;
+}
+
+// The dW GEMM's work list: 64x64 blocks of every layer's weight matrix, and the number of K-slices of the records
+void build_dw_macros(colnde_handle* h, size_t n_rec, std::vector<DwMacro>& mac) {
+    const DevModel& m = h->m;
+    const size_t R = dwtape_row_floats(m);
+    std::vector<int> matrix_of;
+    for (int net = 0; net < m.n_nets; net++)
+        for (int l = 0; l < m.n_layers; l++) {
+            const int ni = m.sizes[l], no = m.sizes[l + 1];
+            for (int i0 = 0; i0 < ni; i0 += 64)
+                for (int j0 = 0; j0 < no; j0 += 64) {
+                    DwMacro d;
+                    d.a_feat = l == 0 ? i0 : dwtape_ns4(m) + net * dwtape_act4(m) + m.act_off[l - 1] + i0;
+                    d.d_feat = dwtape_ns4(m) + (m.n_nets + net) * dwtape_act4(m) + m.act_off[l] + j0;
+                    d.ni_rem = std::min(64, ni - i0);
+                    d.no_rem = std::min(64, no - j0);
+                    d.g_off = net * m.net_size + m.w_off[l] + i0 * no + j0;
+                    d.no = no;
+                    mac.push_back(d);
+                    matrix_of.push_back(net * m.n_layers + l);
+                }
+        }
+    h->n_macros = (int)mac.size();
+    dw_split_free(h->dw_split);
+    // the split (bf16-pipe) dW GEMM keeps only a pass's operand FEATURES in LDS, as planes: it also serves records that do not fit the LDS whole (the wide
+    // wind-mixing networks: 325 KB per 16-column record), with the large matrices cut into chunks of output blocks (dw_split_build)
+    const bool lds_fit = dw_gemm_lds_fits((int)R, h->n_macros);
+    const bool split_ok = dw_split_build(mac, matrix_of, (int)R, h->dw_split);
+    const int n_groups = (h->n_macros + 3) / 4;
+    size_t slices = std::max<size_t>(8, ((size_t)2048 / n_groups + 7) / 8 * 8);
+    slices = std::min(slices, std::max<size_t>(8, (n_rec / 8 + 7) / 8 * 8));
+    if (lds_fit || (split_ok && h->sp_dw))           // one workgroup per CU (two records / two plane buffers in LDS): two rounds of slices
+        slices = std::min<size_t>(512, std::max<size_t>(1, n_rec));
+    h->dw_slices = (int)slices;
+}
+
+// fc32 gradient path: the records (forward: xs, a1, a2; adjoint: dz1, dz2, dz3) and the bit tapes.  When they do not fit in the free HBM for the
+// whole problem there are two ways to cut it:
+//   * column blocks (a multiple of the 32-column tile): forward -> adjoint -> dW GEMM block after block.  No extra work, but a block of fewer than
+//     16,384 columns leaves CUs with one workgroup or none (the kernels get their speed from two per CU);
+//   * time segments: ALL columns, the tapes hold `fc_seg` save intervals.  One tape-less forward pass first (it saves the state at every save
+//     point, and tapes the last segment on its way), then, from the last segment to the first, a taped forward restarted from the saved state,
+//     the adjoint over the segment (λ handed on through d_fc_lam) and the dW GEMM.  Costs (n_seg - 1)/n_seg of an extra forward solve, keeps every
+//     CU at two workgroups.
+// Blocks are used when they hold at least 16,384 columns (or everything), segments otherwise; COLNDE_FC_BLOCK=<columns> / COLNDE_FC_SEG=<intervals> force.
+static int fc_plan_tapes(colnde_handle* h) {
+    if (h->d_dwtape) return 0;
+    const DevModel& m = h->m;
+    const int n_iv = h->cfg.n_save - 1;
+    const size_t R = dwtape_row_floats(m);
+    if (R != fc_record_row_floats(m.Nz)) return fail("fc32: record layout mismatch (%zu vs %zu floats per column)", R, fc_record_row_floats(m.Nz));
+    const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE;
+    // bytes of tape per column and save interval
+    const int cw = h->fc_cw;
+    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0) +
+                                                                 (h->conv.c ? fc_conv_tape_floats(m.Nz) / 16 * sizeof(float) : 0));      // (conv handles: the conv tape)
+    const int n32 = (h->n_col + 31) / 32 * 32;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t margin = ((size_t)3 << 30) + (size_t)(n32 / cw * 8 + 4096) * (m.n_params + 8) * sizeof(float) + (size_t)n32 * m.Nz * sizeof(float);
+    const FcTapePlan plan = plan_fc_block_seg(n32, n_iv, cw, per_col_iv, hbm_budget(free_b, margin), m.n_params);
+    int block = plan.block, seg = plan.seg;
+    const char* eb = env_get(ENV_FC_BLOCK);
+    const char* es = env_get(ENV_FC_SEG);
+    if (eb && atoi(eb) >= 32) { block = std::min(n32, (atoi(eb) / 32) * 32); if (!es) seg = n_iv; }
+    if (es && atoi(es) >= 1) seg = std::min(n_iv, atoi(es));
+    if (block < 32 || seg < 1) return fail("fc32: the tapes of even one 32-column tile and one save interval (%zu bytes) do not fit in the free device memory", 32 * per_col_iv);
+    h->fc_block = block;
+    h->fc_nblocks = (n32 + block - 1) / block;
+    h->fc_seg = seg;
+    h->fc_nseg = (n_iv + seg - 1) / seg;
+    const size_t tiles_b = (size_t)block / cw;                                  // (block is a multiple of 32)
+    const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;          // (tile, stage) records per tile held by the tapes
+    const size_t n_rec = tiles_b * (cw / 16) * stage_recs;                     // records are tile16's: 16 columns each
+    std::vector<DwMacro> mac;
+    build_dw_macros(h, n_rec, mac);
+    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw_slices;
+    const int stride = m.n_params + 8;
+    const size_t mark = h->mem.mark();
+    hipError_t e = h->mem.alloc(&h->d_dwtape, n_rec * CT * R);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_fc_masks, tiles_b * stage_recs * fc_mask_words());
+    if (e == hipSuccess && ca) e = h->mem.alloc(&h->d_fc_switch, tiles_b * stage_recs * fc_switch_words(cw));
+    if (e == hipSuccess && h->fc_nseg > 1) e = h->mem.alloc(&h->d_fc_lam, (size_t)n32 * m.Nz);
+    if (e == hipSuccess && h->conv.c) {
+        h->conv.cslab_rows = h->fc_nblocks * h->fc_nseg * FC_CONV_GRAD_MAX_SLICES;
+        e = h->mem.alloc(&h->conv.d_ctape, n_rec * fc_conv_tape_floats(m.Nz));
+        if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_cslab, (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS);
+    }
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
+    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !h->d_slab) e = h->mem.alloc(&h->d_slab, (size_t)h->fc_rows * stride);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h->mem.rollback(mark);
+        return fail("fc32: hipMalloc of the tapes (%zu bytes for %d columns x %d save intervals) failed: %s", (size_t)block * per_col_iv * seg, block, seg,
+                    hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// tile16, taped weight gradients: decide once per handle.  On when the tapes fit in the free HBM (the in-register adjoint_kernel
+// geometries remain the fallback; 64-256-256-63's 384 gradient tiles spill there);
+// COLNDE_T16_DWTAPE=1 / 0 forces it on / off.
+static int t16_plan_dwtape(colnde_handle* h) {
+    if (h->t16_dwtape >= 0) return 0;
+    const DevModel& m = h->m;
+    const char* ev = env_get(ENV_T16_DWTAPE);
+    // default: on whenever the tapes fit — with the hidden pre-activations taped too, the 1,024-thread accumulator-free adjoint beats
+    // the in-register kernels at every size measured (8 columns: 53 vs 64 ms per iteration; 32-128-128-31: 162 vs 198 ms)
+    bool want = ev ? atoi(ev) != 0 : true;
+    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
+    const size_t R = dwtape_row_floats(m);
+    if (want && (size_t)CT * m.ns > 6 * 512) want = false;
+    // LDS of the taped adjoint: with the Z tape (the default) it holds no activation array; a network that fits only that way (3 x 96-400-31: 166 KB with
+    // the array, 83 KB without) then NEEDS the Z tape
+    bool need_z = false;
+    if (want && !h->ag_rows && (MODEL_FLOATS + lds_floats_adjoint(m)) * sizeof(float) > 160 * 1024) {
+        const char* ez = env_get(ENV_T16_ZTAPE);
+        if (!(ez && atoi(ez) == 0) && (MODEL_FLOATS + lds_floats_adjoint_noA(m)) * sizeof(float) <= 160 * 1024 && m.n_bias <= 4 * 512) need_z = true;
+        else want = false;
+    }
+    if (h->ag_rows) {       // rows in global memory: the taped adjoint with the Z tape is the ONLY gradient path (1,024 threads: n_bias <= 4 x 1,024, CT ns <= 2 x 1,024)
+        if (!want) return fail("COLNDE_T16_DWTAPE=0: this network's activation rows live in global memory, and only the taped-dW adjoint runs that way");
+        if (m.n_bias > 4 * 1024 || (MODEL_FLOATS + lds_floats_adjoint_ag(m)) * sizeof(float) > 160 * 1024)
+            return fail("network too large for the taped adjoint with rows in global memory (%d biases, %zu B of LDS)", m.n_bias, (MODEL_FLOATS + lds_floats_adjoint_ag(m)) * sizeof(float));
+    }
+    // The tapes hold ONE block of columns (a multiple of the 16-column tile; whole rounds of 4,096 columns = one workgroup per CU when
+    // possible); larger problems run forward -> adjoint -> dW GEMM block after block.  COLNDE_T16_BLOCK=<columns> forces a size.
+    const size_t per_col = (size_t)n_steps * m.nst * (R + t16_ztape_col_floats(m) + m.ns) * sizeof(float);
+    const int n16 = h->n_tiles * CT;
+    int block = 0;
+    // the net-split pair's rich tape replaces the pre-activation tape on small blocks and is 4x its size per column (13,824 floats per
+    // 16-column record against 216 per column): it is part of the fit estimate, not an afterthought behind the 3 GB margin
+    const char* ezt0 = env_get(ENV_T16_ZTAPE);
+    const char* er0 = env_get(ENV_T16_SPLIT_RICH);
+    const bool rich_possible = h->adj_split && !(ezt0 && atoi(ezt0) == 0) && !(er0 && atoi(er0) == 0);
+    const size_t per_col_rich = (size_t)n_steps * m.nst * (R + rt_split_rich_record_floats() / CT + m.ns) * sizeof(float);
+    bool want_rich = false;
+    if (want) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        const size_t margin = ((size_t)3 << 30) + (size_t)h->n_tiles * (m.n_params + 8) * sizeof(float);
+        const size_t budget = hbm_budget(free_b, margin);
+        block = plan_column_block(n16, budget / per_col, CT, 4096);
+        const char* eb = env_get(ENV_T16_BLOCK);
+        if (eb && atoi(eb) >= CT) block = std::min(n16, (atoi(eb) / CT) * CT);
+        if (block <= 0) want = false;
+        // rich tape: by default on blocks of at most 2,048 columns; forced on by COLNDE_T16_SPLIT_RICH=1.  It must fit WITH the other tapes:
+        // a forced rich tape shrinks the block, an automatic one is dropped.
+        want_rich = want && rich_possible && ((er0 && atoi(er0) != 0) || block <= 128 * CT);
+        if (want_rich && (size_t)block * per_col_rich > budget) {
+            const size_t fit_rich = budget / per_col_rich / CT * CT;
+            if (er0 && atoi(er0) != 0 && fit_rich >= CT) block = (int)std::min<size_t>((size_t)block, fit_rich);
+            else want_rich = false;
+        }
+    }
+    if (!want) {
+        if (h->ag_rows) return fail("the delta tape of this network (%zu B per column) does not fit in HBM beside the solve", per_col);
+        h->t16_dwtape = 0;
+        return 0;
+    }
+    const int tiles_b = block / CT;
+    const size_t n_rec = (size_t)tiles_b * n_steps * h->m.nst;
+    const size_t need = n_rec * CT * R * sizeof(float);
+    h->t16_block = block;
+    h->t16_nblocks = (n16 + block - 1) / block;
+    std::vector<DwMacro> mac;
+    build_dw_macros(h, n_rec, mac);
+    h->t16_rows = h->n_tiles + h->t16_nblocks * h->dw_slices;
+    const int stride = m.n_params + 8;
+    const size_t mark = h->mem.mark();
+    hipError_t e = h->mem.alloc(&h->d_dwtape, need / sizeof(float));
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
+    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !h->d_slab) e = h->mem.alloc(&h->d_slab, (size_t)h->t16_rows * stride);
+    if (e != hipSuccess) {                  // no delta tape: the in-register path follows
+        (void)hipGetLastError();
+        h->mem.rollback(mark);
+        h->t16_dwtape = 0;
+        if (h->ag_rows) return fail("allocating the delta tape (%zu B) failed: %s", need, hipGetErrorString(e));
+        return 0;
+    }
+    h->t16_dwtape = 1;
+    // the block's stage tape, and (COLNDE_T16_ZTAPE=0 disables) the hidden pre-activations the forward kernel tapes for the adjoint
+    if (!h->d_tape) {
+        e = h->mem.alloc(&h->d_tape, n_rec * CT * m.ns);
+        if (e != hipSuccess) {
+            h->mem.rollback(mark);
+            h->t16_dwtape = 0;
+            if (h->ag_rows) return fail("allocating the stage tape failed: %s", hipGetErrorString(e));
+            return 0;
+        }
+    }
+    const char* ezt = env_get(ENV_T16_ZTAPE);
+    // net-split kernels on a small block (<= 2,048 columns, where it pays: 64-step iteration with the four-wave kernels 2.36 vs 2.48 ms at 1,024
+    // columns, 2.69 vs 2.77 at 2,048, 3.99 vs 3.53 at 4,096): the rich tape in place of the pre-activations
+    if (want_rich && h->mem.alloc(&h->d_t16_ztape, n_rec * rt_split_rich_record_floats()) == hipSuccess) {
+        h->split_rich = true;
+        return 0;
+    }
+    if (!(ezt && atoi(ezt) == 0)) (void)h->mem.alloc(&h->d_t16_ztape, n_rec * CT * t16_ztape_col_floats(m));      // (optional: null when it fails)
+    if ((h->ag_rows || need_z) && !h->d_t16_ztape)
+        return fail("this network's taped adjoint needs the pre-activation tape (COLNDE_T16_ZTAPE=0 or its allocation failed): no gradient path for it without one");
+    return 0;
+}
+
+// regtile: the tapes hold one block of columns; forward -> adjoint -> dW1 block after block
+static int rt_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    const int stride = h->m.n_params + 8;
+    if (!h->have_problem) return fail("colnde_set_problem has not been called");
+    if (rt_plan_tapes(h)) return 1;
+    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
+    const int n_wt = rt_n_wtiles(h->n_col), n_dw = rt_dw1_waves(h->rt_block, n_steps);
+    if (!h->d_rt_slab) {
+        h->rt_rows = n_wt + h->rt_nblocks * n_dw;
+        hipError_t e = h->mem.alloc(&h->d_rt_slab, (size_t)h->rt_rows * stride);
+        if (e != hipSuccess) return fail("hipMalloc of the partial-gradient slab failed: %s", hipGetErrorString(e));
+    }
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    hipError_t e = rt_launch_pack(h->m, d_weights, h->d_wimg, h->stream);
+    if (e != hipSuccess) return fail("rt pack launch failed: %s", hipGetErrorString(e));
+    HIPCHK(hipMemsetAsync(h->d_rt_slab, 0, (size_t)h->rt_rows * stride * sizeof(float), h->stream));
+    const size_t ns = h->m.ns;
+    for (int b = 0; b < h->rt_nblocks; b++) {
+        const int c0 = b * h->rt_block, nc = std::min(h->rt_block, h->n_col - c0);
+        if (nc <= 0) break;
+        if (rt_forward_range(h, h->d_sol, true, c0, nc)) return 1;
+        {
+            Timed tm(h, K_ADJOINT);
+            e = rt_launch_adjoint(h->m, h->d_wimg, h->d_bcs + (size_t)c0 * h->m.n_bc, h->d_times, h->cfg.n_save, h->cfg.substeps,
+                                  h->d_sol + (size_t)c0 * h->cfg.n_save * ns, h->d_truth + (size_t)c0 * h->cfg.n_save * ns, h->d_rt_tape,
+                                  h->d_rt_tape2, h->rt_ztape ? h->d_rt_tapez : nullptr, lw,
+                                  h->d_rt_slab + (size_t)(c0 / 32) * stride, nc, h->sp_adj, h->stream);
+            if (e != hipSuccess) return fail("rt adjoint launch failed: %s", hipGetErrorString(e));
+        }
+        {
+            Timed tm(h, K_DW1);
+            e = rt_launch_dw1(h->m, h->d_rt_tape, h->d_rt_tape2, nc, n_steps, h->d_rt_slab + ((size_t)n_wt + (size_t)b * n_dw) * stride,
+                              h->sp_dw, h->stream);
+            if (e != hipSuccess) return fail("rt dW1 launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    {
+        Timed tm(h, K_REDUCE);
+        e = launch_reduce(h->d_rt_slab, h->rt_rows, h->m.n_params, stride, lw, d_out, h->stream);
+        if (e != hipSuccess) return fail("reduce launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// fc32, for a single handle and for a free-convection ensemble alike (FcEns strides; the ensemble is the case of one column block): forward ->
+// adjoint -> dW GEMM block after block, within a block segment by segment from the end of the time axis, λ handed on per model
+int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    const int stride = h->m.n_params + 8;
+    if (!h->have_problem) return fail("colnde_set_problem has not been called");
+    if (fc_plan_tapes(h)) return 1;
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    const size_t ns = h->m.ns;
+    // an ensemble hands the kernels the strides of what a model owns (a single handle: one model, no strides) and its own words in the launch errors
+    const int K = h->n_models;
+    const FcEns* en = h->ensemble ? &h->fens : nullptr;
+    const char* ens = h->ensemble ? "ensemble " : "";
+    if (fc_pack(h, d_weights)) return 1;
+    const FcConv cv = fc_conv_args(h);                                  // (after the plan: the conv tape exists)
+    hipError_t e;
+    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->fc_rows * stride * sizeof(float), h->stream));
+    if (h->conv.c) HIPCHK(hipMemsetAsync(h->conv.d_cslab, 0, (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS * sizeof(float), h->stream));
+    const int cw = h->fc_cw;
+    const int n_wg = (h->n_col + cw - 1) / cw, n_iv = h->cfg.n_save - 1, nseg = h->fc_nseg;
+    const size_t gemm_rows0 = (size_t)n_wg * nseg;                      // slab: [tile][segment] adjoint rows, then [block][segment][slice] GEMM rows
+    for (int b = 0; b < h->fc_nblocks; b++) {
+        const int c0 = b * h->fc_block, nc = std::min(h->fc_block, h->n_col - c0);
+        if (nc <= 0) break;
+        const size_t tiles_b = ((size_t)nc + cw - 1) / cw;
+        // time segments: the states at the save points first (tape-less), then segment by segment from the end of the axis
+        // (that first pass tapes the LAST segment on its way, which is the first one the backward sweep needs)
+        if (nseg > 1 && fc_forward_range(h, h->d_sol, true, c0, nc, 0, n_iv, (nseg - 1) * h->fc_seg)) return 1;
+        for (int sg = nseg - 1; sg >= 0; sg--) {
+            const int iv0 = sg * h->fc_seg, iv1 = std::min(n_iv, iv0 + h->fc_seg);
+            if (!(nseg > 1 && sg == nseg - 1) && fc_forward_range(h, h->d_sol, true, c0, nc, iv0, iv1)) return 1;
+            {
+                Timed tm(h, K_ADJOINT);
+                e = fc_launch_adjoint(h->m, h->fc_cw, h->d_fc_imgb, (h->sp_adj && fc_split_supported(h->fc_cw)) ? h->d_fc_simgb : nullptr, h->d_times, h->cfg.n_save, iv0, iv1, h->cfg.substeps, h->d_sol + (size_t)c0 * h->cfg.n_save * ns,
+                                      h->d_truth + (size_t)c0 * h->cfg.n_save * ns, h->d_dwtape, h->d_fc_masks, h->d_fc_switch, lw.w[2],
+                                      nseg > 1 ? h->d_fc_lam + (size_t)c0 * h->m.Nz : nullptr,
+                                      h->d_slab + ((size_t)sg * n_wg + (size_t)(c0 / cw)) * stride, nc, h->stream, en, h->conv.c ? &cv : nullptr);
+                if (e != hipSuccess) return fail("fc32 %sadjoint launch failed: %s", ens, hipGetErrorString(e));
+            }
+            {
+                Timed tm(h, K_DW1);
+                if (h->sp_dw && !h->dw_split.passes.empty())
+                    e = launch_dw_gemm_split(h->d_dwtape, tiles_b * (cw / 16) * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst, (int)dwtape_row_floats(h->m), h->dw_split,
+                                             h->dw_slices, h->d_slab + (gemm_rows0 + ((size_t)b * nseg + sg) * h->dw_slices) * stride, stride, h->stream, K, h->fens.dwtape, h->fens.slab);
+                else
+                e = launch_dw_gemm(h->d_dwtape, tiles_b * (cw / 16) * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst, (int)dwtape_row_floats(h->m), h->d_macros,
+                                   h->n_macros, h->dw_slices, h->d_slab + (gemm_rows0 + ((size_t)b * nseg + sg) * h->dw_slices) * stride, stride, h->stream, K, h->fens.dwtape, h->fens.slab);
+                if (e != hipSuccess) return fail("%sdW GEMM launch failed: %s", ens, hipGetErrorString(e));
+                if (h->conv.c) {                                        // the filter's c + 1 entries, from the conv tape of the same records
+                    e = launch_fc_conv_grad(h->conv.d_ctape, (long)(tiles_b * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst) * 16, h->m.Nz, h->conv.c,
+                                            h->conv.d_cslab + ((size_t)b * nseg + sg) * FC_CONV_GRAD_MAX_SLICES * FC_CONV_GRAD_SLOTS, h->stream);
+                    if (e != hipSuccess) return fail("conv filter gradient launch failed: %s", hipGetErrorString(e));
+                }
+            }
+        }
+    }
+    {
+        Timed tm(h, K_REDUCE);
+        e = launch_reduce(h->d_slab, h->fc_rows, h->m.n_params, stride, lw, h->conv.c ? h->conv.d_gpad : d_out, h->stream, K, h->fens.slab, h->ensemble ? stride : 0);
+        if (e != hipSuccess) return fail("%sreduce launch failed: %s", ens, hipGetErrorString(e));
+        if (h->conv.c) {                                                // the user's layout: filter entries in front, W1's padded columns dropped
+            e = launch_fc_conv_fold(h->conv.d_gpad, h->conv.d_cslab, h->conv.cslab_rows, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->conv.n_params + 8, d_out,
+                                    h->stream);
+            if (e != hipSuccess) return fail("conv gradient fold launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    return 0;
+}
+
+// tile16 with the delta tape: forward -> adjoint -> dW GEMM block after block
+static int t16_taped_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    const int stride = h->m.n_params + 8;
+    if (!h->have_problem) return fail("colnde_set_problem has not been called");
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
+    const size_t ns = h->m.ns;
+    if (pack(h, d_weights)) return 1;
+    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)h->t16_rows * stride * sizeof(float), h->stream));
+    for (int b = 0; b < h->t16_nblocks; b++) {
+        const int c0 = b * h->t16_block, nc = std::min(h->t16_block, h->n_col - c0);
+        if (nc <= 0) break;
+        const int tiles_b = (nc + CT - 1) / CT;
+        if (t16_forward_range(h, d_weights, h->d_sol, true, c0, nc)) return 1;
+        {
+            Timed tm(h, K_ADJOINT);
+            AdjointGeom g = {512, 1, 3, 0};
+            hipError_t e;
+            if (h->adj_split && h->d_t16_ztape)
+                // the companion of the split forward: one wavefront per flux net (+ a helper) per tile, writing tile16's delta tape
+                e = rt_launch_adjoint_split(h->m, h->d_wimg, h->d_times, h->cfg.n_save, h->cfg.substeps,
+                                            h->d_sol + (size_t)c0 * h->cfg.n_save * ns, h->d_truth + (size_t)c0 * h->cfg.n_save * ns, h->d_tape,
+                                            h->d_t16_ztape, lw, h->d_slab + (size_t)(c0 / CT) * stride, nc, h->d_dwtape, h->split_rich, h->adj_helper, h->sp_adj, h->stream);
+            else
+            e = launch_adjoint(h->m, h->pk, d_weights, h->d_wf, h->d_wb, h->d_tiles, h->d_bias_zoff, h->d_bias_goff,
+                                          h->d_bcs + (size_t)c0 * h->m.n_bc, h->d_times, h->cfg.n_save, h->cfg.substeps,
+                                          h->d_sol + (size_t)c0 * h->cfg.n_save * ns, h->d_truth + (size_t)c0 * h->cfg.n_save * ns, h->d_tape,
+                                          lw, h->d_slab + (size_t)(c0 / CT) * stride, nc, g,
+                                          (MODEL_FLOATS + (h->ag_rows ? lds_floats_adjoint_ag(h->m) : (h->d_t16_ztape ? lds_floats_adjoint_noA(h->m) : lds_floats_adjoint(h->m)))) * sizeof(float),
+                                          h->stream, h->d_dwtape, h->d_t16_ztape);
+            if (e != hipSuccess) return fail("adjoint (taped dW) launch failed: %s", hipGetErrorString(e));
+        }
+        {
+            Timed tm(h, K_DW1);
+            hipError_t e = (h->sp_dw && !h->dw_split.passes.empty())
+                ? launch_dw_gemm_split(h->d_dwtape, (size_t)tiles_b * n_steps * h->m.nst, (int)dwtape_row_floats(h->m), h->dw_split,
+                                       h->dw_slices, h->d_slab + ((size_t)h->n_tiles + (size_t)b * h->dw_slices) * stride, stride, h->stream)
+                : launch_dw_gemm(h->d_dwtape, (size_t)tiles_b * n_steps * h->m.nst, (int)dwtape_row_floats(h->m), h->d_macros, h->n_macros,
+                                          h->dw_slices, h->d_slab + ((size_t)h->n_tiles + (size_t)b * h->dw_slices) * stride, stride, h->stream);
+            if (e != hipSuccess) return fail("dW GEMM launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    {
+        Timed tm(h, K_REDUCE);
+        hipError_t e = launch_reduce(h->d_slab, h->t16_rows, h->m.n_params, stride, lw, d_out, h->stream);
+        if (e != hipSuccess) return fail("reduce launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// tile16 with the weight-gradient tiles in registers: the whole problem in one adjoint launch
+static int t16_inreg_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    const int stride = h->m.n_params + 8;
+    if (forward_impl(h, d_weights, h->d_sol, true)) return 1;
+    if (!h->geo_ok)
+        return fail("network too large for the tile engine's in-register adjoint (%d weight-gradient tiles, %zu B of LDS) and its "
+                    "delta tape does not fit in HBM (or COLNDE_T16_DWTAPE=0)", h->m.n_tiles, h->lds_adj);
+    if (!h->d_slab) {
+        hipError_t e = h->mem.alloc(&h->d_slab, (size_t)h->n_tiles * stride);
+        if (e != hipSuccess) return fail("hipMalloc of the partial-gradient slab failed: %s", hipGetErrorString(e));
+    }
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    {
+        Timed tm(h, K_ADJOINT);
+        hipError_t e = launch_adjoint(h->m, h->pk, d_weights, h->d_wf, h->d_wb, h->d_tiles, h->d_bias_zoff, h->d_bias_goff,
+                                      h->d_bcs, h->d_times, h->cfg.n_save, h->cfg.substeps, h->d_sol, h->d_truth, h->d_tape,
+                                      lw, h->d_slab, h->n_col, h->geo, h->lds_adj, h->stream);
+        if (e != hipSuccess) return fail("adjoint launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        Timed tm(h, K_REDUCE);
+        hipError_t e = launch_reduce(h->d_slab, h->n_tiles, h->m.n_params, stride, lw, d_out, h->stream);
+        if (e != hipSuccess) return fail("reduce launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+extern "C" int colnde_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    SINGLE_MODEL_ONLY(h);
+    if (!h) return fail("null handle");
+    if (!d_weights || !scalings || !d_out) return fail("null pointer argument");
+    if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
+    if (h->m.inplace) return fail("the in-place NDE! variant is an evaluation RHS; gradients use the training RHS (inplace_variant = 0)");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->auto_substeps) {
+        if (!h->have_problem) return fail("colnde_set_problem has not been called");
+        if (refuse_auto_on_a_shard(h)) return 1;
+        h->auto_substeps = false;
+        if (choose_substeps_impl(h, d_weights, h->cfg.reltol, nullptr, nullptr)) { h->auto_substeps = true; return 1; }
+    }
+    if (check_stability(h)) return 1;
+    if (h->use_rt) return rt_loss_grad(h, d_weights, scalings, d_out);
+    if (h->use_fc) return fc_loss_grad(h, d_weights, scalings, d_out);
+    if (t16_plan_dwtape(h)) return 1;
+    return h->t16_dwtape == 1 ? t16_taped_loss_grad(h, d_weights, scalings, d_out) : t16_inreg_loss_grad(h, d_weights, scalings, d_out);
+}
+
+extern "C" int colnde_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float terms[6],
+                                float* total, float* grad) {
+    SINGLE_MODEL_ONLY(h);
+    if (!h) return fail("null handle");
+    if (!weights || !scalings || !terms || !total || !grad) return fail("null pointer argument");
+    HIPCHK(hipSetDevice(h->device));
+    const int np = user_params(h);
+    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * np, hipMemcpyHostToDevice, h->stream));
+    if (colnde_loss_grad_dev(h, h->d_w, scalings, h->d_out)) return 1;
+    float o[8];
+    HIPCHK(hipMemcpyAsync(grad, h->d_out, sizeof(float) * np, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(o, h->d_out + np, sizeof(o), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < 6; q++) terms[q] = o[q];
+    *total = o[6];
+    if (!std::isfinite(o[6])) return fail("the loss is not finite (%g): the solve left the stable regime (time step, weights or inputs)", o[6]);
+    return 0;
+}

@@ -1,8 +1,13 @@
-// api_internal.h — what the translation units of the C ABI share (api.hip, api_embed.hip): the handle, the error and timing plumbing, and the
-// staging of host arrays through one device scratch.  Not part of the public header; nothing here is exported.
+// api_internal.h — what the translation units of the C ABI share (api.hip and api_{grad,ensemble,closure,substeps,embed}.hip): the handle and the pool
+// that owns its device buffers, the error and timing plumbing, the environment switches, the helpers that cross files, and the staging of host arrays
+// through one device scratch.  Not part of the public header; nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -20,11 +25,32 @@ struct colnde_handle;
 
 // ---- defined once, in api.hip ------------------------------------------------------------------------------
 int fail(const char* fmt, ...);   // stores the thread-local message of colnde_last_error, returns 1
+int validate(const colnde_config* c);
+int open_device(int device);      // selects it; refuses anything but a gfx950
+double stiff_lambda(const colnde_config* c);
+RtPhys closure_constants(float nu0, float nu_minus, float dRi, float Ric, float Pr);
+void build_model(const colnde_config* c, DevModel* m, PackInfo* pk);
+int refresh_rkc(colnde_handle* h);
+int refuse_unstable_substeps(const colnde_config* cfg);
+int check_stability(const colnde_handle* h);
+int refuse_auto_on_a_shard(const colnde_handle* h);
+int user_params(const colnde_handle* h);
+void loss_weights(const colnde_handle* h, const float scalings[6], LossWeights* lw);
 int pack(colnde_handle* h, const float* d_weights);
+int fc_pack(colnde_handle* h, const float* d_weights);
+FcConv fc_conv_args(const colnde_handle* h);
 int ensure_tmp(colnde_handle* h, size_t n_columns);
 int ensure_ag(colnde_handle* h, size_t tiles);
 void drain_events(colnde_handle* h);
+int forward_impl(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape);
+int rt_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int nc);
+int t16_forward_range(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape, int c0, int nc);
+int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int nc, int iv0 = 0, int iv1 = -1, int tape_iv0 = -1);
+// ---- api_grad.hip, api_ensemble.hip, api_substeps.hip -------------------------------------------------------
+void build_dw_macros(colnde_handle* h, size_t n_rec, std::vector<DwMacro>& mac);
+int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
 colnde_config model_config(const colnde_config* cfg, const float* physics, int k);
+int choose_substeps_impl(colnde_handle* h, const float* d_weights, float reltol, int* chosen, float* estimate);
 // ---- defined in api_embed.hip: the handles the embedding's kernels cover (colnde_describe reports them) ------
 bool wm_infer_covers(const colnde_handle* h);
 bool fce_covers(const colnde_handle* h);
@@ -59,6 +85,67 @@ enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1
 
 struct PendingEvent { hipEvent_t a, b; int which; };
 
+// ---- environment switches ------------------------------------------------------------------------------------
+// Every variable some part of the library reads: colnde_describe reports from this list.  The ABI files read through env_get alone, so a switch read
+// there is in the list by construction; the engine files read FC_CW, RT_FWD, T16_DWLDS, T16_TAPE_THREADS and T16_TAPE_WLDS themselves.
+#define COLNDE_ENV_LIST(X)                                                                                                                  \
+    X(FWD_SPLIT) X(ADJ_SPLIT) X(DW_SPLIT) X(ADJ_GEOM) X(FWD_WLDS) X(FWD_THREADS) X(T16_FWD_HELPER) X(T16_ADJ_HELPER) X(T16_FWD_SPLIT)         \
+    X(T16_ADJ_SPLIT) X(FC) X(FC_CW) X(FC_EMBED_FUSED) X(FC_BLOCK) X(FC_SEG) X(WM_ENS_GRID) X(RT_ZTAPE) X(RT_BLOCK) X(RT_FWD) X(ALLOW_UNSTABLE_DT) \
+    X(T16_DWTAPE) X(T16_ZTAPE) X(T16_SPLIT_RICH) X(T16_BLOCK) X(T16_DWLDS) X(T16_TAPE_THREADS) X(T16_TAPE_WLDS)
+#define X(n) ENV_##n,
+enum EnvSwitch { COLNDE_ENV_LIST(X) ENV_COUNT };
+#undef X
+const char* env_name(EnvSwitch s);
+const char* env_get(EnvSwitch s);                                      // the raw string, or null when unset or empty
+inline int env_int(EnvSwitch s, int unset) { const char* e = env_get(s); return e ? atoi(e) : unset; }
+inline bool allow_unstable() { return env_int(ENV_ALLOW_UNSTABLE_DT, 0) != 0; }
+
+// ---- device memory -------------------------------------------------------------------------------------------
+// The owner of every device buffer a handle keeps.  The handle still names its pointers (launch code reads them); the pool remembers where they live,
+// so that colnde_destroy, a refused creator and a planner that fails half-way free exactly what was allocated and leave the slots null.
+class DevPool {
+    std::vector<void**> slots_;
+
+  public:
+    // hipMalloc of `count` elements into *slot (which must not hold a buffer).  A failure clears the sticky error and leaves *slot null.
+    template <class T> hipError_t alloc(T** slot, size_t count) {
+        const hipError_t e = hipMalloc((void**)slot, count * sizeof(T));
+        if (e != hipSuccess) { (void)hipGetLastError(); *slot = nullptr; }
+        else if (*slot) slots_.push_back((void**)slot);
+        return e;
+    }
+    template <class T> void release(T** slot) {
+        if (!*slot) return;
+        (void)hipFree(*slot);
+        *slot = nullptr;
+        slots_.erase(std::remove(slots_.begin(), slots_.end(), (void**)slot), slots_.end());
+    }
+    template <class T> hipError_t resize(T** slot, size_t count) { release(slot); return alloc(slot, count); }
+    size_t mark() const { return slots_.size(); }
+    void rollback(size_t mark) {            // frees what was allocated since mark(), newest first (nothing may be released in between)
+        while (slots_.size() > mark) {
+            (void)hipFree(*slots_.back());
+            *slots_.back() = nullptr;
+            slots_.pop_back();
+        }
+    }
+    void free_all() { rollback(0); }
+};
+
+// Device scratch of one call: freed when the call returns, after the work queued on the stream has drained
+struct DevScratch {
+    hipStream_t stream;
+    float* p = nullptr;
+    explicit DevScratch(hipStream_t s) : stream(s) {}
+    DevScratch(const DevScratch&) = delete;
+    hipError_t alloc(size_t bytes) { return hipMalloc((void**)&p, bytes); }
+    ~DevScratch() {
+        if (!p) return;
+        (void)hipStreamSynchronize(stream);
+        (void)hipFree(p);
+    }
+};
+
 // colnde_create_conv: the filter in front of the plain fc32 network the handle holds in `m`
 struct ConvBlock {
     int c = 0;                      // taps (0: not a conv handle)
@@ -73,6 +160,7 @@ struct ConvBlock {
 };
 
 struct colnde_handle {
+    DevPool mem;                    // owns every d_* below
     colnde_config cfg;
     ConvBlock conv;
     std::vector<float> save_times;

@@ -18,7 +18,7 @@
 //  * a workgroup has read all of its tile's T before it writes any T′, and tiles are disjoint: T_out may be T.
 // LDS: fc_infer_kernel's carve + the two halo cells per column (256 B at most): 76 KB per workgroup at Nz = 64 on 32 columns, two fit a CU's 160 KB.
 // Which launches the C entry points issue was decided by measurement (profiles/fc_embed_rate.json): the diagnosis-only and the
-// three-output kernels always; forcing + adjustment alone runs as the two existing launches unless COLNDE_FC_EMBED_FUSED=1 (api.hip).
+// three-output kernels always; forcing + adjustment alone runs as the two existing launches unless COLNDE_FC_EMBED_FUSED=1 (api_embed.hip).
 #include <algorithm>
 #include "engine_fc_embed.h"
 #include "engine_fc.h"

@@ -100,6 +100,27 @@ def test_refused_create_and_failed_calls_leave_nothing_behind():
     assert before - after <= (8 << 20), before - after
 
 
+def test_create_refused_after_partial_construction_leaves_nothing_behind():
+    """A creator that refuses AFTER it has allocated: the wide 3 x 96-400-400-31 network has its activation rows and both bf16 plane images on the
+    device (about 8 MB: (75 + 325 + 26) tile-blocks x 192 items x 16 B x 3 nets each way, plus the rows) by the time `engine = regtile` turns out not to
+    cover it; an RKC2 wind-mixing configuration has its coefficient table (kilobytes: there for the exit path) when `engine = fc32` does not."""
+    from colnde.nde import ENGINE_FC32
+    wide = synthetic.wind_mixing_problem(16, n_frames=3, weight_divisor=1e2, layer_sizes=(96, 400, 400, 31), activations=("swish", "swish", "identity"))
+    small = synthetic.wind_mixing_problem(16, n_frames=3)
+    for cfg, engine in ((wide.cfg, ENGINE_REGTILE), (small.cfg.with_(stepper="rkc2"), ENGINE_FC32)):
+        def refused():
+            with pytest.raises(colnde.ColndeError, match="requested, but it covers only"):
+                colnde.ColumnNDE(cfg, 16, engine=engine)
+
+        refused()                                                        # (warm-up of the error path)
+        before = _free_bytes()
+        for _ in range(8):
+            refused()
+        after = _free_bytes()
+        print("refused create x 8: free memory fell by %d bytes (%s)" % (before - after, "regtile on the wide network" if engine == ENGINE_REGTILE else "fc32, RKC2"))
+        assert before - after <= (8 << 20), (engine, before - after)
+
+
 def test_two_handles_in_two_host_threads_do_not_disturb_each_other():
     """include/colnde.h: one handle = one host thread AT A TIME; two handles may be driven by two threads at once (ctypes releases the GIL
     for the call).  Their results are bit-identical to the serial ones and colnde_last_error stays per thread."""
