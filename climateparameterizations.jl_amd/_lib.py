@@ -94,6 +94,7 @@ SYMBOLS = [
     ("colnde_ensemble_wm_embedded_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _V, ctypes.c_int] + [_V] * 9 + [ctypes.c_int]),
     ("colnde_create_fc_ensemble", ctypes.c_int, [_V, ctypes.c_int, ctypes.POINTER(_V)]),
     ("colnde_create_conv", ctypes.c_int, [_V, ctypes.c_int, ctypes.POINTER(_V)]),
+    ("colnde_create_conv_ensemble", ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_V)]),
     ("colnde_conv_filter", ctypes.c_int, [_V]),
     ("colnde_ensemble_column_loss_dev", ctypes.c_int, [_V, _V, _V]),
     ("colnde_ensemble_causal_penalty_dev", ctypes.c_int, [_V, _V, _V, _V]),

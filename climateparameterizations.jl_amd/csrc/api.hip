@@ -722,6 +722,13 @@ FcConv fc_conv_args(const colnde_handle* h) {
     cv.ctape = h->conv.d_ctape;
     return cv;
 }
+// ... model 0's, in a conv ensemble; model k's lie at these strides (its own vector of conv.n_params floats, its own conv tape)
+FcConvEns fc_conv_ens_args(const colnde_handle* h) {
+    FcConvEns ce;
+    ce.wb = (size_t)h->conv.n_params;
+    ce.ctape = h->conv.ctape_stride;
+    return ce;
+}
 
 // The operand images of the weights: one network's, or those of every model of a free-convection ensemble (FcEns strides).  The vector packed is the
 // caller's, or — behind a conv filter — its dense part with W1 padded to 4Nz x Nz (one small kernel on the stream)
@@ -729,7 +736,7 @@ int fc_pack(colnde_handle* h, const float* d_weights) {
     hipError_t e = hipSuccess;
     if (h->conv.c) {
         h->conv.d_user = d_weights;
-        e = launch_fc_conv_pad(d_weights, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->m.n_params, h->conv.d_wpad, h->stream);
+        e = launch_fc_conv_pad(d_weights, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->m.n_params, h->conv.d_wpad, h->stream, h->n_models, (size_t)h->conv.n_params);
         if (e != hipSuccess) return fail("conv weight padding launch failed: %s", hipGetErrorString(e));
         d_weights = h->conv.d_wpad;
     }
@@ -742,6 +749,7 @@ int fc_pack(colnde_handle* h, const float* d_weights) {
 int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int nc, int iv0, int iv1, int tape_iv0) {
     const size_t ns = h->m.ns;
     const FcConv cv = fc_conv_args(h);
+    const FcConvEns ce = fc_conv_ens_args(h);
     FcEns en = h->fens;
     en.x0 = iv0 == 0 ? 0 : en.sol;
     if (iv1 < 0) iv1 = h->cfg.n_save - 1;
@@ -752,7 +760,7 @@ int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int
     hipError_t e = fc_launch_forward(h->m, h->fc_cw, h->d_fc_imgf, (h->sp_fwd && fc_split_supported(h->fc_cw)) ? h->d_fc_simgf : nullptr, h->d_fc_bias, init, stride, h->d_bcs + (size_t)c0 * h->m.n_bc, h->d_times, h->cfg.n_save,
                                      iv0, iv1, tape_iv0, h->cfg.substeps, d_sol ? d_sol + (size_t)c0 * h->cfg.n_save * ns : nullptr,
                                      with_tape ? h->d_dwtape : nullptr, with_tape ? h->d_fc_masks : nullptr, with_tape ? h->d_fc_switch : nullptr, nc,
-                                     h->stream, h->ensemble ? &en : nullptr, h->conv.c ? &cv : nullptr);
+                                     h->stream, h->ensemble ? &en : nullptr, h->conv.c ? &cv : nullptr, &ce);
     if (e != hipSuccess) return fail("fc32 %sforward launch failed: %s", h->ensemble ? "ensemble " : "", hipGetErrorString(e));
     return 0;
 }

@@ -1,4 +1,4 @@
-// api_ensemble.hip — handles built on colnde_create: wind-mixing and free-convection ensembles, the conv network; the colnde_ensemble_* entry points.
+// api_ensemble.hip — handles built on colnde_create: wind-mixing and free-convection ensembles, the conv network and its ensembles; the colnde_ensemble_* entry points.
 #include "api_internal.h"
 #include "tape_plan.h"
 
@@ -255,6 +255,19 @@ static int conv_refusals(const colnde_config* cfg, int c) {
     return 0;
 }
 
+// Puts the c-tap filter in front of a plain fc32 handle: the user's layout, and the padded weight vector and gradient row of each of K models
+static hipError_t conv_attach(colnde_handle* h, int conv_filter, size_t K) {
+    const DevModel& m = h->m;
+    const int H = 4 * m.Nz, M = m.Nz - conv_filter + 1;
+    h->conv.w1_end = m.w_off[0] + H * M;
+    h->conv.n_zero = H * (conv_filter - 1);
+    h->conv.n_params = conv_filter + 1 + m.n_params - h->conv.n_zero;
+    hipError_t e = m.w_off[0] == 0 ? h->mem.alloc(&h->conv.d_wpad, K * (size_t)m.n_params) : hipErrorInvalidValue;
+    if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_gpad, K * ((size_t)m.n_params + 8));
+    if (e == hipSuccess) h->conv.c = conv_filter;
+    return e;
+}
+
 extern "C" int colnde_create_conv(const colnde_config* cfg, int conv_filter, colnde_handle** out) {
     if (!out) return fail("null out pointer");
     *out = nullptr;
@@ -266,18 +279,11 @@ extern "C" int colnde_create_conv(const colnde_config* cfg, int conv_filter, col
         colnde_destroy(h);
         return fail("colnde_create_conv: the configuration did not select the 16-column fc32 kernels");
     }
-    const DevModel& m = h->m;
-    const int H = 4 * m.Nz, M = m.Nz - conv_filter + 1;
-    h->conv.w1_end = m.w_off[0] + H * M;
-    h->conv.n_zero = H * (conv_filter - 1);
-    h->conv.n_params = conv_filter + 1 + m.n_params - h->conv.n_zero;
-    hipError_t e = m.w_off[0] == 0 ? h->mem.alloc(&h->conv.d_wpad, (size_t)m.n_params) : hipErrorInvalidValue;
-    if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_gpad, (size_t)m.n_params + 8);
+    const hipError_t e = conv_attach(h, conv_filter, 1);
     if (e != hipSuccess) {
         colnde_destroy(h);
         return fail("colnde_create_conv: allocating the padded weight and gradient vectors failed: %s", hipGetErrorString(e));
     }
-    h->conv.c = conv_filter;
     *out = h;
     return 0;
 }
@@ -285,6 +291,8 @@ extern "C" int colnde_create_conv(const colnde_config* cfg, int conv_filter, col
 // The tapes of all K models, planned once at creation by fc_plan_tapes' rules on a per-model budget of (free memory - margin) / K: one block of all columns
 // (column blocks do not occur at <= 4,096 columns), the whole time axis when it fits and time segments otherwise (COLNDE_FC_SEG=<intervals> forces), the
 // slice count a single handle of this size plans.  Refused with the bytes it needs when not even one save interval per segment fits.
+// A conv ensemble (h->conv.c): the conv tape rides in the bytes per column and interval, as in fc_plan_tapes; a model also owns its filter slab and its
+// padded weight vector and gradient row (tape_plan.h: fc_conv_ens_model_bytes).
 static int fc_ens_plan_tapes(colnde_handle* h) {
     const DevModel& m = h->m;
     const size_t K = (size_t)h->n_models;
@@ -292,15 +300,20 @@ static int fc_ens_plan_tapes(colnde_handle* h) {
     const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
     if (R != fc_record_row_floats(m.Nz)) return fail("fc32: record layout mismatch (%zu vs %zu floats per column)", R, fc_record_row_floats(m.Nz));
     const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE;
-    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0));
+    const int conv = h->conv.c;
+    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0) +
+                                                                 (conv ? fc_conv_tape_floats(m.Nz) / 16 * sizeof(float) : 0));
+    const size_t cslab_seg = (size_t)FC_CONV_GRAD_MAX_SLICES * FC_CONV_GRAD_SLOTS;          // floats of filter slab per time segment
     const int n32 = (h->n_col + 31) / 32 * 32;
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     const size_t budget = hbm_budget(free_b, (size_t)3 << 30) / K;
-    int seg = plan_fc_ens_seg(n32, n_iv, cw, m.Nz, per_col_iv, budget, m.n_params);
+    int seg = conv ? plan_fc_conv_ens_seg(n32, n_iv, cw, m.Nz, per_col_iv, budget, m.n_params, cslab_seg)
+                   : plan_fc_ens_seg(n32, n_iv, cw, m.Nz, per_col_iv, budget, m.n_params);
     const char* es = env_get(ENV_FC_SEG);
     if (es && atoi(es) >= 1) seg = std::min(n_iv, atoi(es));
-    const size_t need = fc_ens_model_bytes(n32, n_iv, cw, m.Nz, per_col_iv, m.n_params, seg);
+    const size_t need = conv ? fc_conv_ens_model_bytes(n32, n_iv, cw, m.Nz, per_col_iv, m.n_params, seg, cslab_seg)
+                             : fc_ens_model_bytes(n32, n_iv, cw, m.Nz, per_col_iv, m.n_params, seg);
     if (need > budget)
         return fail("a free-convection ensemble of %d models needs %zu bytes of device memory for its tapes and slab rows (%zu per model with %d save interval(s) per "
                     "time segment, %d substeps x %d stages); %zu bytes are free (3 GB kept in reserve): use fewer models per handle",
@@ -326,6 +339,13 @@ static int fc_ens_plan_tapes(colnde_handle* h) {
     if (e == hipSuccess) e = h->mem.alloc(&h->d_fc_masks, K * en.masks);
     if (e == hipSuccess && ca) e = h->mem.alloc(&h->d_fc_switch, K * en.swtape);
     if (e == hipSuccess && h->fc_nseg > 1) e = h->mem.alloc(&h->d_fc_lam, K * en.lam);
+    if (e == hipSuccess && conv) {                           // per model: the conv tape of the same records, and one single handle's filter slab
+        h->conv.cslab_rows = h->fc_nblocks * h->fc_nseg * FC_CONV_GRAD_MAX_SLICES;
+        h->conv.ctape_stride = n_rec * fc_conv_tape_floats(m.Nz);
+        h->conv.cslab_stride = (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS;
+        e = h->mem.alloc(&h->conv.d_ctape, K * h->conv.ctape_stride);
+        if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_cslab, K * h->conv.cslab_stride);
+    }
     if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = h->mem.alloc(&h->d_slab, K * en.slab);
@@ -336,13 +356,17 @@ static int fc_ens_plan_tapes(colnde_handle* h) {
     }
     h->ens.slab = en.slab;
     h->ens_model_bytes = (en.dwtape + en.slab + (h->fc_nseg > 1 ? en.lam : 0)) * sizeof(float) + en.masks * sizeof(unsigned int) + en.swtape * sizeof(unsigned long long);
+    if (conv) h->ens_model_bytes += (h->conv.ctape_stride + h->conv.cslab_stride + 2 * (size_t)m.n_params + 8) * sizeof(float);
     return 0;
 }
 
-extern "C" int colnde_create_fc_ensemble(const colnde_config* cfg, int n_models, colnde_handle** out) {
+// conv_filter = 0: K plain networks (colnde_create_fc_ensemble); c = 2..8: K --conv networks of that filter length (colnde_create_conv_ensemble), whose
+// refusals are the union of the two creators', each in its own words
+static int create_fc_ensemble(const colnde_config* cfg, int conv_filter, int n_models, colnde_handle** out) {
     if (!out) return fail("null out pointer");
     *out = nullptr;
     if (validate(cfg)) return 1;
+    if (conv_filter && conv_refusals(cfg, conv_filter)) return 1;
     if (fc_ens_refusals(cfg, n_models)) return 1;
     colnde_handle* h = nullptr;
     if (colnde_create(cfg, &h)) return 1;
@@ -352,11 +376,19 @@ extern "C" int colnde_create_fc_ensemble(const colnde_config* cfg, int n_models,
     }
     h->ensemble = true;
     h->n_models = n_models;
-    const size_t K = (size_t)n_models, P = (size_t)h->m.n_params;
+    if (conv_filter) {
+        const hipError_t ec = conv_attach(h, conv_filter, (size_t)n_models);
+        if (ec != hipSuccess) {
+            colnde_destroy(h);
+            return fail("colnde_create_conv_ensemble: allocating the padded weight and gradient vectors of %d models failed: %s", n_models, hipGetErrorString(ec));
+        }
+    }
+    // P: the floats of a model's vector as the caller passes it (d_w, d_out); the kernels pack the plain network's (en.w), padded behind a filter
+    const size_t K = (size_t)n_models, P = (size_t)user_params(h);
     const int Nz = h->m.Nz;
     FcEns& en = h->fens;
     en.n_models = n_models;
-    en.w = P;
+    en.w = (size_t)h->m.n_params;
     en.img = fc_image_floats(Nz);
     en.simg = fc_split_image_words(Nz);
     en.bias = (fc_bias_floats(Nz) + 3) / 4 * 4;
@@ -376,10 +408,22 @@ extern "C" int colnde_create_fc_ensemble(const colnde_config* cfg, int n_models,
     return 0;
 }
 
+extern "C" int colnde_create_fc_ensemble(const colnde_config* cfg, int n_models, colnde_handle** out) { return create_fc_ensemble(cfg, 0, n_models, out); }
+
+// ---- conv ensembles (colnde_create_conv_ensemble): K --conv networks of one filter length side by side ------------------------------------------------
+// The product of the two handles above: the 16-column kernels' third entry points (fc_forward_conv_ens_kernel, fc_adjoint_conv_ens_kernel) carry the model
+// index AND the filter; the pad, filter-gradient and fold kernels take K models in grid.y.  Row k of every result is, bit for bit, what a
+// colnde_create_conv handle computes for model k's weights: the same records, slices, slab rows and orders of summation, at a stride.
+extern "C" int colnde_create_conv_ensemble(const colnde_config* cfg, int conv_filter, int n_models, colnde_handle** out) {
+    if (out) *out = nullptr;
+    if (conv_filter == 0) return fail("conv_filter = 0 outside 2..%d: K plain networks are colnde_create_fc_ensemble's", FC_CONV_MAX);
+    return create_fc_ensemble(cfg, conv_filter, n_models, out);
+}
+
 static int ensemble_only(const colnde_handle* h) {
     if (!h) return fail("null handle");
     if (h->closure) return fail("colnde_ensemble_* take weight vectors, but this is a closure handle (no networks): use colnde_closure_* (include/colnde.h)");
-    if (h->conv.c) return fail("colnde_ensemble_* do not cover the convolutional first layer of a colnde_create_conv handle (conv=%d): ensembles of conv networks are out of scope", h->conv.c);
+    if (h->conv.c && !h->ensemble) return fail("colnde_ensemble_* do not cover the convolutional first layer of a colnde_create_conv handle (conv=%d): ensembles of conv networks are out of scope", h->conv.c);
     if (!h->ensemble) return fail("not an ensemble handle: colnde_ensemble_* take the handles of colnde_create_ensemble (colnde_create: the single-model calls)");
     return 0;
 }
@@ -406,7 +450,10 @@ extern "C" int colnde_ensemble_causal_penalty_dev(colnde_handle* h, const float*
     if (!d_weights || !d_coeff || !d_result) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
     Timed tm(h, K_REDUCE);
-    hipError_t e = launch_causal_penalty(d_weights, d_coeff, d_result, h->m.Nz, h->m.w_off[0], h->m.n_params, h->n_models, h->stream);
+    // the first Dense weight as the caller's vector holds it: 4Nz x Nz at its offset, or — behind a filter — 4Nz x (Nz - c + 1) at c + 1
+    const int c = h->conv.c;
+    hipError_t e = launch_causal_penalty(d_weights, d_coeff, d_result, 4 * h->m.Nz, c ? h->m.Nz - c + 1 : h->m.Nz, c ? c + 1 : h->m.w_off[0], user_params(h), h->n_models,
+                                         h->stream);
     if (e != hipSuccess) return fail("causal penalty launch failed: %s", hipGetErrorString(e));
     return 0;
 }
@@ -511,7 +558,7 @@ extern "C" int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights,
     if (ensemble_only(h)) return 1;
     if (!weights || !scalings || !out) return fail("null pointer argument");
     HIPCHK(hipSetDevice(h->device));
-    const size_t K = (size_t)h->n_models, P = (size_t)h->m.n_params;
+    const size_t K = (size_t)h->n_models, P = (size_t)user_params(h);
     HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * K * P, hipMemcpyHostToDevice, h->stream));
     if (colnde_ensemble_loss_grad_dev(h, h->d_w, scalings, h->d_out)) return 1;
     HIPCHK(hipMemcpyAsync(out, h->d_out, sizeof(float) * K * (P + 8), hipMemcpyDeviceToHost, h->stream));
@@ -527,8 +574,8 @@ extern "C" int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights,
     if (!(beta1_t < 1.0f && beta2_t < 1.0f)) return fail("running powers beta^t must be < 1");
     HIPCHK(hipSetDevice(h->device));
     Timed tm(h, K_ADAM);
-    hipError_t e = launch_adam_ensemble(d_weights, d_result, h->m.n_params + 8, d_m, d_v, d_eta, beta1, beta2, eps, beta1_t, beta2_t, h->m.n_params,
-                                        h->n_models, h->stream);
+    const int np = user_params(h);
+    hipError_t e = launch_adam_ensemble(d_weights, d_result, np + 8, d_m, d_v, d_eta, beta1, beta2, eps, beta1_t, beta2_t, np, h->n_models, h->stream);
     if (e != hipSuccess) return fail("ensemble ADAM launch failed: %s", hipGetErrorString(e));
     return 0;
 }

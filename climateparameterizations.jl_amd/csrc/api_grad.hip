@@ -306,9 +306,11 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
     const char* ens = h->ensemble ? "ensemble " : "";
     if (fc_pack(h, d_weights)) return 1;
     const FcConv cv = fc_conv_args(h);                                  // (after the plan: the conv tape exists)
+    const FcConvEns ce = fc_conv_ens_args(h);
+    const size_t cslab_model = (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS;      // the filter slab of one model
     hipError_t e;
     HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->fc_rows * stride * sizeof(float), h->stream));
-    if (h->conv.c) HIPCHK(hipMemsetAsync(h->conv.d_cslab, 0, (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS * sizeof(float), h->stream));
+    if (h->conv.c) HIPCHK(hipMemsetAsync(h->conv.d_cslab, 0, (size_t)K * cslab_model * sizeof(float), h->stream));
     const int cw = h->fc_cw;
     const int n_wg = (h->n_col + cw - 1) / cw, n_iv = h->cfg.n_save - 1, nseg = h->fc_nseg;
     const size_t gemm_rows0 = (size_t)n_wg * nseg;                      // slab: [tile][segment] adjoint rows, then [block][segment][slice] GEMM rows
@@ -327,7 +329,7 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
                 e = fc_launch_adjoint(h->m, h->fc_cw, h->d_fc_imgb, (h->sp_adj && fc_split_supported(h->fc_cw)) ? h->d_fc_simgb : nullptr, h->d_times, h->cfg.n_save, iv0, iv1, h->cfg.substeps, h->d_sol + (size_t)c0 * h->cfg.n_save * ns,
                                       h->d_truth + (size_t)c0 * h->cfg.n_save * ns, h->d_dwtape, h->d_fc_masks, h->d_fc_switch, lw.w[2],
                                       nseg > 1 ? h->d_fc_lam + (size_t)c0 * h->m.Nz : nullptr,
-                                      h->d_slab + ((size_t)sg * n_wg + (size_t)(c0 / cw)) * stride, nc, h->stream, en, h->conv.c ? &cv : nullptr);
+                                      h->d_slab + ((size_t)sg * n_wg + (size_t)(c0 / cw)) * stride, nc, h->stream, en, h->conv.c ? &cv : nullptr, &ce);
                 if (e != hipSuccess) return fail("fc32 %sadjoint launch failed: %s", ens, hipGetErrorString(e));
             }
             {
@@ -339,9 +341,10 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
                 e = launch_dw_gemm(h->d_dwtape, tiles_b * (cw / 16) * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst, (int)dwtape_row_floats(h->m), h->d_macros,
                                    h->n_macros, h->dw_slices, h->d_slab + (gemm_rows0 + ((size_t)b * nseg + sg) * h->dw_slices) * stride, stride, h->stream, K, h->fens.dwtape, h->fens.slab);
                 if (e != hipSuccess) return fail("%sdW GEMM launch failed: %s", ens, hipGetErrorString(e));
-                if (h->conv.c) {                                        // the filter's c + 1 entries, from the conv tape of the same records
+                if (h->conv.c) {                                        // the filter's c + 1 entries (every model's), from the conv tape of the same records
                     e = launch_fc_conv_grad(h->conv.d_ctape, (long)(tiles_b * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst) * 16, h->m.Nz, h->conv.c,
-                                            h->conv.d_cslab + ((size_t)b * nseg + sg) * FC_CONV_GRAD_MAX_SLICES * FC_CONV_GRAD_SLOTS, h->stream);
+                                            h->conv.d_cslab + ((size_t)b * nseg + sg) * FC_CONV_GRAD_MAX_SLICES * FC_CONV_GRAD_SLOTS, h->stream, K, h->conv.ctape_stride,
+                                            h->conv.cslab_stride);
                     if (e != hipSuccess) return fail("conv filter gradient launch failed: %s", hipGetErrorString(e));
                 }
             }
@@ -353,7 +356,7 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
         if (e != hipSuccess) return fail("%sreduce launch failed: %s", ens, hipGetErrorString(e));
         if (h->conv.c) {                                                // the user's layout: filter entries in front, W1's padded columns dropped
             e = launch_fc_conv_fold(h->conv.d_gpad, h->conv.d_cslab, h->conv.cslab_rows, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->conv.n_params + 8, d_out,
-                                    h->stream);
+                                    h->stream, K, (size_t)stride, h->conv.cslab_stride);
             if (e != hipSuccess) return fail("conv gradient fold launch failed: %s", hipGetErrorString(e));
         }
     }

@@ -39,6 +39,7 @@ void loss_weights(const colnde_handle* h, const float scalings[6], LossWeights* 
 int pack(colnde_handle* h, const float* d_weights);
 int fc_pack(colnde_handle* h, const float* d_weights);
 FcConv fc_conv_args(const colnde_handle* h);
+FcConvEns fc_conv_ens_args(const colnde_handle* h);
 int ensure_tmp(colnde_handle* h, size_t n_columns);
 int ensure_ag(colnde_handle* h, size_t tiles);
 void drain_events(colnde_handle* h);
@@ -157,6 +158,7 @@ struct ConvBlock {
     float* d_ctape = nullptr;       // [record][16][2 Nz] stage inputs and filter cotangents (planned with the other tapes)
     float* d_cslab = nullptr;       // [block][segment][FC_CONV_GRAD_MAX_SLICES][FC_CONV_GRAD_SLOTS] the filter gradient's partial sums
     int cslab_rows = 0;
+    size_t ctape_stride = 0, cslab_stride = 0;   // a conv ensemble: floats from one model's conv tape / filter slab to the next's (d_wpad: m.n_params, d_gpad: + 8)
 };
 
 struct colnde_handle {

@@ -33,17 +33,21 @@ hipError_t launch_loss_per_tstep(const float* sol, const float* truth, int n_col
 hipError_t launch_rel_diff_max(const float* a, const float* b, long n_rows, int row, float floor, float* partial, float* out, hipStream_t stream);
 // Free-convection ensembles.  out[k][c][n] = mean over Nz (32 | 64) levels of (sol[k][c][n][:] - truth[c][n][:])^2; rows_per_model = n_col * n_save
 hipError_t launch_column_loss(const float* sol, const float* truth, int Nz, long rows_per_model, int n_models, float* out, hipStream_t stream);
-// result[k][n_params + 6] += coeff[k] * sum_{r < q} W1_k[r, q]^2, result[k][index of W1[r, q]] += 2 coeff[k] W1_k[r, q] (W1: 4 Nz x Nz at w1_off,
-// column-major); w [K][n_params], result [K][n_params + 8]; coeff[k] = 0 leaves row k untouched
-hipError_t launch_causal_penalty(const float* w, const float* coeff, float* result, int Nz, int w1_off, int n_params, int n_models, hipStream_t stream);
-// The --conv network (colnde_create_conv).  theta: the user's vector [w (c); b; W1 (4Nz x M); ...]; padded: the plain network's, W1 as 4Nz x Nz with
+// result[k][n_params + 6] += coeff[k] * sum_{r < q} W1_k[r, q]^2, result[k][index of W1[r, q]] += 2 coeff[k] W1_k[r, q] (W1: H x M at w1_off,
+// column-major, M <= H — the plain network: 4 Nz x Nz; behind a c-tap filter: 4 Nz x (Nz - c + 1) at c + 1); w [K][n_params], result [K][n_params + 8];
+// coeff[k] = 0 leaves row k untouched
+hipError_t launch_causal_penalty(const float* w, const float* coeff, float* result, int H, int M, int w1_off, int n_params, int n_models, hipStream_t stream);
+// The --conv network (colnde_create_conv; n_models > 1: a conv ensemble, model k's arrays at the given strides, in floats).  theta: the user's vector [w (c); b; W1 (4Nz x M); ...]; padded: the plain network's, W1 as 4Nz x Nz with
 // n_zero = 4Nz (c - 1) zeros behind its w1_end = w1_off + 4Nz M entries.
-hipError_t launch_fc_conv_pad(const float* theta, int c, int w1_end, int n_zero, int n_pad, float* padded, hipStream_t stream);
+hipError_t launch_fc_conv_pad(const float* theta, int c, int w1_end, int n_zero, int n_pad, float* padded, hipStream_t stream, int n_models = 1,
+                              size_t theta_stride = 0);
 // The filter's gradient from n_rows (record, column) rows of the conv tape ([x (Nz) | z̄ (Nz)], Nz = 32 | 64): fc_conv_grad_slices(n_rows) rows of
 // FC_CONV_GRAD_SLOTS floats at slab_rows (slot d: d/dw[c - d], the last slot: d/db), every sum in a fixed order
 #define FC_CONV_GRAD_SLOTS 9
 #define FC_CONV_GRAD_MAX_SLICES 256
 int fc_conv_grad_slices(long n_rows);
-hipError_t launch_fc_conv_grad(const float* ctape, long n_rows, int Nz, int c, float* slab_rows, hipStream_t stream);
+hipError_t launch_fc_conv_grad(const float* ctape, long n_rows, int Nz, int c, float* slab_rows, hipStream_t stream, int n_models = 1, size_t ctape_stride = 0,
+                               size_t slab_stride = 0);
 // out [n_out = user parameters + 8]: the filter entries summed over the n_rows rows of the filter slab, then gpad [padded + 8] without W1's padded columns
-hipError_t launch_fc_conv_fold(const float* gpad, const float* cslab, int n_rows, int c, int w1_end, int n_zero, int n_out, float* out, hipStream_t stream);
+hipError_t launch_fc_conv_fold(const float* gpad, const float* cslab, int n_rows, int c, int w1_end, int n_zero, int n_out, float* out, hipStream_t stream,
+                               int n_models = 1, size_t gpad_stride = 0, size_t cslab_stride = 0);

@@ -576,19 +576,20 @@ hipError_t launch_column_loss(const float* sol, const float* truth, int Nz, long
 }
 
 // The soft spatial-causality penalty of train_free_convection_nde.jl:186-197 for every model: c_k sum_{r < q} W1_k[r, q]^2 over the strict upper triangle of
-// the first Dense weight (4 Nz x Nz, W1[r, q] at w1_off + q * 4 Nz + r: Flux.destructure's column-major order), added to the total of the model's result
+// the first Dense weight (H x M, W1[r, q] at w1_off + q * H + r: Flux.destructure's column-major order; the plain network: 4 Nz x Nz at offset 0, the
+// --conv network: 4 Nz x (Nz - c + 1) at offset c + 1 — ps[dense_layer_params_idx], :189-195; M <= H), added to the total of the model's result
 // row, and its gradient 2 c_k W1_k[r, q] added to the row's gradient entries.  One workgroup per model; thread t owns the masked entries e = t, t + 256, ...
 // of the triangle's column-by-column enumeration and the partial sums meet in a fixed tree, so the value is bit-reproducible.  c_k = 0: the row is not
 // touched at all (not even rewritten).  Plain vector loads and stores; every entry has one owner, so nothing is atomic.
 __global__ void __launch_bounds__(256) causal_penalty_kernel(const float* __restrict__ w, const float* __restrict__ coeff, float* __restrict__ result,
-                                                             int Nz, int w1_off, int n_params) {
+                                                             int H, int M, int w1_off, int n_params) {
     __shared__ float part[256];
     const size_t k = blockIdx.x;
     const float c = coeff[k];
     if (c == 0.0f) return;                                           // (uniform over the workgroup)
     const float* W = w + k * (size_t)n_params + w1_off;
     float* row = result + k * ((size_t)n_params + 8);
-    const int H = 4 * Nz, n_mask = Nz * (Nz - 1) / 2;
+    const int n_mask = M * (M - 1) / 2;
     float s = 0.0f;
     for (int e = threadIdx.x; e < n_mask; e += 256) {
         // column q holds the q entries r = 0 .. q - 1; entries of columns < q: q (q - 1) / 2
@@ -610,9 +611,9 @@ __global__ void __launch_bounds__(256) causal_penalty_kernel(const float* __rest
     if (threadIdx.x == 0) row[n_params + 6] += c * part[0];
 }
 
-hipError_t launch_causal_penalty(const float* w, const float* coeff, float* result, int Nz, int w1_off, int n_params, int n_models, hipStream_t stream) {
-    if (Nz < 2 || n_models < 1 || w1_off < 0 || w1_off + 4 * Nz * Nz > n_params) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(causal_penalty_kernel, dim3(n_models), dim3(256), 0, stream, w, coeff, result, Nz, w1_off, n_params);
+hipError_t launch_causal_penalty(const float* w, const float* coeff, float* result, int H, int M, int w1_off, int n_params, int n_models, hipStream_t stream) {
+    if (M < 2 || M > H || n_models < 1 || w1_off < 0 || (long)w1_off + (long)H * M > n_params) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(causal_penalty_kernel, dim3(n_models), dim3(256), 0, stream, w, coeff, result, H, M, w1_off, n_params);
     return hipGetLastError();
 }
 
@@ -622,21 +623,29 @@ hipError_t launch_causal_penalty(const float* w, const float* coeff, float* resu
 //   theta  = [w (c); b; vec(W1) (4Nz x M, column-major, M = Nz - c + 1); b1; W2; b2; W3; b3]        the user's vector (Flux.params order)
 //   padded = [vec(W1), 4Nz (c - 1) zeros; b1; ...]                                                  the plain network's vector the engine packs
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) fc_conv_pad_kernel(const float* __restrict__ theta, int c, int w1_end, int n_zero, int n_pad, float* __restrict__ padded) {
+// (blockIdx.y = model of a conv ensemble: the user's vectors theta_stride floats apart, the padded ones n_pad)
+__global__ void __launch_bounds__(256) fc_conv_pad_kernel(const float* __restrict__ theta, int c, int w1_end, int n_zero, int n_pad, float* __restrict__ padded,
+                                                           size_t theta_stride) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n_pad) return;
+    theta += blockIdx.y * theta_stride;
+    padded += blockIdx.y * (size_t)n_pad;
     padded[p] = p < w1_end ? theta[c + 1 + p] : (p < w1_end + n_zero ? 0.0f : theta[c + 1 + p - n_zero]);
 }
 
 // The filter's gradient from the conv tape [row = (record, column)][x (Nz) | z̄ (Nz)]: slot d of a workgroup's output row is the sum over its rows and
 // levels of z̄[i] x[i + d] (= ∂/∂w[c - d], 1-based), slot FC_CG_SLOTS - 1 the sum of z̄ (= ∂/∂b).  Lane = level (Nz = 32: two rows per wave); x[i + d]
 // comes from the lane d above — within the row wherever z̄[i] can be non-zero (i < M).  Every sum in a fixed order: a thread over its rows, then one
-// thread per slot over the 256 partial sums.
+// thread per slot over the 256 partial sums.  blockIdx.y = model of a conv ensemble (its tape and its slab rows at a stride): the sums of a model are
+// those of a single handle, in the same order.
 #define FC_CG_TAPS 8                               // = FC_CONV_MAX (engine_fc.h)
 #define FC_CG_SLOTS (FC_CG_TAPS + 1)
 template <int NZ>
-__global__ void __launch_bounds__(256) fc_conv_grad_kernel(const float* __restrict__ ctape, long n_rows, long rows_per_wg, int c, float* __restrict__ out) {
+__global__ void __launch_bounds__(256) fc_conv_grad_kernel(const float* __restrict__ ctape, long n_rows, long rows_per_wg, int c, float* __restrict__ out,
+                                                            size_t ctape_stride, size_t out_stride) {
     __shared__ float scr[FC_CG_SLOTS][256];
+    ctape += blockIdx.y * ctape_stride;
+    out += blockIdx.y * out_stride;
     constexpr int RPB = 256 / NZ;                   // rows in flight per workgroup
     const int tid = threadIdx.x, i = tid & (NZ - 1), rs = tid / NZ;
     const long r0 = (long)blockIdx.x * rows_per_wg, r1 = r0 + rows_per_wg < n_rows ? r0 + rows_per_wg : n_rows;
@@ -664,11 +673,14 @@ __global__ void __launch_bounds__(256) fc_conv_grad_kernel(const float* __restri
 }
 
 // The user's result [c + 1 filter entries; the padded gradient without W1's padded columns (exactly zero: their input is); 8 loss slots]: the filter
-// entries are the sums over the rows of the filter slab, in row order.
+// entries are the sums over the rows of the filter slab, in row order.  blockIdx.y = model of a conv ensemble (strides in floats; the rows of out: n_out).
 __global__ void __launch_bounds__(256) fc_conv_fold_kernel(const float* __restrict__ gpad, const float* __restrict__ cslab, int n_rows, int c, int w1_end,
-                                                            int n_zero, int n_out, float* __restrict__ out) {
+                                                            int n_zero, int n_out, float* __restrict__ out, size_t gpad_stride, size_t cslab_stride) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= n_out) return;
+    gpad += blockIdx.y * gpad_stride;
+    cslab += blockIdx.y * cslab_stride;
+    out += blockIdx.y * (size_t)n_out;
     if (idx <= c) {
         const int slot = idx < c ? c - 1 - idx : FC_CG_SLOTS - 1;
         float s = 0.0f;
@@ -680,9 +692,9 @@ __global__ void __launch_bounds__(256) fc_conv_fold_kernel(const float* __restri
     out[idx] = gpad[q < w1_end ? q : q + n_zero];
 }
 
-hipError_t launch_fc_conv_pad(const float* theta, int c, int w1_end, int n_zero, int n_pad, float* padded, hipStream_t stream) {
-    if (c < 2 || c > FC_CG_TAPS || w1_end < 1 || n_zero < 1 || n_pad < w1_end + n_zero) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(fc_conv_pad_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, stream, theta, c, w1_end, n_zero, n_pad, padded);
+hipError_t launch_fc_conv_pad(const float* theta, int c, int w1_end, int n_zero, int n_pad, float* padded, hipStream_t stream, int n_models, size_t theta_stride) {
+    if (c < 2 || c > FC_CG_TAPS || w1_end < 1 || n_zero < 1 || n_pad < w1_end + n_zero || n_models < 1 || n_models > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fc_conv_pad_kernel, dim3((n_pad + 255) / 256, n_models), dim3(256), 0, stream, theta, c, w1_end, n_zero, n_pad, padded, theta_stride);
     return hipGetLastError();
 }
 
@@ -691,18 +703,21 @@ int fc_conv_grad_slices(long n_rows) {
     return (int)(s < 1 ? 1 : (s > FC_CONV_GRAD_MAX_SLICES ? FC_CONV_GRAD_MAX_SLICES : s));
 }
 
-hipError_t launch_fc_conv_grad(const float* ctape, long n_rows, int Nz, int c, float* slab_rows, hipStream_t stream) {
-    if (n_rows < 1 || c < 2 || c > FC_CG_TAPS || (Nz != 32 && Nz != 64)) return hipErrorInvalidValue;
+hipError_t launch_fc_conv_grad(const float* ctape, long n_rows, int Nz, int c, float* slab_rows, hipStream_t stream, int n_models, size_t ctape_stride,
+                               size_t slab_stride) {
+    if (n_rows < 1 || c < 2 || c > FC_CG_TAPS || (Nz != 32 && Nz != 64) || n_models < 1 || n_models > 65535) return hipErrorInvalidValue;
     const int n_wg = fc_conv_grad_slices(n_rows);
     const int rpb = 256 / Nz;
     const long per = ((n_rows + n_wg - 1) / n_wg + rpb - 1) / rpb * rpb;
-    if (Nz == 64) hipLaunchKernelGGL(fc_conv_grad_kernel<64>, dim3(n_wg), dim3(256), 0, stream, ctape, n_rows, per, c, slab_rows);
-    else hipLaunchKernelGGL(fc_conv_grad_kernel<32>, dim3(n_wg), dim3(256), 0, stream, ctape, n_rows, per, c, slab_rows);
+    if (Nz == 64) hipLaunchKernelGGL(fc_conv_grad_kernel<64>, dim3(n_wg, n_models), dim3(256), 0, stream, ctape, n_rows, per, c, slab_rows, ctape_stride, slab_stride);
+    else hipLaunchKernelGGL(fc_conv_grad_kernel<32>, dim3(n_wg, n_models), dim3(256), 0, stream, ctape, n_rows, per, c, slab_rows, ctape_stride, slab_stride);
     return hipGetLastError();
 }
 
-hipError_t launch_fc_conv_fold(const float* gpad, const float* cslab, int n_rows, int c, int w1_end, int n_zero, int n_out, float* out, hipStream_t stream) {
-    if (n_rows < 1 || c < 2 || c > FC_CG_TAPS || n_out <= c + 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(fc_conv_fold_kernel, dim3((n_out + 255) / 256), dim3(256), 0, stream, gpad, cslab, n_rows, c, w1_end, n_zero, n_out, out);
+hipError_t launch_fc_conv_fold(const float* gpad, const float* cslab, int n_rows, int c, int w1_end, int n_zero, int n_out, float* out, hipStream_t stream,
+                               int n_models, size_t gpad_stride, size_t cslab_stride) {
+    if (n_rows < 1 || c < 2 || c > FC_CG_TAPS || n_out <= c + 1 || n_models < 1 || n_models > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fc_conv_fold_kernel, dim3((n_out + 255) / 256, n_models), dim3(256), 0, stream, gpad, cslab, n_rows, c, w1_end, n_zero, n_out, out,
+                       gpad_stride, cslab_stride);
     return hipGetLastError();
 }

@@ -39,6 +39,12 @@ struct FcConv {
     float* ctape = nullptr;
 };
 static inline size_t fc_conv_tape_floats(int Nz) { return (size_t)16 * 2 * Nz; }       // per record (16-column tile and stage)
+// A conv ensemble (colnde_create_conv_ensemble): what model k owns of the filter's lies at k strides from model 0's — the taps and bias at the head of
+// its own parameter vector (wb floats apart: the conv parameter count) and its conv tape (ctape floats apart).  Passed by value to the CONV + ENS
+// entry points only, beside FcConv (model 0's pointers) and FcEns: the argument blocks of the other entry points stay as they are.
+struct FcConvEns {
+    size_t wb = 0, ctape = 0;
+};
 // ens != null (cw = 16, both image kinds given): the images of all ens->n_models models, weights ens->w floats apart
 hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf, float* imgb, float* bias, unsigned int* simgf, unsigned int* simgb,
                           hipStream_t stream, const FcEns* ens = nullptr);
@@ -50,14 +56,14 @@ hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf
 hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const unsigned int* simgf, const float* bias, const float* x0, size_t x0_stride,
                              const float* bcs, const float* save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps, float* sol,
                              float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens = nullptr,
-                             const FcConv* conv = nullptr);
+                             const FcConv* conv = nullptr, const FcConvEns* cens = nullptr);
 // slab: one row of n_params + 8 floats per tile (bias gradients and the squared-error sum; the weight gradients are the dW GEMM's).
 // lam_io [columns padded to 32][Nz]: carries λ between the time segments of a segmented gradient pass (null when one launch covers the axis).
 hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const unsigned int* simgb, const float* save_times, int n_save, int iv_begin, int iv_end,
                              int substeps,
                              const float* sol, const float* truth, float* dwtape, const unsigned int* masks, const unsigned long long* swtape,
                              float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens = nullptr,
-                             const FcConv* conv = nullptr);
+                             const FcConv* conv = nullptr, const FcConvEns* cens = nullptr);
 // compute_neural_network_forcing! (double_gyre_nn.jl:149-168): T [n_col][Nz] model units, top_flux [n_col], out = -dz(wT) on cell centres
 hipError_t fc_launch_infer(const DevModel& m, int cw, const float* imgf, const float* bias, const float* T, const float* top_flux, float inv_dz,
                            float* out, int n_col, hipStream_t stream);

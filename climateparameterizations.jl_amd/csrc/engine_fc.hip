@@ -276,6 +276,7 @@ typedef unsigned long long u64;
 //   CONV: the --conv network (FcConv, engine_fc.h) — the filter is applied where the stage input goes to LDS.  The kernel's text is ONE body
 //        (fc_forward_body.inc) behind two entry points: fc_forward_kernel (name and arguments as they were; CONV = false) and fc_forward_conv_kernel, which
 //        adds the FcConv argument.  A template flag on fc_forward_kernel itself would rename every existing instantiation and lengthen its argument block.
+//        ENS and CONV together (a conv ensemble) is a third entry point for the same reason: fc_forward_conv_ens_kernel, below.
 // the filter's pre-activation for this lane's level from the column's levels in the lanes above (d = 0: the lane's own): ONE instruction sequence for the
 // forward kernel and for the adjoint's recomputation, so that both see the same bits and the same sign
 __device__ __forceinline__ float fc_conv_pre(float x, const float (&cw)[FC_CONV_MAX], float cb, int c) {
@@ -314,6 +315,21 @@ fc_forward_conv_kernel(const void* __restrict__ imgf, const float* __restrict__ 
     constexpr int CW = 16;
     constexpr bool ENS = false, CONV = true;
     const FcEns en = FcEns();
+#include "fc_forward_body.inc"
+}
+// ENS and CONV together (colnde_create_conv_ensemble): blockIdx.y = model.  The body offsets what FcEns names; the filter's two pointers are offset here,
+// once, the same way — scalar arithmetic on kernel arguments (cv0: model 0's, ce: the strides), before the body reads the taps.
+template <int NZ, bool TAPE, bool CA, bool RKC, bool SPLIT>
+__global__ void __launch_bounds__(256, 2)
+fc_forward_conv_ens_kernel(const void* __restrict__ imgf, const float* __restrict__ bias, const float* __restrict__ x0, size_t x0_stride,
+                           const float* __restrict__ bcs, const float* __restrict__ save_times, int n_save, int iv_begin, int iv_end, int tape_iv0,
+                           int substeps, float CN, float caKN, int nst, const float* __restrict__ rkc, float* __restrict__ sol, float* __restrict__ dwtape,
+                           u32* __restrict__ masks, u64* __restrict__ swtape, int n_col, FcConv cv0, FcEns en, FcConvEns ce) {
+    constexpr int CW = 16;
+    constexpr bool ENS = true, CONV = true;
+    FcConv cv = cv0;
+    cv.wb += (size_t)blockIdx.y * ce.wb;
+    if constexpr (TAPE) cv.ctape += (size_t)blockIdx.y * ce.ctape;
 #include "fc_forward_body.inc"
 }
 
@@ -405,6 +421,19 @@ fc_adjoint_conv_kernel(const void* __restrict__ imgb, const float* __restrict__ 
     const FcEns en = FcEns();
 #include "fc_adjoint_body.inc"
 }
+template <int NZ, bool CA, bool RKC, bool SPLIT>
+__global__ void __launch_bounds__(256, 2)
+fc_adjoint_conv_ens_kernel(const void* __restrict__ imgb, const float* __restrict__ save_times, int n_save, int iv_begin, int iv_end, int substeps, float CN,
+                           float caKN, int nst, const float* __restrict__ rkc, const float* __restrict__ sol, const float* __restrict__ truth,
+                           float* __restrict__ dwtape, const u32* __restrict__ masks, const u64* __restrict__ swtape, float w_loss, float* __restrict__ lam_io,
+                           float* __restrict__ slab, FcGrad go, int n_col, FcConv cv0, FcEns en, FcConvEns ce) {
+    constexpr int CW = 16;
+    constexpr bool ENS = true, CONV = true;
+    FcConv cv = cv0;
+    cv.wb += (size_t)blockIdx.y * ce.wb;
+    cv.ctape += (size_t)blockIdx.y * ce.ctape;
+#include "fc_adjoint_body.inc"
+}
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -474,6 +503,17 @@ hipError_t fc_set_kernel_attributes() {
     FC_FOR_EACH_ADJ16(FC_ATTR_AC)
 #undef FC_ATTR_FC
 #undef FC_ATTR_AC
+    // ... and those of a conv ensemble
+#define FC_ATTR_FCE(N, W, T, C, K)                                                                                                                                       \
+    if ((e = hipFuncSetAttribute((const void*)(fc_forward_conv_ens_kernel<N, T, C, K, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_fwd<N, W>())) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)(fc_forward_conv_ens_kernel<N, T, C, K, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_fwd<N, W>())) != hipSuccess) return e;
+#define FC_ATTR_ACE(N, W, C, K)                                                                                                                                          \
+    if ((e = hipFuncSetAttribute((const void*)(fc_adjoint_conv_ens_kernel<N, C, K, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_adj<N, W>())) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)(fc_adjoint_conv_ens_kernel<N, C, K, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fc_lds_adj<N, W>())) != hipSuccess) return e;
+    FC_FOR_EACH_FWD16(FC_ATTR_FCE)
+    FC_FOR_EACH_ADJ16(FC_ATTR_ACE)
+#undef FC_ATTR_FCE
+#undef FC_ATTR_ACE
 #undef FC_ATTR_F
 #undef FC_ATTR_A
 #undef FC_ATTR_I
@@ -531,18 +571,25 @@ hipError_t fc_launch_infer(const DevModel& m, int cw, const float* imgf, const f
 
 hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const unsigned int* simgf, const float* bias, const float* x0, size_t x0_stride,
                              const float* bcs, const float* save_times, int n_save, int iv_begin, int iv_end, int tape_iv0, int substeps, float* sol,
-                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens, const FcConv* conv) {
+                             float* dwtape, unsigned int* masks, unsigned long long* swtape, int n_col, hipStream_t stream, const FcEns* ens, const FcConv* conv, const FcConvEns* cens) {
     if (n_col < 1 || iv_begin < 0 || iv_end > n_save - 1 || iv_begin >= iv_end || tape_iv0 < iv_begin || tape_iv0 >= iv_end) return hipErrorInvalidValue;
     if (conv) {                                             // the --conv network: the CONV entry points of the 16-column kernels, either arithmetic
-        if (ens || cw != 16 || conv->c < 2 || conv->c > FC_CONV_MAX || !conv->wb || (dwtape && !conv->ctape)) return hipErrorInvalidValue;
-        const dim3 grid((n_col + 15) / 16), block(256);
+        if (cw != 16 || conv->c < 2 || conv->c > FC_CONV_MAX || !conv->wb || (dwtape && !conv->ctape)) return hipErrorInvalidValue;
+        if (ens && (!cens || ens->n_models < 1 || ens->n_models > 65535)) return hipErrorInvalidValue;      // a conv ensemble: grid.y = model
+        const dim3 grid((n_col + 15) / 16, ens ? ens->n_models : 1), block(256);
         const float CN = m.C_fc * (float)m.Nz, caKN = m.ca_K * (float)m.Nz;
         const bool tape = dwtape != nullptr, ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE, rk = m.rkc != nullptr, split = simgf != nullptr;
         if ((tape && (!masks || (ca && !swtape))) || (rk && !ca)) return hipErrorInvalidValue;
         bool launched = false;
 #define FC_FWDC(N, W, T, C, K)                                                                                                                       \
     if (!launched && m.Nz == N && tape == T && ca == C && rk == K) {                                                                                 \
-        if (split)                                                                                                                                   \
+        if (ens && split)                                                                                                                            \
+            hipLaunchKernelGGL((fc_forward_conv_ens_kernel<N, T, C, K, true>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)simgf, bias, x0, x0_stride, bcs,   \
+                               save_times, n_save, iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, *conv, *ens, *cens); \
+        else if (ens)                                                                                                                                \
+            hipLaunchKernelGGL((fc_forward_conv_ens_kernel<N, T, C, K, false>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)imgf, bias, x0, x0_stride, bcs,   \
+                               save_times, n_save, iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, *conv, *ens, *cens); \
+        else if (split)                                                                                                                              \
             hipLaunchKernelGGL((fc_forward_conv_kernel<N, T, C, K, true>), grid, block, (fc_lds_fwd<N, W>()), stream, (const void*)simgf, bias, x0, x0_stride, bcs,       \
                                save_times, n_save, iv_begin, iv_end, tape_iv0, substeps, CN, caKN, m.nst, m.rkc, sol, dwtape, masks, swtape, n_col, *conv); \
         else                                                                                                                                         \
@@ -610,12 +657,13 @@ hipError_t fc_launch_forward(const DevModel& m, int cw, const float* imgf, const
 
 hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const unsigned int* simgb, const float* save_times, int n_save, int iv_begin, int iv_end,
                              int substeps, const float* sol, const float* truth, float* dwtape, const unsigned int* masks, const unsigned long long* swtape,
-                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens, const FcConv* conv) {
+                             float w_loss, float* lam_io, float* slab, int n_col, hipStream_t stream, const FcEns* ens, const FcConv* conv, const FcConvEns* cens) {
     if (n_col < 1 || !dwtape || !masks || iv_begin < 0 || iv_end > n_save - 1 || iv_begin >= iv_end) return hipErrorInvalidValue;
     if ((iv_begin > 0 || iv_end < n_save - 1) && !lam_io) return hipErrorInvalidValue;
     if (conv) {
-        if (ens || cw != 16 || conv->c < 2 || conv->c > FC_CONV_MAX || !conv->wb || !conv->ctape) return hipErrorInvalidValue;
-        const dim3 grid((n_col + 15) / 16), block(256);
+        if (cw != 16 || conv->c < 2 || conv->c > FC_CONV_MAX || !conv->wb || !conv->ctape) return hipErrorInvalidValue;
+        if (ens && (!cens || ens->n_models < 1 || ens->n_models > 65535)) return hipErrorInvalidValue;
+        const dim3 grid((n_col + 15) / 16, ens ? ens->n_models : 1), block(256);
         const float CN = m.C_fc * (float)m.Nz, caKN = m.ca_K * (float)m.Nz;
         const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE, rk = m.rkc != nullptr, split = simgb != nullptr;
         if ((ca && !swtape) || (rk && !ca)) return hipErrorInvalidValue;
@@ -625,7 +673,13 @@ hipError_t fc_launch_adjoint(const DevModel& m, int cw, const float* imgb, const
         bool launched = false;
 #define FC_ADJC(N, W, C, K)                                                                                                                          \
     if (!launched && m.Nz == N && ca == C && rk == K) {                                                                                              \
-        if (split)                                                                                                                                   \
+        if (ens && split)                                                                                                                            \
+            hipLaunchKernelGGL((fc_adjoint_conv_ens_kernel<N, C, K, true>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)simgb, save_times, n_save, iv_begin,  \
+                               iv_end, substeps, CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, *conv, *ens, *cens); \
+        else if (ens)                                                                                                                                \
+            hipLaunchKernelGGL((fc_adjoint_conv_ens_kernel<N, C, K, false>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)imgb, save_times, n_save, iv_begin,  \
+                               iv_end, substeps, CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, *conv, *ens, *cens); \
+        else if (split)                                                                                                                              \
             hipLaunchKernelGGL((fc_adjoint_conv_kernel<N, C, K, true>), grid, block, (fc_lds_adj<N, W>()), stream, (const void*)simgb, save_times, n_save, iv_begin,      \
                                iv_end, substeps, CN, caKN, m.nst, m.rkc, sol, truth, dwtape, masks, swtape, w_loss, lam_io, slab, go, n_col, *conv); \
         else                                                                                                                                         \

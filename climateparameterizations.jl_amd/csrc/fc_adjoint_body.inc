@@ -1,7 +1,7 @@
-// fc_adjoint_body.inc — the text of the fc32 adjoint kernel (engine_fc.hip), included by fc_adjoint_kernel (CONV = false) and fc_adjoint_conv_kernel
-// (CW = 16, ENS = false, CONV = true): see fc_forward_body.inc.
+// fc_adjoint_body.inc — the text of the fc32 adjoint kernel (engine_fc.hip), included by fc_adjoint_kernel (CONV = false), fc_adjoint_conv_kernel
+// (CW = 16, ENS = false, CONV = true) and fc_adjoint_conv_ens_kernel (CW = 16, ENS = CONV = true): see fc_forward_body.inc.
     static_assert(!ENS || CW == 16, "ensembles run the 16-column tiles");
-    static_assert(!CONV || (CW == 16 && !ENS), "the conv network runs single handles on the 16-column tiles");
+    static_assert(!CONV || CW == 16, "the conv network runs the 16-column tiles");
     if constexpr (ENS) {
         const size_t k = blockIdx.y;
         if constexpr (SPLIT) imgb = reinterpret_cast<const u32*>(imgb) + k * en.simg;
@@ -133,7 +133,7 @@
                 for (int ks = 0; ks < S::KS3; ks++) yb += XBP[(ks * CW + oc[r]) * NZ + oi];
                 const int cc = cv.c + zero, oio = oi + zero;                     // (through the opaque zero: see the forward kernel)
                 const float pre = fc_conv_pre(xc[r], cwv, cbv, cc);
-                const float zb = (oio <= NZ - cc && pre > 0.0f) ? yb : 0.0f;
+                const float zb = (oio <= NZ - cc && (ENS ? !(pre <= 0.0f) : pre > 0.0f)) ? yb : 0.0f;      // (the forward's predicate)
                 FC_STORE(zb, cv.ctape + ri * (size_t)(CW * 2 * NZ) + oc[r] * (2 * NZ) + NZ + oi);
                 float v = xph[r];
 #pragma unroll

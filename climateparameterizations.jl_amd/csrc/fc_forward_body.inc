@@ -1,8 +1,9 @@
-// fc_forward_body.inc — the text of the fc32 forward kernel (engine_fc.hip), included by its two entry points: fc_forward_kernel (CONV = false) and
-// fc_forward_conv_kernel (CW = 16, ENS = false, CONV = true, the filter in `cv`).  Textual inclusion, not an inlined function: the existing
+// fc_forward_body.inc — the text of the fc32 forward kernel (engine_fc.hip), included by its three entry points: fc_forward_kernel (CONV = false),
+// fc_forward_conv_kernel (CW = 16, ENS = false, CONV = true, the filter in `cv`) and fc_forward_conv_ens_kernel (CW = 16, ENS = CONV = true, `cv` already
+// offset to the workgroup's model).  Textual inclusion, not an inlined function: the existing
 // instantiations compile to the instructions they compiled to before the second entry point existed (an inlined body did not: tools/asm_same.py).
     static_assert(!ENS || CW == 16, "ensembles run the 16-column tiles");
-    static_assert(!CONV || (CW == 16 && !ENS), "the conv network runs single handles on the 16-column tiles");
+    static_assert(!CONV || CW == 16, "the conv network runs the 16-column tiles");
     if constexpr (ENS) {
         const size_t k = blockIdx.y;
         if constexpr (SPLIT) imgf = reinterpret_cast<const u32*>(imgf) + k * en.simg;
@@ -77,7 +78,9 @@
                 //  and per comparison in scalar registers across the whole time loop and spills them)
                 const int cc = cv.c + zero, oio = oi + zero;
                 const float pre = fc_conv_pre(vst[r], cwv, cbv, cc);
-                const float y = (oio <= NZ - cc && pre > 0.0f) ? pre : 0.0f;
+                // (a conv ensemble lets a NaN pre-activation through, as Flux's relu = max(0, x) does: a member whose filter went NaN must show as a
+                //  non-finite row, not as a silent all-zero filter output.  Finite values: the same bits either way.)
+                const float y = (oio <= NZ - cc && (ENS ? !(pre <= 0.0f) : pre > 0.0f)) ? pre : 0.0f;
                 X[oc[r] * S::LDX + oi] = y;
                 if (tp) {
                     FC_STORE(y, rec + (size_t)oc[r] * S::R + oi);

@@ -53,3 +53,15 @@ inline int plan_fc_ens_seg(int n32, int n_iv, int cw, int Nz, size_t per_col_iv,
     while (seg > 1 && fc_ens_model_bytes(n32, n_iv, cw, Nz, per_col_iv, n_params, seg) > budget) seg--;
     return seg;
 }
+
+// A conv ensemble (colnde_create_conv_ensemble): per_col_iv carries the conv tape's bytes too; beside what fc_ens_model_bytes counts a model owns the filter
+// slab (cslab_seg_floats floats per time segment), the padded weight vector (n_params floats) and the padded gradient row (n_params + 8).
+inline size_t fc_conv_ens_model_bytes(int n32, int n_iv, int cw, int Nz, size_t per_col_iv, int n_params, int seg, size_t cslab_seg_floats) {
+    const size_t nsg = ((size_t)n_iv + seg - 1) / seg;
+    return fc_ens_model_bytes(n32, n_iv, cw, Nz, per_col_iv, n_params, seg) + (nsg * cslab_seg_floats + 2 * (size_t)n_params + 8) * sizeof(float);
+}
+inline int plan_fc_conv_ens_seg(int n32, int n_iv, int cw, int Nz, size_t per_col_iv, size_t budget, int n_params, size_t cslab_seg_floats) {
+    int seg = n_iv;
+    while (seg > 1 && fc_conv_ens_model_bytes(n32, n_iv, cw, Nz, per_col_iv, n_params, seg, cslab_seg_floats) > budget) seg--;
+    return seg;
+}

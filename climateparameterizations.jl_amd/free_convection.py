@@ -239,7 +239,7 @@ def train_neural_differential_equation_device(nde: FreeConvectionNDE, weights, o
 
 # ---- ensembles: many networks on the same simulations (colnde_create_fc_ensemble) -----------------------------------------------------------------
 
-def _fc_ensemble(cfg: NDEConfig, T0, nde_params, true_sols, W, device, matrix_arithmetic):
+def _fc_ensemble(cfg: NDEConfig, T0, nde_params, true_sols, W, device, matrix_arithmetic, conv=0):
     """Shape checks first (no handle is requested for arrays that do not fit), then the ensemble with its problem set."""
     from .nde import FreeConvectionEnsemble, check_fc_ensemble_arrays
     T0 = np.ascontiguousarray(T0, dtype=np.float32)
@@ -247,33 +247,34 @@ def _fc_ensemble(cfg: NDEConfig, T0, nde_params, true_sols, W, device, matrix_ar
     if T0.ndim != 2 or W.ndim != 2:
         raise ValueError("T0 must be [n_sims, Nz] and the weights [K, n_params], got %s and %s" % (T0.shape, W.shape))
     n, K = T0.shape[0], W.shape[0]
-    check_fc_ensemble_arrays(cfg, n, K, weights=W)
+    check_fc_ensemble_arrays(cfg, n, K, weights=W, conv=conv)
     bcs = np.ascontiguousarray(nde_params, dtype=np.float32)
     if T0.shape != (n, cfg.Nz) or bcs.shape != (n, 2):
         raise ValueError("T0: expected [n_sims, %d], nde_params: [n_sims, 2] ([bottom, top]); got %s and %s" % (cfg.Nz, T0.shape, bcs.shape))
     truth = None if true_sols is None else np.ascontiguousarray(true_sols, dtype=np.float32)
     if truth is not None and truth.shape != (n, cfg.n_save, cfg.Nz):
         raise ValueError("true_sols: expected %s, got %s" % ((n, cfg.n_save, cfg.Nz), truth.shape))
-    ens = FreeConvectionEnsemble(cfg, n, K, device=device, matrix_arithmetic=matrix_arithmetic)
+    ens = FreeConvectionEnsemble(cfg, n, K, device=device, matrix_arithmetic=matrix_arithmetic, conv=conv)
     ens.set_problem(T0, bcs, truth)
     return ens, W
 
 
 def train_neural_differential_equation_ensemble(T0, nde_params, true_sols, cfg: NDEConfig, W, etas, epochs: int, causal_coeff=None, device: int = 0,
-                                                beta=(0.9, 0.999), eps: float = 1e-8, matrix_arithmetic="bf16x3_exact"):
+                                                beta=(0.9, 0.999), eps: float = 1e-8, matrix_arithmetic="bf16x3_exact", conv: int = 0):
     """`train_neural_differential_equation!` (training.jl:44-74) for K networks at once — the sweep of train_free_convection_nde.jl (one process per
     seed, optimiser rate or `--spatial_causality` there) on the same simulations.  T0 [n_sims, Nz], nde_params [n_sims, 2] = [bottom, top],
     true_sols [n_sims, Nt, Nz] (scaled); W [K, n_params], etas [K]; causal_coeff [K] or None: model k trains on
     `Flux.mse(...) + c_k sum(abs2, W1[mask])` (train_free_convection_nde.jl:186-197; 1 is the reference's penalty, 0 none).  θ and the ADAM state stay
     on the device; per epoch one loss + gradient, one penalty add (with coefficients) and one ADAM step for all K.
+    conv = c > 1: K `--conv c` networks, cfg the plain configuration, W [K, conv_n_params(Nz, c)]; the penalty masks the conv chain's first Dense weight.
     Returns (θ [K, n_params], loss history [epochs, K] — the penalty included, as `nde_loss` returns it)."""
     import torch
     from .nde import check_fc_ensemble_arrays
     et = np.ascontiguousarray(etas, dtype=np.float32)
     cc = None if causal_coeff is None else np.ascontiguousarray(causal_coeff, dtype=np.float32)
     Wn = np.asarray(W)
-    check_fc_ensemble_arrays(cfg, np.shape(T0)[0], Wn.shape[0] if Wn.ndim == 2 else 0, weights=Wn, etas=et, coeff=cc)
-    ens, Wc = _fc_ensemble(cfg, T0, nde_params, true_sols, W, device, matrix_arithmetic)
+    check_fc_ensemble_arrays(cfg, np.shape(T0)[0], Wn.shape[0] if Wn.ndim == 2 else 0, weights=Wn, etas=et, coeff=cc, conv=conv)
+    ens, Wc = _fc_ensemble(cfg, T0, nde_params, true_sols, W, device, matrix_arithmetic, conv)
     try:
         dev = torch.device("cuda", ens.device)
         K, n = ens.n_models, ens.n_params
@@ -299,10 +300,11 @@ def train_neural_differential_equation_ensemble(T0, nde_params, true_sols, cfg: 
         ens.close()
 
 
-def compute_nde_solution_history(T0, nde_params, cfg: NDEConfig, W_history, device: int = 0, matrix_arithmetic="bf16x3_exact"):
+def compute_nde_solution_history(T0, nde_params, cfg: NDEConfig, W_history, device: int = 0, matrix_arithmetic="bf16x3_exact", conv: int = 0):
     """`compute_nde_solution_history` (free_convection/src/testing.jl:1-32): the NDE re-solved for the network of EVERY epoch on every simulation —
-    one forward call for all E networks.  W_history [E, n_params]; returns T [E, n_sims, Nz, Nt], unscaled (`inv(T_scaling)`)."""
-    ens, Wc = _fc_ensemble(cfg, T0, nde_params, None, W_history, device, matrix_arithmetic)
+    one forward call for all E networks.  W_history [E, n_params]; returns T [E, n_sims, Nz, Nt], unscaled (`inv(T_scaling)`).  conv = c > 1: the
+    `--conv c` networks of a run trained with that switch."""
+    ens, Wc = _fc_ensemble(cfg, T0, nde_params, None, W_history, device, matrix_arithmetic, conv)
     try:
         sol = ens.forward(Wc)                                                    # [E, n, Nt, Nz], scaled
     finally:
@@ -310,12 +312,12 @@ def compute_nde_solution_history(T0, nde_params, cfg: NDEConfig, W_history, devi
     return np.transpose(cfg.sigma[2] * sol + cfg.mu[2], (0, 1, 3, 2))
 
 
-def nde_loss_history(T0, nde_params, true_sols, cfg: NDEConfig, W_history, device: int = 0, matrix_arithmetic="bf16x3_exact"):
+def nde_loss_history(T0, nde_params, true_sols, cfg: NDEConfig, W_history, device: int = 0, matrix_arithmetic="bf16x3_exact", conv: int = 0):
     """What `plot_epoch_loss` and `animate_nde_loss` plot (testing.jl:34-105), in scaled units: per epoch and simulation `Flux.mse(true, nde)`
     ([E, n_sims]) and `Flux.mse(true, nde, agg = x -> mean(x, dims=1))` per save time ([E, n_sims, Nt]).  One forward call and one column-loss
     call for all E networks; the first is the mean of the second over the save times."""
     import torch
-    ens, Wc = _fc_ensemble(cfg, T0, nde_params, true_sols, W_history, device, matrix_arithmetic)
+    ens, Wc = _fc_ensemble(cfg, T0, nde_params, true_sols, W_history, device, matrix_arithmetic, conv)
     try:
         sol = ens.forward(torch.from_numpy(Wc).to(torch.device("cuda", ens.device)))
         per_t = ens.column_loss(sol).cpu().numpy()

@@ -1023,10 +1023,23 @@ CLOSURE_N_PARAMS = 5
 FC_ENSEMBLE_MAX_COLUMNS = 4096      # the size up to which a single handle runs 16-column tiles (fc_tile_width)
 
 
-def check_fc_ensemble_arrays(cfg: NDEConfig, n_columns: int, n_models: int, weights=None, etas=None, coeff=None, sol=None, result=None):
+FC_CONV_FILTERS = range(2, 9)       # filter lengths of the --conv network (FC_CONV_MAX = 8 taps)
+
+
+def fc_ensemble_n_params(cfg: NDEConfig, conv: int = 0) -> int:
+    """Parameters per model of a `FreeConvectionEnsemble`: the plain network's, or — conv = c > 1 — the conv chain's
+    (`free_convection.conv_n_params(Nz, c)`: c + 1 filter entries, the first Dense 4Nz x (Nz - c + 1))."""
+    c = int(conv)
+    return cfg.n_params if not c else c + 1 + cfg.n_params - 4 * cfg.Nz * (c - 1)
+
+
+def check_fc_ensemble_arrays(cfg: NDEConfig, n_columns: int, n_models: int, weights=None, etas=None, coeff=None, sol=None, result=None, conv: int = 0):
     """Shape rules of `FreeConvectionEnsemble` (no GPU needed), raised before any library call: a free-convection config of the fc32 shape
     Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1) with Nz = 32 or 64, 1 <= n_columns <= 4096, n_models >= 1; weights [K, n_params],
-    etas and coeff [K], sol [K, n_columns, n_save, Nz], result [K, n_params + 8]."""
+    etas and coeff [K], sol [K, n_columns, n_save, Nz], result [K, n_params + 8].  conv = c (2..8): K `--conv c` networks — cfg stays the plain
+    configuration and n_params is `fc_ensemble_n_params(cfg, c)`."""
+    if int(conv) and int(conv) not in FC_CONV_FILTERS:
+        raise ValueError("conv = %d outside 2..8 (0: the plain three-Dense network)" % int(conv))
     if cfg.model not in (FREE_CONVECTION, CONVECTIVE_ADJUSTMENT_NDE):
         raise ValueError("FreeConvectionEnsemble needs a free-convection config (FreeConvectionNDE or ConvectiveAdjustmentNDE); wind mixing: ColumnNDEEnsemble")
     Nz = cfg.Nz
@@ -1036,8 +1049,9 @@ def check_fc_ensemble_arrays(cfg: NDEConfig, n_columns: int, n_models: int, weig
     if not 1 <= int(n_columns) <= FC_ENSEMBLE_MAX_COLUMNS:
         raise ValueError("n_columns = %d outside 1..%d (the 16-column tiles)" % (int(n_columns), FC_ENSEMBLE_MAX_COLUMNS))
     K = int(n_models)
-    check_ensemble_arrays(K, cfg.n_params, weights=weights, etas=etas)
-    for name, a, shape in (("coeff", coeff, (K,)), ("sol", sol, (K, int(n_columns), cfg.n_save, Nz)), ("result", result, (K, cfg.n_params + 8))):
+    n_params = fc_ensemble_n_params(cfg, conv)
+    check_ensemble_arrays(K, n_params, weights=weights, etas=etas)
+    for name, a, shape in (("coeff", coeff, (K,)), ("sol", sol, (K, int(n_columns), cfg.n_save, Nz)), ("result", result, (K, n_params + 8))):
         if a is not None and tuple(a.shape) != shape:
             raise ValueError("%s: expected shape %s for %d models, got %s" % (name, shape, K, tuple(a.shape)))
 
@@ -1047,11 +1061,15 @@ class FreeConvectionEnsemble(ColumnNDEEnsemble):
     free_convection/train_free_convection_nde.jl (one process per seed / optimiser rate / penalty setting there) and the judging of a training run
     (free_convection/src/testing.jl: the network of every epoch on every simulation), every kernel launched once for all K.  `forward`, `loss`,
     `loss_grad` and `adam_step` are `ColumnNDEEnsemble`'s, with its NumPy / torch rules; row k holds the bits a `ColumnNDE` handle computes for
-    model k's weights.  There are no constants to vary: `set_physics` and `wm_embedded` are refused."""
+    model k's weights.  There are no constants to vary: `set_physics` and `wm_embedded` are refused.
+    conv = c > 1: K `--conv c` networks (`colnde_create_conv_ensemble`) — cfg is the plain configuration, a model's vector has
+    `free_convection.conv_n_params(Nz, c)` entries and row k holds the bits of `ColumnNDE(cfg, n, conv=c)`; `causal_penalty` masks the first Dense
+    weight of the conv chain, 4Nz x (Nz - c + 1)."""
 
-    def __init__(self, cfg: NDEConfig, n_columns: int, n_models: int, device: int = 0, engine: int = 0, matrix_arithmetic="bf16x3_exact"):
+    def __init__(self, cfg: NDEConfig, n_columns: int, n_models: int, device: int = 0, engine: int = 0, matrix_arithmetic="bf16x3_exact", conv: int = 0):
         cfg.validate()
-        check_fc_ensemble_arrays(cfg, n_columns, n_models)
+        check_fc_ensemble_arrays(cfg, n_columns, n_models, conv=conv)
+        self.conv = int(conv)
         self.cfg = cfg
         self.n_columns = int(n_columns)
         self.n_models = int(n_models)
@@ -1059,10 +1077,14 @@ class FreeConvectionEnsemble(ColumnNDEEnsemble):
         self._h = ctypes.c_void_p()
         L = _lib.lib()
         c, keep = to_c_config(cfg, n_columns, device, engine, matrix_arithmetic)
-        _lib.check(L.colnde_create_fc_ensemble(ctypes.byref(c), self.n_models, ctypes.byref(self._h)))
+        if self.conv:
+            _lib.check(L.colnde_create_conv_ensemble(ctypes.byref(c), self.conv, self.n_models, ctypes.byref(self._h)))
+        else:
+            _lib.check(L.colnde_create_fc_ensemble(ctypes.byref(c), self.n_models, ctypes.byref(self._h)))
         self._L = L
         self.n_params = L.colnde_n_params(self._h)
-        assert self.n_params == cfg.n_params and L.colnde_n_models(self._h) == self.n_models
+        assert self.n_params == fc_ensemble_n_params(cfg, self.conv) and L.colnde_n_models(self._h) == self.n_models
+        assert L.colnde_conv_filter(self._h) == self.conv
         self.n_columns_total = self.n_columns
         self.engine = L.colnde_engine(self._h)
 
@@ -1070,7 +1092,7 @@ class FreeConvectionEnsemble(ColumnNDEEnsemble):
         """[K, n_columns, n_save]: the mean over the levels of (sol - truth)^2 per model, simulation and save point, scaled units —
         `Flux.mse(true, nde, agg = x -> mean(x, dims=1))` (testing.jl:83).  sol: `forward`'s output (torch on the device, or NumPy)."""
         import torch
-        check_fc_ensemble_arrays(self.cfg, self.n_columns, self.n_models, sol=sol)
+        check_fc_ensemble_arrays(self.cfg, self.n_columns, self.n_models, sol=sol, conv=self.conv)
         is_t = _is_torch(sol)
         s = sol if is_t else torch.from_numpy(_f32(sol)).to(torch.device("cuda", self.device))
         self._chk_dev(s, tuple(sol.shape))
@@ -1084,7 +1106,7 @@ class FreeConvectionEnsemble(ColumnNDEEnsemble):
         total += c_k sum_{r<q} W1_k[r, q]^2, gradient += 2 c_k W1_k[r, q]; coeff [K].  Torch device tensors are updated in place; NumPy arrays
         are copied to the device and the updated result is returned."""
         import torch
-        check_fc_ensemble_arrays(self.cfg, self.n_columns, self.n_models, weights=weights, coeff=coeff, result=result)
+        check_fc_ensemble_arrays(self.cfg, self.n_columns, self.n_models, weights=weights, coeff=coeff, result=result, conv=self.conv)
         if _is_torch(result):
             for t, shape in ((weights, (self.n_models, self.n_params)), (coeff, (self.n_models,)), (result, (self.n_models, self.n_params + 8))):
                 self._chk_dev(t, shape)

@@ -508,7 +508,7 @@ int colnde_create_fc_ensemble(const colnde_config* cfg, int n_models, colnde_han
  * d_sol: [K][n_col][n_save][Nz], the layout of colnde_ensemble_forward_dev.  Fixed-order sums: bit-reproducible. */
 int colnde_ensemble_column_loss_dev(colnde_handle* h, const float* d_sol, float* d_out /* [K][n_col][n_save] */);
 /* result[k][n_params + 6] += c_k * sum_{r < q} W1_k[r, q]^2 ;  result[k][index of W1[r, q]] += 2 c_k W1_k[r, q]
- * W1 = the first Dense weight (4Nz x Nz, column-major as Flux.destructure lays it out), r < q the mask of
+ * W1 = the first Dense weight (4Nz x Nz, column-major as Flux.destructure lays it out; a conv ensemble: 4Nz x (Nz-c+1) at offset c + 1), r < q the mask of
  * train_free_convection_nde.jl:193; c_k = 1 is the reference's penalty, 0 leaves row k's bits alone.
  * d_result: the buffer of colnde_ensemble_loss_grad_dev, updated in place. */
 int colnde_ensemble_causal_penalty_dev(colnde_handle* h, const float* d_weights, const float* d_coeff /* [K] */, float* d_result);
@@ -553,14 +553,32 @@ int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weights, const fl
  * matrix_arithmetic, n_params, engine, conv_filter, plan (info[6] = c), describe ("conv=c"), profiling and kernel times (the filter-gradient kernel is timed
  * with the dW GEMM, slot 5), destroy; the array utilities that read no network (coarse_grain, zscore_stats, scale, convective_adjustment, implicit_diffusion,
  * mpp_diagnose_flux).  Every other call refuses a conv handle with a sentence naming the call: rhs, flux, error_estimate, choose_substeps, infer_*, the embedded
- * steps and diagnoses, pretrain_flux, set_global_columns and allreduce_result (multi-GPU results), the ensemble and closure calls.
+ * steps and diagnoses, pretrain_flux, set_global_columns and allreduce_result (multi-GPU results), the ensemble and closure calls (K conv networks side by
+ * side: colnde_create_conv_ensemble, below).
  * Refused here, before any device work, each with its reason: conv_filter outside 2..8, a wind-mixing model, another network shape or Nz, an engine other than
  * AUTO or FC32, FreeConvectionNDE under RKC2, substeps = 0, substeps < colnde_min_substeps, more than 4,096 columns, COLNDE_FC=0, COLNDE_FC_CW=32,
  * COLNDE_FC_BLOCK.  Then "no HIP device ... no CPU fallback".  The tapes are planned by the first colnde_loss_grad (colnde_set_substeps works until then); tapes
  * that do not fit are refused there with the bytes needed. */
 int colnde_create_conv(const colnde_config* cfg, int conv_filter, colnde_handle** out);
-/* c of a conv handle, 0 for every other handle (-1: null) */
+/* c of a conv handle or conv ensemble, 0 for every other handle (-1: null) */
 int colnde_conv_filter(const colnde_handle* h);
+/* ---- conv ensembles: K --conv networks of ONE filter length on the same simulations ---------------------------------------------------------------------
+ * The sweep of train_free_convection_nde.jl (seed, optimiser rate, --spatial_causality) with --conv c among the swept architectures: the product of
+ * colnde_create_fc_ensemble and colnde_create_conv.  cfg is the plain fc32 configuration, as for colnde_create_conv; model k's parameter vector has that
+ * handle's layout, [w (c); b; vec(W1) 4Nz x M; b1; ...], colnde_n_params floats, the K vectors back to back.  Every kernel of a training iteration is
+ * launched once for all K: the 16-column forward and adjoint kernels carry the model index in the launch grid and the filter (third entry points), the
+ * padding, filter-gradient and fold kernels take the models in grid.y.  Row k of every result holds the bits a colnde_create_conv handle computes for
+ * model k's weights, under either matrix arithmetic (and the same COLNDE_FC_SEG).
+ * Accepted by colnde_ensemble_forward_dev, _loss_dev, _loss_grad_dev, _loss_grad, _adam_step_dev (over K x n_params), _column_loss_dev and
+ * _causal_penalty_dev — there W1 is the first Dense weight of the conv chain, 4Nz x M at offset c + 1 of the model's vector, mask r < q
+ * (ps[dense_layer_params_idx], train_free_convection_nde.jl:189-195) — and by the handle-level calls a free-convection ensemble accepts: n_params (the conv
+ * count), conv_filter (c), n_models (K), plan (info[6] = c), describe ("models=K", "conv=c", the bytes per model, time_segments).  Everything a free-convection
+ * ensemble or a conv handle refuses is refused, with a sentence naming the call.
+ * Refused at creation, before any device work, each with its reason: what colnde_create_conv refuses and what colnde_create_fc_ensemble refuses (in those
+ * creators' words).  Then "no HIP device ... no CPU fallback", and tapes that do not fit, with the bytes needed: all K models' tapes — the conv tape in the
+ * bytes per column and save interval, the filter slab and the padded vectors in the bytes per model — are planned here as colnde_create_fc_ensemble plans
+ * them. */
+int colnde_create_conv_ensemble(const colnde_config* cfg, int conv_filter, int n_models, colnde_handle** out);
 
 /* ---- closure-only model: fitting the five Pacanowski-Philander constants before any network is trained ------------------------------------------------
  * optimise_modified_pacanowski_philander (wind_mixing/src/diffusivity_parameter_optimisation.jl:35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl

@@ -558,6 +558,20 @@ function ConvHandle(cfg::Config, save_times::Vector{Float32}, conv::Integer)
 end
 const create_conv = ConvHandle
 
+"K `--conv c` networks of one filter length on the same columns (`colnde_create_conv_ensemble`): `cfg` and the per-model weight layout are `ConvHandle`'s,
+the K vectors are the columns of an `h.n_params x K` matrix; accepted by the `ensemble_*` calls (row k = the bits a `ConvHandle` computes for model k;
+the causal penalty masks the 4Nz x (Nz-c+1) first Dense weight), refused by `set_physics!` and the single-model calls"
+function ConvEnsembleHandle(cfg::Config, save_times::Vector{Float32}, conv::Integer, n_models::Integer)
+    cfg.n_save = length(save_times)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve save_times begin
+        cfg.save_times = pointer(save_times)
+        check(ccall((:colnde_create_conv_ensemble, libcolnde), Cint, (Ref{Config}, Cint, Cint, Ref{Ptr{Cvoid}}), cfg, conv, n_models, out))
+    end
+    h = Handle(out[], ccall((:colnde_n_params, libcolnde), Cint, (Ptr{Cvoid},), out[]), cfg.Nz, cfg.n_save, cfg.n_columns, 1)
+    finalizer(x -> ccall((:colnde_destroy, libcolnde), Cvoid, (Ptr{Cvoid},), x.ptr), h)
+end
+
 "c of a conv handle, 0 for every other handle"
 conv_filter(h::Handle) = Int(ccall((:colnde_conv_filter, libcolnde), Cint, (Ptr{Cvoid},), h.ptr))
 

@@ -4,7 +4,15 @@
   (b) the plain fc32 handle of the same build (the three-Dense network)
   (c) tile16 on the four-layer Toeplitz network (free_convection.conv_to_dense): what a `--conv` user could run before the conv handle
 Each timing is the mean of `--reps` iterations after a warm-up, repeated `--rounds` times; the spread is (max - min) over the rounds.
-    python tools/fc_conv_rate.py [--out profiles/fc_conv_rate.jsonl]"""
+    python tools/fc_conv_rate.py [--out profiles/fc_conv_rate.jsonl]
+
+--ensemble: the K sweep of the conv ENSEMBLE (colnde_create_conv_ensemble) on the reference's training shape — 9 simulations, Nz = 32 and 64, c = 3,
+FreeConvectionNDE (RK4) and ConvectiveAdjustmentNDE under RKC2, 129 save points x 4 sub-steps: ms per training iteration (loss_grad + ADAM on device
+tensors) of K networks in one handle, K = 1, 4, 16, 64, against what a user has without it — a single conv handle run K times one after another, each
+with its own weights and ADAM state (the single handle's kernels are the parent commit's, instruction for instruction: tools/asm_same.py).  Both sides
+are warmed up and timed in the same process, ensemble and baseline in turn per K, ending in a device synchronise; the per-kernel slots come from a
+separate profiled pass.
+    python tools/fc_conv_rate.py --ensemble [--out profiles/fc_conv_ens_rate.json]"""
 import argparse
 import json
 import os
@@ -45,14 +53,111 @@ def measure(make, x0, bcs, w, w_truth, reps, rounds):
                     kernel_ms_per_iteration=kt, describe=nde.describe().split(" | env")[0])
 
 
+ENS_KERNELS = ("forward", "adjoint", "dw1", "reduce", "adam")          # dw1: the dW GEMM and the filter-gradient kernel; reduce: reduction and fold
+
+
+def ensemble_sweep(a):
+    import torch
+    dev = torch.device("cuda", 0)
+    c, n = a.conv, 9
+    rows = []
+
+    def timed(step, warmup, iters):
+        for _ in range(warmup):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / iters
+
+    for model in ("fc_rk4", "ca_rkc2"):
+        for Nz in (32, 64):
+            pc = synthetic.free_convection_conv_problem(n, c, Nz=Nz, convective_adjustment=model == "ca_rkc2")
+            cfg = pc.cfg.with_(stepper="rkc2") if model == "ca_rkc2" else pc.cfg
+            P = c + 1 + cfg.n_params - 4 * Nz * (c - 1)
+            try:
+                single = colnde.ColumnNDE(cfg, n, conv=c)
+            except colnde.ColndeError as err:
+                rows.append(dict(model=model, Nz=Nz, conv=c, columns=n, refused=str(err)))
+                print(json.dumps(rows[-1]), flush=True)
+                continue
+            with single:
+                single.set_problem(pc.x0, pc.bcs)
+                truth = single.forward(pc.weights_truth)
+                x0, bcs, tr = (torch.from_numpy(np.ascontiguousarray(t)).to(dev) for t in (pc.x0, pc.bcs, truth))
+                single.set_problem(x0, bcs, tr)
+                rng = np.random.default_rng(1)
+                Wall = (pc.weights[None, :] * (1 + 0.05 * rng.standard_normal((64, P)))).astype(np.float32)
+                for K in (1, 4, 16, 64):
+                    iters, warmup = (a.reps, 2) if K < 16 else (max(2, a.reps // 2), 1)
+                    W = torch.from_numpy(Wall[:K].copy()).to(dev)
+                    out = torch.empty((K, P + 8), device=dev)
+                    m, v = torch.zeros((K, P), device=dev), torch.zeros((K, P), device=dev)
+                    etas = torch.full((K,), 1e-4, device=dev)
+                    row = dict(model=model, Nz=Nz, conv=c, columns=n, n_save=cfg.n_save, substeps=cfg.substeps, K=K, iterations=iters, warmup=warmup)
+                    try:
+                        ens = colnde.FreeConvectionEnsemble(cfg, n, K, conv=c)
+                    except colnde.ColndeError as err:
+                        row["refused"] = str(err)
+                        rows.append(row)
+                        print(json.dumps(row), flush=True)
+                        continue
+                    with ens:
+                        ens.set_problem(x0, bcs, tr)
+
+                        def ens_step():
+                            ens.loss_grad(W, SC, out=out)
+                            ens.adam_step(W, out, m, v, etas, beta_t=(0.9, 0.999))
+
+                        # the baseline: the single handle K times in turn, member k on its own weights and moments
+                        Wb, mb, vb = W.clone(), torch.zeros((K, P), device=dev), torch.zeros((K, P), device=dev)
+
+                        def base_step():
+                            for k in range(K):
+                                single.loss_grad(Wb[k], SC, out=out[k])
+                                single.adam_step(Wb[k], out[k], mb[k], vb[k], 1e-4, beta_t=(0.9, 0.999))
+
+                        ms_e, ms_b = [], []
+                        for _ in range(a.rounds):                              # in turn: the machine's drift falls on both
+                            ms_e.append(timed(ens_step, warmup, iters))
+                            ms_b.append(timed(base_step, warmup, iters))
+                        ens.set_profiling(True)
+                        ens.reset_kernel_times()
+                        for _ in range(2):
+                            ens_step()
+                        torch.cuda.synchronize()
+                        kt = {k: round(ens.kernel_time(k)[0] / 2, 3) for k in ENS_KERNELS}
+                        desc = ens.describe().split(" | env")[0]
+                    e, b = float(np.median(ms_e)), float(np.median(ms_b))
+                    row.update(ensemble_ms_per_iteration=round(e, 3), ensemble_ms_rounds=[round(x, 3) for x in ms_e],
+                               one_after_another_ms_per_iteration=round(b, 3), one_after_another_ms_rounds=[round(x, 3) for x in ms_b],
+                               ensemble_model_iterations_per_s=round(K * 1e3 / e, 2), one_after_another_model_iterations_per_s=round(K * 1e3 / b, 2),
+                               speedup=round(b / e, 3), ensemble_kernel_ms_per_iteration=kt, finite=bool(torch.isfinite(out[:, P + 6]).all().item()),
+                               bytes_per_model=int(desc.split("tape_bytes_per_model=")[1].split()[0]), describe=desc)
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
+                    del W, out, m, v, Wb, mb, vb
+                    torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ensemble", action="store_true")
     ap.add_argument("--conv", type=int, default=3)
     ap.add_argument("--columns", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.ensemble:
+        return ensemble_sweep(a)
     rows = []
     for Nz in (32, 64):
         c, n = a.conv, a.columns
