@@ -419,6 +419,7 @@ extern "C" int colnde_create(const colnde_config* cfg, colnde_handle** out) {
     {
         hipError_t e = set_kernel_attributes(lds_cap);
         if (e == hipSuccess) e = rt_set_attributes();
+        if (e == hipSuccess) e = rt_set_attributes_split();
         if (e != hipSuccess) { colnde_destroy(h); return fail("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); }
     }
     // AUTO: regtile where it applies, except for problems of at most 8,192 columns (two rounds of one 16-column tile per CU).  Those
@@ -694,7 +695,7 @@ int t16_forward_range(colnde_handle* h, const float* d_weights, float* d_sol, bo
     }
     Timed tm(h, K_FORWARD);
     if (h->fwd_split) {
-        // latency points of the wind-mixing shape: one wavefront per flux net (+ a helper) per 16-column tile (engine_regtile.hip); the tapes
+        // latency points of the wind-mixing shape: one wavefront per flux net (+ a helper) per 16-column tile (engine_netsplit.hip); the tapes
         // come out in tile16's formats for its taped adjoint
         hipError_t es = rt_launch_pack(h->m, d_weights, h->d_wimg, h->stream);
         if (es == hipSuccess)
@@ -1147,9 +1148,9 @@ extern "C" int colnde_debug_stamps(colnde_handle* h, unsigned long long* out16) 
     if (!h || !out16) return fail("null argument");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->use_rt || h->adj_split) {
+    if (h->use_rt || h->adj_split) {      // each translation unit keeps the stamps of its own kernels
         for (int i = 0; i < 16; i++) out16[i] = 0;
-        HIPCHK(rt_debug_read_stamps(out16));
+        HIPCHK(h->use_rt ? rt_debug_read_stamps(out16) : rt_debug_read_stamps_split(out16));
         return 0;
     }
     HIPCHK(debug_read_stamps(out16));

@@ -13,6 +13,7 @@
 
 #include "engine_tile16.h"
 #include "engine_regtile.h"
+#include "engine_netsplit.h"
 #include "engine_fc.h"
 #include "column_ops.h"
 #include "engine_closure.h"

@@ -50,16 +50,7 @@
 #define RT_NSA_WORDS (RT_NSA_L + 3 * 2 * 6 * 256)
 #define RT_IMG_ALLOC (RT_NSA_OFF + RT_NSA_WORDS)
 
-// Ensembles (colnde_create_ensemble): K models of this shape in ONE launch per kernel, the model index in blockIdx.y.  A model owns its packed
-// weight image, solution, tapes and slab rows (per-model strides in floats below) and its Pacanowski-Philander constants; x0, bcs and truth are
-// shared.  A single model launches with grid.y = 1 and phys = nullptr: the constants of DevModel, every offset zero.
-struct RtPhys { float nu0, nu_minus, Ric, inv_dRi, inv_Pr, c_rib, pad0, pad1; };
-struct RtEns {
-    const RtPhys* phys = nullptr;        // [n_models] closure constants, or nullptr
-    size_t wimg = 0, sol = 0, tape = 0, ztape = 0, dwtape = 0, slab = 0;
-    int n_models = 1;
-};
-#define RT_IMG_STRIDE ((RT_IMG_ALLOC + 63) & ~63)   // floats between the weight images of two models
+#define RT_IMG_STRIDE ((RT_IMG_ALLOC + 63) & ~63)   // floats between the weight images of two models (ensembles: engine_netsplit.h)
 
 bool rt_supported(const DevModel& m);
 size_t rt_forward_lds_bytes();
@@ -68,15 +59,6 @@ hipError_t rt_launch_pack(const DevModel& m, const float* w, float* wimg, hipStr
 hipError_t rt_launch_forward(const DevModel& m, const float* wimg, const float* x0, const float* bcs,
                              const float* save_times, int n_save, int substeps, float* sol, float* tape, float* tapez,
                              int n_col, bool fwd32, bool split, hipStream_t stream);
-hipError_t rt_launch_forward_split(const DevModel& m, const float* wimg, const float* x0, const float* bcs, const float* save_times,
-                                   int n_save, int substeps, float* sol, float* t16_tape, float* t16_ztape, int n_col, bool rich, bool use_helper, bool want_split, hipStream_t stream,
-                                   const RtEns& ens = RtEns());
-size_t rt_split_rich_record_floats();   // floats per (tile, step, stage) of the net-split kernels' rich tape (which then takes the place of t16_ztape)
-hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const float* save_times, int n_save, int substeps, const float* sol,
-                                   const float* truth, const float* t16_tape, const float* t16_ztape, const LossWeights& lw, float* slab,
-                                   int n_col, float* dwtape, bool rich, bool use_helper, bool want_split, hipStream_t stream,
-                                   const RtEns& ens = RtEns());
-bool rt_adjoint_split_has_bf16(const DevModel& m, bool use_helper);   // the net-split adjoint has a split (bf16-pipe) kernel for this configuration
 bool rt_forward_is32();   // COLNDE_RT_FWD=32 in the environment (read when a handle is created)
 size_t rt_adjoint_lds_bytes();
 size_t rt_tape_floats(int n_col, int n_steps);
@@ -89,4 +71,4 @@ hipError_t rt_launch_adjoint(const DevModel& m, const float* wimg, const float* 
                              const float* tapez, const LossWeights& lw, float* slab, int n_col, bool want_split, hipStream_t stream);
 hipError_t rt_launch_dw1(const DevModel& m, const float* tape, const float* tape2, int n_col, int n_steps, float* slab_rows,
                          bool split, hipStream_t stream);
-hipError_t rt_debug_read_stamps(unsigned long long* out8);
+hipError_t rt_debug_read_stamps(unsigned long long* out16);   // diagnostic builds (-DCOLNDE_STAMPS): the phase stamps of this unit's kernels

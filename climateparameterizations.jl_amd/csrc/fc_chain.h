@@ -11,17 +11,10 @@ typedef unsigned int u32;
 #ifndef FC_PF
 #define FC_PF 8                                    // ring depth in groups of four MFMAs: 8 x 256 cycles of cover
 #endif
-#ifndef FC_NT
-#define FC_NT 0                                    // tape traffic with the non-temporal cache policy: measured SLOWER (A/B on one box, 16,384 columns:
-#endif                                             // Nz = 32 forward 26.8 vs 16.7 ms, adjoint 25.4 vs 17.6; Nz = 64 61.0 vs 53.9 and 61.0 vs 54.0) — an
-                                                   // nt store is acknowledged late, and every wait for a ring load (vmcnt is in order) waits behind it
-#if FC_NT
-#define FC_STORE(v, p) __builtin_nontemporal_store(v, p)
-#define FC_LOAD(p) __builtin_nontemporal_load(p)
-#else
+// tape traffic: the default cache policy.  (Non-temporal was measured SLOWER: an nt store is acknowledged late, and every wait for a ring load — vmcnt
+// is in order — waits behind it; figures in profiles/README.md)
 #define FC_STORE(v, p) (*(p) = (v))
 #define FC_LOAD(p) (*(p))
-#endif
 #define FC_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 // The group addresses of a stage are loop-invariant: left alone, the optimiser computes all ~100 of them once, outside the time loop, and
 // keeps them in (spilled) registers.  An opaque zero added to the wave-uniform bases at the top of every stage keeps them what they should

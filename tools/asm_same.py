@@ -1,4 +1,5 @@
 """Are the kernels of two device-assembly files (make -C csrc asm) the same?  python tools/asm_same.py OLD.s NEW.s
+Either side may be several files joined with commas (a translation unit that was split: OLD.s NEW_a.s,NEW_b.s): their kernels are taken together.
 
 Compares per mangled kernel name, not per byte: the order in which the compiler emits template instantiations follows the
 host code's references, and the function numbers inside local labels (.LBB12_3) follow that order.  Per kernel: the text from
@@ -6,8 +7,8 @@ its 'Begin function' to its 'End function' line (instructions and the .amdhsa_ke
 scratch sizes), its .set lines and its metadata entry (spill counts, arguments), comments dropped, label numbers removed."""
 import re, sys
 
-def kernels(path):
-    s = open(path).read()
+def kernels(paths):
+    s = "\n".join(open(p).read() for p in paths.split(','))
     out = {}
     for m in re.finditer(r'; -- Begin function (\S+)\n(.*?); -- End function', s, re.S):
         out[m.group(1)] = m.group(2)

@@ -1,11 +1,14 @@
 """Diagnostic: instruction mix and a compact op trace of the innermost (stage) loop of a kernel in the generated assembly.
-usage: loop_mix.py [asm file] [mangled-name prefix]   (make -C climateparameterizations.jl_amd/csrc asm first)"""
+usage: loop_mix.py [asm file] [mangled-name prefix]   (make -C climateparameterizations.jl_amd/csrc asm first)
+Without an asm file the kernel is looked for in engine_regtile.s, then in engine_netsplit.s (the rt16s_* / rt16sh_* kernels)."""
 import collections, re, sys, textwrap, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 args = [a for a in sys.argv[1:] if not a.startswith("-")]
-path = args[0] if len(args) > 0 else os.path.join(ROOT, "climateparameterizations.jl_amd/csrc/_build/engine_regtile.s")
 name = args[1] if len(args) > 1 else "_Z17rt_adjoint_kernelILi2ELb1ELb1EEv"
-s = open(path).read()
+paths = [a for a in args[:1] if not a.startswith("_Z")] or [os.path.join(ROOT, "climateparameterizations.jl_amd/csrc/_build", f) for f in ("engine_regtile.s", "engine_netsplit.s")]
+if len(args) == 1 and args[0].startswith("_Z"): name = args[0]
+s = next((t for t in (open(p).read() for p in paths if os.path.exists(p)) if name in t), None)
+if s is None: sys.exit("%s: not in %s" % (name, ", ".join(paths)))
 start = s.index(name); start = s.index(":", start)
 end = s.index(".Lfunc_end", start)
 k = s[start:end].split("\n")
