@@ -583,6 +583,12 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
         for (int t = (13 * n) >> 2; t <= (13 * n + 12) >> 2; t++)
 #pragma unroll
             for (int c = 0; c < 2; c++) {
+                // net 0 keeps one element of tile 3's first record (quad 12, register 24): a 4-byte load.  As a 16-byte load its three dropped
+                // registers are handed to the next instructions, which then have to wait for the load to land before they may write them.
+                if (n == 0 && t == 3) {
+                    if (c == 0) Z[1][8] = __builtin_nontemporal_load(srcz + (2 * t + c) * 256);
+                    continue;
+                }
                 const f32x4v v = RT_TAPE_LOAD4(srcz + (2 * t + c) * 256);
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
@@ -619,6 +625,12 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
 #pragma unroll
                 for (int r = 9; r < 16; r++) { A1[1][r] = 0.0f; D1[1][r] = 0.0f; A1n[1][r] = 0.0f; D1n[1][r] = 0.0f; }
                 load_x(step, st);
+                // With the Z1 tape only the closure reads X, and `tape` is const __restrict__: LLVM sinks the twelve loads into rt_physics_vjp's closure branch, behind
+                // the whole cotangent block, in two dependent batches — two exposed HBM round trips per stage.  Handing the tape pointer to an empty asm that may
+                // write memory keeps them here (a bare memory clobber does not order a load through a noalias pointer); their wait stays at the closure's first use
+                // of X, since the asm does not name the loaded registers.  (!ZT: layer 1 reads X, the loads are here already; the pin would only put a spill reload
+                // behind them, and vmcnt, counting in order, would wait for all twelve with it.)
+                if constexpr (ZT) asm volatile("" :: "v"(tp) : "memory");
                 // (1) stage cotangent and the physics pullback: dO = cotangent of the NN fluxes, xb = physics part of x̄
                 f32x16 dOk[3];
                 {
@@ -627,6 +639,10 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
                     for (int q = 0; q < 3; q++)
 #pragma unroll
                         for (int r = 0; r < 16; r++) kb[q][r] = cwl * lam[RT_LAM(q * 16 + r, lane)] + cwx * xb[q][r];
+#ifdef COLNDE_STAMPS
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    RT_STAMP(8);                    // diagnostic build only: the stage-input request, kb and what is left of the loads' latency behind kb (the shipped build waits later, in the closure)
+#endif
                     rt_physics_vjp(m, X, kb, h, xb);       // kb now holds dO
 #pragma unroll
                     for (int q = 0; q < 3; q++) dOk[q] = kb[q];
@@ -641,13 +657,32 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
                     // (2) hidden layer 1 of net n: activation A1 (feeds layer 2 and the dW2 products) and derivative D1 (feeds dZ1),
                     //     evaluated once, together.  With the Z1 tape (ZT) nets 1 and 2 arrive already activated: their taped
                     //     pre-activations were fetched and activated in the shadow of the previous net's W1^T products (6).
+                    constexpr bool EARLY3 = ZT;       // net 0 with the Z1 tape does two pieces of (3) here, under its tape's round trip
+                    f32x16 TA3, da3;
                     if (ZT) {
                         if (n == 0) {
                             load_z1(step, st, 0, A1);      // (requested BEFORE the physics pullback instead: 55.9 -> 57.0 ms, round 5)
+                            // Net 0's record is requested here and nothing above can cover it.  What follows needs
+                            // dO only — layer 3's transposition and bias sum and the sixteen products of W3^T dO — so it runs first, and the wait for the
+                            // tape moves from the request to the activation pairs.  Three things hold the order: the pointer handed to the asm keeps the loads
+                            // ahead of the chain (as for the stage input), the scheduling barrier keeps the chain ahead of the pairs, and the second asm ties
+                            // the pairs' inputs and the chain's result together, because both are pure arithmetic and instruction selection orders them freely
+                            // otherwise (it put the pairs, and the wait with them, behind the chain's first product).
+                            asm volatile("" :: "v"(tpz) : "memory");
+                            TA3 = rt_transpose(tb, dOn, wbase, rbase);
+                            b3acc[n] += rt_sum16(TA3);
+                            const int base = b3T + n * 31 * RT_LD3;
+                            da3 = rt_chain<16, 8>(wl, (f32x16)(0.0f), [=](int k) { return base + RHO0(k) * RT_LD3; },
+                                                  [&](int k) { return dOn[k]; });
+                            __builtin_amdgcn_sched_barrier(0);
 #ifdef COLNDE_STAMPS
                             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                            RT_STAMP(7);            // diagnostic build only: the exposed latency of net 0's Z1 loads
+                            RT_STAMP(7);            // diagnostic build only: what is left of the latency of net 0's Z1 loads behind that work
 #endif
+                            asm volatile("" : "+v"(A1[0][0]), "+v"(A1[0][1]), "+v"(A1[0][2]), "+v"(A1[0][3]), "+v"(A1[0][4]), "+v"(A1[0][5]), "+v"(A1[0][6]), "+v"(A1[0][7]),
+                                              "+v"(A1[0][8]), "+v"(A1[0][9]), "+v"(A1[0][10]), "+v"(A1[0][11]), "+v"(A1[0][12]), "+v"(A1[0][13]), "+v"(A1[0][14]), "+v"(A1[0][15]),
+                                              "+v"(A1[1][0]), "+v"(A1[1][1]), "+v"(A1[1][2]), "+v"(A1[1][3]), "+v"(A1[1][4]), "+v"(A1[1][5]), "+v"(A1[1][6]), "+v"(A1[1][7]),
+                                              "+v"(A1[1][8]), "+a"(da3));
 #pragma unroll
                             for (int G = 0; G < 24; G += 4) rt_act_pair4_at<ACT>(A1, D1, G);
                             rt_act_pair_at<ACT>(A1, D1, 24);
@@ -684,8 +719,9 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
                     // (3) layer 3: weight/bias gradient, then dZ2 = (W3^T dO) .* act'(Z2)
                     //     (evaluating the layer-2 activation pairs inside the W3^T chain instead was measured slower: 94.8 vs 89.7 ms)
                     {
-                        const f32x16 TA = rt_transpose(tb, dOn, wbase, rbase);
-                        b3acc[n] += rt_sum16(TA);
+                        f32x16 TA;
+                        if (EARLY3 && n == 0) TA = TA3;
+                        else { TA = rt_transpose(tb, dOn, wbase, rbase); b3acc[n] += rt_sum16(TA); }
                         f32x16 A2;
 #pragma unroll
                         for (int r = 0; r < 16; r += 4) {
@@ -700,8 +736,10 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
                     }
                     {
                         const int base = b3T + n * 31 * RT_LD3;
-                        const f32x16 da = rt_chain<16, 8>(wl, (f32x16)(0.0f), [=](int k) { return base + RHO0(k) * RT_LD3; },
-                                                          [&](int k) { return dOn[k]; });
+                        f32x16 da;
+                        if (EARLY3 && n == 0) da = da3;
+                        else da = rt_chain<16, 8>(wl, (f32x16)(0.0f), [=](int k) { return base + RHO0(k) * RT_LD3; },
+                                                  [&](int k) { return dOn[k]; });
 #pragma unroll
                         for (int r = 0; r < 16; r++) Z2[r] = da[r] * Z2[r];
                     }

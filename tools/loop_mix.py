@@ -1,5 +1,5 @@
 """Diagnostic: instruction mix and a compact op trace of the innermost (stage) loop of a kernel in the generated assembly.
-usage: loop_mix.py [asm file] [mangled-name prefix]   (make -C climateparameterizations.jl_amd/csrc asm first)
+usage: loop_mix.py [asm file] [mangled-name prefix] [-q] [--where=LETTERS]   (make -C climateparameterizations.jl_amd/csrc asm first)
 Without an asm file the kernel is looked for in engine_regtile.s, then in engine_netsplit.s (the rt16s_* / rt16sh_* kernels)."""
 import collections, re, sys, textwrap, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,5 +49,8 @@ print(dict(collections.Counter(tr).most_common()))
 print("legend: M mfma  . valu  E exp/log  R rcp  a accvgpr move  d/w LDS read/write  | lgkm wait  V vm wait  G/T global ld/st  L/S scratch ld/st  n nop  s scalar")
 if "-q" not in sys.argv:
     print("\n".join(textwrap.wrap(tr, 200)))
+for a in sys.argv[1:]:
+    if a.startswith("--where="):      # loop indices of the instructions of the given trace letters, e.g. --where=GV (a scheduling change shows here)
+        print("where %s:" % a[8:], " ".join("%s%d" % (c, i) for i, c in enumerate(tr) if c in a[8:]))
 ops = collections.Counter(l.split()[0] for l in body)
 print(ops.most_common(25))

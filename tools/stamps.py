@@ -1,5 +1,5 @@
 """Diagnostic: per-phase cycle shares of one adjoint stage (workgroup 0, wave 0) from the -DCOLNDE_STAMPS build.
-Usage (GPU box): make -C climateparameterizations.jl_amd/csrc stamps && python tools/stamps.py"""
+Usage (GPU box): make -C climateparameterizations.jl_amd/csrc stamps && python tools/stamps.py [--lib libcolnde_stamps_<other>.so] [columns] [frames]"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,7 +10,12 @@ from colnde import _lib, synthetic
 os.environ.setdefault("COLNDE_T16_FWD_HELPER", "0")
 FWD = "--fwd" in sys.argv      # forward-kernel stamps: build with -DCOLNDE_STAMPS -DCOLNDE_STAMPS_FWD into libcolnde_stamps_fwd.so
 if FWD: sys.argv.remove("--fwd")
-_lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libcolnde_stamps_fwd.so" if FWD else "libcolnde_stamps.so")
+LIB = "libcolnde_stamps_fwd.so" if FWD else "libcolnde_stamps.so"
+if "--lib" in sys.argv:        # another stamps build (a parent's, beside this one's)
+    i = sys.argv.index("--lib")
+    LIB = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+_lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), LIB)
 L = _lib.lib()
 L.colnde_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]
 FC64 = "--fc64" in sys.argv     # free convection 64-256-256-63 (tile16, taped weight gradients)
@@ -40,11 +45,14 @@ elif nde.engine == 2 and FWD:
     names = ["X tape store + top flux", "layer 1 (10 chains, Z1 tape store, activation)", "layers 2, 3", "physics", "RK4 update"]
 elif nde.engine == 2:
     # (stamp 6 sits behind the net loop: the W1^T chains of nets 0 and 1 are charged to the next net's stamp 1)
-    names = ["kbar + physics pullback + dO park", "net 0 activation pairs + W1^T chains of nets 0, 1", "L2 chain (3 nets)", "dW3 + W3^T + dZ2",
-             "dW2 (transposes + outer)", "W2^T + dZ1 + tape2 store", "W1^T chains of net 2", "(net 0's Z1 loads: issue -> landed)"]
+    # (stamp 7 sits behind net 0's dO transposition and W3^T chain, which run under its Z1 loads; stamp 8 — slot 10 — behind the stage cotangent, under the stage-input loads:
+    #  both are the forced wait for what is left of a round trip, and exist in the diagnostic build only)
+    names = ["physics pullback + dO park", "net 0 activation pairs + W1^T chains of nets 0, 1", "L2 chain (3 nets)", "dW3 + W3^T + dZ2",
+             "dW2 (transposes + outer)", "W2^T + dZ1 + tape2 store", "W1^T chains of net 2", "(net 0: dO transposition + W3^T chain + rest of the Z1 wait)",
+             "(stage-input request + kbar + rest of the X wait)"]
 else:
     names = ["tape load + kbar", "mlp_forward", "physics_vjp", "mlp_backward", "dW tiles", "bias + xbar sum + barrier"]
-v = np.array(list(buf)[:len(names)], dtype=np.float64)
+v = np.array((list(buf)[:8] + [buf[10]])[:len(names)], dtype=np.float64)
 nstage = p.cfg.n_steps * 4
 for n, x in zip(names, v):
     print("%-28s %10.0f cycles/stage  %5.1f %%" % (n, x / nstage, 100 * x / v.sum()))
