@@ -418,6 +418,7 @@ extern "C" int colnde_create(const colnde_config* cfg, colnde_handle** out) {
     if (h->lds_adj > lds_cap) h->geo_ok = false;
     {
         hipError_t e = set_kernel_attributes(lds_cap);
+        if (e == hipSuccess) e = dw_set_kernel_attributes(lds_cap);
         if (e == hipSuccess) e = rt_set_attributes();
         if (e == hipSuccess) e = rt_set_attributes_split();
         if (e != hipSuccess) { colnde_destroy(h); return fail("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); }
@@ -521,7 +522,6 @@ extern "C" void colnde_destroy(colnde_handle* h) {
     (void)hipSetDevice(h->device);
     drain_events(h);
     h->mem.free_all();
-    dw_split_free(h->dw_split);
     delete h;
 }
 
@@ -1045,11 +1045,11 @@ extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
     } else if (h->use_fc) {
         bf_fwd = h->sp_fwd && fc_split_supported(h->fc_cw);
         bf_adj = h->sp_adj && fc_split_supported(h->fc_cw);
-        bf_dw = h->sp_dw && (h->d_dwtape ? !h->dw_split.passes.empty() : true);
+        bf_dw = h->sp_dw && (h->d_dwtape ? !h->dw.passes.empty() : true);
     } else {
         bf_fwd = (h->sp_fwd && h->fwd_split && h->fwd_helper) || h->m.sf != nullptr;
         bf_adj = (h->sp_adj && h->adj_split && rt_adjoint_split_has_bf16(h->m, h->adj_helper) && (h->t16_dwtape < 0 || (h->t16_dwtape == 1 && h->d_t16_ztape))) || h->m.sb != nullptr;
-        bf_dw = h->sp_dw && h->t16_dwtape == 1 && !h->dw_split.passes.empty();
+        bf_dw = h->sp_dw && h->t16_dwtape == 1 && !h->dw.passes.empty();
     }
     info[7] |= (bf_fwd ? 2 : 0) | (bf_adj ? 4 : 0) | (bf_dw ? 8 : 0);
     if (h->use_fc) {
@@ -1057,7 +1057,7 @@ extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
         info[2] = h->fc_nblocks;
         info[3] = h->fc_nseg > 1 ? h->fc_nseg : 0;       // fc32: time segments of the tapes (0: the tapes hold the whole axis)
         info[4] = h->d_dwtape ? 1 : 0;
-        info[5] = h->d_dwtape ? h->dw_slices : 0;
+        info[5] = h->d_dwtape ? h->dw.slices : 0;
         info[6] = h->conv.c;
     } else if (h->use_rt) {
         info[1] = h->rt_block;
@@ -1067,7 +1067,7 @@ extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
         info[1] = h->t16_dwtape == 1 ? h->t16_block : 0;
         info[2] = h->t16_dwtape == 1 ? h->t16_nblocks : 0;
         info[4] = h->t16_dwtape == 1 ? 1 : 0;
-        info[5] = h->t16_dwtape == 1 ? h->dw_slices : 0;
+        info[5] = h->t16_dwtape == 1 ? h->dw.slices : 0;
         info[6] = (h->fwd_split ? 1 : 0) | ((h->adj_split && h->t16_dwtape == 1 && h->d_t16_ztape) ? 2 : 0) | (h->split_rich ? 4 : 0);
     }
     return 0;

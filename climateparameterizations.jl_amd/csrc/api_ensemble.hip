@@ -66,9 +66,8 @@ static int ens_plan_tapes(colnde_handle* h) {
     const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
     const size_t n_rec = (size_t)h->n_tiles * n_steps * m.nst;
     const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
-    std::vector<DwMacro> mac;
-    build_dw_macros(h, n_rec, mac);                          // the slice count a single handle of this size plans: same reduction order
-    h->t16_rows = h->n_tiles + h->dw_slices;
+    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order
+    h->t16_rows = h->n_tiles + h->dw.slices;
     const size_t f_tape = n_rec * CT * m.ns, f_dw = n_rec * CT * R, f_rich = n_rec * rt_split_rich_record_floats(),
                  f_plain = n_rec * CT * t16_ztape_col_floats(m), f_slab = (size_t)h->t16_rows * P8,
                  f_sol = (size_t)h->n_col * h->cfg.n_save * m.ns, f_img = RT_IMG_STRIDE;
@@ -91,8 +90,7 @@ static int ens_plan_tapes(colnde_handle* h) {
     if (e == hipSuccess) e = h->mem.alloc(&h->d_tape, (size_t)K * f_tape);
     if (e == hipSuccess) e = h->mem.alloc(&h->d_t16_ztape, (size_t)K * f_z);
     if (e == hipSuccess) e = h->mem.alloc(&h->d_slab, (size_t)K * f_slab);
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
-    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload_dw_plan(h);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         h->mem.rollback(mark);
@@ -325,9 +323,8 @@ static int fc_ens_plan_tapes(colnde_handle* h) {
     const size_t tiles_b = (size_t)n32 / cw;
     const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;
     const size_t n_rec = tiles_b * (cw / 16) * stage_recs;
-    std::vector<DwMacro> mac;
-    build_dw_macros(h, n_rec, mac);                          // the slice count a single handle of this size plans: same reduction order
-    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw_slices;
+    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order
+    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw.slices;
     FcEns& en = h->fens;
     en.dwtape = n_rec * CT * R;
     en.masks = tiles_b * stage_recs * fc_mask_words();
@@ -346,8 +343,7 @@ static int fc_ens_plan_tapes(colnde_handle* h) {
         e = h->mem.alloc(&h->conv.d_ctape, K * h->conv.ctape_stride);
         if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_cslab, K * h->conv.cslab_stride);
     }
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
-    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload_dw_plan(h);
     if (e == hipSuccess) e = h->mem.alloc(&h->d_slab, K * en.slab);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -539,11 +535,7 @@ extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_we
     {
         Timed tm(h, K_DW1);
         const size_t n_rec = (size_t)h->n_tiles * (h->cfg.n_save - 1) * h->cfg.substeps * h->m.nst;
-        float* rows = h->d_slab + (size_t)h->n_tiles * stride;
-        e = (h->sp_dw && !h->dw_split.passes.empty())
-            ? launch_dw_gemm_split(h->d_dwtape, n_rec, (int)dwtape_row_floats(h->m), h->dw_split, h->dw_slices, rows, stride, h->stream, K, h->ens.dwtape, h->ens.slab)
-            : launch_dw_gemm(h->d_dwtape, n_rec, (int)dwtape_row_floats(h->m), h->d_macros, h->n_macros, h->dw_slices, rows, stride, h->stream, K, h->ens.dwtape,
-                             h->ens.slab);
+        e = dw_launch(h, n_rec, h->d_slab + (size_t)h->n_tiles * stride, K, h->ens.dwtape, h->ens.slab);
         if (e != hipSuccess) return fail("ensemble dW GEMM launch failed: %s", hipGetErrorString(e));
     }
     {

@@ -1,6 +1,7 @@
 // api_grad.hip — loss and gradient of a single handle: the tape planners of the three engines and colnde_loss_grad[_dev].
 #include "api_internal.h"
 #include "tape_plan.h"
+#include "dw_plan.h"
 
 // Sizes the regtile engine's tapes.  They hold ONE block of columns; a problem whose tapes exceed the free HBM (many columns, or a
 // long horizon: 1,153 frames need 4x the bytes per column of the 2-day suite) runs its gradient path block after block into the same
@@ -41,39 +42,28 @@ static int rt_plan_tapes(colnde_handle* h) {
     return 0;
 }
 
-// The dW GEMM's work list: 64x64 blocks of every layer's weight matrix, and the number of K-slices of the records
-void build_dw_macros(colnde_handle* h, size_t n_rec, std::vector<DwMacro>& mac) {
-    const DevModel& m = h->m;
-    const size_t R = dwtape_row_floats(m);
-    std::vector<int> matrix_of;
-    for (int net = 0; net < m.n_nets; net++)
-        for (int l = 0; l < m.n_layers; l++) {
-            const int ni = m.sizes[l], no = m.sizes[l + 1];
-            for (int i0 = 0; i0 < ni; i0 += 64)
-                for (int j0 = 0; j0 < no; j0 += 64) {
-                    DwMacro d;
-                    d.a_feat = l == 0 ? i0 : dwtape_ns4(m) + net * dwtape_act4(m) + m.act_off[l - 1] + i0;
-                    d.d_feat = dwtape_ns4(m) + (m.n_nets + net) * dwtape_act4(m) + m.act_off[l] + j0;
-                    d.ni_rem = std::min(64, ni - i0);
-                    d.no_rem = std::min(64, no - j0);
-                    d.g_off = net * m.net_size + m.w_off[l] + i0 * no + j0;
-                    d.no = no;
-                    mac.push_back(d);
-                    matrix_of.push_back(net * m.n_layers + l);
-                }
-        }
-    h->n_macros = (int)mac.size();
-    dw_split_free(h->dw_split);
-    // the split (bf16-pipe) dW GEMM keeps only a pass's operand FEATURES in LDS, as planes: it also serves records that do not fit the LDS whole (the wide
-    // wind-mixing networks: 325 KB per 16-column record), with the large matrices cut into chunks of output blocks (dw_split_build)
-    const bool lds_fit = dw_gemm_lds_fits((int)R, h->n_macros);
-    const bool split_ok = dw_split_build(mac, matrix_of, (int)R, h->dw_split);
-    const int n_groups = (h->n_macros + 3) / 4;
-    size_t slices = std::max<size_t>(8, ((size_t)2048 / n_groups + 7) / 8 * 8);
-    slices = std::min(slices, std::max<size_t>(8, (n_rec / 8 + 7) / 8 * 8));
-    if (lds_fit || (split_ok && h->sp_dw))           // one workgroup per CU (two records / two plane buffers in LDS): two rounds of slices
-        slices = std::min<size_t>(512, std::max<size_t>(1, n_rec));
-    h->dw_slices = (int)slices;
+// The dW GEMM's plan for tapes of n_rec records: the block lists and passes of the network, the slice count of this size and arithmetic (dw_plan.h)
+void build_dw_plan(colnde_handle* h, size_t n_rec) {
+    dw_plan_blocks(h->m, h->dw);
+    dw_plan_slices(h->dw, n_rec, dw_gemm_lds_fits((int)dwtape_row_floats(h->m), h->dw.n_macros), h->sp_dw);
+}
+
+hipError_t upload_dw_plan(colnde_handle* h) {
+    const DwPlan& p = h->dw;
+    hipError_t e = h->mem.alloc(&h->d_macros, p.macros.size());
+    if (e == hipSuccess) e = hipMemcpy(h->d_macros, p.macros.data(), p.macros.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess && p.split_ok) e = h->mem.alloc(&h->d_split_macros, p.split_macros.size());
+    if (e == hipSuccess && p.split_ok) e = hipMemcpy(h->d_split_macros, p.split_macros.data(), p.split_macros.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    return e;
+}
+
+// The bf16-split kernel when the handle's weight-gradient arithmetic asks for it and the plan has passes, else the f32 kernels.
+// (Open advisor finding, left for its own change: the slice count was chosen for the arithmetic at plan time and is not re-planned by colnde_set_matrix_arithmetic.)
+hipError_t dw_launch(colnde_handle* h, size_t n_records, float* slab_rows, int K, size_t tape_mstride, size_t slab_mstride) {
+    const int R = (int)dwtape_row_floats(h->m), stride = h->m.n_params + 8;
+    if (h->sp_dw && !h->dw.passes.empty())
+        return launch_dw_gemm_split(h->d_dwtape, n_records, R, h->dw, h->d_split_macros, h->dw.slices, slab_rows, stride, h->stream, K, tape_mstride, slab_mstride);
+    return launch_dw_gemm(h->d_dwtape, n_records, R, h->d_macros, h->dw.n_macros, h->dw.slices, slab_rows, stride, h->stream, K, tape_mstride, slab_mstride);
 }
 
 // fc32 gradient path: the records (forward: xs, a1, a2; adjoint: dz1, dz2, dz3) and the bit tapes.  When they do not fit in the free HBM for the
@@ -114,9 +104,8 @@ static int fc_plan_tapes(colnde_handle* h) {
     const size_t tiles_b = (size_t)block / cw;                                  // (block is a multiple of 32)
     const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;          // (tile, stage) records per tile held by the tapes
     const size_t n_rec = tiles_b * (cw / 16) * stage_recs;                     // records are tile16's: 16 columns each
-    std::vector<DwMacro> mac;
-    build_dw_macros(h, n_rec, mac);
-    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw_slices;
+    build_dw_plan(h, n_rec);
+    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw.slices;
     const int stride = m.n_params + 8;
     const size_t mark = h->mem.mark();
     hipError_t e = h->mem.alloc(&h->d_dwtape, n_rec * CT * R);
@@ -128,8 +117,7 @@ static int fc_plan_tapes(colnde_handle* h) {
         e = h->mem.alloc(&h->conv.d_ctape, n_rec * fc_conv_tape_floats(m.Nz));
         if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_cslab, (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS);
     }
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
-    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload_dw_plan(h);
     if (e == hipSuccess && !h->d_slab) e = h->mem.alloc(&h->d_slab, (size_t)h->fc_rows * stride);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -206,14 +194,12 @@ static int t16_plan_dwtape(colnde_handle* h) {
     const size_t need = n_rec * CT * R * sizeof(float);
     h->t16_block = block;
     h->t16_nblocks = (n16 + block - 1) / block;
-    std::vector<DwMacro> mac;
-    build_dw_macros(h, n_rec, mac);
-    h->t16_rows = h->n_tiles + h->t16_nblocks * h->dw_slices;
+    build_dw_plan(h, n_rec);
+    h->t16_rows = h->n_tiles + h->t16_nblocks * h->dw.slices;
     const int stride = m.n_params + 8;
     const size_t mark = h->mem.mark();
     hipError_t e = h->mem.alloc(&h->d_dwtape, need / sizeof(float));
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_macros, mac.size());
-    if (e == hipSuccess) e = hipMemcpy(h->d_macros, mac.data(), mac.size() * sizeof(DwMacro), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload_dw_plan(h);
     if (e == hipSuccess && !h->d_slab) e = h->mem.alloc(&h->d_slab, (size_t)h->t16_rows * stride);
     if (e != hipSuccess) {                  // no delta tape: the in-register path follows
         (void)hipGetLastError();
@@ -334,12 +320,8 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
             }
             {
                 Timed tm(h, K_DW1);
-                if (h->sp_dw && !h->dw_split.passes.empty())
-                    e = launch_dw_gemm_split(h->d_dwtape, tiles_b * (cw / 16) * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst, (int)dwtape_row_floats(h->m), h->dw_split,
-                                             h->dw_slices, h->d_slab + (gemm_rows0 + ((size_t)b * nseg + sg) * h->dw_slices) * stride, stride, h->stream, K, h->fens.dwtape, h->fens.slab);
-                else
-                e = launch_dw_gemm(h->d_dwtape, tiles_b * (cw / 16) * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst, (int)dwtape_row_floats(h->m), h->d_macros,
-                                   h->n_macros, h->dw_slices, h->d_slab + (gemm_rows0 + ((size_t)b * nseg + sg) * h->dw_slices) * stride, stride, h->stream, K, h->fens.dwtape, h->fens.slab);
+                e = dw_launch(h, tiles_b * (cw / 16) * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst,
+                              h->d_slab + (gemm_rows0 + ((size_t)b * nseg + sg) * h->dw.slices) * stride, K, h->fens.dwtape, h->fens.slab);
                 if (e != hipSuccess) return fail("%sdW GEMM launch failed: %s", ens, hipGetErrorString(e));
                 if (h->conv.c) {                                        // the filter's c + 1 entries (every model's), from the conv tape of the same records
                     e = launch_fc_conv_grad(h->conv.d_ctape, (long)(tiles_b * (size_t)(iv1 - iv0) * h->cfg.substeps * h->m.nst) * 16, h->m.Nz, h->conv.c,
@@ -398,11 +380,7 @@ static int t16_taped_loss_grad(colnde_handle* h, const float* d_weights, const f
         }
         {
             Timed tm(h, K_DW1);
-            hipError_t e = (h->sp_dw && !h->dw_split.passes.empty())
-                ? launch_dw_gemm_split(h->d_dwtape, (size_t)tiles_b * n_steps * h->m.nst, (int)dwtape_row_floats(h->m), h->dw_split,
-                                       h->dw_slices, h->d_slab + ((size_t)h->n_tiles + (size_t)b * h->dw_slices) * stride, stride, h->stream)
-                : launch_dw_gemm(h->d_dwtape, (size_t)tiles_b * n_steps * h->m.nst, (int)dwtape_row_floats(h->m), h->d_macros, h->n_macros,
-                                          h->dw_slices, h->d_slab + ((size_t)h->n_tiles + (size_t)b * h->dw_slices) * stride, stride, h->stream);
+            hipError_t e = dw_launch(h, (size_t)tiles_b * n_steps * h->m.nst, h->d_slab + ((size_t)h->n_tiles + (size_t)b * h->dw.slices) * stride);
             if (e != hipSuccess) return fail("dW GEMM launch failed: %s", hipGetErrorString(e));
         }
     }

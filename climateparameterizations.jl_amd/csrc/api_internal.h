@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "engine_dwgemm.h"
 #include "engine_tile16.h"
 #include "engine_regtile.h"
 #include "engine_netsplit.h"
@@ -49,7 +50,11 @@ int rt_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int
 int t16_forward_range(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape, int c0, int nc);
 int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int nc, int iv0 = 0, int iv1 = -1, int tape_iv0 = -1);
 // ---- api_grad.hip, api_ensemble.hip, api_substeps.hip -------------------------------------------------------
-void build_dw_macros(colnde_handle* h, size_t n_rec, std::vector<DwMacro>& mac);
+// the dW GEMM of the taped gradient paths: h->dw planned for n_rec records (dw_plan.h), its two block lists uploaded into slots of h->mem (inside the
+// caller's mark / rollback bracket), and the one place that launches it — K models: grid.y, their records and slab rows the strides apart
+void build_dw_plan(colnde_handle* h, size_t n_rec);
+hipError_t upload_dw_plan(colnde_handle* h);
+hipError_t dw_launch(colnde_handle* h, size_t n_records, float* slab_rows, int K = 1, size_t tape_mstride = 0, size_t slab_mstride = 0);
 int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
 colnde_config model_config(const colnde_config* cfg, const float* physics, int k);
 int choose_substeps_impl(colnde_handle* h, const float* d_weights, float reltol, int* chosen, float* estimate);
@@ -212,9 +217,9 @@ struct colnde_handle {
     int t16_dwtape = -1;            // -1 undecided, 0 off, 1 on
     float* d_dwtape = nullptr;
     float* d_t16_ztape = nullptr;   // taped mode: hidden pre-activations written by the forward kernel (the adjoint skips its forward GEMMs)
-    DwMacro* d_macros = nullptr;
-    DwSplitPlan dw_split;                       // the dW GEMM on the bf16 pipe (exact operand splitting), built with the tapes' plan whenever the records fit LDS; used when sp_dw
-    int n_macros = 0, dw_slices = 0, t16_rows = 0;
+    DwPlan dw;                      // the dW GEMM's plan, built with the tapes' (build_dw_plan); its split passes run when sp_dw
+    DwMacro *d_macros = nullptr, *d_split_macros = nullptr;   // ... and the device copies of its two block lists (the split one: null without a split plan)
+    int t16_rows = 0;
     int t16_block = 0, t16_nblocks = 0;   // taped mode: columns per pass (multiple of 16) — the tapes hold one block
     int *d_bias_zoff = nullptr, *d_bias_goff = nullptr;
     bool have_problem = false, have_truth = false;

@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
-#include "engine_tile16.h"   // LossWeights
+#include "engine_dwgemm.h"   // LossWeights
 
 #define CLOSURE_N_PARAMS 5   // nu0, nu_minus, dRi, Ric, Pr (mpp_parameters order)
 #define CLOSURE_ROW 16       // floats per (set, column) partial row: 5 sensitivities, 6 raw loss sums, padding

@@ -7,6 +7,7 @@
 //
 // Reference arithmetic: wind_mixing/src/NDE_training.jl:46-165 (NDE, predict_flux, predict_NDE).
 #include "engine_netsplit.h"
+#include "engine_tile16.h"   // t16_ztape_col_floats: the pre-activation tape this unit's kernels share with tile16
 #include "regtile_dev.h"
 #include "kernel_select.h"
 

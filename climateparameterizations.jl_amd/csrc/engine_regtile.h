@@ -2,7 +2,7 @@
 // (Nz = 32, three Chain(Dense(96,50,σ), Dense(50,20,σ), Dense(20,31)) nets: wind_mixing/train_NDE.jl:103).
 #pragma once
 #include "colnde_dev.h"
-#include "engine_tile16.h"
+#include "engine_dwgemm.h"   // LossWeights
 
 #define RT_COLS 32                 // columns per wavefront tile (N of v_mfma_f32_32x32x2_f32)
 #define RT_WAVES 4                 // wavefronts per workgroup (one per SIMD, up to 512 VGPRs each)

@@ -1,15 +1,14 @@
-// engine_tile16.h — host/device interface of the MFMA tile engine.
+// engine_tile16.h — host/device interface of the MFMA tile engine: pack, rhs, forward, loss, adjoint, infer, pretrain and their launch geometry.
+// (The taped adjoint's records are contracted by engine_dwgemm.h's GEMM, every slab is reduced by its launch_reduce.)
 #pragma once
-#include <vector>
 #include "colnde_dev.h"
+#include "engine_dwgemm.h"   // LossWeights, dwtape_row_floats (the record launch_adjoint's dwtape holds)
 
 struct PackInfo {
     int pf_off[COLNDE_MAX_LAYERS + 1];   // per-layer offsets inside one net's forward A-operand image
     int pb_off[COLNDE_MAX_LAYERS + 1];   // ... backward (transposed) image
     int pf_net, pb_net;                  // floats per net
 };
-
-struct LossWeights { float w[8]; };       // w[q] = loss_scaling[q] / (global element count of term q)
 
 // launch geometry chosen by the host for the adjoint kernel
 struct AdjointGeom { int nthreads, maxt, maxr, wlds; };
@@ -53,26 +52,6 @@ hipError_t launch_adjoint(const DevModel& m, const PackInfo& pk, const float* w,
                           size_t lds_bytes, hipStream_t stream, float* dwtape = nullptr, const float* ztape = nullptr);
 // hidden pre-activation tape of the taped-dW mode: floats per column
 static inline size_t t16_ztape_col_floats(const DevModel& m) { return (size_t)((m.n_nets * m.act_off[m.n_layers - 1] + 3) & ~3); }
-// taped-dW mode (dwtape != nullptr above): floats per 16-column tile and stage, and the contraction kernel
-static inline int dwtape_ns4(const DevModel& m) { return (m.ns + 3) & ~3; }
-static inline int dwtape_act4(const DevModel& m) { return (m.act_total + 3) & ~3; }
-static inline size_t dwtape_row_floats(const DevModel& m) { return (size_t)dwtape_ns4(m) + (size_t)2 * m.n_nets * dwtape_act4(m); }
-bool dw_gemm_lds_fits(int row_floats, int n_macros);     // the LDS-staged dW kernel applies (else the L2-streaming one)
-// n_models > 1 (ensembles): grid.y = model, its records tape_mstride and its slab rows slab_mstride floats after the previous model's
-hipError_t launch_dw_gemm(const float* dwtape, size_t n_records, int row_floats, const DwMacro* macros, int n_macros, int n_slices,
-                          float* slab_rows, int slab_stride, hipStream_t stream, int n_models = 1, size_t tape_mstride = 0, size_t slab_mstride = 0);
-// dW GEMM on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT; the plan is built with the tapes whenever the records fit LDS): the blocks are
-// dealt to passes by layer so that a pass's operand features (split ONCE per record into LDS planes) and its accumulators fit one workgroup
-struct DwSeg { int src, len, dst; };                                  // floats of a record row [src, src + len) -> compact features [dst, dst + len)
-struct DwPassDesc { DwSeg seg[8]; int n_seg, Fc, m0, n_macros, maxm, nit; };
-struct DwSplitPlan { std::vector<DwPassDesc> passes; DwMacro* d_macros = nullptr; };
-bool dw_split_build(const std::vector<DwMacro>& mac, const std::vector<int>& matrix_of, int row_floats, DwSplitPlan& plan);
-void dw_split_free(DwSplitPlan& plan);
-hipError_t launch_dw_gemm_split(const float* dwtape, size_t n_records, int row_floats, const DwSplitPlan& plan, int n_slices,
-                                float* slab_rows, int slab_stride, hipStream_t stream, int n_models = 1, size_t tape_mstride = 0, size_t slab_mstride = 0);
-// n_models > 1 (ensembles): grid.y = model, slab slab_mstride and out out_mstride floats apart per model
-hipError_t launch_reduce(const float* slab, int n_tiles, int n_params, int stride, const LossWeights& lw, float* out,
-                         hipStream_t stream, int n_models = 1, size_t slab_mstride = 0, int out_mstride = 0);
 hipError_t launch_infer(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* T,
                         const float* top_flux, float inv_dz, float* out, int n_col, int nthreads, size_t lds_bytes,
                         hipStream_t stream);
