@@ -571,3 +571,46 @@ extern "C" int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights,
     if (e != hipSuccess) return fail("ensemble ADAM launch failed: %s", hipGetErrorString(e));
     return 0;
 }
+
+// ---- T -> wT pre-training of all K networks in one launch (engine_fc_pretrain.hip; train_free_convection_nde.jl:182-216) -----------------------------
+// Semantics of colnde_pretrain_flux_dev, per model: the K sums of the per-sample losses come back in one copy and the means are formed here with the
+// single call's expression.
+extern "C" int colnde_ensemble_pretrain_flux_dev(colnde_handle* h, float* d_theta, float* d_m, float* d_v, const float* d_T, const float* d_bcs,
+                                                 const float* d_flux, const int32_t* d_order, int n_samples, const float* d_coeff, int optimiser,
+                                                 const float* d_eta, float beta1, float beta2, float eps, double beta_t[2], int update, float* mean_loss) {
+    if (!h) return fail("%s: null handle", __func__);
+    if (h->closure) return fail("%s takes the weight vectors of a free-convection ensemble, but this is a closure handle (no networks)", __func__);
+    if (!h->ensemble)
+        return fail("%s takes the handles of colnde_create_fc_ensemble / colnde_create_conv_ensemble (K = 1 for one network): this is a single-model handle "
+                    "(colnde_pretrain_flux_dev pre-trains a plain single model)", __func__);
+    if (!h->use_fc) return fail("%s covers the free-convection ensembles: this ensemble holds wind-mixing models (no T -> wT pre-training)", __func__);
+    if (!d_theta || !d_T || !d_bcs || !d_flux || !beta_t || !mean_loss) return fail("%s: null pointer argument", __func__);
+    if (optimiser != FCP_ADAM && optimiser != FCP_DESCENT) return fail("%s: optimiser = %d outside {0 = ADAM, 1 = Descent}", __func__, optimiser);
+    if (n_samples < 1) return fail("%s: n_samples must be >= 1", __func__);
+    const bool adam = optimiser == FCP_ADAM;
+    if (update && !d_eta) return fail("%s: the rates d_eta [K] are needed when update != 0", __func__);
+    if (update && adam && (!d_m || !d_v)) return fail("%s: the ADAM moments are needed when update != 0 under optimiser 0", __func__);
+    if (adam && !(beta_t[0] < 1.0 && beta_t[1] < 1.0)) return fail("%s: running powers beta^t must be < 1", __func__);
+    const int K = h->n_models;
+    const DevModel dense = fc_pretrain_dense_model(h->m, h->conv.c);
+    if (dense.n_params != user_params(h)) return fail("%s: parameter layout mismatch (%d vs %d)", __func__, dense.n_params, user_params(h));
+    if (fc_pretrain_lds_bytes(dense, h->conv.c) > PRETRAIN_LDS_CAP)
+        return fail("%s: network too large, a workgroup needs %zu B of LDS (> %zu)", __func__, fc_pretrain_lds_bytes(dense, h->conv.c), PRETRAIN_LDS_CAP);
+    HIPCHK(hipSetDevice(h->device));
+    DevScratch sc(h->stream);
+    const size_t loss_bytes = ((size_t)K * sizeof(float) + 15) / 16 * 16;
+    HIPCHK(sc.alloc(loss_bytes + 2 * sizeof(double)));
+    float* d_loss = sc.p;
+    double* d_bt = reinterpret_cast<double*>(reinterpret_cast<char*>(d_loss) + loss_bytes);
+    hipError_t e = launch_fc_pretrain_ens(dense, h->conv.c, K, d_theta, adam ? d_m : nullptr, adam ? d_v : nullptr, d_T, d_bcs, d_flux, d_order, n_samples, d_coeff,
+                                          optimiser, d_eta, beta1, beta2, eps, beta_t[0], beta_t[1], update, d_loss, d_bt, h->stream);
+    std::vector<float> loss((size_t)K, 0.0f);
+    double bt[2] = {beta_t[0], beta_t[1]};
+    if (e == hipSuccess) e = hipMemcpyAsync(loss.data(), d_loss, (size_t)K * sizeof(float), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(bt, d_bt, sizeof(bt), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail("%s failed: %s", __func__, hipGetErrorString(e));
+    for (int k = 0; k < K; k++) mean_loss[k] = loss[k] / (float)n_samples;
+    if (update && adam) { beta_t[0] = bt[0]; beta_t[1] = bt[1]; }
+    return 0;
+}

@@ -20,6 +20,7 @@
 #include "engine_closure.h"
 #include "engine_wm_infer.h"
 #include "engine_fc_embed.h"
+#include "engine_fc_pretrain.h"
 
 #pragma GCC visibility push(hidden)
 

@@ -21,6 +21,7 @@
 #include "engine_tile16.h"
 #include "kernel_select.h"
 #include "split_bf16.h"
+#include "pretrain_sample.h"
 #include <algorithm>
 
 #define FWD_MAXR 12   // owner-thread register items per state array in the forward kernel: CT*ns <= FWD_MAXR*blockDim
@@ -760,8 +761,8 @@ __device__ void physics_vjp(const DevModel& m, const float* xs, const float* dba
 //     NN_flux = [b; NN(x); t]-style face vector minus the diffusive / adjustment flux of the state (independent of the weights)
 //     loss    = mse(NN_flux, flux) + gradient_scaling * mse(D^c flux, D^c NN_flux)
 // update = 0 evaluates the mean loss at fixed weights (`total_loss(training_data)`, :234-236).
-// LDS: act[act_total + ns] (a_0 = x, then every layer's activations), z[act_total] pre-activations, d[act_total] deltas,
-//      F, y, c: [Nz + 1] face vectors, red[64].
+// The per-sample chain (forward, loss, backward, update) and the LDS carving live in pretrain_sample.h, shared with fc_pretrain_ens_kernel
+// (engine_fc_pretrain.hip: one workgroup per model of a free-convection ensemble); this kernel adds the wind-mixing closures of the face flux.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(512)
 pretrain_kernel(DevModel m, int flux_type, float* __restrict__ theta, float* __restrict__ mom, float* __restrict__ vel,
@@ -770,23 +771,17 @@ pretrain_kernel(DevModel m, int flux_type, float* __restrict__ theta, float* __r
                 float* __restrict__ loss_out, double* __restrict__ bt_out) {
     extern __shared__ __attribute__((aligned(16))) float pt_smem[];
     const int tid = threadIdx.x, nth = blockDim.x;
-    const int Nz = m.Nz, nf = Nz + 1, L = m.n_layers, ns = m.ns;
-    float* a0 = pt_smem;                       // x
-    float* act = a0 + ((ns + 3) & ~3);         // a_l at act + act_off[l-1]... (act_off[l] = offset of layer l+1's outputs)
-    float* zz = act + m.act_total + 4;
-    float* dd = zz + m.act_total + 4;
-    float* F = dd + m.act_total + 4;
-    float* yv = F + nf + 3;
-    float* cf = yv + nf + 3;
-    float* red = cf + nf + 3;
+    const int Nz = m.Nz, nf = Nz + 1;
+    const PtLds lds = pt_carve(m, pt_smem);
+    const float* a0 = lds.a0;
+    float* cf = lds.cf;
     const bool wm = m.model == COLNDE_MODEL_WIND_MIXING;
     const int k = wm ? flux_type : 2;
     double p1 = bt1, p2 = bt2;                 // running powers beta^t (uniform over the workgroup)
     float loss_sum = 0.0f;
     for (int s = 0; s < n_samples; s++) {
         const int idx = order ? order[s] : s;
-        for (int i = tid; i < ns; i += nth) a0[i] = X[(size_t)idx * ns + i];
-        for (int f = tid; f < nf; f += nth) yv[f] = Y[(size_t)idx * nf + f];
+        pt_load(m, lds, X, Y, idx, tid, nth);
         __syncthreads();
         // weight-independent part of the face flux: boundary faces and the diffusive / adjustment flux of the state
         for (int f = tid; f < nf; f += nth) {
@@ -805,84 +800,21 @@ pretrain_kernel(DevModel m, int flux_type, float* __restrict__ theta, float* __r
                     c = -m.cs[2] * m.kappa * fminf(0.0f, gT);
                 }
             } else {
-                c = f == 0 ? bc[0] : (f == Nz ? bc[1] : 0.0f);
+                c = pt_bc_face(bc, f, Nz);
             }
             cf[f] = c;
         }
-        // forward
+        // the per-sample chain of pretrain_sample.h: forward, loss and cotangent, backward, Flux ADAM on every parameter of this net
         const float* th = theta + (wm ? k * m.net_size : 0);
-        for (int l = 0; l < L; l++) {
-            const int ni = m.sizes[l], no = m.sizes[l + 1];
-            const float* ain = l == 0 ? a0 : act + m.act_off[l - 1];
-            const float* W = th + m.w_off[l];
-            for (int o = tid; o < no; o += nth) {
-                float acc = th[m.b_off[l] + o];
-                for (int i = 0; i < ni; i++) acc = fmaf(W[i * no + o], ain[i], acc);
-                zz[m.act_off[l] + o] = acc;
-                act[m.act_off[l] + o] = dev_act(m.acts[l], acc);
-            }
-            __syncthreads();
-        }
-        // face flux, loss and its cotangent on the network output
-        const float* out = act + m.act_off[L - 1];
-        for (int f = tid; f < nf; f += nth) F[f] = cf[f] + ((f >= 1 && f < Nz) ? out[f - 1] : 0.0f);
-        __syncthreads();
-        float part = 0.0f;
-        for (int f = tid; f < nf; f += nth) {
-            const float r = F[f] - yv[f];
-            part += r * r * (1.0f / (float)nf);
-            if (f < Nz) {
-                const float dg = ((F[f + 1] - F[f]) - (yv[f + 1] - yv[f])) * (float)Nz;
-                part += gs * dg * dg * (1.0f / (float)Nz);
-            }
-            if (f >= 1 && f < Nz) {
-                const float dgm = ((F[f] - F[f - 1]) - (yv[f] - yv[f - 1])) * (float)Nz;
-                const float dgp = ((F[f + 1] - F[f]) - (yv[f + 1] - yv[f])) * (float)Nz;
-                const float g = 2.0f / (float)nf * r + gs * 2.0f * (dgm - dgp);
-                dd[m.act_off[L - 1] + f - 1] = g * dev_act_grad(m.acts[L - 1], zz[m.act_off[L - 1] + f - 1]);
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off);
-        if ((tid & 63) == 0) red[tid >> 6] = part;
-        __syncthreads();
-        if (tid == 0) {
-            float t = 0.0f;
-            for (int w = 0; w < (nth >> 6); w++) t += red[w];
-            loss_sum += t;
-        }
+        pt_forward(m, lds, th, a0, tid, nth);
+        loss_sum += pt_loss(m, lds, gs, tid, nth);
         if (!update) { __syncthreads(); continue; }
-        // backward: every delta with the weights as they stood before this sample's update
-        for (int l = L - 1; l >= 1; l--) {
-            const int ni = m.sizes[l], no = m.sizes[l + 1];
-            const float* W = th + m.w_off[l];
-            for (int i = tid; i < ni; i += nth) {
-                float acc = 0.0f;
-                for (int o = 0; o < no; o++) acc = fmaf(W[i * no + o], dd[m.act_off[l] + o], acc);
-                dd[m.act_off[l - 1] + i] = acc * dev_act_grad(m.acts[l - 1], zz[m.act_off[l - 1] + i]);
-            }
-            __syncthreads();
-        }
-        // Flux ADAM (apply! + update!) on every parameter of this net; gradient element = delta_out * input (bias: delta_out)
+        pt_backward(m, lds, th, tid, nth);
         const float c1 = (float)(1.0 / (1.0 - p1)), c2 = (float)(1.0 / (1.0 - p2));
         float* tw = theta + (wm ? k * m.net_size : 0);
         float* tm = mom + (wm ? k * m.net_size : 0);
         float* tv = vel + (wm ? k * m.net_size : 0);
-        for (int l = 0; l < L; l++) {
-            const int ni = m.sizes[l], no = m.sizes[l + 1];
-            const float* ain = l == 0 ? a0 : act + m.act_off[l - 1];
-            const int nw = ni * no;
-            for (int e = tid; e < nw + no; e += nth) {
-                const bool bias = e >= nw;
-                const int o = bias ? e - nw : e % no, i = bias ? 0 : e / no;
-                const float g = dd[m.act_off[l] + o] * (bias ? 1.0f : ain[i]);
-                const int q = (bias ? m.b_off[l] - nw : m.w_off[l]) + e;
-                const float mt = b1 * tm[q] + (1.0f - b1) * g;
-                const float vt = b2 * tv[q] + (1.0f - b2) * g * g;
-                tm[q] = mt;
-                tv[q] = vt;
-                tw[q] -= eta * (mt * c1) / (sqrtf(vt * c2) + eps_adam);
-            }
-        }
+        pt_update<true>(m, lds, tw, tm, tv, a0, 0.0f, eta, b1, b2, eps_adam, c1, c2, tid, nth);
         p1 *= (double)b1;
         p2 *= (double)b2;
         __syncthreads();

@@ -324,3 +324,67 @@ def nde_loss_history(T0, nde_params, true_sols, cfg: NDEConfig, W_history, devic
     finally:
         ens.close()
     return per_t.astype(np.float64).mean(axis=2).astype(np.float32), per_t
+
+
+# ---- T -> wT pre-training of a whole sweep (train_free_convection_nde.jl:182-216) --------------------------------------------------------------------
+
+def pretrain_orders(seeds, n: int, n_passes: int):
+    """The sample orders of `train_neural_network_ensemble`: [n_passes, K, n] int32 — model k draws a fresh permutation of 0..n-1 per pass from
+    `numpy.random.default_rng(seeds[k])` (`Flux.train!` over the shuffled data set; the reference's process k seeds its own shuffle)."""
+    rngs = [np.random.default_rng(int(s)) for s in seeds]
+    return np.stack([np.stack([r.permutation(n) for r in rngs]) for _ in range(n_passes)]).astype(np.int32) if n_passes else np.zeros((0, len(rngs), n), np.int32)
+
+
+def train_neural_network_ensemble(ens, W, T, bcs, wT, etas=None, epochs: int = 10, optimizers=(("adam", 1e-3), ("descent", 1e-2)), causal_coeff=None,
+                                  seeds=None, beta=(0.9, 0.999), eps: float = 1e-8):
+    """The driver's pre-training loop `for opt in optimizers, e in 1:epochs; Flux.train!(loss, ps, data, opt, cb = nn_callback)`
+    (train_free_convection_nde.jl:198-216) for the K networks of `ens` (a `FreeConvectionEnsemble`, plain or conv — the handle that then trains the
+    NDE) at once: one `pretrain_flux` launch per epoch, one optimiser update per sample and model, each model walking its own fresh permutation
+    (`pretrain_orders(seeds, n, passes)`; seeds None: 0..K-1).  W [K, n_params]; T [n, Nz], bcs [n, 2] = [bottom, top], wT [n, Nz + 1], scaled.
+    optimizers: (kind, rate) pairs, "adam" | "descent"; an ADAM's moments and running powers start afresh with it and carry across its epochs.
+    etas: None (every model takes each optimiser's rate) or [len(optimizers), K] per-model rates.  causal_coeff [K] or None: model k's loss is
+    mse([bottom; NN(T); top], wT) + c_k sum(abs2, W1[mask]).
+    Returns (theta [K, n_params], history [passes, K]): after each pass the loss over the training set at the weights it left (`nn_callback`)."""
+    import torch
+    from .nde import FC_PRETRAIN_OPTIMISERS, check_fc_pretrain_arrays
+    K = ens.n_models
+    Wn = np.ascontiguousarray(W, dtype=np.float32)
+    Tn, Bn, Yn = (np.ascontiguousarray(a, dtype=np.float32) for a in (T, bcs, wT))
+    cc = None if causal_coeff is None else np.ascontiguousarray(causal_coeff, dtype=np.float32)
+    kinds = []
+    for kind, _ in optimizers:
+        if kind not in FC_PRETRAIN_OPTIMISERS:
+            raise ValueError("optimizers: kinds are 'adam' and 'descent', got %r" % (kind,))
+        kinds.append(kind)
+    if etas is None:
+        et = np.array([[rate] * K for _, rate in optimizers], dtype=np.float32).reshape(len(kinds), K)
+    else:
+        et = np.ascontiguousarray(etas, dtype=np.float32)
+        if et.shape != (len(kinds), K):
+            raise ValueError("etas: expected shape %s (one row of per-model rates per optimiser), got %s" % ((len(kinds), K), et.shape))
+    if int(epochs) < 0:
+        raise ValueError("epochs must be >= 0")
+    seeds = list(range(K)) if seeds is None else list(seeds)
+    if len(seeds) != K:
+        raise ValueError("seeds: expected %d entries (one per model), got %d" % (K, len(seeds)))
+    n_passes = len(kinds) * int(epochs)
+    n = check_fc_pretrain_arrays(ens.cfg, K, Wn, Tn, Bn, Yn, coeff=cc, conv=ens.conv)
+    orders = pretrain_orders(seeds, n, n_passes)
+    if n_passes:
+        check_fc_pretrain_arrays(ens.cfg, K, Wn, Tn, Bn, Yn, order=orders[0], conv=ens.conv)
+    dev = torch.device("cuda", ens.device)
+    up = lambda a: None if a is None else torch.from_numpy(a).to(dev).contiguous()
+    theta, Td, Bd, Yd, cd = up(Wn.copy()), up(Tn), up(Bn), up(Yn), up(cc)
+    history = np.zeros((n_passes, K), np.float32)
+    p = 0
+    for i, kind in enumerate(kinds):
+        adam = kind == "adam"
+        m = torch.zeros_like(theta) if adam else None
+        v = torch.zeros_like(theta) if adam else None
+        bt = [float(beta[0]), float(beta[1])]
+        eta_d = up(et[i])
+        for _ in range(int(epochs)):
+            ens.pretrain_flux(theta, m, v, Td, Bd, Yd, up(orders[p]), cd, kind, eta_d, beta, eps, bt, update=True)
+            history[p] = ens.pretrain_flux(theta, None, None, Td, Bd, Yd, None, cd, kind, None, beta, eps, bt, update=False)
+            p += 1
+    return theta.cpu().numpy(), history

@@ -1056,6 +1056,42 @@ def check_fc_ensemble_arrays(cfg: NDEConfig, n_columns: int, n_models: int, weig
             raise ValueError("%s: expected shape %s for %d models, got %s" % (name, shape, K, tuple(a.shape)))
 
 
+FC_PRETRAIN_OPTIMISERS = {"adam": 0, "descent": 1}      # `optimiser` of colnde_ensemble_pretrain_flux_dev
+
+
+def _dtype_name(a) -> str:
+    return str(a.dtype).replace("torch.", "")
+
+
+def check_fc_pretrain_arrays(cfg: NDEConfig, n_models: int, theta, T, bcs, fluxes, order=None, coeff=None, etas=None, m=None, v=None, conv: int = 0):
+    """Shape, dtype and order-range rules of `FreeConvectionEnsemble.pretrain_flux` (no GPU needed; NumPy arrays or torch tensors), raised before any
+    handle is touched: theta, m, v [K, n_params] float32 (n_params = `fc_ensemble_n_params(cfg, conv)`); T [n, Nz], bcs [n, 2] = [bottom, top],
+    fluxes [n, Nz + 1] float32 with n >= 1; order [K, n] int32 with every entry in 0..n-1 (an index may repeat), or None; coeff, etas [K] float32 or
+    None.  Returns n."""
+    check_fc_ensemble_arrays(cfg, 1, n_models, conv=conv)
+    K, P, Nz = int(n_models), fc_ensemble_n_params(cfg, conv), cfg.Nz
+    if len(tuple(T.shape)) != 2 or int(T.shape[0]) < 1:
+        raise ValueError("T: expected shape [n, %d] with n >= 1, got %s" % (Nz, tuple(T.shape)))
+    n = int(T.shape[0])
+    for name, a, shape in (("theta", theta, (K, P)), ("m", m, (K, P)), ("v", v, (K, P)), ("T", T, (n, Nz)), ("bcs", bcs, (n, 2)), ("fluxes", fluxes, (n, Nz + 1)),
+                           ("coeff", coeff, (K,)), ("etas", etas, (K,))):
+        if a is None:
+            continue
+        if tuple(a.shape) != shape:
+            raise ValueError("%s: expected shape %s for %d models and %d samples, got %s" % (name, shape, K, n, tuple(a.shape)))
+        if _dtype_name(a) != "float32":
+            raise ValueError("%s: expected float32, got %s" % (name, _dtype_name(a)))
+    if order is not None:
+        if tuple(order.shape) != (K, n):
+            raise ValueError("order: expected shape %s (one row per model), got %s" % ((K, n), tuple(order.shape)))
+        if _dtype_name(order) != "int32":
+            raise ValueError("order: expected int32, got %s" % _dtype_name(order))
+        lo, hi = int(order.min()), int(order.max())
+        if lo < 0 or hi >= n:
+            raise ValueError("order: entries must lie in 0..%d, got %d..%d" % (n - 1, lo, hi))
+    return n
+
+
 class FreeConvectionEnsemble(ColumnNDEEnsemble):
     """K free-convection networks of the fc32 shape on the same simulations (`colnde_create_fc_ensemble`): the sweep of
     free_convection/train_free_convection_nde.jl (one process per seed / optimiser rate / penalty setting there) and the judging of a training run
@@ -1118,6 +1154,41 @@ class FreeConvectionEnsemble(ColumnNDEEnsemble):
         self.use_torch_stream()
         _lib.check(self._L.colnde_ensemble_causal_penalty_dev(self._h, w.data_ptr(), c.data_ptr(), r.data_ptr()))
         return r.cpu().numpy()
+
+    def pretrain_flux(self, theta, m, v, T, bcs, fluxes, order, coeff, opt_kind, etas, beta=(0.9, 0.999), eps: float = 1e-8, beta_t=None, update: bool = True):
+        """`colnde_ensemble_pretrain_flux_dev`: one `Flux.train!` pass of the T -> wT pre-training (train_free_convection_nde.jl:182-216) for all K
+        networks in one launch, over device tensors: theta, m, v [K, n_params] (updated in place), T [n, Nz], bcs [n, 2], fluxes [n, Nz + 1], order
+        [K, n] int32 or None (0..n-1 for every model), coeff [K] or None (the soft spatial-causality penalty c_k sum(abs2, W1[mask])), etas [K].
+        opt_kind "adam" | "descent" (or 0 | 1); under "descent" m and v may be None and beta_t stays.  beta_t: a list [beta1^t, beta2^t] advanced in place
+        by n steps (ADAM with update; None: a fresh optimiser's).  update=False: nothing is written, the mean loss at the given weights.
+        Returns the K mean losses (NumPy): with update, the mean of each sample's loss just before its own update."""
+        kind = FC_PRETRAIN_OPTIMISERS.get(opt_kind, opt_kind) if isinstance(opt_kind, str) else opt_kind
+        if kind not in (0, 1):
+            raise ValueError("opt_kind: 'adam' (0) or 'descent' (1), got %r" % (opt_kind,))
+        adam = kind == 0
+        if update and etas is None:
+            raise ValueError("the rates etas [K] are needed when update=True")
+        if update and adam and (m is None or v is None):
+            raise ValueError("the ADAM moments m and v are needed when update=True under 'adam'")
+        n = check_fc_pretrain_arrays(self.cfg, self.n_models, theta, T, bcs, fluxes, order, coeff, etas, m if adam else None, v if adam else None, conv=self.conv)
+        K, P, Nz = self.n_models, self.n_params, self.cfg.Nz
+        for t, shape in ((theta, (K, P)), (T, (n, Nz)), (bcs, (n, 2)), (fluxes, (n, Nz + 1)), (coeff, (K,)), (etas, (K,))) + (((m, (K, P)), (v, (K, P))) if adam else ()):
+            if t is not None:
+                self._chk_dev(t, shape)
+        if order is not None and not (order.is_cuda and order.is_contiguous() and order.device.index == self.device):
+            raise ValueError("order must be a contiguous int32 tensor on the handle's device")
+        if beta_t is None:
+            beta_t = [float(beta[0]), float(beta[1])]
+        P_ = lambda a: a.data_ptr() if a is not None else None
+        self.use_torch_stream()
+        bt = (ctypes.c_double * 2)(float(beta_t[0]), float(beta_t[1]))
+        loss = (ctypes.c_float * K)()
+        _lib.check(self._L.colnde_ensemble_pretrain_flux_dev(self._h, P_(theta), P_(m) if adam else None, P_(v) if adam else None, P_(T), P_(bcs), P_(fluxes),
+                                                             P_(order), n, P_(coeff), int(kind), P_(etas), float(beta[0]), float(beta[1]), float(eps), bt,
+                                                             int(bool(update)), loss))
+        if update and adam:
+            beta_t[0], beta_t[1] = bt[0], bt[1]
+        return np.array(loss, dtype=np.float32)
 
     def set_physics(self, physics):
         _lib.check(self._L.colnde_ensemble_set_physics(self._h, _ptr(_f32(np.asarray(physics)))))

@@ -512,6 +512,24 @@ int colnde_ensemble_column_loss_dev(colnde_handle* h, const float* d_sol, float*
  * train_free_convection_nde.jl:193; c_k = 1 is the reference's penalty, 0 leaves row k's bits alone.
  * d_result: the buffer of colnde_ensemble_loss_grad_dev, updated in place. */
 int colnde_ensemble_causal_penalty_dev(colnde_handle* h, const float* d_weights, const float* d_coeff /* [K] */, float* d_result);
+/* T -> wT pre-training of all K networks of a free-convection ensemble in ONE launch: one pass of `Flux.train!(loss, ps, data, opt)` per model —
+ * free_convection/train_free_convection_nde.jl:182-216, one optimiser update per sample in the order given, loss = mse([bottom; NN(T); top], wT)
+ * + c_k sum(abs2, W1[mask]) (--spatial_causality soft, :186-197; mask r < q as colnde_ensemble_causal_penalty_dev).  One workgroup per model
+ * (blockIdx.x = model); model k reads and writes only row k of d_theta / d_m / d_v ([K][n_params], the ensemble's layout) and reads row k of d_order,
+ * d_eta and d_coeff; the samples d_T [n][Nz], d_bcs [n][2] = bottom, top and d_flux [n][Nz+1] (scaled) are shared.
+ * Handles: colnde_create_fc_ensemble (the plain network) and colnde_create_conv_ensemble (theta = [w (c); b; vec(W1) 4Nz x (Nz-c+1); b1; ...]; K = 1 is
+ * the single --conv run), any K >= 1 — the same handle then trains the NDE.
+ * optimiser 0 = Flux ADAM (d_m, d_v, beta_t as colnde_pretrain_flux_dev), 1 = Descent: theta -= eta_k g, d_m / d_v not touched (may be NULL), beta_t
+ * not advanced.  d_order NULL: 0..n-1 for every model; an index may repeat.  d_coeff NULL: no penalty.
+ * update = 0: nothing on the device is written and mean_loss[k] = the mean loss at the given weights, the penalty included (the driver's nn_callback);
+ * update != 0: mean_loss[k] = the mean of each sample's loss just before its own update; beta_t advances by n_samples steps (ADAM).  mean_loss: HOST, [K].
+ * A plain ensemble under ADAM with c_k = 0: row k of d_theta, d_m, d_v and mean_loss[k] hold the bits colnde_pretrain_flux_dev computes on a
+ * colnde_create handle for model k's weights with gradient_scaling = 0 and the same order (the two kernels share one per-sample body).
+ * Refused before any launch, each with its reason and this call's name: a null handle or null pointers, a wind-mixing ensemble, single-model and closure
+ * handles, an optimiser outside {0, 1}, ADAM with update but without moments, beta_t >= 1 under ADAM, n_samples < 1.  Synchronises the handle's stream. */
+int colnde_ensemble_pretrain_flux_dev(colnde_handle* h, float* d_theta, float* d_m, float* d_v, const float* d_T, const float* d_bcs, const float* d_flux,
+                                      const int32_t* d_order, int n_samples, const float* d_coeff, int optimiser, const float* d_eta, float beta1,
+                                      float beta2, float eps, double beta_t[2], int update, float* mean_loss);
 
 /* All K models of an ensemble in the embedding ocean column at once — one iteration of progress_neural_network (wind_mixing/src/NDE_oceananigans.jl:380-405) and / or
  * the saved-state diagnoses diagnose_NN_flux_uw / _vw / _wT (:226-286) for every model, each on its OWN column state with its own weights and its own constants: how

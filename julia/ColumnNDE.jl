@@ -585,6 +585,21 @@ gradient += 2 cₖ W1ₖ[mask]; dcoeff one coefficient per model (1: the referen
 ensemble_causal_penalty_dev!(h::Handle, dθ::Ptr{Float32}, dcoeff::Ptr{Float32}, dresult::Ptr{Float32}) =
     check(ccall((:colnde_ensemble_causal_penalty_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, dcoeff, dresult))
 
+"one `Flux.train!(loss, ps, data, opt)` pass of the T → wT pre-training (train_free_convection_nde.jl:182-216) for all K networks of a free-convection
+ensemble (plain or conv) in one launch: dθ, dm, dv K × n_params (row k = model k), dT, dbcs, dflux the n shared samples, dorder K × n (C_NULL: 1:n for
+every model), dcoeff K penalty coefficients (C_NULL: none), optimiser 0 = ADAM | 1 = Descent (dm, dv may be C_NULL, βᵗ stays), dη K rates.
+Returns (the K mean losses, βᵗ); update = false evaluates the loss over the data at fixed weights (`nn_callback`)."
+function ensemble_pretrain_flux!(h::Handle, n_models, dθ::Ptr{Float32}, dm::Ptr{Float32}, dv::Ptr{Float32}, dT::Ptr{Float32}, dbcs::Ptr{Float32},
+                                 dflux::Ptr{Float32}, dorder::Ptr{Int32}, n, dcoeff::Ptr{Float32}, optimiser, dη::Ptr{Float32}, β, ϵ,
+                                 βᵗ::Vector{Float64}; update=true)
+    loss = zeros(Float32, n_models)
+    check(ccall((:colnde_ensemble_pretrain_flux_dev, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Cint, Ptr{Float32}, Cint,
+         Ptr{Float32}, Cfloat, Cfloat, Cfloat, Ptr{Float64}, Cint, Ptr{Float32}),
+        h.ptr, dθ, dm, dv, dT, dbcs, dflux, dorder, n, dcoeff, optimiser, dη, β[1], β[2], ϵ, βᵗ, update ? 1 : 0, loss))
+    loss, βᵗ
+end
+
 # ---- the closure without networks: fitting (ν₀, ν₋, ΔRi, Riᶜ, Pr) — wind_mixing/src/diffusivity_parameter_optimisation.jl (DE :1-33,
 # optimise_modified_pacanowski_philander :35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl and ..._args.jl)
 
