@@ -34,6 +34,14 @@
 #define RT_TAPEZ (20 * 256)   // floats per (tile, step, stage) of the layer-1 pre-activation tape: the forward kernel's 10 tiles x 2 lane pairs x 64 lanes x 4
 #define RT_TAPE2 (20 * 256)   // ... of the layer-1 delta tape: 20 groups x 64 lanes x 4, the three nets' 25 registers stacked (G = 25 n + g)
 
+// Row stacking of layer 1 in the 16-column forward kernels (and so of the Z1 tape record): ten 16-row tiles, stacked quad Q = 4 t + e is element e of tile t and
+// carries features 4 qq + g of one net.  A net has 13 quads (52 rows, 2 of them padding).  Its twelve full quads fill three whole tiles, Q = 12 n + qq (tiles
+// 3n .. 3n+2); tile 9 takes the three half-empty quads qq = 12 (features 48, 49), net n in element n, and one slot of padding (Q = 39).  So every 16-byte group
+// of the record but tile 9's belongs to ONE net, and the adjoint fetches no element it does not keep.  The one place that knows the map:
+__host__ __device__ constexpr int rt16_q_net(int Q) { return Q < 36 ? Q / 12 : Q - 36; }          // Q = 39: padding (callers test Q < 39)
+__host__ __device__ constexpr int rt16_q_quad(int Q) { return Q < 36 ? Q % 12 : 12; }
+__host__ __device__ constexpr int rt16_q_slot(int n, int qq) { return qq < 12 ? 12 * n + qq : 36 + n; }
+
 // The three MLPs on the stage input X (3 tiles u, v, T) -> face-flux tiles O (3 tiles), all in registers.
 // The activations of a finished tile are issued as "filler" inside the next chain's chunks (MFMA shadow).
 template <int ACT>
@@ -191,7 +199,7 @@ __global__ void rt_pack_kernel(DevModel m, const float* __restrict__ w, float* _
 
 // The forward nets as A operands of v_mfma_f32_16x16x32_bf16 (COLNDE_MATRIX_BF16X3_EXACT), made from the fp32 image: group G, plane p, lane (i = lane & 15,
 // kg = lane >> 4), element e = the weight that multiplies the B element e of lane (column, kg) — see rt16_forward_kernel<ACT, true>:
-//   layer 1, G = 3 t + q            : row of quad Q = 4 t + (i & 3), feature 4 (Q % 13) + (i >> 2) of net Q / 13; input 32 q + level(kg, e),
+//   layer 1, G = 3 t + q            : row of quad Q = 4 t + (i & 3), feature 4 rt16_q_quad(Q) + (i >> 2) of net rt16_q_net(Q); input 32 q + level(kg, e),
 //                                     level = e < 4 ? 4 kg + e : 16 + 4 kg + (e - 4)          (the two D tiles of a 32-level variable)
 //   layer 2, G = 30 + 4 n + 2 u + c : output 4 (4 u + (i & 3)) + (i >> 2) (< 20) of net n; input feature 4 (8 c + e) + kg (< 50)
 //   layer 3, G = 42 + 2 n + v       : face 16 v + i (>= 1) of net n; input feature 4 e + kg (e < 5)
@@ -206,9 +214,9 @@ __global__ void rt_pack_split_kernel(const float* __restrict__ img, unsigned* __
             const int e = 2 * pr + z;
             float w = 0.0f;
             if (G < 30) {
-                const int t = G / 3, q = G - 3 * t, Q = 4 * t + r_i, f = 4 * (Q % 13) + g_i;
+                const int t = G / 3, q = G - 3 * t, Q = 4 * t + r_i, f = 4 * rt16_q_quad(Q) + g_i;
                 const int lev = e < 4 ? 4 * kg + e : 16 + 4 * kg + (e - 4);
-                if (Q < 39 && f < 50) w = img[RT_W1C + ((Q / 13) * 50 + f) * RT_LD1 + 32 * q + lev];
+                if (Q < 39 && f < 50) w = img[RT_W1C + (rt16_q_net(Q) * 50 + f) * RT_LD1 + 32 * q + lev];
             } else if (G < 42) {
                 const int y = G - 30, n = y >> 2, u = (y >> 1) & 1, c = y & 1;
                 const int Q2 = 4 * u + r_i, qq = 8 * c + e, f = 4 * qq + kg;
@@ -574,28 +582,26 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
     inject(0, false);
 
     // taped layer-1 pre-activations of net n at (step, stage): registers G' < 25 of Z (padding registers untouched).  The record is the forward kernel's
-    // ten layer-1 tiles as they left its accumulators: group (t, c), lane, element e = stacked quad Q = 4 t + e (net Q / 13, qq = Q % 13), feature 4 qq + h + 2 c,
-    // i.e. register G' = 2 qq + c of this lane.  Net n's 13 quads lie in four tiles; a tile shared with a neighbouring net is fetched by both (its other
-    // elements are dropped here, not kept: the registers do not exist).  Eight 16-byte loads, each one contiguous KiB per wave; every index is compile-time.
+    // ten layer-1 tiles as they left its accumulators: group (t, c), lane, element e = stacked quad Q = 4 t + e (rt16_q_net / rt16_q_quad), feature 4 qq + h + 2 c,
+    // i.e. register G' = 2 qq + c of this lane.  Net n's twelve full quads are the whole tiles 3n .. 3n+2: six 16-byte loads, each one contiguous KiB per wave,
+    // every element kept.  Its quad 12 (register 24) is element n of tile 9's first group: a 4-byte load.  No load has a destination register that nobody reads —
+    // such registers are handed to the next instructions, which then have to wait for the load to land before they may write them (the earlier record, 13 quads
+    // per net stacked back to back, put two nets into tiles 3 and 6: every net's request was waited for within a few instructions).  Every index is compile-time.
     auto load_z1 = [&](int step, int st, int n, f32x16 (&Z)[2]) {
         const float* srcz = tpz + ((size_t)step * 4 + st) * RT_TAPEZ;
 #pragma unroll
-        for (int t = (13 * n) >> 2; t <= (13 * n + 12) >> 2; t++)
+        for (int t = 3 * n; t < 3 * n + 3; t++)
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                // net 0 keeps one element of tile 3's first record (quad 12, register 24): a 4-byte load.  As a 16-byte load its three dropped
-                // registers are handed to the next instructions, which then have to wait for the load to land before they may write them.
-                if (n == 0 && t == 3) {
-                    if (c == 0) Z[1][8] = __builtin_nontemporal_load(srcz + (2 * t + c) * 256);
-                    continue;
-                }
+                static_assert(rt16_q_slot(1, 0) == 12 && rt16_q_slot(2, 11) == 35 && rt16_q_slot(2, 12) == 38, "load_z1 addresses the record by this map");
                 const f32x4v v = RT_TAPE_LOAD4(srcz + (2 * t + c) * 256);
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    const int G = 2 * (4 * t + e - 13 * n) + c;
-                    if ((4 * t + e) / 13 == n && G < 25) Z[G >> 4][G & 15] = v[e];
+                    const int G = 2 * (rt16_q_quad(4 * t + e)) + c;
+                    Z[G >> 4][G & 15] = v[e];
                 }
             }
+        Z[1][8] = __builtin_nontemporal_load(srcz + (rt16_q_slot(n, 12) >> 2) * 2 * 256 + (rt16_q_slot(n, 12) & 3));
     };
 
     // stage input (taped by the forward kernel)
@@ -650,6 +656,15 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
                 RT_STAMP(0);
                 float* dst = tp2 + ((size_t)step * 4 + st) * RT_TAPE2;
                 float carry[2] = {0.0f, 0.0f};
+                // diagnostic build only: stamps at the first use of net n + 1's record inside net n's W1^T products — the work since stamp 5, then what is left of the
+                // latency of the record's loads behind it (dW2 and the W2^T chains, before stamp 5, cover it too)
+                auto z1_stamp = [&](int n) {
+#ifdef COLNDE_STAMPS
+                    RT_STAMP(9 + 2 * n);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    RT_STAMP(10 + 2 * n);
+#endif
+                };
                 // the nets are handled one after the other so that only one net's hidden state is live at a time
 #pragma unroll
                 for (int n = 0; n < 3; n++) {
@@ -806,6 +821,11 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
                     if constexpr (!SPLIT) store_delta();       // (SPLIT: behind the W1^T products — vmcnt is in order, and the l-plane loads must not queue behind these stores)
                     RT_STAMP(5);
                     // (6) x̄ += W1_n^T dZ1_n
+                    // Net n + 1's activation pairs below are pure arithmetic on the record's registers: left alone, the first instruction of a pair (a v_med3_f32) is
+                    // lifted out of the products, past the W2^T chains and into dW2 (fp32 mish: 10 MFMAs behind the request), and the wait for the record comes with it.
+                    // Nothing crosses this barrier, so the first wait stays behind dW2 and the W2^T chains.  (Tying the 25 registers to an asm at the first pair, as for
+                    // net 0, makes the allocator copy them out of the loads' tuples at the request: a wait one instruction behind it.)
+                    if (ZT && n < 2) __builtin_amdgcn_sched_barrier(0);
                     if constexpr (SPLIT) {
                         const u32x4* hm = reinterpret_cast<const u32x4*>(rt_smem) + lane;
 #pragma unroll
@@ -824,6 +844,7 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
                                 const u32x4 Ah = hm[(G * 2) * 64], Am = hm[(G * 2 + 1) * 64];
                                 // net n + 1's 25 activation pairs, spread over slots 2 .. 8 (as in the fp32 chain: not under the first chunks)
                                 if (ZT && n < 2 && slot >= 2) {
+                                    if (slot == 2) z1_stamp(n);
                                     if (slot < 8) rt_act_pair4_at<ACT>(A1n, D1n, 4 * (slot - 2));
                                     else rt_act_pair_at<ACT>(A1n, D1n, 24);
                                 }
@@ -850,6 +871,7 @@ rt_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __res
                                                      [&](int c) {
                                                          // net n + 1's 25 activation pairs, spread over the 15 chunks
                                                          if (ZT && n < 2 && (q > 0 || c > 0)) {
+                                                             if (q * 5 + c == 2) z1_stamp(n);
 #pragma unroll
                                                              for (int G = 0; G < 24; G += 4)
                                                                  if ((G >> 2) * 2 + 2 == q * 5 + c)
@@ -1142,15 +1164,17 @@ rt_dw1_split_kernel(DevModel m, const float* __restrict__ tape, const float* __r
 // one wave's activations / physics / RK update hide under the other's MFMA chains.  The stage tape is written in the
 // 32-column register-image format the adjoint and dW1 kernels read (two 16-column waves make one 32-column tile).
 //
-// Row placement: layer-1 outputs stacked into 10 tiles; quad Q = 4 t + r (rows 16t + 4g + r) carries features 4 (Q%13) + g
-// of net Q / 13 (13 quads = 52 rows per net, 2 of them padding); layer-2 outputs: quad Q2 = 4u + r carries features
+// Row placement: layer-1 outputs stacked into 10 tiles; quad Q = 4 t + r (rows 16t + 4g + r) carries features 4 rt16_q_quad(Q) + g
+// of net rt16_q_net(Q) (13 quads = 52 rows per net, 2 of them padding; a net's twelve full quads are three whole tiles, the three
+// quads 12 share tile 9 — see rt16_q_slot); layer-2 outputs: quad Q2 = 4u + r carries features
 // 4 Q2 + g (Q2 < 5); layer-3 output row = face index.
 // ------------------------------------------------------------------------------------------------
 // Z1 tape of the 16-column forward kernels: layer-1 tile tt leaves as it sits in the accumulators, one 16-byte store per lane (a wave instruction writes four
 // complete 256-byte runs, no address or mask arithmetic).  Record of one (32-column tile, step, stage): [t = 0..9][c = 0..1][64 lanes][4]; group (t, c), lane
-// j + 16 half + 32 h, element e = the pre-activation of stacked quad Q = 4 t + e (net Q / 13, qq = Q % 13), feature 4 qq + g with g = h + 2 c, column j + 16 half:
-// A1[t] of forward lane (j, g).  The adjoint's loads do the renaming into its per-net registers (load_z1).  Slot Q = 39 and the qq = 12, g >= 2 slots hold what the
-// padding rows produce (finite, never read).  (The earlier record in the adjoint's per-net register-image format took 39 dword stores per lane and stage, each wave
+// j + 16 half + 32 h, element e = the pre-activation of stacked quad Q = 4 t + e (net n = rt16_q_net(Q), qq = rt16_q_quad(Q)), feature 4 qq + g with g = h + 2 c,
+// column j + 16 half: A1[t] of forward lane (j, g).  Groups (3n .. 3n+2, c) are net n's quads 0 .. 11 and nothing else; group (9, 0) holds the three nets' quad 12
+// (features 48, 49) in elements 0, 1, 2.  The adjoint's loads do the renaming into its per-net registers (load_z1).  Slot Q = 39 and the qq = 12, g >= 2 slots (all of
+// group (9, 1)) hold what the padding rows produce (finite, never read).  (The earlier record in the adjoint's per-net register-image format took 39 dword stores per lane and stage, each wave
 // store filling 8 of every 16 bytes; assembling that format's 16-byte groups with v_permlane32_swap was measured slower still: forward 28.0 -> 31.7 ms, round 5.)
 template <int ACT, bool SPLIT = false>
 __global__ void __launch_bounds__(512)
@@ -1185,8 +1209,8 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
     int a1b[10];
 #pragma unroll
     for (int t = 0; t < 10; t++) {
-        const int Q = 4 * t + r_i, f = 4 * (Q % 13) + g_i;
-        const int row = (Q < 39 && f < 50) ? (Q / 13) * 50 + f : 0;       // padding rows read a valid row; never consumed
+        const int Q = 4 * t + r_i, f = 4 * rt16_q_quad(Q) + g_i;
+        const int row = (Q < 39 && f < 50) ? rt16_q_net(Q) * 50 + f : 0;       // padding rows read a valid row; never consumed
         a1b[t] = RT_W1C + row * RT_LD1 + 4 * g;
     }
     int a2b[2], a2l[2], a3b[2];
@@ -1267,7 +1291,7 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
                             const int Q = 4 * t + r;
-                            A1[t][r] = Q < 39 ? bl[RT_B1C + (Q / 13) * 50 + min(4 * (Q % 13) + g, 49)] : 0.0f;
+                            A1[t][r] = Q < 39 ? bl[RT_B1C + rt16_q_net(Q) * 50 + min(4 * rt16_q_quad(Q) + g, 49)] : 0.0f;
                         }
                     Bf3 Apf = rt16_ldA(simg, 0, lz);
 #pragma unroll
@@ -1328,7 +1352,7 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         const int Q = 4 * t + r;
-                        acc[r] = Q < 39 ? wl[RT_B1C + (Q / 13) * 50 + min(4 * (Q % 13) + g, 49)] : 0.0f;
+                        acc[r] = Q < 39 ? wl[RT_B1C + rt16_q_net(Q) * 50 + min(4 * rt16_q_quad(Q) + g, 49)] : 0.0f;
                     }
                     const int base = a1b[t];
                     // (tile t - 1's tape store and activation issued between tile t's MFMAs instead: 35.4 ms against 34.0-34.9 — two waves per SIMD already overlap what can be overlapped)
@@ -1350,7 +1374,7 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                         for (int c = 0; c < 2; c++) {
                             float a8[8];
 #pragma unroll
-                            for (int e = 0; e < 8; e++) a8[e] = 8 * c + e < 13 ? A1[(13 * n + 8 * c + e) >> 2][(13 * n + 8 * c + e) & 3] : 0.0f;
+                            for (int e = 0; e < 8; e++) a8[e] = 8 * c + e < 13 ? A1[rt16_q_slot(n, 8 * c + e) >> 2][rt16_q_slot(n, 8 * c + e) & 3] : 0.0f;
                             HB[c] = bf3_split8(a8);
                         }
                     }
@@ -1369,7 +1393,7 @@ rt16_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __r
                         } else {
                         const int base = a2b[u] + n * 20 * RT_LD2, basel = a2l[u] + n * 20 * RT_LD2;
                         acc = rt16_chain<13, 13>(wl, acc, [=](int k) { return k < 12 ? base + 4 * k : basel; },
-                                                 [&](int k) { return A1[(13 * n + k) >> 2][(13 * n + k) & 3]; });
+                                                 [&](int k) { return A1[rt16_q_slot(n, k) >> 2][rt16_q_slot(n, k) & 3]; });
                         }
                         // (SPLIT: the four values of tile 0 on scalar f32, as layer 1; tile 1 has ONE live value, which the compiler evaluates on scalar instructions from
                         //  either form — its packed source form is kept, because there the split below contracts its residual onto the last product, and the bits hang on it)

@@ -15,11 +15,11 @@ typedef float f32x2v __attribute__((ext_vector_type(2)));
 // header has its own (device symbols cannot be shared between units without relocatable device code), read back by rt_read_unit_stamps below.
 #ifdef COLNDE_STAMPS
 static __device__ unsigned long long g_rt_stamps[16];
-#define RT_STAMP_DECL unsigned long long rs_t0 = 0, rs_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long rs_kk = __builtin_amdgcn_s_memtime(), rs_rr = __builtin_amdgcn_s_memrealtime()
+#define RT_STAMP_DECL unsigned long long rs_t0 = 0, rs_acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long rs_kk = __builtin_amdgcn_s_memtime(), rs_rr = __builtin_amdgcn_s_memrealtime()
 #define RT_STAMP_BEGIN() do { __builtin_amdgcn_sched_barrier(0); rs_t0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define RT_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); rs_acc[i] += t_ - rs_t0; rs_t0 = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-// slots 8, 9: the whole kernel in shader ticks and in 100 MHz reference ticks (their ratio is the clock the kernel ran at); slot 10: phase stamp 8
-#define RT_STAMP_FLUSH() do { if (blockIdx.x == 0 && threadIdx.x == 0) { for (int q_ = 0; q_ < 8; q_++) g_rt_stamps[q_] = rs_acc[q_]; g_rt_stamps[8] = __builtin_amdgcn_s_memtime() - rs_kk; g_rt_stamps[9] = __builtin_amdgcn_s_memrealtime() - rs_rr; g_rt_stamps[10] = rs_acc[8]; } } while (0)
+// slots 8, 9: the whole kernel in shader ticks and in 100 MHz reference ticks (their ratio is the clock the kernel ran at); slot 10: phase stamp 8; slots 11 .. 14: phase stamps 9 .. 12
+#define RT_STAMP_FLUSH() do { if (blockIdx.x == 0 && threadIdx.x == 0) { for (int q_ = 0; q_ < 8; q_++) g_rt_stamps[q_] = rs_acc[q_]; g_rt_stamps[8] = __builtin_amdgcn_s_memtime() - rs_kk; g_rt_stamps[9] = __builtin_amdgcn_s_memrealtime() - rs_rr; g_rt_stamps[10] = rs_acc[8]; for (int q_ = 9; q_ < 13; q_++) g_rt_stamps[q_ + 2] = rs_acc[q_]; } } while (0)
 static inline hipError_t rt_read_unit_stamps(unsigned long long* out16) { return hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_rt_stamps), sizeof(unsigned long long) * 16); }
 #else
 #define RT_STAMP_DECL

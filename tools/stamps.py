@@ -57,6 +57,12 @@ nstage = p.cfg.n_steps * 4
 for n, x in zip(names, v):
     print("%-28s %10.0f cycles/stage  %5.1f %%" % (n, x / nstage, 100 * x / v.sum()))
 print("total %.0f cycles/stage" % (v.sum() / nstage))
+if nde.engine == 2 and not FWD and any(buf[11:15]):
+    # stamps 9 .. 12 sit at the first use of the next net's Z1 record, inside a net's W1^T products (slot 2): the products issued since stamp 5, then the
+    # forced wait for what is left of the record's round trip.  In this build they take their cycles out of the rows "W1^T chains" above.
+    for k, n in enumerate(["net 0: W1^T products before net 1's Z1 record is used", "rest of the wait for net 1's Z1 record",
+                           "net 1: W1^T products before net 2's Z1 record is used", "rest of the wait for net 2's Z1 record"]):
+        print("  %-56s %8.0f cycles/stage" % (n, buf[11 + k] / nstage))
 if FWD and not SPLIT:
     print("whole kernel (workgroup 0, wave 0): %d s_memtime ticks in %.3f ms (s_memrealtime, 100 MHz) -> %.3f ticks/ns; stage loop share %.1f %%"
           % (buf[6], buf[7] / 1e5, buf[6] / (buf[7] * 10.0), 100.0 * v.sum() / buf[6]))
