@@ -96,6 +96,8 @@ SYMBOLS = [
     ("colnde_create_conv", ctypes.c_int, [_V, ctypes.c_int, ctypes.POINTER(_V)]),
     ("colnde_create_conv_ensemble", ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_V)]),
     ("colnde_conv_filter", ctypes.c_int, [_V]),
+    ("colnde_ensemble_fc_embedded", ctypes.c_int, [_V] * 6 + [ctypes.c_float] * 3 + [_V] * 3 + [ctypes.c_int]),
+    ("colnde_ensemble_fc_embedded_dev", ctypes.c_int, [_V] * 6 + [ctypes.c_float] * 3 + [_V] * 3 + [ctypes.c_int]),
     ("colnde_ensemble_column_loss_dev", ctypes.c_int, [_V, _V, _V]),
     ("colnde_ensemble_causal_penalty_dev", ctypes.c_int, [_V, _V, _V, _V]),
     ("colnde_ensemble_pretrain_flux_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_int, _V, ctypes.c_int, _V] + [ctypes.c_float] * 3 +

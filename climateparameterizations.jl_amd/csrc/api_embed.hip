@@ -512,26 +512,34 @@ extern "C" int colnde_mpp_diagnose_flux(colnde_handle* h, const float* u, const 
 }
 
 // ---- free-convection embedded step (free_convection/src/oceananigans_nn.jl:100-118, :153-165; engine_fc_embed.hip) ----------------------
-// the handles the kernels cover: the network shapes of fc32 (fc_supported), whatever engine and stepper the handle trains with
-bool fce_covers(const colnde_handle* h) {
+// the handles the kernels cover: the network shapes of fc32 (fc_supported), whatever engine and stepper the handle trains with — fce_shape_covers whatever
+// the number of models (colnde_ensemble_fc_embedded), fce_covers the single-model entry points' (colnde_describe reports it)
+static bool fce_shape_covers(const colnde_handle* h);
+bool fce_covers(const colnde_handle* h) { return !h->ensemble && fce_shape_covers(h); }
+static bool fce_shape_covers(const colnde_handle* h) {
     const DevModel& m = h->m;
-    return !h->closure && !h->ensemble && !h->ag_rows && (m.model == COLNDE_MODEL_FREE_CONVECTION || m.model == COLNDE_MODEL_CONV_ADJ_NDE) &&
+    return !h->closure && !h->ag_rows && (m.model == COLNDE_MODEL_FREE_CONVECTION || m.model == COLNDE_MODEL_CONV_ADJ_NDE) &&
            (m.Nz == 32 || m.Nz == 64) && m.n_layers == 3 && m.n_nets == 1 && m.sizes[0] == m.Nz && m.sizes[1] == 4 * m.Nz && m.sizes[2] == 4 * m.Nz &&
            m.sizes[3] == m.Nz - 1 && m.acts[0] == COLNDE_ACT_RELU && m.acts[1] == COLNDE_ACT_RELU && m.acts[2] == COLNDE_ACT_IDENTITY;
 }
-static int fce_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, float K, int n_columns) {
-    if (!h) return fail("null handle");
+// the refusals by kind and shape of the handle (its callers have dealt with ensembles and closure handles), fn named in each
+static int fce_shape_check(const colnde_handle* h, const char* fn) {
     const colnde_config& c = h->cfg;
     if (c.model == COLNDE_MODEL_WIND_MIXING)
         return fail("%s needs a free-convection handle (one network on T); a wind-mixing handle has colnde_wm_embedded_step", fn);
     if (h->ag_rows) return fail("%s: this handle's network keeps its activation rows in global memory (a wide network); the embedded step covers the fc32 shapes only", fn);
     if (c.Nz != 32 && c.Nz != 64) return fail("%s covers Nz = 32 or 64 (this handle has Nz = %d)", fn, c.Nz);
-    if (!fce_covers(h)) {
+    if (!fce_shape_covers(h)) {
         std::string shape;
         for (int l = 0; l <= c.n_layers; l++) shape += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
         return fail("%s covers the fc32 network Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1); this handle has Nz = %d and network %s", fn, c.Nz,
                     shape.c_str());
     }
+    return 0;
+}
+static int fce_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, float K, int n_columns) {
+    if (!h) return fail("null handle");
+    if (fce_shape_check(h, fn)) return 1;
     for (int i = 0; i < n_ptrs; i++)
         if (!ptrs[i]) return fail("null pointer argument");
     if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
@@ -633,4 +641,111 @@ extern "C" int colnde_fc_diagnose_wT(colnde_handle* h, const float* weights, con
     const void* const ptrs[4] = {weights, T, top_flux, wT_faces};
     if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
     return fce_host(h, __func__, weights, T, top_flux, halo_bottom, halo_top, Lz, 0.0f, K, nullptr, nullptr, wT_faces, n_columns);
+}
+
+// ---- the K networks of a free-convection ensemble in the embedding at once (engine_fc_embed.hip: fce_ens_kernel) -------------------
+// A plain fc ensemble, a conv ensemble, or a single fc handle as K = 1, plain or conv.  Everything the call refuses that does not depend on where the
+// arrays live; host: the host twin's arrays (no alignment rule of their own).
+static int fce_ens_check(colnde_handle* h, const char* fn, const float* T, const float* top_flux, float Lz, float dt, float K, const float* dz_wT,
+                         const float* T_out, const float* wT_faces, int n_columns, bool host) {
+    if (!h) return fail("%s: null handle", fn);
+    if (h->closure)
+        return fail("%s takes K weight vectors, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", fn,
+                    h->n_models);
+    if (h->cfg.model == COLNDE_MODEL_WIND_MIXING)
+        return fail("%s needs free-convection networks (one network on T per model); a wind-mixing handle has colnde_ensemble_wm_embedded", fn);
+    if (fce_shape_check(h, fn)) return 1;
+    if (!T || !top_flux) return fail("%s: null pointer argument (T, top_flux)", fn);
+    if ((dz_wT != nullptr) != (T_out != nullptr))
+        return fail("%s: dz_wT and T_out are one output group — both given (the forcing and the adjustment step) or both NULL (no step); one of 2 given", fn);
+    if (!dz_wT && !wT_faces) return fail("%s: nothing to compute — give the step group (dz_wT, T_out), wT_faces, or both", fn);
+    if (n_columns < 1 || !(Lz > 0.0f)) return fail("%s: n_columns >= 1 and Lz > 0 required", fn);
+    if (dz_wT && !(dt > 0.0f)) return fail("%s: dt > 0 required when a step is asked for (dz_wT, T_out given); dt = %g", fn, dt);
+    if (!(K >= 0.0f)) return fail("%s: K_ca >= 0 required; K_ca = %g", fn, K);
+    if (!host) {
+        const void* const ptrs[4] = {T, dz_wT, T_out, wT_faces};
+        for (const void* p : ptrs)
+            if ((uintptr_t)p & 15) return fail("%s: the base pointers of T, dz_wT, T_out and wT_faces must be 16-byte aligned", fn);
+    }
+    return 0;
+}
+
+// first call on a handle: the members' images, biases and filters at tile width 16 (the handle's own training images are left alone) and the LDS limits
+static int fce_ens_prepare(colnde_handle* h) {
+    if (h->fce_ens_ready) return 0;
+    const size_t K = (size_t)h->n_models;
+    if (!h->d_fce_ens_imgf) HIPCHK(h->mem.alloc(&h->d_fce_ens_imgf, K * fc_image_floats(h->m.Nz)));
+    if (!h->d_fce_ens_bias) HIPCHK(h->mem.alloc(&h->d_fce_ens_bias, K * fc_bias_floats(h->m.Nz)));
+    if (h->conv.c && !h->d_fce_ens_taps) HIPCHK(h->mem.alloc(&h->d_fce_ens_taps, K * FCE_TAPS_FLOATS));
+    hipError_t e = fce_set_kernel_attributes();
+    if (e != hipSuccess) return fail("hipFuncSetAttribute (fc_embed) failed: %s", hipGetErrorString(e));
+    h->fce_ens_ready = true;
+    return 0;
+}
+
+// K forward images, bias blocks and (conv) filters from the members' vectors, user_params(h) floats apart; behind a filter the dense part goes through
+// the padded vectors (W1 with zero columns), as in training (fc_pack)
+static int fce_ens_pack(colnde_handle* h, const char* fn, const float* d_weights) {
+    const float* dense = d_weights;
+    FcEns en;
+    en.n_models = h->n_models;
+    en.w = (size_t)h->m.n_params;
+    en.img = fc_image_floats(h->m.Nz);
+    en.bias = fc_bias_floats(h->m.Nz);
+    hipError_t e = hipSuccess;
+    if (h->conv.c) {
+        e = launch_fce_taps(d_weights, (size_t)h->conv.n_params, h->conv.c, h->n_models, h->d_fce_ens_taps, h->stream);
+        if (e == hipSuccess)
+            e = launch_fc_conv_pad(d_weights, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->m.n_params, h->conv.d_wpad, h->stream, h->n_models,
+                                   (size_t)h->conv.n_params);
+        if (e != hipSuccess) return fail("%s: conv filter / weight padding launch failed: %s", fn, hipGetErrorString(e));
+        dense = h->conv.d_wpad;
+    }
+    e = fc_launch_pack(h->m, 16, dense, h->d_fce_ens_imgf, nullptr, h->d_fce_ens_bias, nullptr, nullptr, h->stream, &en);
+    if (e != hipSuccess) return fail("%s: forward-image pack launch failed: %s", fn, hipGetErrorString(e));
+    h->fce_ens_packed = true;
+    return 0;
+}
+
+extern "C" int colnde_ensemble_fc_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
+                                               const float* d_halo_top, float Lz, float dt, float K_ca, float* d_dz_wT, float* d_T_out, float* d_wT_faces,
+                                               int n_columns) {
+    if (fce_ens_check(h, __func__, d_T, d_top_flux, Lz, dt, K_ca, d_dz_wT, d_T_out, d_wT_faces, n_columns, false)) return 1;
+    if (!d_weights && !h->fce_ens_packed)
+        return fail("%s: weights == NULL reuses the operand images of the previous call on this handle, and no call has given weights yet", __func__);
+    HIPCHK(hipSetDevice(h->device));
+    if (fce_ens_prepare(h)) return 1;
+    // One launch at every size, 16-column tiles (profiles/fc_ens_embed_rate.json).  The pack runs outside the timed scope, as in
+    // colnde_fc_embedded_step: slot 9 is the embedded kernel's alone.
+    if (d_weights && fce_ens_pack(h, __func__, d_weights)) return 1;
+    FcEmbedArgs a = {};
+    a.cw = 16;
+    a.imgf = h->d_fce_ens_imgf; a.bias = h->d_fce_ens_bias; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top;
+    a.Lz = Lz; a.dt = dt; a.K = K_ca; a.dz_wT = d_dz_wT; a.T_out = d_T_out; a.wT_faces = d_wT_faces; a.n_col = n_columns; a.step = d_dz_wT != nullptr;
+    Timed tm(h, K_FCEMBED);
+    hipError_t e = launch_fc_embed_ens(h->m, a, h->n_models, h->conv.c, h->d_fce_ens_taps, h->stream);
+    if (e != hipSuccess) return fail("%s launch failed: %s", __func__, hipGetErrorString(e));
+    return 0;
+}
+
+// host arrays: the step in place on the T block it uploaded; top_flux [n] is shared by the members, the halos are [K][n]
+extern "C" int colnde_ensemble_fc_embedded(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
+                                           const float* halo_top, float Lz, float dt, float K_ca, float* dz_wT, float* T_out, float* wT_faces, int n_columns) {
+    if (fce_ens_check(h, __func__, T, top_flux, Lz, dt, K_ca, dz_wT, T_out, wT_faces, n_columns, true)) return 1;
+    if (!weights && !h->fce_ens_packed)
+        return fail("%s: weights == NULL reuses the operand images of the previous call on this handle, and no call has given weights yet", __func__);
+    HIPCHK(hipSetDevice(h->device));
+    const size_t K = (size_t)h->n_models, Nz = (size_t)h->m.Nz, nc = (size_t)n_columns;
+    float *d_T, *d_To, *d_dz, *d_faces, *d_top, *d_hb, *d_ht;
+    HostStage st(h, __func__);
+    if (weights) st.to(h->d_w, weights, K * (size_t)user_params(h));
+    st.inout(&d_T, &d_To, T, T_out, K * nc * Nz);
+    st.out(&d_dz, dz_wT, K * nc * Nz);
+    st.out(&d_faces, wT_faces, K * nc * (Nz + 1));
+    st.in(&d_top, top_flux, nc);
+    st.in(&d_hb, halo_bottom, K * nc);
+    st.in(&d_ht, halo_top, K * nc);
+    if (st.upload()) return 1;
+    if (colnde_ensemble_fc_embedded_dev(h, weights ? h->d_w : nullptr, d_T, d_top, d_hb, d_ht, Lz, dt, K_ca, d_dz, d_To, d_faces, n_columns)) return 1;
+    return st.download();
 }

@@ -194,7 +194,10 @@ struct colnde_handle {
                                                       // f32 MFMA — cfg.matrix_arithmetic with the test overrides COLNDE_{FWD,ADJ,DW}_SPLIT (resolve_arithmetic)
     bool use_fc = false;            // 32-column free-convection engine (engine_fc.hip: Nz = 32 | 64, the reference's relu network, RK4)
     bool fce_ready = false;         // colnde_fc_embedded_step / colnde_fc_diagnose_wT: images allocated, LDS limits raised (first call)
-    float *d_fc_imgf = nullptr, *d_fc_imgb = nullptr, *d_fc_bias = nullptr;
+    // colnde_ensemble_fc_embedded: the members' forward images, biases and filters at tile width 16, kept from one call to the next (weights == NULL
+    // reuses them); allocated and the LDS limits raised on the first call, fce_ens_packed once a call has given weights
+    bool fce_ens_ready = false, fce_ens_packed = false;
+    float *d_fce_ens_imgf = nullptr, *d_fce_ens_bias = nullptr, *d_fce_ens_taps = nullptr;    float *d_fc_imgf = nullptr, *d_fc_imgb = nullptr, *d_fc_bias = nullptr;
     unsigned int *d_fc_simgf = nullptr, *d_fc_simgb = nullptr;   // the split operand images (COLNDE_MATRIX_BF16X3_EXACT; 32-column tiles)
     unsigned int* d_fc_masks = nullptr;
     unsigned long long* d_fc_switch = nullptr;   // ConvectiveAdjustmentNDE: the taped switch patterns

@@ -45,7 +45,8 @@ static inline size_t fc_conv_tape_floats(int Nz) { return (size_t)16 * 2 * Nz; }
 struct FcConvEns {
     size_t wb = 0, ctape = 0;
 };
-// ens != null (cw = 16, both image kinds given): the images of all ens->n_models models, weights ens->w floats apart
+// ens != null (cw = 16, both image kinds given): the images of all ens->n_models models, weights ens->w floats apart.  With imgb, simgf and simgb all
+// null it is a forward-only pack: the f32 forward images and the biases (the embedded step's operands, engine_fc_embed.hip)
 hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf, float* imgb, float* bias, unsigned int* simgf, unsigned int* simgb,
                           hipStream_t stream, const FcEns* ens = nullptr);
 // Save intervals [iv_begin, iv_end) from x0 (column stride x0_stride floats).  dwtape == nullptr: plain forward solve.  Otherwise, from interval

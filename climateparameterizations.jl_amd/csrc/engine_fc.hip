@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(256) fc_pack_kernel(FcOffsets o, const float* 
         const size_t k = blockIdx.y;
         w += k * en.w;
         imgf += k * en.img;
-        imgb += k * en.img;
+        if (imgb) imgb += k * en.img;
         bias += k * en.bias;
     }
     const int total = 2 * S::IMG + S::BIAS;
@@ -184,6 +184,7 @@ __global__ void __launch_bounds__(256) fc_pack_kernel(FcOffsets o, const float* 
             continue;
         }
         const bool fwd = idx < S::IMG;
+        if (!fwd && !imgb) continue;                          // a forward-only pack (the embedding's ensemble images)
         const int e = fwd ? idx : idx - S::IMG;
         const int sec = e < S::F2 ? 0 : (e < S::F3 ? 1 : 2);
         const int r = e - (sec == 0 ? S::F1 : (sec == 1 ? S::F2 : S::F3));
@@ -277,15 +278,7 @@ typedef unsigned long long u64;
 //        (fc_forward_body.inc) behind two entry points: fc_forward_kernel (name and arguments as they were; CONV = false) and fc_forward_conv_kernel, which
 //        adds the FcConv argument.  A template flag on fc_forward_kernel itself would rename every existing instantiation and lengthen its argument block.
 //        ENS and CONV together (a conv ensemble) is a third entry point for the same reason: fc_forward_conv_ens_kernel, below.
-// the filter's pre-activation for this lane's level from the column's levels in the lanes above (d = 0: the lane's own): ONE instruction sequence for the
-// forward kernel and for the adjoint's recomputation, so that both see the same bits and the same sign
-__device__ __forceinline__ float fc_conv_pre(float x, const float (&cw)[FC_CONV_MAX], float cb, int c) {
-    float pre = cb;
-#pragma unroll
-    for (int d = 0; d < FC_CONV_MAX; d++)
-        if (d < c) pre = fmaf(cw[d], __shfl_down(x, d), pre);                   // taps in a fixed order: w[c], w[c-1], ..., w[1]
-    return pre;
-}
+// (the filter's pre-activation, fc_conv_pre: fc_chain.h — the embedded step applies the same filter)
 // cw[d] = w[c - d] (1-based: the tap that multiplies x[i + d]), zero beyond the filter; cb = b
 __device__ __forceinline__ void fc_conv_load(const FcConv& cv, float (&cw)[FC_CONV_MAX], float& cb) {
 #pragma unroll
@@ -532,13 +525,15 @@ hipError_t fc_launch_pack(const DevModel& m, int cw, const float* w, float* imgf
     FcOffsets o;
     for (int l = 0; l < 3; l++) { o.w[l] = m.w_off[l]; o.b[l] = m.b_off[l]; }
     if (ens) {                                             // every model's images in one launch each (16-column tiles only)
-        if (cw != 16 || ens->n_models < 1 || ens->n_models > 65535 || !simgf || !simgb) return hipErrorInvalidValue;
+        // forward-only (imgb and both split images null): the f32 forward images and biases alone — what the embedded step reads
+        const bool fwd_only = !imgb && !simgf && !simgb;
+        if (cw != 16 || ens->n_models < 1 || ens->n_models > 65535 || !imgf || !bias || (!fwd_only && (!imgb || !simgf || !simgb))) return hipErrorInvalidValue;
         const unsigned K = (unsigned)ens->n_models;
         if (m.Nz == 64) {
-            hipLaunchKernelGGL((fc_pack_split16_kernel<64, true>), dim3(256, K), dim3(256), 0, stream, o, w, simgf, simgb, *ens);
+            if (!fwd_only) hipLaunchKernelGGL((fc_pack_split16_kernel<64, true>), dim3(256, K), dim3(256), 0, stream, o, w, simgf, simgb, *ens);
             hipLaunchKernelGGL((fc_pack_kernel<64, 16, true>), dim3(256, K), dim3(256), 0, stream, o, w, imgf, imgb, bias, *ens);
         } else {
-            hipLaunchKernelGGL((fc_pack_split16_kernel<32, true>), dim3(128, K), dim3(256), 0, stream, o, w, simgf, simgb, *ens);
+            if (!fwd_only) hipLaunchKernelGGL((fc_pack_split16_kernel<32, true>), dim3(128, K), dim3(256), 0, stream, o, w, simgf, simgb, *ens);
             hipLaunchKernelGGL((fc_pack_kernel<32, 16, true>), dim3(128, K), dim3(256), 0, stream, o, w, imgf, imgb, bias, *ens);
         }
         return hipGetLastError();

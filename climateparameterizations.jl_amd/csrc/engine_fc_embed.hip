@@ -19,6 +19,8 @@
 // LDS: fc_infer_kernel's carve + the two halo cells per column (256 B at most): 76 KB per workgroup at Nz = 64 on 32 columns, two fit a CU's 160 KB.
 // Which launches the C entry points issue was decided by measurement (profiles/fc_embed_rate.json): the diagnosis-only and the
 // three-output kernels always; forcing + adjustment alone runs as the two existing launches unless COLNDE_FC_EMBED_FUSED=1 (api_embed.hip).
+// A second family, fce_ens_kernel<NZ, STEP, DIAG, CONV>, runs the K members of an ensemble in one launch (colnde_ensemble_fc_embedded):
+// 16-column tiles, the model in blockIdx.y, the same per-tile text (fc_embed_body.inc), and — CONV — the --conv filter where the scaled rows go to LDS.
 #include <algorithm>
 #include "engine_fc_embed.h"
 #include "engine_fc.h"
@@ -37,115 +39,46 @@ fce_kernel(const float* __restrict__ imgf, const float* __restrict__ bias, const
            const float* __restrict__ halo_bottom, const float* __restrict__ halo_top, float mu_T, float inv_sig_T, float sig_wT, float mu_wT,
            float inv_dz_out /* −Nz/Lz: fc_infer_kernel's argument for +∂z wT */, float inv_dz, float c, float K, float* __restrict__ dz_wT, float* T_out,
            float* __restrict__ faces, int n_col) {
-    static_assert(STEP || DIAG, "nothing to do");
-    using S = Fc<NZ, CW>;
-    constexpr int LDT = NZ + 1;                                  // raw rows: odd stride, conflict-free per-lane column walks (as convadj_kernel)
-    static_assert(2 * CW * LDT <= CW * S::LDH, "the raw and the adjusted rows live in A2's rows");
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & (CW - 1), h = lane / CW;               // column of the tile; k / row quad
-    float* X = fce_smem;
-    float* A1 = X + CW * S::LDX;
-    float* A2 = A1 + CW * S::LDH;
-    float* PART = A1;
-    float* BL = A2 + CW * S::LDH;
-    float* HB = BL + S::BIAS;                                    // [CW] halo cell below k = 0 (absent: T[0])
-    float* HT = HB + CW;                                         // [CW] halo cell above k = NZ - 1 (absent: T[NZ-1])
-    float* TR = A2;                                              // [CW][LDT] T as given
-    float* TS = A2 + CW * LDT;                                   // [CW][LDT] a second copy, solved in place: T′
-    for (int q = tid; q < S::BIAS; q += 256) BL[q] = bias[q];
-    FC_OWNER_INDEX();
-    const f32x4* base[3];
-    base[0] = reinterpret_cast<const f32x4*>(imgf + S::F1) + (w * S::S_IN) * 64;
-    base[1] = reinterpret_cast<const f32x4*>(imgf + S::F2) + (w * S::S_H) * 64;
-    base[2] = reinterpret_cast<const f32x4*>(imgf + S::F3) + ((w % S::MT3) * S::S_H + (w / S::MT3) * S::G3) * 64;
-    // The A-operand ring streams from one tile to the next, as in fc_infer_kernel — except (Nz = 64, 16 columns, with the sweep): the sweep's 3 x 64
-    // live floats and the ring's 32 registers do not fit 256 registers together (36 bytes of scratch), so there the ring is refilled after the sweep
-    // of every tile (what the last groups of the previous tile prefetched is dropped: the L2 latency shows once per tile, under the other workgroup).
-    constexpr bool REFILL = STEP && NZ == 64 && CW == 16;
-    f32x4 ring[FC_PF];
-    if constexpr (!REFILL) {
-#pragma unroll
-        for (int q = 0; q < FC_PF; q++) ring[q] = (base[fc_sec<NZ, CW>(q)] + fc_off<NZ, CW>(q))[lane];
-    }
-    const float b3v = oi < S::NO ? bias[2 * S::H + oi] : 0.0f;
-    asm volatile("" :: "v"(b3v));
-    const int n_tiles = (n_col + CW - 1) / CW;
-#pragma nounroll
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        int zero = 0;
-        FC_OPAQUE_ZERO(zero);
-        const f32x4* const sb[3] = {base[0] + zero, base[1] + zero, base[2] + zero};
-        const int col0 = tile * CW;
-        // ---- the tile's T: scaled rows (layer 1's B operand), raw rows, halo cells.  A partial tile repeats its last column.
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) {
-            const int col = min(col0 + oc[r], n_col - 1);
-            const float t = T[(size_t)col * NZ + oi];
-            X[oc[r] * S::LDX + oi] = fc_infer_scale(t, mu_T, inv_sig_T);
-            TR[oc[r] * LDT + oi] = t;
-            if constexpr (STEP) TS[oc[r] * LDT + oi] = t;
-            if (oi == 0) HB[oc[r]] = halo_bottom ? halo_bottom[col] : t;
-            if (oi == NZ - 1) HT[oc[r]] = halo_top ? halo_top[col] : t;
-        }
-        FC_BARRIER();
-        // ---- convective_adjustment! (:13-40): one lane per column, then T′ out in 16-byte pieces before the chains start
+    constexpr bool CONV = false;
+    const float* const conv_taps = nullptr;
+    const int conv_c = 0;
+#include "fc_embed_body.inc"
+}
+
+// The K members of an ensemble in one launch (colnde_ensemble_fc_embedded): 16-column tiles, blockIdx.y = model, as the fc ensembles'
+// kernels (engine_fc.h).  What a member owns — operand image, biases, filter, state, halos, outputs — lies at the strides of `en` from model 0's;
+// the top flux is shared.  The offsets are scalar arithmetic on kernel arguments, once, here; the per-tile text is fce_kernel's.
+// CONV: members with the --conv filter (taps [FC_CONV_MAX + 1] per model as fce_taps_kernel lays them out).
+template <int NZ, bool STEP, bool DIAG, bool CONV>
+__global__ void __launch_bounds__(256, 2)
+fce_ens_kernel(const float* __restrict__ imgf, const float* __restrict__ bias, const float* T, const float* __restrict__ top_flux,
+               const float* __restrict__ halo_bottom, const float* __restrict__ halo_top, float mu_T, float inv_sig_T, float sig_wT, float mu_wT,
+               float inv_dz_out, float inv_dz, float c, float K, float* __restrict__ dz_wT, float* T_out, float* __restrict__ faces, int n_col,
+               FceEns en, const float* __restrict__ conv_taps, int conv_c) {
+    constexpr int CW = 16;
+    {
+        const size_t k = blockIdx.y;
+        imgf += k * en.img;
+        bias += k * en.bias;
+        T += k * en.state;
+        if (halo_bottom) halo_bottom += k * en.halo;
+        if (halo_top) halo_top += k * en.halo;
         if constexpr (STEP) {
-            if (w == 0 && lane < CW) {
-                float* t = TS + lane * LDT;
-                const float *halo_bottom = HB, *halo_top = HT;   // (never null here: the load above resolved an absent halo to the interior value)
-                const int ca_i = lane;
-#include "convadj_sweep.inc"
-            }
-            FC_BARRIER();
-            constexpr int Q = NZ / 4;
-#pragma unroll
-            for (int e0 = 0; e0 < CW * Q; e0 += 256) {
-                const int e = e0 + tid, cl = e / Q, k = (e % Q) * 4;
-                if (e < CW * Q) {
-                    const float* d = TS + cl * LDT + k;
-                    const f32x4 q = {d[0], d[1], d[2], d[3]};
-                    if (col0 + cl < n_col) *reinterpret_cast<f32x4*>(T_out + (size_t)(col0 + cl) * NZ + k) = q;
-                }
-            }
+            dz_wT += k * en.state;
+            T_out += k * en.state;
         }
-        float tf[S::OWN];
-        // ---- diagnose_wT_NN's κ_f ∂T/∂z (:107-115) of this thread's faces oi + 1 (kept for the end) and, oi = 0, face 0 (F[0] = 0: stored now)
-        float kg[S::OWN];
-        if constexpr (DIAG) {
-#pragma unroll
-            for (int r = 0; r < S::OWN; r++) {
-                const int c = oc[r];
-                const float tc = TR[c * LDT + oi];
-                const float inside = TR[c * LDT + oi + 1];       // (oi = NZ - 1: the pad float of the row, not used)
-                const float up = oi == NZ - 1 ? HT[c] : inside;
-                const float g = (up - tc) * inv_dz;
-                kg[r] = (g < 0.0f ? K : 0.0f) * g;
-                if (oi == 0 && col0 + c < n_col) {
-                    const float g0 = (tc - HB[c]) * inv_dz;
-                    faces[(size_t)(col0 + c) * (NZ + 1)] = 0.0f - (g0 < 0.0f ? K : 0.0f) * g0;
-                }
-            }
-        }
-        // (loaded here, not with T: nothing but the sweep's own registers is live across it)
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) tf[r] = top_flux[min(col0 + oc[r], n_col - 1)];
-        if constexpr (REFILL) {
-#pragma unroll
-            for (int q = 0; q < FC_PF; q++) ring[q] = (sb[fc_sec<NZ, CW>(q)] + fc_off<NZ, CW>(q))[lane];
-        }
-        // ---- the network (layer 2's epilogues overwrite TR and TS: every wave is past the barrier after layer 1 by then)
-#include "fc_infer_chain.inc"
-#pragma unroll
-        for (int r = 0; r < S::OWN; r++) {
-            float lo, hi;
-            fc_infer_faces<NZ, CW>(PART, oc[r], oi, b3v, sig_wT, mu_wT, tf[r], lo, hi);
-            if (col0 + oc[r] < n_col) {
-                if constexpr (STEP) dz_wT[(size_t)(col0 + oc[r]) * NZ + oi] = -(hi - lo) * inv_dz_out;
-                if constexpr (DIAG) faces[(size_t)(col0 + oc[r]) * (NZ + 1) + oi + 1] = hi - kg[r];
-            }
-        }
-        FC_BARRIER();                                                               // PART (= A1's rows), X, TR are rewritten by the next tile
+        if constexpr (DIAG) faces += k * en.faces;
+        if constexpr (CONV) conv_taps += k * (FC_CONV_MAX + 1);
     }
+#include "fc_embed_body.inc"
+}
+
+// the filter of every member from the head of its parameter vector (w_stride floats apart) into the kernel's order: taps[d] = w[c - 1 - d], the tap
+// that multiplies x[i + d] (NNlib's conv flips the kernel), zero beyond the filter; taps[FC_CONV_MAX] = b
+__global__ void fce_taps_kernel(const float* __restrict__ w, size_t w_stride, int c, float* __restrict__ taps) {
+    const int d = threadIdx.x;
+    const float* wk = w + (size_t)blockIdx.x * w_stride;
+    if (d <= FC_CONV_MAX) taps[(size_t)blockIdx.x * (FC_CONV_MAX + 1) + d] = d == FC_CONV_MAX ? wk[c] : (d < c ? wk[c - 1 - d] : 0.0f);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -170,9 +103,26 @@ static void fce_for_each_kernel(F&& f) {
     shape(std::integral_constant<int, 32>{}, std::integral_constant<int, 16>{});
 }
 
+// ... and its sibling for the ensemble family: f(Nz, step, diag, conv, kernel, dynamic LDS bytes), 16-column tiles
+template <class F>
+static void fce_ens_for_each_kernel(F&& f) {
+    auto shape = [&](auto N, auto C) {
+        f(N(), true, false, C(), fce_ens_kernel<N(), true, false, C()>, fce_lds<N(), 16>());
+        f(N(), false, true, C(), fce_ens_kernel<N(), false, true, C()>, fce_lds<N(), 16>());
+        f(N(), true, true, C(), fce_ens_kernel<N(), true, true, C()>, fce_lds<N(), 16>());
+    };
+    shape(std::integral_constant<int, 64>{}, std::false_type{});
+    shape(std::integral_constant<int, 32>{}, std::false_type{});
+    shape(std::integral_constant<int, 64>{}, std::true_type{});
+    shape(std::integral_constant<int, 32>{}, std::true_type{});
+}
+
 hipError_t fce_set_kernel_attributes() {
     hipError_t e = hipSuccess;
     fce_for_each_kernel([&](int, int, bool, bool, auto* k, size_t lds) {
+        if (e == hipSuccess) e = set_max_lds(k, lds);
+    });
+    fce_ens_for_each_kernel([&](int, bool, bool, bool, auto* k, size_t lds) {
         if (e == hipSuccess) e = set_max_lds(k, lds);
     });
     return e;
@@ -199,4 +149,43 @@ hipError_t launch_fc_embed(const DevModel& m, const FcEmbedArgs& a, hipStream_t 
         launched = true;
     });
     return launched ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// All members in one launch: tiles along x, the model in grid.y.  The grid's x is capped as the single-model launch's, so a member's workgroups
+// walk over its tiles with the operand ring streaming from one tile to the next.
+hipError_t launch_fc_embed_ens(const DevModel& m, const FcEmbedArgs& a, int n_models, int conv, const float* taps, hipStream_t stream) {
+    if (a.n_col < 1 || !(a.Lz > 0.0f) || !a.imgf || !a.bias || !a.T || !a.top_flux || a.cw != 16) return hipErrorInvalidValue;
+    if (n_models < 1 || n_models > 65535) return hipErrorInvalidValue;
+    if (conv && (conv < 2 || conv > FC_CONV_MAX || !taps)) return hipErrorInvalidValue;
+    const bool diag = a.wT_faces != nullptr;
+    if (!a.step && !diag) return hipErrorInvalidValue;
+    if (a.step && (!a.dz_wT || !a.T_out || !(a.dt > 0.0f))) return hipErrorInvalidValue;
+    uintptr_t al = (uintptr_t)a.T | (uintptr_t)a.wT_faces;
+    if (a.step) al |= (uintptr_t)a.dz_wT | (uintptr_t)a.T_out;
+    if (al & 15) return hipErrorInvalidValue;
+    const int n_tiles = (a.n_col + 15) / 16;
+    const dim3 grid(std::min(n_tiles, 512), n_models), block(256);
+    const float dz = a.Lz / (float)m.Nz;
+    const float c = a.step ? a.dt / (dz * dz) : 0.0f;
+    const float inv_dz = (float)m.Nz / a.Lz;
+    FceEns en;
+    en.img = fc_image_floats(m.Nz);
+    en.bias = fc_bias_floats(m.Nz);
+    en.state = (size_t)a.n_col * m.Nz;
+    en.halo = (size_t)a.n_col;
+    en.faces = (size_t)a.n_col * (m.Nz + 1);
+    bool launched = false;
+    fce_ens_for_each_kernel([&](int Nz, bool step, bool dg, bool cv, auto* k, size_t lds) {
+        if (launched || Nz != m.Nz || step != a.step || dg != diag || cv != (conv != 0)) return;
+        hipLaunchKernelGGL(k, grid, block, lds, stream, a.imgf, a.bias, a.T, a.top_flux, a.halo_bottom, a.halo_top, m.mu_T, 1.0f / m.sig_T, m.sig_wT, m.mu_wT,
+                           -1.0f * (float)m.Nz / a.Lz, inv_dz, c, a.K, a.dz_wT, a.T_out, a.wT_faces, a.n_col, en, taps, conv);
+        launched = true;
+    });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+hipError_t launch_fce_taps(const float* w, size_t w_stride, int conv, int n_models, float* taps, hipStream_t stream) {
+    if (!w || !taps || conv < 2 || conv > FC_CONV_MAX || n_models < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fce_taps_kernel, dim3(n_models), dim3(64), 0, stream, w, w_stride, conv, taps);
+    return hipGetLastError();
 }

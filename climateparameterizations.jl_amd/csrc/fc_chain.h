@@ -4,6 +4,7 @@
 // definition, so that both kernels issue the same MFMA sequence and round the same way: their ∂z wT agree bit for bit.
 #pragma once
 #include "colnde_dev.h"
+#include "engine_fc.h"                             // FC_CONV_MAX
 
 typedef float fc16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32;
@@ -118,6 +119,17 @@ __device__ __forceinline__ void fc_section(f32x4 (&ring)[FC_PF], const f32x4* co
     int oc[S::OWN];                                                        \
     const int oi = tid & (NZ - 1);                                         \
     _Pragma("unroll") for (int r = 0; r < S::OWN; r++) oc[r] = (tid + 256 * r) / NZ
+
+// The --conv filter's pre-activation (FcConv, engine_fc.h) for this lane's level from the column's levels in the lanes above (d = 0: the lane's own):
+// ONE instruction sequence for the forward kernel, the adjoint's recomputation and the embedded step, so that all see the same bits and the same sign.
+// cw[d] multiplies x[i + d] (w[c - d], 1-based), cb = b.
+__device__ __forceinline__ float fc_conv_pre(float x, const float (&cw)[FC_CONV_MAX], float cb, int c) {
+    float pre = cb;
+#pragma unroll
+    for (int d = 0; d < FC_CONV_MAX; d++)
+        if (d < c) pre = fmaf(cw[d], __shfl_down(x, d), pre);                   // taps in a fixed order: w[c], w[c-1], ..., w[1]
+    return pre;
+}
 
 // ------------------------------------------------------------------------------------------------
 // embedded inference, shared pieces (fc_infer_kernel, fce_kernel).  LDS rows as in the forward solve: X [CW][LDX] the scaled input,

@@ -206,6 +206,37 @@ def diagnose_wT_NN(engine: ColumnNDE, weights, T, top_flux, Lz: float, K: float,
     return engine.fc_diagnose_wT(weights, T2, top, Lz, K, halos).reshape(shape[:-1] + (shape[-1] + 1,))
 
 
+def _ens_embed_args(ens, T, top_flux, halos):
+    K = int(getattr(ens, "n_models", 1))
+    T = np.asarray(T, dtype=np.float32)
+    shape = T.shape
+    T3 = np.ascontiguousarray(T.reshape(K, -1, shape[-1]))
+    n = T3.shape[1]
+    top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_flux, np.float32).reshape(-1), (n,)))
+    if halos is not None:
+        halos = tuple(None if a is None else np.ascontiguousarray(np.asarray(a, np.float32).reshape(K, n)) for a in halos)
+    return T3, shape, top, halos
+
+
+def ensemble_progress_neural_network(ens, weights, T, top_flux, Lz: float, dt: float, K: float, halos=None, diagnose: bool = False):
+    """`progress_neural_network` (src/oceananigans_nn.jl:153-165) for the K members of a `FreeConvectionEnsemble` — plain or `--conv` — in one launch
+    (`ColumnNDE.fc_embedded`); a single `ColumnNDE(cfg, n, conv=c)` is K = 1.  T [K, ..., Nz], each member its own state; top_flux a scalar or one
+    value per column, shared by the members; halos = None or (halo_bottom, halo_top), each [K, ...] or None; weights [K, n_params] or None (the
+    images of the previous call).  Returns (∂z_wT_NN, Tⁿ⁺¹) in T's shape — with diagnose=True also `diagnose_wT_NN` of the state as given,
+    [K, ..., Nz + 1].  Row k is what `progress_neural_network` gives for a plain member k, bit for bit."""
+    T3, shape, top, halos = _ens_embed_args(ens, T, top_flux, halos)
+    r = ens.fc_embedded(weights, T3, top, Lz, K, dt, halos, step=True, faces=bool(diagnose))
+    out = (r.dz_wT.reshape(shape), r.T_new.reshape(shape))
+    return out + (r.faces.reshape(shape[:-1] + (shape[-1] + 1,)),) if diagnose else out
+
+
+def ensemble_diagnose_wT_NN(ens, weights, T, top_flux, Lz: float, K: float, halos=None):
+    """`diagnose_wT_NN(model)` (src/oceananigans_nn.jl:100-118) for the K members in one launch: [K, ..., Nz + 1].  Arguments as
+    `ensemble_progress_neural_network`."""
+    T3, shape, top, halos = _ens_embed_args(ens, T, top_flux, halos)
+    return ens.fc_embedded(weights, T3, top, Lz, K, None, halos, step=False, faces=True).faces.reshape(shape[:-1] + (shape[-1] + 1,))
+
+
 def train_neural_differential_equation_device(nde: FreeConvectionNDE, weights, opt: ADAM, epochs: int, process_group=None, comm=None):
     """`Flux.train!` (training.jl:71) with θ and the ADAM state resident on the GPU: per epoch one `colnde_loss_grad_dev`,
     [one SUM all-reduce when the simulations are sharded over `process_group`], one fused `colnde_adam_step_dev`.

@@ -145,6 +145,55 @@ def check_fc_embed_arrays(Nz: int, n: int, T, top_flux, halos=None, dz_out=None,
                 raise ValueError("%s overlaps %s" % (to, tj))
 
 
+class FcEnsembleEmbedded(NamedTuple):
+    """What `fc_embedded` returns: dz_wT (∂z_wT_NN of T as given) and T_new (T′), each [K, n, Nz], or None (step=False); faces (wT_NN − κ ∂T/∂z of the
+    state as given) [K, n, Nz + 1], or None (faces=False)."""
+    dz_wT: Optional[object]
+    T_new: Optional[object]
+    faces: Optional[object]
+
+
+def check_fc_ens_embed_arrays(n_models: int, n_params: int, Nz: int, weights, T, top_flux, dt=None, halos=None, step: bool = True, faces: bool = True,
+                              dz_out=None, T_out=None):
+    """Shape, dtype and group rules of `fc_embedded` (no GPU needed), raised before any library call: weights [K, n_params] (n_params the HANDLE's
+    count — `fc_ensemble_n_params(cfg, conv)`: a conv ensemble does not take vectors of the plain length) or None; T [K, n, Nz] with n >= 1;
+    top_flux [n], shared by the members; halos = None or (halo_bottom, halo_top), each [K, n] or None; every array float32; at least one of step
+    and faces; step=True needs dt > 0; dz_out and T_out [K, n, Nz] (caller-owned outputs of the step) are one group: both or neither.  Returns n."""
+    K = int(n_models)
+    if K < 1:
+        raise ValueError("n_models must be >= 1, got %d" % K)
+    if weights is not None and tuple(weights.shape) != (K, int(n_params)):
+        raise ValueError("weights: expected shape %s for %d models (n_params is the handle's count: a conv member's vector leads with its filter), got %s"
+                         % ((K, int(n_params)), K, tuple(weights.shape)))
+    if len(tuple(T.shape)) != 3 or int(T.shape[0]) != K or int(T.shape[2]) != Nz or int(T.shape[1]) < 1:
+        raise ValueError("T: expected shape (%d, n, %d) for %d models with n >= 1, got %s" % (K, Nz, K, tuple(T.shape)))
+    n = int(T.shape[1])
+    if tuple(top_flux.shape) != (n,):
+        raise ValueError("top_flux: expected shape %s (shared by the members), got %s" % ((n,), tuple(top_flux.shape)))
+    if halos is not None and len(halos) != 2:
+        raise ValueError("halos must be (halo_bottom, halo_top); either may be None")
+    named = [("weights", weights), ("T", T), ("top_flux", top_flux)]
+    for nm, a in zip(("halo_bottom", "halo_top"), halos if halos is not None else ()):
+        if a is not None and tuple(a.shape) != (K, n):
+            raise ValueError("%s: expected shape %s, got %s" % (nm, (K, n), tuple(a.shape)))
+        named.append((nm, a))
+    for nm, a in named:
+        if a is not None and _dtype_name(a) != "float32":
+            raise ValueError("%s: expected float32, got %s" % (nm, _dtype_name(a)))
+    if (dz_out is None) != (T_out is None):
+        raise ValueError("dz_out and T_out are one output group (the step): give both or neither, got only %s" % ("dz_out" if T_out is None else "T_out"))
+    if dz_out is not None and not step:
+        raise ValueError("dz_out / T_out are the step's outputs: step=False writes none")
+    for nm, a in (("dz_out", dz_out), ("T_out", T_out)):
+        if a is not None and tuple(a.shape) != (K, n, Nz):
+            raise ValueError("%s: expected shape %s, got %s" % (nm, (K, n, Nz), tuple(a.shape)))
+    if not step and not faces:
+        raise ValueError("nothing to compute: step (dz_wT, T′) and faces are the two output groups — ask for at least one")
+    if step and (dt is None or not float(dt) > 0.0):
+        raise ValueError("step=True takes the adjustment step and needs dt > 0, got dt = %r (step=False: the faces of the state as given)" % (dt,))
+    return n
+
+
 def min_substeps(cfg: NDEConfig) -> int:
     """`colnde_min_substeps`: the least RK4 sub-steps per save interval inside the diffusive stability bound (no GPU needed)."""
     c, keep = to_c_config(cfg, 1, 0, 0)
@@ -791,6 +840,52 @@ class ColumnNDE:
         _lib.check(self._L.colnde_fc_diagnose_wT(self._h, _ptr(w), _ptr(T), _ptr(top_flux), _ptr(hb), _ptr(ht), float(Lz), float(K), _ptr(faces), n))
         return faces
 
+    def fc_embedded(self, weights, T, top_flux, Lz: float, K: float, dt=None, halos=None, step: bool = True, faces: bool = True, dz_out=None,
+                    T_out=None) -> "FcEnsembleEmbedded":
+        """One embedded iteration of ALL members in one launch (`colnde_ensemble_fc_embedded`): per member what `fc_embedded_step` (step) and
+        `fc_diagnose_wT` (faces) give for that member's weights and state — on a `FreeConvectionEnsemble`, plain or conv, and on a single
+        `ColumnNDE` as K = 1, plain or `conv=c`: the one embedding call that runs a `--conv` network.  weights [K, n_params], or None: the
+        operand images the previous call on this handle packed (an embedding calls with fixed weights); T [K, n, Nz], each member its own
+        state; top_flux [n], shared; halos = None or (halo_bottom, halo_top), each [K, n] or None; step=True needs dt > 0.  numpy arrays or
+        torch device tensors (all of one kind; `dz_out` and `T_out`, device tensors given together, receive the step — `T_out` may be `T`: in
+        place).  Returns `FcEnsembleEmbedded(dz_wT, T_new, faces)`."""
+        Nz, Km = self.cfg.Nz, int(getattr(self, "n_models", 1))
+        n = check_fc_ens_embed_arrays(Km, self.n_params, Nz, weights, T, top_flux, dt, halos, step, faces, dz_out, T_out)
+        hb, ht = halos if halos is not None else (None, None)
+        dtv = float(dt) if step else 0.0
+        if _is_torch(T):
+            import torch
+            if weights is not None:
+                self._chk_dev(weights, (Km, self.n_params))
+            self._chk_dev(T, (Km, n, Nz))
+            self._chk_dev(top_flux, (n,))
+            for a in (hb, ht):
+                if a is not None:
+                    self._chk_dev(a, (Km, n))
+            for a in (dz_out, T_out):
+                if a is not None:
+                    self._chk_dev(a, (Km, n, Nz))
+            dz = (dz_out if dz_out is not None else torch.empty_like(T)) if step else None
+            Tn = (T_out if T_out is not None else torch.empty_like(T)) if step else None
+            fc = torch.empty((Km, n, Nz + 1), dtype=T.dtype, device=T.device) if faces else None
+            self.use_torch_stream()
+            P = lambda a: a.data_ptr() if a is not None else None
+            fn = self._L.colnde_ensemble_fc_embedded_dev
+        else:
+            if dz_out is not None or T_out is not None:
+                raise ValueError("dz_out / T_out are for device tensors; host arrays are returned")
+            weights = _f32(weights, (Km, self.n_params)) if weights is not None else None
+            T, top_flux = _f32(T), _f32(top_flux)
+            hb = _f32(hb) if hb is not None else None
+            ht = _f32(ht) if ht is not None else None
+            dz = np.empty_like(T) if step else None
+            Tn = np.empty_like(T) if step else None
+            fc = np.empty((Km, n, Nz + 1), np.float32) if faces else None
+            P = _ptr
+            fn = self._L.colnde_ensemble_fc_embedded
+        _lib.check(fn(self._h, P(weights), P(T), P(top_flux), P(hb), P(ht), float(Lz), dtv, float(K), P(dz), P(Tn), P(fc), n))
+        return FcEnsembleEmbedded(dz, Tn, fc)
+
     def adam_step(self, weights, grad, m, v, eta: float, beta=(0.9, 0.999), eps: float = 1e-8, beta_t=None):
         """One fused `Flux.Optimise.ADAM` apply!/update! on device vectors (in place).  beta_t = running powers (β₁ᵗ, β₂ᵗ)."""
         import torch
@@ -1097,7 +1192,8 @@ class FreeConvectionEnsemble(ColumnNDEEnsemble):
     free_convection/train_free_convection_nde.jl (one process per seed / optimiser rate / penalty setting there) and the judging of a training run
     (free_convection/src/testing.jl: the network of every epoch on every simulation), every kernel launched once for all K.  `forward`, `loss`,
     `loss_grad` and `adam_step` are `ColumnNDEEnsemble`'s, with its NumPy / torch rules; row k holds the bits a `ColumnNDE` handle computes for
-    model k's weights.  There are no constants to vary: `set_physics` and `wm_embedded` are refused.
+    model k's weights.  There are no constants to vary: `set_physics` and `wm_embedded` are refused.  `fc_embedded` (inherited from `ColumnNDE`)
+    takes the K networks into the embedding ocean column in one launch.
     conv = c > 1: K `--conv c` networks (`colnde_create_conv_ensemble`) — cfg is the plain configuration, a model's vector has
     `free_convection.conv_n_params(Nz, c)` entries and row k holds the bits of `ColumnNDE(cfg, n, conv=c)`; `causal_penalty` masks the first Dense
     weight of the conv chain, 4Nz x (Nz - c + 1)."""

@@ -497,7 +497,7 @@ int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const floa
  * [K][n_params + 8] result rows), and by the handle-level calls a wind-mixing ensemble accepts (describe adds models=K, the bytes per model and
  * time_segments).  Row k of every result holds the bits a colnde_create handle computes for model k's weights, under either matrix arithmetic (and the same
  * COLNDE_FC_SEG: the segment count orders the gradient's sums).  colnde_ensemble_set_physics (no constants to vary), colnde_ensemble_wm_embedded and every
- * single-model call refuse it.
+ * single-model call refuse it; colnde_ensemble_fc_embedded (below) takes its K networks into the embedding.
  * Refused at creation, before any device work, each with its reason: a wind-mixing model, another network shape or Nz, an engine other than AUTO or FC32,
  * substeps = 0, substeps < colnde_min_substeps, n_models outside 1..65535, more than 4,096 columns per model (above it a single handle runs 32-column
  * tiles), COLNDE_FC=0, COLNDE_FC_CW=32, COLNDE_FC_BLOCK.  Then "no HIP device ... no CPU fallback", and tapes that do not fit, with the bytes needed: all K
@@ -570,7 +570,7 @@ int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weights, const fl
  * the filter's c + 1 first, then the 8 loss slots), loss_per_tstep[_dev], adam_step_dev, set_stream, set_substeps / substeps, set_matrix_arithmetic /
  * matrix_arithmetic, n_params, engine, conv_filter, plan (info[6] = c), describe ("conv=c"), profiling and kernel times (the filter-gradient kernel is timed
  * with the dW GEMM, slot 5), destroy; the array utilities that read no network (coarse_grain, zscore_stats, scale, convective_adjustment, implicit_diffusion,
- * mpp_diagnose_flux).  Every other call refuses a conv handle with a sentence naming the call: rhs, flux, error_estimate, choose_substeps, infer_*, the embedded
+ * mpp_diagnose_flux); colnde_ensemble_fc_embedded[_dev] (below: the network in the embedding, K = 1).  Every other call refuses a conv handle with a sentence naming the call: rhs, flux, error_estimate, choose_substeps, infer_*, the embedded
  * steps and diagnoses, pretrain_flux, set_global_columns and allreduce_result (multi-GPU results), the ensemble and closure calls (K conv networks side by
  * side: colnde_create_conv_ensemble, below).
  * Refused here, before any device work, each with its reason: conv_filter outside 2..8, a wind-mixing model, another network shape or Nz, an engine other than
@@ -597,6 +597,38 @@ int colnde_conv_filter(const colnde_handle* h);
  * bytes per column and save interval, the filter slab and the padded vectors in the bytes per model — are planned here as colnde_create_fc_ensemble plans
  * them. */
 int colnde_create_conv_ensemble(const colnde_config* cfg, int conv_filter, int n_models, colnde_handle** out);
+
+/* ---- the K networks of a free-convection ensemble in the embedding ocean column at once ------------------------------------------------------------------
+ * What free_convection/test_free_convection_nde.jl:118-122 does with each trained network (oceananigans_convective_adjustment_nn, src/oceananigans_nn.jl:42-198):
+ * per iteration progress_neural_network (:153-165), with every saved state diagnose_wT_NN (:100-118) — for every member of a sweep in ONE launch,
+ * each member on its OWN column state with its own weights.  The one embedding call that accepts --conv networks.
+ *   Handles: a colnde_create_fc_ensemble handle, a colnde_create_conv_ensemble handle, or a single free-convection handle as K = 1 — colnde_create or
+ *   colnde_create_conv: this is how one trained --conv network is deployed (colnde_fc_embedded_step, colnde_fc_diagnose_wT and colnde_infer_* keep refusing
+ *   ensembles and conv handles).  Shapes: Nz = 32 | 64 with Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1) behind the optional filter, whatever engine
+ *   or stepper the handle trains with.
+ *   d_weights [K][colnde_n_params] (the handle's layout; a conv member's vector leads with its filter), or NULL: the operand images the previous call on this
+ *   handle packed are used again — an embedding calls with fixed weights hundreds of times, and packing K images per call rivals the kernel at these sizes.
+ *   NULL on a handle that has never been given weights is an error.  The images are this call's own (tile width 16): training calls in between do not touch them.
+ *   d_T [K][n_col][Nz], k = 0 deepest, the units colnde_infer_dz_wT takes; d_top_flux [n_col], SHARED by the members (they are driven by the same simulations);
+ *   d_halo_bottom, d_halo_top [K][n_col] or NULL (the nearest interior value: zero-gradient fill).
+ *   d_dz_wT and d_T_out [K][n_col][Nz] are one output group — both given: the forcing of T AS GIVEN, then convective_adjustment!(model, dt, K_ca), dt > 0
+ *   required, d_T_out may be d_T — or both NULL (no step, dt ignored).  d_wT_faces [K][n_col][Nz+1] or NULL: diagnose_wT_NN of the state AS GIVEN.
+ * Per member the arithmetic is colnde_fc_embedded_step's and colnde_fc_diagnose_wT's (above).  A conv member's filter sits in front of the dense chain exactly as in
+ * training — y[i] = relu(b + sum_d w[c-1-d] x~[i+d]) (0-based) on the SCALED input x~ for i < M = Nz - c + 1, zero above, W1 padded with zero columns — and the
+ * adjustment and the face gradients read the unfiltered T.  Row k of a plain ensemble is, bit for bit, what the single-model calls write for member k (at tile
+ * width 16, their default up to 4,096 columns); row k of a conv ensemble is what this call writes on a colnde_create_conv handle with member k's vector.  The
+ * matrix pipe is f32 MFMA under either matrix_arithmetic ("fc_embed=f32" in colnde_describe).  More than 4,096 columns per member run correctly, on the same
+ * 16-column tiles.
+ * Alignment: only the BASE pointers d_T, d_dz_wT, d_T_out and d_wT_faces must be 16-byte aligned.  Member k's wT_faces start k n_col (Nz + 1) floats in — not
+ * a multiple of four for every n_col — and the kernel stores faces one float at a time; a member's T, dz_wT and T_out start a multiple of Nz floats in.
+ * Refused, each with this call's name and the reason in colnde_last_error: a null handle, a wind-mixing or closure handle, a free-convection shape outside the
+ * above, a half-given step group, neither output group given, a step with dt <= 0, K_ca < 0, n_columns < 1 or Lz <= 0, misaligned base pointers, NULL weights
+ * on the first call.  Timed under colnde_kernel_time slot 9 (the launch alone; the pack is not in it).  Handle's stream, not synchronised. */
+int colnde_ensemble_fc_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
+        const float* d_halo_top, float Lz, float dt, float K_ca, float* d_dz_wT, float* d_T_out, float* d_wT_faces, int n_columns);
+/* the same with host arrays (no alignment rule; the step runs in place on the uploaded T block); synchronises the stream */
+int colnde_ensemble_fc_embedded(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
+        const float* halo_top, float Lz, float dt, float K_ca, float* dz_wT, float* T_out, float* wT_faces, int n_columns);
 
 /* ---- closure-only model: fitting the five Pacanowski-Philander constants before any network is trained ------------------------------------------------
  * optimise_modified_pacanowski_philander (wind_mixing/src/diffusivity_parameter_optimisation.jl:35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl
@@ -636,7 +668,7 @@ int colnde_closure_loss_grad(colnde_handle* h, const float* params, const float 
 /* ---- measurement: HIP-event timing of the handle's kernels on its stream.
  * which: 0 = forward solve kernel, 1 = adjoint kernel, 2 = gradient reduce, 3 = rhs, 4 = inference,
  * 5 = streaming dW1 GEMM (regtile engine only), 6 = convective adjustment, 7 = ADAM step, 8 = implicit diffusion,
- * 9 = free-convection embedded step / diagnose_wT, 10 = wind-mixing flux diagnoses (colnde_wm_diagnose_flux, colnde_wm_embedded_step_flux,
+ * 9 = free-convection embedded step / diagnose_wT (colnde_ensemble_fc_embedded too), 10 = wind-mixing flux diagnoses (colnde_wm_diagnose_flux, colnde_wm_embedded_step_flux,
  * colnde_mpp_diagnose_flux, colnde_ensemble_wm_embedded).
  * Returns accumulated milliseconds and launch count since the last reset (synchronises the stream). */
 int colnde_set_profiling(colnde_handle* h, int enabled);

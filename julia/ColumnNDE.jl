@@ -440,6 +440,23 @@ function ensemble_progress_neural_network_flux(h::Handle, θ::Matrix{Float32}, u
     (uw, vw, wT)
 end
 
+"progress_neural_network (free_convection/src/oceananigans_nn.jl:153-165) and diagnose_wT_NN (:100-118) for ALL K networks of a free-convection
+ensemble handle — plain or --conv; a single handle, plain or conv, is K = 1 — in one launch (colnde_ensemble_fc_embedded): θ (n_params, K), or
+nothing: the operand images the previous call on this handle packed; T and ∂z_wT_NN (Nz, n_columns, K), every member on its own state, adjusted in
+place; surface_flux one value per column, shared by the members; halo_bottom, halo_top (n_columns, K) or nothing.  Returns wT_faces
+(Nz+1, n_columns, K) of the states as given."
+function ensemble_progress_neural_network!(h::Handle, θ::Union{Nothing,Matrix{Float32}}, T::Array{Float32,3}, surface_flux::Vector{Float32}, Lz, Δt, K,
+                                           ∂z_wT_NN::Array{Float32,3}; halo_bottom=nothing, halo_top=nothing)
+    w = θ === nothing ? C_NULL : pointer(θ)
+    hb = halo_bottom === nothing ? C_NULL : pointer(halo_bottom); ht = halo_top === nothing ? C_NULL : pointer(halo_top)
+    wT = Array{Float32,3}(undef, size(T, 1) + 1, size(T, 2), size(T, 3))
+    GC.@preserve θ halo_bottom halo_top check(ccall((:colnde_ensemble_fc_embedded, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Cfloat, Ptr{Float32}, Ptr{Float32},
+         Ptr{Float32}, Cint),
+        h.ptr, w, T, surface_flux, hb, ht, Lz, Δt, K, ∂z_wT_NN, T, wT, size(T, 2)))
+    wT
+end
+
 "diagnose_baseline_flux_uw, _vw, _wT (wind_mixing/src/NDE_oceananigans.jl:157-191): (−ν ∂z u, −ν ∂z v, −νT ∂z T) on the faces with the top
 face replaced by the top flux, each (Nz+1, n_columns); no networks"
 function diagnose_baseline_flux(h::Handle, u::Matrix{Float32}, v::Matrix{Float32}, T::Matrix{Float32}, top_fluxes::Matrix{Float32}, Δz, constants, p,
