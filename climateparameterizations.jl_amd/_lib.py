@@ -92,6 +92,8 @@ SYMBOLS = [
     ("colnde_ensemble_adam_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V] + [ctypes.c_float] * 5),
     ("colnde_ensemble_wm_embedded", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _V, ctypes.c_int] + [_V] * 9 + [ctypes.c_int]),
     ("colnde_ensemble_wm_embedded_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _V, ctypes.c_int] + [_V] * 9 + [ctypes.c_int]),
+    ("colnde_ensemble_profile", ctypes.c_int, [_V] * 9),
+    ("colnde_ensemble_profile_dev", ctypes.c_int, [_V] * 9),
     ("colnde_create_fc_ensemble", ctypes.c_int, [_V, ctypes.c_int, ctypes.POINTER(_V)]),
     ("colnde_create_conv", ctypes.c_int, [_V, ctypes.c_int, ctypes.POINTER(_V)]),
     ("colnde_create_conv_ensemble", ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_V)]),

@@ -19,6 +19,7 @@
 #include "column_ops.h"
 #include "engine_closure.h"
 #include "engine_wm_infer.h"
+#include "engine_wm_profile.h"
 #include "engine_fc_embed.h"
 #include "engine_fc_pretrain.h"
 
@@ -89,7 +90,7 @@ bool fce_covers(const colnde_handle* h);
     } while (0)
 
 // the timing slots of colnde_kernel_time
-enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1 = 5, K_CONVADJ = 6, K_ADAM = 7, K_IMPLDIFF = 8, K_FCEMBED = 9, K_FLUXDIAG = 10, K_COUNT = 11 };
+enum { K_FORWARD = 0, K_ADJOINT = 1, K_REDUCE = 2, K_RHS = 3, K_INFER = 4, K_DW1 = 5, K_CONVADJ = 6, K_ADAM = 7, K_IMPLDIFF = 8, K_FCEMBED = 9, K_FLUXDIAG = 10, K_PROFILE = 11, K_COUNT = 12 };
 
 struct PendingEvent { hipEvent_t a, b; int which; };
 
@@ -98,7 +99,7 @@ struct PendingEvent { hipEvent_t a, b; int which; };
 // there is in the list by construction; the engine files read FC_CW, RT_FWD, T16_DWLDS, T16_TAPE_THREADS and T16_TAPE_WLDS themselves.
 #define COLNDE_ENV_LIST(X)                                                                                                                  \
     X(FWD_SPLIT) X(ADJ_SPLIT) X(DW_SPLIT) X(ADJ_GEOM) X(FWD_WLDS) X(FWD_THREADS) X(T16_FWD_HELPER) X(T16_ADJ_HELPER) X(T16_FWD_SPLIT)         \
-    X(T16_ADJ_SPLIT) X(FC) X(FC_CW) X(FC_EMBED_FUSED) X(FC_BLOCK) X(FC_SEG) X(WM_ENS_GRID) X(RT_ZTAPE) X(RT_BLOCK) X(RT_FWD) X(ALLOW_UNSTABLE_DT) \
+    X(T16_ADJ_SPLIT) X(FC) X(FC_CW) X(FC_EMBED_FUSED) X(FC_BLOCK) X(FC_SEG) X(WM_ENS_GRID) X(WM_PROFILE_GRID) X(RT_ZTAPE) X(RT_BLOCK) X(RT_FWD) X(ALLOW_UNSTABLE_DT) \
     X(T16_DWTAPE) X(T16_ZTAPE) X(T16_SPLIT_RICH) X(T16_BLOCK) X(T16_DWLDS) X(T16_TAPE_THREADS) X(T16_TAPE_WLDS)
 #define X(n) ENV_##n,
 enum EnvSwitch { COLNDE_ENV_LIST(X) ENV_COUNT };
@@ -247,6 +248,7 @@ struct colnde_handle {
     std::vector<float> phys_raw;    // ... as given: [n_models][5] {nu0, nu_minus, dRi, Ric, Pr} (empty: cfg's constants for every model)
     MppParams* d_wm_ens_mpp = nullptr;          // colnde_ensemble_wm_embedded: the per-model sweep constants on the device, and what they hold
     std::vector<MppParams> wm_ens_mpp_host;
+    RtPhys* d_prof_phys = nullptr;  // colnde_ensemble_profile: the closure constants of a call that overrides the handle's (physics != NULL)
     RtEns ens;                      // per-model strides of the buffers a model owns
     FcEns fens;                     // ... of a free-convection ensemble (colnde_create_fc_ensemble): the fc32 kernels' strides
     size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)

@@ -476,9 +476,12 @@ hipError_t launch_mpp_diagnose_flux(const float* u, const float* v, const float*
 // ------------------------------------------------------------------------------------------------
 // loss_per_tstep (wind_mixing/src/loss.jl:44-46; called on the six profile matrices of one simulation at training_postprocessing.jl:311-316)
 // ------------------------------------------------------------------------------------------------
+// blockIdx.y = model: its solution [n_col][n_save][n_var Nz] and its output [n_col][6][n_save] follow the previous model's; the truth is shared
 __global__ void __launch_bounds__(256) loss_per_tstep_kernel(const float* __restrict__ sol, const float* __restrict__ truth, int n_col, int n_save, int Nz,
                                                              int n_var, float* __restrict__ out) {
     const long total = (long)n_col * n_save * n_var;
+    sol += (size_t)blockIdx.y * total * Nz;
+    out += (size_t)blockIdx.y * n_col * 6 * n_save;
     for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long)gridDim.x * 256) {
         const int v = (int)(it % n_var);
         const long cs = it / n_var;                        // column * n_save + save point
@@ -499,12 +502,13 @@ __global__ void __launch_bounds__(256) loss_per_tstep_kernel(const float* __rest
     }
 }
 
-hipError_t launch_loss_per_tstep(const float* sol, const float* truth, int n_col, int n_save, int Nz, int n_var, float* out, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(out, 0, (size_t)n_col * 6 * n_save * sizeof(float), stream);
+hipError_t launch_loss_per_tstep(const float* sol, const float* truth, int n_col, int n_save, int Nz, int n_var, float* out, hipStream_t stream, int n_models) {
+    if (n_models < 1 || n_models > 65535) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)n_models * n_col * 6 * n_save * sizeof(float), stream);
     if (e != hipSuccess) return e;
     const long total = (long)n_col * n_save * n_var;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(loss_per_tstep_kernel, dim3(blocks), dim3(256), 0, stream, sol, truth, n_col, n_save, Nz, n_var, out);
+    hipLaunchKernelGGL(loss_per_tstep_kernel, dim3(blocks, n_models), dim3(256), 0, stream, sol, truth, n_col, n_save, Nz, n_var, out);
     return hipGetLastError();
 }
 

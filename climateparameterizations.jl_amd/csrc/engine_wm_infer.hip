@@ -32,21 +32,7 @@
 #include "engine_wm_infer.h"
 #include "colnde_dev.h"
 #include "kernel_select.h"
-
-typedef float wm_f32x16 __attribute__((ext_vector_type(16)));
-
-#define WM_WAVES 4
-#define WM_W_LDS (((3 * WM_NET + 3) / 4) * 4)             // floats of the weight image (padded to 16 bytes)
-#define WM_LD (WM_NZ + 1)                                  // fused: row stride of the staged state (conflict-free column walks)
-#define WM_FS (32 * WM_LD)                                 // ... floats per field of one wave's 32 columns
-#define WM_OFF_B1 (96 * WM_H1)
-#define WM_OFF_W2 (WM_OFF_B1 + WM_H1)
-#define WM_OFF_B2 (WM_OFF_W2 + WM_H1 * WM_H2)
-#define WM_OFF_W3 (WM_OFF_B2 + WM_H2)
-#define WM_OFF_B3 (WM_OFF_W3 + WM_H2 * 31)
-#define WM_RHO0(r) (((r) & 3) + 8 * ((r) >> 2))
-// the staged state rows belong to ONE wave, whose LDS operations complete in order: no s_barrier, only the compiler is held to the order
-#define WM_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
+#include "wm_infer_dev.h"              // the tile layout, the operand bases and the face stores, shared with engine_wm_profile.hip
 
 struct WmScal { float mu[3], inv_sig[3], fmu[3], fsig[3], inv_dz, dz; int act1, act2; };
 
@@ -55,8 +41,6 @@ __device__ __forceinline__ float wm_unscaled_minus_zero(float sig, float mu, flo
 #pragma clang fp contract(off)
     return (sig * y + mu) - (sig * 0.0f + mu);
 }
-
-__device__ __forceinline__ wm_f32x16 wm_mfma(float a, float b, wm_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
 // 16-byte loads of one tile's state: xr[f][q] = levels 8 q + 4 h .. + 3 of field f of the lane's column (zeros past the last column)
 __device__ __forceinline__ void wm_load_tile(const float* const (&src)[3], long long col, int h, int n_col, f32x4 (&xr)[3][4]) {
@@ -70,19 +54,6 @@ __device__ __forceinline__ void wm_load_tile(const float* const (&src)[3], long 
         }
 }
 
-// A-operand bases (floats into wl).  Row i of an MFMA's A is row i of its result: register ri of lane half hi.
-//   a1[tl]: layer 1, stacked tile tl: net n, feature 2 g + hi;  + 50 (32 t + rho(v, 0)) per k-step (G >= 75: padding rows, never consumed)
-//   a2: layer 2: output feature 2 ri + hi; + 40 s per k-step;  a3: layer 3: output = interior face j;  + 62 s per k-step
-#define WM_OPERAND_BASES() \
-    const int ri = (j & 3) + 4 * (j >> 3), hi = (j >> 2) & 1; \
-    int a1[5]; \
-    _Pragma("unroll") \
-    for (int tl = 0; tl < 5; tl++) { \
-        const int G = min(16 * tl + ri, 74); \
-        a1[tl] = (G / 25) * WM_NET + 2 * (G % 25) + hi + 4 * h * WM_H1; \
-    } \
-    const int a2 = WM_OFF_W2 + min(2 * ri + hi, WM_H2 - 1) + h * WM_H2; \
-    const int a3 = WM_OFF_W3 + min(j, 30) + h * 31;
 // the wave's span of one face output in 16-byte pieces (a last tile of c columns: 33 c floats, the odd ones singly); o is 16-byte aligned
 #define WM_STORE_FACES_ALIGNED(o, img, cnt) \
                 if (cnt > 0) { \
@@ -128,22 +99,6 @@ wm_infer_kernel(const float* __restrict__ w, WmScal S, const float* u, const flo
 #undef WM_TILE_STORE_FACES
     }
 }
-
-// cnt floats of the wave's LDS image to o, which is only 4-byte aligned (model m's faces start m n_col 33 floats into the output): singly up to
-// the first 16-byte boundary, 16-byte pieces from there, the rest singly.  An aligned o takes the pieces of WM_STORE_FACES_ALIGNED.
-#define WM_STORE_FACES_ANY(o, img, cnt) \
-                if (cnt > 0) { \
-                    const int pad = (int)(((uintptr_t)(o) >> 2) & 3); \
-                    _Pragma("unroll") \
-                    for (int i = 0; i < 5; i++) { \
-                        const int p = 4 * (i * 64 + lane) - pad; \
-                        if (p >= 0 && p + 3 < cnt) { \
-                            const f32x4 val = {img[p], img[p + 1], img[p + 2], img[p + 3]}; \
-                            *reinterpret_cast<f32x4*>(o + p) = val; \
-                        } else if (p + 3 >= 0 && p < cnt) \
-                            for (int t = max(p, 0); t < min(p + 4, cnt); t++) o[t] = img[t]; \
-                    } \
-                }
 
 // The ensemble form (engine_wm_infer.h: wm_ens_range): arrays carry a leading model index; the workgroup walks its contiguous items of the
 // model-major list, holds ONE model's weight image at a time and re-copies it at a model boundary between two barriers — the first so that no

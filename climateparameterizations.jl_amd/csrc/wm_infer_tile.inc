@@ -85,42 +85,11 @@
         }
 
         // ---- layer 1, the three nets stacked: 5 tiles x 48 k-steps
-        wm_f32x16 acc1[5];
-#pragma unroll
-        for (int tl = 0; tl < 5; tl++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int G = 16 * tl + r < 75 ? 16 * tl + r : 74;
-                acc1[tl][r] = wl[(G / 25) * WM_NET + WM_OFF_B1 + 2 * (G % 25) + h];
-            }
-#pragma unroll
-        for (int s = 0; s < 48; s++) {
-            const int in0 = 32 * (s >> 4) + WM_RHO0(s & 15);
-#pragma unroll
-            for (int tl = 0; tl < 5; tl++) acc1[tl] = wm_mfma(wl[a1[tl] + WM_H1 * in0], xs[s], acc1[tl]);
-        }
-#pragma unroll
-        for (int tl = 0; tl < 5; tl++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc1[tl][r] = dev_act(S.act1, acc1[tl][r]);
+#include "wm_net_layer1.inc"
 
 #pragma unroll
         for (int n = 0; n < 3; n++) {
-            // ---- layer 2: 25 k-steps over this net's registers of the stacked tiles
-            wm_f32x16 acc2;
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc2[r] = r < 10 ? wl[n * WM_NET + WM_OFF_B2 + 2 * r + h] : 0.0f;
-#pragma unroll
-            for (int s = 0; s < 25; s++) {
-                const int G = 25 * n + s;
-                acc2 = wm_mfma(wl[n * WM_NET + a2 + 2 * WM_H2 * s], acc1[G >> 4][G & 15], acc2);
-            }
-            // ---- layer 3: 10 k-steps; row rho(r, h) = interior face (row 31: padding)
-            wm_f32x16 y;
-#pragma unroll
-            for (int r = 0; r < 16; r++) y[r] = wl[n * WM_NET + WM_OFF_B3 + min(WM_RHO0(r) + 4 * h, 30)];
-#pragma unroll
-            for (int s = 0; s < 10; s++) y = wm_mfma(wl[n * WM_NET + a3 + 62 * s], dev_act(S.act2, acc2[s]), y);
+#include "wm_net_layer23.inc"
 
             // ---- interior face values in physical units, relative to the first (:292, :301, :318)
             // faces [0; interior; top] (:220-224): the cell's upper face is its own row (row 31: the top flux), its lower face the row below

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .config import CONVECTIVE_ADJUSTMENT_NDE, FREE_CONVECTION, MATRIX_ARITHMETIC_NAMES, NDEConfig, matrix_arithmetic_id, to_c_config
 
-KERNEL_IDS = {"forward": 0, "adjoint": 1, "reduce": 2, "rhs": 3, "infer": 4, "dw1": 5, "convadj": 6, "adam": 7, "impldiff": 8, "fc_embed": 9, "flux_diag": 10}
+KERNEL_IDS = {"forward": 0, "adjoint": 1, "reduce": 2, "rhs": 3, "infer": 4, "dw1": 5, "convadj": 6, "adam": 7, "impldiff": 8, "fc_embed": 9, "flux_diag": 10, "wm_profile": 11}
 ENGINE_AUTO, ENGINE_TILE16, ENGINE_REGTILE, ENGINE_FC32 = 0, 1, 2, 3
 
 
@@ -1110,6 +1110,62 @@ class ColumnNDEEnsemble(ColumnNDE):
         _lib.check(fn(self._h, P(weights), P(u), P(v), P(T), P(top_flux), P(halo_bottom), P(halo_top), float(Lz), dtv, pr, ca, P(dz[0]), P(dz[1]), P(dz[2]),
                       P(s3[0]), P(s3[1]), P(s3[2]), P(f3[0]), P(f3[1]), P(f3[2]), n))
         return WmEnsembleEmbedded(dz, st, fc)
+
+    def profile(self, weights, sol, physics=None, flux: bool = True, Ri: bool = True, losses: bool = True) -> "EnsembleProfile":
+        """What `NDE_profile` (wind_mixing/src/training_postprocessing.jl:404-431, :310-317) evaluates on the saved states of a solve, for ALL K
+        models (`colnde_ensemble_profile`): uw, vw, wT [K, n_columns, n_save, Nz + 1] (`predict_flux` per state, scaled units; flux), the Richardson
+        number without ε, NaN on the two boundary faces as in the reference (Ri), and `loss_per_tstep` [K, n_columns, 6, n_save] (losses; needs
+        truth).  weights [K, n_params]; sol [K, n_columns, n_save, 3 Nz]: the states to diagnose — `forward`'s output or any other solve; nothing
+        is solved here.  physics [K, 5] overrides the closure constants for this call only (rows with nu0 = nu_minus = 0: the networks' own share
+        of the flux).  numpy arrays or torch device tensors (weights and sol of one kind)."""
+        c, K = self.cfg, self.n_models
+        check_wm_profile_arrays(K, self.n_params, self.n_columns, c.n_save, c.Nz, weights, sol, physics, flux, Ri, losses)
+        ph = None if physics is None else (ctypes.c_float * (5 * K))(*[float(x) for x in np.asarray(physics, dtype=np.float64).reshape(-1)])
+        fshape, lshape = (K, self.n_columns, c.n_save, c.Nz + 1), (K, self.n_columns, 6, c.n_save)
+        n_out = (3 if flux else 0) + (1 if Ri else 0)
+        if _is_torch(sol):
+            import torch
+            self._chk_dev(weights, (K, self.n_params))
+            self._chk_dev(sol, (K, self.n_columns, c.n_save, c.n_state))
+            faces = [torch.empty(fshape, dtype=torch.float32, device=sol.device) for _ in range(n_out)]
+            ls = torch.empty(lshape, dtype=torch.float32, device=sol.device) if losses else None
+            self.use_torch_stream()
+            P = lambda a: a.data_ptr() if a is not None else None
+            fn = self._L.colnde_ensemble_profile_dev
+        else:
+            weights, sol = _f32(weights, (K, self.n_params)), _f32(sol, (K, self.n_columns, c.n_save, c.n_state))
+            faces = [np.empty(fshape, np.float32) for _ in range(n_out)]
+            ls = np.empty(lshape, np.float32) if losses else None
+            P = _ptr
+            fn = self._L.colnde_ensemble_profile
+        f3 = faces[:3] if flux else [None] * 3
+        ri = faces[-1] if Ri else None
+        _lib.check(fn(self._h, P(weights), P(sol), ph, P(f3[0]), P(f3[1]), P(f3[2]), P(ri), P(ls)))
+        return EnsembleProfile(f3[0], f3[1], f3[2], ri, ls)
+
+
+class EnsembleProfile(NamedTuple):
+    """What `ColumnNDEEnsemble.profile` returns: uw, vw, wT, Ri [K, n_columns, n_save, Nz + 1] and losses [K, n_columns, 6, n_save]; None for
+    an output group that was not asked for."""
+    uw: object
+    vw: object
+    wT: object
+    Ri: object
+    losses: object
+
+
+def check_wm_profile_arrays(n_models: int, n_params: int, n_columns: int, n_save: int, Nz: int, weights, sol, physics=None, flux: bool = True,
+                            Ri: bool = True, losses: bool = True):
+    """Shape and argument rules of `ColumnNDEEnsemble.profile` (no GPU needed), raised before any library call."""
+    K = int(n_models)
+    check_ensemble_arrays(K, n_params, weights=weights, physics=None if physics is None else np.asarray(physics))
+    shape = (K, int(n_columns), int(n_save), 3 * int(Nz))
+    if tuple(sol.shape) != shape:
+        raise ValueError("sol: expected shape %s for %d models, got %s" % (shape, K, tuple(sol.shape)))
+    if _is_torch(sol) != _is_torch(weights):
+        raise ValueError("weights and sol must be of one kind: both torch device tensors or both NumPy arrays")
+    if not (flux or Ri or losses):
+        raise ValueError("no outputs: at least one of flux, Ri, losses must be asked for")
 
 
 CLOSURE_N_PARAMS = 5

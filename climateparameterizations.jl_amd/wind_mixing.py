@@ -324,6 +324,156 @@ def _is_torch_tensor(x):
     return type(x).__module__.startswith("torch")
 
 
+# ---- NDE_profile (wind_mixing/src/training_postprocessing.jl:250-632) --------------------------------------------------------------------------
+PROFILE_LOSS_KEYS = ("u", "v", "T", "∂u∂z", "∂v∂z", "∂T∂z")      # the reference's output keys are `<name>_losses`
+_MPP = "_modified_pacanowski_philander"
+
+
+def _local_richardson(cfg: NDEConfig, sol):
+    """`local_richardson` on `D_face * u, v, T` WITHOUT ε (training_postprocessing.jl:429-430), Float32: [.., 3 Nz] -> [.., Nz + 1]; the two boundary
+    faces are 0 / 0 = NaN, as in the reference."""
+    f = np.float32
+    Nz = cfg.Nz
+    x = np.asarray(sol, f)
+    g = []
+    for q in range(3):
+        d = np.zeros(x.shape[:-1] + (Nz + 1,), f)
+        d[..., 1:Nz] = (x[..., q * Nz + 1:(q + 1) * Nz] - x[..., q * Nz:(q + 1) * Nz - 1]) * f(Nz)
+        g.append(d)
+    B = f(f(f(cfg.H) * f(cfg.g)) * f(cfg.alpha)) * f(cfg.sigma[2])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (B * g[2]) / ((f(cfg.sigma[0]) * g[0]) ** 2 + (f(cfg.sigma[1]) * g[1]) ** 2)
+
+
+def _profile_block(cfg: NDEConfig, a, loss_scalings, suffix: str, flux_suffix=None):
+    """The keys one solve contributes (:400-423, :310-322, :515-517): a = dict(sol [n_sim, n_save, 3 Nz], uw, vw, wT, Ri [n_sim, n_save, Nz + 1],
+    losses [n_sim, 6, n_save]); every profile array comes out as the reference's Nz x Nt (faces: Nz + 1 x Nt) per simulation."""
+    f = np.float32
+    Nz = cfg.Nz
+    out = {}
+    T = lambda x: np.ascontiguousarray(np.swapaxes(np.asarray(x, f), -1, -2))
+    sol = np.asarray(a["sol"], f)
+    for q, name in enumerate(("u", "v", "T")):
+        out["test_%s%s" % (name, suffix)] = T(f(cfg.sigma[q]) * sol[..., q * Nz:(q + 1) * Nz] + f(cfg.mu[q]))
+    for q, name in enumerate(("uw", "vw", "wT")):
+        un = T(f(cfg.sigma[3 + q]) * np.asarray(a[name], f) + f(cfg.mu[3 + q]))          # inv(scalings.uw).(test_uw)
+        out["test_%s%s" % (name, flux_suffix if flux_suffix is not None else suffix)] = un - un[..., :1, :1]     # test_uw .- test_uw[1, 1]
+    out["test_Ri%s" % suffix] = T(a["Ri"])
+    ls = np.asarray(a["losses"], f)
+    sc = [f(s) for s in loss_scalings]
+    scaled = [sc[q] * ls[..., q, :] for q in range(6)]                                     # apply_loss_scalings, per time step
+    for q, name in enumerate(PROFILE_LOSS_KEYS):
+        out["%s_losses%s" % (name, suffix)] = scaled[q]
+    prof, grad = scaled[0] + scaled[1] + scaled[2], scaled[3] + scaled[4] + scaled[5]
+    out["losses%s" % suffix] = prof
+    out["loss%s" % suffix] = prof.mean(axis=-1)
+    out["losses%s_gradient" % suffix] = grad
+    out["loss%s_gradient" % suffix] = grad.mean(axis=-1)
+    return out
+
+
+def _assemble_NDE_profile(cfg: NDEConfig, arrays, truth, loss_scalings, arrays_mpp=None, NN_only=None, train_parameters=None, truth_fluxes=None):
+    """Everything `NDE_profile` does after its solves and flux evaluations (training_postprocessing.jl:392-599), for ONE member, on host arrays,
+    in Float32 as the reference: the unscaling, `test_uw .- test_uw[1, 1]` on the unscaled fluxes (:515-526), `apply_loss_scalings`, the sums and
+    the means.  arrays = dict(sol, uw, vw, wT, Ri, losses) of the member (scaled units; `ColumnNDEEnsemble.profile`'s rows plus the solution);
+    truth [n_sim, n_save, 3 Nz], scaled.  With the closure: arrays_mpp, the same of the closure-only solve (all-zero networks), NN_only = (uw, vw,
+    wT) evaluated with ν₀ = ν₋ = 0 on the member's solution, and train_parameters.  Every array carries a leading simulation axis in front of the
+    reference's layout (`NDE_profile` judges one simulation): test_u [n_sim, Nz, Nt], test_uw [n_sim, Nz + 1, Nt], u_losses [n_sim, Nt],
+    loss [n_sim].  The KPP keys are left out (OceanTurb is out of scope)."""
+    f = np.float32
+    Nz = cfg.Nz
+    truth = np.asarray(truth, f)
+    T = lambda x: np.ascontiguousarray(np.swapaxes(np.asarray(x, f), -1, -2))
+    dz = f(cfg.H) / f(Nz)
+    out = {"depth_profile": (-f(cfg.H) + dz * (np.arange(Nz, dtype=f) + f(0.5))),
+           "depth_flux": (-f(cfg.H) + dz * np.arange(Nz + 1, dtype=f)),
+           "t": np.asarray(cfg.save_times, f) * f(cfg.tau)}
+    for q, name in enumerate(("u", "v", "T")):
+        out["truth_" + name] = T(f(cfg.sigma[q]) * truth[..., q * Nz:(q + 1) * Nz] + f(cfg.mu[q]))
+    for q, name in enumerate(("uw", "vw", "wT")):
+        out["truth_" + name] = None if truth_fluxes is None else np.asarray(truth_fluxes[q], f)
+    out["truth_Ri"] = T(_local_richardson(cfg, truth))
+    out.update(_profile_block(cfg, arrays, loss_scalings, ""))
+    if cfg.modified_pacanowski_philander:
+        if arrays_mpp is None or NN_only is None:
+            raise ValueError("with the closure on, NDE_profile needs the closure-only arrays (arrays_mpp) and the NN-only fluxes (NN_only)")
+        out["train_parameters"] = dict(train_parameters or {}, loss_scalings=tuple(float(s) for s in loss_scalings))
+        out.update(_profile_block(cfg, arrays_mpp, loss_scalings, _MPP))
+        nn = _profile_block(cfg, dict(arrays, uw=NN_only[0], vw=NN_only[1], wT=NN_only[2]), loss_scalings, "", flux_suffix="_NN_only")
+        out.update({k: v for k, v in nn.items() if k.endswith("_NN_only")})
+    return out
+
+
+def ensemble_NDE_profile(problem: WindMixingNDE, weights, physics=None, loss_scalings=(1.0, 1.0, 1.0, 5e-3, 5e-3, 5e-3), solve: str = "ensemble",
+                         truth_fluxes=None) -> List[dict]:
+    """`NDE_profile` (wind_mixing/src/training_postprocessing.jl:250-632) for the K members of a sweep at once: one dict per member with the
+    reference's keys (see `_assemble_NDE_profile` for the layout; the KPP keys are left out).  weights [K, n_params]; physics [K, 5] = (nu0,
+    nu_minus, dRi, Ric, Pr) per member or None (the problem's constants); the problem's simulations are the test simulations and need truth.
+    Every flux, Richardson number and per-time-step loss comes from `colnde_ensemble_profile`: one call for the members, and with the closure one
+    with ν₀ = ν₋ = 0 (`*_NN_only`) and one with all-zero networks on the closure-only solve (`*_modified_pacanowski_philander`).
+    solve = "ensemble": the members are solved by `ColumnNDEEnsemble.forward`, the TRAINING right-hand side (`NDE`), all in one launch.
+    solve = "mutating": each member is solved on a single `inplace_variant` handle — `NDE!`, what the reference's `solve_NDE_mutating` (:302) runs —
+    and the result uploaded.  The two differ as `NDE` and `NDE!` do: `NDE!` has no ε in the Richardson number of the closure, and it carries the two
+    documented in-place quirks (ν_T switched on ∂u∂z under convective adjustment, the diurnal top flux without −scaling(0)); without diurnal forcing
+    and convective adjustment ε is the only difference.  The fluxes are `predict_flux`'s (the training conventions) in both modes, as in the reference."""
+    from .nde import ColumnNDEEnsemble, check_ensemble_arrays
+    if solve not in ("ensemble", "mutating"):
+        raise ValueError("solve must be 'ensemble' or 'mutating', got %r" % (solve,))
+    if problem.uvT_trains is None:
+        raise ValueError("NDE_profile compares with the truth trajectories: the problem has none")
+    cfg = problem.cfg
+    if solve == "mutating" and not cfg.modified_pacanowski_philander:
+        raise ValueError("solve='mutating' runs NDE!, which hard-wires the Pacanowski-Philander closure (training_postprocessing.jl:105-153): "
+                         "a configuration without the closure is solved with solve='ensemble'")
+    W = np.ascontiguousarray(weights, dtype=np.float32)
+    ph = None if physics is None else np.ascontiguousarray(physics, dtype=np.float32)
+    K = W.shape[0] if W.ndim == 2 else 0
+    check_ensemble_arrays(K, cfg.n_params, W, ph)
+    mpp = bool(cfg.modified_pacanowski_philander)
+    eng = problem.engine
+    x0, bcs, truth = problem.uvT0, problem.BCs, np.ascontiguousarray(problem.uvT_trains, dtype=np.float32)
+    rows = ph if ph is not None else np.tile(np.array([[cfg.nu0, cfg.nu_minus, cfg.dRi, cfg.Ric, cfg.Pr]], np.float32), (K, 1))
+    Z = np.zeros_like(W)
+
+    def solve_mutating(Wm):
+        sols = []
+        for k in range(K):
+            c = cfg.with_(inplace_variant=True, nu0=float(rows[k, 0]), nu_minus=float(rows[k, 1]), dRi=float(rows[k, 2]), Ric=float(rows[k, 3]),
+                          Pr=float(rows[k, 4]))
+            with ColumnNDE(c, problem.n_simulations, device=eng.device, matrix_arithmetic=eng.matrix_arithmetic) as one:
+                one.set_problem(x0, bcs, truth)
+                sols.append(one.forward(Wm[k]))
+        return np.stack(sols)
+
+    with ColumnNDEEnsemble(cfg, problem.n_simulations, K, physics=ph if mpp else None, device=eng.device, matrix_arithmetic=eng.matrix_arithmetic) as ens:
+        ens.set_problem(x0, bcs, truth)
+        run = (lambda Wm: ens.forward(Wm)) if solve == "ensemble" else solve_mutating
+        sol = run(W)
+        main = ens.profile(W, sol)
+        if mpp:
+            nn_rows = rows.copy()
+            nn_rows[:, :2] = 0.0                                          # constants_NN_only (:286)
+            nn = ens.profile(W, sol, physics=nn_rows, Ri=False, losses=False)
+            sol0 = run(Z)
+            zero = ens.profile(Z, sol0)
+    out = []
+    for k in range(K):
+        a = dict(sol=sol[k], uw=main.uw[k], vw=main.vw[k], wT=main.wT[k], Ri=main.Ri[k], losses=main.losses[k])
+        if mpp:
+            a0 = dict(sol=sol0[k], uw=zero.uw[k], vw=zero.vw[k], wT=zero.wT[k], Ri=zero.Ri[k], losses=zero.losses[k])
+            tp = dict(zip(MPP_KEYS, (float(x) for x in rows[k])))
+            out.append(_assemble_NDE_profile(cfg, a, truth, loss_scalings, a0, (nn.uw[k], nn.vw[k], nn.wT[k]), tp, truth_fluxes))
+        else:
+            out.append(_assemble_NDE_profile(cfg, a, truth, loss_scalings, truth_fluxes=truth_fluxes))
+    return out
+
+
+def NDE_profile(problem: WindMixingNDE, weights, loss_scalings=(1.0, 1.0, 1.0, 5e-3, 5e-3, 5e-3), truth_fluxes=None) -> dict:
+    """`NDE_profile` of one network triple: `ensemble_NDE_profile` with K = 1 and the reference's own solve (`solve_NDE_mutating`, which needs the
+    closure: `NDE!` hard-wires it)."""
+    return ensemble_NDE_profile(problem, np.asarray(weights, np.float32)[None, :], None, loss_scalings, solve="mutating", truth_fluxes=truth_fluxes)[0]
+
+
 def train_NN(engine: ColumnNDE, NN_type: str, weights, profiles, BCs, fluxes, optimizers: Sequence[ADAM], train_epochs: Sequence[int],
              gradient_scaling: float = 1e-4, order=None, cb: Optional[Callable] = None):
     """`train_NN(NN, 𝒟train, optimizers, train_epochs, FILE_PATH, NN_type; …)` — wind_mixing/src/NN_training.jl:207-249: for each

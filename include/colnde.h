@@ -496,7 +496,7 @@ int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const floa
  * It is accepted by colnde_ensemble_forward_dev, _loss_dev, _loss_grad_dev, _loss_grad and _adam_step_dev with their layouts ([K][n_params] weights,
  * [K][n_params + 8] result rows), and by the handle-level calls a wind-mixing ensemble accepts (describe adds models=K, the bytes per model and
  * time_segments).  Row k of every result holds the bits a colnde_create handle computes for model k's weights, under either matrix arithmetic (and the same
- * COLNDE_FC_SEG: the segment count orders the gradient's sums).  colnde_ensemble_set_physics (no constants to vary), colnde_ensemble_wm_embedded and every
+ * COLNDE_FC_SEG: the segment count orders the gradient's sums).  colnde_ensemble_set_physics (no constants to vary), colnde_ensemble_wm_embedded, colnde_ensemble_profile and every
  * single-model call refuse it; colnde_ensemble_fc_embedded (below) takes its K networks into the embedding.
  * Refused at creation, before any device work, each with its reason: a wind-mixing model, another network shape or Nz, an engine other than AUTO or FC32,
  * substeps = 0, substeps < colnde_min_substeps, n_models outside 1..65535, more than 4,096 columns per model (above it a single handle runs 32-column
@@ -554,6 +554,32 @@ int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weights, const fl
         const float* top_flux, const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params,
         int convective_adjustment, float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out,
         float* uw, float* vw, float* wT, int n_columns);
+
+/* Judging the K members of a wind-mixing sweep — what NDE_profile (wind_mixing/src/training_postprocessing.jl:250-632) evaluates on the saved states of a solve,
+ * for all K models at once.  The call solves nothing: d_sol [K][n_col][n_save][96] holds the states to diagnose in scaled units — the output of
+ * colnde_ensemble_forward_dev, or of any other solve (the reference's solve_NDE_mutating :302: inplace_variant single handles, uploaded).
+ *   d_uw, d_vw, d_wT [K][n_col][n_save][33], scaled units: predict_flux (NDE_training.jl:83-147) on state n of simulation c of model k (test_uw, test_vw, test_wT,
+ *       :404-423) with the simulation's boundary fluxes from colnde_set_problem and, in the diurnal case, the top temperature flux at the frame's time — the training
+ *       RHS in its three branches (the Pacanowski-Philander closure with eps on the gradients; convective adjustment; neither).  One launch of wm_profile_ens_kernel
+ *       (f32 matrix pipe under either matrix_arithmetic; colnde_describe: wm_profile=f32).
+ *   d_Ri [K][n_col][n_save][33]: local_richardson on D_face u, v, T WITHOUT eps, as :430 calls it.  D_face's first and last rows are zero, so the two boundary faces
+ *       are 0 / 0 = NaN in the reference; they are NaN here (not repaired).
+ *   d_losses [K][n_col][6][n_save]: loss_per_tstep (:310-317) of each member against the shared truth: row k holds the bits colnde_loss_per_tstep_dev writes on a
+ *       single handle for the same solution.
+ *   physics: HOST memory [K][5] = {nu0, nu_minus, dRi, Ric, Pr} per model for THIS call only, or NULL: the handle's.  Rows with nu0 = nu_minus = 0 give the networks'
+ *       own share of the flux (constants_NN_only, :286, :474-495).  Nothing is integrated, so there is no stability check; dRi > 0, Pr > 0 and finiteness are checked.
+ *       The closure-only set (:326-352, :433-472) is the same call with all-zero weights on the closure-only solve.
+ * The flux outputs are all three given or all three NULL; d_Ri and d_losses may each be NULL; at least one output group is required; d_losses needs truth.
+ * Accepts a wind-mixing ensemble handle, K >= 1.  Refused before any launch, each with its reason in colnde_last_error: free-convection and conv ensembles, closure and
+ * single-model handles, null handle / weights / sol, a half-given flux group, no outputs, d_losses without truth, base pointers that are not 16-byte aligned (_dev
+ * only; a model's rows need no alignment of their own), a call before colnde_set_problem, a physics array without the closure.  A model whose states are not finite
+ * gets non-finite rows; the other models' rows are unaffected.  The flux / Ri launch is timed under colnde_kernel_time slot 11 (the losses under slot 2).
+ * COLNDE_WM_PROFILE_GRID=<n> (a test override) caps the workgroups of this launch and of no other. */
+int colnde_ensemble_profile_dev(colnde_handle* h, const float* d_weights, const float* d_sol, const float* physics, float* d_uw, float* d_vw, float* d_wT,
+        float* d_Ri, float* d_losses);
+/* the same with host arrays (no alignment rule); synchronises the stream */
+int colnde_ensemble_profile(colnde_handle* h, const float* weights, const float* sol, const float* physics, float* uw, float* vw, float* wT,
+        float* Ri, float* losses);
 
 /* ---- the free-convection driver's --conv network (train_free_convection_nde.jl:50-53, 110-122) ----------------------------------------------------------
  * With --conv c > 1 the reference trains
@@ -669,7 +695,7 @@ int colnde_closure_loss_grad(colnde_handle* h, const float* params, const float 
  * which: 0 = forward solve kernel, 1 = adjoint kernel, 2 = gradient reduce, 3 = rhs, 4 = inference,
  * 5 = streaming dW1 GEMM (regtile engine only), 6 = convective adjustment, 7 = ADAM step, 8 = implicit diffusion,
  * 9 = free-convection embedded step / diagnose_wT (colnde_ensemble_fc_embedded too), 10 = wind-mixing flux diagnoses (colnde_wm_diagnose_flux, colnde_wm_embedded_step_flux,
- * colnde_mpp_diagnose_flux, colnde_ensemble_wm_embedded).
+ * colnde_mpp_diagnose_flux, colnde_ensemble_wm_embedded), 11 = the flux / Richardson-number launch of colnde_ensemble_profile.
  * Returns accumulated milliseconds and launch count since the last reset (synchronises the stream). */
 int colnde_set_profiling(colnde_handle* h, int enabled);
 int colnde_kernel_time(colnde_handle* h, int which, float* ms_total, int* n_launches);

@@ -440,6 +440,22 @@ function ensemble_progress_neural_network_flux(h::Handle, θ::Matrix{Float32}, u
     (uw, vw, wT)
 end
 
+"What NDE_profile (wind_mixing/src/training_postprocessing.jl:404-431, :310-317) evaluates on the saved states of a solve, for ALL K members of a
+wind-mixing ensemble handle at once (colnde_ensemble_profile): θ (n_params, K); sol (3Nz, n_save, n_columns, K), scaled units — the states to
+diagnose, nothing is solved; physics (5, K) = (ν₀, ν₋, ΔRi, Riᶜ, Pr) per member for this call only (ν₀ = ν₋ = 0: the *_NN_only fluxes), or nothing:
+the handle's.  Returns (uw, vw, wT, Ri), each (Nz+1, n_save, n_columns, K) — predict_flux per state in scaled units and local_richardson without ϵ,
+NaN on the two boundary faces as in the reference — and losses (n_save, 6, n_columns, K), loss_per_tstep against the truth of set_problem!."
+function ensemble_NDE_profile_arrays(h::Handle, θ::Matrix{Float32}, sol::Array{Float32,4}; physics=nothing)
+    pp = physics === nothing ? C_NULL : pointer(physics)
+    Nz = size(sol, 1) ÷ 3
+    uw, vw, wT, Ri = (Array{Float32,4}(undef, Nz + 1, size(sol, 2), size(sol, 3), size(sol, 4)) for _ in 1:4)
+    losses = Array{Float32,4}(undef, size(sol, 2), 6, size(sol, 3), size(sol, 4))
+    GC.@preserve physics check(ccall((:colnde_ensemble_profile, libcolnde), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+        h.ptr, θ, sol, pp, uw, vw, wT, Ri, losses))
+    (uw, vw, wT, Ri, losses)
+end
+
 "progress_neural_network (free_convection/src/oceananigans_nn.jl:153-165) and diagnose_wT_NN (:100-118) for ALL K networks of a free-convection
 ensemble handle — plain or --conv; a single handle, plain or conv, is K = 1 — in one launch (colnde_ensemble_fc_embedded): θ (n_params, K), or
 nothing: the operand images the previous call on this handle packed; T and ∂z_wT_NN (Nz, n_columns, K), every member on its own state, adjusted in
