@@ -104,6 +104,8 @@ SYMBOLS = [
     ("colnde_ensemble_causal_penalty_dev", ctypes.c_int, [_V, _V, _V, _V]),
     ("colnde_ensemble_pretrain_flux_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_int, _V, ctypes.c_int, _V] + [ctypes.c_float] * 3 +
      [ctypes.POINTER(ctypes.c_double), ctypes.c_int, _F]),
+    ("colnde_ensemble_pretrain_wm_flux_dev", ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V, _V, _V, _V, ctypes.c_int, ctypes.c_float, _V] +
+     [ctypes.c_float] * 3 + [ctypes.POINTER(ctypes.c_double), ctypes.c_int, _F]),
     ("colnde_closure_min_substeps", ctypes.c_int, [_V, _F]),
     ("colnde_create_closure", ctypes.c_int, [_V, ctypes.c_int, ctypes.POINTER(_V)]),
     ("colnde_closure_forward_dev", ctypes.c_int, [_V, _V, _V]),

@@ -420,6 +420,7 @@ extern "C" int colnde_create(const colnde_config* cfg, colnde_handle** out) {
         hipError_t e = set_kernel_attributes(lds_cap);
         if (e == hipSuccess) e = dw_set_kernel_attributes(lds_cap);
         if (e == hipSuccess) e = fcp_set_kernel_attributes(lds_cap);
+        if (e == hipSuccess) e = wmp_set_kernel_attributes(lds_cap);
         if (e == hipSuccess) e = rt_set_attributes();
         if (e == hipSuccess) e = rt_set_attributes_split();
         if (e != hipSuccess) { colnde_destroy(h); return fail("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); }

@@ -614,3 +614,45 @@ extern "C" int colnde_ensemble_pretrain_flux_dev(colnde_handle* h, float* d_thet
     if (update && adam) { beta_t[0] = bt[0]; beta_t[1] = bt[1]; }
     return 0;
 }
+
+// ---- train_NN for the K x 3 flux networks of a wind-mixing ensemble in one launch (engine_wm_pretrain.hip; wind_mixing/src/NN_training.jl:207-249) ----
+// Semantics of colnde_pretrain_flux_dev per (model, net), with model k's closure constants (h->d_phys): the K x 3 sums of the per-sample losses come
+// back in one copy and the means are formed here with the single call's expression.
+extern "C" int colnde_ensemble_pretrain_wm_flux_dev(colnde_handle* h, int nets, float* d_theta, float* d_m, float* d_v, const float* d_profiles,
+                                                    const float* d_bcs, const float* d_flux, const int32_t* d_order, int n_samples, float gradient_scaling,
+                                                    const float* d_eta, float beta1, float beta2, float eps, double beta_t[2], int update, float* mean_loss) {
+    if (!h) return fail("%s: null handle", __func__);
+    if (h->closure) return fail("%s takes the weight vectors of a wind-mixing ensemble, but this is a closure handle (no networks)", __func__);
+    if (!h->ensemble)
+        return fail("%s takes the handles of colnde_create_ensemble (K = 1 for one model): this is a single-model handle "
+                    "(colnde_pretrain_flux_dev pre-trains one net of a single model)", __func__);
+    if (h->use_fc)
+        return fail("%s covers the wind-mixing ensembles: this ensemble holds free-convection networks (colnde_ensemble_pretrain_flux_dev pre-trains "
+                    "those on T -> wT)", __func__);
+    if (!d_theta || !d_profiles || !d_bcs || !d_flux || !beta_t || !mean_loss) return fail("%s: null pointer argument", __func__);
+    if (nets < 1 || nets > 7) return fail("%s: nets = %d outside 1..7 (bit 0 = uw, bit 1 = vw, bit 2 = wT)", __func__, nets);
+    if (update && !d_eta) return fail("%s: the rates d_eta [K][3] are needed when update != 0", __func__);
+    if (update && (!d_m || !d_v)) return fail("%s: the ADAM moments are needed when update != 0", __func__);
+    if (!(beta_t[0] < 1.0 && beta_t[1] < 1.0)) return fail("%s: running powers beta^t must be < 1", __func__);
+    if (n_samples < 1) return fail("%s: n_samples must be >= 1", __func__);
+    if (wm_pretrain_lds_bytes(h->m, update) > PRETRAIN_LDS_CAP)
+        return fail("%s: network too large, a workgroup needs %zu B of LDS (> %zu)", __func__, wm_pretrain_lds_bytes(h->m, update), PRETRAIN_LDS_CAP);
+    const int K = h->n_models, C = 3 * K;
+    HIPCHK(hipSetDevice(h->device));
+    DevScratch sc(h->stream);
+    const size_t loss_bytes = ((size_t)C * sizeof(float) + 15) / 16 * 16;
+    HIPCHK(sc.alloc(loss_bytes + 2 * sizeof(double)));
+    float* d_loss = sc.p;
+    double* d_bt = reinterpret_cast<double*>(reinterpret_cast<char*>(d_loss) + loss_bytes);
+    hipError_t e = launch_wm_pretrain_ens(h->m, K, nets, h->d_phys, d_theta, update ? d_m : nullptr, update ? d_v : nullptr, d_profiles, d_bcs, d_flux, d_order,
+                                          n_samples, gradient_scaling, d_eta, beta1, beta2, eps, beta_t[0], beta_t[1], update, d_loss, d_bt, h->stream);
+    std::vector<float> loss((size_t)C, 0.0f);
+    double bt[2] = {beta_t[0], beta_t[1]};
+    if (e == hipSuccess) e = hipMemcpyAsync(loss.data(), d_loss, (size_t)C * sizeof(float), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && update) e = hipMemcpyAsync(bt, d_bt, sizeof(bt), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail("%s failed: %s", __func__, hipGetErrorString(e));
+    for (int c = 0; c < C; c++) mean_loss[c] = ((nets >> (c % 3)) & 1) ? loss[c] / (float)n_samples : 0.0f;
+    if (update) { beta_t[0] = bt[0]; beta_t[1] = bt[1]; }
+    return 0;
+}

@@ -22,6 +22,7 @@
 #include "engine_wm_profile.h"
 #include "engine_fc_embed.h"
 #include "engine_fc_pretrain.h"
+#include "engine_wm_pretrain.h"
 
 #pragma GCC visibility push(hidden)
 

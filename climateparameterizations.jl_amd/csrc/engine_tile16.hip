@@ -506,26 +506,7 @@ __device__ __forceinline__ float wm_top_flux(const DevModel& m, const float* bc,
     return (wq - m.mu_wT) / m.sig_wT;
 }
 
-struct FaceGrad { float gu, gv, gT, S2, Ri; };
-
-// tanh(y) = 1 - 2/(1 + e^{2y}) on the fast exp / reciprocal units (|rel err| ~ 1e-6)
-__device__ __forceinline__ float fast_tanh(float y) {
-    const float e = __expf(2.0f * fminf(fmaxf(y, -15.0f), 15.0f));
-    return 1.0f - fast_div(2.0f, 1.0f + e);
-}
-
-__device__ __forceinline__ FaceGrad wm_face(const DevModel& m, const float* x, int f, float eps) {
-    const int Nz = m.Nz;
-    const bool in = f >= 1 && f < Nz;
-    FaceGrad g;
-    g.gu = in ? (x[f] - x[f - 1]) * (float)Nz : 0.0f;
-    g.gv = in ? (x[Nz + f] - x[Nz + f - 1]) * (float)Nz : 0.0f;
-    g.gT = in ? (x[2 * Nz + f] - x[2 * Nz + f - 1]) * (float)Nz : 0.0f;
-    const float a1 = m.sig_u * (g.gu + eps), a2 = m.sig_v * (g.gv + eps);
-    g.S2 = a1 * a1 + a2 * a2;
-    g.Ri = fast_div(m.B * (g.gT + eps), g.S2);   // local_richardson, NDE_training.jl:46-52
-    return g;
-}
+// (FaceGrad, fast_tanh and wm_face: pretrain_sample.h, shared with wm_pretrain_ens_kernel)
 
 // k[c][:] = RHS(xs[c][:]).  A holds the nets' activations (last layer = interior fluxes).  Ends with a barrier.
 __device__ void physics_forward(const DevModel& m, const float* xs, const float* A, float* F, float* Ri_l,
@@ -786,23 +767,7 @@ pretrain_kernel(DevModel m, int flux_type, float* __restrict__ theta, float* __r
         // weight-independent part of the face flux: boundary faces and the diffusive / adjustment flux of the state
         for (int f = tid; f < nf; f += nth) {
             const float* bc = BC + (size_t)idx * m.n_bc;
-            float c = 0.0f;
-            if (wm) {
-                const float bb = bc[2 * k], bt = bc[2 * k + 1];
-                const bool in = f >= 1 && f < Nz;
-                if (!in) c = m.zero_w ? (f == 0 ? bb : bt) - m.s0[k] : (f == 0 ? bb : bt);      // (MPP's end faces: NN_training.jl:62-66)
-                else if (m.mpp) {
-                    const FaceGrad g = wm_face(m, a0, f, m.eps);
-                    const float nu = m.nu0 + m.nu_minus * (1.0f - fast_tanh((g.Ri - m.Ric) * m.inv_dRi)) * 0.5f;
-                    c = -m.cs[k] * (k == 2 ? nu * m.inv_Pr : nu) * (k == 0 ? g.gu : (k == 1 ? g.gv : g.gT));
-                } else if (m.ca && k == 2) {
-                    const float gT = (a0[2 * Nz + f] - a0[2 * Nz + f - 1]) * (float)Nz;
-                    c = -m.cs[2] * m.kappa * fminf(0.0f, gT);
-                }
-            } else {
-                c = pt_bc_face(bc, f, Nz);
-            }
-            cf[f] = c;
+            cf[f] = wm ? pt_wm_face_const(m, a0, bc, k, f, m.nu0, m.nu_minus, m.Ric, m.inv_dRi, m.inv_Pr) : pt_bc_face(bc, f, Nz);
         }
         // the per-sample chain of pretrain_sample.h: forward, loss and cotangent, backward, Flux ADAM on every parameter of this net
         const float* th = theta + (wm ? k * m.net_size : 0);

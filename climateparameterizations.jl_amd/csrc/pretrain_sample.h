@@ -1,6 +1,7 @@
-// pretrain_sample.h — the per-sample body of flux-MLP pre-training, shared by pretrain_kernel (engine_tile16.hip: one model, one workgroup) and
-// fc_pretrain_ens_kernel (engine_fc_pretrain.hip: one workgroup per model).  Both kernels instantiate THESE functions on the same LDS carving, so a
-// model's chain of updates is the same sequence of float operations in either: row k of an ensemble pass holds the bits of the single call.
+// pretrain_sample.h — the per-sample body of flux-MLP pre-training, shared by pretrain_kernel (engine_tile16.hip: one model, one workgroup),
+// fc_pretrain_ens_kernel (engine_fc_pretrain.hip: one workgroup per model) and wm_pretrain_ens_kernel (engine_wm_pretrain.hip: one workgroup per
+// model and flux net).  The kernels instantiate THESE functions on the same LDS carving, so a model's chain of updates is the same sequence of float
+// operations in each: row k of an ensemble pass holds the bits of the single call.
 // Nothing here spreads a dot product over lanes: an output (forward), an input (backward) or a parameter (update) has one owning thread that walks its
 // sum in index order.
 #pragma once
@@ -33,6 +34,49 @@ __device__ __forceinline__ void pt_load(const DevModel& m, const PtLds& s, const
 
 // T-only models: the weight-independent part of the face flux is the two boundary faces, [bottom; NN(T); top]
 __device__ __forceinline__ float pt_bc_face(const float* bc, int f, int Nz) { return f == 0 ? bc[0] : (f == Nz ? bc[1] : 0.0f); }
+
+struct FaceGrad { float gu, gv, gT, S2, Ri; };
+
+// tanh(y) = 1 - 2/(1 + e^{2y}) on the fast exp / reciprocal units (|rel err| ~ 1e-6)
+__device__ __forceinline__ float fast_tanh(float y) {
+    const float e = __expf(2.0f * fminf(fmaxf(y, -15.0f), 15.0f));
+    return 1.0f - fast_div(2.0f, 1.0f + e);
+}
+
+__device__ __forceinline__ FaceGrad wm_face(const DevModel& m, const float* x, int f, float eps) {
+    const int Nz = m.Nz;
+    const bool in = f >= 1 && f < Nz;
+    FaceGrad g;
+    g.gu = in ? (x[f] - x[f - 1]) * (float)Nz : 0.0f;
+    g.gv = in ? (x[Nz + f] - x[Nz + f - 1]) * (float)Nz : 0.0f;
+    g.gT = in ? (x[2 * Nz + f] - x[2 * Nz + f - 1]) * (float)Nz : 0.0f;
+    const float a1 = m.sig_u * (g.gu + eps), a2 = m.sig_v * (g.gv + eps);
+    g.S2 = a1 * a1 + a2 * a2;
+    g.Ri = fast_div(m.B * (g.gT + eps), g.S2);   // local_richardson, NDE_training.jl:46-52
+    return g;
+}
+
+// Wind-mixing models: the weight-independent part of face f of flux k (0 = uw, 1 = vw, 2 = wT) for the profile a0 and the sample's six boundary
+// fluxes bc — the boundary faces (MPP's end faces under zero_weights: NN_training.jl:62-66), the Richardson-number closure, or the
+// convective-adjustment term of wT.  The five closure constants are arguments: pretrain_kernel passes the handle's (DevModel), wm_pretrain_ens_kernel
+// those of its model (RtPhys), and both evaluate this one text.
+__device__ __forceinline__ float pt_wm_face_const(const DevModel& m, const float* a0, const float* bc, int k, int f, float nu0, float nu_minus, float Ric,
+                                                  float inv_dRi, float inv_Pr) {
+    const int Nz = m.Nz;
+    float c = 0.0f;
+    const float bb = bc[2 * k], bt = bc[2 * k + 1];
+    const bool in = f >= 1 && f < Nz;
+    if (!in) c = m.zero_w ? (f == 0 ? bb : bt) - m.s0[k] : (f == 0 ? bb : bt);
+    else if (m.mpp) {
+        const FaceGrad g = wm_face(m, a0, f, m.eps);
+        const float nu = nu0 + nu_minus * (1.0f - fast_tanh((g.Ri - Ric) * inv_dRi)) * 0.5f;
+        c = -m.cs[k] * (k == 2 ? nu * inv_Pr : nu) * (k == 0 ? g.gu : (k == 1 ? g.gv : g.gT));
+    } else if (m.ca && k == 2) {
+        const float gT = (a0[2 * Nz + f] - a0[2 * Nz + f - 1]) * (float)Nz;
+        c = -m.cs[2] * m.kappa * fminf(0.0f, gT);
+    }
+    return c;
+}
 
 // forward through the dense layers of net `th`; ain0: the input of layer 0 (the profile, or the filter's activations)
 __device__ __forceinline__ void pt_forward(const DevModel& m, const PtLds& s, const float* th, const float* ain0, int tid, int nth) {

@@ -975,6 +975,55 @@ def check_wm_ens_embed_arrays(n_models: int, n_params: int, Nz: int, weights, st
     return n
 
 
+WM_PRETRAIN_NETS = {"uw": 1, "vw": 2, "wT": 4}      # bits of `nets` of colnde_ensemble_pretrain_wm_flux_dev
+
+
+def wm_pretrain_nets_mask(nets) -> int:
+    """The bit mask of `nets`: an int in 1..7 as it is, or names out of ("uw", "vw", "wT")."""
+    if isinstance(nets, (int, np.integer)) and not isinstance(nets, bool):
+        mask = int(nets)
+    else:
+        names = (nets,) if isinstance(nets, str) else tuple(nets) if isinstance(nets, (tuple, list, set, frozenset)) else (None,)
+        if not all(isinstance(nm, str) and nm in WM_PRETRAIN_NETS for nm in names):
+            raise ValueError("nets: names out of ('uw', 'vw', 'wT') or a bit mask in 1..7, got %r" % (nets,))
+        mask = sum(WM_PRETRAIN_NETS[nm] for nm in set(names))
+    if not 1 <= mask <= 7:
+        raise ValueError("nets: names out of ('uw', 'vw', 'wT') or a bit mask in 1..7, got %r" % (nets,))
+    return mask
+
+
+def check_wm_pretrain_arrays(cfg: NDEConfig, n_models: int, theta, profiles, bcs, fluxes, order=None, etas=None, m=None, v=None):
+    """Shape, dtype and order-range rules of `ColumnNDEEnsemble.pretrain_fluxes` (no GPU needed; NumPy arrays or torch tensors), raised before any
+    handle is touched: theta, m, v [K, n_params] float32; profiles [n, 3Nz], bcs [n, 6], fluxes [3, n, Nz + 1] (uw, vw, wT; scaled) float32 with
+    n >= 1; order [K, 3, n] int32 with every entry in 0..n-1 (an index may repeat), or None; etas [K, 3] float32 or None.  Returns n."""
+    K = int(n_models)
+    if K < 1:
+        raise ValueError("n_models must be >= 1, got %d" % K)
+    if cfg.model != 0 or cfg.n_nets != 3:
+        raise ValueError("the flux pre-training of an ensemble's three nets takes a wind-mixing configuration (free-convection ensembles: check_fc_pretrain_arrays)")
+    P, Nz = cfg.n_params, cfg.Nz
+    if len(tuple(profiles.shape)) != 2 or int(profiles.shape[0]) < 1:
+        raise ValueError("profiles: expected shape [n, %d] with n >= 1, got %s" % (3 * Nz, tuple(profiles.shape)))
+    n = int(profiles.shape[0])
+    for name, a, shape in (("theta", theta, (K, P)), ("m", m, (K, P)), ("v", v, (K, P)), ("profiles", profiles, (n, 3 * Nz)), ("bcs", bcs, (n, 6)),
+                           ("fluxes", fluxes, (3, n, Nz + 1)), ("etas", etas, (K, 3))):
+        if a is None:
+            continue
+        if tuple(a.shape) != shape:
+            raise ValueError("%s: expected shape %s for %d models and %d samples, got %s" % (name, shape, K, n, tuple(a.shape)))
+        if _dtype_name(a) != "float32":
+            raise ValueError("%s: expected float32, got %s" % (name, _dtype_name(a)))
+    if order is not None:
+        if tuple(order.shape) != (K, 3, n):
+            raise ValueError("order: expected shape %s (one row per model and net), got %s" % ((K, 3, n), tuple(order.shape)))
+        if _dtype_name(order) != "int32":
+            raise ValueError("order: expected int32, got %s" % _dtype_name(order))
+        lo, hi = int(order.min()), int(order.max())
+        if lo < 0 or hi >= n:
+            raise ValueError("order: entries must lie in 0..%d, got %d..%d" % (n - 1, lo, hi))
+    return n
+
+
 class ColumnNDEEnsemble(ColumnNDE):
     """K models of ONE architecture on the same columns (`colnde_create_ensemble`): own weights, own Pacanowski-Philander constants, own ADAM rate —
     the sweep of wind_mixing/train_NDE_args.jl (one model per process there) with every kernel launched once for all K models.
@@ -1067,6 +1116,39 @@ class ColumnNDEEnsemble(ColumnNDE):
         _lib.check(self._L.colnde_ensemble_adam_step_dev(self._h, weights.data_ptr(), result.data_ptr(), m.data_ptr(), v.data_ptr(), etas.data_ptr(),
                                                          float(beta[0]), float(beta[1]), float(eps), float(bt[0]), float(bt[1])))
         return weights
+
+    def pretrain_fluxes(self, theta, m, v, profiles, bcs, fluxes, order, gradient_scaling: float, etas, nets=("uw", "vw", "wT"), beta=(0.9, 0.999),
+                        eps: float = 1e-8, beta_t=None, update: bool = True):
+        """`colnde_ensemble_pretrain_wm_flux_dev`: one `Flux.train!` pass of `train_NN` (wind_mixing/src/NN_training.jl:207-249) for the chosen flux
+        nets of all K models in one launch, each model under its own closure constants, over device tensors: theta, m, v [K, n_params] (the chosen
+        nets' blocks updated in place), profiles [n, 3Nz], bcs [n, 6], fluxes [3, n, Nz + 1] (uw, vw, wT), order [K, 3, n] int32 or None (0..n-1 for
+        every chain), etas [K, 3].  nets: names out of ("uw", "vw", "wT") or a bit mask in 1..7.  beta_t: a list [beta1^t, beta2^t] advanced in place
+        by n steps (with update; None: a fresh optimiser's).  update=False: nothing is written (m, v, etas may be None), the mean loss at the given
+        weights.  Returns the mean losses [K, 3] (NumPy; 0 for a net not chosen): with update, the mean of each sample's loss just before its own update."""
+        mask = wm_pretrain_nets_mask(nets)
+        if update and etas is None:
+            raise ValueError("the rates etas [K, 3] are needed when update=True")
+        if update and (m is None or v is None):
+            raise ValueError("the ADAM moments m and v are needed when update=True")
+        n = check_wm_pretrain_arrays(self.cfg, self.n_models, theta, profiles, bcs, fluxes, order, etas, m, v)
+        K, P, Nz = self.n_models, self.n_params, self.cfg.Nz
+        for t, shape in ((theta, (K, P)), (m, (K, P)), (v, (K, P)), (profiles, (n, 3 * Nz)), (bcs, (n, 6)), (fluxes, (3, n, Nz + 1)), (etas, (K, 3))):
+            if t is not None:
+                self._chk_dev(t, shape)
+        if order is not None and not (order.is_cuda and order.is_contiguous() and order.device.index == self.device):
+            raise ValueError("order must be a contiguous int32 tensor on the handle's device")
+        if beta_t is None:
+            beta_t = [float(beta[0]), float(beta[1])]
+        P_ = lambda a: a.data_ptr() if a is not None else None
+        self.use_torch_stream()
+        bt = (ctypes.c_double * 2)(float(beta_t[0]), float(beta_t[1]))
+        loss = (ctypes.c_float * (3 * K))()
+        _lib.check(self._L.colnde_ensemble_pretrain_wm_flux_dev(self._h, mask, P_(theta), P_(m), P_(v), P_(profiles), P_(bcs), P_(fluxes), P_(order), n,
+                                                                float(gradient_scaling), P_(etas), float(beta[0]), float(beta[1]), float(eps), bt,
+                                                                int(bool(update)), loss))
+        if update:
+            beta_t[0], beta_t[1] = bt[0], bt[1]
+        return np.array(loss, dtype=np.float32).reshape(K, 3)
 
 
     def wm_embedded(self, weights, u, v, T, top_flux, Lz: float, dt=None, params=None, convective_adjustment: bool = False, halo_bottom=None,

@@ -503,6 +503,60 @@ def train_NN(engine: ColumnNDE, NN_type: str, weights, profiles, BCs, fluxes, op
     return theta.cpu().numpy(), hist
 
 
+def train_NN_ensemble(ens, weights, profiles, BCs, fluxes, optimizers: Sequence[ADAM], train_epochs: Sequence[int], etas=None,
+                      gradient_scaling: float = 1e-4, seeds=None, nets=("uw", "vw", "wT"), cb: Optional[Callable] = None):
+    """The loop of `train_NN` (wind_mixing/src/NN_training.jl:207-249) for the chosen flux nets of all K models of `ens` (a `ColumnNDEEnsemble` — the
+    handle that then trains the NDE sweep) at once: per optimiser and epoch ONE `pretrain_fluxes` launch (one ADAM update per sample and chain, model
+    k's nets fitted under model k's closure constants) and one update=False launch for `total_loss(training_data)`, which `cb(total_loss [K, 3],
+    weights)` receives.  Each (model, net) walks its own fresh permutation per pass (`free_convection.pretrain_orders`, one seed per chain; seeds
+    None: 0..3K-1, else [K, 3]); the loss over the data is summed in that pass's order, as `train_NN` does.
+    weights [K, n_params]; profiles [n, 3Nz], BCs [n, 6], fluxes [3, n, Nz + 1] = 𝒟.uw / vw / wT.scaled.  optimizers: flux_compat.ADAMs, read for
+    rate, beta and eps only — moments and running powers start afresh with each and carry across its epochs.  etas: None (every chain takes each
+    optimiser's rate), [S, K] per-model or [S, K, 3] per-chain rates for the S optimisers.
+    Returns (weights [K, n_params], history [passes, K, 3]): after each pass the loss over the training set at the weights it left (0: net not chosen)."""
+    import torch
+    from .free_convection import pretrain_orders
+    from .nde import check_wm_pretrain_arrays, wm_pretrain_nets_mask
+    K, S = ens.n_models, len(optimizers)
+    mask = wm_pretrain_nets_mask(nets)
+    Wn = np.ascontiguousarray(weights, dtype=np.float32)
+    Xn, Bn, Yn = (np.ascontiguousarray(a, dtype=np.float32) for a in (profiles, BCs, fluxes))
+    if len(train_epochs) != S or any(int(e) < 0 for e in train_epochs):
+        raise ValueError("train_epochs: expected %d counts >= 0 (one per optimiser), got %r" % (S, list(train_epochs)))
+    if etas is None:
+        et = np.array([opt.eta for opt in optimizers], dtype=np.float32).reshape(S, 1, 1) * np.ones((1, K, 3), np.float32)
+    else:
+        et = np.asarray(etas, dtype=np.float32)
+        if et.shape == (S, K):
+            et = np.repeat(et[:, :, None], 3, axis=2)
+        if et.shape != (S, K, 3):
+            raise ValueError("etas: expected shape %s or %s (per-model or per-chain rates, one row per optimiser), got %s" % ((S, K), (S, K, 3), np.shape(etas)))
+    et = np.ascontiguousarray(et, dtype=np.float32)
+    seeds = np.arange(3 * K) if seeds is None else np.asarray(seeds)
+    if seeds.shape != (K, 3) and not (seeds.ndim == 1 and seeds.size == 3 * K):
+        raise ValueError("seeds: expected shape %s (one per model and net), got %s" % ((K, 3), seeds.shape))
+    n_passes = int(sum(int(e) for e in train_epochs))
+    n = check_wm_pretrain_arrays(ens.cfg, K, Wn, Xn, Bn, Yn, etas=et[0] if S else None)
+    orders = pretrain_orders(seeds.reshape(-1), n, n_passes).reshape(n_passes, K, 3, n)
+    dev = torch.device("cuda", ens.device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev).contiguous()
+    theta, Xd, Bd, Yd = up(Wn.copy()), up(Xn), up(Bn), up(Yn)
+    history = np.zeros((n_passes, K, 3), np.float32)
+    p = 0
+    for i, (opt, n_ep) in enumerate(zip(optimizers, train_epochs)):
+        m, v = torch.zeros_like(theta), torch.zeros_like(theta)
+        bt = [float(opt.beta[0]), float(opt.beta[1])]
+        eta_d = up(et[i])
+        for _ in range(int(n_ep)):
+            od = up(orders[p])
+            ens.pretrain_fluxes(theta, m, v, Xd, Bd, Yd, od, gradient_scaling, eta_d, mask, opt.beta, opt.eps, bt, update=True)
+            history[p] = ens.pretrain_fluxes(theta, None, None, Xd, Bd, Yd, od, gradient_scaling, None, mask, opt.beta, opt.eps, bt, update=False)
+            if cb is not None:
+                cb(history[p], theta)
+            p += 1
+    return theta.cpu().numpy(), history
+
+
 def _named(d, *names):
     for nm in names:
         if isinstance(d, dict) and nm in d:

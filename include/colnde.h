@@ -530,6 +530,27 @@ int colnde_ensemble_causal_penalty_dev(colnde_handle* h, const float* d_weights,
 int colnde_ensemble_pretrain_flux_dev(colnde_handle* h, float* d_theta, float* d_m, float* d_v, const float* d_T, const float* d_bcs, const float* d_flux,
                                       const int32_t* d_order, int n_samples, const float* d_coeff, int optimiser, const float* d_eta, float beta1,
                                       float beta2, float eps, double beta_t[2], int update, float* mean_loss);
+/* train_NN (wind_mixing/src/NN_training.jl:207-249) for the K x 3 flux networks of a wind-mixing ensemble in ONE launch: per (model k, net j) one pass of
+ * `Flux.train!(NN_loss, Flux.params(NN), training_data, opt)` with the semantics of colnde_pretrain_flux_dev — Flux ADAM, one update per sample in the
+ * order given, loss = mse + gradient_scaling * mse of the centred differences — and with MODEL k's closure constants (nu0, nu_minus, dRi, Ric, Pr of
+ * colnde_create_ensemble / colnde_ensemble_set_physics) in the weight-independent part of the face flux.  The conditions (modified Pacanowski-Philander,
+ * convective adjustment, zero_weights) are the handle's.  One workgroup per chain (blockIdx.x = model, blockIdx.y = net); chain (k, j) reads and writes only
+ * floats [k P + j net_size, k P + (j + 1) net_size) of d_theta / d_m / d_v ([K][P], the ensemble's layout) and reads row (k, j) of d_order and d_eta; the
+ * samples d_profiles, d_bcs and the three nets' fluxes d_flux (scaled, on the faces) are shared.
+ * nets: bit j set = train net j (0 = uw, 1 = vw, 2 = wT), 1..7; the blocks of the other nets keep their bits and their mean_loss entries are 0.
+ * d_order NULL: 0..n-1 for every chain; an index may repeat.
+ * update = 0: nothing on the device is written, beta_t does not advance and mean_loss[k][j] = the mean loss at the given weights (d_m, d_v, d_eta may be
+ * NULL); update != 0: mean_loss[k][j] = the mean of each sample's loss just before its own update, and beta_t advances by n_samples steps, once (every
+ * selected chain takes the same number of steps).
+ * Block (k, j) of d_theta, d_m, d_v, mean_loss[k][j] and beta_t hold the bits colnde_pretrain_flux_dev computes on a colnde_create handle whose config
+ * carries model k's five constants, with flux_type = j, rate d_eta[k][j] and the same samples and order (the two kernels share one per-sample body).
+ * Refused before any launch, each with its reason and this call's name: a null handle or null pointers, a free-convection or conv ensemble
+ * (colnde_ensemble_pretrain_flux_dev), single-model and closure handles, nets outside 1..7, update without moments or rates, beta_t >= 1, n_samples < 1.
+ * Runs on the handle's stream and synchronises it. */
+int colnde_ensemble_pretrain_wm_flux_dev(colnde_handle* h, int nets /* bit j: train net j */, float* d_theta, float* d_m, float* d_v,
+                                         const float* d_profiles /* [n][96] */, const float* d_bcs /* [n][6] */, const float* d_flux /* [3][n][33] scaled, faces */,
+                                         const int32_t* d_order /* [K][3][n] or NULL */, int n_samples, float gradient_scaling, const float* d_eta /* [K][3] */,
+                                         float beta1, float beta2, float eps, double beta_t[2], int update, float* mean_loss /* HOST [K][3] */);
 
 /* All K models of an ensemble in the embedding ocean column at once — one iteration of progress_neural_network (wind_mixing/src/NDE_oceananigans.jl:380-405) and / or
  * the saved-state diagnoses diagnose_NN_flux_uw / _vw / _wT (:226-286) for every model, each on its OWN column state with its own weights and its own constants: how

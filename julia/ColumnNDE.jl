@@ -633,6 +633,21 @@ function ensemble_pretrain_flux!(h::Handle, n_models, dθ::Ptr{Float32}, dm::Ptr
     loss, βᵗ
 end
 
+"one `Flux.train!(NN_loss, Flux.params(NN), training_data, opt)` pass of `train_NN` (wind_mixing/src/NN_training.jl:207-249) for the K × 3 flux networks of a
+wind-mixing ensemble in one launch, each model under its own (ν₀, ν₋, ΔRi, Riᶜ, Pr): nets a bit mask (bit j-1: net j of uw, vw, wT), dθ, dm, dv K × n_params,
+dprofiles, dbcs the n shared samples, dflux the three nets' fluxes (33 × n × 3), dorder n × 3 × K (C_NULL: 1:n for every chain), dη 3 × K ADAM rates.
+Returns (the 3 × K mean losses, βᵗ); update = false evaluates the loss over the data at fixed weights (`total_loss`)."
+function ensemble_pretrain_wm_flux!(h::Handle, n_models, nets, dθ::Ptr{Float32}, dm::Ptr{Float32}, dv::Ptr{Float32}, dprofiles::Ptr{Float32},
+                                    dbcs::Ptr{Float32}, dflux::Ptr{Float32}, dorder::Ptr{Int32}, n, gradient_scaling, dη::Ptr{Float32}, β, ϵ,
+                                    βᵗ::Vector{Float64}; update=true)
+    loss = zeros(Float32, 3, n_models)
+    check(ccall((:colnde_ensemble_pretrain_wm_flux_dev, libcolnde), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Cint, Cfloat,
+         Ptr{Float32}, Cfloat, Cfloat, Cfloat, Ptr{Float64}, Cint, Ptr{Float32}),
+        h.ptr, nets, dθ, dm, dv, dprofiles, dbcs, dflux, dorder, n, gradient_scaling, dη, β[1], β[2], ϵ, βᵗ, update ? 1 : 0, loss))
+    loss, βᵗ
+end
+
 # ---- the closure without networks: fitting (ν₀, ν₋, ΔRi, Riᶜ, Pr) — wind_mixing/src/diffusivity_parameter_optimisation.jl (DE :1-33,
 # optimise_modified_pacanowski_philander :35-231; drivers wind_mixing/optimise_modified_pacanowski_philander.jl and ..._args.jl)
 
