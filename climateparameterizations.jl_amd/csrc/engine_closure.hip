@@ -87,14 +87,21 @@ __device__ __forceinline__ Col closure_vjp(const ClosureModel& m, const Phys& ph
     const float c2 = in ? -m.A[2] * (db.T - dTb) * m.cs[2] * ph.inv_Pr : 0.0f;
     float gub = c0 * g.nu, gvb = c1 * g.nu, gTb = c2 * g.nu;
     const float nub = c0 * g.gu + c1 * g.gv + c2 * g.gT;
-    const float sech2 = 4.0f * g.e * g.h * g.h;                                   // 1 - tanh^2 y = 4 e / (1 + e)^2
+    // 1 - tanh^2 y = 4 e / (1 + e)^2 holds while e = exp(2 y): inside closure_face's clamp.  Beyond it e stays at exp(+-30) and the formula at
+    // 3.7e-13 however large |y| grows, while y, Ri and 1 / S2 below are the unclamped values: a face at rest (u = v = 0: S2 = 2 (sigma eps)^2 =
+    // 5e-17, |Ri| ~ 1e15) would put 3e3 on dRi-bar and 3e10 on the state cotangent where the derivative is 0.  There sech^2 |y| < 6e-12: the face
+    // is saturated, Ri-bar is exactly 0 and none of its products is formed (0 * Inf included).
+    const bool live = !(fabsf(g.y) >= 15.0f);                                      // (a NaN y stays live: it must reach the result)
+    const float sech2 = 4.0f * g.e * g.h * g.h;
     const float rib = nub * (-0.5f * ph.nu_minus) * sech2 * ph.inv_dRi;           // Ri-bar
     if (in) {
         acc[0] += nub;
         acc[1] += nub * g.h;
+        acc[4] -= c2 * g.nu * g.gT * ph.inv_Pr;
+    }
+    if (in && live) {
         acc[2] -= rib * g.y;
         acc[3] -= rib;
-        acc[4] -= c2 * g.nu * g.gT * ph.inv_Pr;
         gTb += fast_div(rib * m.B, g.S2);
         const float q = fast_div(rib * -g.Ri, g.S2) * 2.0f;
         gub += q * m.sig_u * m.sig_u * (g.gu + m.eps);
