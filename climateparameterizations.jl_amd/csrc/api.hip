@@ -151,8 +151,16 @@ extern "C" int colnde_min_substeps(const colnde_config* c) {
         const double need = span * stiff_lambda(c) / (COLNDE_RKC_SAFETY * rkc_tables(s, nullptr));
         return need <= 1.0 ? 1 : (int)ceil(need);
     }
-    const double need = span * stiff_lambda(c) / COLNDE_RK4_REAL_BOUND;
-    return need <= 1.0 ? 1 : (int)ceil(need);
+    return sched_interval_min(span, stiff_lambda(c), COLNDE_RK4_REAL_BOUND);
+}
+
+// The same bound on each save interval's own length (RK4): what colnde_min_substeps gives for the two-point configuration of that interval
+extern "C" int colnde_schedule_min(const colnde_config* c, int* counts) {
+    if (!counts) return fail("null counts");
+    if (validate(c)) return 1;
+    if (c->stepper != COLNDE_STEPPER_RK4) return fail("a step schedule covers RK4 only: the RKC2 stage table depends on dt");
+    sched_minima(c->save_times, c->n_save, stiff_lambda(c), COLNDE_RK4_REAL_BOUND, counts);
+    return 0;
 }
 
 // inv_dRi, inv_Pr and c_rib of the Richardson-number closure from the five Pacanowski-Philander constants: ONE expression for the single
@@ -691,7 +699,7 @@ int rt_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int
 int t16_forward_range(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape, int c0, int nc) {
     const size_t ns = h->m.ns;
     if (with_tape && !h->d_tape) {     // in-register gradient mode: the whole problem's stage tape
-        const size_t n = (size_t)h->n_tiles * (h->cfg.n_save - 1) * h->cfg.substeps * h->m.nst * CT * ns;
+        const size_t n = sched_tape_floats((size_t)h->n_tiles, total_steps(h), h->m.nst, CT * ns);
         hipError_t e = h->mem.alloc(&h->d_tape, n);
         if (e != hipSuccess) return fail("hipMalloc of the %zu-byte stage tape failed: %s", n * sizeof(float), hipGetErrorString(e));
     }
@@ -703,10 +711,12 @@ int t16_forward_range(colnde_handle* h, const float* d_weights, float* d_sol, bo
         if (es == hipSuccess)
             es = rt_launch_forward_split(h->m, h->d_wimg, h->d_x0 + (size_t)c0 * ns, h->d_bcs + (size_t)c0 * h->m.n_bc, h->d_times, h->cfg.n_save,
                                          h->cfg.substeps, d_sol ? d_sol + (size_t)c0 * h->cfg.n_save * ns : nullptr,
-                                         with_tape ? h->d_tape : nullptr, with_tape ? h->d_t16_ztape : nullptr, nc, with_tape && h->split_rich, h->fwd_helper, h->sp_fwd, h->stream);
+                                         with_tape ? h->d_tape : nullptr, with_tape ? h->d_t16_ztape : nullptr, nc, with_tape && h->split_rich, h->fwd_helper, h->sp_fwd, h->stream,
+                                         RtEns(), sched_dev(h), total_steps(h));
         if (es != hipSuccess) return fail("split forward launch failed: %s", hipGetErrorString(es));
         return 0;
     }
+    if (!h->sched.empty()) return fail("a step schedule is set, but this solve does not run on rt16sh_forward_kernel");
     hipError_t e = launch_forward(h->m, h->pk, d_weights, h->d_wf, h->d_x0 + (size_t)c0 * ns, h->d_bcs + (size_t)c0 * h->m.n_bc, h->d_times,
                                   h->cfg.n_save, h->cfg.substeps, d_sol ? d_sol + (size_t)c0 * h->cfg.n_save * ns : nullptr,
                                   with_tape ? h->d_tape : nullptr, nc, h->fwd_threads, h->fwd_wlds, h->lds_fwd_solve, h->stream,
@@ -771,6 +781,15 @@ int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int
 // ---- forward solve -------------------------------------------------------------------------------------
 // A time step outside RK4's stability region gives a blown-up or NaN trajectory, loss and gradient with rc = 0: refuse it.
 int check_stability(const colnde_handle* h) {
+    if (!h->sched.empty()) {          // a schedule: each interval against its own bound
+        std::vector<int> need;
+        if (schedule_minima(h, &need)) return 1;
+        int bad = 0;
+        if (sched_validate(h->sched.data(), need.data(), (int)need.size(), allow_unstable(), &bad) == SCHED_BELOW_MIN)
+            return fail("schedule[%d] = %d puts the RK4 step of save interval %d outside its stability region: need >= %d (colnde_schedule_min; "
+                        "COLNDE_ALLOW_UNSTABLE_DT=1 overrides)", bad, h->sched[bad], bad, need[bad]);
+        return 0;
+    }
     if (h->cfg.substeps >= h->min_substeps || allow_unstable()) return 0;
     if (h->cfg.stepper == COLNDE_STEPPER_RKC2)
         return fail("substeps = %d with %d RKC2 stages does not cover the stiffest diffusive mode (lambda = -%.4g): need substeps >= %d, "
@@ -1109,6 +1128,7 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
     snprintf(t, sizeof t, "engine=%s columns=%d stepper=%s substeps=%d%s", eng, h->cfg.n_columns, h->cfg.stepper == COLNDE_STEPPER_RKC2 ? "rkc2" : "rk4",
              h->cfg.substeps, why);
     s += t;
+    if (!h->sched.empty()) { snprintf(t, sizeof t, " schedule=%d/%d intervals", total_steps(h), h->cfg.n_save - 1); s += t; }
     if (h->conv.c) { snprintf(t, sizeof t, " conv=%d n_params=%d", h->conv.c, h->conv.n_params); s += t; }
     if (h->ensemble) { snprintf(t, sizeof t, " models=%d tape_bytes_per_model=%zu", h->n_models, h->ens_model_bytes); s += t; }
     if (h->cfg.stepper == COLNDE_STEPPER_RKC2) { snprintf(t, sizeof t, " rkc_stages=%d%s", h->m.nst, h->cfg.rkc_stages ? "" : "(automatic)"); s += t; }

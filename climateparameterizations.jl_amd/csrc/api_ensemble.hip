@@ -63,8 +63,8 @@ static int ens_upload_physics(colnde_handle* h, const float* physics) {
 static int ens_plan_tapes(colnde_handle* h) {
     const DevModel& m = h->m;
     const int K = h->n_models;
-    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
-    const size_t n_rec = (size_t)h->n_tiles * n_steps * m.nst;
+    const int n_steps = total_steps(h);
+    const size_t n_rec = sched_records((size_t)h->n_tiles, n_steps, m.nst);
     const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
     build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order
     h->t16_rows = h->n_tiles + h->dw.slices;
@@ -110,6 +110,20 @@ static int ens_plan_tapes(colnde_handle* h) {
     h->ens.phys = h->d_phys;
     h->ens_model_bytes = need;
     return 0;
+}
+
+// colnde_set_schedule on an ensemble: its tapes were sized at creation for (n_save - 1) x substeps steps, so they are planned again for the total in force
+int ens_replan_tapes(colnde_handle* h) {
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->mem.release(&h->d_dwtape);
+    h->mem.release(&h->d_tape);
+    h->mem.release(&h->d_t16_ztape);
+    h->mem.release(&h->d_slab);
+    h->mem.release(&h->d_macros);
+    h->mem.release(&h->d_split_macros);
+    h->t16_dwtape = -1;
+    return ens_plan_tapes(h);
 }
 
 extern "C" int colnde_create_ensemble(const colnde_config* cfg, int n_models, const float* physics, colnde_handle** out) {
@@ -484,7 +498,7 @@ static int ens_forward(colnde_handle* h, const float* d_weights, float* d_sol, b
     if (e == hipSuccess)
         e = rt_launch_forward_split(h->m, h->d_wimg, h->d_x0, h->d_bcs, h->d_times, h->cfg.n_save, h->cfg.substeps, d_sol,
                                     with_tape ? h->d_tape : nullptr, with_tape ? h->d_t16_ztape : nullptr, h->n_col, with_tape && h->split_rich,
-                                    true, h->sp_fwd, h->stream, ens);
+                                    true, h->sp_fwd, h->stream, ens, sched_dev(h), total_steps(h));
     if (e != hipSuccess) return fail("ensemble forward launch failed: %s", hipGetErrorString(e));
     return 0;
 }
@@ -529,12 +543,12 @@ extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_we
     {
         Timed tm(h, K_ADJOINT);
         e = rt_launch_adjoint_split(h->m, h->d_wimg, h->d_times, h->cfg.n_save, h->cfg.substeps, h->d_sol, h->d_truth, h->d_tape, h->d_t16_ztape, lw,
-                                    h->d_slab, h->n_col, h->d_dwtape, h->split_rich, true, h->sp_adj, h->stream, h->ens);
+                                    h->d_slab, h->n_col, h->d_dwtape, h->split_rich, true, h->sp_adj, h->stream, h->ens, sched_dev(h), total_steps(h));
         if (e != hipSuccess) return fail("ensemble adjoint launch failed: %s", hipGetErrorString(e));
     }
     {
         Timed tm(h, K_DW1);
-        const size_t n_rec = (size_t)h->n_tiles * (h->cfg.n_save - 1) * h->cfg.substeps * h->m.nst;
+        const size_t n_rec = sched_records((size_t)h->n_tiles, total_steps(h), h->m.nst);
         e = dw_launch(h, n_rec, h->d_slab + (size_t)h->n_tiles * stride, K, h->ens.dwtape, h->ens.slab);
         if (e != hipSuccess) return fail("ensemble dW GEMM launch failed: %s", hipGetErrorString(e));
     }

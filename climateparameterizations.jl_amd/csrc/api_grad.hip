@@ -138,7 +138,7 @@ static int t16_plan_dwtape(colnde_handle* h) {
     // default: on whenever the tapes fit — with the hidden pre-activations taped too, the 1,024-thread accumulator-free adjoint beats
     // the in-register kernels at every size measured (8 columns: 53 vs 64 ms per iteration; 32-128-128-31: 162 vs 198 ms)
     bool want = ev ? atoi(ev) != 0 : true;
-    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
+    const int n_steps = total_steps(h);
     const size_t R = dwtape_row_floats(m);
     if (want && (size_t)CT * m.ns > 6 * 512) want = false;
     // LDS of the taped adjoint: with the Z tape (the default) it holds no activation array; a network that fits only that way (3 x 96-400-31: 166 KB with
@@ -351,8 +351,10 @@ static int t16_taped_loss_grad(colnde_handle* h, const float* d_weights, const f
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
     LossWeights lw;
     loss_weights(h, scalings, &lw);
-    const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
+    const int n_steps = total_steps(h);
     const size_t ns = h->m.ns;
+    if (!h->sched.empty() && !(h->adj_split && h->adj_helper && h->d_t16_ztape))
+        return fail("a step schedule is set, but this gradient does not run on rt16sh_adjoint_kernel (no pre-activation or rich tape)");
     if (pack(h, d_weights)) return 1;
     HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)h->t16_rows * stride * sizeof(float), h->stream));
     for (int b = 0; b < h->t16_nblocks; b++) {
@@ -368,7 +370,8 @@ static int t16_taped_loss_grad(colnde_handle* h, const float* d_weights, const f
                 // the companion of the split forward: one wavefront per flux net (+ a helper) per tile, writing tile16's delta tape
                 e = rt_launch_adjoint_split(h->m, h->d_wimg, h->d_times, h->cfg.n_save, h->cfg.substeps,
                                             h->d_sol + (size_t)c0 * h->cfg.n_save * ns, h->d_truth + (size_t)c0 * h->cfg.n_save * ns, h->d_tape,
-                                            h->d_t16_ztape, lw, h->d_slab + (size_t)(c0 / CT) * stride, nc, h->d_dwtape, h->split_rich, h->adj_helper, h->sp_adj, h->stream);
+                                            h->d_t16_ztape, lw, h->d_slab + (size_t)(c0 / CT) * stride, nc, h->d_dwtape, h->split_rich, h->adj_helper, h->sp_adj, h->stream,
+                                            RtEns(), sched_dev(h), n_steps);
             else
             e = launch_adjoint(h->m, h->pk, d_weights, h->d_wf, h->d_wb, h->d_tiles, h->d_bias_zoff, h->d_bias_goff,
                                           h->d_bcs + (size_t)c0 * h->m.n_bc, h->d_times, h->cfg.n_save, h->cfg.substeps,
@@ -437,6 +440,7 @@ extern "C" int colnde_loss_grad_dev(colnde_handle* h, const float* d_weights, co
     if (h->use_rt) return rt_loss_grad(h, d_weights, scalings, d_out);
     if (h->use_fc) return fc_loss_grad(h, d_weights, scalings, d_out);
     if (t16_plan_dwtape(h)) return 1;
+    if (!h->sched.empty() && h->t16_dwtape != 1) return fail("a step schedule is set, but the delta tape of this problem was not planned: no gradient path runs it");
     return h->t16_dwtape == 1 ? t16_taped_loss_grad(h, d_weights, scalings, d_out) : t16_inreg_loss_grad(h, d_weights, scalings, d_out);
 }
 

@@ -23,6 +23,7 @@
 #include "engine_fc_embed.h"
 #include "engine_fc_pretrain.h"
 #include "engine_wm_pretrain.h"
+#include "step_schedule.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -61,6 +62,8 @@ hipError_t dw_launch(colnde_handle* h, size_t n_records, float* slab_rows, int K
 int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
 colnde_config model_config(const colnde_config* cfg, const float* physics, int k);
 int choose_substeps_impl(colnde_handle* h, const float* d_weights, float reltol, int* chosen, float* estimate);
+int schedule_minima(const colnde_handle* h, std::vector<int>* minima);   // per save interval; an ensemble: the largest any model needs (api_substeps.hip)
+int ens_replan_tapes(colnde_handle* h);   // an ensemble's tapes, planned at creation, re-planned for the step total in force (colnde_set_schedule)
 // ---- defined in api_embed.hip: the handles the embedding's kernels cover (colnde_describe reports them) ------
 bool wm_infer_covers(const colnde_handle* h);
 bool fce_covers(const colnde_handle* h);
@@ -240,6 +243,9 @@ struct colnde_handle {
     std::vector<float> rkc_host;    // host copy of the RKC2 coefficient table in use (refresh_rkc)
     bool ag_rows = false;           // the tile16 kernels keep the activation rows in global memory (DevModel::ag)
     bool substeps_chosen = false;   // the count in use came out of choose_substeps_impl (colnde_describe says so, with the estimate)
+    // step schedule (colnde_set_schedule; step_schedule.h): RK4 steps per save interval in cfg.substeps' place — empty: none — and its device copy
+    std::vector<int> sched;
+    int* d_sched = nullptr;         // [n_save - 1], allocated by the first colnde_set_schedule
     float* d_rkc = nullptr;         // RKC2 coefficient table (DevModel::rkc)
     // ensembles (colnde_create_ensemble): n_models models of this configuration in one launch per kernel (blockIdx.y = model)
     bool ensemble = false;
@@ -263,6 +269,13 @@ struct colnde_handle {
     double ms[K_COUNT] = {};
     int launches[K_COUNT] = {};
 };
+
+// The steps of the whole time axis — what sizes the tapes, the slab rows' dW records and the kernels' tape strides: the one place that forms it
+inline int total_steps(const colnde_handle* h) {
+    return (int)sched_total(h->sched.empty() ? nullptr : h->sched.data(), h->cfg.n_save - 1, h->cfg.substeps);
+}
+// ... and the schedule argument of the net-split launches (null: cfg.substeps in every interval)
+inline const int* sched_dev(const colnde_handle* h) { return h->sched.empty() ? nullptr : h->d_sched; }
 
 // times the launches of its scope into slot `which` when the handle profiles (colnde_set_profiling)
 struct Timed {

@@ -1,4 +1,4 @@
-// api_substeps.hip — the sub-step count: error estimate, colnde_choose_substeps, colnde_set_substeps.
+// api_substeps.hip — the sub-step count: error estimate, colnde_choose_substeps, colnde_set_substeps; the per-interval step schedule.
 #include "api_internal.h"
 
 // ---- error-controlled time stepping: what `reltol` means at this boundary ------------------------------------------------------------
@@ -22,6 +22,8 @@ static int forward_at(colnde_handle* h, const float* d_weights, float* d_sol, in
 }
 
 static int tapes_planned(const colnde_handle* h) { return h->d_rt_tape || h->d_dwtape || h->d_tape; }
+static int forward_scheduled(colnde_handle* h, const float* d_weights, float* d_sol, const std::vector<int>& S);
+static int upload_schedule(colnde_handle* h, const int* counts);
 
 // estimate at `substeps` given its solution d_a; d_b receives the solution at 2 x substeps; *d_est (device) the estimate
 static int estimate_from(colnde_handle* h, const float* d_weights, const float* d_a, float* d_b, int substeps, float* d_est, float floor_) {
@@ -54,8 +56,20 @@ extern "C" int colnde_error_estimate_dev(colnde_handle* h, const float* d_weight
     DevScratch sc(h->stream);
     HIPCHK(sc.alloc((n + 4) * sizeof(float)));
     float* d_b = sc.p;
-    int rc = forward_at(h, d_weights, h->d_sol, h->cfg.substeps);
-    if (!rc) rc = estimate_from(h, d_weights, h->d_sol, d_b, h->cfg.substeps, d_b + n, norm_floor(h->cfg.reltol));
+    int rc = 0;
+    if (!h->sched.empty()) {          // under a step schedule: the schedule against every interval doubled
+        const std::vector<int> S = h->sched;
+        std::vector<int> S2(S);
+        for (int& c : S2) c *= 2;
+        rc = forward_scheduled(h, d_weights, h->d_sol, S) || forward_scheduled(h, d_weights, d_b, S2);
+        if (!rc && launch_rel_diff_max(h->d_sol, d_b, (long)h->n_col * h->cfg.n_save, h->m.ns, norm_floor(h->cfg.reltol), h->d_partial, d_b + n, h->stream) != hipSuccess)
+            rc = fail("error-estimate launch failed");
+        h->sched = S;                                                // the counts in force again, on the device too
+        if (upload_schedule(h, S.data())) rc = 1;
+    } else {
+        rc = forward_at(h, d_weights, h->d_sol, h->cfg.substeps);
+        if (!rc) rc = estimate_from(h, d_weights, h->d_sol, d_b, h->cfg.substeps, d_b + n, norm_floor(h->cfg.reltol));
+    }
     float est = 0.0f;
     if (!rc && (hipMemcpyAsync(&est, d_b + n, sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess))
         rc = fail("error estimate: device-to-host copy failed");
@@ -78,6 +92,14 @@ extern "C" int colnde_error_estimate(colnde_handle* h, const float* weights, flo
 int choose_substeps_impl(colnde_handle* h, const float* d_weights, float reltol, int* chosen, float* estimate) {
     if (tapes_planned(h)) return fail("the sub-step count sizes the tapes: choose it before the first colnde_loss_grad of this handle");
     if (!(reltol > 0.0f)) return fail("reltol must be > 0");
+    // one count for every interval is what is chosen here: it takes a step schedule's place (which a failure puts back; its device copy is untouched)
+    struct Restore {
+        colnde_handle* h;
+        std::vector<int> keep;
+        bool done = false;
+        ~Restore() { if (!done) h->sched.swap(keep); }
+    } schedule_guard{h, {}};
+    schedule_guard.keep.swap(h->sched);
     const size_t n = (size_t)h->n_col * h->cfg.n_save * h->m.ns;
     DevScratch sc(h->stream);
     HIPCHK(sc.alloc((2 * n + 4) * sizeof(float)));
@@ -113,6 +135,7 @@ int choose_substeps_impl(colnde_handle* h, const float* d_weights, float reltol,
                                "%g at half as many)", reltol, est, S, prev);
     if (est > reltol) return fail("reltol = %g is not met with %d sub-steps per save interval (estimate %g): the right-hand side is too stiff for this stepper", reltol, S, est);
     h->cfg.substeps = S;
+    schedule_guard.done = true;
     if (refresh_rkc(h)) return 1;
     h->last_estimate = est;
     h->substeps_chosen = true;
@@ -139,12 +162,12 @@ extern "C" int colnde_choose_substeps(colnde_handle* h, const float* weights, fl
 extern "C" int colnde_substeps(const colnde_handle* h) { return h ? h->cfg.substeps : -1; }
 
 // Impose a sub-step count (e.g. the MAX over ranks of what colnde_choose_substeps chose on each shard).  Refused once the tapes are planned (the count
-// sizes them) and outside the stepper's stability bound; clears a pending substeps = 0.
+// sizes them) and outside the stepper's stability bound; clears a pending substeps = 0 and a step schedule (colnde_set_schedule).
 extern "C" int colnde_set_substeps(colnde_handle* h, int substeps) {
     SINGLE_MODEL_ONLY(h);
     if (!h) return fail("null handle");
     if (substeps < 1) return fail("substeps must be >= 1");
-    if (substeps == h->cfg.substeps && !h->auto_substeps) return 0;
+    if (substeps == h->cfg.substeps && !h->auto_substeps && h->sched.empty()) return 0;
     if (tapes_planned(h)) return fail("the sub-step count sizes the tapes: set it before the first colnde_loss_grad of this handle");
     colnde_config c = h->cfg;
     c.substeps = substeps;
@@ -153,8 +176,200 @@ extern "C" int colnde_set_substeps(colnde_handle* h, int substeps) {
     if (substeps < need && !allow_unstable())
         return fail("substeps = %d is outside the stepper's stability bound: need >= %d (colnde_min_substeps)", substeps, need);
     h->cfg.substeps = substeps;
+    h->sched.clear();                                      // one count for every interval again
     h->auto_substeps = false;
     h->substeps_chosen = false;
     h->last_estimate = -1.0f;
     return refresh_rkc(h);
+}
+
+// ---- the step schedule: RK4 steps per save interval (step_schedule.h) ------------------------------------------------------------------
+// One global `substeps` makes every save interval pay for the most demanding one.  A schedule gives interval n its own count S_n, the same for all
+// columns and members; the four-wave net-split pair (rt16sh_forward_sched_kernel / rt16sh_adjoint_sched_kernel) steps and tapes by it.
+
+// per interval, what the stability bound asks: of an ensemble, the largest any model's constants ask
+int schedule_minima(const colnde_handle* h, std::vector<int>* minima) {
+    const int n_iv = h->cfg.n_save - 1;
+    minima->assign((size_t)n_iv, 1);
+    std::vector<int> one((size_t)n_iv);
+    const bool per_model = h->ensemble && !h->phys_raw.empty();
+    for (int k = 0; k < (per_model ? h->n_models : 1); k++) {
+        const colnde_config c = per_model ? model_config(&h->cfg, h->phys_raw.data(), k) : h->cfg;
+        if (colnde_schedule_min(&c, one.data())) return 1;
+        for (int i = 0; i < n_iv; i++) (*minima)[i] = std::max((*minima)[i], one[i]);
+    }
+    return 0;
+}
+
+// Which handles step by a schedule: those whose solves run on rt16sh_forward_kernel / rt16sh_adjoint_kernel.  Decided from the handle alone, before any device work.
+static int refuse_schedule(const colnde_handle* h) {
+    static const char* only = "a step schedule covers the four-wave net-split kernels (rt16sh_forward_kernel / rt16sh_adjoint_kernel: the wind-mixing NDE, RK4, at most 8,192 columns)";
+    if (h->closure) return fail("%s: the closure engine (colnde_create_closure) steps with one substeps", only);
+    if (h->conv.c) return fail("%s: a conv handle (colnde_create_conv, conv=%d) runs the fc32 engine", only, h->conv.c);
+    if (h->use_fc || h->cfg.model != COLNDE_MODEL_WIND_MIXING)
+        return fail("%s: %s", only, h->ensemble ? "a free-convection ensemble (colnde_create_fc_ensemble) runs the fc32 engine" : "the free-convection models run the fc32 and tile16 engines");
+    if (h->cfg.stepper == COLNDE_STEPPER_RKC2) return fail("a step schedule covers RK4 only: the RKC2 stage table depends on dt");
+    if (h->use_rt) return fail("%s: this handle runs regtile (more than 8,192 columns, or engine = regtile)", only);
+    if (!rt_supported(h->m))
+        return fail("%s: this configuration (network shape, Nz, smoothing or inplace_variant) runs the tile16 engine", only);
+    for (EnvSwitch sw : {ENV_T16_FWD_HELPER, ENV_T16_ADJ_HELPER, ENV_T16_FWD_SPLIT, ENV_T16_ADJ_SPLIT, ENV_T16_ZTAPE, ENV_T16_DWTAPE}) {
+        const char* e = env_get(sw);
+        if (e && atoi(e) == 0) return fail("%s: %s=0 selects the three-wave or tile16 kernels (or no delta / pre-activation tape)", only, env_name(sw));
+    }
+    if (!h->fwd_split || !h->adj_split || !h->fwd_helper || !h->adj_helper) return fail("%s: this handle's engine selection runs tile16", only);
+    return 0;
+}
+
+static int upload_schedule(colnde_handle* h, const int* counts) {
+    const size_t n_iv = (size_t)h->cfg.n_save - 1;
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->d_sched && h->mem.alloc(&h->d_sched, n_iv) != hipSuccess) return fail("allocating the step schedule (%zu counts) failed", n_iv);
+    // in stream order behind the kernels that still read the previous counts; completed before returning (the caller's array is not kept)
+    if (hipMemcpyAsync(h->d_sched, counts, n_iv * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+        return fail("uploading the step schedule failed");
+    return 0;
+}
+
+// The RK4 steps of every save interval (NULL: back to cfg.substeps everywhere).  Refused once a single handle's tapes are planned — the total sizes
+// them; an ensemble's, planned at creation, are planned again — and outside each interval's stability bound.  Clears a pending substeps = 0.
+extern "C" int colnde_set_schedule(colnde_handle* h, const int* counts) {
+    if (!h) return fail("null handle");
+    const int n_iv = h->cfg.n_save - 1;
+    const char* planned = "the step schedule sizes the tapes: set it before the first colnde_loss_grad of this handle";
+    if (!counts) {
+        if (h->sched.empty()) return 0;
+        if (!h->ensemble && tapes_planned(h)) return fail("%s", planned);
+        std::vector<int> keep;
+        keep.swap(h->sched);
+        if (h->ensemble && ens_replan_tapes(h)) {
+            h->sched.swap(keep);
+            return 1;
+        }
+        h->last_estimate = -1.0f;
+        h->substeps_chosen = false;
+        return 0;
+    }
+    if (refuse_schedule(h)) return 1;
+    if (!h->sched.empty() && std::equal(h->sched.begin(), h->sched.end(), counts)) return 0;
+    if (!h->ensemble && tapes_planned(h)) return fail("%s", planned);
+    std::vector<int> need;
+    if (schedule_minima(h, &need)) return 1;
+    int bad = 0;
+    switch (sched_validate(counts, need.data(), n_iv, allow_unstable(), &bad)) {
+    case SCHED_NOT_POSITIVE: return fail("schedule[%d] = %d: every save interval takes at least one step", bad, counts[bad]);
+    case SCHED_ABOVE_MAX: return fail("schedule[%d] = %d is above %d steps per save interval", bad, counts[bad], COLNDE_SCHEDULE_MAX);
+    case SCHED_BELOW_MIN:
+        return fail("schedule[%d] = %d is outside the stepper's stability bound on save interval %d: need >= %d (colnde_schedule_min; COLNDE_ALLOW_UNSTABLE_DT=1 overrides)",
+                    bad, counts[bad], bad, need[bad]);
+    case SCHED_OK: break;
+    }
+    std::vector<int> keep(counts, counts + n_iv);
+    if (upload_schedule(h, keep.data())) return 1;
+    keep.swap(h->sched);                                   // (keep: the schedule that was in force)
+    if (h->ensemble && ens_replan_tapes(h)) {
+        const std::string msg = colnde_last_error();
+        h->sched.swap(keep);
+        if (!h->sched.empty()) (void)upload_schedule(h, h->sched.data());
+        (void)ens_replan_tapes(h);
+        return fail("%s", msg.c_str());
+    }
+    h->auto_substeps = false;
+    h->substeps_chosen = false;
+    h->last_estimate = -1.0f;
+    return 0;
+}
+
+// counts (nullable) receives the steps of every save interval — cfg.substeps each without a schedule; returns their total, -1 on a null handle
+extern "C" int colnde_schedule(const colnde_handle* h, int* counts) {
+    if (!h) { fail("null handle"); return -1; }
+    if (counts)
+        for (int i = 0; i < h->cfg.n_save - 1; i++) counts[i] = h->sched.empty() ? h->cfg.substeps : h->sched[i];
+    return total_steps(h);
+}
+
+// forward solve under the counts S (uploaded; h->sched is left holding them)
+static int forward_scheduled(colnde_handle* h, const float* d_weights, float* d_sol, const std::vector<int>& S) {
+    if (upload_schedule(h, S.data())) return 1;
+    h->sched = S;
+    return forward_impl(h, d_weights, d_sol, false);
+}
+
+// The fixed-step form of reltol, interval by interval.  From the stability minima rounded up to powers of two: solve at S and at 2 S (every interval
+// doubled), E[n] = the estimate of colnde_error_estimate at save point n alone (max over columns); while max E > reltol, the intervals that add the
+// most to it — d[n] = max(0, E[n] - E[n-1]) at least half the largest — are doubled.  Errors are handed from one interval to the next, so E[n] - E[n-1]
+// is what interval n adds; a diffusive solve damps what it inherits, hence the clamp at 0.
+static int choose_schedule_impl(colnde_handle* h, const float* d_weights, float reltol, int* counts, float* estimate) {
+    const int n_iv = h->cfg.n_save - 1, n_save = h->cfg.n_save;
+    const size_t n = (size_t)h->n_col * n_save * h->m.ns;
+    DevScratch sc(h->stream);
+    HIPCHK(sc.alloc((2 * n + (size_t)n_save + 4) * sizeof(float)));
+    float *d_a = sc.p, *d_b = sc.p + n, *d_e = sc.p + 2 * n;
+    std::vector<int> S;
+    if (schedule_minima(h, &S)) return 1;
+    for (int& s : S) s = sched_pow2_ceil(s);
+    std::vector<float> E((size_t)n_save), d((size_t)n_iv);
+    float est = -1.0f, prev = -1.0f;
+    for (;;) {
+        std::vector<int> S2(S);
+        for (int& s : S2) s *= 2;
+        if (forward_scheduled(h, d_weights, d_a, S) || forward_scheduled(h, d_weights, d_b, S2)) return 1;
+        hipError_t e = launch_rel_diff_save_max(d_a, d_b, h->n_col, n_save, h->m.ns, norm_floor(reltol), d_e, h->stream);
+        if (e != hipSuccess) return fail("error-estimate launch failed: %s", hipGetErrorString(e));
+        if (hipMemcpyAsync(E.data(), d_e, (size_t)n_save * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+            return fail("choose_schedule: device-to-host copy failed");
+        est = 0.0f;
+        const int total = (int)sched_total(S.data(), n_iv);
+        for (int i = 0; i < n_save; i++) {
+            E[i] *= richardson_factor(h);
+            if (!(E[i] == E[i]) || E[i] > 3.0e38f) return fail("the solve is not finite under a schedule of %d steps in all: no schedule can be chosen", total);
+            est = std::max(est, E[i]);
+        }
+        if (est <= reltol) break;
+        // every interval doubled last round was one of its contributors (that is how they are picked), so an estimate that fell by less than a fifth is the
+        // float32 round-off of the two solves it compares, as in colnde_choose_substeps
+        if (prev > 0.0f && est > 0.8f * prev)
+            return fail("reltol = %g is below the float32 round-off floor of this solve: the estimate stopped falling at %g (%d steps in all, %g before the last doubling)",
+                        reltol, est, total, prev);
+        prev = est;
+        float dmax = 0.0f;
+        for (int i = 0; i < n_iv; i++) { d[i] = std::max(0.0f, E[i + 1] - (i ? E[i] : 0.0f)); dmax = std::max(dmax, d[i]); }
+        bool doubled = false;
+        for (int i = 0; i < n_iv; i++)
+            if (d[i] >= 0.5f * dmax && S[i] < COLNDE_SCHEDULE_MAX) { S[i] *= 2; doubled = true; }
+        if (!doubled)
+            return fail("reltol = %g is not met with %d steps in the save intervals that carry the error (estimate %g): the right-hand side is too stiff for this stepper",
+                        reltol, COLNDE_SCHEDULE_MAX, est);
+    }
+    if (upload_schedule(h, S.data())) return 1;
+    h->sched = S;
+    h->last_estimate = est;
+    h->substeps_chosen = false;
+    if (counts) std::copy(S.begin(), S.end(), counts);
+    if (estimate) *estimate = est;
+    return 0;
+}
+
+extern "C" int colnde_choose_schedule(colnde_handle* h, const float* weights, float reltol, int* counts, float* estimate) {
+    SINGLE_MODEL_ONLY(h);
+    if (!h) return fail("null handle");
+    if (!weights) return fail("null weights");
+    if (refuse_schedule(h)) return 1;
+    if (!h->have_problem) return fail("colnde_set_problem has not been called");
+    if (refuse_auto_on_a_shard(h)) return 1;
+    if (tapes_planned(h)) return fail("the step schedule sizes the tapes: choose it before the first colnde_loss_grad of this handle");
+    if (reltol == 0.0f) reltol = h->cfg.reltol;
+    if (!(reltol > 0.0f)) return fail("reltol must be > 0");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * h->m.n_params, hipMemcpyHostToDevice, h->stream));
+    const std::vector<int> keep = h->sched;
+    const bool au = h->auto_substeps;
+    h->auto_substeps = false;
+    if (choose_schedule_impl(h, h->d_w, reltol, counts, estimate)) {
+        const std::string msg = colnde_last_error();
+        h->sched = keep;
+        h->auto_substeps = au;
+        if (!keep.empty()) (void)upload_schedule(h, keep.data());
+        return fail("%s", msg.c_str());
+    }
+    return 0;
 }

@@ -549,6 +549,35 @@ hipError_t launch_rel_diff_max(const float* a, const float* b, long n_rows, int 
     return hipGetLastError();
 }
 
+// The same norm per save point (colnde_choose_schedule): out[n] = max over the columns of the row norm at save point n, rows [column][n_save][row].
+// One workgroup per save point; a maximum, so the order of the reduction does not matter.
+__global__ void __launch_bounds__(256) rel_diff_save_max_kernel(const float* __restrict__ a, const float* __restrict__ b, int n_col, int n_save, int row, float floor,
+                                                                float* __restrict__ out) {
+    const int n = blockIdx.x;
+    float mx = 0.0f;
+    for (int c = threadIdx.x; c < n_col; c += 256) {
+        const size_t r = ((size_t)c * n_save + n) * row;
+        float s2 = 0.0f;
+        for (int i = 0; i < row; i++) {
+            const float q = (a[r + i] - b[r + i]) / (floor + fabsf(b[r + i]));
+            s2 += q * q;
+        }
+        const float v = sqrtf(s2 / (float)row);
+        mx = (v <= 3.0e38f) ? fmaxf(mx, v) : __int_as_float(0x7f800000);              // a NaN or Inf anywhere: +inf
+    }
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_down(mx, off));
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) out[n] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+hipError_t launch_rel_diff_save_max(const float* a, const float* b, int n_col, int n_save, int row, float floor, float* out, hipStream_t stream) {
+    if (n_col < 1 || n_save < 1 || row < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rel_diff_save_max_kernel, dim3(n_save), dim3(256), 0, stream, a, b, n_col, n_save, row, floor, out);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // Free-convection ensembles (colnde_create_fc_ensemble): judging K networks on the same simulations.
 // ------------------------------------------------------------------------------------------------

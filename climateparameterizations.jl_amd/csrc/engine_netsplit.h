@@ -14,13 +14,15 @@ struct RtEns {
 };
 
 hipError_t rt_set_attributes_split();   // the dynamic-LDS limit of every kernel of this unit (beside rt_set_attributes)
+// sched != nullptr (device, int[n_save - 1]; colnde_set_schedule): save interval n takes sched[n] RK4 steps instead of `substeps`, the tapes hold
+// total_steps = their sum per tile — the four-wave RK4 kernels only (rt16sh_forward_sched_kernel / rt16sh_adjoint_sched_kernel), anything else is refused
 hipError_t rt_launch_forward_split(const DevModel& m, const float* wimg, const float* x0, const float* bcs, const float* save_times,
                                    int n_save, int substeps, float* sol, float* t16_tape, float* t16_ztape, int n_col, bool rich, bool use_helper, bool want_split, hipStream_t stream,
-                                   const RtEns& ens = RtEns());
+                                   const RtEns& ens = RtEns(), const int* sched = nullptr, int total_steps = 0);
 size_t rt_split_rich_record_floats();   // floats per (tile, step, stage) of the net-split kernels' rich tape (which then takes the place of t16_ztape)
 hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const float* save_times, int n_save, int substeps, const float* sol,
                                    const float* truth, const float* t16_tape, const float* t16_ztape, const LossWeights& lw, float* slab,
                                    int n_col, float* dwtape, bool rich, bool use_helper, bool want_split, hipStream_t stream,
-                                   const RtEns& ens = RtEns());
+                                   const RtEns& ens = RtEns(), const int* sched = nullptr, int total_steps = 0);
 bool rt_adjoint_split_has_bf16(const DevModel& m, bool use_helper);   // the net-split adjoint has a split (bf16-pipe) kernel for this configuration
 hipError_t rt_debug_read_stamps_split(unsigned long long* out16);   // diagnostic builds (-DCOLNDE_STAMPS): the phase stamps of this unit's kernels

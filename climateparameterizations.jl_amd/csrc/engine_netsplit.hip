@@ -389,383 +389,31 @@ __device__ __forceinline__ RtPhys rt_phys_of(const DevModel& m) {
 // chains; a second bare barrier per stage (B) hands the fluxes over.  Every wave executes exactly the barriers (B) and (A) in every stage.
 // SPLIT (COLNDE_MATRIX_BF16X3_EXACT; RK4 and, since round 4, RKC2): layers 1 and 2 on v_mfma_f32_16x16x32_bf16 from exact three-way operand splits (rt16_forward_kernel<ACT, true>;
 // image RT_SIMG2_*: rt_pack_split_ns_kernel); layer 3 and the biases stay on the tail of the fp32 image
+// SCHED (colnde_set_schedule; RK4): save interval iv takes sched[iv] steps instead of `substeps` — one scalar load per save interval, the same trip
+// counts in all four waves — and the tapes are indexed by the running step counter, total_steps = sum of sched in n_steps' place.  The body is one
+// text, rt16sh_forward_body.inc, compiled twice (RT16SH_SCHED = 0 | 1: a preprocessor switch, so that rt16sh_forward_kernel stays the machine code it
+// was — as an inlined function template with a SCHED parameter the same text came out as different code in every instantiation).
 template <int ACT, bool RICH, bool RKC = false, bool SPLIT = false>
 __global__ void __launch_bounds__(256)
 rt16sh_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ x0, const float* __restrict__ bcs,
                      const float* __restrict__ save_times, int n_save, int substeps, float* __restrict__ sol,
                      float* __restrict__ t16_tape, float* __restrict__ t16_ztape, int n_col, RtEns ens) {
-    // ensembles: blockIdx.y = model — its weight image, solution, tapes and closure constants (x0, bcs shared); grid.y = 1: one model
-    wimg += (size_t)blockIdx.y * ens.wimg;
-    if (sol) sol += (size_t)blockIdx.y * ens.sol;
-    if (t16_tape) t16_tape += (size_t)blockIdx.y * ens.tape;
-    if (t16_ztape) t16_ztape += (size_t)blockIdx.y * ens.ztape;
-    const RtPhys ph = ens.phys ? ens.phys[blockIdx.y] : rt_phys_of(m);
-    float* wl = rt_smem;
-    const u32x4* simg = reinterpret_cast<const u32x4*>(rt_smem);
-    f32x4v* ex = reinterpret_cast<f32x4v*>(rt_smem + ((RT_IMG_FLOATS + 3) & ~3));          // [2 buffers][3 variables][2 tiles][64 lanes]
-    if constexpr (SPLIT) {
-        // LDS: [bf16 operand image RT_SIMG2_WORDS][fp32 image from RT_W3C on: W3 and the biases][exchange][closure]
-        const u32x4* src = reinterpret_cast<const u32x4*>(wimg + RT_SIMG2_OFF);
-        u32x4* dst = reinterpret_cast<u32x4*>(rt_smem);
-        for (int e = threadIdx.x; e < RT_SIMG2_WORDS / 4; e += 256) dst[e] = src[e];
-        for (int e = threadIdx.x; e < RT_IMG_FLOATS - RT_W3C; e += 256) rt_smem[RT_SIMG2_WORDS + e] = wimg[RT_W3C + e];
-        wl = rt_smem + RT_SIMG2_WORDS - RT_W3C;                                            // wl[RT_W3C ...], wl[RT_B1C ...] as in the fp32 layout
-        ex = reinterpret_cast<f32x4v*>(rt_smem + RT_SIMG2_WORDS + ((RT_IMG_FLOATS - RT_W3C + 3) & ~3));
-    } else {
-        for (int e = threadIdx.x; e < RT_IMG_FLOATS; e += 256) wl[e] = wimg[e];
-    }
-    f32x4v* cl = ex + 2 * 384;                                                             // the helper wave's closure fluxes [3 variables][2 tiles][64 lanes]
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                     // 0..2: net = variable; 3: the helper (fourth SIMD)
-    const bool helper = role == 3;
-    const int n = helper ? 2 : role;
-    const int j = lane & 15, g = lane >> 4;
-    const int tile = blockIdx.x;
-    const int col = tile * 16 + j;
-    const bool valid = col < n_col;
-    const int colc = min(col, n_col - 1);
-    const int i_ = lane & 15, g_i = i_ >> 2, r_i = i_ & 3;
-    const bool live3 = r_i == 0 && g_i < 2;            // (SPLIT) this lane holds a row of the net's fourth layer-1 tile
-    const int l83 = g_i * 4 + (lane >> 4);
-    int a1b[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const int Q = 4 * t + r_i, f = 4 * Q + g_i;
-        a1b[t] = RT_W1C + (n * 50 + ((Q < 13 && f < 50) ? f : 0)) * RT_LD1 + 4 * g;       // padding rows read a valid row; never consumed
-    }
-    int a2b[2], a2l[2], a3b[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int Q2 = 4 * u + r_i;
-        const int row2 = n * 20 + (Q2 < 5 ? 4 * Q2 + g_i : 0);
-        a2b[u] = RT_W2C + row2 * RT_LD2 + g;
-        a2l[u] = RT_W2C + row2 * RT_LD2 + (g < 2 ? 48 + g : 50);
-        a3b[u] = RT_W3C + (n * 31 + 16 * u + i_ - 1) * RT_LD3 + g;
-    }
-    float bcb, bct, bc5;
-    {
-        const float* bp = bcs + (size_t)colc * 6;
-        bcb = bp[2 * n];
-        bct = bp[2 * n + 1];
-        bc5 = bp[5];
-    }
-    V16 Xs[3], Xn, Kacc;
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-#pragma unroll
-        for (int tau = 0; tau < 2; tau++) Xs[q].t[tau] = *reinterpret_cast<const f32x4v*>(x0 + (size_t)colc * 96 + q * 32 + 16 * tau + 4 * g);
-    // (wave-uniform n: a select, not a dynamic register index)
-#pragma unroll
-    for (int tau = 0; tau < 2; tau++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) Xn.t[tau][r] = n == 0 ? Xs[0].t[tau][r] : (n == 1 ? Xs[1].t[tau][r] : Xs[2].t[tau][r]);
-    if (sol && valid && !helper)
-#pragma unroll
-        for (int tau = 0; tau < 2; tau++) *reinterpret_cast<f32x4v*>(sol + ((size_t)col * n_save) * 96 + n * 32 + 16 * tau + 4 * g) = Xn.t[tau];
-    const int n_steps = (n_save - 1) * substeps;
-    // stepper: classical RK4 (nst = 4) or the s-stage RKC2 step of colnde_dev.h (m.rkc: coefficient table; increment form as in tile16's
-    // forward_kernel) — a template parameter: as a run-time switch it cost the RK4 latency kernels 8 % (8 simulations: 16.6 -> 18.2 ms)
-    const int nst = RKC ? m.nst : 4;
-    constexpr bool rkc = RKC;
-    const float* mu_t = m.rkc, *nu_t = m.rkc + RKC_LD, *mut_t = m.rkc + 2 * RKC_LD, *gat_t = m.rkc + 3 * RKC_LD, *c_t = m.rkc + 4 * RKC_LD;
-    float* tp = t16_tape ? t16_tape + (size_t)tile * n_steps * nst * 1536 + j * 96 + n * 32 + 4 * g : nullptr;
-    float* tz = (t16_ztape && !RICH) ? t16_ztape + (size_t)tile * n_steps * nst * (16 * 216) + j * 216 + n * 72 + g : nullptr;
-    float* tr = (t16_ztape && RICH) ? t16_ztape + (size_t)tile * n_steps * nst * RT16S_RREC + lane * 4 : nullptr;
-    const float Nz = 32.0f;
-    const float L2E = 1.4426950408889634f;
-    const float cU = m.sig_u * Nz, sU = m.sig_u * m.eps, cV = m.sig_v * Nz, sV = m.sig_v * m.eps, cB = m.B * Nz, sB = m.B * m.eps;
-    const float kE = 2.0f * ph.inv_dRi * L2E, oE = -2.0f * ph.Ric * ph.inv_dRi * L2E, cE = 30.0f * L2E;
-    const float nA = -0.5f * ph.nu_minus, nB = ph.nu0 + 0.5f * ph.nu_minus;
-    const float s0n = n == 0 ? m.s0[0] : (n == 1 ? m.s0[1] : m.s0[2]);
-    const float An = n == 0 ? m.A[0] : (n == 1 ? m.A[1] : m.A[2]);
-    int step = 0, buf = 0;
-    RT_STAMP_DECL;
-    for (int iv = 0; iv < n_save - 1; iv++) {
-        const float t0 = save_times[iv];
-        const float dt = (save_times[iv + 1] - t0) / (float)substeps;
-        for (int s = 0; s < substeps; s++, step++) {
-            const float ts = t0 + (float)s * dt;
-            Kacc.t[0] = (f32x4t)(0.0f);
-            Kacc.t[1] = (f32x4t)(0.0f);
-            V16 Ym1, Ym2, F0;                           // RKC2: d_{j-1}, d_{j-2} (increments Y_j - Y_0) and F_0 of variable n
-#pragma unroll
-            for (int tau = 0; tau < 2; tau++) { Ym1.t[tau] = (f32x4t)(0.0f); Ym2.t[tau] = (f32x4t)(0.0f); F0.t[tau] = (f32x4t)(0.0f); }
-#pragma nounroll
-            for (int st = 0; st < nst; st++) {
-                const float ca = rkc ? c_t[st] : (st == 0 ? 0.0f : (st == 3 ? 1.0f : 0.5f));
-                const float cb = (st == 0 || st == 3) ? 1.0f / 6.0f : 1.0f / 3.0f;
-                RT_STAMP_BEGIN();
-                f32x4v* eb = ex + buf * 384;
-                if (helper) {
-                    // ---- the Richardson-number closure of all three variables (predict_flux), once, on the fourth SIMD, while the net waves run
-                    //      their chains: diffusive face fluxes to LDS, and (RICH) the nine pullback coefficients to the tape
-                    float* orr = tr ? tr + ((size_t)step * nst + st) * RT16S_RREC : nullptr;
-                    V16 C[3];
-                    if (m.mpp) {
-                        const V16 Ud = shift_down16(Xs[0], lane, 0.0f), Vd = shift_down16(Xs[1], lane, 0.0f), Td = shift_down16(Xs[2], lane, 0.0f);
-                        const float f0 = -m.cs[0] * Nz, f1 = -m.cs[1] * Nz, f2 = -m.cs[2] * ph.inv_Pr * Nz;
-                        const float m0 = -m.cs[0], m1 = -m.cs[1], m2 = -m.cs[2] * ph.inv_Pr, nr = Nz * ph.c_rib;
-#pragma unroll
-                        for (int tau = 0; tau < 2; tau++)
-#pragma unroll
-                            for (int r = 0; r < 4; r += 2) {
-                                const f32x2v dU = {Xs[0].t[tau][r] - Ud.t[tau][r], Xs[0].t[tau][r + 1] - Ud.t[tau][r + 1]};
-                                const f32x2v dV = {Xs[1].t[tau][r] - Vd.t[tau][r], Xs[1].t[tau][r + 1] - Vd.t[tau][r + 1]};
-                                const f32x2v dT = {Xs[2].t[tau][r] - Td.t[tau][r], Xs[2].t[tau][r + 1] - Td.t[tau][r + 1]};
-                                const f32x2v a1 = dU * cU + sU, a2 = dV * cV + sV;
-                                const f32x2v s2 = a2 * a2 + a1 * a1;
-                                f32x2v rS;
-                                rS.x = __builtin_amdgcn_rcpf(s2.x);
-                                rS.y = __builtin_amdgcn_rcpf(s2.y);
-                                const f32x2v Ri = (dT * cB + sB) * rS;
-                                const f32x2v arg = Ri * kE + oE;
-                                f32x2v e;
-                                e.x = __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(arg.x, -cE, cE));
-                                e.y = __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(arg.y, -cE, cE));
-                                const f32x2v e1 = e + 1.0f;
-                                f32x2v rc;
-                                rc.x = __builtin_amdgcn_rcpf(e1.x);
-                                rc.y = __builtin_amdgcn_rcpf(e1.y);
-                                const f32x2v th = rc * -2.0f + 1.0f;
-                                const f32x2v nu = th * nA + nB;
-                                const f32x2v c0 = (nu * dU) * f0, c1 = (nu * dV) * f1, c2 = (nu * dT) * f2;
-                                C[0].t[tau][r] = c0.x; C[0].t[tau][r + 1] = c0.y;
-                                C[1].t[tau][r] = c1.x; C[1].t[tau][r + 1] = c1.y;
-                                C[2].t[tau][r] = c2.x; C[2].t[tau][r + 1] = c2.y;
-                                if (RICH && orr) {
-                                    const bool z0 = tau == 0 && r == 0 && g == 0;            // face 0 carries no diffusive flux
-                                    const f32x2v wf = (1.0f - th * th) * rS, wR = wf * Ri;
-                                    f32x2v pn = nu, pc0 = wR * (a1 * (-2.0f * m.sig_u)), pc1 = wR * (a2 * (-2.0f * m.sig_v)), pc2 = wf * m.B;
-                                    if (z0) { pn.x = 0.0f; pc0.x = 0.0f; pc1.x = 0.0f; pc2.x = 0.0f; }
-                                    float* o2 = orr + (36 + tau) * 256 + r;
-                                    const f32x2v d0 = dU * (m0 * nr), d1 = dV * (m1 * nr), d2 = dT * (m2 * nr), q0 = pn * m0, q1 = pn * m1, q2 = pn * m2;
-                                    *reinterpret_cast<f32x2v*>(o2 + 0 * 512) = d0;  *reinterpret_cast<f32x2v*>(o2 + 1 * 512) = d1;  *reinterpret_cast<f32x2v*>(o2 + 2 * 512) = d2;
-                                    *reinterpret_cast<f32x2v*>(o2 + 3 * 512) = q0;  *reinterpret_cast<f32x2v*>(o2 + 4 * 512) = q1;  *reinterpret_cast<f32x2v*>(o2 + 5 * 512) = q2;
-                                    *reinterpret_cast<f32x2v*>(o2 + 6 * 512) = pc0; *reinterpret_cast<f32x2v*>(o2 + 7 * 512) = pc1; *reinterpret_cast<f32x2v*>(o2 + 8 * 512) = pc2;
-                                }
-                            }
-                    } else {
-                        const V16 Td = shift_down16(Xs[2], lane, 0.0f);
-#pragma unroll
-                        for (int tau = 0; tau < 2; tau++)
-#pragma unroll
-                            for (int r = 0; r < 4; r++) {
-                                const bool in = !(tau == 0 && r == 0 && g == 0);
-                                const float gT = (Xs[2].t[tau][r] - Td.t[tau][r]) * Nz;
-                                C[0].t[tau][r] = 0.0f;
-                                C[1].t[tau][r] = 0.0f;
-                                C[2].t[tau][r] = (m.ca && in) ? -m.cs[2] * m.kappa * fminf(0.0f, gT) : 0.0f;
-                                if (RICH && orr && m.ca) {
-                                    float* o2 = orr + (36 + tau) * 256 + r;
-#pragma unroll
-                                    for (int a9 = 0; a9 < 9; a9++) o2[a9 * 512] = (a9 == 5 && in && gT < 0.0f) ? -m.cs[2] * m.kappa : 0.0f;
-                                }
-                            }
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; k++)
-#pragma unroll
-                        for (int tau = 0; tau < 2; tau++) cl[(k * 2 + tau) * 64 + lane] = C[k].t[tau];
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // (B) the closure is in LDS
-                } else {
-                V16 Xme;               // (element-wise selects on the wave-uniform n: a select between the aggregates becomes a scratch array)
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) Xme.t[tau][r] = n == 0 ? Xs[0].t[tau][r] : (n == 1 ? Xs[1].t[tau][r] : Xs[2].t[tau][r]);
-                if (tp) {
-                    float* o = tp + ((size_t)step * nst + st) * 1536;
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++) *reinterpret_cast<f32x4v*>(o + 16 * tau) = Xme.t[tau];
-                }
-                float* oz = tz ? tz + ((size_t)step * nst + st) * (16 * 216) : nullptr;
-                float* orr = tr ? tr + ((size_t)step * nst + st) * RT16S_RREC : nullptr;
-                const float top_raw = n == 2 ? rt_top_flux(m, bc5, ts + ca * dt) : bct;
-                RT_STAMP(0);
-                // ---- net n ----------------------------------------------------------------------------------------------
-                int lz = lane;
-                Bf3 XB[3];
-                if constexpr (SPLIT) {
-                    asm volatile("" : "+v"(lz));          // operand addresses stay (lane base + immediate): see rt16_forward_kernel
-                    // only the first k-block's split stands in front of the products: those of blocks 1 and 2 follow tile 0's MFMAs of the block before
-                    // (one wave per SIMD: nothing else hides their 88 vector instructions)
-                    const float x8[8] = {Xs[0].t[0][0], Xs[0].t[0][1], Xs[0].t[0][2], Xs[0].t[0][3], Xs[0].t[1][0], Xs[0].t[1][1], Xs[0].t[1][2], Xs[0].t[1][3]};
-                    XB[0] = bf3_split8(x8);
-                }
-                f32x4t A1[4];
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    f32x4t acc;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int Q = 4 * t + r;
-                        acc[r] = Q < 13 ? wl[RT_B1C + n * 50 + min(4 * Q + g, 49)] : 0.0f;
-                    }
-                    if constexpr (SPLIT) {
-                        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                        for (int q = 0; q < 3; q++) {
-                            Bf3 A;
-                            if (t < 3) A = rt16_ldA(simg, (n * 3 + t) * 3 + q, lz);
-                            else {          // the net's fourth tile holds quad 12 alone: rows 0 and 4 (features 48, 49); every other lane reads the zero operand
-                                const int at = live3 ? RT_SIMG2_T3 / 4 + (n * 3 + q) * 24 + l83 + (lz - lane) : RT_SIMG2_ZERO / 4 + (lz - lane);
-                                A.h = simg[at]; A.m = simg[at + (live3 ? 8 : 0)]; A.l = simg[at + (live3 ? 16 : 0)];
-                            }
-                            acc = mfma16_bf3(A, XB[q], acc);
-                            if (t == 0 && q < 2) {
-                                const int qn = q < 2 ? q + 1 : 2;
-                                const float n8[8] = {Xs[qn].t[0][0], Xs[qn].t[0][1], Xs[qn].t[0][2], Xs[qn].t[0][3], Xs[qn].t[1][0], Xs[qn].t[1][1], Xs[qn].t[1][2], Xs[qn].t[1][3]};
-                                XB[qn] = bf3_split8(n8);
-                            }
-                        }
-                        __builtin_amdgcn_s_setprio(0);
-                        RT_SCHED_FENCE();
-                    } else {
-                    const int base = a1b[t];
-                    acc = rt16_chain<24, 8>(wl, acc, [=](int k) { return base + (k >> 3) * 32 + ((k >> 2) & 1) * 16 + (k & 3); },
-                                            [&](int k) { return Xs[k >> 3].t[(k >> 2) & 1][k & 3]; });
-                    }
-                    if (oz) {
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int Q = 4 * t + r;
-                            if (Q < 13 && (Q < 12 || g < 2)) oz[4 * Q] = acc[r];             // feature 4 Q + g of layer 1
-                        }
-                    }
-                    if (RICH && orr) {
-                        f32x4t dd;
-                        rt16_act_pair<ACT>(acc, A1[t], dd);
-                        if (t == 3) { dd[1] = 0.0f; dd[2] = 0.0f; dd[3] = 0.0f; if (g >= 2) dd[0] = 0.0f; }   // padding: quads >= 13, features 50, 51
-                        *reinterpret_cast<f32x4v*>(orr + (n * 12 + t) * 256) = A1[t];
-                        *reinterpret_cast<f32x4v*>(orr + (n * 12 + 4 + t) * 256) = dd;
-                    } else
-                        A1[t] = rt_act4<ACT>(acc);
-                }
-                RT_STAMP(1);
-                f32x4t A2[2];
-                Bf3 HB[2];
-                if constexpr (SPLIT) {
-                    // the net's 13 quads of layer-1 activations as two 32-deep k-blocks (element e of block c: quad 8 c + e; three zero slots)
-#pragma unroll
-                    for (int c = 0; c < 2; c++) {
-                        float a8[8];
-#pragma unroll
-                        for (int e = 0; e < 8; e++) a8[e] = 8 * c + e < 13 ? A1[(8 * c + e) >> 2][(8 * c + e) & 3] : 0.0f;
-                        HB[c] = bf3_split8(a8);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 2; u++) {
-                    f32x4t acc;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) acc[r] = (4 * u + r < 5) ? wl[RT_B2C + n * 20 + 4 * (4 * u + r) + g] : 0.0f;
-                    if constexpr (SPLIT) {
-                        const Bf3 Aa = rt16_ldA(simg, 27 + (n * 2 + u) * 2, lz), Ab = rt16_ldA(simg, 27 + (n * 2 + u) * 2 + 1, lz);
-                        __builtin_amdgcn_s_setprio(1);
-                        acc = mfma16_bf3(Aa, HB[0], acc);
-                        acc = mfma16_bf3(Ab, HB[1], acc);
-                        __builtin_amdgcn_s_setprio(0);
-                        RT_SCHED_FENCE();
-                    } else {
-                    const int base = a2b[u], basel = a2l[u];
-                    acc = rt16_chain<13, 13>(wl, acc, [=](int k) { return k < 12 ? base + 4 * k : basel; },
-                                             [&](int k) { return A1[k >> 2][k & 3]; });
-                    }
-                    if (oz) {
-#pragma unroll
-                        for (int r = 0; r < 4; r++)
-                            if (4 * u + r < 5) oz[52 + 4 * (4 * u + r)] = acc[r];            // feature 4 Q2 + g of layer 2
-                    }
-                    if (RICH && orr) {
-                        f32x4t dd;
-                        rt16_act_pair<ACT>(acc, A2[u], dd);
-                        if (u == 1) { dd[1] = 0.0f; dd[2] = 0.0f; dd[3] = 0.0f; }                             // padding: quads >= 5
-                        *reinterpret_cast<f32x4v*>(orr + (n * 12 + 8 + u) * 256) = A2[u];
-                        *reinterpret_cast<f32x4v*>(orr + (n * 12 + 10 + u) * 256) = dd;
-                    } else
-                        A2[u] = rt_act4<ACT>(acc);
-                }
-                V16 O;
-#pragma unroll
-                for (int v = 0; v < 2; v++) {
-                    f32x4t acc;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) acc[r] = wl[RT_B3C + n * 32 + 16 * v + 4 * g + r];
-                    const int base = a3b[v];
-                    O.t[v] = rt16_chain<5, 5>(wl, acc, [=](int k) { return base + 4 * k; }, [&](int k) { return A2[k >> 2][k & 3]; });
-                }
-                RT_STAMP(2);
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");           // (B) the helper's closure fluxes are in LDS
-                // ---- physics: face flux = NN flux + closure flux, tendency of variable n (predict_flux / predict_NDE) ---------
-                V16 F;
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++) F.t[tau] = O.t[tau] + cl[(n * 2 + tau) * 64 + lane];
-                if (g == 0) F.t[0][0] = m.mpp ? (m.zero_w ? bcb - s0n : bcb) : (m.zero_w ? 0.0f : bcb);      // face 0: the bottom boundary
-                {
-                    const float top = m.zero_w ? top_raw - s0n : top_raw;
-                    const V16 Fu = shift_up16(F, lane, top);
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            float v = -An * (Fu.t[tau][r] - F.t[tau][r]);
-                            if (n == 0) v += m.cor_u * (m.sig_v * Xs[1].t[tau][r] + m.mu_v);
-                            if (n == 1) v -= m.cor_v * (m.sig_u * Xs[0].t[tau][r] + m.mu_u);
-                            F.t[tau][r] = v;                                                // F now holds the tendency of variable n
-                        }
-                }
-                RT_STAMP(3);
-                // ---- RK4 bookkeeping for variable n; the next stage input (or, after stage 3, the new state) is exchanged -------------
-                V16 Xnext;
-                if (rkc) {
-                    // Y_j, j = st + 1: d_1 = mu~_1 h F_0;  d_j = mu_j d_{j-1} + nu_j d_{j-2} + mu~_j h F_{j-1} + gamma~_j h F_0;  Y_s ends the step
-                    const int jj = st + 1;
-                    const float cmu = mu_t[jj], cnu = nu_t[jj], cmt = mut_t[jj] * dt, cga = gat_t[jj] * dt;
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++) {
-                        if (st == 0) F0.t[tau] = F.t[tau];
-                        const f32x4t dj = st == 0 ? cmt * F0.t[tau] : cmu * Ym1.t[tau] + cnu * Ym2.t[tau] + cmt * F.t[tau] + cga * F0.t[tau];
-                        Xnext.t[tau] = Xn.t[tau] + dj;
-                        Ym2.t[tau] = Ym1.t[tau];
-                        Ym1.t[tau] = dj;
-                        if (jj == nst) Xn.t[tau] = Xnext.t[tau];
-                    }
-                } else {
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++) {
-                    Kacc.t[tau] += cb * F.t[tau];
-                    if (st < 3) {
-                        const float can = st == 2 ? 1.0f : 0.5f;
-                        Xnext.t[tau] = Xn.t[tau] + (can * dt) * F.t[tau];
-                    } else {
-                        Xn.t[tau] += dt * Kacc.t[tau];
-                        Xnext.t[tau] = Xn.t[tau];
-                    }
-                }
-                }
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++) eb[(n * 2 + tau) * 64 + lane] = Xnext.t[tau];
-                }
-                // (a bare barrier behind the LDS writes: __syncthreads() would also drain vmcnt, i.e. wait for this stage's tape stores)
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-                for (int q = 0; q < 3; q++)
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++) Xs[q].t[tau] = eb[(q * 2 + tau) * 64 + lane];
-                buf ^= 1;
-                RT_STAMP(4);
-            }
-            if (s == substeps - 1 && sol && valid && !helper) {
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++)
-                    *reinterpret_cast<f32x4v*>(sol + ((size_t)col * n_save + iv + 1) * 96 + n * 32 + 16 * tau + 4 * g) = Xn.t[tau];
-            }
-        }
-    }
-#ifdef COLNDE_STAMPS_FWD
-    RT_STAMP_FLUSH();
-#endif
+#define RT16SH_SCHED 0
+#include "rt16sh_forward_body.inc"
+#undef RT16SH_SCHED
+}
+// ... under a step schedule (RK4): sched[n_save - 1] steps per save interval, total_steps their sum
+template <int ACT, bool RICH, bool SPLIT>
+__global__ void __launch_bounds__(256)
+rt16sh_forward_sched_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ x0, const float* __restrict__ bcs,
+                            const float* __restrict__ save_times, int n_save, float* __restrict__ sol,
+                            float* __restrict__ t16_tape, float* __restrict__ t16_ztape, int n_col, RtEns ens,
+                            const int* __restrict__ sched, int total_steps) {
+    constexpr bool RKC = false;
+    int substeps;                                          // the steps of the save interval in hand
+#define RT16SH_SCHED 1
+#include "rt16sh_forward_body.inc"
+#undef RT16SH_SCHED
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1283,452 +931,31 @@ rt16s_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __
 // v_mfma_f32_16x16x32_bf16 from exact three-way operand splits: δz1 is already held as the B operand needs it (lane group kq holds the features
 // 4 Q + kq of its column: two 32-deep k-blocks, quads 0..7 and 8..12 + padding), W1_n^T comes pre-split (RT_NSA_*), planes h and m from LDS in the
 // fp32 W1's place (the rest of the fp32 image moves down), plane l from L2 into registers before barrier B.
+// SCHED (colnde_set_schedule; RK4): the intervals and their steps are walked in reverse with the forward kernel's counts — sched[iv] steps in save
+// interval iv, the helper wave and the net waves alike — and the tapes and dW records are indexed by the running step counter (total_steps = sum of
+// sched in n_steps' place).  One text compiled twice, as for the forward kernel: rt16sh_adjoint_body.inc under RT16SH_SCHED = 0 | 1.
 template <int ACT, bool RICH, bool RKC = false, bool SPLIT = false>
 __global__ void __launch_bounds__(256)
 rt16sh_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ save_times, int n_save, int substeps,
                       const float* __restrict__ sol, const float* __restrict__ truth, const float* __restrict__ t16_tape,
                       const float* __restrict__ t16_ztape, LossWeights lw, float* __restrict__ slab, int n_col,
                       float* __restrict__ dwtape, RtEns ens) {
-    // ensembles: blockIdx.y = model — its weight image, solution, tapes, slab rows and closure constants (truth shared); grid.y = 1: one model
-    wimg += (size_t)blockIdx.y * ens.wimg;
-    sol += (size_t)blockIdx.y * ens.sol;
-    t16_tape += (size_t)blockIdx.y * ens.tape;
-    t16_ztape += (size_t)blockIdx.y * ens.ztape;
-    slab += (size_t)blockIdx.y * ens.slab;
-    dwtape += (size_t)blockIdx.y * ens.dwtape;
-    const RtPhys ph = ens.phys ? ens.phys[blockIdx.y] : rt_phys_of(m);
-    // SPLIT: LDS holds the fp32 image from W2 on (addressed through wl as before: wl[RT_W2C + x]), no fp32 W1
-    constexpr int IMG0 = SPLIT ? RT_W2C : 0;
-    constexpr int IMGF = ((RT_IMG_FLOATS - IMG0) + 3) & ~3;
-    float* wl = rt_smem - IMG0;
-    for (int e = IMG0 + threadIdx.x; e < RT_IMG_FLOATS; e += 256) wl[e] = wimg[e];
-    float* lbase = rt_smem + IMGF;
-    f32x4v* ex = reinterpret_cast<f32x4v*>(lbase);                    // the nets' parts of x̄: [3 nets][6 tiles][64 lanes]
-    f32x4v* dOl = ex + 3 * 6 * 64;                                     // the helper's dO: [3 variables][2 tiles][64 lanes]
-    float* stg_all = lbase + (3 * 6 * 64 + 3 * 2 * 64) * 4;           // record staging: see rt16s_adjoint_kernel
-    for (int e = threadIdx.x; e < 3 * RT16S_STG; e += 256) stg_all[e] = 0.0f;
-    const u32x4* hm = reinterpret_cast<const u32x4*>(stg_all + 3 * RT16S_STG);      // SPLIT: [net][kb][tile][h, m][64 lanes] operand planes
-    if constexpr (SPLIT) {
-        const u32x4* src = reinterpret_cast<const u32x4*>(wimg + RT_NSA_OFF);
-        u32x4* dst = reinterpret_cast<u32x4*>(stg_all + 3 * RT16S_STG);
-        for (int e = threadIdx.x; e < RT_NSA_HM_WORDS / 4; e += 256) dst[e] = src[e];
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool helper = role == 3;
-    const int n = helper ? 0 : role;                                    // the net of a net wave
-    const int j = lane & 15, g = lane >> 4;
-    const int tile = blockIdx.x;
-    const int col = tile * 16 + j;
-    const bool valid = col < n_col;
-    const int colc = min(col, n_col - 1);
-    const int n_steps = (n_save - 1) * substeps;
-    const int nst = RKC ? m.nst : 4;                                    // RHS evaluations (= tape records) per step: 4 (RK4) or s (RKC2)
-    constexpr bool rkc = RKC;
-    const float* tp = t16_tape + (size_t)tile * n_steps * nst * 1536 + j * 96 + 4 * g;
-    const bool phys = m.mpp || m.ca;
-    float* out = slab + (size_t)tile * (m.n_params + 8);
-
-    if (helper) {
-        // ================================================= the helper wave: λ, x̄, loss injection, physics pullback ======================
-        const float* tzr = t16_ztape + (size_t)tile * n_steps * nst * RT16S_RREC + lane * 4;             // RICH: the rich tape
-        V16 lam[3], xb[3], xbs[3];
-#pragma unroll
-        for (int q = 0; q < 3; q++)
-#pragma unroll
-            for (int tau = 0; tau < 2; tau++) { lam[q].t[tau] = (f32x4t)(0.0f); xb[q].t[tau] = (f32x4t)(0.0f); xbs[q].t[tau] = (f32x4t)(0.0f); }
-        float sum_d[3] = {0.0f, 0.0f, 0.0f}, sum_g[3] = {0.0f, 0.0f, 0.0f};
-        auto inject = [&](int sv, bool add) __attribute__((always_inline)) {
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                V16 d;
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++) {
-                    const size_t o = ((size_t)colc * n_save + sv) * 96 + q * 32 + 16 * tau + 4 * g;
-                    const f32x4v a = *reinterpret_cast<const f32x4v*>(sol + o);
-                    const f32x4v b = *reinterpret_cast<const f32x4v*>(truth + o);
-#pragma unroll
-                    for (int e = 0; e < 4; e++) d.t[tau][e] = valid ? a[e] - b[e] : 0.0f;
-                }
-                const V16 dd = shift_down16(d, lane, 0.0f);
-                V16 gg;
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        gg.t[tau][r] = (tau == 0 && r == 0 && g == 0) ? 0.0f : (d.t[tau][r] - dd.t[tau][r]) * 32.0f;
-                        sum_d[q] += d.t[tau][r] * d.t[tau][r];
-                        sum_g[q] += gg.t[tau][r] * gg.t[tau][r];
-                    }
-                if (add) {
-                    const V16 gu_ = shift_up16(gg, lane, 0.0f);
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++)
-                            lam[q].t[tau][r] += 2.0f * lw.w[q] * d.t[tau][r] + 2.0f * lw.w[3 + q] * 32.0f * (gg.t[tau][r] - gu_.t[tau][r]);
-                }
-            }
-        };
-        // what the pullback reads from the tapes, one stage ahead: RICH the nine coefficients, otherwise the stage input
-        PhysC Pp;
-        V16 Xp[3];
-        auto prefetch = [&](int qs) __attribute__((always_inline)) {
-            if (RICH) {
-                if (phys) {
-                    const float* sr = tzr + (size_t)qs * RT16S_RREC;
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++) {
-                        Pp.dn0.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 0 + tau) * 256);
-                        Pp.dn1.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 2 + tau) * 256);
-                        Pp.dn2.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 4 + tau) * 256);
-                        Pp.nu0.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 6 + tau) * 256);
-                        Pp.nu1.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 8 + tau) * 256);
-                        Pp.nu2.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 10 + tau) * 256);
-                        Pp.c0.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 12 + tau) * 256);
-                        Pp.c1.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 14 + tau) * 256);
-                        Pp.c2.t[tau] = *reinterpret_cast<const f32x4v*>(sr + (36 + 16 + tau) * 256);
-                    }
-                }
-            } else {
-                const float* sx = tp + (size_t)qs * 1536;
-#pragma unroll
-                for (int q = 0; q < 3; q++)
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++) Xp[q].t[tau] = *reinterpret_cast<const f32x4v*>(sx + q * 32 + 16 * tau);
-            }
-        };
-        // RKC2 (discrete adjoint of the recurrence, as in tile16's adjoint_kernel): cotangents of Y_{j-1} (yb1), Y_{j-2} (yb2), Y_0 (yb0), F_0 (f0b);
-        // lam is the cotangent of Y_j.  The convective-adjustment switch is pulled back with ONE pattern per step, that of Y_{s-1}:
-        // the physics data of every stage of a step are then read from the record of its last stage.
-        V16 yb0[3], yb1[3], yb2[3], f0b[3];
-#pragma unroll
-        for (int q = 0; q < 3; q++)
-#pragma unroll
-            for (int tau = 0; tau < 2; tau++) { yb0[q].t[tau] = (f32x4t)(0.0f); yb1[q].t[tau] = (f32x4t)(0.0f); yb2[q].t[tau] = (f32x4t)(0.0f); f0b[q].t[tau] = (f32x4t)(0.0f); }
-        const float* mu_t = m.rkc, *nu_t = m.rkc + RKC_LD, *mut_t = m.rkc + 2 * RKC_LD, *gat_t = m.rkc + 3 * RKC_LD, *kap_t = m.rkc + 5 * RKC_LD;
-        const bool one_pattern = rkc && m.ca && !m.mpp;
-#define PHYS_Q(q) (one_pattern ? ((q) / nst) * nst + nst - 1 : (q))
-        inject(0, false);
-        prefetch(PHYS_Q(n_steps * nst - 1));
-        for (int iv = n_save - 2; iv >= 0; iv--) {
-            const float dt = (save_times[iv + 1] - save_times[iv]) / (float)substeps;
-            inject(iv + 1, true);
-            for (int s = substeps - 1; s >= 0; s--) {
-                const int step = iv * substeps + s;
-#pragma nounroll
-                for (int st = nst - 1; st >= 0; st--) {
-                    const float cwl = (st == 0 || st == 3) ? dt / 6.0f : dt / 3.0f;
-                    const float cwx = st == 3 ? 0.0f : (st == 2 ? dt : 0.5f * dt);
-                    const int qs = step * nst + st;
-                    V16 kb[3], xbp[3];
-                    if (rkc) {
-                        // stage input Y_st feeds Y_j, j = st + 1, through mu~_j h F_st
-                        const float cmu = mu_t[st + 1], cnu = nu_t[st + 1], cmt = mut_t[st + 1] * dt, cga = gat_t[st + 1] * dt, ck0 = kap_t[st + 1];
-#pragma unroll
-                        for (int q = 0; q < 3; q++)
-#pragma unroll
-                            for (int tau = 0; tau < 2; tau++) {
-                                if (st < nst - 1) {        // lam = cotangent of Y_j, complete once the previous pullback (xb: J(Y_j)^T F̄_j) is added
-                                    lam[q].t[tau] = yb1[q].t[tau] + xb[q].t[tau];
-                                    yb1[q].t[tau] = yb2[q].t[tau];
-                                    yb2[q].t[tau] = (f32x4t)(0.0f);
-                                }
-                                if (st >= 1) {
-                                    yb0[q].t[tau] += ck0 * lam[q].t[tau];
-                                    yb1[q].t[tau] += cmu * lam[q].t[tau];
-                                    yb2[q].t[tau] += cnu * lam[q].t[tau];
-                                    f0b[q].t[tau] += cga * lam[q].t[tau];
-                                    kb[q].t[tau] = cmt * lam[q].t[tau];
-                                } else {                   // Y_1 = Y_0 + mu~_1 h F_0: lam holds Ȳ_1, yb1 the nu_2 part of Ȳ_0
-                                    yb0[q].t[tau] += lam[q].t[tau] + yb1[q].t[tau];
-                                    kb[q].t[tau] = f0b[q].t[tau] + cmt * lam[q].t[tau];
-                                    yb1[q].t[tau] = (f32x4t)(0.0f);
-                                    f0b[q].t[tau] = (f32x4t)(0.0f);
-                                }
-                            }
-                    } else {
-#pragma unroll
-                    for (int q = 0; q < 3; q++)
-#pragma unroll
-                        for (int tau = 0; tau < 2; tau++) kb[q].t[tau] = cwl * lam[q].t[tau] + cwx * xb[q].t[tau];
-                    }
-                    if (RICH) {
-                        rt16_physics_apply(m, Pp, kb, lane, xbp);                        // kb now holds dO
-                        if (qs > 0) prefetch(PHYS_Q(qs - 1));
-                    } else {
-                        V16 X[3];
-#pragma unroll
-                        for (int q = 0; q < 3; q++) X[q] = Xp[q];
-                        if (qs > 0) prefetch(PHYS_Q(qs - 1));
-                        rt16_physics_vjp(m, ph, X, kb, lane, xbp);
-                    }
-#pragma unroll
-                    for (int q = 0; q < 3; q++)
-#pragma unroll
-                        for (int tau = 0; tau < 2; tau++) dOl[(q * 2 + tau) * 64 + lane] = kb[q].t[tau];
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // (B) dO is in LDS
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // (A) the nets' parts of x̄ are in LDS
-#pragma unroll
-                    for (int q = 0; q < 3; q++)
-#pragma unroll
-                        for (int tau = 0; tau < 2; tau++) {
-                            const f32x4v c0 = ex[(0 * 6 + q * 2 + tau) * 64 + lane], c1 = ex[(1 * 6 + q * 2 + tau) * 64 + lane],
-                                         c2 = ex[(2 * 6 + q * 2 + tau) * 64 + lane];
-                            xb[q].t[tau] = xbp[q].t[tau] + ((c0 + c1) + c2);
-                            xbs[q].t[tau] += xb[q].t[tau];
-                        }
-                }
-                // RK4: λ_n = λ_{n+1} + x̄_1 + x̄_2 + x̄_3 + x̄_4;  RKC2: λ_n = Ȳ_0 + J(Y_0)^T F̄_0
-#pragma unroll
-                for (int q = 0; q < 3; q++)
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++) {
-                        if (rkc) { lam[q].t[tau] = yb0[q].t[tau] + xb[q].t[tau]; yb0[q].t[tau] = (f32x4t)(0.0f); }
-                        else lam[q].t[tau] += xbs[q].t[tau];
-                        xbs[q].t[tau] = (f32x4t)(0.0f);
-                    }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            float sd = sum_d[q], sg = sum_g[q];
-            for (int off = 32; off > 0; off >>= 1) { sd += __shfl_down(sd, off); sg += __shfl_down(sg, off); }
-            if (lane == 0) { out[m.n_params + q] = sd; out[m.n_params + 3 + q] = sg; }
-        }
-        if (lane == 0) { out[m.n_params + 6] = 0.0f; out[m.n_params + 7] = 0.0f; }
-        return;
-    }
-
-    // ===================================================== the three net waves ========================================================
-    float* stg = stg_all + n * RT16S_STG;
-    const int i_ = lane & 15, g_i = i_ >> 2, r_i = i_ & 3;
-    int b3T[2], b2T[4];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int Q2 = 4 * u + r_i;
-        b3T[u] = RT_W3C + (n * 31 + 4 * g - 1) * RT_LD3 + (Q2 < 5 ? 4 * Q2 + g_i : 20);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const int Q = 4 * t + r_i, f = 4 * Q + g_i;
-        b2T[t] = RT_W2C + (n * 20 + g) * RT_LD2 + ((Q < 13 && f < 50) ? f : 50);
-    }
-    const int b1T = RT_W1C + (n * 50 + g) * RT_LD1 + i_;
-    f32x4t gb1[4], gb2[2], gb3[2];                         // bias gradients: this lane's column of every delta, summed over the stages
-#pragma unroll
-    for (int t = 0; t < 4; t++) gb1[t] = (f32x4t)(0.0f);
-#pragma unroll
-    for (int u = 0; u < 2; u++) { gb2[u] = (f32x4t)(0.0f); gb3[u] = (f32x4t)(0.0f); }
-    const float* tz = RICH ? t16_ztape + (size_t)tile * n_steps * nst * RT16S_RREC + lane * 4
-                           : t16_ztape + (size_t)tile * n_steps * nst * RT16S_ZREC + j * 216 + n * 72 + g;
-    float* rec0 = dwtape + (size_t)tile * n_steps * nst * RT16S_REC;
-    int stg_rd[11], rec_wr[11];
-#pragma unroll
-    for (int i = 0; i < 11; i++) {
-        const int e = 64 * i + lane, c = e / 44, f4 = e - 44 * c;
-        stg_rd[i] = c * 180 + 4 * f4;
-        rec_wr[i] = c * 720 + 96 + (f4 < 18 ? n * 104 + 4 * f4 : (3 + n) * 104 + 4 * (f4 - 18));
-    }
-    float* sw = stg + j * 180 + g;
-    // this net's tape data, one stage ahead: variable n of the stage input, and the activations with their derivatives (RICH) or the
-    // pre-activations they are evaluated from
-    V16 Xnp;
-    float z1p[13], z2p[5];
-    f32x4t adp[12];
-    auto prefetch = [&](int qs) __attribute__((always_inline)) {
-        const float* sx = tp + (size_t)qs * 1536;
-#pragma unroll
-        for (int tau = 0; tau < 2; tau++) Xnp.t[tau] = *reinterpret_cast<const f32x4v*>(sx + n * 32 + 16 * tau);
-        if (RICH) {
-            const float* sr = tz + (size_t)qs * RT16S_RREC;
-#pragma unroll
-            for (int e = 0; e < 12; e++) adp[e] = *reinterpret_cast<const f32x4v*>(sr + (n * 12 + e) * 256);
-        } else {
-            const float* sz = tz + (size_t)qs * RT16S_ZREC;
-#pragma unroll
-            for (int Q = 0; Q < 13; Q++) z1p[Q] = (Q < 12 || g < 2) ? sz[4 * Q] : 0.0f;
-#pragma unroll
-            for (int Q2 = 0; Q2 < 5; Q2++) z2p[Q2] = sz[52 + 4 * Q2];
-        }
-    };
-    prefetch(n_steps * nst - 1);
-    RT_STAMP_DECL;
-    for (int iv = n_save - 2; iv >= 0; iv--) {
-        for (int s = substeps - 1; s >= 0; s--) {
-            const int step = iv * substeps + s;
-#pragma nounroll
-            for (int st = nst - 1; st >= 0; st--) {
-                const int qs = step * nst + st;
-                RT_STAMP_BEGIN();
-                // ---- before (B), beside the helper's pullback: everything that depends on the tapes alone ----
-                f32x4t A1[4], D1[4], A2[2], D2[2];
-                const V16 Xme = Xnp;
-                if (RICH) {
-#pragma unroll
-                    for (int t = 0; t < 4; t++) { A1[t] = adp[t]; D1[t] = adp[4 + t]; }
-#pragma unroll
-                    for (int u = 0; u < 2; u++) { A2[u] = adp[8 + u]; D2[u] = adp[10 + u]; }
-                } else {
-#pragma unroll
-                    for (int t = 0; t < 4; t++) {
-                        f32x4t z;
-#pragma unroll
-                        for (int r = 0; r < 4; r++) z[r] = (4 * t + r < 13) ? z1p[(4 * t + r) < 13 ? 4 * t + r : 0] : 0.0f;
-                        rt16_act_pair<ACT>(z, A1[t], D1[t]);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 2; u++) {
-                        f32x4t z;
-#pragma unroll
-                        for (int r = 0; r < 4; r++) z[r] = (4 * u + r < 5) ? z2p[(4 * u + r) < 5 ? 4 * u + r : 0] : 0.0f;
-                        rt16_act_pair<ACT>(z, A2[u], D2[u]);
-                    }
-#pragma unroll
-                    for (int r = 1; r < 4; r++) { D1[3][r] = 0.0f; D2[1][r] = 0.0f; }   // padding quads: Q >= 13, Q2 >= 5
-                    if (g >= 2) D1[3][0] = 0.0f;                                         // features 50, 51 of quad 12
-                }
-                if (qs > 0) prefetch(qs - 1);
-                // (SPLIT) the twelve l-plane operands of this net's W1^T products, from L2: requested here, consumed behind barrier B and two chains
-                // ... and the 24 h / m plane fragments from LDS: all of them before barrier B too, so that behind it the products wait for nothing
-                // (fetched tile by tile in front of their products they exposed an LDS round trip per tile: 8.03 instead of 8.2 ms, no more)
-                u32x4 Lr[12], Hm[24];
-                if constexpr (SPLIT) {
-                    int lz = lane;                        // (opaque: left loop-invariant the loads are hoisted out of the time loop and their registers pinned)
-                    asm volatile("" : "+v"(lz));
-                    const u32x4* lg = reinterpret_cast<const u32x4*>(wimg + RT_NSA_OFF + RT_NSA_L) + n * 12 * 64 + lz;
-#pragma unroll
-                    for (int u = 0; u < 12; u++) Lr[u] = lg[u * 64];
-                    const u32x4* hn = hm + n * 24 * 64 + lz;
-#pragma unroll
-                    for (int u = 0; u < 24; u++) Hm[u] = hn[u * 64];
-                }
-                float a3[2][8], a2[4][5];
-                rt16_fetch_ops<2, 8>(wl, a3, [&](int u, int k) { return b3T[u] + (16 * (k >> 2) + (k & 3)) * RT_LD3; });
-                rt16_fetch_ops<4, 5>(wl, a2, [&](int t, int k) { return b2T[t] + 4 * k * RT_LD2; });
-                float* rec = rec0 + (size_t)qs * RT16S_REC;
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++) *reinterpret_cast<f32x4v*>(rec + j * 720 + n * 32 + 16 * tau + 4 * g) = Xme.t[tau];
-#pragma unroll
-                for (int Q = 0; Q < 13; Q++)
-                    if (Q < 12 || g < 2) sw[4 * Q] = A1[Q >> 2][Q & 3];
-#pragma unroll
-                for (int Q2 = 0; Q2 < 5; Q2++) sw[52 + 4 * Q2] = A2[Q2 >> 2][Q2 & 3];
-                RT_STAMP(0);
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");           // (B) the helper's dO is in LDS
-                RT_STAMP(1);
-                V16 dO;
-#pragma unroll
-                for (int tau = 0; tau < 2; tau++) dO.t[tau] = dOl[(n * 2 + tau) * 64 + lane];
-                // (3) δz2 = (W3^T dO) ∘ act'(z2)
-                f32x4t dZ2[2] = {(f32x4t)(0.0f), (f32x4t)(0.0f)};
-                rt16_run_ops<2, 8>(a3, dZ2, [&](int k) { return dO.t[k >> 2][k & 3]; });
-#pragma unroll
-                for (int u = 0; u < 2; u++) dZ2[u] *= D2[u];
-                float a1[2][2][13];
-                if constexpr (!SPLIT) rt16_fetch_ops<2, 13>(wl, a1[0], [&](int c, int k) { return b1T + 16 * c + 4 * k * RT_LD1; });
-                RT_SCHED_HARD();
-                // (4) δz1 = (W2^T δz2) ∘ act'(z1)
-                f32x4t dZ1[4] = {(f32x4t)(0.0f), (f32x4t)(0.0f), (f32x4t)(0.0f), (f32x4t)(0.0f)};
-                rt16_run_ops<4, 5>(a2, dZ1, [&](int k) { return dZ2[k >> 2][k & 3]; });
-#pragma unroll
-                for (int t = 0; t < 4; t++) dZ1[t] *= D1[t];
-                RT_STAMP(2);
-                {
-#pragma unroll
-                    for (int Q = 0; Q < 13; Q++)
-                        if (Q < 12 || g < 2) sw[72 + 4 * Q] = dZ1[Q >> 2][Q & 3];
-#pragma unroll
-                    for (int Q2 = 0; Q2 < 5; Q2++) sw[124 + 4 * Q2] = dZ2[Q2 >> 2][Q2 & 3];
-                    float* s3 = stg + j * 180 + 144 + 4 * g - 1;                         // output o = face - 1
-#pragma unroll
-                    for (int v = 0; v < 2; v++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++)
-                            if (!(v == 0 && r == 0 && g == 0)) s3[16 * v + r] = dO.t[v][r];
-                    // (deferring this copy to the top of the next stage, beside the helper's pullback, was measured: 7.58 -> 7.63 ms in front of that
-                    //  stage's loads, 7.89 ms behind them — the stores then sit in front of the l-plane loads in the in-order vmcnt queue)
-#pragma unroll
-                    for (int i = 0; i < 11; i++) *reinterpret_cast<f32x4v*>(rec + rec_wr[i]) = *reinterpret_cast<const f32x4v*>(stg + stg_rd[i]);
-                }
-#pragma unroll
-                for (int t = 0; t < 4; t++) gb1[t] += dZ1[t];
-#pragma unroll
-                for (int u = 0; u < 2; u++) { gb2[u] += dZ2[u]; gb3[u] += dO.t[u]; }
-                RT_STAMP(3);
-                // (5) this net's part of the state cotangent, W1_n^T δz1 (6 tiles x 13 k-steps)
-                if constexpr (SPLIT) {
-                    // δz1 as the B operand of two 32-deep k-blocks: element e of k-block kb is quad 8 kb + e of this lane group (padding quads are zero)
-                    const float d80[8] = {dZ1[0][0], dZ1[0][1], dZ1[0][2], dZ1[0][3], dZ1[1][0], dZ1[1][1], dZ1[1][2], dZ1[1][3]};
-                    const float d81[8] = {dZ1[2][0], dZ1[2][1], dZ1[2][2], dZ1[2][3], dZ1[3][0], dZ1[3][1], dZ1[3][2], dZ1[3][3]};
-                    // the first k-block over all six tiles, the second k-block's split issued in pieces between them (one wave per SIMD: nothing else hides
-                    // its 44 vector instructions), then the second k-block
-                    const Bf3 B0 = bf3_split8(d80);
-                    Bf3 B1 = B0;
-                    f32x4t c2[6];
-#pragma unroll
-                    for (int tl = 0; tl < 6; tl++) {
-                        Bf3 A0;
-                        A0.h = Hm[tl * 2 + 0]; A0.m = Hm[tl * 2 + 1]; A0.l = Lr[tl];
-                        c2[tl] = mfma16_bf3(A0, B0, (f32x4t)(0.0f));
-                        RT_SCHED_FENCE();
-                        if (tl < 4) {
-                            bf3_split_pair(d81[2 * tl], d81[2 * tl + 1], tl, B1);
-                            RT_SCHED_FENCE();
-                        }
-                    }
-#pragma unroll
-                    for (int tl = 0; tl < 6; tl++) {
-                        Bf3 A1_;
-                        A1_.h = Hm[(6 + tl) * 2 + 0]; A1_.m = Hm[(6 + tl) * 2 + 1]; A1_.l = Lr[6 + tl];
-                        c2[tl] = mfma16_bf3(A1_, B1, c2[tl]);
-                        ex[(n * 6 + tl) * 64 + lane] = c2[tl];
-                        RT_SCHED_FENCE();
-                    }
-                } else
-#pragma unroll
-                for (int q = 0; q < 3; q++) {
-                    if (q < 2) rt16_fetch_ops<2, 13>(wl, a1[(q + 1) & 1], [&](int c, int k) { return b1T + 32 * (q + 1) + 16 * c + 4 * k * RT_LD1; });
-                    RT_SCHED_HARD();
-                    f32x4t c2[2] = {(f32x4t)(0.0f), (f32x4t)(0.0f)};
-                    rt16_run_ops<2, 13>(a1[q & 1], c2, [&](int k) { return dZ1[k >> 2][k & 3]; });
-#pragma unroll
-                    for (int tau = 0; tau < 2; tau++) ex[(n * 6 + q * 2 + tau) * 64 + lane] = c2[tau];
-                    RT_SCHED_HARD();
-                }
-                RT_STAMP(4);
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");           // (A) this net's part of x̄ is in LDS
-                RT_STAMP(5);
-            }
-        }
-    }
-#ifndef COLNDE_STAMPS_FWD
-    RT_STAMP_FLUSH();
-#endif
-    // ---- the tile's slab row: bias gradients of net n (sums over the 16 columns = the lanes of a g-group); the loss sums are the helper's ----
-    auto colsum = [&](float v) {
-        v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-        return v;
-    };
-#pragma unroll
-    for (int Q = 0; Q < 13; Q++) {
-        const float v = colsum(gb1[Q >> 2][Q & 3]);
-        if (j == 0 && (Q < 12 || g < 2)) out[n * m.net_size + m.b_off[0] + 4 * Q + g] = v;
-    }
-#pragma unroll
-    for (int Q2 = 0; Q2 < 5; Q2++) {
-        const float v = colsum(gb2[Q2 >> 2][Q2 & 3]);
-        if (j == 0) out[n * m.net_size + m.b_off[1] + 4 * Q2 + g] = v;
-    }
-#pragma unroll
-    for (int v_ = 0; v_ < 2; v_++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float v = colsum(gb3[v_][r]);
-            const int face = 16 * v_ + 4 * g + r;
-            if (j == 0 && face >= 1) out[n * m.net_size + m.b_off[2] + face - 1] = v;
-        }
+#define RT16SH_SCHED 0
+#include "rt16sh_adjoint_body.inc"
+#undef RT16SH_SCHED
+}
+// ... under a step schedule (RK4): the counts the forward kernel stepped with
+template <int ACT, bool RICH, bool SPLIT>
+__global__ void __launch_bounds__(256)
+rt16sh_adjoint_sched_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ save_times, int n_save,
+                            const float* __restrict__ sol, const float* __restrict__ truth, const float* __restrict__ t16_tape,
+                            const float* __restrict__ t16_ztape, LossWeights lw, float* __restrict__ slab, int n_col,
+                            float* __restrict__ dwtape, RtEns ens, const int* __restrict__ sched, int total_steps) {
+    constexpr bool RKC = false;
+    int substeps;                                          // the steps of the save interval in hand
+#define RT16SH_SCHED 1
+#include "rt16sh_adjoint_body.inc"
+#undef RT16SH_SCHED
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1773,6 +1000,18 @@ static Rt16shForwardFn rt16sh_forward_pick(int act, bool rich, bool rkc, bool sp
     });
     return k;
 }
+using Rt16shForwardSchedFn = decltype(&rt16sh_forward_sched_kernel<COLNDE_ACT_RELU, false, false>);
+using Rt16shAdjointSchedFn = decltype(&rt16sh_adjoint_sched_kernel<COLNDE_ACT_RELU, false, false>);
+static Rt16shForwardSchedFn rt16sh_forward_sched_pick(int act, bool rich, bool split) {
+    Rt16shForwardSchedFn k = nullptr;
+    with_act(act, [&](auto A) { with_bools([&](auto R, auto S) { k = rt16sh_forward_sched_kernel<decltype(A)::value, decltype(R)::value, decltype(S)::value>; }, rich, split); });
+    return k;
+}
+static Rt16shAdjointSchedFn rt16sh_adjoint_sched_pick(int act, bool rich, bool split) {
+    Rt16shAdjointSchedFn k = nullptr;
+    with_act(act, [&](auto A) { with_bools([&](auto R, auto S) { k = rt16sh_adjoint_sched_kernel<decltype(A)::value, decltype(R)::value, decltype(S)::value>; }, rich, split); });
+    return k;
+}
 static Rt16sAdjointFn rt16s_adjoint_pick(int act, bool rich) {
     Rt16sAdjointFn k = nullptr;
     with_act(act, [&](auto A) { with_bools([&](auto R) { k = rt16s_adjoint_kernel<decltype(A)::value, decltype(R)::value>; }, rich); });
@@ -1799,6 +1038,10 @@ hipError_t rt_set_attributes_split() {
                     set(rt16sh_forward_pick(A, a, b, c));
                     set(rt16sh_adjoint_pick(A, a, b, c));
                 }
+            for (int c = 0; c < 2; c++) {
+                set(rt16sh_forward_sched_pick(A, a, c));
+                set(rt16sh_adjoint_sched_pick(A, a, c));
+            }
         }
     });
     return e;
@@ -1807,15 +1050,20 @@ hipError_t rt_set_attributes_split() {
 // the three-wavefronts-per-tile forward solve of the latency points; tapes (optional) in tile16's formats
 hipError_t rt_launch_forward_split(const DevModel& m, const float* wimg, const float* x0, const float* bcs, const float* save_times,
                                    int n_save, int substeps, float* sol, float* t16_tape, float* t16_ztape, int n_col, bool rich, bool use_helper, bool want_split, hipStream_t stream,
-                                   const RtEns& ens) {
+                                   const RtEns& ens, const int* sched, int total_steps) {
     const dim3 grid((n_col + 15) / 16), block(192);
     const dim3 gridh((n_col + 15) / 16, ens.n_models), blockh(256);       // ensembles: grid.y = model (the four-wave kernels only)
     if (m.nst != 4 && !(m.rkc && use_helper)) return hipErrorInvalidValue;      // RKC2 lives in the four-wave kernels only
+    if (sched && (!use_helper || m.rkc || m.nst != 4 || total_steps < n_save - 1)) return hipErrorInvalidValue;   // a schedule: the four-wave RK4 kernels only
     if (ens.n_models != 1 && !use_helper) return hipErrorInvalidValue;
     // layers 1 and 2 on the bf16 pipe with exact three-way operand splitting (COLNDE_MATRIX_BF16X3_EXACT; the four-wave kernels, RK4 and RKC2)
     const bool split = want_split && use_helper;
     if (split) hipLaunchKernelGGL(rt_pack_split_ns_kernel, dim3(41, ens.n_models), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_SIMG2_OFF, (int)ens.wimg);
-    if (use_helper) {
+    if (sched) {
+        const auto k = rt16sh_forward_sched_pick(m.acts[0], rich, split);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, gridh, blockh, rt16sh_forward_lds_bytes(split), stream, m, wimg, x0, bcs, save_times, n_save, sol, t16_tape, t16_ztape, n_col, ens, sched, total_steps);
+    } else if (use_helper) {
         const auto k = rt16sh_forward_pick(m.acts[0], rich, m.rkc != nullptr, split);
         if (!k) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k, gridh, blockh, rt16sh_forward_lds_bytes(split), stream, m, wimg, x0, bcs, save_times, n_save, substeps, sol, t16_tape, t16_ztape, n_col, ens);
@@ -1832,7 +1080,8 @@ bool rt_adjoint_split_has_bf16(const DevModel& m, bool use_helper) { return use_
 hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const float* save_times, int n_save, int substeps, const float* sol,
                                    const float* truth, const float* t16_tape, const float* t16_ztape, const LossWeights& lw, float* slab,
                                    int n_col, float* dwtape, bool rich, bool use_helper, bool want_split, hipStream_t stream,
-                                   const RtEns& ens) {
+                                   const RtEns& ens, const int* sched, int total_steps) {
+    if (sched && (!use_helper || m.rkc || m.nst != 4 || total_steps < n_save - 1)) return hipErrorInvalidValue;   // a schedule: the four-wave RK4 kernels only
     // the record formats this kernel reads and writes are tile16's for exactly this shape
     if (!rt_supported(m) || dwtape_row_floats(m) * CT != RT16S_REC || t16_ztape_col_floats(m) * CT != RT16S_ZREC || (m.nst != 4 && !(m.rkc && use_helper)))
         return hipErrorInvalidValue;
@@ -1842,7 +1091,11 @@ hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const f
     // COLNDE_MATRIX_BF16X3_EXACT: the W1^T products on the bf16 pipe (four-wave kernels, RK4 and RKC2)
     const bool split = want_split && rt_adjoint_split_has_bf16(m, use_helper);
     if (split) hipLaunchKernelGGL(rt_pack_split_nsadj_kernel, dim3(36, ens.n_models), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_NSA_OFF, (int)ens.wimg);
-    if (use_helper) {
+    if (sched) {
+        const auto k = rt16sh_adjoint_sched_pick(m.acts[0], rich, split);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, gridh, blockh, rt16sh_adjoint_lds_bytes(split), stream, m, wimg, save_times, n_save, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens, sched, total_steps);
+    } else if (use_helper) {
         const auto k = rt16sh_adjoint_pick(m.acts[0], rich, m.rkc != nullptr, split);
         if (!k) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k, gridh, blockh, rt16sh_adjoint_lds_bytes(split), stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens);

@@ -202,3 +202,23 @@ def agree_substeps(choose_local, impose, rank_allreduce_max, device=None) -> int
         raise RuntimeError("agree_substeps: the MAX over ranks (%d) is below this rank's own count (%d)" % (agreed, local))
     impose(agreed)
     return agreed
+
+
+def agree_schedule(counts, process_group=None, device=None):
+    """One step schedule for every rank of a column-sharded run: the analogue of `agree_substeps` for `ColumnNDE.set_schedule`.  A schedule is the
+    same for all columns, so ranks that each hold a shard must step with the same counts: every rank brings the counts it would use for its own
+    columns (the stability minima `colnde.schedule_min(cfg)`, or what a single handle of its shard chose), ONE element-wise MAX all-reduce over
+    `process_group` (torch.distributed; None: the default group) makes them equal, and every rank imposes the result:
+
+        nde.set_schedule(agree_schedule(counts, group))
+
+    `device`: where the reduced tensor lives (a backend that reduces device tensors only needs the rank's GPU).  Returns the agreed counts."""
+    import torch
+    import torch.distributed as dist
+    local = [int(c) for c in counts]
+    t = torch.tensor(local, dtype=torch.int32, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=process_group)
+    agreed = tuple(int(v) for v in t.cpu().tolist())
+    if any(a < l for a, l in zip(agreed, local)):
+        raise RuntimeError("agree_schedule: the MAX over ranks %r is below this rank's own counts %r" % (agreed, tuple(local)))
+    return agreed

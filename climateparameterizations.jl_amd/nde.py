@@ -203,6 +203,14 @@ def min_substeps(cfg: NDEConfig) -> int:
     return int(n)
 
 
+def schedule_min(cfg: NDEConfig):
+    """`colnde_schedule_min`: the RK4 stability bound of every save interval's own length, as a tuple of n_save - 1 counts (no GPU needed)."""
+    c, keep = to_c_config(cfg, 1, 0, 0)
+    counts = (ctypes.c_int * (cfg.n_save - 1))()
+    _lib.check(_lib.lib().colnde_schedule_min(ctypes.byref(c), counts))
+    return tuple(int(v) for v in counts)
+
+
 def rkc_stages(cfg: NDEConfig) -> int:
     """`colnde_rkc_stages`: stages per RKC2 step this configuration runs with (no GPU needed)."""
     c, keep = to_c_config(cfg, 1, 0, 0)
@@ -441,8 +449,38 @@ class ColumnNDE:
 
     @property
     def n_steps(self) -> int:
-        """Time steps of one solve with the sub-step count IN USE (cfg.n_steps is 0 for a config created with substeps = 0)."""
-        return (self.cfg.n_save - 1) * self.substeps
+        """Time steps of one solve with the sub-step count IN USE (cfg.n_steps is 0 for a config created with substeps = 0); under a step schedule
+        (set_schedule) the sum of its counts."""
+        return int(self._L.colnde_schedule(self._h, None))
+
+    # ---- a step schedule: RK4 steps per save interval (include/colnde.h: colnde_set_schedule) ----------
+    def set_schedule(self, counts) -> None:
+        """colnde_set_schedule: the RK4 steps of every save interval (n_save - 1 positive integers, the same for all columns and members) in
+        cfg.substeps' place; None clears it.  The four-wave net-split kernels only (single wind-mixing handles up to 8,192 columns, wind-mixing
+        ensembles); before the first loss_grad of a single handle."""
+        if counts is None:
+            _lib.check(self._L.colnde_set_schedule(self._h, None))
+            return
+        c = [int(v) for v in counts]
+        if len(c) != self.cfg.n_save - 1:
+            raise ValueError("a schedule holds one count per save interval: expected %d, got %d" % (self.cfg.n_save - 1, len(c)))
+        _lib.check(self._L.colnde_set_schedule(self._h, (ctypes.c_int * len(c))(*c)))
+
+    def schedule(self):
+        """colnde_schedule: the steps of every save interval in use, as a tuple (cfg.substeps each without a schedule); n_steps is their sum."""
+        c = (ctypes.c_int * (self.cfg.n_save - 1))()
+        if self._L.colnde_schedule(self._h, c) < 0:
+            _lib.check(1)
+        return tuple(int(v) for v in c)
+
+    def choose_schedule(self, weights, reltol: float = 0.0):
+        """colnde_choose_schedule: from the per-interval stability minima (powers of two), double the save intervals that add the most to the error
+        estimate until it meets `reltol` (0: cfg.reltol); the handle keeps the schedule.  Returns (counts, estimate).  Single handles, before the
+        first loss_grad."""
+        w = _f32(weights.cpu().numpy() if _is_torch(weights) else weights, (self.n_params,))
+        c, est = (ctypes.c_int * (self.cfg.n_save - 1))(), ctypes.c_float(0)
+        _lib.check(self._L.colnde_choose_schedule(self._h, _ptr(w), float(reltol), c, ctypes.byref(est)))
+        return tuple(int(v) for v in c), float(est.value)
 
     def error_estimate(self, weights) -> float:
         """Richardson estimate of the solve's error at the current sub-step count against one at twice the count, in the integrator's mixed norm

@@ -139,7 +139,7 @@ class WindMixingNDE:
 
 
 def train_NDE(problem: WindMixingNDE, weights, optimizers: Sequence[ADAM], epochs: int = 1, maxiters: int = 500,
-              cb: Optional[Callable] = None, continue_state: bool = False) -> TrainResult:
+              cb: Optional[Callable] = None, continue_state: bool = False, schedule=None) -> TrainResult:
     """The optimiser loop of `train_NDE` (NDE_training.jl:340-372): for each optimiser and epoch one
     `res = solve(prob_loss, opt, cb=cb, maxiters=maxiters); weights .= res.minimizer`.
 
@@ -153,7 +153,10 @@ def train_NDE(problem: WindMixingNDE, weights, optimizers: Sequence[ADAM], epoch
         more, so a solve that is not halted issues maxiters + 1 callbacks.
     The reference's OWN callback ignores that extra call: its body is guarded by `if iter <= maxiters` with `iter += 1` behind it
     (NDE_training.jl:343-368), so it prints and `write_data_NDE_training`s exactly `maxiters` records per solve.  A `cb` that logs must carry
-    the same guard to produce a reference-shaped log: `reference_logging_callback` below is that closure."""
+    the same guard to produce a reference-shaped log: `reference_logging_callback` below is that closure.
+    schedule: RK4 steps per save interval for the problem's engine (`ColumnNDE.set_schedule`; before its first gradient), None: cfg.substeps."""
+    if schedule is not None:
+        problem.engine.set_schedule(schedule)
     theta = np.array(weights, dtype=np.float32)
     history = []
     for opt in optimizers:
@@ -216,15 +219,18 @@ def _check_replicas(theta, comm, process_group, it):
 
 
 def train_NDE_device(problem: WindMixingNDE, weights, optimizers: Sequence[ADAM], epochs: int = 1, maxiters: int = 500,
-                     process_group=None, continue_state: bool = False, comm=None, sync_check_every: int = 0) -> TrainResult:
+                     process_group=None, continue_state: bool = False, comm=None, sync_check_every: int = 0, schedule=None) -> TrainResult:
     """`train_NDE`'s optimiser loop (NDE_training.jl:340-372) with θ, the ADAM state and the best-loss copy resident on the
     GPU: per iteration one `colnde_loss_grad_dev`, [one SUM all-reduce of the gradient buffer when the columns are sharded
     over `process_group`], one fused `colnde_adam_step_dev`; nothing crosses PCIe until the end.  Same update rule, per-solve
     state reset and `save_best` selection as `train_NDE`; the per-iteration callback is not available here.
     sync_check_every = K > 0 (sharded runs): every K iterations, and before the first, the ranks compare checksums of their weight vectors
-    with one 12-float MAX all-reduce (`distributed.weights_in_sync`) and raise if the replicas have drifted apart."""
+    with one 12-float MAX all-reduce (`distributed.weights_in_sync`) and raise if the replicas have drifted apart.
+    schedule: RK4 steps per save interval (`ColumnNDE.set_schedule`; sharded runs: the same on every rank — `distributed.agree_schedule`), None: cfg.substeps."""
     import torch
     eng = problem.engine
+    if schedule is not None:
+        eng.set_schedule(schedule)
     dev = torch.device("cuda", eng.device)
     n = eng.n_params
     theta = torch.as_tensor(np.asarray(weights, dtype=np.float32)).to(dev).contiguous()
@@ -268,12 +274,13 @@ def train_NDE_device(problem: WindMixingNDE, weights, optimizers: Sequence[ADAM]
 
 
 def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: int = 1, maxiters: int = 500, beta=(0.9, 0.999),
-                       eps: float = 1e-8) -> List[TrainResult]:
+                       eps: float = 1e-8, schedule=None) -> List[TrainResult]:
     """`train_NDE_device`'s loop (NDE_training.jl:340-372: ADAM, per-solve state reset, save_best) for K models at once — the sweep of
     wind_mixing/train_NDE_args.jl, which trains one model per process with its own ADAM rate (ARGS[2], :143) and Pacanowski-Philander constants
     (ARGS[3], :175).  weights [K, n_params], physics [K, 5] = (nu0, nu_minus, dRi, Ric, Pr) per model or None (the problem's constants), etas [K].
     One `colnde_ensemble_loss_grad_dev` and one `colnde_ensemble_adam_step_dev` per iteration for all models, on the problem's simulations and
-    loss scalings; `save_best` per model (torch.where over rows).  Returns one TrainResult per model."""
+    loss scalings; `save_best` per model (torch.where over rows).  Returns one TrainResult per model.
+    schedule: RK4 steps per save interval shared by the K models (`ColumnNDEEnsemble.set_schedule`), None: cfg.substeps."""
     import torch
     from .nde import ColumnNDEEnsemble, check_ensemble_arrays
     W = np.ascontiguousarray(weights, dtype=np.float32)
@@ -284,6 +291,8 @@ def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: i
     eng = problem.engine
     ens = ColumnNDEEnsemble(problem.cfg, problem.n_simulations, K, physics=ph, device=eng.device, matrix_arithmetic=eng.matrix_arithmetic)
     try:
+        if schedule is not None:
+            ens.set_schedule(schedule)
         dev = torch.device("cuda", eng.device)
         t = lambda a: a if a is None or _is_torch_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32))
         x0, bcs, truth = (t(a).to(dev).contiguous() for a in (problem.uvT0, problem.BCs, problem.uvT_trains))

@@ -191,6 +191,35 @@ int colnde_substeps(const colnde_handle* h);
  * STEP, not the stage count — see the table in DESIGN section 2 (tools/rkc_conditioning.py). */
 int colnde_set_substeps(colnde_handle* h, int substeps);
 
+/* ---- a step SCHEDULE: the fixed-step form of the adaptive stepper's uneven steps.  One `substeps` serves the whole time axis, so every save interval pays
+ * for the most demanding one: the stability bound follows the LONGEST interval, colnde_choose_substeps the worst.  A schedule is n_save - 1 positive counts
+ * S_n, the RK4 steps of save interval n — the same for all columns and all members; interval n is stepped with dt_n = (t[n+1] - t[n]) / S_n.  Tapes, slab
+ * rows and dW records are sized by the total, sum of S_n.  A handle without a schedule behaves, bit for bit, as it always did, and a schedule whose counts
+ * all equal c gives the bits of substeps = c.
+ * colnde_schedule_min (no GPU): counts[n_save - 1] = the stability bound of each interval's own length — colnde_min_substeps of the two-point configuration
+ *   of that interval (RK4 only).
+ * colnde_set_schedule: impose counts[n_save - 1]; NULL clears the schedule (cfg.substeps everywhere again).  Covers the handles whose solves run on the
+ *   four-wave net-split kernels (rt16sh_forward_kernel / rt16sh_adjoint_kernel): single wind-mixing handles of the net-split shape under engine AUTO with at
+ *   most 8,192 columns, and colnde_create_ensemble handles.  Refused, each with its reason and before any device work: once a single handle's tapes are
+ *   planned (the first colnde_loss_grad; an ensemble's tapes, planned at creation, are planned again for the new total, and a total that does not fit is
+ *   refused with the old schedule kept); a count below colnde_schedule_min (of an ensemble: below any model's; COLNDE_ALLOW_UNSTABLE_DT=1 overrides), below 1
+ *   or above 4096; RKC2 (its stage table depends on dt); regtile (more than 8,192 columns or engine = regtile), tile16 shapes (wide networks, smoothing,
+ *   inplace_variant), fc32, conv, closure and free-convection ensemble handles; COLNDE_T16_{FWD,ADJ}_HELPER=0, COLNDE_T16_{FWD,ADJ}_SPLIT=0,
+ *   COLNDE_T16_ZTAPE=0, COLNDE_T16_DWTAPE=0.  Clears a pending substeps = 0.  colnde_set_substeps and a successful colnde_choose_substeps on a handle with a
+ *   schedule CLEAR the schedule: one count for every interval is what they set.  colnde_error_estimate on such a handle estimates the schedule (against every
+ *   interval doubled).
+ * colnde_schedule: writes the counts in force (counts nullable; cfg.substeps each without a schedule) and returns their total (-1: null handle).
+ * colnde_choose_schedule (single handles; refused on a column shard and once the tapes are planned, as colnde_choose_substeps): starts from
+ *   colnde_schedule_min rounded up to powers of two; each round solves at S and at 2 S (every interval doubled) and forms E[n], colnde_error_estimate's norm
+ *   at save point n alone (max over columns); stops when max E <= reltol (0: cfg.reltol); otherwise doubles every interval whose own addition
+ *   d[n] = max(0, E[n] - E[n-1]) is at least half the largest.  Fails on a non-finite estimate, when max E fell by less than a fifth after a round (the
+ *   float32 round-off floor, as colnde_choose_substeps), and when the intervals that carry the error are at 4096 (too stiff).  On success the handle keeps the
+ *   schedule; counts / estimate (nullable) receive it and max E. */
+int colnde_schedule_min(const colnde_config* cfg, int* counts /* [n_save - 1] */);
+int colnde_set_schedule(colnde_handle* h, const int* counts /* [n_save - 1]; NULL clears */);
+int colnde_schedule(const colnde_handle* h, int* counts /* [n_save - 1], nullable */);
+int colnde_choose_schedule(colnde_handle* h, const float* weights, float reltol, int* counts /* nullable */, float* estimate /* nullable */);
+
 /* predict_flux(uvT, BCs, ...) (wind_mixing/src/NDE_training.jl:83-147; exported at wind_mixing/src/WindMixing.jl:6): the face fluxes whose divergence the
  * RHS takes — uw, vw, wT on the Nz + 1 faces, NN output minus the closure's diffusive flux (MPP) or convective-adjustment flux, boundary faces as the
  * conditions say — for n_columns states: flux [n_col][3][Nz + 1], scaled units.  T-only models: flux [n_col][1][Nz + 1] = [bottom; NN(T); top]

@@ -242,6 +242,35 @@ substeps(h::Handle) = ccall((:colnde_substeps, libcolnde), Cint, (Ptr{Cvoid},), 
 "impose a sub-step count (column shards: choose_substeps! on every rank, MAX over ranks, set_substeps! — colnde_set_substeps)"
 set_substeps!(h::Handle, n::Integer) = (check(ccall((:colnde_set_substeps, libcolnde), Cint, (Ptr{Cvoid}, Cint), h.ptr, n)); h)
 
+"the RK4 stability bound of every save interval's own length, n_save - 1 counts (no GPU) — colnde_schedule_min"
+function schedule_min(cfg::Config, save_times::Vector{Float32})
+    cfg.n_save = length(save_times)
+    counts = Vector{Cint}(undef, length(save_times) - 1)
+    GC.@preserve save_times begin
+        cfg.save_times = pointer(save_times)
+        check(ccall((:colnde_schedule_min, libcolnde), Cint, (Ref{Config}, Ptr{Cint}), cfg, counts))
+    end
+    Int.(counts)
+end
+"impose a step schedule: the RK4 steps of every save interval, the same for all columns and members (`nothing` clears it) — colnde_set_schedule"
+function set_schedule!(h::Handle, counts::Union{Nothing,AbstractVector{<:Integer}})
+    c = counts === nothing ? Ptr{Cint}(C_NULL) : Vector{Cint}(counts)
+    check(ccall((:colnde_set_schedule, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Cint}), h.ptr, c)); h
+end
+"the steps of every save interval in use (n_save - 1 counts; their sum is the solve's step total) — colnde_schedule"
+function schedule(h::Handle, n_save::Integer)
+    counts = Vector{Cint}(undef, n_save - 1)
+    total = ccall((:colnde_schedule, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Cint}), h.ptr, counts)
+    total < 0 && check(Cint(1))
+    Int.(counts)
+end
+"double the save intervals that carry the error until the estimate meets reltol (0: the handle's); kept by the handle — colnde_choose_schedule"
+function choose_schedule!(h::Handle, weights::Vector{Float32}, n_save::Integer, reltol=0f0)
+    counts = Vector{Cint}(undef, n_save - 1); est = Ref{Float32}(0)
+    check(ccall((:colnde_choose_schedule, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cfloat, Ptr{Cint}, Ref{Float32}), h.ptr, weights, reltol, counts, est))
+    Int.(counts), est[]
+end
+
 "+∂z wT as compute_neural_network_forcing! stores it in params.∂z_wT_NN (double_gyre_nn.jl:165; the forcing function negates it, :135)"
 function compute_∂z_wT!(dz_wT::Matrix{Float32}, h::Handle, weights::Vector{Float32}, T_interior::Matrix{Float32}, surface_flux::Vector{Float32}, Lz)
     check(ccall((:colnde_infer_dz_wT, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Ptr{Float32}, Cint),

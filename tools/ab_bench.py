@@ -15,9 +15,14 @@ sc = [1, 1, 1, 5e-3, 5e-3, 5e-3]
 out = torch.empty(p.cfg.n_params + 8, device=dev)
 
 
+ALL_SYMBOLS = list(_lib.SYMBOLS)
+
+
 def make(path):
     _lib._lib = None
     _lib.LIB_PATH = os.path.join(ROOT, "climateparameterizations.jl_amd", path)
+    probe = ctypes.CDLL(_lib.LIB_PATH)                 # an older build lacks the newer symbols: bind what it exports
+    _lib.SYMBOLS[:] = [s for s in ALL_SYMBOLS if hasattr(probe, s[0])]
     h = colnde.ColumnNDE(p.cfg, ncol)
     h.set_problem(x0, bcs)
     truth = h.forward(wt)
