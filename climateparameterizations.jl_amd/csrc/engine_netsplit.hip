@@ -98,6 +98,13 @@ __global__ void rt_pack_split_ns_kernel(const float* __restrict__ img, unsigned*
 // — the activation derivatives with the padding slots already zeroed, and the nine per-level coefficients of rt16_physics_apply (everything in the
 // Richardson-number closure that depends on the stage input alone: all the transcendental work of the pullback).
 #define RT16S_RREC ((3 * 12 + 18) * 256)    // floats per rich tape record
+// Behind a layer's MFMA chain of the forward kernels: the accumulators are moved to vector registers HERE, in the chain's own basic block, before the
+// `if (oz)` / `if (orr)` branches that follow.  Without it the compiler sinks the v_accvgpr_read into both sides of the tape branch and gives only the
+// fall-through side the wait states an MFMA result needs; a tape-less solve (colnde_forward, colnde_loss) takes the other side, five instructions
+// behind the chain's last MFMA, and read accumulators short of its last products: tanh, fp32 MFMA, 7e-2 off the float64 solution and not
+// repeatable from call to call (tests/test_gpu_distinct_nets.py; the taped solves behind colnde_loss_grad were right).  The fence computes nothing:
+// it only fixes where the reads stand.
+#define RT16S_ACC_FENCE(acc) asm volatile("" : "+v"(acc))
 template <int ACT, bool RICH>
 __global__ void __launch_bounds__(192)
 rt16s_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ x0, const float* __restrict__ bcs,
@@ -204,6 +211,7 @@ rt16s_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __
                     const int base = a1b[t];
                     acc = rt16_chain<24, 8>(wl, acc, [=](int k) { return base + (k >> 3) * 32 + ((k >> 2) & 1) * 16 + (k & 3); },
                                             [&](int k) { return Xs[k >> 3].t[(k >> 2) & 1][k & 3]; });
+                    RT16S_ACC_FENCE(acc);
                     if (oz) {
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
@@ -230,6 +238,7 @@ rt16s_forward_kernel(DevModel m, const float* __restrict__ wimg, const float* __
                     const int base = a2b[u], basel = a2l[u];
                     acc = rt16_chain<13, 13>(wl, acc, [=](int k) { return k < 12 ? base + 4 * k : basel; },
                                              [&](int k) { return A1[k >> 2][k & 3]; });
+                    RT16S_ACC_FENCE(acc);
                     if (oz) {
 #pragma unroll
                         for (int r = 0; r < 4; r++)

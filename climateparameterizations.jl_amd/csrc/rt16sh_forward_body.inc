@@ -239,6 +239,7 @@
                     acc = rt16_chain<24, 8>(wl, acc, [=](int k) { return base + (k >> 3) * 32 + ((k >> 2) & 1) * 16 + (k & 3); },
                                             [&](int k) { return Xs[k >> 3].t[(k >> 2) & 1][k & 3]; });
                     }
+                    RT16S_ACC_FENCE(acc);
                     if (oz) {
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
@@ -285,6 +286,7 @@
                     acc = rt16_chain<13, 13>(wl, acc, [=](int k) { return k < 12 ? base + 4 * k : basel; },
                                              [&](int k) { return A1[k >> 2][k & 3]; });
                     }
+                    RT16S_ACC_FENCE(acc);
                     if (oz) {
 #pragma unroll
                         for (int r = 0; r < 4; r++)
