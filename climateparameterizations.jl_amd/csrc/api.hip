@@ -1136,6 +1136,7 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
              (info[7] & 2) ? "bf16x3" : "f32", (info[7] & 4) ? "bf16x3" : "f32", (info[7] & 8) ? "bf16x3" : "f32");
     s += t;
     if (wm_infer_covers(h)) s += " wm_infer=f32";      // colnde_wm_infer_dz_flux / colnde_wm_embedded_step[_flux] / colnde_wm_diagnose_flux: the f32 matrix pipe under either arithmetic
+    if (wm_generic_serves(h)) s += " wm_embed=generic_f32";      // colnde_ensemble_wm_embedded with this single handle as K = 1: engine_wm_embed_any.hip, likewise
     if (h->ensemble && !h->use_fc) s += " wm_profile=f32";      // colnde_ensemble_profile: likewise
     if (!h->conv.c && fce_covers(h)) s += " fc_embed=f32";      // colnde_fc_embedded_step / colnde_fc_diagnose_wT: likewise
     if (info[1]) { snprintf(t, sizeof t, " block=%dx%d", info[1], info[2]); s += t; } else s += " block=(not planned yet)";

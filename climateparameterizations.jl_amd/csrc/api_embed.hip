@@ -165,11 +165,27 @@ static int wm_shape_check(const colnde_handle* h, const char* fn) {
         return fail("%s: the embedding has no smoothing filter (NDE_oceananigans.jl:288-329 apply the networks unfiltered), so a handle with smooth_NN is refused", fn);
     std::string shape_is;
     for (int l = 0; l <= c.n_layers; l++) shape_is += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
-    return fail("%s covers Nz = 32 with three 96-50-20-31 networks and an identity output layer; this handle has Nz = %d, networks %s, output activation %d", fn,
-                c.Nz, shape_is.c_str(), c.activations[c.n_layers - 1]);
+    // (the unified call serves other layer sizes itself: only the older entry points point at it)
+    const bool unified = !strncmp(fn, "colnde_ensemble_wm_embedded", 27);
+    return fail("%s covers Nz = 32 with three 96-50-20-31 networks and an identity output layer; this handle has Nz = %d, networks %s, output activation %d%s", fn,
+                c.Nz, shape_is.c_str(), c.activations[c.n_layers - 1],
+                unified ? "" : "; colnde_ensemble_wm_embedded deploys a single handle of any layer sizes 96-...-31 at Nz = 32 as K = 1");
 }
 // the handles the single-model entry points cover
 bool wm_infer_covers(const colnde_handle* h) { return !h->closure && !h->ensemble && !wm_shape_check(h, nullptr); }
+
+// ---- networks of any trained architecture (engine_wm_embed_any.hip: wm_embed_any_kernel) --------------------------------------------
+static_assert(WMA_MAX_LAYERS == COLNDE_MAX_LAYERS && WMA_NZ == WM_NZ, "engine_wm_embed_any.h restates these");
+// a single wind-mixing handle at Nz = 32 whose three nets are 96-...-31, whatever lies between; the fixed shape only under COLNDE_WM_GENERIC=1 (the
+// kernel-against-kernel tests), the persistent kernel otherwise
+static bool wm_generic_shape(const colnde_handle* h) {
+    const colnde_config& c = h->cfg;
+    return !h->closure && !h->ensemble && !h->conv.c && c.model == COLNDE_MODEL_WIND_MIXING && !c.smooth_NN && c.Nz == WM_NZ && c.n_layers >= 1 &&
+           c.layer_sizes[0] == 3 * WM_NZ && c.layer_sizes[c.n_layers] == WM_NZ - 1 && (wm_shape_check(h, nullptr) || env_int(ENV_WM_GENERIC, 0) != 0);
+}
+static WmAnyPlan wm_generic_plan(const colnde_handle* h) { return wm_any_plan(h->cfg.n_layers, h->cfg.layer_sizes); }
+// ... and whose LDS plan fits: the handles colnde_ensemble_wm_embedded sends to the generic kernel (colnde_describe: wm_embed=generic_f32)
+bool wm_generic_serves(const colnde_handle* h) { return wm_generic_shape(h) && wm_any_fits(wm_generic_plan(h)); }
 // (its callers have refused ensembles and closure handles: SINGLE_MODEL_ONLY); fn names the entry point in the refusal
 static int wm_infer_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, int n_columns) {
     if (!h) return fail("null handle");
@@ -366,7 +382,16 @@ static int wm_ens_check(colnde_handle* h, const char* fn, const float* weights, 
     if (h->closure)
         return fail("%s takes K weight vectors, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", fn,
                     h->n_models);
-    if (wm_shape_check(h, fn)) return 1;
+    if (wm_generic_shape(h)) {
+        const WmAnyPlan plan = wm_generic_plan(h);
+        if (!wm_any_fits(plan)) {
+            std::string shape_is;
+            for (int l = 0; l <= h->cfg.n_layers; l++) shape_is += (l ? "-" : "") + std::to_string(h->cfg.layer_sizes[l]);
+            return fail("%s: the networks %s need %zu bytes of LDS per 16-column tile (state and face rows, the scaled input, the outputs and two activation buffers "
+                        "of %d and %d floats per column), more than the %d bytes of a workgroup; hidden widths up to 600 fit", fn, shape_is.c_str(), plan.bytes,
+                        plan.ld[0], plan.ld[1], WMA_LDS_LIMIT);
+        }
+    } else if (wm_shape_check(h, fn)) return 1;
     if (!weights || !u || !v || !T || !top_flux || !dz_uw || !dz_vw || !dz_wT) return fail("null pointer argument");
     const int n_step = (u_out != nullptr) + (v_out != nullptr) + (T_out != nullptr), n_flux = (uw != nullptr) + (vw != nullptr) + (wT != nullptr);
     if (n_step != 0 && n_step != 3)
@@ -415,6 +440,33 @@ static int wm_ens_grid_cap() {
     return e && *e ? std::max(0, atoi(e)) : 0;
 }
 
+// A single handle of any architecture as K = 1: the one launch of wm_embed_any_kernel (the caller has run wm_ens_check).  The constants are the
+// handle's own unless params is given; they travel as a kernel argument, there is no device table.
+static int wm_generic_launch(colnde_handle* h, const char* fn, const float* d_weights, const float* d_u, const float* d_v, const float* d_T, const float* d_top_flux,
+                             const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt, const float* params, int ca, float* d_dz_uw, float* d_dz_vw,
+                             float* d_dz_wT, float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
+    WmAnyArgs a = {};
+    const DevModel& m = h->m;
+    a.net.n_layers = m.n_layers;
+    a.net.net_size = m.net_size;
+    for (int l = 0; l < m.n_layers; l++) { a.net.sizes[l] = m.sizes[l]; a.net.acts[l] = m.acts[l]; a.net.w_off[l] = m.w_off[l]; a.net.b_off[l] = m.b_off[l]; }
+    a.net.sizes[m.n_layers] = m.sizes[m.n_layers];
+    for (int i = 0; i < 6; i++) { a.mu[i] = h->cfg.mu[i]; a.sigma[i] = h->cfg.sigma[i]; }
+    const float dz = Lz / (float)WM_NZ;
+    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top; a.Lz = Lz;
+    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT;
+    a.fused = d_u_out != nullptr; a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
+    a.diag = d_uw != nullptr; a.uw = d_uw; a.vw = d_vw; a.wT = d_wT;
+    a.n_col = n_columns;
+    float own[7];
+    if (!params) wm_ens_model_params(h, 0, own);
+    a.mpp = mpp_params(params ? params : own, a.fused ? dt : dz * dz, dz, ca);              // (without a step c is not read: 1, as the other diagnoses pass it)
+    Timed tm(h, K_FLUXDIAG);
+    hipError_t e = launch_wm_embed_any(a, h->stream);
+    if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", fn, hipGetErrorString(e));
+    return 0;
+}
+
 extern "C" int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
                                                const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt,
                                                const float* params, int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT,
@@ -424,6 +476,9 @@ extern "C" int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_
         return 1;
     HIPCHK(hipSetDevice(h->device));
     const bool step = d_u_out != nullptr;
+    if (wm_generic_serves(h))
+        return wm_generic_launch(h, __func__, d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, params, convective_adjustment, d_dz_uw, d_dz_vw,
+                                 d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT, n_columns);
     if (wm_ens_upload_mpp(h, params, step, dt, Lz / (float)WM_NZ, convective_adjustment)) return 1;
     WmEnsArgs a = {};
     wm_scalings(h, &a);

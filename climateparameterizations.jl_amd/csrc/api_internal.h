@@ -19,6 +19,7 @@
 #include "column_ops.h"
 #include "engine_closure.h"
 #include "engine_wm_infer.h"
+#include "engine_wm_embed_any.h"
 #include "engine_wm_profile.h"
 #include "engine_fc_embed.h"
 #include "engine_fc_pretrain.h"
@@ -66,6 +67,7 @@ int schedule_minima(const colnde_handle* h, std::vector<int>* minima);   // per 
 int ens_replan_tapes(colnde_handle* h);   // an ensemble's tapes, planned at creation, re-planned for the step total in force (colnde_set_schedule)
 // ---- defined in api_embed.hip: the handles the embedding's kernels cover (colnde_describe reports them) ------
 bool wm_infer_covers(const colnde_handle* h);
+bool wm_generic_serves(const colnde_handle* h);
 bool fce_covers(const colnde_handle* h);
 
 // Entry points that take ONE weight vector refuse an ensemble handle (colnde_create_ensemble)
@@ -103,7 +105,7 @@ struct PendingEvent { hipEvent_t a, b; int which; };
 // there is in the list by construction; the engine files read FC_CW, RT_FWD, T16_DWLDS, T16_TAPE_THREADS and T16_TAPE_WLDS themselves.
 #define COLNDE_ENV_LIST(X)                                                                                                                  \
     X(FWD_SPLIT) X(ADJ_SPLIT) X(DW_SPLIT) X(ADJ_GEOM) X(FWD_WLDS) X(FWD_THREADS) X(T16_FWD_HELPER) X(T16_ADJ_HELPER) X(T16_FWD_SPLIT)         \
-    X(T16_ADJ_SPLIT) X(FC) X(FC_CW) X(FC_EMBED_FUSED) X(FC_BLOCK) X(FC_SEG) X(WM_ENS_GRID) X(WM_PROFILE_GRID) X(RT_ZTAPE) X(RT_BLOCK) X(RT_FWD) X(ALLOW_UNSTABLE_DT) \
+    X(T16_ADJ_SPLIT) X(FC) X(FC_CW) X(FC_EMBED_FUSED) X(FC_BLOCK) X(FC_SEG) X(WM_ENS_GRID) X(WM_GENERIC) X(WM_PROFILE_GRID) X(RT_ZTAPE) X(RT_BLOCK) X(RT_FWD) X(ALLOW_UNSTABLE_DT) \
     X(T16_DWTAPE) X(T16_ZTAPE) X(T16_SPLIT_RICH) X(T16_BLOCK) X(T16_DWLDS) X(T16_TAPE_THREADS) X(T16_TAPE_WLDS)
 #define X(n) ENV_##n,
 enum EnvSwitch { COLNDE_ENV_LIST(X) ENV_COUNT };

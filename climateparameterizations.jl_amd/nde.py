@@ -778,6 +778,50 @@ class ColumnNDE:
                                                         _ptr(faces[0]), _ptr(faces[1]), _ptr(faces[2]), n))
         return dz, res, faces
 
+    def wm_embedded(self, weights, u, v, T, top_flux, Lz: float, dt=None, params=None, convective_adjustment: bool = False, halo_bottom=None,
+                    halo_top=None, step: bool = True, flux: bool = True) -> "WmEnsembleEmbedded":
+        """One embedded iteration of ALL K models in one launch (`colnde_ensemble_wm_embedded`): per model what `wm_embedded_step_flux` (step and
+        flux), `wm_embedded_step` (step), `wm_diagnose_flux` and `wm_infer_dz_flux` (flux; the ∂z arrays are always returned) give for that model's
+        weights, state and constants, bit for bit — on a `ColumnNDEEnsemble`, and on a single `ColumnNDE` as K = 1: the one embedding call that
+        deploys three networks of ANY layer sizes 96-…-31 and activations (Nz = 32; `describe()`: wm_embed=generic_f32), where the four
+        single-model calls above cover 96-50-20-31 alone.  weights [K, n_params]; u, v, T [K, n, Nz], each model its own state; top_flux [3, n],
+        shared; halo_bottom, halo_top [K, 3, n] or None; params [K, 7] = (nu0, nu_minus, dRi, Ric, Pr, alpha, g) per model, or None: the handle's
+        physics with cfg.alpha, cfg.g.  numpy arrays or torch device tensors (all of one kind)."""
+        Nz, K = self.cfg.Nz, int(getattr(self, "n_models", 1))
+        n = check_wm_ens_embed_arrays(K, self.n_params, Nz, weights, (u, v, T), top_flux, dt, params, halo_bottom, halo_top, step)
+        pr = None if params is None else (ctypes.c_float * (7 * K))(*[float(x) for x in np.asarray(params, dtype=np.float64).reshape(-1)])
+        dtv = float(dt) if step else 0.0
+        ca = int(bool(convective_adjustment))
+        if _is_torch(T):
+            import torch
+            self._chk_dev(weights, (K, self.n_params))
+            for a in (u, v, T):
+                self._chk_dev(a, (K, n, Nz))
+            self._chk_dev(top_flux, (3, n))
+            for a in (halo_bottom, halo_top):
+                if a is not None:
+                    self._chk_dev(a, (K, 3, n))
+            dz = tuple(torch.empty_like(T) for _ in range(3))
+            st = tuple(torch.empty_like(T) for _ in range(3)) if step else None
+            fc = tuple(torch.empty((K, n, Nz + 1), dtype=T.dtype, device=T.device) for _ in range(3)) if flux else None
+            self.use_torch_stream()
+            P = lambda a: a.data_ptr() if a is not None else None
+            fn = self._L.colnde_ensemble_wm_embedded_dev
+        else:
+            weights = _f32(weights, (K, self.n_params))
+            u, v, T, top_flux = _f32(u), _f32(v), _f32(T), _f32(top_flux)
+            halo_bottom = _f32(halo_bottom) if halo_bottom is not None else None
+            halo_top = _f32(halo_top) if halo_top is not None else None
+            dz = tuple(np.empty_like(T) for _ in range(3))
+            st = tuple(np.empty_like(T) for _ in range(3)) if step else None
+            fc = tuple(np.empty((K, n, Nz + 1), np.float32) for _ in range(3)) if flux else None
+            P = _ptr
+            fn = self._L.colnde_ensemble_wm_embedded
+        s3, f3 = st or (None,) * 3, fc or (None,) * 3
+        _lib.check(fn(self._h, P(weights), P(u), P(v), P(T), P(top_flux), P(halo_bottom), P(halo_top), float(Lz), dtv, pr, ca, P(dz[0]), P(dz[1]), P(dz[2]),
+                      P(s3[0]), P(s3[1]), P(s3[2]), P(f3[0]), P(f3[1]), P(f3[2]), n))
+        return WmEnsembleEmbedded(dz, st, fc)
+
     def mpp_diagnose_flux(self, u, v, T, top_flux, dz: float, params, convective_adjustment: bool = False, halo_bottom=None, faces_out=None):
         """`diagnose_baseline_flux_uw`, `_vw`, `_wT` (wind_mixing/src/NDE_oceananigans.jl:157-191): (uw, vw, wT), each [n][Nz+1], of the
         diffusivity-only model: −ν ∂z u, −ν ∂z v, −νT ∂z T with the top face replaced by top_flux [3][n].  params, halo_bottom as
@@ -1188,48 +1232,6 @@ class ColumnNDEEnsemble(ColumnNDE):
             beta_t[0], beta_t[1] = bt[0], bt[1]
         return np.array(loss, dtype=np.float32).reshape(K, 3)
 
-
-    def wm_embedded(self, weights, u, v, T, top_flux, Lz: float, dt=None, params=None, convective_adjustment: bool = False, halo_bottom=None,
-                    halo_top=None, step: bool = True, flux: bool = True) -> WmEnsembleEmbedded:
-        """One embedded iteration of ALL K models in one launch (`colnde_ensemble_wm_embedded`): per model what `wm_embedded_step_flux` (step and
-        flux), `wm_embedded_step` (step), `wm_diagnose_flux` and `wm_infer_dz_flux` (flux; the ∂z arrays are always returned) give for that model's
-        weights, state and constants, bit for bit.  weights [K, n_params]; u, v, T [K, n, Nz], each model its own state; top_flux [3, n], shared;
-        halo_bottom, halo_top [K, 3, n] or None; params [K, 7] = (nu0, nu_minus, dRi, Ric, Pr, alpha, g) per model, or None: the handle's physics
-        with cfg.alpha, cfg.g.  numpy arrays or torch device tensors (all of one kind)."""
-        Nz, K = self.cfg.Nz, self.n_models
-        n = check_wm_ens_embed_arrays(K, self.n_params, Nz, weights, (u, v, T), top_flux, dt, params, halo_bottom, halo_top, step)
-        pr = None if params is None else (ctypes.c_float * (7 * K))(*[float(x) for x in np.asarray(params, dtype=np.float64).reshape(-1)])
-        dtv = float(dt) if step else 0.0
-        ca = int(bool(convective_adjustment))
-        if _is_torch(T):
-            import torch
-            self._chk_dev(weights, (K, self.n_params))
-            for a in (u, v, T):
-                self._chk_dev(a, (K, n, Nz))
-            self._chk_dev(top_flux, (3, n))
-            for a in (halo_bottom, halo_top):
-                if a is not None:
-                    self._chk_dev(a, (K, 3, n))
-            dz = tuple(torch.empty_like(T) for _ in range(3))
-            st = tuple(torch.empty_like(T) for _ in range(3)) if step else None
-            fc = tuple(torch.empty((K, n, Nz + 1), dtype=T.dtype, device=T.device) for _ in range(3)) if flux else None
-            self.use_torch_stream()
-            P = lambda a: a.data_ptr() if a is not None else None
-            fn = self._L.colnde_ensemble_wm_embedded_dev
-        else:
-            weights = _f32(weights, (K, self.n_params))
-            u, v, T, top_flux = _f32(u), _f32(v), _f32(T), _f32(top_flux)
-            halo_bottom = _f32(halo_bottom) if halo_bottom is not None else None
-            halo_top = _f32(halo_top) if halo_top is not None else None
-            dz = tuple(np.empty_like(T) for _ in range(3))
-            st = tuple(np.empty_like(T) for _ in range(3)) if step else None
-            fc = tuple(np.empty((K, n, Nz + 1), np.float32) for _ in range(3)) if flux else None
-            P = _ptr
-            fn = self._L.colnde_ensemble_wm_embedded
-        s3, f3 = st or (None,) * 3, fc or (None,) * 3
-        _lib.check(fn(self._h, P(weights), P(u), P(v), P(T), P(top_flux), P(halo_bottom), P(halo_top), float(Lz), dtv, pr, ca, P(dz[0]), P(dz[1]), P(dz[2]),
-                      P(s3[0]), P(s3[1]), P(s3[2]), P(f3[0]), P(f3[1]), P(f3[2]), n))
-        return WmEnsembleEmbedded(dz, st, fc)
 
     def profile(self, weights, sol, physics=None, flux: bool = True, Ri: bool = True, losses: bool = True) -> "EnsembleProfile":
         """What `NDE_profile` (wind_mixing/src/training_postprocessing.jl:404-431, :310-317) evaluates on the saved states of a solve, for ALL K

@@ -575,6 +575,23 @@ def _named(d, *names):
     raise KeyError(names[0])
 
 
+WM_FIXED_SHAPE = (96, 50, 20, 31)        # the one architecture the four single-model embedding calls cover (Nz = 32, identity output layer)
+
+
+def _wm_fixed_shape(engine: ColumnNDE) -> bool:
+    """whether the four single-model calls serve the engine (one that states no configuration is taken at its word: it has those calls)"""
+    c = getattr(engine, "cfg", None)
+    return c is None or c.Nz == 32 and tuple(c.layer_sizes) == WM_FIXED_SHAPE and c.activations[-1] == "identity"
+
+
+def _wm_embedded_single(engine: ColumnNDE, weights, u2, v2, T2, top, Lz, dt=None, params=None, ca=False, hb=None, ht=None, step=False, flux=False):
+    """Any other architecture: `ColumnNDE.wm_embedded` with the single handle as K = 1 (`colnde_ensemble_wm_embedded`); the leading axis taken off."""
+    one = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, np.float32))[None]
+    r = engine.wm_embedded(np.asarray(weights, np.float32).reshape(1, -1), one(u2), one(v2), one(T2), top, Lz, dt,
+                           None if params is None else np.asarray(params, np.float64).reshape(1, 7), ca, one(hb), one(ht), step=step, flux=flux)
+    return tuple(None if g is None else tuple(a[0] for a in g) for g in r)
+
+
 def NN_forcings(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz: float):
     """`NN_uw_forcing`, `NN_vw_forcing`, `NN_wT_forcing` (wind_mixing/src/NDE_oceananigans.jl:288-329) as the ocean model applies them
     (`- p.∂z_uw_NN[k]`, :333, :338, :343): the three forcings [n, Nz] (or [Nz]) of `interior(u)`, `interior(v)`, `interior(T)` in the
@@ -584,6 +601,8 @@ def NN_forcings(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz: float):
     shape = T.shape
     u2, v2, T2 = (a.reshape(-1, shape[-1]) for a in (u, v, T))
     top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_fluxes, np.float32).reshape(3, -1), (3, T2.shape[0])))
+    if not _wm_fixed_shape(engine):
+        return tuple(-d.reshape(shape) for d in _wm_embedded_single(engine, weights, u2, v2, T2, top, Lz)[0])
     return tuple(-d.reshape(shape) for d in engine.wm_infer_dz_flux(weights, u2, v2, T2, top, Lz))
 
 
@@ -599,7 +618,10 @@ def progress_neural_network(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz:
     u2, v2, T2 = (a.reshape(-1, shape[-1]) for a in (u, v, T))
     top = np.ascontiguousarray(np.broadcast_to(np.asarray(top_fluxes, np.float32).reshape(3, -1), (3, T2.shape[0])))
     hb = None if halo_bottom is None else np.asarray(halo_bottom, np.float32).reshape(3, -1)
-    dz, st = engine.wm_embedded_step(weights, u2, v2, T2, top, Lz, dt, params, convective_adjustment, hb)
+    if not _wm_fixed_shape(engine):
+        dz, st, _ = _wm_embedded_single(engine, weights, u2, v2, T2, top, Lz, dt, params, convective_adjustment, hb, step=True)
+    else:
+        dz, st = engine.wm_embedded_step(weights, u2, v2, T2, top, Lz, dt, params, convective_adjustment, hb)
     return tuple(d.reshape(shape) for d in dz), tuple(a.reshape(shape) for a in st)
 
 
@@ -653,7 +675,11 @@ def diagnose_NN_flux(engine: ColumnNDE, weights, u, v, T, top_fluxes, Lz: float,
     `modified_pacanowski_philander_step`; top_fluxes as `NN_forcings`; halos = None or (halo_bottom, halo_top): the u, v, T halo cells
     below and above the column, each [3, n] (or [3]) or None (zero-gradient fill)."""
     shape, u2, v2, T2, top, halos = _diag_args(u, v, T, top_fluxes, halos)
-    faces = engine.wm_diagnose_flux(weights, u2, v2, T2, top, Lz, _mpp_tuple(p, constants), convective_adjustment, halos)
+    if not _wm_fixed_shape(engine):
+        hb, ht = halos if halos is not None else (None, None)
+        faces = _wm_embedded_single(engine, weights, u2, v2, T2, top, Lz, None, _mpp_tuple(p, constants), convective_adjustment, hb, ht, flux=True)[2]
+    else:
+        faces = engine.wm_diagnose_flux(weights, u2, v2, T2, top, Lz, _mpp_tuple(p, constants), convective_adjustment, halos)
     return tuple(f.reshape(shape) for f in faces)
 
 

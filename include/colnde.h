@@ -594,7 +594,15 @@ int colnde_ensemble_pretrain_wm_flux_dev(colnde_handle* h, int nets /* bit j: tr
  * colnde_wm_embedded_step, colnde_wm_infer_dz_flux) writes for model k's weights, state, halos and params.  Accepts an ensemble handle; a single-model handle is
  * K = 1.  Refuses, with the reason in colnde_last_error, what those calls refuse (shape, smooth_NN, null, the 16-byte alignment of every state and output BASE
  * pointer, dRi != 0, Pr > 0) and a closure handle, a half-given output group, dt <= 0 with a step.  Timed under colnde_kernel_time slot 10.
- * COLNDE_WM_ENS_GRID=<n> (a test override) caps the workgroups of this launch and of no other. */
+ * COLNDE_WM_ENS_GRID=<n> (a test override) caps the workgroups of this launch and of no other.
+ * Networks of ANY trained architecture: a single (non-ensemble) wind-mixing handle at Nz = 32 whose three nets have layer sizes 96-h1-...-31 — whatever the
+ *   hidden widths, the number of layers (up to COLNDE_MAX_LAYERS) and the per-layer activations colnde_create accepts — is served too, as K = 1, by a kernel of its
+ *   own (csrc/engine_wm_embed_any.hip; colnde_describe: wm_embed=generic_f32): the same arithmetic and the same output groups in one launch, the
+ *   weights read in place from d_weights, the f32 matrix pipe under either matrix_arithmetic.  This is the one embedding call that deploys 3 x 96-400-400-31 or
+ *   3 x 96-400-31 (train_NDE.jl:97-103, train_NN_args.jl:101-103); the four single-model calls above keep to 96-50-20-31 and say so.  A shape whose activation
+ *   rows do not fit a workgroup's 160 KiB of LDS is refused before any device work, with the bytes it needs (hidden widths up to 600 fit; 96-2048-2048-31 does
+ *   not).  An ensemble of such networks cannot be created (colnde_create_ensemble).  COLNDE_WM_GENERIC=1 (a test switch, read per call) sends a single handle
+ *   of the 96-50-20-31 shape to that kernel as well; without it that shape runs the persistent kernel, single or ensemble, with the bits it always had. */
 int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
         const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt, const float* params,
         int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out, float* d_T_out,

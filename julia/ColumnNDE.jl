@@ -452,7 +452,9 @@ end
 "progress_neural_network and diagnose_NN_flux_* for ALL K models of an ensemble handle in one launch (colnde_ensemble_wm_embedded): θ (n_params, K);
 u, v, T and the ∂z arrays (Nz, n_columns, K), every model on its own state, stepped in place; top_fluxes (n_columns, 3), shared by the models;
 `ps`: a vector of K parameter dictionaries, or nothing (the ensemble's own physics with the handle's α, g); halo_bottom, halo_top (n_columns, 3, K)
-or nothing.  Returns (uw, vw, wT) of the states as given, each (Nz+1, n_columns, K).  Slice k is progress_neural_network_flux of model k, bit for bit."
+or nothing.  Returns (uw, vw, wT) of the states as given, each (Nz+1, n_columns, K).  Slice k is progress_neural_network_flux of model k, bit for bit.
+A single (non-ensemble) handle is K = 1, and of ANY architecture: three nets of layer sizes 96-h1-...-31 with any activations at Nz = 32 (for instance the
+3 x 96-400-400-31 of train_NDE.jl) are deployed by this call alone — progress_neural_network and the other single-model wrappers cover 96-50-20-31."
 function ensemble_progress_neural_network_flux(h::Handle, θ::Matrix{Float32}, u::Array{Float32,3}, v::Array{Float32,3}, T::Array{Float32,3},
                                                top_fluxes::Matrix{Float32}, Lz, constants, Δt, ps, convective_adjustment,
                                                ∂z_uw_NN::Array{Float32,3}, ∂z_vw_NN::Array{Float32,3}, ∂z_wT_NN::Array{Float32,3};
