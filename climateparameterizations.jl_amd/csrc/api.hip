@@ -551,8 +551,14 @@ extern "C" int colnde_set_matrix_arithmetic(colnde_handle* h, int ma) {
     if (!h) return fail("null handle");
     if (ma != COLNDE_MATRIX_BF16X3_EXACT && ma != COLNDE_MATRIX_F32_MFMA)
         return fail("unknown matrix_arithmetic %d (COLNDE_MATRIX_BF16X3_EXACT = 0, COLNDE_MATRIX_F32_MFMA = 1)", ma);
+    const int before = h->cfg.matrix_arithmetic;
     h->cfg.matrix_arithmetic = ma;
     resolve_arithmetic(h);
+    if (replan_dw_slices(h)) {              // a planned dW GEMM follows the arithmetic; when it cannot, the previous arithmetic stays
+        h->cfg.matrix_arithmetic = before;
+        resolve_arithmetic(h);
+        return 1;
+    }
     return 0;
 }
 extern "C" int colnde_matrix_arithmetic(const colnde_handle* h) { return h ? h->cfg.matrix_arithmetic : -1; }

@@ -66,8 +66,8 @@ static int ens_plan_tapes(colnde_handle* h) {
     const int n_steps = total_steps(h);
     const size_t n_rec = sched_records((size_t)h->n_tiles, n_steps, m.nst);
     const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
-    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order
-    h->t16_rows = h->n_tiles + h->dw.slices;
+    h->t16_nblocks = 1;
+    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order (and h->t16_rows)
     const size_t f_tape = n_rec * CT * m.ns, f_dw = n_rec * CT * R, f_rich = n_rec * rt_split_rich_record_floats(),
                  f_plain = n_rec * CT * t16_ztape_col_floats(m), f_slab = (size_t)h->t16_rows * P8,
                  f_sol = (size_t)h->n_col * h->cfg.n_save * m.ns, f_img = RT_IMG_STRIDE;
@@ -337,8 +337,7 @@ static int fc_ens_plan_tapes(colnde_handle* h) {
     const size_t tiles_b = (size_t)n32 / cw;
     const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;
     const size_t n_rec = tiles_b * (cw / 16) * stage_recs;
-    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order
-    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw.slices;
+    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order (and h->fc_rows)
     FcEns& en = h->fens;
     en.dwtape = n_rec * CT * R;
     en.masks = tiles_b * stage_recs * fc_mask_words();

@@ -46,6 +46,46 @@ static int rt_plan_tapes(colnde_handle* h) {
 void build_dw_plan(colnde_handle* h, size_t n_rec) {
     dw_plan_blocks(h->m, h->dw);
     dw_plan_slices(h->dw, n_rec, dw_gemm_lds_fits((int)dwtape_row_floats(h->m), h->dw.n_macros), h->sp_dw);
+    h->dw_n_rec = n_rec;
+    dw_slab_rows(h);
+}
+
+// The slab rows that follow the plan's slice count: the adjoint's rows (one per tile, fc32: per tile and time segment), then the dW GEMM's (one per
+// block, fc32: and segment, and slice); an ensemble's models lie that many rows apart.  The planners size d_slab by it and the setter below re-sizes it.
+void dw_slab_rows(colnde_handle* h) {
+    const size_t P8 = (size_t)h->m.n_params + 8;
+    if (h->use_fc) {
+        h->fc_rows = ((h->n_col + 31) / 32 * 32 / h->fc_cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw.slices;
+        if (h->ensemble) h->fens.slab = h->ens.slab = (size_t)h->fc_rows * P8;
+    } else {
+        h->t16_rows = h->n_tiles + h->t16_nblocks * h->dw.slices;
+        if (h->ensemble) h->ens.slab = (size_t)h->t16_rows * P8;
+    }
+}
+
+// colnde_set_matrix_arithmetic on a handle whose tapes are planned: the slice count was chosen for the arithmetic at plan time (dw_plan.h:
+// dw_slice_count), and the kernel the new arithmetic runs may not take it (the L2-streaming f32 kernel: multiples of 8).  Leaves the handle with the
+// count, slab rows and slab a fresh handle of the arithmetic now in h->sp_dw plans; a failure leaves the plan as it was.
+int replan_dw_slices(colnde_handle* h) {
+    if (!h->d_dwtape || !h->d_slab) return 0;
+    const int slices = dw_slice_count(h->dw, h->dw_n_rec, h->dw.lds_fit, h->sp_dw), old = h->dw.slices;
+    if (slices == old) return 0;
+    const size_t P8 = (size_t)h->m.n_params + 8, K = (size_t)h->n_models;
+    const size_t old_model = (size_t)(h->use_fc ? h->fc_rows : h->t16_rows) * P8;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));             // (launches in flight write the slab about to be freed)
+    h->dw.slices = slices;
+    dw_slab_rows(h);
+    const size_t new_model = (size_t)(h->use_fc ? h->fc_rows : h->t16_rows) * P8;
+    const hipError_t e = h->mem.replace(&h->d_slab, K * new_model);      // the new slab first: a failure keeps the old one
+    if (e != hipSuccess) {
+        h->dw.slices = old;
+        dw_slab_rows(h);
+        return fail("re-planning the dW GEMM for the new arithmetic: hipMalloc of the %zu-byte slab of %d slices failed (%s); the arithmetic and the plan "
+                    "of %d slices stay in force", K * new_model * sizeof(float), slices, hipGetErrorString(e), old);
+    }
+    if (h->ensemble) h->ens_model_bytes = h->ens_model_bytes - old_model * sizeof(float) + new_model * sizeof(float);
+    return 0;
 }
 
 hipError_t upload_dw_plan(colnde_handle* h) {
@@ -58,7 +98,7 @@ hipError_t upload_dw_plan(colnde_handle* h) {
 }
 
 // The bf16-split kernel when the handle's weight-gradient arithmetic asks for it and the plan has passes, else the f32 kernels.
-// (Open advisor finding, left for its own change: the slice count was chosen for the arithmetic at plan time and is not re-planned by colnde_set_matrix_arithmetic.)
+// (The slice count follows the arithmetic: replan_dw_slices.)
 hipError_t dw_launch(colnde_handle* h, size_t n_records, float* slab_rows, int K, size_t tape_mstride, size_t slab_mstride) {
     const int R = (int)dwtape_row_floats(h->m), stride = h->m.n_params + 8;
     if (h->sp_dw && !h->dw.passes.empty())
@@ -104,8 +144,7 @@ static int fc_plan_tapes(colnde_handle* h) {
     const size_t tiles_b = (size_t)block / cw;                                  // (block is a multiple of 32)
     const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;          // (tile, stage) records per tile held by the tapes
     const size_t n_rec = tiles_b * (cw / 16) * stage_recs;                     // records are tile16's: 16 columns each
-    build_dw_plan(h, n_rec);
-    h->fc_rows = (n32 / cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw.slices;
+    build_dw_plan(h, n_rec);                                                    // (and h->fc_rows: dw_slab_rows)
     const int stride = m.n_params + 8;
     const size_t mark = h->mem.mark();
     hipError_t e = h->mem.alloc(&h->d_dwtape, n_rec * CT * R);
@@ -194,8 +233,7 @@ static int t16_plan_dwtape(colnde_handle* h) {
     const size_t need = n_rec * CT * R * sizeof(float);
     h->t16_block = block;
     h->t16_nblocks = (n16 + block - 1) / block;
-    build_dw_plan(h, n_rec);
-    h->t16_rows = h->n_tiles + h->t16_nblocks * h->dw.slices;
+    build_dw_plan(h, n_rec);                                                    // (and h->t16_rows: dw_slab_rows)
     const int stride = m.n_params + 8;
     const size_t mark = h->mem.mark();
     hipError_t e = h->mem.alloc(&h->d_dwtape, need / sizeof(float));

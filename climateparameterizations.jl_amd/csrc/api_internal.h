@@ -58,6 +58,8 @@ int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int
 // the dW GEMM of the taped gradient paths: h->dw planned for n_rec records (dw_plan.h), its two block lists uploaded into slots of h->mem (inside the
 // caller's mark / rollback bracket), and the one place that launches it — K models: grid.y, their records and slab rows the strides apart
 void build_dw_plan(colnde_handle* h, size_t n_rec);
+void dw_slab_rows(colnde_handle* h);      // h->t16_rows / h->fc_rows (an ensemble: and the models' slab stride) for h->dw.slices
+int replan_dw_slices(colnde_handle* h);    // colnde_set_matrix_arithmetic: the slice count, slab rows and slab of the arithmetic switched to
 hipError_t upload_dw_plan(colnde_handle* h);
 hipError_t dw_launch(colnde_handle* h, size_t n_records, float* slab_rows, int K = 1, size_t tape_mstride = 0, size_t slab_mstride = 0);
 int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
@@ -136,6 +138,15 @@ class DevPool {
         slots_.erase(std::remove(slots_.begin(), slots_.end(), (void**)slot), slots_.end());
     }
     template <class T> hipError_t resize(T** slot, size_t count) { release(slot); return alloc(slot, count); }
+    // resize that allocates BEFORE it frees: a failure leaves *slot (which holds a buffer) and its contents as they were
+    template <class T> hipError_t replace(T** slot, size_t count) {
+        T* fresh = nullptr;
+        const hipError_t e = hipMalloc((void**)&fresh, count * sizeof(T));
+        if (e != hipSuccess || !fresh) { (void)hipGetLastError(); return e != hipSuccess ? e : hipErrorOutOfMemory; }
+        (void)hipFree(*slot);
+        *slot = fresh;
+        return hipSuccess;
+    }
     size_t mark() const { return slots_.size(); }
     void rollback(size_t mark) {            // frees what was allocated since mark(), newest first (nothing may be released in between)
         while (slots_.size() > mark) {
@@ -229,6 +240,7 @@ struct colnde_handle {
     float* d_dwtape = nullptr;
     float* d_t16_ztape = nullptr;   // taped mode: hidden pre-activations written by the forward kernel (the adjoint skips its forward GEMMs)
     DwPlan dw;                      // the dW GEMM's plan, built with the tapes' (build_dw_plan); its split passes run when sp_dw
+    size_t dw_n_rec = 0;            // ... the records it was planned for (replan_dw_slices plans the slices again when the arithmetic changes)
     DwMacro *d_macros = nullptr, *d_split_macros = nullptr;   // ... and the device copies of its two block lists (the split one: null without a split plan)
     int t16_rows = 0;
     int t16_block = 0, t16_nblocks = 0;   // taped mode: columns per pass (multiple of 16) — the tapes hold one block

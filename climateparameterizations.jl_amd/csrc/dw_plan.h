@@ -141,13 +141,19 @@ inline void dw_plan_blocks(const DevModel& m, DwPlan& plan) {
 }
 
 // K-slices of n_rec records.  lds_fit: the LDS-staged f32 kernel applies (dw_gemm_lds_fits, which reads its switch where it always has);
-// sp_dw: the handle's weight-gradient arithmetic is the bf16 split.
-inline void dw_plan_slices(DwPlan& plan, size_t n_rec, bool lds_fit, bool sp_dw) {
+// sp_dw: the handle's weight-gradient arithmetic is the bf16 split.  The one rule: the tape planners call it when they build a plan, and
+// colnde_set_matrix_arithmetic calls it again for the arithmetic switched to (the L2-streaming f32 kernel takes multiples of 8 only, the LDS-staged
+// and split kernels any count), so that a handle always holds the count a fresh handle of its arithmetic plans.
+inline int dw_slice_count(const DwPlan& plan, size_t n_rec, bool lds_fit, bool sp_dw) {
     const int n_groups = (plan.n_macros + 3) / 4;
     size_t slices = std::max<size_t>(8, ((size_t)2048 / n_groups + 7) / 8 * 8);
     slices = std::min(slices, std::max<size_t>(8, (n_rec / 8 + 7) / 8 * 8));
     if (lds_fit || (plan.split_ok && sp_dw))         // one workgroup per CU (two records / two plane buffers in LDS): two rounds of slices
         slices = std::min<size_t>(512, std::max<size_t>(1, n_rec));
+    return (int)slices;
+}
+
+inline void dw_plan_slices(DwPlan& plan, size_t n_rec, bool lds_fit, bool sp_dw) {
     plan.lds_fit = lds_fit;
-    plan.slices = (int)slices;
+    plan.slices = dw_slice_count(plan, n_rec, lds_fit, sp_dw);
 }

@@ -275,7 +275,8 @@ class ColumnNDE:
         self.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
 
     def set_matrix_arithmetic(self, matrix_arithmetic):
-        """Switch the handle between "bf16x3_exact" and "f32_mfma" (tapes and plans do not depend on it: same-handle A/B)."""
+        """Switch the handle between "bf16x3_exact" and "f32_mfma" for a same-handle A/B.  The tapes stay; a planned dW GEMM
+        takes the slice count (and the slab rows) a fresh handle of the new arithmetic plans, so the results are that handle's bit for bit."""
         _lib.check(self._L.colnde_set_matrix_arithmetic(self._h, matrix_arithmetic_id(matrix_arithmetic)))
 
     @property

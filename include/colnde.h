@@ -139,8 +139,10 @@ void colnde_destroy(colnde_handle* h);
 int  colnde_n_params(const colnde_handle* h);
 int  colnde_engine(const colnde_handle* h);                  /* engine actually selected */
 int  colnde_set_stream(colnde_handle* h, void* hip_stream);  /* default: the null stream */
-/* Switch the matrix arithmetic of an existing handle (COLNDE_MATRIX_*): tapes, plans and results layout do not depend on it, so the same
- * handle can run both for an A/B on identical inputs.  colnde_matrix_arithmetic returns the configured value. */
+/* Switch the matrix arithmetic of an existing handle (COLNDE_MATRIX_*): tapes and results layout do not depend on it, so the same
+ * handle can run both for an A/B on identical inputs.  A dW GEMM already planned takes the slice count a fresh handle of the new arithmetic plans (the
+ * partial-gradient slab is replaced after the stream has drained), so the results are that handle's bit for bit; if the slab cannot be allocated the call
+ * fails and the previous arithmetic and plan stay in force.  colnde_matrix_arithmetic returns the configured value. */
 int  colnde_set_matrix_arithmetic(colnde_handle* h, int matrix_arithmetic);
 int  colnde_matrix_arithmetic(const colnde_handle* h);
 /* Global column count when columns are sharded over ranks: losses and gradients are normalised by it so

@@ -278,7 +278,7 @@ function compute_∂z_wT!(dz_wT::Matrix{Float32}, h::Handle, weights::Vector{Flo
     dz_wT
 end
 
-"switch an existing handle between MATRIX_BF16X3_EXACT and MATRIX_F32_MFMA (tapes and plans do not depend on it) — colnde_set_matrix_arithmetic"
+"switch an existing handle between MATRIX_BF16X3_EXACT and MATRIX_F32_MFMA (the tapes stay; a planned dW GEMM takes the new arithmetic's slice count) — colnde_set_matrix_arithmetic"
 set_matrix_arithmetic!(h::Handle, ma) = check(ccall((:colnde_set_matrix_arithmetic, libcolnde), Cint, (Ptr{Cvoid}, Cint), h.ptr, ma))
 matrix_arithmetic(h::Handle) = ccall((:colnde_matrix_arithmetic, libcolnde), Cint, (Ptr{Cvoid},), h.ptr)
 
