@@ -69,10 +69,11 @@ __global__ void __launch_bounds__(64) convadj_kernel(const float* T, const float
     }
 }
 
-// any Nz <= 128 (not a multiple of 4, or none of the instantiated sizes): one thread per column straight from HBM
-__global__ void __launch_bounds__(256) convadj_generic_kernel(const float* __restrict__ T, const float* __restrict__ halo_bottom,
+// any Nz <= 128 (not a multiple of 4, unaligned pointers, or none of the instantiated sizes): one thread per column straight from HBM
+// (T and out carry no __restrict__: out may be T itself, in place, as in convadj_kernel)
+__global__ void __launch_bounds__(256) convadj_generic_kernel(const float* T, const float* __restrict__ halo_bottom,
                                                                const float* __restrict__ halo_top, float c, float K,
-                                                               float* __restrict__ out, int Nz, int n_col) {
+                                                               float* out, int Nz, int n_col) {
     const int col = blockIdx.x * 256 + threadIdx.x;
     if (col >= n_col) return;
     const float* t = T + (size_t)col * Nz;
