@@ -151,6 +151,13 @@ extern "C" int colnde_implicit_diffusion(colnde_handle* h, const float* u, const
     return st.download();
 }
 
+// a network as the refusals print it: 96-50-20-31
+static std::string layer_sizes_string(const colnde_config& c) {
+    std::string s;
+    for (int l = 0; l <= c.n_layers; l++) s += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
+    return s;
+}
+
 // ---- wind-mixing embedded inference (wind_mixing/src/NDE_oceananigans.jl:288-329, :380-405; engine_wm_infer.hip) ----------------------
 // The configurations the kernels cover: 0 when h's is one.  Otherwise 1, and with fn (the entry point's name) the refusal is left as the message.
 static int wm_shape_check(const colnde_handle* h, const char* fn) {
@@ -163,12 +170,10 @@ static int wm_shape_check(const colnde_handle* h, const char* fn) {
         return fail("%s needs a wind-mixing handle (three flux networks on [u; v; T]); a free-convection handle has colnde_infer_forcing", fn);
     if (c.smooth_NN)
         return fail("%s: the embedding has no smoothing filter (NDE_oceananigans.jl:288-329 apply the networks unfiltered), so a handle with smooth_NN is refused", fn);
-    std::string shape_is;
-    for (int l = 0; l <= c.n_layers; l++) shape_is += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
     // (the unified call serves other layer sizes itself: only the older entry points point at it)
     const bool unified = !strncmp(fn, "colnde_ensemble_wm_embedded", 27);
     return fail("%s covers Nz = 32 with three 96-50-20-31 networks and an identity output layer; this handle has Nz = %d, networks %s, output activation %d%s", fn,
-                c.Nz, shape_is.c_str(), c.activations[c.n_layers - 1],
+                c.Nz, layer_sizes_string(c).c_str(), c.activations[c.n_layers - 1],
                 unified ? "" : "; colnde_ensemble_wm_embedded deploys a single handle of any layer sizes 96-...-31 at Nz = 32 as K = 1");
 }
 // the handles the single-model entry points cover
@@ -186,14 +191,45 @@ static bool wm_generic_shape(const colnde_handle* h) {
 static WmAnyPlan wm_generic_plan(const colnde_handle* h) { return wm_any_plan(h->cfg.n_layers, h->cfg.layer_sizes); }
 // ... and whose LDS plan fits: the handles colnde_ensemble_wm_embedded sends to the generic kernel (colnde_describe: wm_embed=generic_f32)
 bool wm_generic_serves(const colnde_handle* h) { return wm_generic_shape(h) && wm_any_fits(wm_generic_plan(h)); }
-// (its callers have refused ensembles and closure handles: SINGLE_MODEL_ONLY); fn names the entry point in the refusal
-static int wm_infer_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, int n_columns) {
+
+// One call of the wind-mixing embedding as its entry point received it: what it reads and writes (engine_wm_infer.h: the optional groups of the
+// record choose the fused step and the face diagnosis) and what is the call's own.  params: seven constants — an ensemble call: [K][7], or null for
+// the handle's own.
+struct WmCall {
+    WmEmbedIO io;
+    const float* weights;
+    float dt;                             // the step's
+    const float* params;                  // the step's and the diagnosis'
+    int ca;
+};
+// what every call has; the entry points add their groups by name
+static WmCall wm_call(const float* weights, const float* u, const float* v, const float* T, const float* top_flux, float Lz, int n_columns) {
+    WmCall c = {};
+    c.weights = weights; c.io.u = u; c.io.v = v; c.io.T = T; c.io.top_flux = top_flux; c.io.Lz = Lz; c.io.n_col = n_columns;
+    return c;
+}
+static void wm_dz_group(WmCall* c, float* dz_uw, float* dz_vw, float* dz_wT) { c->io.dz_uw = dz_uw; c->io.dz_vw = dz_vw; c->io.dz_wT = dz_wT; }
+static void wm_step_group(WmCall* c, float* u_out, float* v_out, float* T_out) { c->io.u_out = u_out; c->io.v_out = v_out; c->io.T_out = T_out; }
+static void wm_face_group(WmCall* c, float* uw, float* vw, float* wT) { c->io.uw = uw; c->io.vw = vw; c->io.wT = wT; }
+static void wm_physics(WmCall* c, const float* halo_bottom, const float* halo_top, float dt, const float* params, int ca) {
+    c->io.halo_bottom = halo_bottom; c->io.halo_top = halo_top; c->dt = dt; c->params = params; c->ca = ca;
+}
+
+// (its callers have refused ensembles and closure handles: SINGLE_MODEL_ONLY); fn names the entry point in the refusal.  dz, faces: the call
+// writes the d/dz arrays, the face arrays
+static int wm_infer_check(colnde_handle* h, const char* fn, const WmCall& c, bool dz, bool faces) {
+    const WmEmbedIO& io = c.io;
     if (!h) return fail("null handle");
     if (wm_shape_check(h, fn)) return 1;
-    for (int i = 0; i < n_ptrs; i++)
-        if (!ptrs[i]) return fail("null pointer argument");
-    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
+    if (!c.weights || !io.u || !io.v || !io.T || !io.top_flux) return fail("null pointer argument");
+    if (dz && (!io.dz_uw || !io.dz_vw || !io.dz_wT)) return fail("null pointer argument");
+    if (faces && (!io.uw || !io.vw || !io.wT)) return fail("null pointer argument");
+    if (io.n_col < 1 || !(io.Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
     return 0;
+}
+static int wm_step_check(colnde_handle* h, const WmCall& c) {
+    const WmEmbedIO& io = c.io;
+    return impl_diff_check(h, io.u, io.v, io.T, io.u_out, io.v_out, io.T_out, c.dt, io.Lz / (float)WM_NZ, c.params, io.n_col);
 }
 // the scalings and hidden activations the kernels take from the configuration: WmInferArgs and WmEnsArgs
 template <class Args>
@@ -203,21 +239,15 @@ static void wm_scalings(const colnde_handle* h, Args* a) {
     a->act2 = h->cfg.activations[1];
 }
 
-// The one launch behind the four single-model entry points.  The optional groups decide what the kernel does: u_out, v_out, T_out the fused step
-// (halo_bottom, dt, params, ca), uw, vw, wT the face diagnosis (both halos, params, ca).  `what` names the call in the launch failure.
-static int wm_launch(colnde_handle* h, int slot, const char* what, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
-                     const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt, const float* params, int ca,
-                     float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT,
-                     int n_columns) {
+// The one launch behind the four single-model entry points.  `what` names the call in the launch failure.
+static int wm_launch(colnde_handle* h, int slot, const char* what, const WmCall& c) {
+    HIPCHK(hipSetDevice(h->device));
     WmInferArgs a = {};
     wm_scalings(h, &a);
-    const float dz = Lz / (float)WM_NZ;
-    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.Lz = Lz; a.n_col = n_columns;
-    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT;
-    a.fused = d_u_out != nullptr; a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
-    a.diag = d_uw != nullptr; a.uw = d_uw; a.vw = d_vw; a.wT = d_wT;
-    a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top;
-    if (a.fused || a.diag) a.mpp = mpp_params(params, a.fused ? dt : dz * dz, dz, ca);          // (the diagnosis alone takes no step: c is not read)
+    a.io = c.io;
+    a.weights = c.weights;
+    const float dz = c.io.Lz / (float)WM_NZ;
+    if (a.io.fused() || a.io.diag()) a.mpp = mpp_params(c.params, a.io.fused() ? c.dt : dz * dz, dz, c.ca);      // (the diagnosis alone takes no step: c is not read)
     Timed tm(h, slot);
     hipError_t e = launch_wm_infer(a, h->stream);
     if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", what, hipGetErrorString(e));
@@ -228,11 +258,10 @@ extern "C" int colnde_wm_infer_dz_flux_dev(colnde_handle* h, const float* d_weig
                                            const float* d_top_flux, float Lz, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
     PLAIN_NETWORK_ONLY(h);
-    const void* const ptrs[8] = {d_weights, d_u, d_v, d_T, d_top_flux, d_dz_uw, d_dz_vw, d_dz_wT};
-    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    return wm_launch(h, K_INFER, "wm_infer", d_weights, d_u, d_v, d_T, d_top_flux, nullptr, nullptr, Lz, 0.0f, nullptr, 0, d_dz_uw, d_dz_vw, d_dz_wT, nullptr,
-                     nullptr, nullptr, nullptr, nullptr, nullptr, n_columns);
+    WmCall c = wm_call(d_weights, d_u, d_v, d_T, d_top_flux, Lz, n_columns);
+    wm_dz_group(&c, d_dz_uw, d_dz_vw, d_dz_wT);
+    if (wm_infer_check(h, __func__, c, true, false)) return 1;
+    return wm_launch(h, K_INFER, "wm_infer", c);
 }
 
 extern "C" int colnde_wm_embedded_step_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
@@ -241,21 +270,27 @@ extern "C" int colnde_wm_embedded_step_dev(colnde_handle* h, const float* d_weig
                                            float* d_T_out, int n_columns) {
     SINGLE_MODEL_ONLY(h);
     PLAIN_NETWORK_ONLY(h);
-    const void* const ptrs[8] = {d_weights, d_u, d_v, d_T, d_top_flux, d_dz_uw, d_dz_vw, d_dz_wT};
-    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
-    if (impl_diff_check(h, d_u, d_v, d_T, d_u_out, d_v_out, d_T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    return wm_launch(h, K_INFER, "wm_embedded_step", d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, nullptr, Lz, dt, params, convective_adjustment,
-                     d_dz_uw, d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, nullptr, nullptr, nullptr, n_columns);
+    WmCall c = wm_call(d_weights, d_u, d_v, d_T, d_top_flux, Lz, n_columns);
+    wm_physics(&c, d_halo_bottom, nullptr, dt, params, convective_adjustment);
+    wm_dz_group(&c, d_dz_uw, d_dz_vw, d_dz_wT);
+    wm_step_group(&c, d_u_out, d_v_out, d_T_out);
+    if (wm_infer_check(h, __func__, c, true, false)) return 1;
+    if (wm_step_check(h, c)) return 1;
+    return wm_launch(h, K_INFER, "wm_embedded_step", c);
 }
-
 // ---- the saved-state flux diagnoses of the wind-mixing embedding (NDE_oceananigans.jl:157-191, :226-286) ---------------------------------
-static int wm_diag_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, const float params[7], int n_columns) {
-    if (wm_infer_check(h, fn, ptrs, n_ptrs, Lz, n_columns)) return 1;
-    if (!params) return fail("null pointer argument");
-    if (!(params[2] != 0.0f) || !(params[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
-    for (int i = 0; i < n_ptrs; i++)
-        if ((uintptr_t)ptrs[i] & 15) return fail("%s: the state and output arrays must be 16-byte aligned", fn);
+// the device calls that write the faces; step: the d/dz arrays and u_out, v_out, T_out with them
+static int wm_diag_check(colnde_handle* h, const char* fn, const WmCall& c, bool step) {
+    const WmEmbedIO& io = c.io;
+    if (!h) return fail("null handle");
+    if (wm_shape_check(h, fn)) return 1;
+    if (!io.u || !io.v || !io.T || !io.uw || !io.vw || !io.wT) return fail("null pointer argument");
+    if (step && (!io.dz_uw || !io.dz_vw || !io.dz_wT || !io.u_out || !io.v_out || !io.T_out)) return fail("null pointer argument");
+    if (io.n_col < 1 || !(io.Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
+    if (!c.params) return fail("null pointer argument");
+    if (!(c.params[2] != 0.0f) || !(c.params[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
+    if (!wm_io_aligned(io, true)) return fail("%s: the state and output arrays must be 16-byte aligned", fn);
+    if (!c.weights || !io.top_flux) return fail("null pointer argument");
     return 0;
 }
 
@@ -264,12 +299,11 @@ extern "C" int colnde_wm_diagnose_flux_dev(colnde_handle* h, const float* d_weig
                                            int convective_adjustment, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
     PLAIN_NETWORK_ONLY(h);
-    const void* const ptrs[8] = {d_u, d_v, d_T, d_uw, d_vw, d_wT, d_weights, d_top_flux};
-    if (wm_diag_check(h, __func__, ptrs, 6, Lz, params, n_columns)) return 1;
-    if (!d_weights || !d_top_flux) return fail("null pointer argument");
-    HIPCHK(hipSetDevice(h->device));
-    return wm_launch(h, K_FLUXDIAG, __func__, d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, 0.0f, params, convective_adjustment, nullptr,
-                     nullptr, nullptr, nullptr, nullptr, nullptr, d_uw, d_vw, d_wT, n_columns);
+    WmCall c = wm_call(d_weights, d_u, d_v, d_T, d_top_flux, Lz, n_columns);
+    wm_physics(&c, d_halo_bottom, d_halo_top, 0.0f, params, convective_adjustment);
+    wm_face_group(&c, d_uw, d_vw, d_wT);
+    if (wm_diag_check(h, __func__, c, false)) return 1;
+    return wm_launch(h, K_FLUXDIAG, __func__, c);
 }
 
 extern "C" int colnde_wm_embedded_step_flux_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
@@ -278,45 +312,51 @@ extern "C" int colnde_wm_embedded_step_flux_dev(colnde_handle* h, const float* d
                                                 float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
     PLAIN_NETWORK_ONLY(h);
-    const void* const ptrs[12] = {d_u, d_v, d_T, d_dz_uw, d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT};
-    if (wm_diag_check(h, __func__, ptrs, 12, Lz, params, n_columns)) return 1;
-    if (!d_weights || !d_top_flux) return fail("null pointer argument");
-    if (impl_diff_check(h, d_u, d_v, d_T, d_u_out, d_v_out, d_T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
-    HIPCHK(hipSetDevice(h->device));
+    WmCall c = wm_call(d_weights, d_u, d_v, d_T, d_top_flux, Lz, n_columns);
+    wm_physics(&c, d_halo_bottom, d_halo_top, dt, params, convective_adjustment);
+    wm_dz_group(&c, d_dz_uw, d_dz_vw, d_dz_wT);
+    wm_step_group(&c, d_u_out, d_v_out, d_T_out);
+    wm_face_group(&c, d_uw, d_vw, d_wT);
+    if (wm_diag_check(h, __func__, c, true)) return 1;
+    if (wm_step_check(h, c)) return 1;
     // One launch, by measurement (profiles/wm_diag_rate.json): it beats colnde_wm_embedded_step_dev + colnde_wm_diagnose_flux_dev by far more than
     // the spread at 9,216, 65,536 and 1,048,576 columns.
-    return wm_launch(h, K_FLUXDIAG, __func__, d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, params, convective_adjustment, d_dz_uw,
-                     d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT, n_columns);
+    return wm_launch(h, K_FLUXDIAG, __func__, c);
 }
 
-// The host arrays of the four single-model entry points, checked by them.  The groups that are given choose the _dev call: u_out, v_out, T_out the
-// step (in place on the u | v | T blocks it uploaded), uw, vw, wT the faces; without the faces the three d/dz arrays are always written.
-static int wm_host(colnde_handle* h, const char* fn, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
-                   const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params, int ca, float* dz_uw, float* dz_vw, float* dz_wT,
-                   float* u_out, float* v_out, float* T_out, float* uw, float* vw, float* wT, int n_columns) {
+// The host arrays of a call its entry point has checked: staged in one scratch, the call's _dev twin on the device blocks, the outputs copied back.
+// The step works in place on the u | v | T blocks it uploaded.  ens: colnde_ensemble_wm_embedded — the K models' blocks, top_flux [3][n] shared by
+// them, the halos [K][3][n]; otherwise the groups that are given choose among the four single-model calls.
+static int wm_host(colnde_handle* h, const char* fn, const WmCall& c, bool ens) {
     HIPCHK(hipSetDevice(h->device));
-    const size_t nc = (size_t)n_columns;
-    const float* src[3] = {u, v, T};
-    float *dst[3] = {u_out, v_out, T_out}, *dzs[3] = {dz_uw, dz_vw, dz_wT}, *faces[3] = {uw, vw, wT};
+    const WmEmbedIO& io = c.io;
+    const size_t K = ens ? (size_t)h->n_models : 1, nc = (size_t)io.n_col;
+    const float* src[3] = {io.u, io.v, io.T};
+    float *dst[3] = {io.u_out, io.v_out, io.T_out}, *dzs[3] = {io.dz_uw, io.dz_vw, io.dz_wT}, *faces[3] = {io.uw, io.vw, io.wT};
     float *d_s[3], *d_o[3], *d_dz[3], *d_f[3], *d_top, *d_hb, *d_ht;
     HostStage st(h, fn);
-    st.to(h->d_w, weights, (size_t)h->m.n_params);
-    for (int f = 0; f < 3; f++) st.inout(&d_s[f], &d_o[f], src[f], dst[f], nc * WM_NZ);
-    for (int f = 0; f < 3; f++) st.out(&d_dz[f], dzs[f], nc * WM_NZ);
-    for (int f = 0; f < 3; f++) st.out(&d_f[f], faces[f], nc * (WM_NZ + 1));
-    st.in(&d_top, top_flux, 3 * nc);
-    st.in(&d_hb, halo_bottom, 3 * nc);
-    st.in(&d_ht, halo_top, 3 * nc);
+    st.to(h->d_w, c.weights, K * (size_t)h->m.n_params);
+    for (int f = 0; f < 3; f++) st.inout(&d_s[f], &d_o[f], src[f], dst[f], K * nc * WM_NZ);
+    for (int f = 0; f < 3; f++) st.out(&d_dz[f], dzs[f], K * nc * WM_NZ);
+    for (int f = 0; f < 3; f++) st.out(&d_f[f], faces[f], K * nc * (WM_NZ + 1));
+    st.in(&d_top, io.top_flux, 3 * nc);
+    st.in(&d_hb, io.halo_bottom, 3 * K * nc);
+    st.in(&d_ht, io.halo_top, 3 * K * nc);
     if (st.upload()) return 1;
+    const float* const w = h->d_w;
+    const int n = io.n_col;
     int rc;
-    if (uw)
-        rc = u_out ? colnde_wm_embedded_step_flux_dev(h, h->d_w, d_s[0], d_s[1], d_s[2], d_top, d_hb, d_ht, Lz, dt, params, ca, d_dz[0], d_dz[1], d_dz[2], d_o[0],
-                                                      d_o[1], d_o[2], d_f[0], d_f[1], d_f[2], n_columns)
-                   : colnde_wm_diagnose_flux_dev(h, h->d_w, d_s[0], d_s[1], d_s[2], d_top, d_hb, d_ht, Lz, params, ca, d_f[0], d_f[1], d_f[2], n_columns);
+    if (ens)
+        rc = colnde_ensemble_wm_embedded_dev(h, w, d_s[0], d_s[1], d_s[2], d_top, d_hb, d_ht, io.Lz, c.dt, c.params, c.ca, d_dz[0], d_dz[1], d_dz[2], d_o[0], d_o[1],
+                                             d_o[2], d_f[0], d_f[1], d_f[2], n);
+    else if (io.diag())
+        rc = io.fused() ? colnde_wm_embedded_step_flux_dev(h, w, d_s[0], d_s[1], d_s[2], d_top, d_hb, d_ht, io.Lz, c.dt, c.params, c.ca, d_dz[0], d_dz[1], d_dz[2],
+                                                           d_o[0], d_o[1], d_o[2], d_f[0], d_f[1], d_f[2], n)
+                        : colnde_wm_diagnose_flux_dev(h, w, d_s[0], d_s[1], d_s[2], d_top, d_hb, d_ht, io.Lz, c.params, c.ca, d_f[0], d_f[1], d_f[2], n);
     else
-        rc = u_out ? colnde_wm_embedded_step_dev(h, h->d_w, d_s[0], d_s[1], d_s[2], d_top, d_hb, Lz, dt, params, ca, d_dz[0], d_dz[1], d_dz[2], d_o[0], d_o[1],
-                                                 d_o[2], n_columns)
-                   : colnde_wm_infer_dz_flux_dev(h, h->d_w, d_s[0], d_s[1], d_s[2], d_top, Lz, d_dz[0], d_dz[1], d_dz[2], n_columns);
+        rc = io.fused() ? colnde_wm_embedded_step_dev(h, w, d_s[0], d_s[1], d_s[2], d_top, d_hb, io.Lz, c.dt, c.params, c.ca, d_dz[0], d_dz[1], d_dz[2], d_o[0],
+                                                      d_o[1], d_o[2], n)
+                        : colnde_wm_infer_dz_flux_dev(h, w, d_s[0], d_s[1], d_s[2], d_top, io.Lz, d_dz[0], d_dz[1], d_dz[2], n);
     return rc ? 1 : st.download();
 }
 
@@ -324,10 +364,10 @@ extern "C" int colnde_wm_infer_dz_flux(colnde_handle* h, const float* weights, c
                                        float* dz_uw, float* dz_vw, float* dz_wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
     PLAIN_NETWORK_ONLY(h);
-    const void* const ptrs[8] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT};
-    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
-    return wm_host(h, __func__, weights, u, v, T, top_flux, nullptr, nullptr, Lz, 0.0f, nullptr, 0, dz_uw, dz_vw, dz_wT, nullptr, nullptr, nullptr, nullptr, nullptr,
-                   nullptr, n_columns);
+    WmCall c = wm_call(weights, u, v, T, top_flux, Lz, n_columns);
+    wm_dz_group(&c, dz_uw, dz_vw, dz_wT);
+    if (wm_infer_check(h, __func__, c, true, false)) return 1;
+    return wm_host(h, __func__, c, false);
 }
 
 extern "C" int colnde_wm_embedded_step(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
@@ -335,11 +375,13 @@ extern "C" int colnde_wm_embedded_step(colnde_handle* h, const float* weights, c
                                        float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, int n_columns) {
     SINGLE_MODEL_ONLY(h);
     PLAIN_NETWORK_ONLY(h);
-    const void* const ptrs[8] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT};
-    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
-    if (impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
-    return wm_host(h, __func__, weights, u, v, T, top_flux, halo_bottom, nullptr, Lz, dt, params, convective_adjustment, dz_uw, dz_vw, dz_wT, u_out, v_out, T_out,
-                   nullptr, nullptr, nullptr, n_columns);
+    WmCall c = wm_call(weights, u, v, T, top_flux, Lz, n_columns);
+    wm_physics(&c, halo_bottom, nullptr, dt, params, convective_adjustment);
+    wm_dz_group(&c, dz_uw, dz_vw, dz_wT);
+    wm_step_group(&c, u_out, v_out, T_out);
+    if (wm_infer_check(h, __func__, c, true, false)) return 1;
+    if (wm_step_check(h, c)) return 1;
+    return wm_host(h, __func__, c, false);
 }
 
 extern "C" int colnde_wm_diagnose_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
@@ -347,11 +389,12 @@ extern "C" int colnde_wm_diagnose_flux(colnde_handle* h, const float* weights, c
                                        float* vw, float* wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
     PLAIN_NETWORK_ONLY(h);
-    const void* const ptrs[8] = {weights, u, v, T, top_flux, uw, vw, wT};
-    if (wm_infer_check(h, __func__, ptrs, 8, Lz, n_columns)) return 1;
+    WmCall c = wm_call(weights, u, v, T, top_flux, Lz, n_columns);
+    wm_physics(&c, halo_bottom, halo_top, 0.0f, params, convective_adjustment);
+    wm_face_group(&c, uw, vw, wT);
+    if (wm_infer_check(h, __func__, c, false, true)) return 1;
     if (!params) return fail("null pointer argument");
-    return wm_host(h, __func__, weights, u, v, T, top_flux, halo_bottom, halo_top, Lz, 0.0f, params, convective_adjustment, nullptr, nullptr, nullptr, nullptr,
-                   nullptr, nullptr, uw, vw, wT, n_columns);
+    return wm_host(h, __func__, c, false);
 }
 
 extern "C" int colnde_wm_embedded_step_flux(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
@@ -360,11 +403,14 @@ extern "C" int colnde_wm_embedded_step_flux(colnde_handle* h, const float* weigh
                                             float* uw, float* vw, float* wT, int n_columns) {
     SINGLE_MODEL_ONLY(h);
     PLAIN_NETWORK_ONLY(h);
-    const void* const ptrs[11] = {weights, u, v, T, top_flux, dz_uw, dz_vw, dz_wT, uw, vw, wT};
-    if (wm_infer_check(h, __func__, ptrs, 11, Lz, n_columns)) return 1;
-    if (impl_diff_check(h, u, v, T, u_out, v_out, T_out, dt, Lz / (float)WM_NZ, params, n_columns)) return 1;
-    return wm_host(h, __func__, weights, u, v, T, top_flux, halo_bottom, halo_top, Lz, dt, params, convective_adjustment, dz_uw, dz_vw, dz_wT, u_out, v_out,
-                   T_out, uw, vw, wT, n_columns);
+    WmCall c = wm_call(weights, u, v, T, top_flux, Lz, n_columns);
+    wm_physics(&c, halo_bottom, halo_top, dt, params, convective_adjustment);
+    wm_dz_group(&c, dz_uw, dz_vw, dz_wT);
+    wm_step_group(&c, u_out, v_out, T_out);
+    wm_face_group(&c, uw, vw, wT);
+    if (wm_infer_check(h, __func__, c, true, true)) return 1;
+    if (wm_step_check(h, c)) return 1;
+    return wm_host(h, __func__, c, false);
 }
 
 // ---- the K models of an ensemble in the embedding at once (engine_wm_infer.hip: wm_infer_ens_kernel) -------------------------------
@@ -375,43 +421,35 @@ static void wm_ens_model_params(const colnde_handle* h, int k, float out[7]) {
 }
 
 // everything the call refuses that does not depend on where the arrays live; host: the host twin's arrays (no alignment rule of their own)
-static int wm_ens_check(colnde_handle* h, const char* fn, const float* weights, const float* u, const float* v, const float* T, const float* top_flux, float Lz,
-                        float dt, const float* params, const float* dz_uw, const float* dz_vw, const float* dz_wT, const float* u_out, const float* v_out,
-                        const float* T_out, const float* uw, const float* vw, const float* wT, int n_columns, bool host) {
+static int wm_ens_check(colnde_handle* h, const char* fn, const WmCall& c, bool host) {
+    const WmEmbedIO& io = c.io;
     if (!h) return fail("null handle");
     if (h->closure)
         return fail("%s takes K weight vectors, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", fn,
                     h->n_models);
     if (wm_generic_shape(h)) {
         const WmAnyPlan plan = wm_generic_plan(h);
-        if (!wm_any_fits(plan)) {
-            std::string shape_is;
-            for (int l = 0; l <= h->cfg.n_layers; l++) shape_is += (l ? "-" : "") + std::to_string(h->cfg.layer_sizes[l]);
+        if (!wm_any_fits(plan))
             return fail("%s: the networks %s need %zu bytes of LDS per 16-column tile (state and face rows, the scaled input, the outputs and two activation buffers "
-                        "of %d and %d floats per column), more than the %d bytes of a workgroup; hidden widths up to 600 fit", fn, shape_is.c_str(), plan.bytes,
-                        plan.ld[0], plan.ld[1], WMA_LDS_LIMIT);
-        }
+                        "of %d and %d floats per column), more than the %d bytes of a workgroup; hidden widths up to 600 fit", fn,
+                        layer_sizes_string(h->cfg).c_str(), plan.bytes, plan.ld[0], plan.ld[1], WMA_LDS_LIMIT);
     } else if (wm_shape_check(h, fn)) return 1;
-    if (!weights || !u || !v || !T || !top_flux || !dz_uw || !dz_vw || !dz_wT) return fail("null pointer argument");
-    const int n_step = (u_out != nullptr) + (v_out != nullptr) + (T_out != nullptr), n_flux = (uw != nullptr) + (vw != nullptr) + (wT != nullptr);
+    if (!c.weights || !io.u || !io.v || !io.T || !io.top_flux || !io.dz_uw || !io.dz_vw || !io.dz_wT) return fail("null pointer argument");
+    const int n_step = (io.u_out != nullptr) + (io.v_out != nullptr) + (io.T_out != nullptr), n_flux = (io.uw != nullptr) + (io.vw != nullptr) + (io.wT != nullptr);
     if (n_step != 0 && n_step != 3)
         return fail("%s: u_out, v_out, T_out are one output group — all three given (the implicit step is taken) or all three NULL (no step); %d of 3 given", fn, n_step);
     if (n_flux != 0 && n_flux != 3)
         return fail("%s: uw, vw, wT are one output group — all three given (the face diagnosis) or all three NULL; %d of 3 given", fn, n_flux);
-    if (n_columns < 1 || !(Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
-    if (n_step && !(dt > 0.0f)) return fail("%s: dt > 0 required when a step is asked for (u_out, v_out, T_out given); dt = %g", fn, dt);
+    if (io.n_col < 1 || !(io.Lz > 0.0f)) return fail("n_columns >= 1 and Lz > 0 required");
+    if (n_step && !(c.dt > 0.0f)) return fail("%s: dt > 0 required when a step is asked for (u_out, v_out, T_out given); dt = %g", fn, c.dt);
     for (int k = 0; k < h->n_models; k++) {
         float own[7];
-        const float* p = params ? params + (size_t)7 * k : own;
-        if (!params) wm_ens_model_params(h, k, own);
+        const float* p = c.params ? c.params + (size_t)7 * k : own;
+        if (!c.params) wm_ens_model_params(h, k, own);
         if (n_step && (!(p[0] >= 0.0f) || !(p[1] >= 0.0f))) return fail("nu0 >= 0 and nu_minus >= 0 required (the tridiagonal must stay diagonally dominant)");
         if (!(p[2] != 0.0f) || !(p[4] > 0.0f)) return fail("dRi != 0 and Pr > 0 required");
     }
-    if (!host) {
-        const void* const ptrs[12] = {u, v, T, dz_uw, dz_vw, dz_wT, u_out, v_out, T_out, uw, vw, wT};
-        for (const void* p : ptrs)
-            if ((uintptr_t)p & 15) return fail("%s: the state and output arrays must be 16-byte aligned", fn);
-    }
+    if (!host && !wm_io_aligned(io, true)) return fail("%s: the state and output arrays must be 16-byte aligned", fn);
     return 0;
 }
 
@@ -442,9 +480,7 @@ static int wm_ens_grid_cap() {
 
 // A single handle of any architecture as K = 1: the one launch of wm_embed_any_kernel (the caller has run wm_ens_check).  The constants are the
 // handle's own unless params is given; they travel as a kernel argument, there is no device table.
-static int wm_generic_launch(colnde_handle* h, const char* fn, const float* d_weights, const float* d_u, const float* d_v, const float* d_T, const float* d_top_flux,
-                             const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt, const float* params, int ca, float* d_dz_uw, float* d_dz_vw,
-                             float* d_dz_wT, float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
+static int wm_generic_launch(colnde_handle* h, const char* fn, const WmCall& c) {
     WmAnyArgs a = {};
     const DevModel& m = h->m;
     a.net.n_layers = m.n_layers;
@@ -452,17 +488,30 @@ static int wm_generic_launch(colnde_handle* h, const char* fn, const float* d_we
     for (int l = 0; l < m.n_layers; l++) { a.net.sizes[l] = m.sizes[l]; a.net.acts[l] = m.acts[l]; a.net.w_off[l] = m.w_off[l]; a.net.b_off[l] = m.b_off[l]; }
     a.net.sizes[m.n_layers] = m.sizes[m.n_layers];
     for (int i = 0; i < 6; i++) { a.mu[i] = h->cfg.mu[i]; a.sigma[i] = h->cfg.sigma[i]; }
-    const float dz = Lz / (float)WM_NZ;
-    a.weights = d_weights; a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top; a.Lz = Lz;
-    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT;
-    a.fused = d_u_out != nullptr; a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
-    a.diag = d_uw != nullptr; a.uw = d_uw; a.vw = d_vw; a.wT = d_wT;
-    a.n_col = n_columns;
+    a.io = c.io;
+    a.weights = c.weights;
+    const float dz = c.io.Lz / (float)WM_NZ;
     float own[7];
-    if (!params) wm_ens_model_params(h, 0, own);
-    a.mpp = mpp_params(params ? params : own, a.fused ? dt : dz * dz, dz, ca);              // (without a step c is not read: 1, as the other diagnoses pass it)
+    if (!c.params) wm_ens_model_params(h, 0, own);
+    a.mpp = mpp_params(c.params ? c.params : own, a.io.fused() ? c.dt : dz * dz, dz, c.ca);      // (without a step c is not read: 1, as the other diagnoses pass it)
     Timed tm(h, K_FLUXDIAG);
     hipError_t e = launch_wm_embed_any(a, h->stream);
+    if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", fn, hipGetErrorString(e));
+    return 0;
+}
+
+// the K models of an ensemble (or a single handle of the fixed shape as K = 1): the one launch of wm_infer_ens_kernel
+static int wm_ens_launch(colnde_handle* h, const char* fn, const WmCall& c) {
+    if (wm_ens_upload_mpp(h, c.params, c.io.fused(), c.dt, c.io.Lz / (float)WM_NZ, c.ca)) return 1;
+    WmEnsArgs a = {};
+    wm_scalings(h, &a);
+    a.io = c.io;
+    a.n_models = h->n_models; a.weights = c.weights; a.w_stride = (size_t)h->m.n_params;
+    a.mpp = h->d_wm_ens_mpp;
+    a.grid_cap = wm_ens_grid_cap();
+    // One launch at every size, by measurement (profiles/wm_ens_embed_rate.json, DESIGN §4k)
+    Timed tm(h, K_FLUXDIAG);
+    hipError_t e = launch_wm_infer_ens(a, h->stream);
     if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", fn, hipGetErrorString(e));
     return 0;
 }
@@ -471,55 +520,28 @@ extern "C" int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_
                                                const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt,
                                                const float* params, int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT,
                                                float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
-    if (wm_ens_check(h, __func__, d_weights, d_u, d_v, d_T, d_top_flux, Lz, dt, params, d_dz_uw, d_dz_vw, d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT,
-                     n_columns, false))
-        return 1;
+    WmCall c = wm_call(d_weights, d_u, d_v, d_T, d_top_flux, Lz, n_columns);
+    wm_physics(&c, d_halo_bottom, d_halo_top, dt, params, convective_adjustment);
+    wm_dz_group(&c, d_dz_uw, d_dz_vw, d_dz_wT);
+    wm_step_group(&c, d_u_out, d_v_out, d_T_out);
+    wm_face_group(&c, d_uw, d_vw, d_wT);
+    if (wm_ens_check(h, __func__, c, false)) return 1;
     HIPCHK(hipSetDevice(h->device));
-    const bool step = d_u_out != nullptr;
-    if (wm_generic_serves(h))
-        return wm_generic_launch(h, __func__, d_weights, d_u, d_v, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, params, convective_adjustment, d_dz_uw, d_dz_vw,
-                                 d_dz_wT, d_u_out, d_v_out, d_T_out, d_uw, d_vw, d_wT, n_columns);
-    if (wm_ens_upload_mpp(h, params, step, dt, Lz / (float)WM_NZ, convective_adjustment)) return 1;
-    WmEnsArgs a = {};
-    wm_scalings(h, &a);
-    a.n_models = h->n_models; a.weights = d_weights; a.w_stride = (size_t)h->m.n_params;
-    a.u = d_u; a.v = d_v; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top; a.Lz = Lz; a.mpp = h->d_wm_ens_mpp;
-    a.dz_uw = d_dz_uw; a.dz_vw = d_dz_vw; a.dz_wT = d_dz_wT;
-    a.fused = step; a.u_out = d_u_out; a.v_out = d_v_out; a.T_out = d_T_out;
-    a.diag = d_uw != nullptr; a.uw = d_uw; a.vw = d_vw; a.wT = d_wT;
-    a.n_col = n_columns;
-    a.grid_cap = wm_ens_grid_cap();
-    // One launch at every size, by measurement (profiles/wm_ens_embed_rate.json, DESIGN §4k)
-    Timed tm(h, K_FLUXDIAG);
-    hipError_t e = launch_wm_infer_ens(a, h->stream);
-    if (e != hipSuccess) return fail("%s launch failed: %s (the state and output arrays must be 16-byte aligned)", __func__, hipGetErrorString(e));
-    return 0;
+    return wm_generic_serves(h) ? wm_generic_launch(h, __func__, c) : wm_ens_launch(h, __func__, c);
 }
 
-// host arrays: the step in place on the u | v | T blocks; top_flux [3][n] is shared by the models, the halos are [K][3][n]
+// host arrays (wm_host: the K models' blocks)
 extern "C" int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weights, const float* u, const float* v, const float* T, const float* top_flux,
                                            const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params, int convective_adjustment,
                                            float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, float* uw, float* vw, float* wT,
                                            int n_columns) {
-    if (wm_ens_check(h, __func__, weights, u, v, T, top_flux, Lz, dt, params, dz_uw, dz_vw, dz_wT, u_out, v_out, T_out, uw, vw, wT, n_columns, true)) return 1;
-    HIPCHK(hipSetDevice(h->device));
-    const size_t K = (size_t)h->n_models, nc = (size_t)n_columns;
-    const float* src[3] = {u, v, T};
-    float *dst[3] = {u_out, v_out, T_out}, *dzs[3] = {dz_uw, dz_vw, dz_wT}, *faces[3] = {uw, vw, wT};
-    float *d_s[3], *d_o[3], *d_dz[3], *d_f[3], *d_top, *d_hb, *d_ht;
-    HostStage st(h, __func__);
-    st.to(h->d_w, weights, K * h->m.n_params);
-    for (int f = 0; f < 3; f++) st.inout(&d_s[f], &d_o[f], src[f], dst[f], K * nc * WM_NZ);
-    for (int f = 0; f < 3; f++) st.out(&d_dz[f], dzs[f], K * nc * WM_NZ);
-    for (int f = 0; f < 3; f++) st.out(&d_f[f], faces[f], K * nc * (WM_NZ + 1));
-    st.in(&d_top, top_flux, 3 * nc);
-    st.in(&d_hb, halo_bottom, 3 * K * nc);
-    st.in(&d_ht, halo_top, 3 * K * nc);
-    if (st.upload()) return 1;
-    if (colnde_ensemble_wm_embedded_dev(h, h->d_w, d_s[0], d_s[1], d_s[2], d_top, d_hb, d_ht, Lz, dt, params, convective_adjustment, d_dz[0], d_dz[1], d_dz[2],
-                                        d_o[0], d_o[1], d_o[2], d_f[0], d_f[1], d_f[2], n_columns))
-        return 1;
-    return st.download();
+    WmCall c = wm_call(weights, u, v, T, top_flux, Lz, n_columns);
+    wm_physics(&c, halo_bottom, halo_top, dt, params, convective_adjustment);
+    wm_dz_group(&c, dz_uw, dz_vw, dz_wT);
+    wm_step_group(&c, u_out, v_out, T_out);
+    wm_face_group(&c, uw, vw, wT);
+    if (wm_ens_check(h, __func__, c, true)) return 1;
+    return wm_host(h, __func__, c, true);
 }
 
 // diagnose_baseline_flux_uw / _vw / _wT (:157-191; column_ops.hip): no networks, any handle kind
@@ -584,12 +606,9 @@ static int fce_shape_check(const colnde_handle* h, const char* fn) {
         return fail("%s needs a free-convection handle (one network on T); a wind-mixing handle has colnde_wm_embedded_step", fn);
     if (h->ag_rows) return fail("%s: this handle's network keeps its activation rows in global memory (a wide network); the embedded step covers the fc32 shapes only", fn);
     if (c.Nz != 32 && c.Nz != 64) return fail("%s covers Nz = 32 or 64 (this handle has Nz = %d)", fn, c.Nz);
-    if (!fce_shape_covers(h)) {
-        std::string shape;
-        for (int l = 0; l <= c.n_layers; l++) shape += (l ? "-" : "") + std::to_string(c.layer_sizes[l]);
+    if (!fce_shape_covers(h))
         return fail("%s covers the fc32 network Dense(Nz,4Nz,relu), Dense(4Nz,4Nz,relu), Dense(4Nz,Nz-1); this handle has Nz = %d and network %s", fn, c.Nz,
-                    shape.c_str());
-    }
+                    layer_sizes_string(c).c_str());
     return 0;
 }
 static int fce_check(colnde_handle* h, const char* fn, const void* const* ptrs, int n_ptrs, float Lz, float K, int n_columns) {
@@ -613,15 +632,22 @@ static int fce_prepare(colnde_handle* h) {
     h->fce_ready = true;
     return 0;
 }
-static int fce_launch(colnde_handle* h, const char* fn, bool step, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
-                      const float* d_halo_top, float Lz, float dt, float K, float* d_dz_wT, float* d_T_out, float* d_wT_faces, int n_columns) {
-    if (fce_prepare(h)) return 1;
+// One call as its entry point received it: FcEmbedArgs (engine_fc_embed.h) without the operand images and the tile width, which the launch fills in.
+// dz_wT given: the step.
+static FcEmbedArgs fce_call(const float* T, const float* top_flux, const float* halo_bottom, const float* halo_top, float Lz, float dt, float K, float* dz_wT,
+                            float* T_out, float* wT_faces, int n_columns) {
     FcEmbedArgs a = {};
-    a.cw = fc_tile_width(n_columns);                         // (the images are packed per call: this call's own tile width, as colnde_infer_forcing)
+    a.T = T; a.top_flux = top_flux; a.halo_bottom = halo_bottom; a.halo_top = halo_top;
+    a.Lz = Lz; a.dt = dt; a.K = K; a.dz_wT = dz_wT; a.T_out = T_out; a.wT_faces = wT_faces; a.n_col = n_columns; a.step = dz_wT != nullptr;
+    return a;
+}
+
+static int fce_launch(colnde_handle* h, const char* fn, const float* d_weights, FcEmbedArgs a) {
+    if (fce_prepare(h)) return 1;
+    a.cw = fc_tile_width(a.n_col);                           // (the images are packed per call: this call's own tile width, as colnde_infer_forcing)
     hipError_t e = fc_launch_pack(h->m, a.cw, d_weights, h->d_fc_imgf, h->d_fc_imgb, h->d_fc_bias, nullptr, nullptr, h->stream);
     if (e != hipSuccess) return fail("fc32 pack launch failed: %s", hipGetErrorString(e));
-    a.imgf = h->d_fc_imgf; a.bias = h->d_fc_bias; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top;
-    a.Lz = Lz; a.dt = dt; a.K = K; a.dz_wT = d_dz_wT; a.T_out = d_T_out; a.wT_faces = d_wT_faces; a.n_col = n_columns; a.step = step;
+    a.imgf = h->d_fc_imgf; a.bias = h->d_fc_bias;
     Timed tm(h, K_FCEMBED);
     e = launch_fc_embed(h->m, a, h->stream);
     if (e != hipSuccess) return fail("%s launch failed: %s (T and the output arrays must be 16-byte aligned)", fn, hipGetErrorString(e));
@@ -646,7 +672,7 @@ extern "C" int colnde_fc_embedded_step_dev(colnde_handle* h, const float* d_weig
         if (colnde_infer_dz_wT_dev(h, d_weights, d_T, d_top_flux, Lz, d_dz_wT, n_columns)) return 1;
         return colnde_convective_adjustment_dev(h, d_T, d_halo_bottom, d_halo_top, dt, Lz / (float)h->m.Nz, K, d_T_out, n_columns);
     }
-    return fce_launch(h, __func__, true, d_weights, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, K, d_dz_wT, d_T_out, d_wT_faces, n_columns);
+    return fce_launch(h, __func__, d_weights, fce_call(d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, K, d_dz_wT, d_T_out, d_wT_faces, n_columns));
 }
 
 extern "C" int colnde_fc_diagnose_wT_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
@@ -655,28 +681,32 @@ extern "C" int colnde_fc_diagnose_wT_dev(colnde_handle* h, const float* d_weight
     PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[4] = {d_weights, d_T, d_top_flux, d_wT_faces};
     if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
-    return fce_launch(h, __func__, false, d_weights, d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, 0.0f, K, nullptr, nullptr, d_wT_faces, n_columns);
+    return fce_launch(h, __func__, d_weights, fce_call(d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, 0.0f, K, nullptr, nullptr, d_wT_faces, n_columns));
 }
 
-// host arrays; T_out given: the step, in place on the T block it uploaded
-static int fce_host(colnde_handle* h, const char* fn, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
-                    const float* halo_top, float Lz, float dt, float K, float* dz_wT, float* T_out, float* wT_faces, int n_columns) {
+// The host arrays of a call its entry point has checked: staged in one scratch, the call's _dev twin on the device blocks, the outputs copied back;
+// the step works in place on the T block it uploaded.  ens: colnde_ensemble_fc_embedded — the K members' blocks, their vectors user_params(h) floats
+// apart (weights == NULL: the images of the previous call), top_flux [n] shared by them, the halos [K][n]; otherwise T_out chooses between the two
+// single-model calls.
+static int fce_host(colnde_handle* h, const char* fn, const float* weights, const FcEmbedArgs& c, bool ens) {
     HIPCHK(hipSetDevice(h->device));
-    const size_t Nz = (size_t)h->m.Nz, nc = (size_t)n_columns;
+    const size_t K = ens ? (size_t)h->n_models : 1, Nz = (size_t)h->m.Nz, nc = (size_t)c.n_col;
     float *d_T, *d_To, *d_dz, *d_faces, *d_top, *d_hb, *d_ht;
     HostStage st(h, fn);
-    st.to(h->d_w, weights, (size_t)h->m.n_params);
-    st.inout(&d_T, &d_To, T, T_out, nc * Nz);
-    st.out(&d_dz, dz_wT, nc * Nz);
-    st.out(&d_faces, wT_faces, nc * (Nz + 1));
-    st.in(&d_top, top_flux, nc);
-    st.in(&d_hb, halo_bottom, nc);
-    st.in(&d_ht, halo_top, nc);
+    if (weights) st.to(h->d_w, weights, K * (size_t)(ens ? user_params(h) : h->m.n_params));
+    st.inout(&d_T, &d_To, c.T, c.T_out, K * nc * Nz);
+    st.out(&d_dz, c.dz_wT, K * nc * Nz);
+    st.out(&d_faces, c.wT_faces, K * nc * (Nz + 1));
+    st.in(&d_top, c.top_flux, nc);
+    st.in(&d_hb, c.halo_bottom, K * nc);
+    st.in(&d_ht, c.halo_top, K * nc);
     if (st.upload()) return 1;
-    if (T_out ? colnde_fc_embedded_step_dev(h, h->d_w, d_T, d_top, d_hb, d_ht, Lz, dt, K, d_dz, d_To, d_faces, n_columns)
-              : colnde_fc_diagnose_wT_dev(h, h->d_w, d_T, d_top, d_hb, d_ht, Lz, K, d_faces, n_columns))
-        return 1;
-    return st.download();
+    const float* const w = weights ? h->d_w : nullptr;
+    int rc;
+    if (ens) rc = colnde_ensemble_fc_embedded_dev(h, w, d_T, d_top, d_hb, d_ht, c.Lz, c.dt, c.K, d_dz, d_To, d_faces, c.n_col);
+    else if (c.T_out) rc = colnde_fc_embedded_step_dev(h, w, d_T, d_top, d_hb, d_ht, c.Lz, c.dt, c.K, d_dz, d_To, d_faces, c.n_col);
+    else rc = colnde_fc_diagnose_wT_dev(h, w, d_T, d_top, d_hb, d_ht, c.Lz, c.K, d_faces, c.n_col);
+    return rc ? 1 : st.download();
 }
 
 extern "C" int colnde_fc_embedded_step(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
@@ -686,7 +716,7 @@ extern "C" int colnde_fc_embedded_step(colnde_handle* h, const float* weights, c
     const void* const ptrs[5] = {weights, T, top_flux, dz_wT, T_out};
     if (fce_check(h, __func__, ptrs, 5, Lz, K, n_columns)) return 1;
     if (!(dt > 0.0f)) return fail("dt > 0 required");
-    return fce_host(h, __func__, weights, T, top_flux, halo_bottom, halo_top, Lz, dt, K, dz_wT, T_out, wT_faces, n_columns);
+    return fce_host(h, __func__, weights, fce_call(T, top_flux, halo_bottom, halo_top, Lz, dt, K, dz_wT, T_out, wT_faces, n_columns), false);
 }
 
 extern "C" int colnde_fc_diagnose_wT(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
@@ -695,14 +725,13 @@ extern "C" int colnde_fc_diagnose_wT(colnde_handle* h, const float* weights, con
     PLAIN_NETWORK_ONLY(h);
     const void* const ptrs[4] = {weights, T, top_flux, wT_faces};
     if (fce_check(h, __func__, ptrs, 4, Lz, K, n_columns)) return 1;
-    return fce_host(h, __func__, weights, T, top_flux, halo_bottom, halo_top, Lz, 0.0f, K, nullptr, nullptr, wT_faces, n_columns);
+    return fce_host(h, __func__, weights, fce_call(T, top_flux, halo_bottom, halo_top, Lz, 0.0f, K, nullptr, nullptr, wT_faces, n_columns), false);
 }
 
 // ---- the K networks of a free-convection ensemble in the embedding at once (engine_fc_embed.hip: fce_ens_kernel) -------------------
 // A plain fc ensemble, a conv ensemble, or a single fc handle as K = 1, plain or conv.  Everything the call refuses that does not depend on where the
 // arrays live; host: the host twin's arrays (no alignment rule of their own).
-static int fce_ens_check(colnde_handle* h, const char* fn, const float* T, const float* top_flux, float Lz, float dt, float K, const float* dz_wT,
-                         const float* T_out, const float* wT_faces, int n_columns, bool host) {
+static int fce_ens_check(colnde_handle* h, const char* fn, const FcEmbedArgs& c, bool host) {
     if (!h) return fail("%s: null handle", fn);
     if (h->closure)
         return fail("%s takes K weight vectors, but this is a closure handle (no networks, %d constant sets): use colnde_closure_* (include/colnde.h)", fn,
@@ -710,18 +739,15 @@ static int fce_ens_check(colnde_handle* h, const char* fn, const float* T, const
     if (h->cfg.model == COLNDE_MODEL_WIND_MIXING)
         return fail("%s needs free-convection networks (one network on T per model); a wind-mixing handle has colnde_ensemble_wm_embedded", fn);
     if (fce_shape_check(h, fn)) return 1;
-    if (!T || !top_flux) return fail("%s: null pointer argument (T, top_flux)", fn);
-    if ((dz_wT != nullptr) != (T_out != nullptr))
+    if (!c.T || !c.top_flux) return fail("%s: null pointer argument (T, top_flux)", fn);
+    if ((c.dz_wT != nullptr) != (c.T_out != nullptr))
         return fail("%s: dz_wT and T_out are one output group — both given (the forcing and the adjustment step) or both NULL (no step); one of 2 given", fn);
-    if (!dz_wT && !wT_faces) return fail("%s: nothing to compute — give the step group (dz_wT, T_out), wT_faces, or both", fn);
-    if (n_columns < 1 || !(Lz > 0.0f)) return fail("%s: n_columns >= 1 and Lz > 0 required", fn);
-    if (dz_wT && !(dt > 0.0f)) return fail("%s: dt > 0 required when a step is asked for (dz_wT, T_out given); dt = %g", fn, dt);
-    if (!(K >= 0.0f)) return fail("%s: K_ca >= 0 required; K_ca = %g", fn, K);
-    if (!host) {
-        const void* const ptrs[4] = {T, dz_wT, T_out, wT_faces};
-        for (const void* p : ptrs)
-            if ((uintptr_t)p & 15) return fail("%s: the base pointers of T, dz_wT, T_out and wT_faces must be 16-byte aligned", fn);
-    }
+    if (!c.dz_wT && !c.wT_faces) return fail("%s: nothing to compute — give the step group (dz_wT, T_out), wT_faces, or both", fn);
+    if (c.n_col < 1 || !(c.Lz > 0.0f)) return fail("%s: n_columns >= 1 and Lz > 0 required", fn);
+    if (c.dz_wT && !(c.dt > 0.0f)) return fail("%s: dt > 0 required when a step is asked for (dz_wT, T_out given); dt = %g", fn, c.dt);
+    if (!(c.K >= 0.0f)) return fail("%s: K_ca >= 0 required; K_ca = %g", fn, c.K);
+    if (!host && (((uintptr_t)c.T | (uintptr_t)c.dz_wT | (uintptr_t)c.T_out | (uintptr_t)c.wT_faces) & 15))
+        return fail("%s: the base pointers of T, dz_wT, T_out and wT_faces must be 16-byte aligned", fn);
     return 0;
 }
 
@@ -765,7 +791,8 @@ static int fce_ens_pack(colnde_handle* h, const char* fn, const float* d_weights
 extern "C" int colnde_ensemble_fc_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_T, const float* d_top_flux, const float* d_halo_bottom,
                                                const float* d_halo_top, float Lz, float dt, float K_ca, float* d_dz_wT, float* d_T_out, float* d_wT_faces,
                                                int n_columns) {
-    if (fce_ens_check(h, __func__, d_T, d_top_flux, Lz, dt, K_ca, d_dz_wT, d_T_out, d_wT_faces, n_columns, false)) return 1;
+    FcEmbedArgs a = fce_call(d_T, d_top_flux, d_halo_bottom, d_halo_top, Lz, dt, K_ca, d_dz_wT, d_T_out, d_wT_faces, n_columns);
+    if (fce_ens_check(h, __func__, a, false)) return 1;
     if (!d_weights && !h->fce_ens_packed)
         return fail("%s: weights == NULL reuses the operand images of the previous call on this handle, and no call has given weights yet", __func__);
     HIPCHK(hipSetDevice(h->device));
@@ -773,34 +800,20 @@ extern "C" int colnde_ensemble_fc_embedded_dev(colnde_handle* h, const float* d_
     // One launch at every size, 16-column tiles (profiles/fc_ens_embed_rate.json).  The pack runs outside the timed scope, as in
     // colnde_fc_embedded_step: slot 9 is the embedded kernel's alone.
     if (d_weights && fce_ens_pack(h, __func__, d_weights)) return 1;
-    FcEmbedArgs a = {};
     a.cw = 16;
-    a.imgf = h->d_fce_ens_imgf; a.bias = h->d_fce_ens_bias; a.T = d_T; a.top_flux = d_top_flux; a.halo_bottom = d_halo_bottom; a.halo_top = d_halo_top;
-    a.Lz = Lz; a.dt = dt; a.K = K_ca; a.dz_wT = d_dz_wT; a.T_out = d_T_out; a.wT_faces = d_wT_faces; a.n_col = n_columns; a.step = d_dz_wT != nullptr;
+    a.imgf = h->d_fce_ens_imgf; a.bias = h->d_fce_ens_bias;
     Timed tm(h, K_FCEMBED);
     hipError_t e = launch_fc_embed_ens(h->m, a, h->n_models, h->conv.c, h->d_fce_ens_taps, h->stream);
     if (e != hipSuccess) return fail("%s launch failed: %s", __func__, hipGetErrorString(e));
     return 0;
 }
 
-// host arrays: the step in place on the T block it uploaded; top_flux [n] is shared by the members, the halos are [K][n]
+// host arrays (fce_host: the K members' blocks)
 extern "C" int colnde_ensemble_fc_embedded(colnde_handle* h, const float* weights, const float* T, const float* top_flux, const float* halo_bottom,
                                            const float* halo_top, float Lz, float dt, float K_ca, float* dz_wT, float* T_out, float* wT_faces, int n_columns) {
-    if (fce_ens_check(h, __func__, T, top_flux, Lz, dt, K_ca, dz_wT, T_out, wT_faces, n_columns, true)) return 1;
+    const FcEmbedArgs c = fce_call(T, top_flux, halo_bottom, halo_top, Lz, dt, K_ca, dz_wT, T_out, wT_faces, n_columns);
+    if (fce_ens_check(h, __func__, c, true)) return 1;
     if (!weights && !h->fce_ens_packed)
         return fail("%s: weights == NULL reuses the operand images of the previous call on this handle, and no call has given weights yet", __func__);
-    HIPCHK(hipSetDevice(h->device));
-    const size_t K = (size_t)h->n_models, Nz = (size_t)h->m.Nz, nc = (size_t)n_columns;
-    float *d_T, *d_To, *d_dz, *d_faces, *d_top, *d_hb, *d_ht;
-    HostStage st(h, __func__);
-    if (weights) st.to(h->d_w, weights, K * (size_t)user_params(h));
-    st.inout(&d_T, &d_To, T, T_out, K * nc * Nz);
-    st.out(&d_dz, dz_wT, K * nc * Nz);
-    st.out(&d_faces, wT_faces, K * nc * (Nz + 1));
-    st.in(&d_top, top_flux, nc);
-    st.in(&d_hb, halo_bottom, K * nc);
-    st.in(&d_ht, halo_top, K * nc);
-    if (st.upload()) return 1;
-    if (colnde_ensemble_fc_embedded_dev(h, weights ? h->d_w : nullptr, d_T, d_top, d_hb, d_ht, Lz, dt, K_ca, d_dz, d_To, d_faces, n_columns)) return 1;
-    return st.download();
+    return fce_host(h, __func__, weights, c, true);
 }

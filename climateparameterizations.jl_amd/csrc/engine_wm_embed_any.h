@@ -54,7 +54,7 @@ inline bool wm_any_fits(const WmAnyPlan& p) { return p.bytes <= (size_t)WMA_LDS_
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
-#include "mpp_sweep.h"
+#include "engine_wm_infer.h"             // WmEmbedIO
 
 struct WmAnyNet {                         // one net's layout inside the flat Flux.destructure vector; the three nets lie net_size apart
     int n_layers, net_size;
@@ -62,20 +62,11 @@ struct WmAnyNet {                         // one net's layout inside the flat Fl
 };
 
 struct WmAnyArgs {
+    WmEmbedIO io;                         // the d/dz arrays are always written
     WmAnyNet net;
     const float* weights;                 // [3 net_size] uw; vw; wT — read in place, no packed image
     float mu[6], sigma[6];                // scalings u, v, T, uw, vw, wT
-    const float *u, *v, *T;               // [n_col][32], k = 0 deepest
-    const float* top_flux;                // [3][n_col]
-    const float *halo_bottom, *halo_top;  // [3][n_col] or null
-    float Lz;
     MppParams mpp;                        // fused or diag
-    float *dz_uw, *dz_vw, *dz_wT;         // [n_col][32], always written
-    bool fused;
-    float *u_out, *v_out, *T_out;         // fused: each may alias its own input
-    bool diag;
-    float *uw, *vw, *wT;                  // diag: [n_col][33]
-    int n_col;
 };
 
 // every pointer of the state and the outputs must be 16-byte aligned and the plan must fit (hipErrorInvalidValue otherwise)

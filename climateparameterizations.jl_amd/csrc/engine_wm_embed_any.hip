@@ -223,13 +223,11 @@ wm_embed_any_kernel(WmAnyNet N, WmAnyPlan L, const float* __restrict__ w, WmAnyS
 }
 
 hipError_t launch_wm_embed_any(const WmAnyArgs& a, hipStream_t stream) {
-    if (a.n_col < 1 || !(a.Lz > 0.0f)) return hipErrorInvalidValue;
+    const WmEmbedIO& io = a.io;
+    if (io.n_col < 1 || !(io.Lz > 0.0f)) return hipErrorInvalidValue;
     const WmAnyNet& N = a.net;
     if (N.n_layers < 1 || N.n_layers > WMA_MAX_LAYERS || N.sizes[0] != 3 * WMA_NZ || N.sizes[N.n_layers] != WMA_NZ - 1) return hipErrorInvalidValue;
-    uintptr_t al = (uintptr_t)a.u | (uintptr_t)a.v | (uintptr_t)a.T | (uintptr_t)a.dz_uw | (uintptr_t)a.dz_vw | (uintptr_t)a.dz_wT;
-    if (a.fused) al |= (uintptr_t)a.u_out | (uintptr_t)a.v_out | (uintptr_t)a.T_out;
-    if (a.diag) al |= (uintptr_t)a.uw | (uintptr_t)a.vw | (uintptr_t)a.wT;
-    if (al & 15) return hipErrorInvalidValue;
+    if (!wm_io_aligned(io, true)) return hipErrorInvalidValue;
     const WmAnyPlan L = wm_any_plan(N.n_layers, N.sizes);
     if (!wm_any_fits(L)) return hipErrorInvalidValue;
     WmAnyScal S;
@@ -239,17 +237,17 @@ hipError_t launch_wm_embed_any(const WmAnyArgs& a, hipStream_t stream) {
         S.fmu[f] = a.mu[3 + f];
         S.fsig[f] = a.sigma[3 + f];
     }
-    S.inv_dz = (float)WMA_NZ / a.Lz;
-    S.dz = a.Lz / (float)WMA_NZ;
-    const int n_tiles = (a.n_col + WMA_CT - 1) / WMA_CT;
+    S.inv_dz = (float)WMA_NZ / io.Lz;
+    S.dz = io.Lz / (float)WMA_NZ;
+    const int n_tiles = (io.n_col + WMA_CT - 1) / WMA_CT;
     hipError_t e = hipSuccess;
     with_bools([&](auto FUSED, auto DIAG) {
         auto* k = wm_embed_any_kernel<FUSED(), DIAG()>;
         e = set_max_lds(k, L.bytes);
         if (e != hipSuccess) return;
-        hipLaunchKernelGGL(k, dim3(n_tiles), dim3(64 * WMA_WAVES), L.bytes, stream, N, L, a.weights, S, a.u, a.v, a.T, a.top_flux, a.halo_bottom, a.halo_top,
-                           a.mpp, a.dz_uw, a.dz_vw, a.dz_wT, a.u_out, a.v_out, a.T_out, a.uw, a.vw, a.wT, a.n_col);
+        hipLaunchKernelGGL(k, dim3(n_tiles), dim3(64 * WMA_WAVES), L.bytes, stream, N, L, a.weights, S, io.u, io.v, io.T, io.top_flux, io.halo_bottom, io.halo_top,
+                           a.mpp, io.dz_uw, io.dz_vw, io.dz_wT, io.u_out, io.v_out, io.T_out, io.uw, io.vw, io.wT, io.n_col);
         e = hipGetLastError();
-    }, a.fused, a.diag);
+    }, io.fused(), io.diag());
     return e;
 }

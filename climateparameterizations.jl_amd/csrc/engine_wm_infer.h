@@ -3,6 +3,7 @@
 // with the diagnosis of the total face fluxes diagnose_NN_flux_uw / _vw / _wT (:226-286).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include "mpp_sweep.h"
 
 // the one shape the kernels are built for: Nz = 32, three 96-50-20-31 networks (regtile's shape)
@@ -11,25 +12,36 @@
 #define WM_H2 20
 #define WM_NET (96 * WM_H1 + WM_H1 + WM_H1 * WM_H2 + WM_H2 + WM_H2 * 31 + 31)   // 6521 parameters per net, Flux.destructure order
 
+// What one call of the embedding reads and writes, whichever kernel serves it (host only: the kernels take the members one by one).  The optional
+// groups decide what is computed: u_out, v_out, T_out the fused diffusion step of the state as given (each may alias its own input), uw, vw, wT the
+// diagnosis of the total face fluxes.  An ensemble's arrays carry a leading [K], top_flux excepted.
+struct WmEmbedIO {
+    const float *u, *v, *T;               // [n_col][32], physical units, k = 0 deepest
+    const float* top_flux;                // [3][n_col]
+    const float *halo_bottom, *halo_top;  // [3][n_col] or null; the step reads halo_bottom alone
+    float Lz;
+    float *dz_uw, *dz_vw, *dz_wT;         // [n_col][32]; the diagnosis without the step writes none (unused)
+    float *u_out, *v_out, *T_out;         // [n_col][32]
+    float *uw, *vw, *wT;                  // [n_col][33]
+    int n_col;
+    bool fused() const { return u_out != nullptr; }
+    bool diag() const { return uw != nullptr; }
+};
+// the 16-byte rule of the state and the outputs a launch touches (an ensemble: of the base pointers); dz: the d/dz arrays are among them
+inline bool wm_io_aligned(const WmEmbedIO& io, bool dz) {
+    uintptr_t al = (uintptr_t)io.u | (uintptr_t)io.v | (uintptr_t)io.T;
+    if (dz) al |= (uintptr_t)io.dz_uw | (uintptr_t)io.dz_vw | (uintptr_t)io.dz_wT;
+    if (io.fused()) al |= (uintptr_t)io.u_out | (uintptr_t)io.v_out | (uintptr_t)io.T_out;
+    if (io.diag()) al |= (uintptr_t)io.uw | (uintptr_t)io.vw | (uintptr_t)io.wT;
+    return !(al & 15);
+}
+
 struct WmInferArgs {
+    WmEmbedIO io;
     const float* weights;                 // [3 WM_NET] uw; vw; wT
     float mu[6], sigma[6];                // scalings u, v, T, uw, vw, wT
     int act1, act2;                       // COLNDE_ACT_* of the two hidden layers (identity on the output)
-    const float *u, *v, *T;               // [n_col][32], physical units, k = 0 deepest
-    const float* top_flux;                // [3][n_col]
-    float Lz;
-    float *dz_uw, *dz_vw, *dz_wT;         // [n_col][32]
-    int n_col;
-    // fused step only (fused = true): the diffusion step of the state as given; outputs may alias their own inputs
-    bool fused;
-    const float* halo_bottom;             // [3][n_col] or null
-    MppParams mpp;
-    float *u_out, *v_out, *T_out;
-    // flux diagnosis (diag = true): uw, vw, wT [n_col][33] of the state as given; mpp (its step is not used unless fused) and halo_bottom as
-    // above, halo_top [3][n_col] or null.  diag without fused writes no d/dz arrays (dz_* unused).
-    bool diag;
-    const float* halo_top;
-    float *uw, *vw, *wT;
+    MppParams mpp;                        // fused or diag (its step is not used unless fused)
 };
 
 // every pointer of the state and the outputs must be 16-byte aligned (hipErrorInvalidValue otherwise)
@@ -53,22 +65,13 @@ inline int wm_ens_grid(int n_models, int n_col, int n_cu, int grid_cap) {
 }
 
 struct WmEnsArgs {
+    WmEmbedIO io;                         // the d/dz arrays are always written
     int n_models;
     const float* weights;                 // [K][w_stride]: model k's [3 WM_NET] first in its row
     size_t w_stride;
     float mu[6], sigma[6];
     int act1, act2;
-    const float *u, *v, *T;               // [K][n_col][32]
-    const float* top_flux;                // [3][n_col], shared by the models
-    const float *halo_bottom, *halo_top;  // [K][3][n_col] or null
-    float Lz;
     const MppParams* mpp;                 // DEVICE array [K]
-    float *dz_uw, *dz_vw, *dz_wT;         // [K][n_col][32], always written
-    bool fused;
-    float *u_out, *v_out, *T_out;         // fused: [K][n_col][32], each may alias its own input
-    bool diag;
-    float *uw, *vw, *wT;                  // diag: [K][n_col][33] (a model's rows need no alignment of their own: only the base pointers do)
-    int n_col;
     int grid_cap;                         // > 0: at most this many workgroups
 };
 

@@ -162,19 +162,9 @@ wm_infer_ens_kernel(const float* __restrict__ w_all, size_t w_stride, WmScal S, 
     }
 }
 
-hipError_t launch_wm_infer(const WmInferArgs& a, hipStream_t stream) {
-    if (a.n_col < 1 || !(a.Lz > 0.0f)) return hipErrorInvalidValue;
-    const bool dz_out = a.fused || !a.diag;
-    uintptr_t al = (uintptr_t)a.u | (uintptr_t)a.v | (uintptr_t)a.T;
-    if (dz_out) al |= (uintptr_t)a.dz_uw | (uintptr_t)a.dz_vw | (uintptr_t)a.dz_wT;
-    if (a.fused) al |= (uintptr_t)a.u_out | (uintptr_t)a.v_out | (uintptr_t)a.T_out;
-    if (a.diag) al |= (uintptr_t)a.uw | (uintptr_t)a.vw | (uintptr_t)a.wT;
-    if (al & 15) return hipErrorInvalidValue;
-    int dev = 0, n_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
+// the scalings as the kernels take them (Args: WmInferArgs, WmEnsArgs)
+template <class Args>
+static WmScal wm_scal(const Args& a) {
     WmScal S;
     for (int f = 0; f < 3; f++) {
         S.mu[f] = a.mu[f];
@@ -182,11 +172,27 @@ hipError_t launch_wm_infer(const WmInferArgs& a, hipStream_t stream) {
         S.fmu[f] = a.mu[3 + f];
         S.fsig[f] = a.sigma[3 + f];
     }
-    S.inv_dz = (float)WM_NZ / a.Lz;
-    S.dz = a.Lz / (float)WM_NZ;
+    S.inv_dz = (float)WM_NZ / a.io.Lz;
+    S.dz = a.io.Lz / (float)WM_NZ;
     S.act1 = a.act1;
     S.act2 = a.act2;
-    const int n_tiles = (a.n_col + 31) / 32, n_groups = (n_tiles + WM_WAVES - 1) / WM_WAVES;
+    return S;
+}
+static hipError_t wm_cu_count(int* n_cu) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    return e != hipSuccess ? e : hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+}
+
+hipError_t launch_wm_infer(const WmInferArgs& a, hipStream_t stream) {
+    const WmEmbedIO& io = a.io;
+    if (io.n_col < 1 || !(io.Lz > 0.0f)) return hipErrorInvalidValue;
+    if (!wm_io_aligned(io, io.fused() || !io.diag())) return hipErrorInvalidValue;       // (the diagnosis alone writes no d/dz arrays)
+    int n_cu = 0;
+    hipError_t e = wm_cu_count(&n_cu);
+    if (e != hipSuccess) return e;
+    const WmScal S = wm_scal(a);
+    const int n_tiles = (io.n_col + 31) / 32, n_groups = (n_tiles + WM_WAVES - 1) / WM_WAVES;
     with_bools([&](auto FUSED, auto DIAG) {
         auto* k = wm_infer_kernel<FUSED(), DIAG()>;
         const size_t lds = (WM_W_LDS + (FUSED() || DIAG() ? WM_WAVES * 3 * WM_FS : 0)) * sizeof(float);
@@ -195,45 +201,31 @@ hipError_t launch_wm_infer(const WmInferArgs& a, hipStream_t stream) {
         // persistent: one workgroup per CU, one wave per SIMD with the whole register file (five stacked accumulator tiles, the input, the
         // prefetched next tile: two waves per SIMD spill)
         const int resident = std::max(1, n_cu);
-        hipLaunchKernelGGL(k, dim3(std::min(n_groups, resident)), dim3(64 * WM_WAVES), lds, stream, a.weights, S, a.u, a.v, a.T, a.top_flux,
-                           a.halo_bottom, a.halo_top, a.mpp, a.dz_uw, a.dz_vw, a.dz_wT, a.u_out, a.v_out, a.T_out, a.uw, a.vw, a.wT, a.n_col, n_groups);
+        hipLaunchKernelGGL(k, dim3(std::min(n_groups, resident)), dim3(64 * WM_WAVES), lds, stream, a.weights, S, io.u, io.v, io.T, io.top_flux,
+                           io.halo_bottom, io.halo_top, a.mpp, io.dz_uw, io.dz_vw, io.dz_wT, io.u_out, io.v_out, io.T_out, io.uw, io.vw, io.wT, io.n_col, n_groups);
         e = hipGetLastError();
-    }, a.fused, a.diag);
+    }, io.fused(), io.diag());
     return e;
 }
 
 hipError_t launch_wm_infer_ens(const WmEnsArgs& a, hipStream_t stream) {
-    if (a.n_models < 1 || a.n_col < 1 || !(a.Lz > 0.0f) || !a.mpp) return hipErrorInvalidValue;
-    uintptr_t al = (uintptr_t)a.u | (uintptr_t)a.v | (uintptr_t)a.T | (uintptr_t)a.dz_uw | (uintptr_t)a.dz_vw | (uintptr_t)a.dz_wT;
-    if (a.fused) al |= (uintptr_t)a.u_out | (uintptr_t)a.v_out | (uintptr_t)a.T_out;
-    if (a.diag) al |= (uintptr_t)a.uw | (uintptr_t)a.vw | (uintptr_t)a.wT;
-    if (al & 15) return hipErrorInvalidValue;
-    int dev = 0, n_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const WmEmbedIO& io = a.io;
+    if (a.n_models < 1 || io.n_col < 1 || !(io.Lz > 0.0f) || !a.mpp) return hipErrorInvalidValue;
+    if (!wm_io_aligned(io, true)) return hipErrorInvalidValue;
+    int n_cu = 0;
+    hipError_t e = wm_cu_count(&n_cu);
     if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    WmScal S;
-    for (int f = 0; f < 3; f++) {
-        S.mu[f] = a.mu[f];
-        S.inv_sig[f] = 1.0f / a.sigma[f];
-        S.fmu[f] = a.mu[3 + f];
-        S.fsig[f] = a.sigma[3 + f];
-    }
-    S.inv_dz = (float)WM_NZ / a.Lz;
-    S.dz = a.Lz / (float)WM_NZ;
-    S.act1 = a.act1;
-    S.act2 = a.act2;
-    const int n_groups = wm_ens_groups(a.n_col), grid = wm_ens_grid(a.n_models, a.n_col, std::max(1, n_cu), a.grid_cap);
+    const WmScal S = wm_scal(a);
+    const int n_groups = wm_ens_groups(io.n_col), grid = wm_ens_grid(a.n_models, io.n_col, std::max(1, n_cu), a.grid_cap);
     with_bools([&](auto FUSED, auto DIAG) {
         auto* k = wm_infer_ens_kernel<FUSED(), DIAG()>;
         const size_t lds = (WM_W_LDS + (FUSED() || DIAG() ? WM_WAVES * 3 * WM_FS : 0)) * sizeof(float);
         e = set_max_lds(k, lds);
         if (e != hipSuccess) return;
         // persistent, one workgroup per CU as wm_infer_kernel (one wave per SIMD with the whole register file)
-        hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WM_WAVES), lds, stream, a.weights, a.w_stride, S, a.u, a.v, a.T, a.top_flux, a.halo_bottom, a.halo_top,
-                           a.mpp, a.dz_uw, a.dz_vw, a.dz_wT, a.u_out, a.v_out, a.T_out, a.uw, a.vw, a.wT, a.n_col, n_groups, a.n_models);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WM_WAVES), lds, stream, a.weights, a.w_stride, S, io.u, io.v, io.T, io.top_flux, io.halo_bottom, io.halo_top,
+                           a.mpp, io.dz_uw, io.dz_vw, io.dz_wT, io.u_out, io.v_out, io.T_out, io.uw, io.vw, io.wT, io.n_col, n_groups, a.n_models);
         e = hipGetLastError();
-    }, a.fused, a.diag);
+    }, io.fused(), io.diag());
     return e;
 }
