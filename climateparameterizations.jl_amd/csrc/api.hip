@@ -539,7 +539,7 @@ extern "C" void colnde_destroy(colnde_handle* h) {
 int user_params(const colnde_handle* h) { return h->conv.c ? h->conv.n_params : h->m.n_params; }
 extern "C" int colnde_n_params(const colnde_handle* h) { return h ? user_params(h) : -1; }
 extern "C" int colnde_conv_filter(const colnde_handle* h) { return h ? h->conv.c : -1; }
-extern "C" int colnde_engine(const colnde_handle* h) { return h ? (h->use_rt ? COLNDE_ENGINE_MFMA : (h->use_fc ? COLNDE_ENGINE_FC32 : COLNDE_ENGINE_GENERIC)) : -1; }
+extern "C" int colnde_engine(const colnde_handle* h) { return h ? engine_id(h) : -1; }
 
 extern "C" int colnde_set_stream(colnde_handle* h, void* s) {
     if (!h) return fail("null handle");
@@ -1060,7 +1060,7 @@ extern "C" int colnde_pretrain_flux_dev(colnde_handle* h, int flux_type, float* 
 extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
     if (!h || !info) return fail("null argument");
     for (int i = 0; i < 8; i++) info[i] = 0;
-    info[0] = h->use_rt ? COLNDE_ENGINE_MFMA : (h->use_fc ? COLNDE_ENGINE_FC32 : COLNDE_ENGINE_GENERIC);
+    info[0] = engine_id(h);
     // RKC2 on a model with a convective-adjustment switch: the gradient is the one-switch-pattern pullback (include/colnde.h)
     info[7] = (h->cfg.stepper == COLNDE_STEPPER_RKC2 && (h->m.model == COLNDE_MODEL_CONV_ADJ_NDE || (h->m.ca && !h->m.mpp))) ? 1 : 0;
     // bits 1..3: which kernel families run the exact three-way bf16 split (where the engine has a split kernel for this shape)
@@ -1079,20 +1079,19 @@ extern "C" int colnde_plan(const colnde_handle* h, int info[8]) {
         bf_dw = h->sp_dw && h->t16_dwtape == 1 && !h->dw.passes.empty();
     }
     info[7] |= (bf_fwd ? 2 : 0) | (bf_adj ? 4 : 0) | (bf_dw ? 8 : 0);
+    // the block of the handle's engine; tile16 reports it once the delta tape is in use
+    if (h->use_rt || h->use_fc || h->t16_dwtape == 1) {
+        info[1] = h->blk.block;
+        info[2] = h->blk.nblocks;
+    }
     if (h->use_fc) {
-        info[1] = h->fc_block;
-        info[2] = h->fc_nblocks;
         info[3] = h->fc_nseg > 1 ? h->fc_nseg : 0;       // fc32: time segments of the tapes (0: the tapes hold the whole axis)
         info[4] = h->d_dwtape ? 1 : 0;
         info[5] = h->d_dwtape ? h->dw.slices : 0;
         info[6] = h->conv.c;
     } else if (h->use_rt) {
-        info[1] = h->rt_block;
-        info[2] = h->rt_nblocks;
         info[3] = h->rt_ztape ? 1 : 0;
     } else {
-        info[1] = h->t16_dwtape == 1 ? h->t16_block : 0;
-        info[2] = h->t16_dwtape == 1 ? h->t16_nblocks : 0;
         info[4] = h->t16_dwtape == 1 ? 1 : 0;
         info[5] = h->t16_dwtape == 1 ? h->dw.slices : 0;
         info[6] = (h->fwd_split ? 1 : 0) | ((h->adj_split && h->t16_dwtape == 1 && h->d_t16_ztape) ? 2 : 0) | (h->split_rich ? 4 : 0);

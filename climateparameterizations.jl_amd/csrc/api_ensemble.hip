@@ -58,54 +58,43 @@ static int ens_upload_physics(colnde_handle* h, const float* physics) {
 }
 
 // The tapes of all K models, planned once at creation: tile16's taped-dW formats for ONE block of all columns per model (the net-split pair has no
-// column-block loop across models), the rich tape while the K models' 16-column tiles number at most 128 (2,048 columns in flight: the single
-// handle's crossover, which counts concurrent tiles whoever owns them).  Refused with the bytes it needs when it does not fit.
+// column-block loop across models), the rich tape by tape_plan.h's plan_t16_ens_tapes.  Refused with the bytes it needs when it does not fit.
 static int ens_plan_tapes(colnde_handle* h) {
     const DevModel& m = h->m;
     const int K = h->n_models;
-    const int n_steps = total_steps(h);
-    const size_t n_rec = sched_records((size_t)h->n_tiles, n_steps, m.nst);
+    const size_t n_rec = sched_records((size_t)h->n_tiles, total_steps(h), m.nst);
     const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
-    h->t16_nblocks = 1;
-    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order (and h->t16_rows)
+    h->blk.block = h->n_tiles * CT;
+    h->blk.nblocks = 1;
+    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order (and h->blk.rows, ens.slab)
     const size_t f_tape = n_rec * CT * m.ns, f_dw = n_rec * CT * R, f_rich = n_rec * rt_split_rich_record_floats(),
-                 f_plain = n_rec * CT * t16_ztape_col_floats(m), f_slab = (size_t)h->t16_rows * P8,
-                 f_sol = (size_t)h->n_col * h->cfg.n_save * m.ns, f_img = RT_IMG_STRIDE;
-    const char* er = env_get(ENV_T16_SPLIT_RICH);
-    const bool forced = er != nullptr;
-    bool rich = forced ? atoi(er) != 0 : (size_t)K * h->n_tiles <= 128;
+                 f_plain = n_rec * CT * t16_ztape_col_floats(m), f_sol = (size_t)h->n_col * h->cfg.n_save * m.ns, f_img = RT_IMG_STRIDE;
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     const size_t budget = hbm_budget(free_b, ((size_t)3 << 30) + (size_t)K * (P8 * 2 + 256 * 8) * sizeof(float));
-    auto per_model = [&](bool r) { return (f_tape + f_dw + (r ? f_rich : f_plain) + f_slab + f_sol + f_img) * sizeof(float); };
-    if (rich && !forced && (size_t)K * per_model(true) > budget) rich = false;       // the automatic rich tape gives way to the plain one, as for one handle
-    const size_t need = per_model(rich);
-    if ((size_t)K * need > budget)
+    auto per_model = [&](size_t f_z) { return (f_tape + f_dw + f_z + h->ens.slab + f_sol + f_img) * sizeof(float); };
+    const T16EnsTapes plan = plan_t16_ens_tapes(K, h->n_tiles, per_model(f_rich), per_model(f_plain), budget, env_flag(ENV_T16_SPLIT_RICH));
+    const size_t need = plan.bytes_per_model;
+    if (plan.refused)
         return fail("an ensemble of %d models needs %zu bytes of device memory for its tapes, slab rows and solutions (%zu per model, %s tape, "
                     "%d substeps x %d stages x %d save intervals); %zu bytes are free (3 GB kept in reserve): use fewer models per handle",
-                    K, (size_t)K * need, need, rich ? "rich" : "plain", h->cfg.substeps, m.nst, h->cfg.n_save - 1, free_b);
-    const size_t f_z = rich ? f_rich : f_plain;
+                    K, (size_t)K * need, need, plan.rich ? "rich" : "plain", h->cfg.substeps, m.nst, h->cfg.n_save - 1, free_b);
     const size_t mark = h->mem.mark();
-    hipError_t e = h->mem.alloc(&h->d_dwtape, (size_t)K * f_dw);
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_tape, (size_t)K * f_tape);
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_t16_ztape, (size_t)K * f_z);
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_slab, (size_t)K * f_slab);
-    if (e == hipSuccess) e = upload_dw_plan(h);
+    int at = 0;
+    hipError_t e = t16_alloc_tapes(h, (size_t)K, n_rec, &at);
+    if (e == hipSuccess) e = t16_alloc_ztape(h, (size_t)K, n_rec, plan.rich);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         h->mem.rollback(mark);
         return fail("allocating the ensemble's tapes (%zu bytes, %zu per model) failed: %s", (size_t)K * need, need, hipGetErrorString(e));
     }
     h->t16_dwtape = 1;
-    h->t16_block = h->n_tiles * CT;
-    h->t16_nblocks = 1;
-    h->split_rich = rich;
+    h->split_rich = plan.rich;
     h->ens.wimg = f_img;
     h->ens.sol = f_sol;
     h->ens.tape = f_tape;
-    h->ens.ztape = f_z;
+    h->ens.ztape = plan.rich ? f_rich : f_plain;
     h->ens.dwtape = f_dw;
-    h->ens.slab = f_slab;
     h->ens.n_models = K;
     h->ens.phys = h->d_phys;
     h->ens_model_bytes = need;
@@ -300,75 +289,6 @@ extern "C" int colnde_create_conv(const colnde_config* cfg, int conv_filter, col
     return 0;
 }
 
-// The tapes of all K models, planned once at creation by fc_plan_tapes' rules on a per-model budget of (free memory - margin) / K: one block of all columns
-// (column blocks do not occur at <= 4,096 columns), the whole time axis when it fits and time segments otherwise (COLNDE_FC_SEG=<intervals> forces), the
-// slice count a single handle of this size plans.  Refused with the bytes it needs when not even one save interval per segment fits.
-// A conv ensemble (h->conv.c): the conv tape rides in the bytes per column and interval, as in fc_plan_tapes; a model also owns its filter slab and its
-// padded weight vector and gradient row (tape_plan.h: fc_conv_ens_model_bytes).
-static int fc_ens_plan_tapes(colnde_handle* h) {
-    const DevModel& m = h->m;
-    const size_t K = (size_t)h->n_models;
-    const int n_iv = h->cfg.n_save - 1, cw = h->fc_cw;
-    const size_t R = dwtape_row_floats(m), P8 = (size_t)m.n_params + 8;
-    if (R != fc_record_row_floats(m.Nz)) return fail("fc32: record layout mismatch (%zu vs %zu floats per column)", R, fc_record_row_floats(m.Nz));
-    const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE;
-    const int conv = h->conv.c;
-    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0) +
-                                                                 (conv ? fc_conv_tape_floats(m.Nz) / 16 * sizeof(float) : 0));
-    const size_t cslab_seg = (size_t)FC_CONV_GRAD_MAX_SLICES * FC_CONV_GRAD_SLOTS;          // floats of filter slab per time segment
-    const int n32 = (h->n_col + 31) / 32 * 32;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const size_t budget = hbm_budget(free_b, (size_t)3 << 30) / K;
-    int seg = conv ? plan_fc_conv_ens_seg(n32, n_iv, cw, m.Nz, per_col_iv, budget, m.n_params, cslab_seg)
-                   : plan_fc_ens_seg(n32, n_iv, cw, m.Nz, per_col_iv, budget, m.n_params);
-    const char* es = env_get(ENV_FC_SEG);
-    if (es && atoi(es) >= 1) seg = std::min(n_iv, atoi(es));
-    const size_t need = conv ? fc_conv_ens_model_bytes(n32, n_iv, cw, m.Nz, per_col_iv, m.n_params, seg, cslab_seg)
-                             : fc_ens_model_bytes(n32, n_iv, cw, m.Nz, per_col_iv, m.n_params, seg);
-    if (need > budget)
-        return fail("a free-convection ensemble of %d models needs %zu bytes of device memory for its tapes and slab rows (%zu per model with %d save interval(s) per "
-                    "time segment, %d substeps x %d stages); %zu bytes are free (3 GB kept in reserve): use fewer models per handle",
-                    h->n_models, K * need, need, seg, h->cfg.substeps, m.nst, free_b);
-    h->fc_block = n32;
-    h->fc_nblocks = 1;
-    h->fc_seg = seg;
-    h->fc_nseg = (n_iv + seg - 1) / seg;
-    const size_t tiles_b = (size_t)n32 / cw;
-    const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;
-    const size_t n_rec = tiles_b * (cw / 16) * stage_recs;
-    build_dw_plan(h, n_rec);                                 // the slice count a single handle of this size plans: same reduction order (and h->fc_rows)
-    FcEns& en = h->fens;
-    en.dwtape = n_rec * CT * R;
-    en.masks = tiles_b * stage_recs * fc_mask_words();
-    en.swtape = ca ? tiles_b * stage_recs * fc_switch_words(cw) : 0;
-    en.lam = (size_t)n32 * m.Nz;
-    en.slab = (size_t)h->fc_rows * P8;
-    const size_t mark = h->mem.mark();
-    hipError_t e = h->mem.alloc(&h->d_dwtape, K * en.dwtape);
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_fc_masks, K * en.masks);
-    if (e == hipSuccess && ca) e = h->mem.alloc(&h->d_fc_switch, K * en.swtape);
-    if (e == hipSuccess && h->fc_nseg > 1) e = h->mem.alloc(&h->d_fc_lam, K * en.lam);
-    if (e == hipSuccess && conv) {                           // per model: the conv tape of the same records, and one single handle's filter slab
-        h->conv.cslab_rows = h->fc_nblocks * h->fc_nseg * FC_CONV_GRAD_MAX_SLICES;
-        h->conv.ctape_stride = n_rec * fc_conv_tape_floats(m.Nz);
-        h->conv.cslab_stride = (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS;
-        e = h->mem.alloc(&h->conv.d_ctape, K * h->conv.ctape_stride);
-        if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_cslab, K * h->conv.cslab_stride);
-    }
-    if (e == hipSuccess) e = upload_dw_plan(h);
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_slab, K * en.slab);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        h->mem.rollback(mark);
-        return fail("allocating the free-convection ensemble's tapes (%zu bytes, %zu per model) failed: %s", K * need, need, hipGetErrorString(e));
-    }
-    h->ens.slab = en.slab;
-    h->ens_model_bytes = (en.dwtape + en.slab + (h->fc_nseg > 1 ? en.lam : 0)) * sizeof(float) + en.masks * sizeof(unsigned int) + en.swtape * sizeof(unsigned long long);
-    if (conv) h->ens_model_bytes += (h->conv.ctape_stride + h->conv.cslab_stride + 2 * (size_t)m.n_params + 8) * sizeof(float);
-    return 0;
-}
-
 // conv_filter = 0: K plain networks (colnde_create_fc_ensemble); c = 2..8: K --conv networks of that filter length (colnde_create_conv_ensemble), whose
 // refusals are the union of the two creators', each in its own words
 static int create_fc_ensemble(const colnde_config* cfg, int conv_filter, int n_models, colnde_handle** out) {
@@ -411,7 +331,7 @@ static int create_fc_ensemble(const colnde_config* cfg, int conv_filter, int n_m
         colnde_destroy(h);
         return fail("allocating the free-convection ensemble's per-model buffers (%d models) failed", n_models);
     }
-    if (fc_ens_plan_tapes(h)) { colnde_destroy(h); return 1; }
+    if (fc_plan_tapes(h)) { colnde_destroy(h); return 1; }
     h->ens_model_bytes += (2 * en.img + en.bias + en.sol) * sizeof(float) + 2 * en.simg * sizeof(unsigned int);
     *out = h;
     return 0;
@@ -553,7 +473,7 @@ extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_we
     }
     {
         Timed tm(h, K_REDUCE);
-        e = launch_reduce(h->d_slab, h->t16_rows, h->m.n_params, stride, lw, d_out, h->stream, K, h->ens.slab, stride);
+        e = launch_reduce(h->d_slab, h->blk.rows, h->m.n_params, stride, lw, d_out, h->stream, K, h->ens.slab, stride);
         if (e != hipSuccess) return fail("ensemble reduce launch failed: %s", hipGetErrorString(e));
     }
     return 0;

@@ -1,44 +1,36 @@
-// api_grad.hip — loss and gradient of a single handle: the tape planners of the three engines and colnde_loss_grad[_dev].
+// api_grad.hip — loss and gradient of a single handle: the tape planners of the three engines (fc32's serves its ensembles too) and colnde_loss_grad[_dev].
 #include "api_internal.h"
 #include "tape_plan.h"
 #include "dw_plan.h"
 
 // Sizes the regtile engine's tapes.  They hold ONE block of columns; a problem whose tapes exceed the free HBM (many columns, or a
 // long horizon: 1,153 frames need 4x the bytes per column of the 2-day suite) runs its gradient path block after block into the same
-// buffers.  COLNDE_RT_BLOCK=<columns> forces a block size (testing aid).
+// buffers.  COLNDE_RT_BLOCK=<columns> forces a block size (testing aid).  The decision is tape_plan.h's plan_rt_tapes.
 static int rt_plan_tapes(colnde_handle* h) {
     if (h->d_rt_tape) return 0;
     const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
-    const char* ez = env_get(ENV_RT_ZTAPE);
-    bool want_z = !h->rt_fwd32 && !(ez && atoi(ez) == 0);
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const size_t budget = hbm_budget(free_b, (size_t)2 << 30);
     const size_t per_col_x = (size_t)n_steps * 4 * 96 * sizeof(float), per_col_2 = (size_t)n_steps * 4 * ((21 * 256) / 32) * sizeof(float);
     const size_t per_col_z = rt_tapez_floats(32, n_steps) / 32 * sizeof(float);      // (twice per_col_2 in the A/B build that tapes activation pairs)
     const int n32 = ((h->n_col + 31) / 32) * 32;
-    int block = 0;
-    for (int pass = 0; pass < 2 && block == 0; pass++) {
-        const size_t per_col = per_col_x + per_col_2 + (want_z ? per_col_z : 0);
-        block = plan_column_block(n32, budget / per_col, 1024, 1024);
-        if (block == 0) want_z = false;          // not even 1,024 columns with the Z1 tape: try without it
-    }
-    const char* eb = env_get(ENV_RT_BLOCK);
-    if (eb && atoi(eb) >= 32) block = std::min(n32, (atoi(eb) / 32) * 32);
+    const RtTapes plan = plan_rt_tapes(n32, per_col_x, per_col_2, per_col_z, hbm_budget(free_b, (size_t)2 << 30), !h->rt_fwd32 && env_flag(ENV_RT_ZTAPE) != FLAG_OFF,
+                                       env_int(ENV_RT_BLOCK, 0));
+    const int block = plan.block;
     if (block == 0) return fail("the stage tapes of even 1,024 columns (%zu bytes per column) do not fit in %zu free bytes of HBM",
                                 per_col_x + per_col_2, free_b);
     const size_t n1 = rt_tape_floats(block, n_steps), n2 = rt_tape2_floats(block, n_steps);
     const size_t mark = h->mem.mark();
     hipError_t e = h->mem.alloc(&h->d_rt_tape, n1);
     if (e == hipSuccess) e = h->mem.alloc(&h->d_rt_tape2, n2);
-    h->rt_ztape = want_z;                        // the Z1 tape is optional: dropped when its allocation fails
-    if (e == hipSuccess && want_z && h->mem.alloc(&h->d_rt_tapez, rt_tapez_floats(block, n_steps)) != hipSuccess) h->rt_ztape = false;
+    h->rt_ztape = plan.ztape;                    // the Z1 tape is optional: dropped when its allocation fails
+    if (e == hipSuccess && plan.ztape && h->mem.alloc(&h->d_rt_tapez, rt_tapez_floats(block, n_steps)) != hipSuccess) h->rt_ztape = false;
     if (e != hipSuccess) {
         h->mem.rollback(mark);                   // leave no half-built state behind
         return fail("hipMalloc of the %zu-byte stage tapes failed: %s", (n1 + n2) * sizeof(float), hipGetErrorString(e));
     }
-    h->rt_block = block;
-    h->rt_nblocks = (n32 + block - 1) / block;
+    h->blk.block = block;
+    h->blk.nblocks = (n32 + block - 1) / block;
     return 0;
 }
 
@@ -53,14 +45,9 @@ void build_dw_plan(colnde_handle* h, size_t n_rec) {
 // The slab rows that follow the plan's slice count: the adjoint's rows (one per tile, fc32: per tile and time segment), then the dW GEMM's (one per
 // block, fc32: and segment, and slice); an ensemble's models lie that many rows apart.  The planners size d_slab by it and the setter below re-sizes it.
 void dw_slab_rows(colnde_handle* h) {
-    const size_t P8 = (size_t)h->m.n_params + 8;
-    if (h->use_fc) {
-        h->fc_rows = ((h->n_col + 31) / 32 * 32 / h->fc_cw) * h->fc_nseg + h->fc_nblocks * h->fc_nseg * h->dw.slices;
-        if (h->ensemble) h->fens.slab = h->ens.slab = (size_t)h->fc_rows * P8;
-    } else {
-        h->t16_rows = h->n_tiles + h->t16_nblocks * h->dw.slices;
-        if (h->ensemble) h->ens.slab = (size_t)h->t16_rows * P8;
-    }
+    const int tiles = h->use_fc ? (h->n_col + 31) / 32 * 32 / h->fc_cw : h->n_tiles, nseg = h->use_fc ? h->fc_nseg : 1;
+    h->blk.rows = (tiles + h->blk.nblocks * h->dw.slices) * nseg;
+    h->fens.slab = h->ens.slab = (size_t)h->blk.rows * ((size_t)h->m.n_params + 8);      // (unused by a single handle: one model, no strides)
 }
 
 // colnde_set_matrix_arithmetic on a handle whose tapes are planned: the slice count was chosen for the arithmetic at plan time (dw_plan.h:
@@ -71,12 +58,12 @@ int replan_dw_slices(colnde_handle* h) {
     const int slices = dw_slice_count(h->dw, h->dw_n_rec, h->dw.lds_fit, h->sp_dw), old = h->dw.slices;
     if (slices == old) return 0;
     const size_t P8 = (size_t)h->m.n_params + 8, K = (size_t)h->n_models;
-    const size_t old_model = (size_t)(h->use_fc ? h->fc_rows : h->t16_rows) * P8;
+    const size_t old_model = (size_t)h->blk.rows * P8;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));             // (launches in flight write the slab about to be freed)
     h->dw.slices = slices;
     dw_slab_rows(h);
-    const size_t new_model = (size_t)(h->use_fc ? h->fc_rows : h->t16_rows) * P8;
+    const size_t new_model = (size_t)h->blk.rows * P8;
     const hipError_t e = h->mem.replace(&h->d_slab, K * new_model);      // the new slab first: a failure keeps the old one
     if (e != hipSuccess) {
         h->dw.slices = old;
@@ -115,157 +102,147 @@ hipError_t dw_launch(colnde_handle* h, size_t n_records, float* slab_rows, int K
 //     the adjoint over the segment (λ handed on through d_fc_lam) and the dW GEMM.  Costs (n_seg - 1)/n_seg of an extra forward solve, keeps every
 //     CU at two workgroups.
 // Blocks are used when they hold at least 16,384 columns (or everything), segments otherwise; COLNDE_FC_BLOCK=<columns> / COLNDE_FC_SEG=<intervals> force.
-static int fc_plan_tapes(colnde_handle* h) {
+// An ensemble (h->ensemble, K = h->n_models; planned once, at creation): one block of all columns per model on a budget of (free memory - margin) / K,
+// the whole time axis when it fits and time segments otherwise, the slice count a single handle of this size plans; refused with the bytes it needs
+// when not even one save interval per segment fits.  The decision is tape_plan.h's plan_fc_tapes; what follows it is the same for both: K models'
+// worth of every buffer, the models the FcEns / ConvBlock strides apart (a single handle's kernels get no strides).
+int fc_plan_tapes(colnde_handle* h) {
     if (h->d_dwtape) return 0;
     const DevModel& m = h->m;
-    const int n_iv = h->cfg.n_save - 1;
+    const size_t K = (size_t)h->n_models;
+    const int n_iv = h->cfg.n_save - 1, cw = h->fc_cw;
     const size_t R = dwtape_row_floats(m);
     if (R != fc_record_row_floats(m.Nz)) return fail("fc32: record layout mismatch (%zu vs %zu floats per column)", R, fc_record_row_floats(m.Nz));
     const bool ca = m.model == COLNDE_MODEL_CONV_ADJ_NDE;
-    // bytes of tape per column and save interval
-    const int cw = h->fc_cw;
-    const size_t per_col_iv = (size_t)h->cfg.substeps * m.nst * (R * sizeof(float) + fc_mask_words() * sizeof(unsigned int) / cw + (ca ? sizeof(unsigned long long) : 0) +
-                                                                 (h->conv.c ? fc_conv_tape_floats(m.Nz) / 16 * sizeof(float) : 0));      // (conv handles: the conv tape)
+    const int conv = h->conv.c;
+    const size_t per_col_iv = fc_tape_bytes_per_col_iv(h->cfg.substeps, m.nst, R, fc_mask_words(), cw, ca, conv ? fc_conv_tape_floats(m.Nz) : 0);
     const int n32 = (h->n_col + 31) / 32 * 32;
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const size_t margin = ((size_t)3 << 30) + (size_t)(n32 / cw * 8 + 4096) * (m.n_params + 8) * sizeof(float) + (size_t)n32 * m.Nz * sizeof(float);
-    const FcTapePlan plan = plan_fc_block_seg(n32, n_iv, cw, per_col_iv, hbm_budget(free_b, margin), m.n_params);
-    int block = plan.block, seg = plan.seg;
-    const char* eb = env_get(ENV_FC_BLOCK);
     const char* es = env_get(ENV_FC_SEG);
-    if (eb && atoi(eb) >= 32) { block = std::min(n32, (atoi(eb) / 32) * 32); if (!es) seg = n_iv; }
-    if (es && atoi(es) >= 1) seg = std::min(n_iv, atoi(es));
-    if (block < 32 || seg < 1) return fail("fc32: the tapes of even one 32-column tile and one save interval (%zu bytes) do not fit in the free device memory", 32 * per_col_iv);
-    h->fc_block = block;
-    h->fc_nblocks = (n32 + block - 1) / block;
+    const FcTapes plan = plan_fc_tapes({n32, n_iv, cw, m.Nz, m.n_params, per_col_iv, free_b, h->ensemble, h->n_models,
+                                        conv ? (size_t)FC_CONV_GRAD_MAX_SLICES * FC_CONV_GRAD_SLOTS : 0, env_int(ENV_FC_BLOCK, 0),
+                                        es ? (atoi(es) >= 1 ? atoi(es) : -1) : 0});
+    const int block = plan.block, seg = plan.seg;
+    if (plan.status == FC_PLAN_NOTHING_FITS)
+        return fail("fc32: the tapes of even one 32-column tile and one save interval (%zu bytes) do not fit in the free device memory", 32 * per_col_iv);
+    if (plan.status == FC_PLAN_ENSEMBLE_REFUSED)
+        return fail("a free-convection ensemble of %d models needs %zu bytes of device memory for its tapes and slab rows (%zu per model with %d save interval(s) per "
+                    "time segment, %d substeps x %d stages); %zu bytes are free (3 GB kept in reserve): use fewer models per handle",
+                    h->n_models, K * plan.model_bytes, plan.model_bytes, seg, h->cfg.substeps, m.nst, free_b);
+    h->blk.block = block;
+    h->blk.nblocks = (n32 + block - 1) / block;
     h->fc_seg = seg;
     h->fc_nseg = (n_iv + seg - 1) / seg;
     const size_t tiles_b = (size_t)block / cw;                                  // (block is a multiple of 32)
     const size_t stage_recs = (size_t)seg * h->cfg.substeps * m.nst;          // (tile, stage) records per tile held by the tapes
     const size_t n_rec = tiles_b * (cw / 16) * stage_recs;                     // records are tile16's: 16 columns each
-    build_dw_plan(h, n_rec);                                                    // (and h->fc_rows: dw_slab_rows)
-    const int stride = m.n_params + 8;
+    build_dw_plan(h, n_rec);                                                    // (and h->blk.rows, fens.slab: dw_slab_rows)
+    FcEns& en = h->fens;
+    en.dwtape = n_rec * CT * R;
+    en.masks = tiles_b * stage_recs * fc_mask_words();
+    en.swtape = ca ? tiles_b * stage_recs * fc_switch_words(cw) : 0;
+    en.lam = (size_t)n32 * m.Nz;
     const size_t mark = h->mem.mark();
-    hipError_t e = h->mem.alloc(&h->d_dwtape, n_rec * CT * R);
-    if (e == hipSuccess) e = h->mem.alloc(&h->d_fc_masks, tiles_b * stage_recs * fc_mask_words());
-    if (e == hipSuccess && ca) e = h->mem.alloc(&h->d_fc_switch, tiles_b * stage_recs * fc_switch_words(cw));
-    if (e == hipSuccess && h->fc_nseg > 1) e = h->mem.alloc(&h->d_fc_lam, (size_t)n32 * m.Nz);
-    if (e == hipSuccess && h->conv.c) {
-        h->conv.cslab_rows = h->fc_nblocks * h->fc_nseg * FC_CONV_GRAD_MAX_SLICES;
-        e = h->mem.alloc(&h->conv.d_ctape, n_rec * fc_conv_tape_floats(m.Nz));
-        if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_cslab, (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS);
+    hipError_t e = h->mem.alloc(&h->d_dwtape, K * en.dwtape);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_fc_masks, K * en.masks);
+    if (e == hipSuccess && ca) e = h->mem.alloc(&h->d_fc_switch, K * en.swtape);
+    if (e == hipSuccess && h->fc_nseg > 1) e = h->mem.alloc(&h->d_fc_lam, K * en.lam);
+    if (e == hipSuccess && conv) {                           // per model: the conv tape of the same records, and one single handle's filter slab
+        h->conv.cslab_rows = h->blk.nblocks * h->fc_nseg * FC_CONV_GRAD_MAX_SLICES;
+        h->conv.ctape_stride = n_rec * fc_conv_tape_floats(m.Nz);
+        h->conv.cslab_stride = (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS;
+        e = h->mem.alloc(&h->conv.d_ctape, K * h->conv.ctape_stride);
+        if (e == hipSuccess) e = h->mem.alloc(&h->conv.d_cslab, K * h->conv.cslab_stride);
     }
     if (e == hipSuccess) e = upload_dw_plan(h);
-    if (e == hipSuccess && !h->d_slab) e = h->mem.alloc(&h->d_slab, (size_t)h->fc_rows * stride);
+    if (e == hipSuccess && !h->d_slab) e = h->mem.alloc(&h->d_slab, K * en.slab);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         h->mem.rollback(mark);
+        if (h->ensemble)
+            return fail("allocating the free-convection ensemble's tapes (%zu bytes, %zu per model) failed: %s", K * plan.model_bytes, plan.model_bytes, hipGetErrorString(e));
         return fail("fc32: hipMalloc of the tapes (%zu bytes for %d columns x %d save intervals) failed: %s", (size_t)block * per_col_iv * seg, block, seg,
                     hipGetErrorString(e));
     }
+    h->ens_model_bytes = (en.dwtape + en.slab + (h->fc_nseg > 1 ? en.lam : 0)) * sizeof(float) + en.masks * sizeof(unsigned int) + en.swtape * sizeof(unsigned long long);
+    if (conv) h->ens_model_bytes += (h->conv.ctape_stride + h->conv.cslab_stride + 2 * (size_t)m.n_params + 8) * sizeof(float);
     return 0;
 }
 
-// tile16, taped weight gradients: decide once per handle.  On when the tapes fit in the free HBM (the in-register adjoint_kernel
-// geometries remain the fallback; 64-256-256-63's 384 gradient tiles spill there);
-// COLNDE_T16_DWTAPE=1 / 0 forces it on / off.
+// The buffers of tile16's taped mode, K models' worth (n_rec records per model), inside the caller's mark / rollback bracket: the delta tape, the dW
+// plan and the slab, then (*at = 1) the stage tape ...
+hipError_t t16_alloc_tapes(colnde_handle* h, size_t K, size_t n_rec, int* at) {
+    const DevModel& m = h->m;
+    *at = 0;
+    hipError_t e = h->mem.alloc(&h->d_dwtape, K * n_rec * CT * dwtape_row_floats(m));
+    if (e == hipSuccess) e = upload_dw_plan(h);
+    if (e == hipSuccess && !h->d_slab) e = h->mem.alloc(&h->d_slab, K * (size_t)h->blk.rows * (m.n_params + 8));
+    if (e != hipSuccess) return e;
+    *at = 1;
+    return h->d_tape ? hipSuccess : h->mem.alloc(&h->d_tape, K * n_rec * CT * m.ns);
+}
+// ... and the net-split pair's rich tape, or the hidden pre-activations the forward kernel tapes for the adjoint
+hipError_t t16_alloc_ztape(colnde_handle* h, size_t K, size_t n_rec, bool rich) {
+    return h->mem.alloc(&h->d_t16_ztape, K * n_rec * (rich ? rt_split_rich_record_floats() : CT * t16_ztape_col_floats(h->m)));
+}
+
+// tile16, taped weight gradients: decide once per handle (tape_plan.h: plan_t16_tapes).  On when the tapes fit in the free HBM (the in-register
+// adjoint_kernel geometries remain the fallback; 64-256-256-63's 384 gradient tiles spill there) — with the hidden pre-activations taped too, the
+// 1,024-thread accumulator-free adjoint beats the in-register kernels at every size measured (8 columns: 53 vs 64 ms per iteration; 32-128-128-31: 162
+// vs 198 ms).  COLNDE_T16_DWTAPE=1 / 0 forces it on / off, COLNDE_T16_BLOCK=<columns> a block size, COLNDE_T16_ZTAPE=0 disables the pre-activation tape.
 static int t16_plan_dwtape(colnde_handle* h) {
     if (h->t16_dwtape >= 0) return 0;
     const DevModel& m = h->m;
-    const char* ev = env_get(ENV_T16_DWTAPE);
-    // default: on whenever the tapes fit — with the hidden pre-activations taped too, the 1,024-thread accumulator-free adjoint beats
-    // the in-register kernels at every size measured (8 columns: 53 vs 64 ms per iteration; 32-128-128-31: 162 vs 198 ms)
-    bool want = ev ? atoi(ev) != 0 : true;
-    const int n_steps = total_steps(h);
+    const int n_steps = total_steps(h), n16 = h->n_tiles * CT, ztape = env_flag(ENV_T16_ZTAPE);
     const size_t R = dwtape_row_floats(m);
-    if (want && (size_t)CT * m.ns > 6 * 512) want = false;
-    // LDS of the taped adjoint: with the Z tape (the default) it holds no activation array; a network that fits only that way (3 x 96-400-31: 166 KB with
-    // the array, 83 KB without) then NEEDS the Z tape
-    bool need_z = false;
-    if (want && !h->ag_rows && (MODEL_FLOATS + lds_floats_adjoint(m)) * sizeof(float) > 160 * 1024) {
-        const char* ez = env_get(ENV_T16_ZTAPE);
-        if (!(ez && atoi(ez) == 0) && (MODEL_FLOATS + lds_floats_adjoint_noA(m)) * sizeof(float) <= 160 * 1024 && m.n_bias <= 4 * 512) need_z = true;
-        else want = false;
-    }
-    if (h->ag_rows) {       // rows in global memory: the taped adjoint with the Z tape is the ONLY gradient path (1,024 threads: n_bias <= 4 x 1,024, CT ns <= 2 x 1,024)
-        if (!want) return fail("COLNDE_T16_DWTAPE=0: this network's activation rows live in global memory, and only the taped-dW adjoint runs that way");
-        if (m.n_bias > 4 * 1024 || (MODEL_FLOATS + lds_floats_adjoint_ag(m)) * sizeof(float) > 160 * 1024)
-            return fail("network too large for the taped adjoint with rows in global memory (%d biases, %zu B of LDS)", m.n_bias, (MODEL_FLOATS + lds_floats_adjoint_ag(m)) * sizeof(float));
-    }
-    // The tapes hold ONE block of columns (a multiple of the 16-column tile; whole rounds of 4,096 columns = one workgroup per CU when
-    // possible); larger problems run forward -> adjoint -> dW GEMM block after block.  COLNDE_T16_BLOCK=<columns> forces a size.
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t margin = ((size_t)3 << 30) + (size_t)h->n_tiles * (m.n_params + 8) * sizeof(float);
+    // (the rich tape is 4x the pre-activation tape per column — 13,824 floats per 16-column record against 216 per column: part of the fit estimate)
     const size_t per_col = (size_t)n_steps * m.nst * (R + t16_ztape_col_floats(m) + m.ns) * sizeof(float);
-    const int n16 = h->n_tiles * CT;
-    int block = 0;
-    // the net-split pair's rich tape replaces the pre-activation tape on small blocks and is 4x its size per column (13,824 floats per
-    // 16-column record against 216 per column): it is part of the fit estimate, not an afterthought behind the 3 GB margin
-    const char* ezt0 = env_get(ENV_T16_ZTAPE);
-    const char* er0 = env_get(ENV_T16_SPLIT_RICH);
-    const bool rich_possible = h->adj_split && !(ezt0 && atoi(ezt0) == 0) && !(er0 && atoi(er0) == 0);
     const size_t per_col_rich = (size_t)n_steps * m.nst * (R + rt_split_rich_record_floats() / CT + m.ns) * sizeof(float);
-    bool want_rich = false;
-    if (want) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t margin = ((size_t)3 << 30) + (size_t)h->n_tiles * (m.n_params + 8) * sizeof(float);
-        const size_t budget = hbm_budget(free_b, margin);
-        block = plan_column_block(n16, budget / per_col, CT, 4096);
-        const char* eb = env_get(ENV_T16_BLOCK);
-        if (eb && atoi(eb) >= CT) block = std::min(n16, (atoi(eb) / CT) * CT);
-        if (block <= 0) want = false;
-        // rich tape: by default on blocks of at most 2,048 columns; forced on by COLNDE_T16_SPLIT_RICH=1.  It must fit WITH the other tapes:
-        // a forced rich tape shrinks the block, an automatic one is dropped.
-        want_rich = want && rich_possible && ((er0 && atoi(er0) != 0) || block <= 128 * CT);
-        if (want_rich && (size_t)block * per_col_rich > budget) {
-            const size_t fit_rich = budget / per_col_rich / CT * CT;
-            if (er0 && atoi(er0) != 0 && fit_rich >= CT) block = (int)std::min<size_t>((size_t)block, fit_rich);
-            else want_rich = false;
-        }
-    }
-    if (!want) {
-        if (h->ag_rows) return fail("the delta tape of this network (%zu B per column) does not fit in HBM beside the solve", per_col);
+    const size_t lds_ag = (MODEL_FLOATS + lds_floats_adjoint_ag(m)) * sizeof(float);
+    const T16Tapes plan = plan_t16_tapes({n16, CT, m.ns, m.n_bias, h->ag_rows, h->adj_split, (MODEL_FLOATS + lds_floats_adjoint(m)) * sizeof(float),
+                                          (MODEL_FLOATS + lds_floats_adjoint_noA(m)) * sizeof(float), lds_ag, per_col, per_col_rich, hbm_budget(free_b, margin),
+                                          env_flag(ENV_T16_DWTAPE), ztape, env_flag(ENV_T16_SPLIT_RICH), env_int(ENV_T16_BLOCK, 0)});
+    switch (plan.status) {
+    case T16_PLAN_REFUSED_OFF:
+        return fail("COLNDE_T16_DWTAPE=0: this network's activation rows live in global memory, and only the taped-dW adjoint runs that way");
+    case T16_PLAN_REFUSED_TOO_LARGE:
+        return fail("network too large for the taped adjoint with rows in global memory (%d biases, %zu B of LDS)", m.n_bias, lds_ag);
+    case T16_PLAN_REFUSED_NO_FIT:
+        return fail("the delta tape of this network (%zu B per column) does not fit in HBM beside the solve", per_col);
+    case T16_PLAN_IN_REGISTER:
         h->t16_dwtape = 0;
         return 0;
+    case T16_PLAN_TAPED:
+        break;
     }
-    const int tiles_b = block / CT;
-    const size_t n_rec = (size_t)tiles_b * n_steps * h->m.nst;
-    const size_t need = n_rec * CT * R * sizeof(float);
-    h->t16_block = block;
-    h->t16_nblocks = (n16 + block - 1) / block;
-    build_dw_plan(h, n_rec);                                                    // (and h->t16_rows: dw_slab_rows)
-    const int stride = m.n_params + 8;
+    const size_t n_rec = (size_t)(plan.block / CT) * n_steps * m.nst;
+    h->blk.block = plan.block;
+    h->blk.nblocks = (n16 + plan.block - 1) / plan.block;
+    build_dw_plan(h, n_rec);                                                    // (and h->blk.rows: dw_slab_rows)
     const size_t mark = h->mem.mark();
-    hipError_t e = h->mem.alloc(&h->d_dwtape, need / sizeof(float));
-    if (e == hipSuccess) e = upload_dw_plan(h);
-    if (e == hipSuccess && !h->d_slab) e = h->mem.alloc(&h->d_slab, (size_t)h->t16_rows * stride);
-    if (e != hipSuccess) {                  // no delta tape: the in-register path follows
+    int at = 0;
+    const hipError_t e = t16_alloc_tapes(h, 1, n_rec, &at);
+    if (e != hipSuccess) {                  // no delta tape (or no stage tape for the block): the in-register path follows
         (void)hipGetLastError();
         h->mem.rollback(mark);
         h->t16_dwtape = 0;
-        if (h->ag_rows) return fail("allocating the delta tape (%zu B) failed: %s", need, hipGetErrorString(e));
+        if (h->ag_rows && at == 0) return fail("allocating the delta tape (%zu B) failed: %s", n_rec * CT * R * sizeof(float), hipGetErrorString(e));
+        if (h->ag_rows) return fail("allocating the stage tape failed: %s", hipGetErrorString(e));
         return 0;
     }
     h->t16_dwtape = 1;
-    // the block's stage tape, and (COLNDE_T16_ZTAPE=0 disables) the hidden pre-activations the forward kernel tapes for the adjoint
-    if (!h->d_tape) {
-        e = h->mem.alloc(&h->d_tape, n_rec * CT * m.ns);
-        if (e != hipSuccess) {
-            h->mem.rollback(mark);
-            h->t16_dwtape = 0;
-            if (h->ag_rows) return fail("allocating the stage tape failed: %s", hipGetErrorString(e));
-            return 0;
-        }
-    }
-    const char* ezt = env_get(ENV_T16_ZTAPE);
     // net-split kernels on a small block (<= 2,048 columns, where it pays: 64-step iteration with the four-wave kernels 2.36 vs 2.48 ms at 1,024
     // columns, 2.69 vs 2.77 at 2,048, 3.99 vs 3.53 at 4,096): the rich tape in place of the pre-activations
-    if (want_rich && h->mem.alloc(&h->d_t16_ztape, n_rec * rt_split_rich_record_floats()) == hipSuccess) {
+    if (plan.rich && t16_alloc_ztape(h, 1, n_rec, true) == hipSuccess) {
         h->split_rich = true;
         return 0;
     }
-    if (!(ezt && atoi(ezt) == 0)) (void)h->mem.alloc(&h->d_t16_ztape, n_rec * CT * t16_ztape_col_floats(m));      // (optional: null when it fails)
-    if ((h->ag_rows || need_z) && !h->d_t16_ztape)
+    if (ztape != FLAG_OFF) (void)t16_alloc_ztape(h, 1, n_rec, false);      // (optional: null when it fails)
+    if ((h->ag_rows || plan.need_z) && !h->d_t16_ztape)
         return fail("this network's taped adjoint needs the pre-activation tape (COLNDE_T16_ZTAPE=0 or its allocation failed): no gradient path for it without one");
     return 0;
 }
@@ -276,20 +253,20 @@ static int rt_loss_grad(colnde_handle* h, const float* d_weights, const float sc
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
     if (rt_plan_tapes(h)) return 1;
     const int n_steps = (h->cfg.n_save - 1) * h->cfg.substeps;
-    const int n_wt = rt_n_wtiles(h->n_col), n_dw = rt_dw1_waves(h->rt_block, n_steps);
+    const int n_wt = rt_n_wtiles(h->n_col), n_dw = rt_dw1_waves(h->blk.block, n_steps);
     if (!h->d_rt_slab) {
-        h->rt_rows = n_wt + h->rt_nblocks * n_dw;
-        hipError_t e = h->mem.alloc(&h->d_rt_slab, (size_t)h->rt_rows * stride);
+        h->blk.rows = n_wt + h->blk.nblocks * n_dw;
+        hipError_t e = h->mem.alloc(&h->d_rt_slab, (size_t)h->blk.rows * stride);
         if (e != hipSuccess) return fail("hipMalloc of the partial-gradient slab failed: %s", hipGetErrorString(e));
     }
     LossWeights lw;
     loss_weights(h, scalings, &lw);
     hipError_t e = rt_launch_pack(h->m, d_weights, h->d_wimg, h->stream);
     if (e != hipSuccess) return fail("rt pack launch failed: %s", hipGetErrorString(e));
-    HIPCHK(hipMemsetAsync(h->d_rt_slab, 0, (size_t)h->rt_rows * stride * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_rt_slab, 0, (size_t)h->blk.rows * stride * sizeof(float), h->stream));
     const size_t ns = h->m.ns;
-    for (int b = 0; b < h->rt_nblocks; b++) {
-        const int c0 = b * h->rt_block, nc = std::min(h->rt_block, h->n_col - c0);
+    for (int b = 0; b < h->blk.nblocks; b++) {
+        const int c0 = b * h->blk.block, nc = std::min(h->blk.block, h->n_col - c0);
         if (nc <= 0) break;
         if (rt_forward_range(h, h->d_sol, true, c0, nc)) return 1;
         {
@@ -309,7 +286,7 @@ static int rt_loss_grad(colnde_handle* h, const float* d_weights, const float sc
     }
     {
         Timed tm(h, K_REDUCE);
-        e = launch_reduce(h->d_rt_slab, h->rt_rows, h->m.n_params, stride, lw, d_out, h->stream);
+        e = launch_reduce(h->d_rt_slab, h->blk.rows, h->m.n_params, stride, lw, d_out, h->stream);
         if (e != hipSuccess) return fail("reduce launch failed: %s", hipGetErrorString(e));
     }
     return 0;
@@ -333,13 +310,13 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
     const FcConvEns ce = fc_conv_ens_args(h);
     const size_t cslab_model = (size_t)h->conv.cslab_rows * FC_CONV_GRAD_SLOTS;      // the filter slab of one model
     hipError_t e;
-    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->fc_rows * stride * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->blk.rows * stride * sizeof(float), h->stream));
     if (h->conv.c) HIPCHK(hipMemsetAsync(h->conv.d_cslab, 0, (size_t)K * cslab_model * sizeof(float), h->stream));
     const int cw = h->fc_cw;
     const int n_wg = (h->n_col + cw - 1) / cw, n_iv = h->cfg.n_save - 1, nseg = h->fc_nseg;
     const size_t gemm_rows0 = (size_t)n_wg * nseg;                      // slab: [tile][segment] adjoint rows, then [block][segment][slice] GEMM rows
-    for (int b = 0; b < h->fc_nblocks; b++) {
-        const int c0 = b * h->fc_block, nc = std::min(h->fc_block, h->n_col - c0);
+    for (int b = 0; b < h->blk.nblocks; b++) {
+        const int c0 = b * h->blk.block, nc = std::min(h->blk.block, h->n_col - c0);
         if (nc <= 0) break;
         const size_t tiles_b = ((size_t)nc + cw - 1) / cw;
         // time segments: the states at the save points first (tape-less), then segment by segment from the end of the axis
@@ -372,7 +349,7 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
     }
     {
         Timed tm(h, K_REDUCE);
-        e = launch_reduce(h->d_slab, h->fc_rows, h->m.n_params, stride, lw, h->conv.c ? h->conv.d_gpad : d_out, h->stream, K, h->fens.slab, h->ensemble ? stride : 0);
+        e = launch_reduce(h->d_slab, h->blk.rows, h->m.n_params, stride, lw, h->conv.c ? h->conv.d_gpad : d_out, h->stream, K, h->fens.slab, h->ensemble ? stride : 0);
         if (e != hipSuccess) return fail("%sreduce launch failed: %s", ens, hipGetErrorString(e));
         if (h->conv.c) {                                                // the user's layout: filter entries in front, W1's padded columns dropped
             e = launch_fc_conv_fold(h->conv.d_gpad, h->conv.d_cslab, h->conv.cslab_rows, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->conv.n_params + 8, d_out,
@@ -394,9 +371,9 @@ static int t16_taped_loss_grad(colnde_handle* h, const float* d_weights, const f
     if (!h->sched.empty() && !(h->adj_split && h->adj_helper && h->d_t16_ztape))
         return fail("a step schedule is set, but this gradient does not run on rt16sh_adjoint_kernel (no pre-activation or rich tape)");
     if (pack(h, d_weights)) return 1;
-    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)h->t16_rows * stride * sizeof(float), h->stream));
-    for (int b = 0; b < h->t16_nblocks; b++) {
-        const int c0 = b * h->t16_block, nc = std::min(h->t16_block, h->n_col - c0);
+    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)h->blk.rows * stride * sizeof(float), h->stream));
+    for (int b = 0; b < h->blk.nblocks; b++) {
+        const int c0 = b * h->blk.block, nc = std::min(h->blk.block, h->n_col - c0);
         if (nc <= 0) break;
         const int tiles_b = (nc + CT - 1) / CT;
         if (t16_forward_range(h, d_weights, h->d_sol, true, c0, nc)) return 1;
@@ -427,7 +404,7 @@ static int t16_taped_loss_grad(colnde_handle* h, const float* d_weights, const f
     }
     {
         Timed tm(h, K_REDUCE);
-        hipError_t e = launch_reduce(h->d_slab, h->t16_rows, h->m.n_params, stride, lw, d_out, h->stream);
+        hipError_t e = launch_reduce(h->d_slab, h->blk.rows, h->m.n_params, stride, lw, d_out, h->stream);
         if (e != hipSuccess) return fail("reduce launch failed: %s", hipGetErrorString(e));
     }
     return 0;

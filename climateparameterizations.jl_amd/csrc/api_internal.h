@@ -58,10 +58,14 @@ int fc_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int
 // the dW GEMM of the taped gradient paths: h->dw planned for n_rec records (dw_plan.h), its two block lists uploaded into slots of h->mem (inside the
 // caller's mark / rollback bracket), and the one place that launches it — K models: grid.y, their records and slab rows the strides apart
 void build_dw_plan(colnde_handle* h, size_t n_rec);
-void dw_slab_rows(colnde_handle* h);      // h->t16_rows / h->fc_rows (an ensemble: and the models' slab stride) for h->dw.slices
+void dw_slab_rows(colnde_handle* h);      // h->blk.rows (and the models' slab stride) for h->dw.slices
 int replan_dw_slices(colnde_handle* h);    // colnde_set_matrix_arithmetic: the slice count, slab rows and slab of the arithmetic switched to
 hipError_t upload_dw_plan(colnde_handle* h);
 hipError_t dw_launch(colnde_handle* h, size_t n_records, float* slab_rows, int K = 1, size_t tape_mstride = 0, size_t slab_mstride = 0);
+int fc_plan_tapes(colnde_handle* h);      // fc32's tapes: a single handle's at its first gradient, an ensemble's (K = h->n_models) at creation
+// tile16's taped mode for K models of n_rec records each: delta tape, dW plan, slab and stage tape (*at = 1 when that one fails), then the Z tape
+hipError_t t16_alloc_tapes(colnde_handle* h, size_t K, size_t n_rec, int* at);
+hipError_t t16_alloc_ztape(colnde_handle* h, size_t K, size_t n_rec, bool rich);
 int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
 colnde_config model_config(const colnde_config* cfg, const float* physics, int k);
 int choose_substeps_impl(colnde_handle* h, const float* d_weights, float reltol, int* chosen, float* estimate);
@@ -115,6 +119,7 @@ enum EnvSwitch { COLNDE_ENV_LIST(X) ENV_COUNT };
 const char* env_name(EnvSwitch s);
 const char* env_get(EnvSwitch s);                                      // the raw string, or null when unset or empty
 inline int env_int(EnvSwitch s, int unset) { const char* e = env_get(s); return e ? atoi(e) : unset; }
+inline int env_flag(EnvSwitch s) { const char* e = env_get(s); return e ? atoi(e) != 0 : -1; }      // tape_plan.h's FLAG_UNSET / FLAG_OFF / FLAG_ON
 inline bool allow_unstable() { return env_int(ENV_ALLOW_UNSTABLE_DT, 0) != 0; }
 
 // ---- device memory -------------------------------------------------------------------------------------------
@@ -219,17 +224,15 @@ struct colnde_handle {
     unsigned int *d_fc_simgf = nullptr, *d_fc_simgb = nullptr;   // the split operand images (COLNDE_MATRIX_BF16X3_EXACT; 32-column tiles)
     unsigned int* d_fc_masks = nullptr;
     unsigned long long* d_fc_switch = nullptr;   // ConvectiveAdjustmentNDE: the taped switch patterns
-    int fc_block = 0, fc_nblocks = 0, fc_rows = 0;   // gradient path: columns per pass (multiple of 32), passes, slab rows
-    int fc_seg = 0, fc_nseg = 0;                      // ... save intervals per time segment of the tapes, segments (1: the tapes hold the whole axis)
+    int fc_seg = 0, fc_nseg = 0;                      // gradient path: save intervals per time segment of the tapes, segments (1: the tapes hold the whole axis)
     int fc_cw = 32;                                   // columns per workgroup tile: 32, or 16 for problems of at most 4,096 columns (fc_tile_width)
     float* d_fc_lam = nullptr;                        // λ handed from one time segment to the one before it
     float* d_wimg = nullptr;
     float *d_rt_tape = nullptr, *d_rt_tape2 = nullptr, *d_rt_slab = nullptr, *d_rt_tapez = nullptr;
     bool rt_fwd32 = false;         // COLNDE_RT_FWD=32 at creation: the 32-column forward kernel (no Z1 tape)
     bool rt_ztape = false;         // layer-1 pre-activations taped by the forward kernel instead of recomputed by the adjoint
-    int rt_rows = 0;
-    int rt_block = 0;              // columns per pass of the gradient path (multiple of 32): the tapes hold one block at a time
-    int rt_nblocks = 0;
+    // the gradient path of the handle's engine: columns per pass (whole tiles: the tapes hold one block at a time), passes, partial-gradient slab rows
+    struct { int block = 0, nblocks = 0, rows = 0; } blk;
     float *d_w = nullptr, *d_wf = nullptr, *d_wb = nullptr, *d_x0 = nullptr, *d_bcs = nullptr, *d_truth = nullptr,
           *d_sol = nullptr, *d_tape = nullptr, *d_slab = nullptr, *d_out = nullptr, *d_times = nullptr,
           *d_partial = nullptr, *d_tmp_a = nullptr, *d_tmp_b = nullptr, *d_tmp_c = nullptr;
@@ -242,8 +245,6 @@ struct colnde_handle {
     DwPlan dw;                      // the dW GEMM's plan, built with the tapes' (build_dw_plan); its split passes run when sp_dw
     size_t dw_n_rec = 0;            // ... the records it was planned for (replan_dw_slices plans the slices again when the arithmetic changes)
     DwMacro *d_macros = nullptr, *d_split_macros = nullptr;   // ... and the device copies of its two block lists (the split one: null without a split plan)
-    int t16_rows = 0;
-    int t16_block = 0, t16_nblocks = 0;   // taped mode: columns per pass (multiple of 16) — the tapes hold one block
     int *d_bias_zoff = nullptr, *d_bias_goff = nullptr;
     bool have_problem = false, have_truth = false;
     bool prof = false;
@@ -284,6 +285,8 @@ struct colnde_handle {
     int launches[K_COUNT] = {};
 };
 
+// The engine a handle runs, as colnde_engine and colnde_plan report it
+inline int engine_id(const colnde_handle* h) { return h->use_rt ? COLNDE_ENGINE_MFMA : h->use_fc ? COLNDE_ENGINE_FC32 : COLNDE_ENGINE_GENERIC; }
 // The steps of the whole time axis — what sizes the tapes, the slab rows' dW records and the kernels' tape strides: the one place that forms it
 inline int total_steps(const colnde_handle* h) {
     return (int)sched_total(h->sched.empty() ? nullptr : h->sched.data(), h->cfg.n_save - 1, h->cfg.substeps);

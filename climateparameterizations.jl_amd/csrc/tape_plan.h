@@ -65,3 +65,140 @@ inline int plan_fc_conv_ens_seg(int n32, int n_iv, int cw, int Nz, size_t per_co
     while (seg > 1 && fc_conv_ens_model_bytes(n32, n_iv, cw, Nz, per_col_iv, n_params, seg, cslab_seg_floats) > budget) seg--;
     return seg;
 }
+
+// ---- the planners' decisions: everything between reading the switches and the first allocation ----------------------------------------------------------
+// Environment switches arrive parsed.  A flag: FLAG_UNSET, or atoi(value) != 0.  A forced block: atoi(value), 0 when unset (a value below one tile
+// forces nothing).  Sizes that come from engine headers (record rows, mask words, LDS bytes of the adjoint variants) arrive as numbers.
+enum { FLAG_UNSET = -1, FLAG_OFF = 0, FLAG_ON = 1 };
+
+// fc32: bytes of tape per column and save interval — the record row, the relu bit masks of a cw-column tile, the switch pattern of
+// ConvectiveAdjustmentNDE, the conv tape of a conv handle (conv_tape_floats_per_record: 0 without a filter)
+inline size_t fc_tape_bytes_per_col_iv(int substeps, int nst, size_t row_floats, size_t mask_words, int cw, bool has_switch_tape, size_t conv_tape_floats_per_record) {
+    return (size_t)substeps * nst * (row_floats * sizeof(float) + mask_words * sizeof(unsigned int) / cw + (has_switch_tape ? sizeof(unsigned long long) : 0) +
+                                     conv_tape_floats_per_record / 16 * sizeof(float));
+}
+
+// fc32, a single handle and an ensemble of K models alike.  forced_seg: COLNDE_FC_SEG as a count, 0 when unset, -1 when set to no count (which
+// still keeps a forced block from resetting seg to the whole axis).
+enum FcPlanStatus { FC_PLAN_OK, FC_PLAN_NOTHING_FITS, FC_PLAN_ENSEMBLE_REFUSED };
+struct FcTapesIn {
+    int n32, n_iv, cw, Nz, n_params;
+    size_t per_col_iv, free_bytes;
+    bool ensemble;
+    int K;                        // models (an ensemble may hold one)
+    size_t cslab_seg_floats;      // a conv ensemble: floats of filter slab per time segment (0: no filter)
+    int forced_block, forced_seg;
+};
+struct FcTapes { int block, seg; size_t model_bytes /* an ensemble: what one model needs */; FcPlanStatus status; };
+inline FcTapes plan_fc_tapes(const FcTapesIn& in) {
+    FcTapes p = {0, 0, 0, FC_PLAN_OK};
+    if (!in.ensemble) {
+        const size_t margin = ((size_t)3 << 30) + (size_t)(in.n32 / in.cw * 8 + 4096) * (in.n_params + 8) * sizeof(float) + (size_t)in.n32 * in.Nz * sizeof(float);
+        const FcTapePlan bs = plan_fc_block_seg(in.n32, in.n_iv, in.cw, in.per_col_iv, hbm_budget(in.free_bytes, margin), in.n_params);
+        p.block = bs.block;
+        p.seg = bs.seg;
+        if (in.forced_block >= 32) { p.block = std::min(in.n32, in.forced_block / 32 * 32); if (in.forced_seg == 0) p.seg = in.n_iv; }
+        if (in.forced_seg >= 1) p.seg = std::min(in.n_iv, in.forced_seg);
+        if (p.block < 32 || p.seg < 1) p.status = FC_PLAN_NOTHING_FITS;
+        return p;
+    }
+    // one block of all columns per model (column blocks do not occur at <= 4,096 columns) on the model's share of the budget
+    const size_t budget = hbm_budget(in.free_bytes, (size_t)3 << 30) / (size_t)in.K;
+    const bool conv = in.cslab_seg_floats != 0;
+    auto need = [&](int seg) {
+        return conv ? fc_conv_ens_model_bytes(in.n32, in.n_iv, in.cw, in.Nz, in.per_col_iv, in.n_params, seg, in.cslab_seg_floats)
+                    : fc_ens_model_bytes(in.n32, in.n_iv, in.cw, in.Nz, in.per_col_iv, in.n_params, seg);
+    };
+    p.block = in.n32;
+    p.seg = conv ? plan_fc_conv_ens_seg(in.n32, in.n_iv, in.cw, in.Nz, in.per_col_iv, budget, in.n_params, in.cslab_seg_floats)
+                 : plan_fc_ens_seg(in.n32, in.n_iv, in.cw, in.Nz, in.per_col_iv, budget, in.n_params);
+    if (in.forced_seg >= 1) p.seg = std::min(in.n_iv, in.forced_seg);
+    p.model_bytes = need(p.seg);
+    if (p.model_bytes > budget) p.status = FC_PLAN_ENSEMBLE_REFUSED;
+    return p;
+}
+
+// tile16 / net-split, a single handle: taped weight gradients on or off, which optional tape, the block.  On when the tapes fit; the in-register
+// adjoint remains the fallback, except for a network whose activation rows live in global memory (ag_rows), where the taped adjoint with the Z tape is
+// the ONLY gradient path (1,024 threads: n_bias <= 4 x 1,024) and every "off" is a refusal.
+enum T16PlanStatus {
+    T16_PLAN_TAPED,
+    T16_PLAN_IN_REGISTER,         // no delta tape: the in-register path follows
+    T16_PLAN_REFUSED_OFF,         // rows in global memory, and the delta tape is off (forced, or the tile state is too large)
+    T16_PLAN_REFUSED_TOO_LARGE,   // rows in global memory, and the network exceeds the taped adjoint's limits
+    T16_PLAN_REFUSED_NO_FIT       // rows in global memory, and not one tile of delta tape fits
+};
+struct T16TapesIn {
+    int n16, tile /* columns per tile */, ns, n_bias;
+    bool ag_rows, adj_split;
+    size_t lds_adjoint, lds_adjoint_noA, lds_adjoint_ag;      // bytes of LDS of the taped adjoint's variants, the model's floats included
+    size_t per_col, per_col_rich, budget;                     // bytes of tape per column with the pre-activation / the rich tape
+    int dwtape, ztape, split_rich;                            // COLNDE_T16_DWTAPE, _ZTAPE, _SPLIT_RICH: flags
+    int forced_block;                                         // COLNDE_T16_BLOCK
+};
+struct T16Tapes { bool need_z; int block; bool rich; T16PlanStatus status; };
+inline T16Tapes plan_t16_tapes(const T16TapesIn& in) {
+    const size_t lds_max = 160 * 1024;
+    T16Tapes p = {false, 0, false, T16_PLAN_IN_REGISTER};
+    bool want = in.dwtape != FLAG_OFF;
+    if (want && (size_t)in.tile * in.ns > 6 * 512) want = false;
+    // with the Z tape (the default) the taped adjoint's LDS holds no activation array; a network that fits only that way (3 x 96-400-31: 166 KB with the
+    // array, 83 KB without) then NEEDS the Z tape
+    if (want && !in.ag_rows && in.lds_adjoint > lds_max) {
+        if (in.ztape != FLAG_OFF && in.lds_adjoint_noA <= lds_max && in.n_bias <= 4 * 512) p.need_z = true;
+        else want = false;
+    }
+    if (in.ag_rows) {
+        if (!want) { p.status = T16_PLAN_REFUSED_OFF; return p; }
+        if (in.n_bias > 4 * 1024 || in.lds_adjoint_ag > lds_max) { p.status = T16_PLAN_REFUSED_TOO_LARGE; return p; }
+    }
+    if (want) {
+        // ONE block of columns (whole rounds of 4,096 columns = one workgroup per CU when possible)
+        p.block = plan_column_block(in.n16, in.budget / in.per_col, in.tile, 4096);
+        if (in.forced_block >= in.tile) p.block = std::min(in.n16, in.forced_block / in.tile * in.tile);
+        if (p.block <= 0) want = false;
+        // The net-split pair's rich tape replaces the pre-activation tape and is 4x its size per column: by default on blocks of at most 2,048
+        // columns (where it pays), forced on or off by COLNDE_T16_SPLIT_RICH.  It must fit WITH the other tapes: a forced one shrinks the block, an
+        // automatic one is dropped.
+        const bool rich_possible = in.adj_split && in.ztape != FLAG_OFF && in.split_rich != FLAG_OFF;
+        p.rich = want && rich_possible && (in.split_rich == FLAG_ON || p.block <= 128 * in.tile);
+        if (p.rich && (size_t)p.block * in.per_col_rich > in.budget) {
+            const size_t fit_rich = in.budget / in.per_col_rich / in.tile * in.tile;
+            if (in.split_rich == FLAG_ON && fit_rich >= (size_t)in.tile) p.block = (int)std::min<size_t>((size_t)p.block, fit_rich);
+            else p.rich = false;
+        }
+    }
+    if (!want) {
+        p.block = 0;
+        p.status = in.ag_rows ? T16_PLAN_REFUSED_NO_FIT : T16_PLAN_IN_REGISTER;
+        return p;
+    }
+    p.status = T16_PLAN_TAPED;
+    return p;
+}
+
+// A wind-mixing ensemble: one block of all columns per model.  The rich tape while the K models' tiles number at most 128 (2,048 columns in flight:
+// the single handle's crossover counts concurrent tiles whoever owns them) unless COLNDE_T16_SPLIT_RICH says; an automatic one gives way to the plain
+// tape when it does not fit, as for one handle.  per_model_*: bytes of a model's tapes, slab rows, solution and weight image with either tape.
+struct T16EnsTapes { bool rich; size_t bytes_per_model; bool refused; };
+inline T16EnsTapes plan_t16_ens_tapes(int K, int n_tiles, size_t per_model_rich, size_t per_model_plain, size_t budget, int split_rich) {
+    const bool forced = split_rich != FLAG_UNSET;
+    T16EnsTapes p = {forced ? split_rich == FLAG_ON : (size_t)K * n_tiles <= 128, 0, false};
+    if (p.rich && !forced && (size_t)K * per_model_rich > budget) p.rich = false;
+    p.bytes_per_model = p.rich ? per_model_rich : per_model_plain;
+    p.refused = (size_t)K * p.bytes_per_model > budget;
+    return p;
+}
+
+// regtile: the block, with the Z1 tape when even 1,024 columns fit with it and without it otherwise; COLNDE_RT_BLOCK forces a size.  block = 0: the
+// stage tapes of not even 1,024 columns fit.
+struct RtTapes { int block; bool ztape; };
+inline RtTapes plan_rt_tapes(int n32, size_t per_col_x, size_t per_col_2, size_t per_col_z, size_t budget, bool want_z, int forced_block) {
+    RtTapes p = {0, want_z};
+    for (int pass = 0; pass < 2 && p.block == 0; pass++) {
+        p.block = plan_column_block(n32, budget / (per_col_x + per_col_2 + (p.ztape ? per_col_z : 0)), 1024, 1024);
+        if (p.block == 0) p.ztape = false;       // not even 1,024 columns with the Z1 tape: try without it
+    }
+    if (forced_block >= 32) p.block = std::min(n32, forced_block / 32 * 32);
+    return p;
+}
