@@ -281,7 +281,9 @@ int ensure_ag(colnde_handle* h, size_t tiles) {
     h->ag_tiles = 0;
     const size_t bytes = tiles * ag_floats_per_tile(h->m) * sizeof(float);
     if (h->mem.resize(&h->d_ag, bytes / sizeof(float)) != hipSuccess) return fail("hipMalloc of the activation rows (%zu B) failed", bytes);
-    if (hipMemset(h->d_ag, 0, bytes) != hipSuccess) return fail("hipMemset of the activation rows failed");
+    // in stream order: the slab is new and the stream has drained, so the fill only has to precede the launches that follow on h->stream (a fill on the
+    // null stream is not ordered before a kernel on a non-blocking stream)
+    if (hipMemsetAsync(h->d_ag, 0, bytes, h->stream) != hipSuccess) return fail("hipMemsetAsync of the activation rows failed");
     h->ag_tiles = tiles;
     h->m.ag = h->d_ag;
     return 0;
@@ -543,6 +545,11 @@ extern "C" int colnde_engine(const colnde_handle* h) { return h ? engine_id(h) :
 
 extern "C" int colnde_set_stream(colnde_handle* h, void* s) {
     if (!h) return fail("null handle");
+    if ((hipStream_t)s == h->stream) return 0;          // (free: the Python front-end issues one per method call)
+    // what the handle wrote on the old stream without synchronising (the problem, packed images, tapes, the RKC table) is read on the new one
+    HIPCHK(hipSetDevice(h->device));
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail("colnde_set_stream: draining the previous stream failed: %s", hipGetErrorString(e));
     h->stream = (hipStream_t)s;
     return 0;
 }

@@ -138,7 +138,12 @@ int  colnde_create(const colnde_config* cfg, colnde_handle** out);
 void colnde_destroy(colnde_handle* h);
 int  colnde_n_params(const colnde_handle* h);
 int  colnde_engine(const colnde_handle* h);                  /* engine actually selected */
-int  colnde_set_stream(colnde_handle* h, void* hip_stream);  /* default: the null stream */
+/* The stream every later call of the handle enqueues on (default: the null stream).  A handle keeps device state from one call to the next that it
+ * wrote in stream order without synchronising — the problem of colnde_set_problem_dev, packed operand images, tapes, coefficient tables — so a call with
+ * ANOTHER stream first synchronises the stream in use (which must still exist) and returns its error; what the handle did there is then complete before
+ * anything is enqueued on the new stream.  The caller's own buffers stay the caller's to order.  A call with the stream already in use costs nothing
+ * (a front-end may issue one per call). */
+int  colnde_set_stream(colnde_handle* h, void* hip_stream);
 /* Switch the matrix arithmetic of an existing handle (COLNDE_MATRIX_*): tapes and results layout do not depend on it, so the same
  * handle can run both for an A/B on identical inputs.  A dW GEMM already planned takes the slice count a fresh handle of the new arithmetic plans (the
  * partial-gradient slab is replaced after the stream has drained), so the results are that handle's bit for bit; if the slab cannot be allocated the call
@@ -256,7 +261,9 @@ int colnde_infer_dz_wT(colnde_handle* h, const float* weights, const float* T, c
                        float Lz, float* out, int n_columns);
 
 /* ---- device-pointer twins: every pointer is device memory on cfg.device; work is enqueued on the
- * handle's stream and NOT synchronised.  d_out of loss_grad_dev has n_params + 8 floats:
+ * handle's stream and NOT synchronised — except where a call has to replace a buffer of the handle, which it does only after the stream has
+ * drained: the first solve and the first gradient of a handle (tapes, plans and tables are made then), and a call on more columns than any call
+ * before it (scratch and, for the wide networks, the activation rows grow).  d_out of loss_grad_dev has n_params + 8 floats:
  * [grad(n_params); scaled terms(6); total; 0] — the buffer a caller all-reduces (RCCL) when sharded. */
 int colnde_set_problem_dev(colnde_handle* h, const float* d_x0, const float* d_bcs, const float* d_truth);
 int colnde_rhs_dev(colnde_handle* h, const float* d_x, const float* d_weights, const float* d_bcs, float t,

@@ -265,8 +265,10 @@ def fc_embed_state(Nz):
     return s
 
 
-def embed(h, kind, n):
-    """The embedding call the handle serves on the first n of 200 columns, as a flat tuple of arrays, or None (the closure handle serves none).
+def embed_call(kind, n):
+    """(method, args, kwargs, arrays) of the embedding call a handle of the kind serves on the first n of 200 columns, or None (the closure handle
+    serves none): `arrays` names the array arguments — positions in args, keys in kwargs, ("halos", i) for the members of that pair — so that a caller
+    can put device tensors in their place (tests/stream_cases.py).
     Single wind-mixing handles: wm_embedded as K = 1 (forcing, step and faces; the wide networks through the generic kernel).  The wind-mixing
     ensemble: wm_embedded for its K models, each with its own state, halo and constants.  Plain fc32 handles: fc_embedded_step with the face
     diagnosis; the conv handle (K = 1) and the free-convection ensemble: fc_embedded.  What a K-model handle keeps from one call to the next — the
@@ -287,11 +289,11 @@ def embed(h, kind, n):
         else:
             w = p.w
             params = [tuple(float(x) for x in row) + W.mpp_params()[5:] for row in (PH2 if n == 200 else PH1)]
-        r = h.wm_embedded(w, uK, vK, TK, np.ascontiguousarray(top[:, :n]), W.LZ, dt=60.0, params=params, halo_bottom=halo)
-        return tuple(a for part in r for a in part)
+        return ("wm_embedded", [w, uK, vK, TK, np.ascontiguousarray(top[:, :n]), W.LZ], dict(dt=60.0, params=params, halo_bottom=halo),
+                [0, 1, 2, 3, 4, "halo_bottom"])
     T, top, hb, ht = fc_embed_state(p.cfg.Nz)
     if k["family"] == "single" and not k.get("conv"):
-        return tuple(h.fc_embedded_step(p.w, c(T), c(top), 1000.0, 600.0, 10.0, halos=(c(hb), c(ht)), diagnose=True))
+        return "fc_embedded_step", [p.w, c(T), c(top), 1000.0, 600.0, 10.0], dict(halos=(c(hb), c(ht)), diagnose=True), [0, 1, 2, ("halos", 0), ("halos", 1)]
     K = k.get("K", 1)
     if k.get("conv"):                                  # K = 1
         w = np.ascontiguousarray((p.w if n == 200 else np.float32(0.5) * p.w)[None])
@@ -300,7 +302,24 @@ def embed(h, kind, n):
     shift = np.arange(K, dtype=np.float32)[:, None, None] * np.float32(0.01)
     TK = np.ascontiguousarray(c(T)[None] + shift)
     hbK, htK = (np.ascontiguousarray(np.repeat(c(a)[None], K, axis=0)) for a in (hb, ht))
-    return tuple(h.fc_embedded(w, TK, c(top), 1000.0, 10.0, dt=600.0, halos=(hbK, htK)))
+    return "fc_embedded", [w, TK, c(top), 1000.0, 10.0], dict(dt=600.0, halos=(hbK, htK)), [0, 1, 2, ("halos", 0), ("halos", 1)]
+
+
+def flat(r):
+    """what an embedding call returns (a tuple of arrays, or a named tuple of such groups, None for a group not asked for) as one flat tuple"""
+    out = []
+    for part in r:
+        out.extend(part if isinstance(part, (tuple, list)) else [part])
+    return tuple(a for a in out if a is not None)
+
+
+def embed(h, kind, n):
+    """The call of `embed_call` on the handle with host arrays, as a flat tuple of arrays, or None (the closure handle)."""
+    call = embed_call(kind, n)
+    if call is None:
+        return None
+    name, args, kwargs, _ = call
+    return flat(getattr(h, name)(*args, **kwargs))
 
 
 # ---- refusals by design ------------------------------------------------------------------------------------------------------------------------------
