@@ -93,6 +93,10 @@ SYMBOLS = [
     ("colnde_ensemble_loss_dev", ctypes.c_int, [_V, _V, _F, _V]),
     ("colnde_ensemble_loss_grad_dev", ctypes.c_int, [_V, _V, _F, _V]),
     ("colnde_ensemble_loss_grad", ctypes.c_int, [_V, _V, _F, _V]),
+    ("colnde_ensemble_set_member_loss", ctypes.c_int, [_V, _V, _V]),
+    ("colnde_ensemble_member_loss_dev", ctypes.c_int, [_V, _V, _V]),
+    ("colnde_ensemble_member_loss_grad_dev", ctypes.c_int, [_V, _V, _V]),
+    ("colnde_ensemble_member_loss_grad", ctypes.c_int, [_V, _V, _V]),
     ("colnde_ensemble_adam_step_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V] + [ctypes.c_float] * 5),
     ("colnde_ensemble_wm_embedded", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _V, ctypes.c_int] + [_V] * 9 + [ctypes.c_int]),
     ("colnde_ensemble_wm_embedded_dev", ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, ctypes.c_float, ctypes.c_float, _V, ctypes.c_int] + [_V] * 9 + [ctypes.c_int]),

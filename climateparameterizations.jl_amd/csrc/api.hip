@@ -1143,6 +1143,8 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
     if (!h->sched.empty()) { snprintf(t, sizeof t, " schedule=%d/%d intervals", total_steps(h), h->cfg.n_save - 1); s += t; }
     if (h->conv.c) { snprintf(t, sizeof t, " conv=%d n_params=%d", h->conv.c, h->conv.n_params); s += t; }
     if (h->ensemble) { snprintf(t, sizeof t, " models=%d tape_bytes_per_model=%zu", h->n_models, h->ens_model_bytes); s += t; }
+    // a member loss that is set (colnde_ensemble_set_member_loss): scalings | columns | scalings+columns; without one the line is what it was (none)
+    if (h->ensemble && (h->ml_scalings || h->ml_columns)) { snprintf(t, sizeof t, " member_loss=%s", member_loss_kind(h->ml_scalings, h->ml_columns)); s += t; }
     if (h->cfg.stepper == COLNDE_STEPPER_RKC2) { snprintf(t, sizeof t, " rkc_stages=%d%s", h->m.nst, h->cfg.rkc_stages ? "" : "(automatic)"); s += t; }
     snprintf(t, sizeof t, " matrix_arithmetic=%s forward=%s adjoint=%s dw=%s", h->cfg.matrix_arithmetic == COLNDE_MATRIX_BF16X3_EXACT ? "bf16x3_exact" : "f32_mfma",
              (info[7] & 2) ? "bf16x3" : "f32", (info[7] & 4) ? "bf16x3" : "f32", (info[7] & 8) ? "bf16x3" : "f32");

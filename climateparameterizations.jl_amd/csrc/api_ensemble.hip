@@ -429,24 +429,90 @@ extern "C" int colnde_ensemble_forward_dev(colnde_handle* h, const float* d_weig
     return ens_forward(h, d_weights, d_sol, false);
 }
 
-extern "C" int colnde_ensemble_loss_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out8) {
+// ---- the member loss (colnde_ensemble_set_member_loss; member_loss.h) -------------------------------------------------------------------
+// Member k's loss is  Σ_q s[k][q] · Σ_c w[k][c] · (term q of column c) / Σ_c w[k][c] : its own six scalings — determine_loss_scalings per run
+// (wind_mixing/src/NDE_training.jl:256-288, calculate_loss_scalings: loss.jl:11-31) — and its own column weights, a 0/1 mask being the run's training
+// simulations (train_free_convection_nde.jl:60-66).  Validation and the K LossWeights rows are member_loss.h's, pure host arithmetic; the rows and the
+// K x n_col weights (ones where none were given) live in two buffers of the handle's pool, uploaded in stream order and complete on return, as
+// colnde_set_schedule uploads its counts.  The shared-scalings entry points never read them.
+extern "C" int colnde_ensemble_set_member_loss(colnde_handle* h, const float* scalings, const float* column_weights) {
     if (ensemble_only(h)) return 1;
-    if (!d_weights || !scalings || !d_out8) return fail("null pointer argument");
+    if (!scalings && !column_weights) {           // clears it (the buffers stay with the handle)
+        h->ml_scalings = h->ml_columns = false;
+        return 0;
+    }
+    const int K = h->n_models, nc = h->n_col;
+    int bk = 0, bi = 0;
+    switch (member_loss_validate(scalings, column_weights, K, nc, (long long)h->n_col_total, &bk, &bi)) {
+        case MEMBER_LOSS_OK: break;
+        case MEMBER_LOSS_GLOBAL_COLUMNS:
+            return fail("a member loss normalises by the sum of a member's column weights over THIS handle's %d columns, but the handle is a shard of %lld "
+                        "(colnde_set_global_columns): the normaliser would be a global sum", nc, (long long)h->n_col_total);
+        case MEMBER_LOSS_BAD_SCALING:
+            return fail("scalings[%d][%d] = %g: a loss scaling must be finite and >= 0", bk, bi, (double)scalings[(size_t)bk * 6 + bi]);
+        case MEMBER_LOSS_BAD_WEIGHT:
+            return fail("column_weights[%d][%d] = %g: a column weight must be finite and >= 0", bk, bi, (double)column_weights[(size_t)bk * nc + bi]);
+        case MEMBER_LOSS_EMPTY_MEMBER:
+            return fail("member %d's column weights sum to 0: it would train on no column (every member needs at least one column of positive weight)", bk);
+    }
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<LossWeights> lw((size_t)K);
+    std::vector<float> cw((size_t)K * nc, 1.0f);
+    const float ones[6] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
+    const bool wm = h->m.model == COLNDE_MODEL_WIND_MIXING;
+    for (int k = 0; k < K; k++) {
+        const float* w = column_weights ? column_weights + (size_t)k * nc : nullptr;
+        member_loss_weights(scalings ? scalings + (size_t)k * 6 : ones, member_weight_sum(w, nc), h->cfg.n_save, h->m.Nz, wm, lw[k].w);
+        if (w) std::copy(w, w + nc, cw.begin() + (size_t)k * nc);
+    }
+    const size_t mark = h->mem.mark();
+    if ((!h->d_ml_lw && h->mem.alloc(&h->d_ml_lw, (size_t)K) != hipSuccess) || (!h->d_ml_cw && h->mem.alloc(&h->d_ml_cw, (size_t)K * nc) != hipSuccess)) {
+        h->mem.rollback(mark);
+        h->ml_scalings = h->ml_columns = false;
+        return fail("allocating the member loss (%d models x %d columns) failed", K, nc);
+    }
+    // in stream order on the handle's stream and complete on return: the caller's arrays are not kept, and a gradient queued earlier has read the old ones
+    if (hipMemcpyAsync(h->d_ml_lw, lw.data(), (size_t)K * sizeof(LossWeights), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyAsync(h->d_ml_cw, cw.data(), (size_t)K * nc * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        h->ml_scalings = h->ml_columns = false;
+        return fail("uploading the member loss failed");
+    }
+    h->ml_scalings = scalings != nullptr;
+    h->ml_columns = column_weights != nullptr;
+    return 0;
+}
+
+// the member entry points: refused, before any device work, when no member loss is set
+static int member_loss_only(const colnde_handle* h, const char* fn) {
+    if (ensemble_only(h)) return 1;
+    if (!(h->ml_scalings || h->ml_columns) || !h->d_ml_lw || !h->d_ml_cw)
+        return fail("%s: no member loss is set — colnde_ensemble_set_member_loss first (colnde_ensemble_loss* take one scalings[6] for all members)", fn);
+    return 0;
+}
+
+// scalings != nullptr: the shared loss, one scalings[6] for all K; nullptr: the member loss that was set
+static int ens_loss(colnde_handle* h, const float* d_weights, const float* scalings, float* d_out8) {
     if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
     HIPCHK(hipSetDevice(h->device));
     if (ens_forward(h, d_weights, h->d_sol, false)) return 1;
-    LossWeights lw;
-    loss_weights(h, scalings, &lw);
     const int nblk = 256;
-    hipError_t e = launch_loss(h->m, h->d_sol, h->d_truth, h->cfg.n_save, h->n_col, h->d_partial, nblk, h->stream, h->n_models, h->ens.sol);
-    if (e == hipSuccess) e = launch_reduce(h->d_partial, nblk, 0, 8, lw, d_out8, h->stream, h->n_models, (size_t)nblk * 8, 8);
+    hipError_t e;
+    if (scalings) {
+        LossWeights lw;
+        loss_weights(h, scalings, &lw);
+        e = launch_loss(h->m, h->d_sol, h->d_truth, h->cfg.n_save, h->n_col, h->d_partial, nblk, h->stream, h->n_models, h->ens.sol);
+        if (e == hipSuccess) e = launch_reduce(h->d_partial, nblk, 0, 8, lw, d_out8, h->stream, h->n_models, (size_t)nblk * 8, 8);
+    } else {
+        e = launch_loss_member(h->m, h->d_sol, h->d_truth, h->cfg.n_save, h->n_col, h->d_partial, nblk, h->stream, h->n_models, h->ens.sol, h->d_ml_cw);
+        if (e == hipSuccess) e = launch_reduce_member(h->d_partial, nblk, 0, 8, h->d_ml_lw, d_out8, h->stream, h->n_models, (size_t)nblk * 8, 8);
+    }
     if (e != hipSuccess) return fail("ensemble loss launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 
-extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
-    if (ensemble_only(h)) return 1;
-    if (!d_weights || !scalings || !d_out) return fail("null pointer argument");
+static int ens_loss_grad(colnde_handle* h, const float* d_weights, const float* scalings, float* d_out) {
     if (!h->have_truth) return fail("no truth trajectories: pass truth to colnde_set_problem");
     HIPCHK(hipSetDevice(h->device));
     if (h->use_fc) {                 // fc32: the single handle's gradient path with the models' strides (api_grad.hip)
@@ -454,15 +520,16 @@ extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_we
         return check_stability(h) ? 1 : fc_loss_grad(h, d_weights, scalings, d_out);
     }
     const int K = h->n_models, stride = h->m.n_params + 8;
-    LossWeights lw;
-    loss_weights(h, scalings, &lw);
+    LossWeights lw = {};
+    if (scalings) loss_weights(h, scalings, &lw);
     HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->ens.slab * sizeof(float), h->stream));
     if (ens_forward(h, d_weights, h->d_sol, true)) return 1;
     hipError_t e;
     {
         Timed tm(h, K_ADJOINT);
         e = rt_launch_adjoint_split(h->m, h->d_wimg, h->d_times, h->cfg.n_save, h->cfg.substeps, h->d_sol, h->d_truth, h->d_tape, h->d_t16_ztape, lw,
-                                    h->d_slab, h->n_col, h->d_dwtape, h->split_rich, true, h->sp_adj, h->stream, h->ens, sched_dev(h), total_steps(h));
+                                    h->d_slab, h->n_col, h->d_dwtape, h->split_rich, true, h->sp_adj, h->stream, h->ens, sched_dev(h), total_steps(h),
+                                    scalings ? nullptr : h->d_ml_lw, scalings ? nullptr : h->d_ml_cw);
         if (e != hipSuccess) return fail("ensemble adjoint launch failed: %s", hipGetErrorString(e));
     }
     {
@@ -473,22 +540,57 @@ extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_we
     }
     {
         Timed tm(h, K_REDUCE);
-        e = launch_reduce(h->d_slab, h->blk.rows, h->m.n_params, stride, lw, d_out, h->stream, K, h->ens.slab, stride);
+        e = scalings ? launch_reduce(h->d_slab, h->blk.rows, h->m.n_params, stride, lw, d_out, h->stream, K, h->ens.slab, stride)
+                     : launch_reduce_member(h->d_slab, h->blk.rows, h->m.n_params, stride, h->d_ml_lw, d_out, h->stream, K, h->ens.slab, stride);
         if (e != hipSuccess) return fail("ensemble reduce launch failed: %s", hipGetErrorString(e));
     }
     return 0;
 }
 
-extern "C" int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float* out) {
-    if (ensemble_only(h)) return 1;
-    if (!weights || !scalings || !out) return fail("null pointer argument");
+static int ens_loss_grad_host(colnde_handle* h, const float* weights, const float* scalings, float* out) {
     HIPCHK(hipSetDevice(h->device));
     const size_t K = (size_t)h->n_models, P = (size_t)user_params(h);
     HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * K * P, hipMemcpyHostToDevice, h->stream));
-    if (colnde_ensemble_loss_grad_dev(h, h->d_w, scalings, h->d_out)) return 1;
+    if (ens_loss_grad(h, h->d_w, scalings, h->d_out)) return 1;
     HIPCHK(hipMemcpyAsync(out, h->d_out, sizeof(float) * K * (P + 8), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
+}
+
+extern "C" int colnde_ensemble_loss_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out8) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !scalings || !d_out8) return fail("null pointer argument");
+    return ens_loss(h, d_weights, scalings, d_out8);
+}
+
+extern "C" int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out) {
+    if (ensemble_only(h)) return 1;
+    if (!d_weights || !scalings || !d_out) return fail("null pointer argument");
+    return ens_loss_grad(h, d_weights, scalings, d_out);
+}
+
+extern "C" int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float* out) {
+    if (ensemble_only(h)) return 1;
+    if (!weights || !scalings || !out) return fail("null pointer argument");
+    return ens_loss_grad_host(h, weights, scalings, out);
+}
+
+extern "C" int colnde_ensemble_member_loss_dev(colnde_handle* h, const float* d_weights, float* d_out8) {
+    if (member_loss_only(h, __func__)) return 1;
+    if (!d_weights || !d_out8) return fail("null pointer argument");
+    return ens_loss(h, d_weights, nullptr, d_out8);
+}
+
+extern "C" int colnde_ensemble_member_loss_grad_dev(colnde_handle* h, const float* d_weights, float* d_out) {
+    if (member_loss_only(h, __func__)) return 1;
+    if (!d_weights || !d_out) return fail("null pointer argument");
+    return ens_loss_grad(h, d_weights, nullptr, d_out);
+}
+
+extern "C" int colnde_ensemble_member_loss_grad(colnde_handle* h, const float* weights, float* out) {
+    if (member_loss_only(h, __func__)) return 1;
+    if (!weights || !out) return fail("null pointer argument");
+    return ens_loss_grad_host(h, weights, nullptr, out);
 }
 
 extern "C" int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_result, float* d_m, float* d_v, const float* d_eta,

@@ -298,12 +298,20 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
     const int stride = h->m.n_params + 8;
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
     if (fc_plan_tapes(h)) return 1;
-    LossWeights lw;
-    loss_weights(h, scalings, &lw);
+    // scalings == nullptr: the member loss of an ensemble — every model its own loss weight and column weights, read on the device (FcEns::member_*)
+    const bool member = !scalings;
+    if (member && !(h->ensemble && h->d_ml_lw && h->d_ml_cw)) return fail("no member loss is set: colnde_ensemble_set_member_loss first");
+    LossWeights lw = {};
+    if (!member) loss_weights(h, scalings, &lw);
     const size_t ns = h->m.ns;
     // an ensemble hands the kernels the strides of what a model owns (a single handle: one model, no strides) and its own words in the launch errors
     const int K = h->n_models;
-    const FcEns* en = h->ensemble ? &h->fens : nullptr;
+    FcEns enm = h->fens;
+    if (member) {
+        enm.member_w = &h->d_ml_lw[0].w[2];
+        enm.member_colw = h->d_ml_cw;
+    }
+    const FcEns* en = h->ensemble ? &enm : nullptr;
     const char* ens = h->ensemble ? "ensemble " : "";
     if (fc_pack(h, d_weights)) return 1;
     const FcConv cv = fc_conv_args(h);                                  // (after the plan: the conv tape exists)
@@ -349,7 +357,8 @@ int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[
     }
     {
         Timed tm(h, K_REDUCE);
-        e = launch_reduce(h->d_slab, h->blk.rows, h->m.n_params, stride, lw, h->conv.c ? h->conv.d_gpad : d_out, h->stream, K, h->fens.slab, h->ensemble ? stride : 0);
+        if (member) e = launch_reduce_member(h->d_slab, h->blk.rows, h->m.n_params, stride, h->d_ml_lw, h->conv.c ? h->conv.d_gpad : d_out, h->stream, K, h->fens.slab, stride);
+        else e = launch_reduce(h->d_slab, h->blk.rows, h->m.n_params, stride, lw, h->conv.c ? h->conv.d_gpad : d_out, h->stream, K, h->fens.slab, h->ensemble ? stride : 0);
         if (e != hipSuccess) return fail("%sreduce launch failed: %s", ens, hipGetErrorString(e));
         if (h->conv.c) {                                                // the user's layout: filter entries in front, W1's padded columns dropped
             e = launch_fc_conv_fold(h->conv.d_gpad, h->conv.d_cslab, h->conv.cslab_rows, h->conv.c, h->conv.w1_end, h->conv.n_zero, h->conv.n_params + 8, d_out,

@@ -25,6 +25,7 @@
 #include "engine_fc_pretrain.h"
 #include "engine_wm_pretrain.h"
 #include "step_schedule.h"
+#include "member_loss.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -66,6 +67,7 @@ int fc_plan_tapes(colnde_handle* h);      // fc32's tapes: a single handle's at 
 // tile16's taped mode for K models of n_rec records each: delta tape, dW plan, slab and stage tape (*at = 1 when that one fails), then the Z tape
 hipError_t t16_alloc_tapes(colnde_handle* h, size_t K, size_t n_rec, int* at);
 hipError_t t16_alloc_ztape(colnde_handle* h, size_t K, size_t n_rec, bool rich);
+// scalings == nullptr: under the handle's member loss (an ensemble on which colnde_ensemble_set_member_loss has set one)
 int fc_loss_grad(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
 colnde_config model_config(const colnde_config* cfg, const float* physics, int k);
 int choose_substeps_impl(colnde_handle* h, const float* d_weights, float reltol, int* chosen, float* estimate);
@@ -275,6 +277,11 @@ struct colnde_handle {
     FcEns fens;                     // ... of a free-convection ensemble (colnde_create_fc_ensemble): the fc32 kernels' strides
     size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)
     int ens_rkc_stages = 0;         // RKC2, automatic stage count: the largest any model needs (refresh_rkc)
+    // member loss (colnde_ensemble_set_member_loss; member_loss.h): what the caller gave, and the device arrays the member kernels read — the K
+    // LossWeights rows and the K x n_col column weights (ones where the caller gave none), allocated by the first call that sets one
+    bool ml_scalings = false, ml_columns = false;
+    LossWeights* d_ml_lw = nullptr;
+    float* d_ml_cw = nullptr;
     // closure-only model (colnde_create_closure): n_models constant sets of the Pacanowski-Philander closure, no networks (engine_closure.hip)
     bool closure = false;
     ClosureModel cm = {};

@@ -37,3 +37,6 @@ hipError_t launch_dw_gemm_split(const float* dwtape, size_t n_records, int row_f
 // n_models > 1 (ensembles): grid.y = model, slab slab_mstride and out out_mstride floats apart per model
 hipError_t launch_reduce(const float* slab, int n_tiles, int n_params, int stride, const LossWeights& lw, float* out,
                          hipStream_t stream, int n_models = 1, size_t slab_mstride = 0, int out_mstride = 0);
+// ... under a member loss (colnde_ensemble_set_member_loss): model k's six raw sums are scaled by its own lwk[k] (device, [n_models])
+hipError_t launch_reduce_member(const float* slab, int n_tiles, int n_params, int stride, const LossWeights* lwk, float* out,
+                                hipStream_t stream, int n_models, size_t slab_mstride, int out_mstride);

@@ -412,6 +412,29 @@ __global__ void __launch_bounds__(1024) reduce_kernel(const float* __restrict__ 
     }
 }
 
+// reduce_kernel under a member loss: the same sums in the same order, the six raw sums of model k scaled by its own weights lwk[k]
+__global__ void __launch_bounds__(1024) reduce_member_kernel(const float* __restrict__ slab, int n_tiles, int n_params, int stride,
+                                                             const LossWeights* __restrict__ lwk, float* __restrict__ out /* [n_params + 8] */,
+                                                             size_t slab_mstride, int out_mstride) {
+    slab += (size_t)blockIdx.y * slab_mstride;
+    out += (size_t)blockIdx.y * out_mstride;
+    __shared__ float part[16][65];
+    const int px = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int p = blockIdx.x * 64 + px;
+    float s = 0.0f;
+    if (p < n_params + 6)
+        for (int t = ry; t < n_tiles; t += 16) s += slab[(size_t)t * stride + p];
+    part[ry][px] = s;
+    __syncthreads();
+    if (ry == 0 && p < n_params + 6) {
+        float tot = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 16; q++) tot += part[q][px];
+        if (p >= n_params) tot *= lwk[blockIdx.y].w[p - n_params];
+        out[p] = tot;
+    }
+}
+
 __global__ void finish_loss_kernel(float* __restrict__ out8, int out_mstride) {
     out8 += (size_t)blockIdx.x * out_mstride;             // ensembles: one workgroup per model
     if (threadIdx.x == 0) {
@@ -425,6 +448,15 @@ __global__ void finish_loss_kernel(float* __restrict__ out8, int out_mstride) {
 hipError_t launch_reduce(const float* slab, int n_tiles, int n_params, int stride, const LossWeights& lw, float* out,
                          hipStream_t stream, int n_models, size_t slab_mstride, int out_mstride) {
     hipLaunchKernelGGL(reduce_kernel, dim3((n_params + 6 + 63) / 64, n_models), dim3(1024), 0, stream, slab, n_tiles, n_params, stride, lw, out,
+                       slab_mstride, out_mstride);
+    hipLaunchKernelGGL(finish_loss_kernel, dim3(n_models), dim3(64), 0, stream, out + n_params, out_mstride);
+    return hipGetLastError();
+}
+
+hipError_t launch_reduce_member(const float* slab, int n_tiles, int n_params, int stride, const LossWeights* lwk, float* out,
+                                hipStream_t stream, int n_models, size_t slab_mstride, int out_mstride) {
+    if (!lwk) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(reduce_member_kernel, dim3((n_params + 6 + 63) / 64, n_models), dim3(1024), 0, stream, slab, n_tiles, n_params, stride, lwk, out,
                        slab_mstride, out_mstride);
     hipLaunchKernelGGL(finish_loss_kernel, dim3(n_models), dim3(64), 0, stream, out + n_params, out_mstride);
     return hipGetLastError();

@@ -22,9 +22,13 @@ bool fc_split_supported(int cw);
 // Ensembles (colnde_create_fc_ensemble): K networks of the shape on the SAME columns, the model index in blockIdx.y of the 16-column kernels.  What a
 // model owns lies at a fixed stride from model 0's, in elements of the array's type; x0 is 0 (the shared initial state) or `sol` (a time segment
 // restarting from the model's own saved state).  x0 at iv_begin = 0, bcs, truth, the save times and the RKC2 table are shared.  Passed by value.
+// member_w / member_colw (the adjoint kernel only; colnde_ensemble_set_member_loss): null, the loss enters through the scalar w_loss with every column
+// weighted 1; given, model k's loss weight is member_w[8 k] (the temperature term of its LossWeights row) and column c enters with member_colw[k][c].
 struct FcEns {
     size_t w = 0, img = 0, simg = 0, bias = 0, x0 = 0, sol = 0, dwtape = 0, masks = 0, swtape = 0, lam = 0, slab = 0;
     int n_models = 1;
+    const float* member_w = nullptr;
+    const float* member_colw = nullptr;
 };
 // The reference's --conv network (train_free_convection_nde.jl:110-122): Conv((c, 1), 1 => 1, relu) in front of the three Dense layers, on the 16-column
 // kernels (colnde_create_conv).  The filter is applied where the stage input goes to LDS: y[i] = relu(b + sum_d w[c-1-d] x[i+d]) (NNlib's conv flips the

@@ -20,9 +20,13 @@ hipError_t rt_launch_forward_split(const DevModel& m, const float* wimg, const f
                                    int n_save, int substeps, float* sol, float* t16_tape, float* t16_ztape, int n_col, bool rich, bool use_helper, bool want_split, hipStream_t stream,
                                    const RtEns& ens = RtEns(), const int* sched = nullptr, int total_steps = 0);
 size_t rt_split_rich_record_floats();   // floats per (tile, step, stage) of the net-split kernels' rich tape (which then takes the place of t16_ztape)
+// member_lw / member_colw (device, [n_models] and [n_models][n_col]; colnde_ensemble_set_member_loss): both given, lw is not read — model k is
+// differentiated under member_lw[k] with column c weighted by member_colw[k][c] (rt16sh_adjoint_member_kernel and its scheduled twin: the four-wave
+// kernels only)
 hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const float* save_times, int n_save, int substeps, const float* sol,
                                    const float* truth, const float* t16_tape, const float* t16_ztape, const LossWeights& lw, float* slab,
                                    int n_col, float* dwtape, bool rich, bool use_helper, bool want_split, hipStream_t stream,
-                                   const RtEns& ens = RtEns(), const int* sched = nullptr, int total_steps = 0);
+                                   const RtEns& ens = RtEns(), const int* sched = nullptr, int total_steps = 0,
+                                   const LossWeights* member_lw = nullptr, const float* member_colw = nullptr);
 bool rt_adjoint_split_has_bf16(const DevModel& m, bool use_helper);   // the net-split adjoint has a split (bf16-pipe) kernel for this configuration
 hipError_t rt_debug_read_stamps_split(unsigned long long* out16);   // diagnostic builds (-DCOLNDE_STAMPS): the phase stamps of this unit's kernels

@@ -950,7 +950,9 @@ rt16sh_adjoint_kernel(DevModel m, const float* __restrict__ wimg, const float* _
                       const float* __restrict__ t16_ztape, LossWeights lw, float* __restrict__ slab, int n_col,
                       float* __restrict__ dwtape, RtEns ens) {
 #define RT16SH_SCHED 0
+#define RT16SH_MEMBER 0
 #include "rt16sh_adjoint_body.inc"
+#undef RT16SH_MEMBER
 #undef RT16SH_SCHED
 }
 // ... under a step schedule (RK4): the counts the forward kernel stepped with
@@ -963,7 +965,39 @@ rt16sh_adjoint_sched_kernel(DevModel m, const float* __restrict__ wimg, const fl
     constexpr bool RKC = false;
     int substeps;                                          // the steps of the save interval in hand
 #define RT16SH_SCHED 1
+#define RT16SH_MEMBER 0
 #include "rt16sh_adjoint_body.inc"
+#undef RT16SH_MEMBER
+#undef RT16SH_SCHED
+}
+// MEMBER (colnde_ensemble_set_member_loss): the same text once more under RT16SH_MEMBER = 1 — the helper wave reads the member's own loss
+// weights, lwk[blockIdx.y] (wave-uniform), and this lane's column weight colw[blockIdx.y][column] once, before the interval loop; nothing is added inside
+// the step or stage loops and the net waves' text is the same.  A preprocessor switch, as SCHED is, so that the kernels above keep their machine code.
+template <int ACT, bool RICH, bool RKC = false, bool SPLIT = false>
+__global__ void __launch_bounds__(256)
+rt16sh_adjoint_member_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ save_times, int n_save, int substeps,
+                             const float* __restrict__ sol, const float* __restrict__ truth, const float* __restrict__ t16_tape,
+                             const float* __restrict__ t16_ztape, const LossWeights* __restrict__ lwk, const float* __restrict__ colw,
+                             float* __restrict__ slab, int n_col, float* __restrict__ dwtape, RtEns ens) {
+#define RT16SH_SCHED 0
+#define RT16SH_MEMBER 1
+#include "rt16sh_adjoint_body.inc"
+#undef RT16SH_MEMBER
+#undef RT16SH_SCHED
+}
+template <int ACT, bool RICH, bool SPLIT>
+__global__ void __launch_bounds__(256)
+rt16sh_adjoint_member_sched_kernel(DevModel m, const float* __restrict__ wimg, const float* __restrict__ save_times, int n_save,
+                                   const float* __restrict__ sol, const float* __restrict__ truth, const float* __restrict__ t16_tape,
+                                   const float* __restrict__ t16_ztape, const LossWeights* __restrict__ lwk, const float* __restrict__ colw,
+                                   float* __restrict__ slab, int n_col, float* __restrict__ dwtape, RtEns ens, const int* __restrict__ sched,
+                                   int total_steps) {
+    constexpr bool RKC = false;
+    int substeps;                                          // the steps of the save interval in hand
+#define RT16SH_SCHED 1
+#define RT16SH_MEMBER 1
+#include "rt16sh_adjoint_body.inc"
+#undef RT16SH_MEMBER
 #undef RT16SH_SCHED
 }
 
@@ -1021,6 +1055,20 @@ static Rt16shAdjointSchedFn rt16sh_adjoint_sched_pick(int act, bool rich, bool s
     with_act(act, [&](auto A) { with_bools([&](auto R, auto S) { k = rt16sh_adjoint_sched_kernel<decltype(A)::value, decltype(R)::value, decltype(S)::value>; }, rich, split); });
     return k;
 }
+using Rt16shAdjointMemberFn = decltype(&rt16sh_adjoint_member_kernel<COLNDE_ACT_RELU, false>);
+using Rt16shAdjointMemberSchedFn = decltype(&rt16sh_adjoint_member_sched_kernel<COLNDE_ACT_RELU, false, false>);
+static Rt16shAdjointMemberFn rt16sh_adjoint_member_pick(int act, bool rich, bool rkc, bool split) {
+    Rt16shAdjointMemberFn k = nullptr;
+    with_act(act, [&](auto A) {
+        with_bools([&](auto R, auto K, auto S) { k = rt16sh_adjoint_member_kernel<decltype(A)::value, decltype(R)::value, decltype(K)::value, decltype(S)::value>; }, rich, rkc, split);
+    });
+    return k;
+}
+static Rt16shAdjointMemberSchedFn rt16sh_adjoint_member_sched_pick(int act, bool rich, bool split) {
+    Rt16shAdjointMemberSchedFn k = nullptr;
+    with_act(act, [&](auto A) { with_bools([&](auto R, auto S) { k = rt16sh_adjoint_member_sched_kernel<decltype(A)::value, decltype(R)::value, decltype(S)::value>; }, rich, split); });
+    return k;
+}
 static Rt16sAdjointFn rt16s_adjoint_pick(int act, bool rich) {
     Rt16sAdjointFn k = nullptr;
     with_act(act, [&](auto A) { with_bools([&](auto R) { k = rt16s_adjoint_kernel<decltype(A)::value, decltype(R)::value>; }, rich); });
@@ -1046,10 +1094,12 @@ hipError_t rt_set_attributes_split() {
                 for (int c = 0; c < 2; c++) {
                     set(rt16sh_forward_pick(A, a, b, c));
                     set(rt16sh_adjoint_pick(A, a, b, c));
+                    set(rt16sh_adjoint_member_pick(A, a, b, c));
                 }
             for (int c = 0; c < 2; c++) {
                 set(rt16sh_forward_sched_pick(A, a, c));
                 set(rt16sh_adjoint_sched_pick(A, a, c));
+                set(rt16sh_adjoint_member_sched_pick(A, a, c));
             }
         }
     });
@@ -1089,8 +1139,9 @@ bool rt_adjoint_split_has_bf16(const DevModel& m, bool use_helper) { return use_
 hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const float* save_times, int n_save, int substeps, const float* sol,
                                    const float* truth, const float* t16_tape, const float* t16_ztape, const LossWeights& lw, float* slab,
                                    int n_col, float* dwtape, bool rich, bool use_helper, bool want_split, hipStream_t stream,
-                                   const RtEns& ens, const int* sched, int total_steps) {
+                                   const RtEns& ens, const int* sched, int total_steps, const LossWeights* member_lw, const float* member_colw) {
     if (sched && (!use_helper || m.rkc || m.nst != 4 || total_steps < n_save - 1)) return hipErrorInvalidValue;   // a schedule: the four-wave RK4 kernels only
+    if ((member_lw != nullptr) != (member_colw != nullptr) || (member_lw && !use_helper)) return hipErrorInvalidValue;   // a member loss: the four-wave kernels only
     // the record formats this kernel reads and writes are tile16's for exactly this shape
     if (!rt_supported(m) || dwtape_row_floats(m) * CT != RT16S_REC || t16_ztape_col_floats(m) * CT != RT16S_ZREC || (m.nst != 4 && !(m.rkc && use_helper)))
         return hipErrorInvalidValue;
@@ -1100,7 +1151,15 @@ hipError_t rt_launch_adjoint_split(const DevModel& m, const float* wimg, const f
     // COLNDE_MATRIX_BF16X3_EXACT: the W1^T products on the bf16 pipe (four-wave kernels, RK4 and RKC2)
     const bool split = want_split && rt_adjoint_split_has_bf16(m, use_helper);
     if (split) hipLaunchKernelGGL(rt_pack_split_nsadj_kernel, dim3(36, ens.n_models), dim3(256), 0, stream, wimg, reinterpret_cast<unsigned*>(const_cast<float*>(wimg)) + RT_NSA_OFF, (int)ens.wimg);
-    if (sched) {
+    if (member_lw && sched) {
+        const auto k = rt16sh_adjoint_member_sched_pick(m.acts[0], rich, split);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, gridh, blockh, rt16sh_adjoint_lds_bytes(split), stream, m, wimg, save_times, n_save, sol, truth, t16_tape, t16_ztape, member_lw, member_colw, slab, n_col, dwtape, ens, sched, total_steps);
+    } else if (member_lw) {
+        const auto k = rt16sh_adjoint_member_pick(m.acts[0], rich, m.rkc != nullptr, split);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, gridh, blockh, rt16sh_adjoint_lds_bytes(split), stream, m, wimg, save_times, n_save, substeps, sol, truth, t16_tape, t16_ztape, member_lw, member_colw, slab, n_col, dwtape, ens);
+    } else if (sched) {
         const auto k = rt16sh_adjoint_sched_pick(m.acts[0], rich, split);
         if (!k) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k, gridh, blockh, rt16sh_adjoint_lds_bytes(split), stream, m, wimg, save_times, n_save, sol, truth, t16_tape, t16_ztape, lw, slab, n_col, dwtape, ens, sched, total_steps);

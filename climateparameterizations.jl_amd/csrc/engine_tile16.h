@@ -45,6 +45,9 @@ hipError_t launch_forward(const DevModel& m, const PackInfo& pk, const float* w,
 // n_models > 1 (ensembles): grid.y = model, sol [K] sol_mstride floats apart, partial [K][n_blocks][8]; truth shared
 hipError_t launch_loss(const DevModel& m, const float* sol, const float* truth, int n_save, int n_col, float* partial,
                        int n_blocks, hipStream_t stream, int n_models = 1, size_t sol_mstride = 0);
+// ... under a member loss (colnde_ensemble_set_member_loss): column c of model k enters its sums with the weight colw[k][c] (device, [n_models][n_col])
+hipError_t launch_loss_member(const DevModel& m, const float* sol, const float* truth, int n_save, int n_col, float* partial,
+                              int n_blocks, hipStream_t stream, int n_models, size_t sol_mstride, const float* colw);
 hipError_t launch_adjoint(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* wb,
                           const TileDesc* tiles, const int* bias_zoff, const int* bias_goff, const float* bcs,
                           const float* save_times, int n_save, int substeps, const float* sol, const float* truth,

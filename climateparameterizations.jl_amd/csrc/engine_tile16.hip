@@ -1069,6 +1069,38 @@ __global__ void loss_kernel(DevModel m, const float* __restrict__ sol, const flo
     block_reduce_sums(sums, 6, red, partial + (size_t)blockIdx.x * 8, tid, nth);
 }
 
+// The member loss of an ensemble (colnde_ensemble_set_member_loss): loss_kernel's sums with the column's weight of the member, colw[model][column].
+// The weighted difference cw d is formed first and the sums take (cw d) d and (cw glo) glo: a weight of 1 gives loss_kernel's bits.  Same rows per
+// workgroup, same order, no atomics.
+__global__ void loss_member_kernel(DevModel m, const float* __restrict__ sol, const float* __restrict__ truth, int n_save,
+                                   int n_col, float* __restrict__ partial /* [gridDim.x][8] */, size_t sol_mstride, const float* __restrict__ colw) {
+    sol += (size_t)blockIdx.y * sol_mstride;
+    partial += (size_t)blockIdx.y * gridDim.x * 8;
+    colw += (size_t)blockIdx.y * n_col;
+    __shared__ float red[16 * 8];
+    const int tid = threadIdx.x, nth = blockDim.x;
+    const int Nz = m.Nz;
+    const bool wm = m.model == COLNDE_MODEL_WIND_MIXING;
+    float sums[6] = {0, 0, 0, 0, 0, 0};
+    const size_t rows = (size_t)n_col * n_save;
+    for (size_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const float cw = colw[row / n_save];
+        const size_t base = row * m.ns;
+        for (int i = tid; i < m.ns; i += nth) {
+            const float d = sol[base + i] - truth[base + i];
+            const float dw = cw * d;
+            if (!wm) { sums[2] += dw * d; continue; }
+            const int k = i / Nz, f = i - k * Nz;
+            sums[k] += dw * d;
+            if (f >= 1) {
+                const float glo = (d - (sol[base + i - 1] - truth[base + i - 1])) * (float)Nz;
+                sums[3 + k] += (cw * glo) * glo;
+            }
+        }
+    }
+    block_reduce_sums(sums, 6, red, partial + (size_t)blockIdx.x * 8, tid, nth);
+}
+
 // ------------------------------------------------------------------------------------------------
 // adjoint: back-propagation through the RK4 steps, replaying the stage-input tape
 // ------------------------------------------------------------------------------------------------
@@ -1553,6 +1585,13 @@ hipError_t launch_forward(const DevModel& m, const PackInfo& pk, const float* w,
 hipError_t launch_loss(const DevModel& m, const float* sol, const float* truth, int n_save, int n_col, float* partial,
                        int n_blocks, hipStream_t stream, int n_models, size_t sol_mstride) {
     hipLaunchKernelGGL(loss_kernel, dim3(n_blocks, n_models), dim3(256), 0, stream, m, sol, truth, n_save, n_col, partial, sol_mstride);
+    return hipGetLastError();
+}
+
+hipError_t launch_loss_member(const DevModel& m, const float* sol, const float* truth, int n_save, int n_col, float* partial,
+                              int n_blocks, hipStream_t stream, int n_models, size_t sol_mstride, const float* colw) {
+    if (!colw) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(loss_member_kernel, dim3(n_blocks, n_models), dim3(256), 0, stream, m, sol, truth, n_save, n_col, partial, sol_mstride, colw);
     return hipGetLastError();
 }
 

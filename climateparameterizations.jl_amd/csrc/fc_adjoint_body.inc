@@ -33,19 +33,49 @@
     u32 swp = 0;                                 // switch bits of this thread's items: bit 2r = face oi, bit 2r + 1 = face oi + 1 of item r
     float db2 = 0.0f, db1 = 0.0f;                // bias gradients of hidden unit tid (< H): column sums of the dz rows, taken from LDS
     float sumsq = 0.0f;
+    // ENS, a member loss (FcEns::member_w / member_colw; colnde_ensemble_set_member_loss): the model's own loss weight in w_loss' place and the weight
+    // of every column of the tile.  The 16 weights are loaded here, before the first save point's reads, and parked in LDS (64 bytes of static LDS, the
+    // ENS instantiations only): the load is consumed by its LDS write (the forward kernel's rule: a register still in flight at the loop header puts a
+    // vmcnt(0) at the top of every stage), no register and no pointer stays live across the stage loop, and an injection reads its weights back with
+    // LDS reads at immediate offsets from one address, formed where it is used (FC_MEMBER_CW: owned column r = tid / NZ + (256 / NZ) r; the opaque zero
+    // keeps the address from being hoisted into a register that would live through the stage loop).  cw d is formed first: the injection takes it, the
+    // sum (cw d) d — without a member loss cw = 1 and both are the unweighted operations, bit for bit.
+#define FC_MEMBER_CW(p)                \
+    const float* p = nullptr;          \
+    if constexpr (ENS) {               \
+        int zcw = 0;                   \
+        FC_OPAQUE_ZERO(zcw);           \
+        p = cwl + (tid + zcw) / NZ;    \
+    }
+    float wl = w_loss;
+    float* cwl = nullptr;
+    // CONV + ENS: the filter is read in front of the member block — behind its barrier (a memory clobber) the compiler no longer takes the taps for
+    // invariant and fetches them with vector loads into nine registers per lane, where scalar loads kept them in SGPRs
+    float cwv[FC_CONV_MAX], cbv = 0.0f;
+    if constexpr (CONV && ENS) fc_conv_load(cv, cwv, cbv);
+    if constexpr (ENS) {
+        __shared__ float fc_member_cw[CW];
+        cwl = fc_member_cw;
+        if (en.member_w) wl = en.member_w[(size_t)blockIdx.y * 8];
+        if (tid < CW) fc_member_cw[tid] = (en.member_colw && col0 + tid < n_col) ? en.member_colw[(size_t)blockIdx.y * n_col + col0 + tid] : 1.0f;
+        FC_BARRIER();
+    }
+    {
+        FC_MEMBER_CW(cwp);
 #pragma unroll
-    for (int r = 0; r < S::OWN; r++) {
-        lam[r] = 0.0f; xb[r] = 0.0f; db3[r] = 0.0f; kb[r] = 0.0f;
-        if (lam_io && iv_end < n_save - 1) lam[r] = lam_io[(size_t)(col0 + oc[r]) * NZ + oi];
-        if (iv_begin == 0 && col0 + oc[r] < n_col) {                // save point 0 enters the loss value only
-            const size_t q = ((size_t)(col0 + oc[r]) * n_save) * NZ + oi;
-            const float d = sol[q] - truth[q];
-            sumsq += d * d;
+        for (int r = 0; r < S::OWN; r++) {
+            lam[r] = 0.0f; xb[r] = 0.0f; db3[r] = 0.0f; kb[r] = 0.0f;
+            if (lam_io && iv_end < n_save - 1) lam[r] = lam_io[(size_t)(col0 + oc[r]) * NZ + oi];
+            if (iv_begin == 0 && col0 + oc[r] < n_col) {                // save point 0 enters the loss value only
+                const size_t q = ((size_t)(col0 + oc[r]) * n_save) * NZ + oi;
+                const float d = sol[q] - truth[q];
+                if constexpr (ENS) sumsq += (cwp[(256 / NZ) * r] * d) * d;
+                else sumsq += d * d;
+            }
         }
     }
     const int n_steps = (iv_end - iv_begin) * substeps;          // steps (and, x nst, records per tile) of this launch
-    float cwv[FC_CONV_MAX], cbv = 0.0f;
-    if constexpr (CONV) fc_conv_load(cv, cwv, cbv);
+    if constexpr (CONV && !ENS) fc_conv_load(cv, cwv, cbv);
 
     // pullback of one right-hand-side evaluation: stage cotangent kb[] (owner layout) -> xb[] = J(Y)ᵀ kb; qi = record index
     auto pull = [&](int qi) {
@@ -169,13 +199,20 @@
     for (int iv = iv_end - 1; iv >= iv_begin; iv--) {
         const float dt = (save_times[iv + 1] - save_times[iv]) / (float)substeps;
         // λ += ∂loss/∂sol[:, iv+1]   (nde_loss = Flux.mse over every (level, save point, simulation): training.jl:55-62)
+        FC_MEMBER_CW(cwp);
 #pragma unroll
         for (int r = 0; r < S::OWN; r++)
             if (col0 + oc[r] < n_col) {
                 const size_t q = ((size_t)(col0 + oc[r]) * n_save + iv + 1) * NZ + oi;
                 const float d = sol[q] - truth[q];
-                sumsq += d * d;
-                lam[r] += 2.0f * w_loss * d;
+                if constexpr (ENS) {
+                    const float dw = cwp[(256 / NZ) * r] * d;
+                    sumsq += dw * d;
+                    lam[r] += 2.0f * wl * dw;
+                } else {
+                    sumsq += d * d;
+                    lam[r] += 2.0f * w_loss * d;
+                }
             }
         for (int s = substeps - 1; s >= 0; s--) {
             const int step = (iv - iv_begin) * substeps + s;
@@ -260,3 +297,4 @@
         out[go.b[0] + tid] = db1;
         out[go.b[1] + tid] = db2;
     }
+#undef FC_MEMBER_CW

@@ -1,5 +1,8 @@
 // The body of rt16sh_adjoint_kernel and rt16sh_adjoint_sched_kernel (engine_netsplit.hip, which describes it): RT16SH_SCHED = 1 reads the steps of each save
 // interval from sched[] and sizes the tapes by total_steps, 0 takes `substeps` everywhere.
+// RT16SH_MEMBER = 1 (rt16sh_adjoint_member_kernel and its scheduled twin: the member loss of an ensemble, colnde_ensemble_set_member_loss): the loss
+// weights are the member's own, lwk[blockIdx.y], and every column carries the member's weight colw[blockIdx.y][column] into the injection and the six
+// sums.  0 compiles the text as it was.
     // ensembles: blockIdx.y = model — its weight image, solution, tapes, slab rows and closure constants (truth shared); grid.y = 1: one model
     wimg += (size_t)blockIdx.y * ens.wimg;
     sol += (size_t)blockIdx.y * ens.sol;
@@ -8,6 +11,9 @@
     slab += (size_t)blockIdx.y * ens.slab;
     dwtape += (size_t)blockIdx.y * ens.dwtape;
     const RtPhys ph = ens.phys ? ens.phys[blockIdx.y] : rt_phys_of(m);
+#if RT16SH_MEMBER
+    const LossWeights lw = lwk[blockIdx.y];                             // wave-uniform: the member's own weights
+#endif
     // SPLIT: LDS holds the fp32 image from W2 on (addressed through wl as before: wl[RT_W2C + x]), no fp32 W1
     constexpr int IMG0 = SPLIT ? RT_W2C : 0;
     constexpr int IMGF = ((RT_IMG_FLOATS - IMG0) + 3) & ~3;
@@ -54,6 +60,11 @@
 #pragma unroll
             for (int tau = 0; tau < 2; tau++) { lam[q].t[tau] = (f32x4t)(0.0f); xb[q].t[tau] = (f32x4t)(0.0f); xbs[q].t[tau] = (f32x4t)(0.0f); }
         float sum_d[3] = {0.0f, 0.0f, 0.0f}, sum_g[3] = {0.0f, 0.0f, 0.0f};
+#if RT16SH_MEMBER
+        // the member's weight of this lane's column, loaded once: cw d is formed first and carries the weight into the injection (linear in d), the
+        // six sums take (cw d) d — a weight of 1 reproduces the unweighted operations exactly, a weight of 0 injects exact zeros
+        const float cw = valid ? colw[(size_t)blockIdx.y * n_col + colc] : 0.0f;
+#endif
         auto inject = [&](int sv, bool add) __attribute__((always_inline)) {
 #pragma unroll
             for (int q = 0; q < 3; q++) {
@@ -66,6 +77,26 @@
 #pragma unroll
                     for (int e = 0; e < 4; e++) d.t[tau][e] = valid ? a[e] - b[e] : 0.0f;
                 }
+#if RT16SH_MEMBER
+                V16 dw;                                                  // cw d
+#pragma unroll
+                for (int tau = 0; tau < 2; tau++)
+#pragma unroll
+                    for (int e = 0; e < 4; e++) dw.t[tau][e] = cw * d.t[tau][e];
+                const V16 dd = shift_down16(d, lane, 0.0f), ddw = shift_down16(dw, lane, 0.0f);
+                V16 gg;                                                  // the gradient of cw d: what is injected
+#pragma unroll
+                for (int tau = 0; tau < 2; tau++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const bool top = tau == 0 && r == 0 && g == 0;
+                        const float gu = top ? 0.0f : (d.t[tau][r] - dd.t[tau][r]) * 32.0f;
+                        gg.t[tau][r] = top ? 0.0f : (dw.t[tau][r] - ddw.t[tau][r]) * 32.0f;
+                        sum_d[q] += dw.t[tau][r] * d.t[tau][r];
+                        sum_g[q] += gg.t[tau][r] * gu;
+                    }
+                d = dw;
+#else
                 const V16 dd = shift_down16(d, lane, 0.0f);
                 V16 gg;
 #pragma unroll
@@ -76,6 +107,7 @@
                         sum_d[q] += d.t[tau][r] * d.t[tau][r];
                         sum_g[q] += gg.t[tau][r] * gg.t[tau][r];
                     }
+#endif
                 if (add) {
                     const V16 gu_ = shift_up16(gg, lane, 0.0f);
 #pragma unroll

@@ -291,16 +291,21 @@ def _fc_ensemble(cfg: NDEConfig, T0, nde_params, true_sols, W, device, matrix_ar
 
 
 def train_neural_differential_equation_ensemble(T0, nde_params, true_sols, cfg: NDEConfig, W, etas, epochs: int, causal_coeff=None, device: int = 0,
-                                                beta=(0.9, 0.999), eps: float = 1e-8, matrix_arithmetic="bf16x3_exact", conv: int = 0):
+                                                beta=(0.9, 0.999), eps: float = 1e-8, matrix_arithmetic="bf16x3_exact", conv: int = 0,
+                                                training_simulations=None):
     """`train_neural_differential_equation!` (training.jl:44-74) for K networks at once — the sweep of train_free_convection_nde.jl (one process per
     seed, optimiser rate or `--spatial_causality` there) on the same simulations.  T0 [n_sims, Nz], nde_params [n_sims, 2] = [bottom, top],
     true_sols [n_sims, Nt, Nz] (scaled); W [K, n_params], etas [K]; causal_coeff [K] or None: model k trains on
     `Flux.mse(...) + c_k sum(abs2, W1[mask])` (train_free_convection_nde.jl:186-197; 1 is the reference's penalty, 0 none).  θ and the ADAM state stay
     on the device; per epoch one loss + gradient, one penalty add (with coefficients) and one ADAM step for all K.
     conv = c > 1: K `--conv c` networks, cfg the plain configuration, W [K, conv_n_params(Nz, c)]; the penalty masks the conv chain's first Dense weight.
+    training_simulations: a list of K index lists — member k trains on its own simulations (`--training-simulations`,
+    train_free_convection_nde.jl:60-66) through the member loss (`set_member_loss` with 0/1 column weights, `member_loss_grad`); every member is
+    still solved on all simulations, and `nde_loss_history` gives the loss on those it did not train on.  None: the calls issued before.
     Returns (θ [K, n_params], loss history [epochs, K] — the penalty included, as `nde_loss` returns it)."""
     import torch
     from .nde import check_fc_ensemble_arrays
+    from .wind_mixing import member_column_weights
     et = np.ascontiguousarray(etas, dtype=np.float32)
     cc = None if causal_coeff is None else np.ascontiguousarray(causal_coeff, dtype=np.float32)
     Wn = np.asarray(W)
@@ -317,8 +322,14 @@ def train_neural_differential_equation_ensemble(T0, nde_params, true_sols, cfg: 
         v = torch.zeros((K, n), dtype=torch.float32, device=dev)
         bt = [beta[0], beta[1]]
         hist = []
+        member = training_simulations is not None
+        if member:
+            ens.set_member_loss(np.tile(np.array([0, 0, 1, 0, 0, 0], np.float32), (K, 1)), member_column_weights(K, ens.n_columns, training_simulations))
         for _ in range(epochs):
-            ens.loss_grad(theta, [0, 0, 1, 0, 0, 0], out=out)
+            if member:
+                ens.member_loss_grad(theta, out=out)
+            else:
+                ens.loss_grad(theta, [0, 0, 1, 0, 0, 0], out=out)
             if cc_d is not None:
                 ens.causal_penalty(theta, cc_d, out)
             hist.append(out[:, n + 6].clone())

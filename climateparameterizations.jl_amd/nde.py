@@ -555,6 +555,42 @@ class ColumnNDEEnsemble(ColumnNDE):
         _lib.check(self._L.colnde_ensemble_loss_grad(self._h, _ptr(w), sc, _ptr(res)))
         return res
 
+    # ---- the member loss: every member its own scalings and its own training simulations (include/colnde.h: colnde_ensemble_set_member_loss) ----
+    def set_member_loss(self, scalings=None, column_weights=None):
+        """`colnde_ensemble_set_member_loss`: member k is differentiated under sum_q s[k][q] sum_c w[k][c] (term q of column c) / sum_c w[k][c].
+        scalings [K, 6] or None (every scaling 1); column_weights [K, n_columns] or None (every column 1; a 0/1 row is the member's training
+        simulations).  Both None clears it.  Host arrays, copied before the call returns; the upload is ordered on torch's current stream."""
+        sc = None if scalings is None else _f32(scalings, (self.n_models, 6))
+        cw = None if column_weights is None else _f32(column_weights, (self.n_models, self.n_columns))
+        self.use_torch_stream()
+        _lib.check(self._L.colnde_ensemble_set_member_loss(self._h, _ptr(sc), _ptr(cw)))
+
+    def member_loss(self, weights):
+        """[K, 8] = [scaled terms(6); total; 0] per model under the member loss that was set (`loss` with every member's own scalings and columns)."""
+        import torch
+        w, is_t = self._weights_dev(weights)
+        out = torch.empty((self.n_models, 8), dtype=torch.float32, device=w.device)
+        self.use_torch_stream()
+        _lib.check(self._L.colnde_ensemble_member_loss_dev(self._h, w.data_ptr(), out.data_ptr()))
+        return out if is_t else out.cpu().numpy()
+
+    def member_loss_grad(self, weights, out=None):
+        """[K, n_params + 8] under the member loss that was set: `loss_grad`'s rows, every member under its own scalings and columns."""
+        shape = (self.n_models, self.n_params + 8)
+        if _is_torch(weights):
+            import torch
+            self._chk_dev(weights, (self.n_models, self.n_params))
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=weights.device)
+            self._chk_dev(out, shape)
+            self.use_torch_stream()
+            _lib.check(self._L.colnde_ensemble_member_loss_grad_dev(self._h, weights.data_ptr(), out.data_ptr()))
+            return out
+        w = _f32(weights, (self.n_models, self.n_params))
+        res = np.empty(shape, dtype=np.float32)
+        _lib.check(self._L.colnde_ensemble_member_loss_grad(self._h, _ptr(w), _ptr(res)))
+        return res
+
     def adam_step(self, weights, result, m, v, etas, beta=(0.9, 0.999), eps: float = 1e-8, beta_t=None):
         """Flux ADAM for every model (in place): weights, m, v [K, P]; the gradient read from `result` [K, P + 8] (loss_grad's buffer); etas [K]."""
         import torch

@@ -273,14 +273,47 @@ def train_NDE_device(problem: WindMixingNDE, weights, optimizers: Sequence[ADAM]
     return TrainResult(theta.cpu().numpy(), history)
 
 
+def member_column_weights(n_models: int, n_simulations: int, training_simulations) -> np.ndarray:
+    """The 0/1 column weights [K, n_simulations] of `training_simulations`: a list of K index lists, member k trains on its own (no GPU needed)."""
+    ts = list(training_simulations)
+    if len(ts) != n_models:
+        raise ValueError("training_simulations: expected %d index lists (one per member), got %d" % (n_models, len(ts)))
+    cw = np.zeros((n_models, n_simulations), dtype=np.float32)
+    for k, idx in enumerate(ts):
+        idx = [int(i) for i in idx]
+        if not idx:
+            raise ValueError("training_simulations[%d] is empty: every member needs at least one simulation" % k)
+        if min(idx) < 0 or max(idx) >= n_simulations or len(set(idx)) != len(idx):
+            raise ValueError("training_simulations[%d]: distinct indices in 0..%d, got %r" % (k, n_simulations - 1, idx))
+        cw[k, idx] = 1.0
+    return cw
+
+
+def member_fractions(n_models: int, training_fractions):
+    """`training_fractions` as a list of K dicts: one dict for all members, or a list of K (no GPU needed)."""
+    if isinstance(training_fractions, dict):
+        return [training_fractions] * n_models
+    fr = list(training_fractions)
+    if len(fr) != n_models or not all(isinstance(f, dict) for f in fr):
+        raise ValueError("training_fractions: a dict for all members or a list of %d dicts" % n_models)
+    return fr
+
+
 def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: int = 1, maxiters: int = 500, beta=(0.9, 0.999),
-                       eps: float = 1e-8, schedule=None) -> List[TrainResult]:
+                       eps: float = 1e-8, schedule=None, training_fractions=None, training_simulations=None,
+                       gradient_scaling=None) -> List[TrainResult]:
     """`train_NDE_device`'s loop (NDE_training.jl:340-372: ADAM, per-solve state reset, save_best) for K models at once — the sweep of
     wind_mixing/train_NDE_args.jl, which trains one model per process with its own ADAM rate (ARGS[2], :143) and Pacanowski-Philander constants
     (ARGS[3], :175).  weights [K, n_params], physics [K, 5] = (nu0, nu_minus, dRi, Ric, Pr) per model or None (the problem's constants), etas [K].
     One `colnde_ensemble_loss_grad_dev` and one `colnde_ensemble_adam_step_dev` per iteration for all models, on the problem's simulations and
     loss scalings; `save_best` per model (torch.where over rows).  Returns one TrainResult per model.
-    schedule: RK4 steps per save interval shared by the K models (`ColumnNDEEnsemble.set_schedule`), None: cfg.substeps."""
+    schedule: RK4 steps per save interval shared by the K models (`ColumnNDEEnsemble.set_schedule`), None: cfg.substeps.
+    The member loss (`ColumnNDEEnsemble.set_member_loss`) — with all three of the following None the function issues the calls above:
+    training_fractions: dict(T, dTdz, profile) for all members or a list of K dicts — `determine_loss_scalings` per member (NDE_training.jl:256-288):
+    one `member_loss` at the initial weights under unit scalings, then `calculate_loss_scalings` (loss.jl:11-31) on every row, so that each member
+    trains under the scalings of its own first solve with its own constants.  training_simulations: a list of K index lists, member k trains on
+    its own simulations (N_sims of train_NDE_args.jl; train_free_convection_nde.jl:60-66) and is still solved on all of them.  gradient_scaling:
+    without fractions, the scalings are (1, 1, 1, g, g, g) for every member (None: the problem's loss scalings)."""
     import torch
     from .nde import ColumnNDEEnsemble, check_ensemble_arrays
     W = np.ascontiguousarray(weights, dtype=np.float32)
@@ -304,6 +337,20 @@ def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: i
         sc = problem.loss_scalings.copy()
         if not problem.cfg.train_gradient:
             sc[3:] = 0.0
+        member = not (training_fractions is None and training_simulations is None and gradient_scaling is None)
+        if member:
+            tg = problem.cfg.train_gradient
+            cw = None if training_simulations is None else member_column_weights(K, problem.n_simulations, training_simulations)
+            if gradient_scaling is not None:
+                g = float(gradient_scaling) if tg else 0.0
+                sc = np.array([1, 1, 1, g, g, g], dtype=np.float64)
+            scs = np.tile(np.asarray(sc, np.float64), (K, 1))
+            if training_fractions is not None:
+                fr = member_fractions(K, training_fractions)
+                ens.set_member_loss(np.tile(np.array([1, 1, 1, 1, 1, 1] if tg else [1, 1, 1, 0, 0, 0], np.float32), (K, 1)), cw)
+                terms = ens.member_loss(theta).cpu().numpy()
+                scs = np.stack([calculate_loss_scalings(terms[k, :6], fr[k], tg) for k in range(K)])
+            ens.set_member_loss(scs.astype(np.float32), cw)
         hist = []
         for _ in range(epochs):
             m = torch.zeros((K, n), dtype=torch.float32, device=dev)
@@ -312,7 +359,10 @@ def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: i
             best = torch.full((K,), float("inf"), dtype=torch.float32, device=dev)
             best_theta = theta.clone()
             for _ in range(maxiters):
-                ens.loss_grad(theta, sc, out=out)
+                if member:
+                    ens.member_loss_grad(theta, out=out)
+                else:
+                    ens.loss_grad(theta, sc, out=out)
                 total = out[:, n + 6]
                 hist.append(out[:, n:n + 7].clone())
                 ens.adam_step(theta, out, m, v, eta_d, beta, eps, beta_t=tuple(bt))

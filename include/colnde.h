@@ -519,6 +519,26 @@ int colnde_ensemble_loss_dev(colnde_handle* h, const float* d_weights, const flo
 int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
 /* the same with host arrays: weights [K][n_params], out [K][n_params + 8]; synchronises the stream */
 int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float* out);
+/* ---- the member loss: every member its own loss scalings and its own training simulations --------------------------------------------------------------
+ * In the reference the loss is per run in two ways.  determine_loss_scalings (wind_mixing/src/NDE_training.jl:256-288) solves once with the run's own
+ * initial weights and constants and feeds the six unscaled terms to calculate_loss_scalings (loss.jl:11-31), so two runs of a sweep train under different
+ * scalings; and --training-simulations (free_convection/train_free_convection_nde.jl:60-66; N_sims of train_NDE_args.jl) trains a run on some of the
+ * simulations and judges it on the rest.  Under a member loss, member k is differentiated under
+ *     loss_k = sum_q s[k][q] * sum_c w[k][c] * (term q of column c) / sum_c w[k][c]
+ * scalings [K][6] (host; NULL: every scaling 1) and column_weights [K][n_col] (host; NULL: every column 1; a 0/1 row is a training set, fractions weigh
+ * simulations).  Both NULL clears the member loss.  The K weight rows are formed on the host in double, by the expression colnde_loss* use with
+ * sum_c w[k][c] (summed in double) in the column count's place; the arrays are uploaded in stream order on the handle's stream and the upload is complete
+ * when the call returns (the caller's arrays are not kept).  Refused before any device work, with the reason in colnde_last_error: a handle that is not
+ * an ensemble (closure handles included), an entry that is negative or not finite, a member whose column weights sum to 0, a handle whose global column
+ * count differs from its own (the normaliser would be a global sum).  Free-convection and conv ensembles take the same calls; as with scalings[6], only
+ * scalings[k][2] is read.  colnde_describe reports member_loss=scalings|columns|scalings+columns while one is set; without one there is no such key and the line is what it was.  The shared-scalings calls above ignore a member loss
+ * that has been set.  With per-member scalings alone, row k is bit for bit the row of the shared call given scalings[k]; all-ones weights give the bits
+ * of column_weights = NULL.  The judge (colnde_ensemble_column_loss_dev, colnde_ensemble_profile) stays unweighted. */
+int colnde_ensemble_set_member_loss(colnde_handle* h, const float* scalings /* host [K][6], or NULL */, const float* column_weights /* host [K][n_col], or NULL */);
+/* colnde_ensemble_loss_dev / _loss_grad_dev / _loss_grad under the member loss that was set (refused when none is): the same layouts */
+int colnde_ensemble_member_loss_dev(colnde_handle* h, const float* d_weights, float* d_out8 /* [K][8] */);
+int colnde_ensemble_member_loss_grad_dev(colnde_handle* h, const float* d_weights, float* d_out /* [K][n_params + 8] */);
+int colnde_ensemble_member_loss_grad(colnde_handle* h, const float* weights, float* out);
 /* Flux.Optimise.ADAM (as colnde_adam_step_dev; NDE_training.jl:340-372) for every model: d_weights, d_m, d_v [K][n_params], the gradient read as the first
  * n_params floats of each [n_params + 8] row of d_result (the buffer of colnde_ensemble_loss_grad_dev), d_eta [K] per-model rates (train_NDE_args.jl:143) */
 int colnde_ensemble_adam_step_dev(colnde_handle* h, float* d_weights, const float* d_result, float* d_m, float* d_v, const float* d_eta,

@@ -582,6 +582,28 @@ ensemble_loss_dev!(h::Handle, dθ::Ptr{Float32}, sc::Vector{Float32}, dout::Ptr{
 ensemble_loss_grad_dev!(h::Handle, dθ::Ptr{Float32}, sc::Vector{Float32}, dout::Ptr{Float32}) =
     check(ccall((:colnde_ensemble_loss_grad_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, sc, dout))
 
+"""The member loss (colnde_ensemble_set_member_loss): member k is differentiated under Σ_q s[q, k] Σ_c w[c, k] (term q of column c) / Σ_c w[c, k] —
+`determine_loss_scalings` per run (wind_mixing/src/NDE_training.jl:256-288, loss.jl:11-31) and the run's own training simulations
+(train_free_convection_nde.jl:60-66).  scalings 6 x K or `nothing` (every scaling 1), column_weights n_columns x K or `nothing` (every column 1);
+both `nothing` clears it."""
+function set_member_loss!(h::Handle, scalings::Union{Nothing,AbstractMatrix}, column_weights::Union{Nothing,AbstractMatrix})
+    sc = scalings === nothing ? Ptr{Float32}(C_NULL) : Matrix{Float32}(scalings)
+    cw = column_weights === nothing ? Ptr{Float32}(C_NULL) : Matrix{Float32}(column_weights)
+    check(ccall((:colnde_ensemble_set_member_loss, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, sc, cw))
+    h
+end
+"the loss of every model under the member loss that was set: device pointers, [8] per model (handle's stream, not synchronised)"
+member_loss!(h::Handle, dθ::Ptr{Float32}, dout::Ptr{Float32}) =
+    check(ccall((:colnde_ensemble_member_loss_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, dout))
+"∇loss of every model under the member loss that was set: device pointers ([n_params + 8] per model), or host weights n_params x K -> (n_params + 8) x K"
+member_loss_grad!(h::Handle, dθ::Ptr{Float32}, dout::Ptr{Float32}) =
+    check(ccall((:colnde_ensemble_member_loss_grad_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, dout))
+function member_loss_grad!(h::Handle, weights::AbstractMatrix{Float32})
+    out = zeros(Float32, h.n_params + 8, size(weights, 2))
+    check(ccall((:colnde_ensemble_member_loss_grad, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, Matrix{Float32}(weights), out))
+    out
+end
+
 "ADAM for every model on device pointers: θ, m, v n_params x K, the gradient read from the loss-gradient result, η one rate per model (device)"
 function ensemble_adam_step!(h::Handle, dθ::Ptr{Float32}, dresult::Ptr{Float32}, dm::Ptr{Float32}, dv::Ptr{Float32}, dη::Ptr{Float32}, β, ϵ, βᵗ)
     check(ccall((:colnde_ensemble_adam_step_dev, libcolnde), Cint,
