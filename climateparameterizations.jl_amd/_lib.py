@@ -87,6 +87,7 @@ SYMBOLS = [
     ("colnde_plan", ctypes.c_int, [_V, ctypes.POINTER(ctypes.c_int)]),
     ("colnde_describe", ctypes.c_int, [_V, ctypes.c_char_p, ctypes.c_int]),
     ("colnde_create_ensemble", ctypes.c_int, [_V, ctypes.c_int, _V, ctypes.POINTER(_V)]),
+    ("colnde_create_tile_ensemble", ctypes.c_int, [_V, ctypes.c_int, _V, ctypes.POINTER(_V)]),
     ("colnde_n_models", ctypes.c_int, [_V]),
     ("colnde_ensemble_set_physics", ctypes.c_int, [_V, _V]),
     ("colnde_ensemble_forward_dev", ctypes.c_int, [_V, _V, _V]),

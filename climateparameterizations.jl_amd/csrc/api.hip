@@ -263,7 +263,7 @@ static void build_tables(const DevModel& m, std::vector<TileDesc>* tiles, std::v
 
 // cfg.matrix_arithmetic, per kernel family; COLNDE_FWD_SPLIT / COLNDE_ADJ_SPLIT / COLNDE_DW_SPLIT = 0 | 1 override one family each (test aid:
 // isolates one kernel's arithmetic against the others').  Read here only — at creation and in colnde_set_matrix_arithmetic — never per call.
-static void resolve_arithmetic(colnde_handle* h) {
+void resolve_arithmetic(colnde_handle* h) {
     const bool split = h->cfg.matrix_arithmetic == COLNDE_MATRIX_BF16X3_EXACT;
     h->sp_fwd = env_int(ENV_FWD_SPLIT, split) != 0;
     h->sp_adj = env_int(ENV_ADJ_SPLIT, split) != 0;
@@ -1143,6 +1143,7 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
     if (!h->sched.empty()) { snprintf(t, sizeof t, " schedule=%d/%d intervals", total_steps(h), h->cfg.n_save - 1); s += t; }
     if (h->conv.c) { snprintf(t, sizeof t, " conv=%d n_params=%d", h->conv.c, h->conv.n_params); s += t; }
     if (h->ensemble) { snprintf(t, sizeof t, " models=%d tape_bytes_per_model=%zu", h->n_models, h->ens_model_bytes); s += t; }
+    if (h->tile_ens) s += " tile_ensemble=1";      // colnde_create_tile_ensemble: tile16's own kernels; the bytes per model count images and activation rows too
     // a member loss that is set (colnde_ensemble_set_member_loss): scalings | columns | scalings+columns; without one the line is what it was (none)
     if (h->ensemble && (h->ml_scalings || h->ml_columns)) { snprintf(t, sizeof t, " member_loss=%s", member_loss_kind(h->ml_scalings, h->ml_columns)); s += t; }
     if (h->cfg.stepper == COLNDE_STEPPER_RKC2) { snprintf(t, sizeof t, " rkc_stages=%d%s", h->m.nst, h->cfg.rkc_stages ? "" : "(automatic)"); s += t; }
@@ -1151,7 +1152,7 @@ extern "C" int colnde_describe(const colnde_handle* h, char* buf, int capacity) 
     s += t;
     if (wm_infer_covers(h)) s += " wm_infer=f32";      // colnde_wm_infer_dz_flux / colnde_wm_embedded_step[_flux] / colnde_wm_diagnose_flux: the f32 matrix pipe under either arithmetic
     if (wm_generic_serves(h)) s += " wm_embed=generic_f32";      // colnde_ensemble_wm_embedded with this single handle as K = 1: engine_wm_embed_any.hip, likewise
-    if (h->ensemble && !h->use_fc) s += " wm_profile=f32";      // colnde_ensemble_profile: likewise
+    if (h->ensemble && !h->use_fc && !h->tile_ens) s += " wm_profile=f32";      // colnde_ensemble_profile: likewise
     if (!h->conv.c && fce_covers(h)) s += " fc_embed=f32";      // colnde_fc_embedded_step / colnde_fc_diagnose_wT: likewise
     if (info[1]) { snprintf(t, sizeof t, " block=%dx%d", info[1], info[2]); s += t; } else s += " block=(not planned yet)";
     if (info[0] == COLNDE_ENGINE_MFMA) { snprintf(t, sizeof t, " z1_tape=%d", info[3]); s += t; }

@@ -520,6 +520,7 @@ extern "C" int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_
                                                const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt,
                                                const float* params, int convective_adjustment, float* d_dz_uw, float* d_dz_vw, float* d_dz_wT,
                                                float* d_u_out, float* d_v_out, float* d_T_out, float* d_uw, float* d_vw, float* d_wT, int n_columns) {
+    NOT_A_TILE_ENSEMBLE(h);
     WmCall c = wm_call(d_weights, d_u, d_v, d_T, d_top_flux, Lz, n_columns);
     wm_physics(&c, d_halo_bottom, d_halo_top, dt, params, convective_adjustment);
     wm_dz_group(&c, d_dz_uw, d_dz_vw, d_dz_wT);
@@ -535,6 +536,7 @@ extern "C" int colnde_ensemble_wm_embedded(colnde_handle* h, const float* weight
                                            const float* halo_bottom, const float* halo_top, float Lz, float dt, const float* params, int convective_adjustment,
                                            float* dz_uw, float* dz_vw, float* dz_wT, float* u_out, float* v_out, float* T_out, float* uw, float* vw, float* wT,
                                            int n_columns) {
+    NOT_A_TILE_ENSEMBLE(h);
     WmCall c = wm_call(weights, u, v, T, top_flux, Lz, n_columns);
     wm_physics(&c, halo_bottom, halo_top, dt, params, convective_adjustment);
     wm_dz_group(&c, dz_uw, dz_vw, dz_wT);

@@ -47,6 +47,8 @@ static int ens_upload_physics(colnde_handle* h, const float* physics) {
     for (int k = 0; k < h->n_models; k++) {
         const colnde_config c = model_config(&h->cfg, physics, k);
         ph[k] = closure_constants(c.nu0, c.nu_minus, c.dRi, c.Ric, c.Pr);
+        // tile16's physics also reads dRi and Pr themselves (build_model: m->dRi = c->dRi, m->Pr = c->Pr): a tile ensemble's table carries them in the pads
+        if (h->tile_ens) { ph[k].pad0 = c.dRi; ph[k].pad1 = c.Pr; }
     }
     // (kernels in flight on the stream may still read the previous table: the copy is ordered on the stream and completed before returning)
     HIPCHK(hipMemcpyAsync(h->d_phys, ph.data(), ph.size() * sizeof(RtPhys), hipMemcpyHostToDevice, h->stream));
@@ -174,6 +176,221 @@ extern "C" int colnde_create_ensemble(const colnde_config* cfg, int n_models, co
         return fail("allocating the ensemble's per-model buffers (%d models) failed", n_models);
     }
     if (ens_upload_physics(h, physics) || ens_plan_tapes(h)) { colnde_destroy(h); return 1; }
+    *out = h;
+    return 0;
+}
+
+// ---- tile ensembles (colnde_create_tile_ensemble): K wind-mixing models of ANY tile16 architecture side by side ------------------------------------
+// The reference's wide nets (wind_mixing/train_NDE.jl:97-102, train_NDE_args.jl:150-166: 96-400-400-31, 96-32-400-31, 96-400-31) are swept like the small
+// one, one model per process at 8-18 simulations: one 16-column workgroup each.  Here tile16's own kernels carry the model index in blockIdx.y
+// (pack_weights_ens_kernel, pack_planes_ens_kernel, forward_ens_kernel, adjoint_ens_kernel; T16Ens strides); the dW GEMM, the loss and gradient
+// reductions and the ADAM step already do.  The launch geometry — weights in LDS or streamed, rows in LDS or in global memory, the taped adjoint's
+// form, the dW slice count — is decided from ONE model's tiles, so that row k of every result is, bit for bit, what a colnde_create handle with
+// engine GENERIC computes for model k's weights and constants.
+
+// Decided from the configuration and the environment alone, before any device work
+static int tile_ens_refusals(const colnde_config* cfg, int n_models, const float* physics) {
+    const size_t lds_cap = 160 * 1024;
+    if (n_models < 1 || n_models > 65535) return fail("n_models = %d outside 1..65535", n_models);
+    if (cfg->model != COLNDE_MODEL_WIND_MIXING)
+        return fail("colnde_create_tile_ensemble covers the wind-mixing NDE: the free-convection models train side by side through colnde_create_fc_ensemble");
+    if (cfg->inplace_variant) return fail("tile ensembles train on the training RHS: inplace_variant (the NDE! evaluation RHS) is not supported");
+    if (cfg->engine != COLNDE_ENGINE_AUTO && cfg->engine != COLNDE_ENGINE_GENERIC)
+        return fail("tile ensembles run the tile16 kernels (engine AUTO or GENERIC): engine forced to %d is not supported (regtile and fc32 have no such entry points)", cfg->engine);
+    if (cfg->substeps == 0)
+        return fail("substeps = 0 (chosen from reltol by the first solve) is not supported: the models share one sub-step count, and the tapes are sized at "
+                    "creation — choose it with a single handle (colnde_choose_substeps) and pass it");
+    if (cfg->n_columns > 4096)
+        return fail("%d columns per model: tile ensembles cover at most 4,096 columns per model (256 tiles: the regime of the 1,024-thread kernels a single handle "
+                    "runs there); above it one handle per model", cfg->n_columns);
+    for (EnvSwitch sw : {ENV_T16_DWTAPE, ENV_T16_ZTAPE}) {
+        const char* e = env_get(sw);
+        if (e && atoi(e) == 0) return fail("%s=0 leaves no delta / pre-activation tape: tile ensembles run the taped adjoint only and refuse it", env_name(sw));
+    }
+    if (env_get(ENV_T16_BLOCK)) return fail("COLNDE_T16_BLOCK: tile ensembles hold one block of columns per model (the column-block loop has no model index)");
+    {
+        const char* e = env_get(ENV_T16_TAPE_THREADS);
+        if (e && atoi(e) != 1024) return fail("COLNDE_T16_TAPE_THREADS=%s selects the 512-thread taped adjoint, which has no model index: tile ensembles refuse it", e);
+        e = env_get(ENV_T16_FWD_SPLIT);
+        if (e && atoi(e) != 0) return fail("COLNDE_T16_FWD_SPLIT=%s selects the net-split kernels: tile ensembles run tile16's own (colnde_create_ensemble runs those)", e);
+    }
+    if (physics && !cfg->modified_pacanowski_philander)
+        return fail("a physics array needs modified_pacanowski_philander = 1: without the Richardson-number closure the five constants are unused (pass NULL)");
+    DevModel dm;
+    PackInfo pk;
+    build_model(cfg, &dm, &pk);
+    const size_t lds_fwd = lds_floats_forward(dm) * sizeof(float), lds_fwd_ag = lds_floats_forward_ag(dm) * sizeof(float);
+    const bool ag_rows = lds_fwd > lds_cap;
+    if (ag_rows && lds_fwd_ag > lds_cap)
+        return fail("network too large for the tile engine: forward needs %zu B of LDS (> %zu), %zu B even with the activation rows in global memory", lds_fwd, lds_cap, lds_fwd_ag);
+    // the single handle's decision (tape_plan.h) on a card with room for everything: what remains is whether the taped adjoint can run this network at all
+    const size_t lds_ag = (MODEL_FLOATS + lds_floats_adjoint_ag(dm)) * sizeof(float);
+    const T16Tapes plan = plan_t16_tapes({(cfg->n_columns + CT - 1) / CT * CT, CT, dm.ns, dm.n_bias, ag_rows, false, (MODEL_FLOATS + lds_floats_adjoint(dm)) * sizeof(float),
+                                          (MODEL_FLOATS + lds_floats_adjoint_noA(dm)) * sizeof(float), lds_ag, 1, 1, (size_t)1 << 40, FLAG_UNSET, FLAG_UNSET, FLAG_OFF, 0});
+    if (plan.status == T16_PLAN_REFUSED_TOO_LARGE)
+        return fail("network too large for the taped adjoint with rows in global memory (%d biases, %zu B of LDS): no gradient path, no tile ensemble", dm.n_bias, lds_ag);
+    if (plan.status != T16_PLAN_TAPED)
+        return fail("the taped adjoint cannot run this network (16 x %d state values per tile against 3,072, or %zu B of LDS without the activation array against %zu): "
+                    "tile ensembles have no in-register adjoint", dm.ns, (MODEL_FLOATS + lds_floats_adjoint_noA(dm)) * sizeof(float), lds_cap);
+    if (CT * dm.ns > 2 * 1024 || dm.n_bias > 4 * 1024)
+        return fail("Nz = %d (%d biases): tile ensembles run the 1,024-thread taped adjoint, which holds 16 x ns <= 2,048 state values and 4,096 biases per tile; a "
+                    "single handle runs this network on the 512-thread kernels, which have no model index", cfg->Nz, dm.n_bias);
+    return 0;
+}
+
+// the K models' weight images (and, with the rows in global memory under the split arithmetic, plane images) in one launch each
+static int tile_ens_pack(colnde_handle* h, const float* d_weights, const T16Ens& en) {
+    hipError_t e = launch_pack_ens(h->m, h->pk, d_weights, h->d_wf, h->d_wb, en, h->stream);
+    if (e != hipSuccess) return fail("tile ensemble pack_weights launch failed: %s", hipGetErrorString(e));
+    if (h->d_sf && (h->m.sf || h->m.sb)) {
+        e = launch_pack_planes_ens(h->m, d_weights, h->d_sf, h->d_sb, en, h->stream);
+        if (e != hipSuccess) return fail("tile ensemble pack_planes launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+static T16Ens tile_ens_strides(const colnde_handle* h) {
+    T16Ens en = h->tens;
+    en.phys = h->d_phys;
+    en.slab = h->ens.slab;            // (follows the dW slice count: dw_slab_rows, replan_dw_slices)
+    return en;
+}
+
+static int tile_ens_forward(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape) {
+    const T16Ens en = tile_ens_strides(h);
+    // every (model, tile) workgroup its own rows of m.ag: K x tiles slabs, sized and zero-filled at creation
+    if (h->ag_rows && h->ag_tiles < (size_t)h->n_models * h->n_tiles) return fail("the activation rows hold %zu tiles, the ensemble needs %zu", h->ag_tiles, (size_t)h->n_models * h->n_tiles);
+    if (tile_ens_pack(h, d_weights, en)) return 1;
+    Timed tm(h, K_FORWARD);
+    const hipError_t e = launch_forward_ens(h->m, h->pk, d_weights, h->d_wf, h->d_x0, h->d_bcs, h->d_times, h->cfg.n_save, h->cfg.substeps, d_sol,
+                                            with_tape ? h->d_tape : nullptr, h->n_col, h->fwd_threads, h->fwd_wlds, h->lds_fwd_solve, en, h->stream,
+                                            with_tape ? h->d_t16_ztape : nullptr);
+    if (e != hipSuccess) return fail("tile ensemble forward launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+static size_t tile_ens_adjoint_lds(const colnde_handle* h) {
+    return (MODEL_FLOATS + (h->ag_rows ? lds_floats_adjoint_ag(h->m) : lds_floats_adjoint_noA(h->m))) * sizeof(float);
+}
+
+static int tile_ens_loss_grad(colnde_handle* h, const float* d_weights, const float* scalings, float* d_out) {
+    const int K = h->n_models, stride = h->m.n_params + 8;
+    LossWeights lw;
+    loss_weights(h, scalings, &lw);
+    HIPCHK(hipMemsetAsync(h->d_slab, 0, (size_t)K * h->ens.slab * sizeof(float), h->stream));
+    if (tile_ens_forward(h, d_weights, h->d_sol, true)) return 1;
+    const T16Ens en = tile_ens_strides(h);
+    hipError_t e;
+    {
+        Timed tm(h, K_ADJOINT);
+        e = launch_adjoint_ens(h->m, h->pk, d_weights, h->d_wf, h->d_wb, h->d_bias_zoff, h->d_bias_goff, h->d_bcs, h->d_times, h->cfg.n_save, h->cfg.substeps, h->d_sol,
+                               h->d_truth, h->d_tape, lw, h->d_slab, h->n_col, tile_ens_adjoint_lds(h), en, h->stream, h->d_dwtape, h->d_t16_ztape);
+        if (e != hipSuccess) return fail("tile ensemble adjoint launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        Timed tm(h, K_DW1);
+        e = dw_launch(h, (size_t)h->n_tiles * total_steps(h) * h->m.nst, h->d_slab + (size_t)h->n_tiles * stride, K, en.dwtape, en.slab);
+        if (e != hipSuccess) return fail("tile ensemble dW GEMM launch failed: %s", hipGetErrorString(e));
+    }
+    {
+        Timed tm(h, K_REDUCE);
+        e = launch_reduce(h->d_slab, h->blk.rows, h->m.n_params, stride, lw, d_out, h->stream, K, en.slab, stride);
+        if (e != hipSuccess) return fail("tile ensemble reduce launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// One block of all columns per model, planned once at creation (tape_plan.h: plan_t16_tile_ens); the dW slice count is the one a single handle of this
+// size plans (build_dw_plan): the same reduction order, and with it the bits
+static int tile_ens_plan_tapes(colnde_handle* h) {
+    const DevModel& m = h->m;
+    const int K = h->n_models, n_steps = total_steps(h);
+    const size_t n_rec = (size_t)h->n_tiles * n_steps * m.nst;
+    h->blk.block = h->n_tiles * CT;
+    h->blk.nblocks = 1;
+    build_dw_plan(h, n_rec);                                 // (and h->blk.rows, ens.slab)
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t img = ((size_t)h->pk.pf_net + h->pk.pb_net) * m.n_nets, planes = h->ag_rows ? ((size_t)m.sf_net + m.sb_net) * m.n_nets * 4 : 0;
+    const T16TileEns plan = plan_t16_tile_ens({K, h->n_tiles, n_steps, m.nst, m.ns, m.n_params, h->n_col, h->cfg.n_save, h->blk.rows, dwtape_row_floats(m),
+                                               t16_ztape_col_floats(m), img, planes, h->ag_rows ? ag_floats_per_tile(m) : 0, free_b});
+    if (plan.refused)
+        return fail("a tile ensemble of %d models needs %zu bytes of device memory for its tapes, slab rows, solutions, weight images and activation rows (%zu per "
+                    "model: %d substeps x %d stages x %d save intervals); %zu bytes are free (3 GB kept in reserve, %zu per model): use fewer models per handle",
+                    K, (size_t)K * plan.bytes_per_model, plan.bytes_per_model, h->cfg.substeps, m.nst, h->cfg.n_save - 1, free_b, plan.share);
+    const size_t mark = h->mem.mark();
+    int at = 0;
+    hipError_t e = t16_alloc_tapes(h, (size_t)K, n_rec, &at);
+    if (e == hipSuccess) e = t16_alloc_ztape(h, (size_t)K, n_rec, false);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h->mem.rollback(mark);
+        return fail("allocating the tile ensemble's tapes (%zu bytes, %zu per model) failed: %s", (size_t)K * plan.bytes_per_model, plan.bytes_per_model, hipGetErrorString(e));
+    }
+    h->t16_dwtape = 1;
+    h->tens.tape = n_rec * CT * m.ns;
+    h->tens.dwtape = n_rec * CT * dwtape_row_floats(m);
+    h->tens.ztape = n_rec * CT * t16_ztape_col_floats(m);
+    h->ens_model_bytes = plan.bytes_per_model;
+    return 0;
+}
+
+extern "C" int colnde_create_tile_ensemble(const colnde_config* cfg, int n_models, const float* physics, colnde_handle** out) {
+    if (!out) return fail("null out pointer");
+    *out = nullptr;
+    if (validate(cfg)) return 1;
+    if (tile_ens_refusals(cfg, n_models, physics)) return 1;
+    int min_sub = 1, stages = 0;
+    if (ens_stability(cfg, n_models, physics, &min_sub, &stages)) return 1;
+    // tile16's own kernels, as a single handle runs them under engine GENERIC (AUTO would send the 96-50-20-31 shape to the net-split pair)
+    colnde_config c = *cfg;
+    c.engine = COLNDE_ENGINE_GENERIC;
+    colnde_handle* h = nullptr;
+    if (colnde_create(&c, &h)) return 1;
+    const size_t lds_cap = 160 * 1024;
+    if (h->use_rt || h->use_fc || h->fwd_split || h->adj_split || !forward_ens_has(h->fwd_wlds, h->fwd_threads, h->ag_rows)) {
+        const int th = h->fwd_threads, wl = h->fwd_wlds;
+        colnde_destroy(h);
+        return fail("this configuration's forward solve (weights in LDS: %d, %d threads; COLNDE_FWD_WLDS / COLNDE_FWD_THREADS) has no tile-ensemble entry point", wl, th);
+    }
+    if (h->lds_fwd_solve + t16_ens_forward_lds_extra() > lds_cap || !adjoint_ens_has(h->m, h->n_tiles, tile_ens_adjoint_lds(h))) {
+        const size_t need = h->lds_fwd_solve + t16_ens_forward_lds_extra();
+        colnde_destroy(h);
+        return fail("the ensemble kernels keep the model description in LDS beside the tile: %zu B against %zu (or the taped adjoint of this network has no 1,024-thread "
+                    "form): one handle per model", need, lds_cap);
+    }
+    h->ensemble = true;
+    h->tile_ens = true;
+    h->n_models = n_models;
+    h->min_substeps = min_sub;
+    if (stages > 0 && stages != h->m.nst) {
+        h->ens_rkc_stages = stages;
+        if (refresh_rkc(h)) { colnde_destroy(h); return 1; }
+    } else if (stages > 0) {
+        h->ens_rkc_stages = stages;
+    }
+    const size_t K = (size_t)n_models, P = (size_t)h->m.n_params;
+    T16Ens& en = h->tens;
+    en.n_models = n_models;
+    en.w = P;
+    en.wf = (size_t)h->pk.pf_net * h->m.n_nets;
+    en.wb = (size_t)h->pk.pb_net * h->m.n_nets;
+    en.sf = h->ag_rows ? (size_t)h->m.sf_net * h->m.n_nets * 4 : 0;
+    en.sb = h->ag_rows ? (size_t)h->m.sb_net * h->m.n_nets * 4 : 0;
+    en.sol = (size_t)h->n_col * h->cfg.n_save * h->m.ns;
+    h->ens.sol = en.sol;
+    h->ens.n_models = n_models;
+    DevPool& mem = h->mem;
+    if (mem.resize(&h->d_w, K * P) || mem.resize(&h->d_out, K * (P + 8)) || mem.resize(&h->d_partial, K * 256 * 8) || mem.resize(&h->d_sol, K * en.sol) ||
+        mem.resize(&h->d_wf, K * en.wf) || mem.resize(&h->d_wb, K * en.wb) || mem.alloc(&h->d_phys, K) ||
+        (h->ag_rows && (mem.resize(&h->d_sf, K * en.sf) || mem.resize(&h->d_sb, K * en.sb)))) {
+        colnde_destroy(h);
+        return fail("allocating the tile ensemble's per-model buffers (%d models) failed", n_models);
+    }
+    resolve_arithmetic(h);                                   // (m.sf / m.sb: the plane images just re-allocated)
+    // K x tiles slabs of activation rows, zero-filled in stream order: no two (model, tile) workgroups share one
+    if (ensure_ag(h, K * (size_t)h->n_tiles)) { colnde_destroy(h); return 1; }
+    if (ens_upload_physics(h, physics) || tile_ens_plan_tapes(h)) { colnde_destroy(h); return 1; }
     *out = h;
     return 0;
 }
@@ -410,6 +627,7 @@ static int ens_forward(colnde_handle* h, const float* d_weights, float* d_sol, b
     if (!h->have_problem) return fail("colnde_set_problem has not been called");
     if (check_stability(h)) return 1;
     if (h->use_fc) return fc_pack(h, d_weights) ? 1 : fc_forward_range(h, d_sol, false, 0, h->n_col);
+    if (h->tile_ens) return tile_ens_forward(h, d_weights, d_sol, with_tape);
     RtEns ens = h->ens;
     ens.sol = (size_t)h->n_col * h->cfg.n_save * h->m.ns;
     Timed tm(h, K_FORWARD);
@@ -436,6 +654,7 @@ extern "C" int colnde_ensemble_forward_dev(colnde_handle* h, const float* d_weig
 // K x n_col weights (ones where none were given) live in two buffers of the handle's pool, uploaded in stream order and complete on return, as
 // colnde_set_schedule uploads its counts.  The shared-scalings entry points never read them.
 extern "C" int colnde_ensemble_set_member_loss(colnde_handle* h, const float* scalings, const float* column_weights) {
+    NOT_A_TILE_ENSEMBLE(h);               // (tile16's adjoint has no column-weight path)
     if (ensemble_only(h)) return 1;
     if (!scalings && !column_weights) {           // clears it (the buffers stay with the handle)
         h->ml_scalings = h->ml_columns = false;
@@ -519,6 +738,11 @@ static int ens_loss_grad(colnde_handle* h, const float* d_weights, const float* 
         if (!h->have_problem) return fail("colnde_set_problem has not been called");
         return check_stability(h) ? 1 : fc_loss_grad(h, d_weights, scalings, d_out);
     }
+    if (h->tile_ens) {               // tile16's own kernels with the models' strides (the member loss is refused before this point)
+        if (!h->have_problem) return fail("colnde_set_problem has not been called");
+        if (!scalings) return fail("a tile ensemble has no member loss");
+        return check_stability(h) ? 1 : tile_ens_loss_grad(h, d_weights, scalings, d_out);
+    }
     const int K = h->n_models, stride = h->m.n_params + 8;
     LossWeights lw = {};
     if (scalings) loss_weights(h, scalings, &lw);
@@ -576,18 +800,21 @@ extern "C" int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights,
 }
 
 extern "C" int colnde_ensemble_member_loss_dev(colnde_handle* h, const float* d_weights, float* d_out8) {
+    NOT_A_TILE_ENSEMBLE(h);
     if (member_loss_only(h, __func__)) return 1;
     if (!d_weights || !d_out8) return fail("null pointer argument");
     return ens_loss(h, d_weights, nullptr, d_out8);
 }
 
 extern "C" int colnde_ensemble_member_loss_grad_dev(colnde_handle* h, const float* d_weights, float* d_out) {
+    NOT_A_TILE_ENSEMBLE(h);
     if (member_loss_only(h, __func__)) return 1;
     if (!d_weights || !d_out) return fail("null pointer argument");
     return ens_loss_grad(h, d_weights, nullptr, d_out);
 }
 
 extern "C" int colnde_ensemble_member_loss_grad(colnde_handle* h, const float* weights, float* out) {
+    NOT_A_TILE_ENSEMBLE(h);
     if (member_loss_only(h, __func__)) return 1;
     if (!weights || !out) return fail("null pointer argument");
     return ens_loss_grad_host(h, weights, nullptr, out);
@@ -657,6 +884,7 @@ extern "C" int colnde_ensemble_pretrain_wm_flux_dev(colnde_handle* h, int nets, 
                                                     const float* d_bcs, const float* d_flux, const int32_t* d_order, int n_samples, float gradient_scaling,
                                                     const float* d_eta, float beta1, float beta2, float eps, double beta_t[2], int update, float* mean_loss) {
     if (!h) return fail("%s: null handle", __func__);
+    NOT_A_TILE_ENSEMBLE(h);
     if (h->closure) return fail("%s takes the weight vectors of a wind-mixing ensemble, but this is a closure handle (no networks)", __func__);
     if (!h->ensemble)
         return fail("%s takes the handles of colnde_create_ensemble (K = 1 for one model): this is a single-model handle "

@@ -50,6 +50,7 @@ FcConv fc_conv_args(const colnde_handle* h);
 FcConvEns fc_conv_ens_args(const colnde_handle* h);
 int ensure_tmp(colnde_handle* h, size_t n_columns);
 int ensure_ag(colnde_handle* h, size_t tiles);
+void resolve_arithmetic(colnde_handle* h);
 void drain_events(colnde_handle* h);
 int forward_impl(colnde_handle* h, const float* d_weights, float* d_sol, bool with_tape);
 int rt_forward_range(colnde_handle* h, float* d_sol, bool with_tape, int c0, int nc);
@@ -95,6 +96,14 @@ bool fce_covers(const colnde_handle* h);
         if ((h) && (h)->conv.c)                                                                                                           \
             return fail("%s does not cover the convolutional first layer of a colnde_create_conv handle (conv=%d): conv handles solve, "  \
                         "differentiate and train (forward, loss, loss_grad, loss_per_tstep, adam_step)", __func__, (h)->conv.c);          \
+    } while (0)
+
+// Entry points whose kernels read a 96-50-20-31 image or a net-split tape refuse a tile ensemble (colnde_create_tile_ensemble), naming themselves
+#define NOT_A_TILE_ENSEMBLE(h)                                                                                                            \
+    do {                                                                                                                                  \
+        if ((h) && (h)->tile_ens)                                                                                                         \
+            return fail("%s does not serve a tile ensemble (colnde_create_tile_ensemble, %d models on the tile16 kernels): its kernels read the "  \
+                        "net-split weight image and tapes of colnde_create_ensemble", __func__, (h)->n_models);                           \
     } while (0)
 
 #define HIPCHK(expr)                                                                              \
@@ -274,6 +283,8 @@ struct colnde_handle {
     std::vector<MppParams> wm_ens_mpp_host;
     RtPhys* d_prof_phys = nullptr;  // colnde_ensemble_profile: the closure constants of a call that overrides the handle's (physics != NULL)
     RtEns ens;                      // per-model strides of the buffers a model owns
+    bool tile_ens = false;          // colnde_create_tile_ensemble: the K models run tile16's own kernels (any architecture), at the strides of ...
+    T16Ens tens;
     FcEns fens;                     // ... of a free-convection ensemble (colnde_create_fc_ensemble): the fc32 kernels' strides
     size_t ens_model_bytes = 0;     // device bytes per model (tapes, slab rows, solution, weight image)
     int ens_rkc_stages = 0;         // RKC2, automatic stage count: the largest any model needs (refresh_rkc)

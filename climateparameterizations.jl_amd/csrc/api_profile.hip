@@ -45,6 +45,7 @@ static int profile_grid_cap() {
 
 extern "C" int colnde_ensemble_profile_dev(colnde_handle* h, const float* d_weights, const float* d_sol, const float* physics, float* d_uw, float* d_vw,
                                            float* d_wT, float* d_Ri, float* d_losses) {
+    NOT_A_TILE_ENSEMBLE(h);
     if (profile_check(h, __func__, d_weights, d_sol, physics, d_uw, d_vw, d_wT, d_Ri, d_losses, false)) return 1;
     HIPCHK(hipSetDevice(h->device));
     const int K = h->n_models;
@@ -83,6 +84,7 @@ extern "C" int colnde_ensemble_profile_dev(colnde_handle* h, const float* d_weig
 
 extern "C" int colnde_ensemble_profile(colnde_handle* h, const float* weights, const float* sol, const float* physics, float* uw, float* vw, float* wT,
                                        float* Ri, float* losses) {
+    NOT_A_TILE_ENSEMBLE(h);
     if (profile_check(h, __func__, weights, sol, physics, uw, vw, wT, Ri, losses, true)) return 1;
     HIPCHK(hipSetDevice(h->device));
     const size_t K = (size_t)h->n_models, states = (size_t)h->n_col * h->cfg.n_save;

@@ -234,6 +234,7 @@ static int upload_schedule(colnde_handle* h, const int* counts) {
 // them; an ensemble's, planned at creation, are planned again — and outside each interval's stability bound.  Clears a pending substeps = 0.
 extern "C" int colnde_set_schedule(colnde_handle* h, const int* counts) {
     if (!h) return fail("null handle");
+    NOT_A_TILE_ENSEMBLE(h);
     const int n_iv = h->cfg.n_save - 1;
     const char* planned = "the step schedule sizes the tapes: set it before the first colnde_loss_grad of this handle";
     if (!counts) {

@@ -53,6 +53,34 @@ hipError_t launch_adjoint(const DevModel& m, const PackInfo& pk, const float* w,
                           const float* save_times, int n_save, int substeps, const float* sol, const float* truth,
                           const float* tape, const LossWeights& lw, float* slab, int n_col, const AdjointGeom& geo,
                           size_t lds_bytes, hipStream_t stream, float* dwtape = nullptr, const float* ztape = nullptr);
+// ---- tile ensembles (colnde_create_tile_ensemble): K models of one architecture, the model index in blockIdx.y ------------------------------------
+// What a model owns lies these strides apart (floats; sf / sb: 32-bit words; ag: floats per model = tiles x ag_floats_per_tile); x0, bcs, truth,
+// the save times and the RKC table are shared.  phys: [n_models] closure constants with dRi and Pr in the two pad floats (tile16's pullback reads
+// them), filled by the host expression a single handle uses.
+struct RtPhys;
+struct T16Ens {
+    const RtPhys* phys = nullptr;
+    size_t w = 0, wf = 0, wb = 0, sf = 0, sb = 0, sol = 0, tape = 0, ztape = 0, dwtape = 0, slab = 0;
+    int n_models = 1;
+};
+// The ensemble kernels keep the model description (with model k's constants patched in) at the head of their LDS: the forward kernel's bytes grow by this
+static inline size_t t16_ens_forward_lds_extra() { return (size_t)MODEL_FLOATS * sizeof(float); }
+hipError_t launch_pack_ens(const DevModel& m, const PackInfo& pk, const float* w, float* wf, float* wb, const T16Ens& en, hipStream_t stream);
+hipError_t launch_pack_planes_ens(const DevModel& m, const float* w, unsigned* sf, unsigned* sb, const T16Ens& en, hipStream_t stream);
+// true when an ensemble entry point exists for this forward geometry (weights in LDS at 1,024 threads; weights streamed at 256, or at 1,024 with rows in global memory)
+bool forward_ens_has(bool wlds, int nthreads, bool ag);
+// lds_bytes: the single handle's (the launcher adds t16_ens_forward_lds_extra); the grid is (tiles of n_col, n_models): the geometry of ONE model's columns
+hipError_t launch_forward_ens(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* x0, const float* bcs,
+                              const float* save_times, int n_save, int substeps, float* sol, float* tape, int n_col, int nthreads, bool wlds,
+                              size_t lds_bytes, const T16Ens& en, hipStream_t stream, float* ztape);
+// ... and for the taped adjoint of n_tiles tiles of ONE model (lds_bytes: as for launch_adjoint; m.ag says where the rows live)
+bool adjoint_ens_has(const DevModel& m, int n_tiles, size_t lds_bytes);
+// the taped-dW adjoint at 1,024 threads, the geometry launch_adjoint picks for one model's tiles (anything else: hipErrorInvalidValue)
+hipError_t launch_adjoint_ens(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* wb, const int* bias_zoff,
+                              const int* bias_goff, const float* bcs, const float* save_times, int n_save, int substeps, const float* sol,
+                              const float* truth, const float* tape, const LossWeights& lw, float* slab, int n_col, size_t lds_bytes,
+                              const T16Ens& en, hipStream_t stream, float* dwtape, const float* ztape);
+
 // hidden pre-activation tape of the taped-dW mode: floats per column
 static inline size_t t16_ztape_col_floats(const DevModel& m) { return (size_t)((m.n_nets * m.act_off[m.n_layers - 1] + 3) & ~3); }
 hipError_t launch_infer(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* T,

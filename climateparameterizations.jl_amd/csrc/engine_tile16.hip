@@ -19,6 +19,7 @@
 #include "colnde_dev.h"
 #include <cstdlib>
 #include "engine_tile16.h"
+#include "engine_netsplit.h"   // RtPhys: the per-model closure constants of an ensemble
 #include "kernel_select.h"
 #include "split_bf16.h"
 #include "pretrain_sample.h"
@@ -123,35 +124,21 @@ __device__ __forceinline__ f32x4 gemm_chain4(const float4* ap4, const float* bp,
 // ------------------------------------------------------------------------------------------------
 __global__ void pack_weights_kernel(DevModel m, PackInfo pk, const float* __restrict__ w, float* __restrict__ wf,
                                     float* __restrict__ wb) {
-    const int total_f = pk.pf_net * m.n_nets, total_b = pk.pb_net * m.n_nets;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total_f + total_b; idx += gridDim.x * blockDim.x) {
-        const bool fwd = idx < total_f;
-        int e = fwd ? idx : idx - total_f;
-        const int pn = fwd ? pk.pf_net : pk.pb_net;
-        const int net = e / pn;
-        e -= net * pn;
-        int l = 0;
-        while (l + 1 < m.n_layers && e >= (fwd ? pk.pf_off[l + 1] : pk.pb_off[l + 1])) l++;
-        e -= fwd ? pk.pf_off[l] : pk.pb_off[l];
-        const int ni = m.sizes[l], no = m.sizes[l + 1];
-        const int jj = e & 3, lane = (e >> 2) & 63;
-        const int blk = e >> 8;
-        const float* W = w + (size_t)net * m.net_size + m.w_off[l];
-        float v = 0.0f;
-        if (fwd) {
-            const int nS = (ni + 15) >> 4;
-            const int mt = blk / nS, S = blk - mt * nS;
-            const int i = mt * 16 + (lane & 15), k = 16 * S + 4 * (lane >> 4) + jj;
-            if (i < no && k < ni) v = W[(size_t)k * no + i];
-            wf[idx] = v;
-        } else {
-            const int nS = (no + 15) >> 4;
-            const int it = blk / nS, S = blk - it * nS;
-            const int i = it * 16 + (lane & 15), j = 16 * S + 4 * (lane >> 4) + jj;
-            if (i < ni && j < no) v = W[(size_t)i * no + j];
-            wb[idx - total_f] = v;
-        }
-    }
+#define T16_ENS 0
+#include "t16_pack_weights_body.inc"
+#undef T16_ENS
+}
+// Tile ensembles (colnde_create_tile_ensemble): the kernels below marked _ens carry the model index in blockIdx.y.  Each is the text of its single-model
+// twin (the t16_*_body.inc files, included by both, so that the single-model kernels stay the machine code they were) behind a preamble that moves
+// every pointer to what model blockIdx.y owns (T16Ens strides).
+__global__ void pack_weights_ens_kernel(DevModel m, PackInfo pk, const float* __restrict__ w, float* __restrict__ wf,
+                                        float* __restrict__ wb, T16Ens en) {
+    w += blockIdx.y * en.w;
+    wf += blockIdx.y * en.wf;
+    wb += blockIdx.y * en.wb;
+#define T16_ENS 1
+#include "t16_pack_weights_body.inc"
+#undef T16_ENS
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -298,42 +285,17 @@ __device__ __forceinline__ f32x4 t16_mfma_bf3(const Bf3& a, const Bf3& b, f32x4 
 #define T16_TG 5      // row tiles per wave and split (25 tiles of a 400-row layer: five jobs per net)
 
 __global__ void pack_planes_kernel(DevModel m, const float* __restrict__ w, unsigned* __restrict__ sf, unsigned* __restrict__ sb) {
-    const long total_f = (long)m.sf_net * m.n_nets, total_b = (long)m.sb_net * m.n_nets;         // 16-byte items
-    for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total_f + total_b; idx += (long)gridDim.x * blockDim.x) {
-        const bool fwd = idx < total_f;
-        long e = fwd ? idx : idx - total_f;
-        const int pn = fwd ? m.sf_net : m.sb_net;
-        const int net = (int)(e / pn);
-        e -= (long)net * pn;
-        int l = 0;
-        while (l + 1 < m.n_layers && e >= (fwd ? m.sf_off[l + 1] : m.sb_off[l + 1])) l++;
-        e -= fwd ? m.sf_off[l] : m.sb_off[l];
-        const int ni = m.sizes[l], no = m.sizes[l + 1];
-        const int lane = (int)(e & 63), plane = (int)((e >> 6) % 3);
-        const long blk = (e >> 6) / 3;
-        const int nS = fwd ? (ni + 31) >> 5 : (no + 31) >> 5;
-        const int tile = (int)(blk / nS), S = (int)(blk - (long)tile * nS);
-        const float* W = w + (size_t)net * m.net_size + m.w_off[l];
-        const int i = tile * 16 + (lane & 15);
-        unsigned out[4];
-#pragma unroll
-        for (int pr = 0; pr < 4; pr++) {
-            float v[2];
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const int k = 32 * S + 8 * (lane >> 4) + 2 * pr + q;
-                float x = 0.0f;
-                if (fwd) { if (i < no && k < ni) x = W[(size_t)k * no + i]; }            // A[i = out row][k = in]
-                else { if (i < ni && k < no) x = W[(size_t)i * no + k]; }               // A[i = in row][k = out]
-                const float hh = __uint_as_float(__float_as_uint(x) & 0xffff0000u), r1 = x - hh;
-                const float mm = __uint_as_float(__float_as_uint(r1) & 0xffff0000u), ll = r1 - mm;
-                v[q] = plane == 0 ? hh : (plane == 1 ? mm : ll);
-            }
-            out[pr] = (__float_as_uint(v[1]) & 0xffff0000u) | (__float_as_uint(v[0]) >> 16);
-        }
-        unsigned* dst = (fwd ? sf : sb) + (size_t)(fwd ? idx : idx - total_f) * 4;
-        dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2]; dst[3] = out[3];
-    }
+#define T16_ENS 0
+#include "t16_pack_planes_body.inc"
+#undef T16_ENS
+}
+__global__ void pack_planes_ens_kernel(DevModel m, const float* __restrict__ w, unsigned* __restrict__ sf, unsigned* __restrict__ sb, T16Ens en) {
+    w += blockIdx.y * en.w;
+    sf += blockIdx.y * en.sf;
+    sb += blockIdx.y * en.sb;
+#define T16_ENS 1
+#include "t16_pack_planes_body.inc"
+#undef T16_ENS
 }
 
 // eight consecutive floats of an activation / delta row (8-byte aligned): fetched one k-block ahead of the split that makes them a B operand (the rows live in global memory)
@@ -868,146 +830,49 @@ __global__ void __launch_bounds__(NTH) forward_kernel(DevModel m, PackInfo pk, c
                                const float* __restrict__ x0, const float* __restrict__ bcs,
                                const float* __restrict__ save_times, int n_save, int substeps,
                                float* __restrict__ sol, float* __restrict__ tape, int n_col, float* __restrict__ ztape) {
-    constexpr int FMAXR = 3072 / NTH;      // owner-thread register items per state array: CT * ns <= 3072 (ns <= 192)
-    const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = nth >> 6;
-    float* wl = smem;                                   // raw weights (WLDS) + 128 floats of zero padding
-    float* xs = smem + (WLDS ? ((m.n_params + 3) & ~3) + 128 : 0);
-    float* kk = xs + CT * m.ld_x;
-    const int zld = (m.n_nets * m.act_off[m.n_layers - 1] + 3) & ~3;      // floats per column of the hidden pre-activation tape
-    float* A = AG ? m.ag + (size_t)blockIdx.x * m.n_nets * CT * m.ld_a : kk + CT * m.ld_x;
-    float* F = AG ? kk + CT * m.ld_x : A + m.n_nets * CT * m.ld_a;
-    float* Ri_l = F + 3 * CT * m.ld_f;
-    float* bcl = Ri_l + CT * m.ld_f;
-    const int total = (int)(bcl + CT * 8 - smem);
-    for (int i = tid; i < total; i += nth) smem[i] = 0.0f;
-    __syncthreads();
-    if (WLDS) for (int i = tid; i < m.n_params; i += nth) wl[i] = w[i];
-    const float* wsrc = WLDS ? wl : w;
-    const int col0 = blockIdx.x * CT;
-    const int n_items = CT * m.ns;
-    load_bcs(m, bcs, bcl, col0, n_col, tid);
+#define T16_ENS 0
+#define T16_AG_TILE (size_t)blockIdx.x
+#include "t16_forward_body.inc"
+#undef T16_AG_TILE
+#undef T16_ENS
+}
 
-    float xn[FMAXR], acc[FMAXR];
-#pragma unroll
-    for (int r = 0; r < FMAXR; r++) {
-        const int it = tid + r * nth;
-        xn[r] = 0.0f;
-        acc[r] = 0.0f;
-        if (it < n_items) {
-            const int c = it / m.ns, i = it - c * m.ns;
-            xn[r] = x0[(size_t)min(col0 + c, n_col - 1) * m.ns + i];
-            if (sol && col0 + c < n_col) sol[((size_t)(col0 + c) * n_save) * m.ns + i] = xn[r];
-        }
-    }
-    const int n_steps = (n_save - 1) * substeps;
-    const int nst = m.nst;                               // RHS evaluations (taped stage inputs) per step: 4 (RK4) or s (RKC2)
-    float* tp = tape ? tape + (size_t)blockIdx.x * n_steps * nst * n_items : nullptr;
-    int step = 0;
-    if (RKC) {     // (a template parameter: the RK4 instantiation must not carry this branch's registers — 244 -> 262 VGPRs cost it a wave per SIMD)
-        // ---- s-stage RKC2 steps (colnde_dev.h; coefficients from the host table): per owner item Y_0 = xn, Y_{j-1} = ym1,
-        //      Y_{j-2} = ym2 and F_0 = f0 stay in registers; stage st evaluates F_st = f(Y_st), the step ends with Y_s
-        const float* mu_t = m.rkc, *nu_t = m.rkc + RKC_LD, *mut_t = m.rkc + 2 * RKC_LD, *gat_t = m.rkc + 3 * RKC_LD, *c_t = m.rkc + 4 * RKC_LD;
-        float ym1[FMAXR], ym2[FMAXR];                    // acc[] serves as f0
-        for (int iv = 0; iv < n_save - 1; iv++) {
-            const float t0 = save_times[iv];
-            const float dt = (save_times[iv + 1] - t0) / (float)substeps;
-            for (int s = 0; s < substeps; s++, step++) {
-                const float ts = t0 + (float)s * dt;
-#pragma nounroll
-                for (int st = 0; st <= nst; st++) {      // st = nst: only the final combination Y_s
-                    const float cmu = mu_t[st], cnu = nu_t[st], cmt = mut_t[st] * dt, cga = gat_t[st] * dt;
-                    const bool last = st == nst;
-                    const bool save = last && s == substeps - 1;
-#pragma unroll
-                    for (int r = 0; r < FMAXR; r++) {
-                        const int it = tid + r * nth;
-                        if (it < n_items) {
-                            const int c = it / m.ns, i = it - c * m.ns;
-                            const int o = c * m.ld_x + i;
-                            // increment form d_j = Y_j - Y_0 (the weights of Y_0, Y_{j-1}, Y_{j-2} sum to one): the differences
-                            // 2 d_{j-1} - d_{j-2} are taken between increments, not O(1) states — float32 stays accurate
-                            float dj = 0.0f;
-                            if (st == 1) {
-                                acc[r] = kk[o];                                        // F_0
-                                dj = cmt * acc[r];
-                            } else if (st >= 2) {
-                                dj = cmu * ym1[r] + cnu * ym2[r] + cmt * kk[o] + cga * acc[r];
-                            }
-                            const float v = xn[r] + dj;
-                            ym2[r] = st == 0 ? 0.0f : ym1[r];
-                            ym1[r] = dj;
-                            if (last) {
-                                xn[r] = v;
-                                if (save && sol && col0 + c < n_col) sol[((size_t)(col0 + c) * n_save + iv + 1) * m.ns + i] = v;
-                            } else {
-                                xs[o] = v;
-                                if (tp) tp[((size_t)step * nst + st) * n_items + it] = v;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                    if (last) break;
-                    if (AG && m.sf) mlp_forward_split(m, wsrc, xs, A, wave, nwaves, lane,
-                                             ztape ? ztape + ((size_t)blockIdx.x * n_steps * nst + (size_t)step * nst + st) * ((size_t)CT * zld) : nullptr, zld);
-                    else
-                    mlp_forward<false, WLDS>(m, pk, wsrc, wf, xs, nullptr, A, wave, nwaves, lane,
-                                             ztape ? ztape + ((size_t)blockIdx.x * n_steps * nst + (size_t)step * nst + st) * ((size_t)CT * zld) : nullptr, zld);
-                    physics_forward(m, xs, A, F, Ri_l, bcl, ts + c_t[st] * dt, kk, tid, nth);
-                }
-            }
-        }
-        return;
-    }
-    for (int iv = 0; iv < n_save - 1; iv++) {
-        const float t0 = save_times[iv];
-        const float dt = (save_times[iv + 1] - t0) / (float)substeps;
-        for (int s = 0; s < substeps; s++, step++) {
-            const float ts = t0 + (float)s * dt;
-#pragma nounroll
-            for (int st = 0; st < 4; st++) {
-                const float ca = st == 0 ? 0.0f : (st == 3 ? 1.0f : 0.5f);            // stage abscissa
-                const float cbp = (st == 1) ? 1.0f / 6.0f : 1.0f / 3.0f;               // weight of k_{st-1}
-#pragma unroll
-                for (int r = 0; r < FMAXR; r++) {
-                    const int it = tid + r * nth;
-                    if (it < n_items) {
-                        const int c = it / m.ns, i = it - c * m.ns;
-                        const int o = c * m.ld_x + i;
-                        float v = xn[r];
-                        if (st > 0) {
-                            const float kv = kk[o];
-                            acc[r] += cbp * kv;
-                            v += ca * dt * kv;
-                        }
-                        xs[o] = v;
-                        if (tp) tp[((size_t)step * 4 + st) * n_items + it] = v;
-                    }
-                }
-                __syncthreads();
-                if (AG && m.sf) mlp_forward_split(m, wsrc, xs, A, wave, nwaves, lane,
-                                         ztape ? ztape + ((size_t)blockIdx.x * n_steps * 4 + (size_t)step * 4 + st) * ((size_t)CT * zld) : nullptr, zld);
-                else
-                mlp_forward<false, WLDS>(m, pk, wsrc, wf, xs, nullptr, A, wave, nwaves, lane,
-                                         ztape ? ztape + ((size_t)blockIdx.x * n_steps * 4 + (size_t)step * 4 + st) * ((size_t)CT * zld) : nullptr, zld);
-                physics_forward(m, xs, A, F, Ri_l, bcl, ts + ca * dt, kk, tid, nth);
-            }
-            const bool save = (s == substeps - 1);
-#pragma unroll
-            for (int r = 0; r < FMAXR; r++) {
-                const int it = tid + r * nth;
-                if (it < n_items) {
-                    const int c = it / m.ns, i = it - c * m.ns;
-                    acc[r] += (1.0f / 6.0f) * kk[c * m.ld_x + i];
-                    xn[r] += dt * acc[r];
-                    acc[r] = 0.0f;
-                    if (save && sol && col0 + c < n_col)
-                        sol[((size_t)(col0 + c) * n_save + iv + 1) * m.ns + i] = xn[r];
-                }
-            }
-            __syncthreads();
-        }
-    }
+// Model k of a tile ensemble sees the DevModel of a single handle built with its constants: the copy in LDS gets the closure constants of row k of the
+// device table (RtPhys, dRi and Pr in its pad floats) and the model's own plane images.  One thread, between two barriers of the caller.
+__device__ __forceinline__ void t16_ens_patch_model(DevModel& ml, const T16Ens& en, size_t k) {
+    const RtPhys ph = en.phys[k];
+    ml.nu0 = ph.nu0; ml.nu_minus = ph.nu_minus; ml.Ric = ph.Ric; ml.inv_dRi = ph.inv_dRi; ml.inv_Pr = ph.inv_Pr; ml.c_rib = ph.c_rib;
+    ml.dRi = ph.pad0; ml.Pr = ph.pad1;
+    if (ml.sf) ml.sf += k * en.sf;
+    if (ml.sb) ml.sb += k * en.sb;
+}
+
+// K models of a tile ensemble: grid (tiles of ONE model's columns, K).  Model k's raw weights, packed image, solution and tapes lie the T16Ens strides
+// behind model 0's (its tiles index them with blockIdx.x exactly as a single handle's do); x0, bcs and the save times are shared.  The model description,
+// with model k's constants, sits at the head of the LDS (as the adjoint keeps it) and the tile's arrays behind it; the rows of m.ag are K x gridDim.x
+// slabs, tile blockIdx.x of model k in slab k * gridDim.x + blockIdx.x — none shared between two workgroups.
+template <bool WLDS, int NTH, bool RKC, bool AG>
+__global__ void __launch_bounds__(NTH) forward_ens_kernel(DevModel m_arg, PackInfo pk, const float* __restrict__ w, const float* __restrict__ wf,
+                               const float* __restrict__ x0, const float* __restrict__ bcs,
+                               const float* __restrict__ save_times, int n_save, int substeps,
+                               float* __restrict__ sol, float* __restrict__ tape, int n_col, float* __restrict__ ztape, T16Ens en) {
+    DevModel& m_lds = *reinterpret_cast<DevModel*>(::smem);
+    for (int i = threadIdx.x; i < (int)(sizeof(DevModel) / 4); i += blockDim.x) ((int*)&m_lds)[i] = ((const int*)&m_arg)[i];
+    __syncthreads();
+    if (threadIdx.x == 0) t16_ens_patch_model(m_lds, en, blockIdx.y);
+    __syncthreads();
+    const DevModel& m = m_lds;
+    float* const smem = ::smem + MODEL_FLOATS;
+    w += blockIdx.y * en.w;
+    wf += blockIdx.y * en.wf;
+    if (sol) sol += blockIdx.y * en.sol;
+    if (tape) tape += blockIdx.y * en.tape;
+    if (ztape) ztape += blockIdx.y * en.ztape;
+#define T16_ENS 1
+#define T16_AG_TILE ((size_t)blockIdx.y * gridDim.x + blockIdx.x)
+#include "t16_forward_body.inc"
+#undef T16_AG_TILE
+#undef T16_ENS
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1115,344 +980,40 @@ adjoint_kernel(DevModel m_arg, PackInfo pk, const float* __restrict__ w, const f
                int n_save, int substeps, const float* __restrict__ sol, const float* __restrict__ truth,
                const float* __restrict__ tape, LossWeights lw, float* __restrict__ slab /* [grid][n_params+8] */,
                int n_col, float* __restrict__ dwtape = nullptr, const float* __restrict__ ztape = nullptr) {
-    const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = nth >> 6;
-    // the model description lives in LDS: per-layer fields indexed with a runtime layer number would otherwise be
-    // dependent scalar loads from the kernarg segment (each followed by a full lgkmcnt(0) drain)
-    // (kept inside the dynamic region: a static __shared__ object would shift its base, guide G17)
-    DevModel& m_lds = *reinterpret_cast<DevModel*>(smem);
-    float* const base = smem + MODEL_FLOATS;
-    float* wl = base;                                   // raw weights (WLDS) + 128 floats of zero padding
-    float* xs = base + (WLDS ? ((m_arg.n_params + 3) & ~3) + 128 : 0);
-    float* dbar = xs + CT * m_arg.ld_x;
-    float* xb = dbar + CT * m_arg.ld_x;
-    static_assert(!AG || TAPEDW, "rows in global memory: the taped-dW adjoint only (the in-register one addresses its operands relative to LDS)");
-    // (AG: the delta rows in the workgroup's slab of m_arg.ag; only with the Z tape, so that no A array exists — the host guarantees it)
-    float* Z = AG ? m_arg.ag + (size_t)blockIdx.x * m_arg.n_nets * CT * m_arg.ld_a : xb + CT * m_arg.ld_x;
-    // taped mode with the hidden pre-activations taped: the activations go from the Z tape straight into the delta tape and are never
-    // needed on chip — no A array, and two workgroups of a 64-level network fit in a CU's LDS
-    const bool noA = TAPEDW && ztape != nullptr;
-    float* A = AG ? Z : Z + m_arg.n_nets * CT * m_arg.ld_a;
-    float* gb = AG ? xb + CT * m_arg.ld_x : (noA ? A : A + m_arg.n_nets * CT * m_arg.ld_a);
-    float* Ri_l = gb + 3 * CT * m_arg.ld_f;
-    float* Rib_l = Ri_l + CT * m_arg.ld_f;
-    float* bcl = Rib_l + CT * m_arg.ld_f;
-    float* red = bcl + CT * 8;
-    const int total = (int)(red + 16 * 8 - smem);
-    for (int i = tid; i < total; i += nth) smem[i] = 0.0f;
-    __syncthreads();
-    for (int i = tid; i < (int)(sizeof(DevModel) / 4); i += nth) ((int*)&m_lds)[i] = ((const int*)&m_arg)[i];
-    if (WLDS) for (int i = tid; i < m_arg.n_params; i += nth) wl[i] = w[i];
-    __syncthreads();
-    const DevModel& m = m_lds;
-    const float* wsrc = WLDS ? wl : w;
-    const int col0 = blockIdx.x * CT;
-    const int n_items = CT * m.ns;
-    load_bcs(m, bcs, bcl, col0, n_col, tid);
+#define T16_ENS 0
+#define T16_AG_TILE (size_t)blockIdx.x
+#include "t16_adjoint_body.inc"
+#undef T16_AG_TILE
+#undef T16_ENS
+}
 
-    f32x4 gacc[MAXT];
-#pragma unroll
-    for (int s = 0; s < MAXT; s++) gacc[s] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-    float dbias[MAXB];
-    int bz[MAXB];
-#pragma unroll
-    for (int r = 0; r < MAXB; r++) {
-        dbias[r] = 0.0f;
-        const int b = tid + r * nth;
-        bz[r] = b < m.n_bias ? bias_zoff[b] : -1;
-    }
-    float lam[MAXR], xbs[MAXR], xpre[MAXR];
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) lam[r] = 0.0f;
-    float sums[6] = {0, 0, 0, 0, 0, 0};
-    STAMP_DECL;
-
-    // per-slot LDS addresses (float indices into smem, lane part folded in) of this wave's weight-gradient tiles
-    int a_ad[MAXT], d_ad[MAXT];
-    unsigned long long a_is_act = 0ull;
-    if (!TAPEDW) {
-        const int cq = lane >> 4;
-#pragma unroll
-        for (int sl = 0; sl < MAXT; sl++) {
-            const int t = wave + sl * nwaves;
-            a_ad[sl] = 0;
-            d_ad[sl] = 0;
-            if (t < m.n_tiles) {
-                const TileDesc d = tiles[t];
-                const int stride = d.a_src ? m.ld_a : m.ld_x;
-                a_ad[sl] = (int)((d.a_src ? A + d.net * CT * m.ld_a : xs) - smem) + d.a_off + (lane & 15) + cq * stride;
-                d_ad[sl] = (int)(Z - smem) + d.net * CT * m.ld_a + d.d_off + (lane & 15) + cq * m.ld_a;
-                if (d.a_src) a_is_act |= 1ull << sl;
-            }
-        }
-    }
-
-    const int n_steps = (n_save - 1) * substeps;
-    const int nst = m.nst;                               // taped stage inputs per step: 4 (RK4) or s (RKC2)
-    constexpr bool rkc = RKC;            // a template parameter: the RK4 instantiations do not carry the RKC cotangent registers
-    const float* mu_t = m.rkc, *nu_t = m.rkc + RKC_LD, *mut_t = m.rkc + 2 * RKC_LD, *gat_t = m.rkc + 3 * RKC_LD, *kap_t = m.rkc + 5 * RKC_LD;
-    const float* tp = tape + (size_t)blockIdx.x * n_steps * nst * n_items;
-    // the tape is read one stage ahead of its use (xpre) so that its HBM latency hides under the previous stage
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) {
-        const int it = tid + r * nth;
-        xpre[r] = it < n_items ? tp[((size_t)n_steps * nst - 1) * n_items + it] : 0.0f;
-    }
-    // RKC2 (discrete adjoint of the recurrence in colnde_dev.h): cotangents of Y_j (lam), Y_{j-1} (yb1), Y_{j-2} (yb2), Y_0 (yb0)
-    // and F_0 (f0b) per owner item; unused by the RK4 path
-    float yb1[MAXR], yb2[MAXR], yb0[MAXR], f0b[MAXR];
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) { yb1[r] = 0.0f; yb2[r] = 0.0f; yb0[r] = 0.0f; f0b[r] = 0.0f; }
-
-    // save point 0 enters the loss value only (x0 does not depend on the weights)
-#pragma unroll
-    for (int r = 0; r < MAXR; r++) {
-        const int it = tid + r * nth;
-        if (it < n_items) {
-            const int c = it / m.ns, i = it - c * m.ns;
-            if (col0 + c < n_col) {
-                float dummy = 0.0f;
-                loss_inject(m, sol, truth, ((size_t)(col0 + c) * n_save) * m.ns, i, lw.w, dummy, sums);
-            }
-        }
-    }
-
-    for (int iv = n_save - 2; iv >= 0; iv--) {
-        const float t0 = save_times[iv];
-        const float dt = (save_times[iv + 1] - t0) / (float)substeps;
-        // λ += ∂loss/∂sol[:, iv+1]
-#pragma unroll
-        for (int r = 0; r < MAXR; r++) {
-            const int it = tid + r * nth;
-            if (it < n_items) {
-                const int c = it / m.ns, i = it - c * m.ns;
-                if (col0 + c < n_col)
-                    loss_inject(m, sol, truth, ((size_t)(col0 + c) * n_save + iv + 1) * m.ns, i, lw.w, lam[r], sums);
-            }
-        }
-        for (int s = substeps - 1; s >= 0; s--) {
-            const int step = iv * substeps + s;
-#pragma unroll
-            for (int r = 0; r < MAXR; r++) xbs[r] = 0.0f;
-#pragma nounroll
-            for (int st = nst - 1; st >= 0; st--) {
-                // k̄4 = dt/6 λ; k̄3 = dt/3 λ + dt x̄4; k̄2 = dt/3 λ + dt/2 x̄3; k̄1 = dt/6 λ + dt/2 x̄2
-                const float cwl = (st == 0 || st == 3) ? dt / 6.0f : dt / 3.0f;
-                const float cwx = st == 2 ? dt : 0.5f * dt;
-                // RKC2, stage input Y_st feeds Y_j, j = st + 1, through mu~_j h F_st:
-                const float cmu = rkc ? mu_t[st + 1] : 0.0f, cnu = rkc ? nu_t[st + 1] : 0.0f;
-                const float cmt = rkc ? mut_t[st + 1] * dt : 0.0f, cga = rkc ? gat_t[st + 1] * dt : 0.0f, ck0 = rkc ? kap_t[st + 1] : 0.0f;
-                STAMP_BEGIN();
-                // stage input from the tape; stage cotangent k̄_st = wl λ + wx x̄_{st+1}
-#pragma unroll
-                for (int r = 0; r < MAXR; r++) {
-                    const int it = tid + r * nth;
-                    if (it < n_items) {
-                        const int c = it / m.ns, i = it - c * m.ns;
-                        const int o = c * m.ld_x + i;
-                        xs[o] = xpre[r];
-                        float kb;
-                        if (rkc) {
-                            // lam = cotangent of Y_j, complete once the previous iteration's pullback (xb: J(Y_j)^T F̄_j) is added
-                            if (st < nst - 1) {
-                                const float yj = yb1[r] + xb[o];
-                                yb1[r] = yb2[r];
-                                yb2[r] = 0.0f;
-                                lam[r] = yj;
-                            }
-                            if (st >= 1) {
-                                yb0[r] += ck0 * lam[r];
-                                yb1[r] += cmu * lam[r];
-                                yb2[r] += cnu * lam[r];
-                                f0b[r] += cga * lam[r];
-                                kb = cmt * lam[r];
-                            } else {
-                                // Y_1 = Y_0 + mu~_1 h F_0: lam holds Ȳ_1, yb1 the nu_2 part of Ȳ_0
-                                yb0[r] += lam[r] + yb1[r];
-                                kb = f0b[r] + cmt * lam[r];
-                                yb1[r] = 0.0f;
-                                f0b[r] = 0.0f;
-                            }
-                        } else {
-                            kb = cwl * lam[r];
-                            if (st < 3) kb += cwx * xb[o];
-                        }
-                        dbar[o] = kb;
-                    }
-                }
-                {
-                    const int qn = step * nst + st - 1;            // the stage handled next (tape order is time order)
-                    if (qn >= 0) {
-#pragma unroll
-                        for (int r = 0; r < MAXR; r++) {
-                            const int it = tid + r * nth;
-                            if (it < n_items) xpre[r] = tp[(size_t)qn * n_items + it];
-                        }
-                    }
-                }
-                __syncthreads();
-                STAMP(0);
-                if (TAPEDW && ztape) {
-                    // hidden-layer pre-activations taped by the forward kernel: Z into LDS, A = act(Z) straight into this stage's record of
-                    // the delta tape (the output layer enters the pullback linearly: its values are not needed; its A slot is never read
-                    // by the dW GEMM either)
-                    const int hid = m.act_off[m.n_layers - 1], zld = (m.n_nets * hid + 3) & ~3;
-                    const float* zr = ztape + ((size_t)blockIdx.x * n_steps * nst + (size_t)step * nst + st) * ((size_t)CT * zld);
-                    const int ns4r = (m.ns + 3) & ~3, act4r = (m.act_total + 3) & ~3;
-                    const int Rr = ns4r + 2 * m.n_nets * act4r;
-                    float* recA = dwtape + ((size_t)blockIdx.x * n_steps * nst + (size_t)step * nst + st) * ((size_t)CT * Rr) + ns4r;
-                    // (segments start at multiples of 4 floats: one float4 never straddles two layers; up to four float4 per lane
-                    //  are fetched back to back so that one HBM latency covers them)
-                    const int nq = (m.n_nets * hid) >> 2;                      // float4 items per column
-                    for (int c = wave; c < CT; c += nwaves)
-                        for (int q0 = lane; q0 < nq; q0 += 4 * 64) {
-                            float4 v[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++)
-                                if (q0 + 64 * u < nq) v[u] = *reinterpret_cast<const float4*>(zr + c * zld + 4 * (q0 + 64 * u));
-#pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const int q = q0 + 64 * u;
-                                if (q < nq) {
-                                    const int f = 4 * q, net = f / hid, o = f - net * hid;
-                                    int l = 0;
-                                    while (o >= m.act_off[l + 1]) l++;
-                                    const int a = m.acts[l];
-                                    // the pad slots behind a layer's last feature were never written by the forward kernel: they must read as
-                                    // zero (a backward chain multiplies them with whatever weight sits behind the row's end)
-                                    const int nvalid = m.sizes[l + 1] - (o - m.act_off[l]);
-                                    if (nvalid < 4) {
-                                        if (nvalid < 1) v[u].x = 0.0f;
-                                        if (nvalid < 2) v[u].y = 0.0f;
-                                        if (nvalid < 3) v[u].z = 0.0f;
-                                        v[u].w = 0.0f;
-                                    }
-                                    float* zd = Z + (net * CT + c) * m.ld_a + o;
-                                    zd[0] = v[u].x; zd[1] = v[u].y; zd[2] = v[u].z; zd[3] = v[u].w;
-                                    *reinterpret_cast<float4*>(recA + (size_t)c * Rr + net * act4r + o) =
-                                        make_float4(dev_act(a, v[u].x), dev_act(a, v[u].y), dev_act(a, v[u].z), dev_act(a, v[u].w));
-                                }
-                            }
-                        }
-                    __syncthreads();
-                } else
-                    mlp_forward<true, WLDS>(m, pk, wsrc, wf, xs, Z, A, wave, nwaves, lane);
-                STAMP(1);
-                physics_vjp(m, xs, dbar, Z, xb, gb, Ri_l, Rib_l, tid, nth, rkc ? (st == nst - 1 ? 1 : 2) : 0);
-                STAMP(2);
-                if (AG && m.sb) mlp_backward_split(m, pk, wb, Z, xb, wave, nwaves, lane);
-                else mlp_backward<WLDS>(m, pk, wsrc, wb, Z, xb, wave, nwaves, lane);
-                STAMP(3);
-                // weight gradients: dW += A_{l-1}^T dZ_l over the tile's 16 columns; operands of slot sl+1 are read
-                // while the MFMAs of slot sl run
-                if (TAPEDW) {
-                    // row = [xs (ns4) | A of every net (act4 each) | dZ of every net (act4 each)], every segment padded to a multiple of
-                    // 4 floats (the pads copy LDS row padding: finite, never stored by dw_gemm).  LDS rows are 8-byte aligned (stride
-                    // == 2 mod 4), tape rows 16-byte aligned: copied two floats at a time
-                    const int ns4 = (m.ns + 3) & ~3, act4 = (m.act_total + 3) & ~3;
-                    const int R = ns4 + 2 * m.n_nets * act4;
-                    float* rec = dwtape + ((size_t)blockIdx.x * n_steps * nst + (size_t)step * nst + st) * ((size_t)CT * R);
-                    const int hx = ns4 >> 1, ha = act4 >> 1;                                        // float2 items per segment
-                    for (int c = wave; c < CT; c += nwaves) {                                       // one wave per column
-                        float* row = rec + (size_t)c * R;
-                        for (int q = lane; q < hx; q += 64)
-                            *reinterpret_cast<float2*>(row + 2 * q) = *reinterpret_cast<const float2*>(xs + c * m.ld_x + 2 * q);
-                        for (int seg = noA ? m.n_nets : 0; seg < 2 * m.n_nets; seg++) {               // A of every net (unless already written), then dZ of every net
-                            const int net = seg < m.n_nets ? seg : seg - m.n_nets;
-                            const float* src = (seg < m.n_nets ? A : Z) + (net * CT + c) * m.ld_a;
-                            float* dst = row + ns4 + seg * act4;
-                            for (int o = lane; o < ha; o += 64)
-                                *reinterpret_cast<float2*>(dst + 2 * o) = *reinterpret_cast<const float2*>(src + 2 * o);
-                        }
-                    }
-                } else {
-                    float pa[2][4], pb[2][4];
-                    const int zs4 = 4 * m.ld_a;
-                    if (wave < m.n_tiles) {
-                        const int as4 = 4 * ((a_is_act & 1ull) ? m.ld_a : m.ld_x);
-#pragma unroll
-                        for (int q = 0; q < 4; q++) {
-                            pa[0][q] = smem[a_ad[0] + q * as4];
-                            pb[0][q] = smem[d_ad[0] + q * zs4];
-                        }
-                    }
-#pragma unroll
-                    for (int sl = 0; sl < MAXT; sl++) {
-                        if (sl + 1 < MAXT && wave + (sl + 1) * nwaves < m.n_tiles) {
-                            const int as4 = 4 * (((a_is_act >> (sl + 1)) & 1ull) ? m.ld_a : m.ld_x);
-#pragma unroll
-                            for (int q = 0; q < 4; q++) {
-                                pa[(sl + 1) & 1][q] = smem[a_ad[(sl + 1) % MAXT] + q * as4];
-                                pb[(sl + 1) & 1][q] = smem[d_ad[(sl + 1) % MAXT] + q * zs4];
-                            }
-                        }
-                        if (wave + sl * nwaves < m.n_tiles) {
-#pragma unroll
-                            for (int q = 0; q < 4; q++) gacc[sl] = mfma16(pa[sl & 1][q], pb[sl & 1][q], gacc[sl]);
-                        }
-                    }
-                }
-                STAMP(4);
-#pragma unroll
-                for (int r = 0; r < MAXB; r++)
-                    if (bz[r] >= 0) {
-                        float sacc = 0.0f;
-#pragma unroll
-                        for (int c = 0; c < CT; c++) sacc += Z[bz[r] + c * m.ld_a];
-                        dbias[r] += sacc;
-                    }
-#pragma unroll
-                for (int r = 0; r < MAXR; r++) {
-                    const int it = tid + r * nth;
-                    if (it < n_items) {
-                        const int c = it / m.ns, i = it - c * m.ns;
-                        xbs[r] += xb[c * m.ld_x + i];
-                    }
-                }
-                __syncthreads();
-                STAMP(5);
-            }
-            if (rkc) {
-                // λ_n = Ȳ_0 + J(Y_0)^T F̄_0 (xb of the st = 0 pullback; visible after the stage's closing barrier)
-#pragma unroll
-                for (int r = 0; r < MAXR; r++) {
-                    const int it = tid + r * nth;
-                    if (it < n_items) {
-                        const int c = it / m.ns, i = it - c * m.ns;
-                        lam[r] = yb0[r] + xb[c * m.ld_x + i];
-                    }
-                    yb0[r] = 0.0f;
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < MAXR; r++) lam[r] += xbs[r];
-            }
-        }
-    }
-
-    STAMP_FLUSH();
-    // flush this tile's partial gradient and loss sums
-    float* out = slab + (size_t)blockIdx.x * (m.n_params + 8);
-#pragma unroll
-    for (int sl = 0; sl < MAXT; sl++) {
-        const int t = wave + sl * nwaves;
-        if (!TAPEDW && t < m.n_tiles) {
-            const TileDesc d = tiles[t];
-            const int j = lane & 15;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int i = 4 * (lane >> 4) + r;
-                if (i < d.ni_rem && j < d.no_rem) out[d.g_off + i * d.no + j] = gacc[sl][r];
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < MAXB; r++) {
-        const int b = tid + r * nth;
-        if (b < m.n_bias) out[bias_goff[b]] = dbias[r];
-    }
-    block_reduce_sums(sums, 6, red, out + m.n_params, tid, nth);
-    if (tid >= 6 && tid < 8) out[m.n_params + tid] = 0.0f;
+// K models of a tile ensemble, taped dW at 1,024 threads: grid (tiles of ONE model's columns, K).  Model k's weights, images, solution, the three tapes and
+// its slab rows lie the T16Ens strides behind model 0's; bcs, truth, the save times and the bias tables are shared (no in-register dW tiles: no TileDesc).
+// The body patches model k's constants and plane images into its LDS copy of the description (T16_ENS) and takes the delta rows of slab
+// k * gridDim.x + blockIdx.x of m.ag.
+template <int MAXR, bool WLDS, bool RKC, bool AG>
+__global__ void __launch_bounds__(1024, 1)
+adjoint_ens_kernel(DevModel m_arg, PackInfo pk, const float* __restrict__ w, const float* __restrict__ wf, const float* __restrict__ wb,
+                   const int* __restrict__ bias_zoff, const int* __restrict__ bias_goff, const float* __restrict__ bcs,
+                   const float* __restrict__ save_times, int n_save, int substeps, const float* __restrict__ sol, const float* __restrict__ truth,
+                   const float* __restrict__ tape, LossWeights lw, float* __restrict__ slab, int n_col, float* __restrict__ dwtape,
+                   const float* __restrict__ ztape, T16Ens en) {
+    constexpr int MAXT = 1;
+    constexpr bool TAPEDW = true;
+    const TileDesc* const tiles = nullptr;
+    w += blockIdx.y * en.w;
+    wf += blockIdx.y * en.wf;
+    wb += blockIdx.y * en.wb;
+    sol += blockIdx.y * en.sol;
+    tape += blockIdx.y * en.tape;
+    slab += blockIdx.y * en.slab;
+    dwtape += blockIdx.y * en.dwtape;
+    ztape += blockIdx.y * en.ztape;
+#define T16_ENS 1
+#define T16_AG_TILE ((size_t)blockIdx.y * gridDim.x + blockIdx.x)
+#include "t16_adjoint_body.inc"
+#undef T16_AG_TILE
+#undef T16_ENS
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1552,6 +1113,100 @@ bool pick_adjoint_geom(const DevModel& m, AdjointGeom* geo, int force) {
     return false;
 }
 
+// The taped-dW adjoint's geometry for a launch of n_tiles tiles (a TAPED_* index, -1: none) and, in *lds_bytes, the LDS it takes: decided here for a
+// single handle and for a tile ensemble alike — the ensemble asks with the tiles of ONE model, so that model k runs the kernel form a single handle of
+// its columns runs.
+static int pick_taped_geom(const DevModel& m, int n_tiles, bool have_ztape, size_t* lds_bytes) {
+    if (m.ag) {
+        // rows in global memory (wide networks): the Z tape is required (no A array), 1,024 threads (n_bias <= MAXB * 1,024, CT * ns <= 2 * 1,024: checked by the host)
+        if (!have_ztape || CT * m.ns > 2 * 1024 || m.n_bias > MAXB * 1024) return -1;
+        return TAPED_AG;
+    }
+    // Two 512-thread workgroups per CU (128 registers each) when two fit in the LDS: one's GEMMs then cover the other's tape
+    // traffic, activations and physics (32-128-128-31: adjoint 84.6 -> 61.6 ms); one 1,024-thread workgroup (four waves per SIMD)
+    // otherwise.  COLNDE_T16_TAPE_THREADS=512|1024 forces either.
+    const char* et = getenv("COLNDE_T16_TAPE_THREADS");
+    const int nth_env = et ? atoi(et) : ((n_tiles > 256 && 2 * *lds_bytes + 2048 <= 160 * 1024) ? 512 : 1024);   // (fewer tiles than CUs: a latency point, the wider workgroup finishes sooner)
+    // latency points (fewer tiles than CUs) with a network that fits beside the tile's arrays: the raw weights staged in LDS, read in
+    // place for W^T — no L2 round trip at the head of every backward chain (8 simulations: adjoint 29.3 -> 25.0 ms)
+    const size_t wl_bytes = ((size_t)((m.n_params + 3) & ~3) + 128) * sizeof(float);
+    const char* ew = getenv("COLNDE_T16_TAPE_WLDS");
+    const bool wlds_ok = nth_env == 1024 && CT * m.ns <= 2 * 1024 && *lds_bytes + wl_bytes <= 160 * 1024;
+    if (wlds_ok && (ew ? atoi(ew) != 0 : n_tiles <= 256)) { *lds_bytes += wl_bytes; return TAPED_1024_WLDS; }
+    if (nth_env == 1024 && CT * m.ns <= 2 * 1024) return TAPED_1024;
+    if (CT * m.ns <= 3 * 512) return TAPED_512_R3;
+    if (CT * m.ns <= 6 * 512) return TAPED_512_R6;
+    return -1;
+}
+
+// ---- tile ensembles: the instantiations an ensemble can reach — both steppers; weights in LDS or streamed; rows in LDS or in global memory (whose arithmetic
+// is a runtime switch, DevModel::sf / sb).  No in-register adjoint geometry and no 512-thread taped one.
+using ForwardEnsFn = decltype(&forward_ens_kernel<false, 256, false, false>);
+static ForwardEnsFn forward_ens_pick(bool wlds, int nthreads, bool rkc, bool ag) {
+    ForwardEnsFn k = nullptr;
+    with_bools([&](auto RK) {
+        constexpr bool rk = decltype(RK)::value;
+        if (wlds && !ag && nthreads == 1024) k = forward_ens_kernel<true, 1024, rk, false>;
+        if (!wlds && !ag && nthreads == 256) k = forward_ens_kernel<false, 256, rk, false>;
+        if (!wlds && ag && nthreads == 1024) k = forward_ens_kernel<false, 1024, rk, true>;
+    }, rkc);
+    return k;
+}
+bool forward_ens_has(bool wlds, int nthreads, bool ag) { return forward_ens_pick(wlds, nthreads, false, ag) != nullptr; }
+using AdjointEnsFn = decltype(&adjoint_ens_kernel<2, true, false, false>);
+static AdjointEnsFn adjoint_ens_pick(int taped_geom, bool rkc) {      // by TAPED_* index
+    AdjointEnsFn k = nullptr;
+    with_bools([&](auto RK) {
+        constexpr bool rk = decltype(RK)::value;
+        if (taped_geom == TAPED_1024_WLDS) k = adjoint_ens_kernel<2, true, rk, false>;
+        if (taped_geom == TAPED_1024) k = adjoint_ens_kernel<2, false, rk, false>;
+        if (taped_geom == TAPED_AG) k = adjoint_ens_kernel<2, false, rk, true>;
+    }, rkc);
+    return k;
+}
+
+bool adjoint_ens_has(const DevModel& m, int n_tiles, size_t lds_bytes) {
+    const int g = pick_taped_geom(m, n_tiles, true, &lds_bytes);
+    return g >= 0 && adjoint_ens_pick(g, false) != nullptr;
+}
+
+hipError_t launch_pack_ens(const DevModel& m, const PackInfo& pk, const float* w, float* wf, float* wb, const T16Ens& en, hipStream_t stream) {
+    const int total = (pk.pf_net + pk.pb_net) * m.n_nets;
+    hipLaunchKernelGGL(pack_weights_ens_kernel, dim3((total + 255) / 256, en.n_models), dim3(256), 0, stream, m, pk, w, wf, wb, en);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_planes_ens(const DevModel& m, const float* w, unsigned* sf, unsigned* sb, const T16Ens& en, hipStream_t stream) {
+    const long total = ((long)m.sf_net + m.sb_net) * m.n_nets;
+    hipLaunchKernelGGL(pack_planes_ens_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 65535), en.n_models), dim3(256), 0, stream, m, w, sf, sb, en);
+    return hipGetLastError();
+}
+
+hipError_t launch_forward_ens(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* x0, const float* bcs,
+                              const float* save_times, int n_save, int substeps, float* sol, float* tape, int n_col, int nthreads, bool wlds,
+                              size_t lds_bytes, const T16Ens& en, hipStream_t stream, float* ztape) {
+    const auto k = forward_ens_pick(wlds, nthreads, m.rkc != nullptr, m.ag != nullptr);
+    if (!k || !en.phys || en.n_models < 1 || en.n_models > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3((n_col + CT - 1) / CT, en.n_models), dim3(nthreads), lds_bytes + t16_ens_forward_lds_extra(), stream, m, pk, w, wf, x0, bcs, save_times,
+                       n_save, substeps, sol, tape, n_col, ztape, en);
+    return hipGetLastError();
+}
+
+hipError_t launch_adjoint_ens(const DevModel& m, const PackInfo& pk, const float* w, const float* wf, const float* wb, const int* bias_zoff,
+                              const int* bias_goff, const float* bcs, const float* save_times, int n_save, int substeps, const float* sol,
+                              const float* truth, const float* tape, const LossWeights& lw, float* slab, int n_col, size_t lds_bytes,
+                              const T16Ens& en, hipStream_t stream, float* dwtape, const float* ztape) {
+    if (!dwtape || !ztape || !tape || !en.phys || en.n_models < 1 || en.n_models > 65535) return hipErrorInvalidValue;
+    const int n_tiles = (n_col + CT - 1) / CT;               // of ONE model: the geometry a single handle of n_col columns runs
+    size_t lds = lds_bytes;
+    const int g = pick_taped_geom(m, n_tiles, true, &lds);
+    const auto k = g < 0 ? nullptr : adjoint_ens_pick(g, m.rkc != nullptr);
+    if (!k) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3(n_tiles, en.n_models), dim3(1024), lds, stream, m, pk, w, wf, wb, bias_zoff, bias_goff, bcs, save_times, n_save, substeps, sol, truth,
+                       tape, lw, slab, n_col, dwtape, ztape, en);
+    return hipGetLastError();
+}
+
 hipError_t launch_pack(const DevModel& m, const PackInfo& pk, const float* w, float* wf, float* wb, hipStream_t stream) {
     const int total = (pk.pf_net + pk.pb_net) * m.n_nets;
     hipLaunchKernelGGL(pack_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, m, pk, w, wf, wb);
@@ -1606,27 +1261,10 @@ hipError_t launch_adjoint(const DevModel& m, const PackInfo& pk, const float* w,
                            n_save, substeps, sol, truth, tape, lw, slab, n_col, dwt, zt);
         return hipGetLastError();
     };
-    if (dwtape && m.ag) {
-        // rows in global memory (wide networks): the Z tape is required (no A array), 1,024 threads (n_bias <= MAXB * 1,024, CT * ns <= 2 * 1,024: checked by the host)
-        if (!ztape || CT * m.ns > 2 * 1024 || m.n_bias > MAXB * 1024) return hipErrorInvalidValue;
-        return launch(kTapedGeoms[TAPED_AG], lds_bytes, dwtape, ztape);
-    }
     if (dwtape) {
-        // Two 512-thread workgroups per CU (128 registers each) when two fit in the LDS: one's GEMMs then cover the other's tape
-        // traffic, activations and physics (32-128-128-31: adjoint 84.6 -> 61.6 ms); one 1,024-thread workgroup (four waves per SIMD)
-        // otherwise.  COLNDE_T16_TAPE_THREADS=512|1024 forces either.
-        const char* et = getenv("COLNDE_T16_TAPE_THREADS");
-        const int nth_env = et ? atoi(et) : ((n_tiles > 256 && 2 * lds_bytes + 2048 <= 160 * 1024) ? 512 : 1024);   // (fewer tiles than CUs: a latency point, the wider workgroup finishes sooner)
-        // latency points (fewer tiles than CUs) with a network that fits beside the tile's arrays: the raw weights staged in LDS, read in
-        // place for W^T — no L2 round trip at the head of every backward chain (8 simulations: adjoint 29.3 -> 25.0 ms)
-        const size_t wl_bytes = ((size_t)((m.n_params + 3) & ~3) + 128) * sizeof(float);
-        const char* ew = getenv("COLNDE_T16_TAPE_WLDS");
-        const bool wlds_ok = nth_env == 1024 && CT * m.ns <= 2 * 1024 && lds_bytes + wl_bytes <= 160 * 1024;
-        if (wlds_ok && (ew ? atoi(ew) != 0 : n_tiles <= 256)) return launch(kTapedGeoms[TAPED_1024_WLDS], lds_bytes + wl_bytes, dwtape, ztape);
-        if (nth_env == 1024 && CT * m.ns <= 2 * 1024) return launch(kTapedGeoms[TAPED_1024], lds_bytes, dwtape, ztape);
-        if (CT * m.ns <= 3 * 512) return launch(kTapedGeoms[TAPED_512_R3], lds_bytes, dwtape, ztape);
-        if (CT * m.ns <= 6 * 512) return launch(kTapedGeoms[TAPED_512_R6], lds_bytes, dwtape, ztape);
-        return hipErrorInvalidValue;
+        size_t lds = lds_bytes;
+        const int g = pick_taped_geom(m, n_tiles, ztape != nullptr, &lds);
+        return g < 0 ? hipErrorInvalidValue : launch(kTapedGeoms[g], lds, dwtape, ztape);
     }
     for (const AdjointInst& a : kGeoms)
         if (a.g.nthreads == geo.nthreads && a.g.maxt == geo.maxt && a.g.maxr == geo.maxr && !a.g.wlds == !geo.wlds) return launch(a, lds_bytes, nullptr, nullptr);
@@ -1664,7 +1302,11 @@ hipError_t set_kernel_attributes(size_t max_lds_bytes) {
         for (const AdjointInst& a : kTapedGeoms) set(a.k[rkc]);
         for (int nthreads : {256, 512, 1024})
             for (int wlds = 0; wlds < 2; wlds++)
-                for (int ag = 0; ag < 2; ag++) set(forward_pick(wlds, nthreads, rkc, ag));
+                for (int ag = 0; ag < 2; ag++) {
+                    set(forward_pick(wlds, nthreads, rkc, ag));
+                    set(forward_ens_pick(wlds, nthreads, rkc, ag));
+                }
+        for (int g = 0; g <= TAPED_AG; g++) set(adjoint_ens_pick(g, rkc));
     }
     return e;
 }

@@ -190,6 +190,31 @@ inline T16EnsTapes plan_t16_ens_tapes(int K, int n_tiles, size_t per_model_rich,
     return p;
 }
 
+// A tile ensemble (colnde_create_tile_ensemble: K models of any tile16 architecture): one block of all columns per model on the model's share of
+// (free memory - 3 GB).  tile16 has no time segments: what a model needs either fits its share or the ensemble is refused with the bytes.  A model
+// owns, for its n_tiles x n_steps x nst records of 16 columns: the stage tape (ns floats per column), the delta tape (row_floats), the hidden
+// pre-activation tape (ztape_col_floats); its slab rows (slab_rows — the adjoint's, one per tile, and the dW GEMM's, one per slice of the count a
+// single handle of this size plans — of n_params + 8 floats); its solution; its two packed weight images (image_floats) and, with the rows in
+// global memory, its bf16 plane images (plane_words) and n_tiles slabs of activation rows (ag_floats_per_tile; 0: rows in LDS).
+struct T16TileEnsIn {
+    int K, n_tiles, n_steps, nst, ns, n_params, n_col, n_save, slab_rows;
+    size_t row_floats, ztape_col_floats, image_floats, plane_words, ag_floats_per_tile;
+    size_t free_bytes;
+};
+struct T16TileEns { size_t records, bytes_per_model, share; bool refused; };
+inline T16TileEns plan_t16_tile_ens(const T16TileEnsIn& in) {
+    T16TileEns p = {(size_t)in.n_tiles * in.n_steps * in.nst, 0, 0, false};
+    const size_t tile = 16;
+    const size_t tapes = p.records * tile * ((size_t)in.ns + in.row_floats + in.ztape_col_floats);
+    const size_t slab = (size_t)in.slab_rows * ((size_t)in.n_params + 8);
+    const size_t sol = (size_t)in.n_col * in.n_save * in.ns;
+    const size_t rows = (size_t)in.n_tiles * in.ag_floats_per_tile;
+    p.bytes_per_model = (tapes + slab + sol + in.image_floats + rows) * sizeof(float) + in.plane_words * sizeof(unsigned int);
+    p.share = hbm_budget(in.free_bytes, (size_t)3 << 30) / (size_t)(in.K > 0 ? in.K : 1);
+    p.refused = p.bytes_per_model > p.share;
+    return p;
+}
+
 // regtile: the block, with the Z1 tape when even 1,024 columns fit with it and without it otherwise; COLNDE_RT_BLOCK forces a size.  block = 0: the
 // stage tapes of not even 1,024 columns fit.
 struct RtTapes { int block; bool ztape; };

@@ -16,7 +16,7 @@ from . import _lib
 from ._arrays import _dtype_name, _f32, _is_torch, _ptr, check_ensemble_arrays
 from .embed import (EmbeddingMixin, FcEnsembleEmbedded, WmEnsembleEmbedded, check_fc_embed_arrays, check_fc_ens_embed_arrays, check_wm_diag_arrays,
                     check_wm_embed_arrays, check_wm_ens_embed_arrays)
-from .config import CONVECTIVE_ADJUSTMENT_NDE, FREE_CONVECTION, MATRIX_ARITHMETIC_NAMES, NDEConfig, matrix_arithmetic_id, to_c_config
+from .config import CONVECTIVE_ADJUSTMENT_NDE, FREE_CONVECTION, WIND_MIXING, MATRIX_ARITHMETIC_NAMES, NDEConfig, matrix_arithmetic_id, to_c_config
 
 KERNEL_IDS = {"forward": 0, "adjoint": 1, "reduce": 2, "rhs": 3, "infer": 4, "dw1": 5, "convadj": 6, "adam": 7, "impldiff": 8, "fc_embed": 9, "flux_diag": 10, "wm_profile": 11}
 ENGINE_AUTO, ENGINE_TILE16, ENGINE_REGTILE, ENGINE_FC32 = 0, 1, 2, 3
@@ -476,6 +476,15 @@ def check_wm_pretrain_arrays(cfg: NDEConfig, n_models: int, theta, profiles, bcs
     return n
 
 
+def is_net_split_shape(cfg: NDEConfig) -> bool:
+    """The configurations `colnde_create_ensemble` accepts (csrc: rt_supported; no GPU needed): the wind-mixing NDE at Nz = 32 with three 96-50-20-31
+    nets, one hidden activation and an identity output layer, on the training RHS without smoothing.  Everything else a tile16 handle trains is
+    `TileNDEEnsemble`'s."""
+    return (cfg.model == WIND_MIXING and cfg.Nz == 32 and tuple(cfg.layer_sizes) == (96, 50, 20, 31) and len(cfg.activations) == 3 and
+            cfg.activations[0] == cfg.activations[1] and cfg.activations[2] == "identity" and not cfg.smooth_NN and not cfg.smooth_Ri and
+            not cfg.inplace_variant)
+
+
 class ColumnNDEEnsemble(ColumnNDE):
     """K models of ONE architecture on the same columns (`colnde_create_ensemble`): own weights, own Pacanowski-Philander constants, own ADAM rate —
     the sweep of wind_mixing/train_NDE_args.jl (one model per process there) with every kernel launched once for all K models.
@@ -670,6 +679,32 @@ class ColumnNDEEnsemble(ColumnNDE):
         ri = faces[-1] if Ri else None
         _lib.check(fn(self._h, P(weights), P(sol), ph, P(f3[0]), P(f3[1]), P(f3[2]), P(ri), P(ls)))
         return EnsembleProfile(f3[0], f3[1], f3[2], ri, ls)
+
+
+class TileNDEEnsemble(ColumnNDEEnsemble):
+    """K wind-mixing models of ANY architecture a tile16 handle trains (`colnde_create_tile_ensemble`): the reference's wide nets
+    (wind_mixing/train_NDE.jl:97-102 — 96-400-400-31, 96-32-400-31, 96-400-31), other depths and activations, other Nz, and the 96-50-20-31 shape on
+    tile16's own kernels.  Row k of `forward`, `loss` and `loss_grad` holds the bits of `ColumnNDE(cfg_k, n_columns, engine=ENGINE_TILE16)`.
+    Everything but the constructor is `ColumnNDEEnsemble`'s; the library refuses, by name, the calls whose kernels read the net-split shape
+    (`set_member_loss` / `member_loss*`, `set_schedule`, `wm_embedded`, `profile`, `pretrain_fluxes`) and every single-model call."""
+
+    def __init__(self, cfg: NDEConfig, n_columns: int, n_models: int, physics=None, device: int = 0, matrix_arithmetic="bf16x3_exact"):
+        cfg.validate()
+        check_ensemble_arrays(n_models, cfg.n_params, physics=None if physics is None else np.asarray(physics))
+        self.cfg = cfg
+        self.n_columns = int(n_columns)
+        self.n_models = int(n_models)
+        self.device = int(device)
+        self._h = ctypes.c_void_p()
+        L = _lib.lib()
+        c, keep = to_c_config(cfg, n_columns, device, 0, matrix_arithmetic)
+        ph = None if physics is None else _f32(physics, (self.n_models, 5))
+        _lib.check(L.colnde_create_tile_ensemble(ctypes.byref(c), self.n_models, _ptr(ph), ctypes.byref(self._h)))
+        self._L = L
+        self.n_params = L.colnde_n_params(self._h)
+        assert self.n_params == cfg.n_params and L.colnde_n_models(self._h) == self.n_models
+        self.n_columns_total = self.n_columns
+        self.engine = L.colnde_engine(self._h)
 
 
 class EnsembleProfile(NamedTuple):

@@ -314,15 +314,23 @@ def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: i
     trains under the scalings of its own first solve with its own constants.  training_simulations: a list of K index lists, member k trains on
     its own simulations (N_sims of train_NDE_args.jl; train_free_convection_nde.jl:60-66) and is still solved on all of them.  gradient_scaling:
     without fractions, the scalings are (1, 1, 1, g, g, g) for every member (None: the problem's loss scalings)."""
+    from .nde import ColumnNDEEnsemble, TileNDEEnsemble, check_ensemble_arrays, is_net_split_shape
+    # any other architecture trains on the tile engine's ensemble (`TileNDEEnsemble`), which has neither a member loss nor a step schedule
+    net_split = is_net_split_shape(problem.cfg)
+    if not net_split:
+        for name, arg in (("training_fractions", training_fractions), ("training_simulations", training_simulations), ("schedule", schedule)):
+            if arg is not None:
+                raise ValueError("%s covers the net-split shape (Nz = 32, three 96-50-20-31 nets): this configuration trains on the tile engine's "
+                                 "ensemble (TileNDEEnsemble), which has no member loss and no step schedule" % name)
     import torch
-    from .nde import ColumnNDEEnsemble, check_ensemble_arrays
     W = np.ascontiguousarray(weights, dtype=np.float32)
     ph = None if physics is None else np.ascontiguousarray(physics, dtype=np.float32)
     et = np.ascontiguousarray(etas, dtype=np.float32)
     K = W.shape[0] if W.ndim == 2 else 0
     check_ensemble_arrays(K, problem.cfg.n_params, W, ph, et)
     eng = problem.engine
-    ens = ColumnNDEEnsemble(problem.cfg, problem.n_simulations, K, physics=ph, device=eng.device, matrix_arithmetic=eng.matrix_arithmetic)
+    ens = (ColumnNDEEnsemble if net_split else TileNDEEnsemble)(problem.cfg, problem.n_simulations, K, physics=ph, device=eng.device,
+                                                                 matrix_arithmetic=eng.matrix_arithmetic)
     try:
         if schedule is not None:
             ens.set_schedule(schedule)
@@ -338,6 +346,10 @@ def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: i
         if not problem.cfg.train_gradient:
             sc[3:] = 0.0
         member = not (training_fractions is None and training_simulations is None and gradient_scaling is None)
+        if member and not net_split:         # gradient_scaling alone: one (1, 1, 1, g, g, g) for every member is the shared loss
+            g = float(gradient_scaling) if problem.cfg.train_gradient else 0.0
+            sc = np.array([1, 1, 1, g, g, g], dtype=np.float64)
+            member = False
         if member:
             tg = problem.cfg.train_gradient
             cw = None if training_simulations is None else member_column_weights(K, problem.n_simulations, training_simulations)

@@ -506,6 +506,26 @@ int colnde_describe(const colnde_handle* h, char* buf, int capacity);
 /* Create: physics [n_models][5] = nu0, nu_minus, dRi, Ric, Pr per model (mpp_parameters order; the train_parameters of train_NDE_args.jl:175), host
  * memory; NULL = cfg's constants for every model.  A physics array needs modified_pacanowski_philander = 1. */
 int colnde_create_ensemble(const colnde_config* cfg, int n_models, const float* physics, colnde_handle** out);
+/* ---- tile ensembles: K wind-mixing models of ANY tile16 architecture side by side ----------------------------------------------------------------------
+ * colnde_create_ensemble covers the net-split shape.  The reference sweeps its wider nets the same way (wind_mixing/train_NDE.jl:97-102,
+ * train_NDE_args.jl:150-166: Dense(96,400)-Dense(400,400)-Dense(400,31), 96-32-400-31, 96-400-31, one model per process at 8 to 18 simulations).  A tile
+ * ensemble runs the tile16 engine's own kernels with the model index in the launch grid; the launch geometry is the one a single handle of n_columns
+ * columns runs, so row k of every result is, bit for bit, what a colnde_create handle with engine = COLNDE_ENGINE_GENERIC computes for model k's weights
+ * and constants.  physics as for colnde_create_ensemble.
+ * Accepted: the wind-mixing model on the training RHS; engine AUTO or GENERIC; any layer sizes and activations colnde_create accepts on tile16 (the
+ * 96-50-20-31 shape included: it then runs tile16's kernels, not the net-split pair); RK4 or RKC2; substeps >= 1; at most 4,096 columns per model; the
+ * modified Pacanowski-Philander, convective-adjustment or plain branches, diurnal forcing, smoothing; 16 x 3 Nz <= 2,048 (the 1,024-thread taped adjoint;
+ * a single handle runs taller grids on 512-thread kernels, which have no model index).
+ * Refused at creation, each with its reason and before any device work: free-convection models (colnde_create_fc_ensemble), inplace_variant, engine
+ * MFMA / FC32, substeps = 0, a step below any model's colnde_min_substeps, n_models outside 1..65535, more than 4,096 columns, a network the taped adjoint
+ * cannot run, COLNDE_T16_DWTAPE=0, COLNDE_T16_ZTAPE=0, COLNDE_T16_BLOCK, COLNDE_T16_TAPE_THREADS=512, COLNDE_T16_FWD_SPLIT=1, a physics array without
+ * the closure, non-finite physics, dRi <= 0, Pr <= 0; and, once the device is known, tapes that do not fit (with the bytes).
+ * Served: colnde_ensemble_forward_dev, _loss_dev, _loss_grad_dev, _loss_grad, _adam_step_dev, _set_physics, colnde_n_models, set_problem[_dev],
+ * set_stream, set_matrix_arithmetic, profiling, plan, n_params, destroy, describe (models=K, tile_ensemble=1, the bytes per model).
+ * Refused, each naming itself (their kernels read a 96-50-20-31 image or a net-split tape): colnde_ensemble_set_member_loss and the member-loss calls,
+ * colnde_set_schedule / colnde_choose_schedule, colnde_ensemble_wm_embedded[_dev], colnde_ensemble_profile[_dev], colnde_ensemble_pretrain_wm_flux_dev,
+ * and every single-model call.  The member loss on the tile engine is left out on purpose: tile16's adjoint has no column-weight path yet. */
+int colnde_create_tile_ensemble(const colnde_config* cfg, int n_models, const float* physics /* [K][5] or NULL */, colnde_handle** out);
 /* number of models: 1 for colnde_create handles, K for an ensemble */
 int colnde_n_models(const colnde_handle* h);
 /* new constants for every model (host [n_models][5]), checked against the stability bound like colnde_create_ensemble */
@@ -630,7 +650,8 @@ int colnde_ensemble_pretrain_wm_flux_dev(colnde_handle* h, int nets /* bit j: tr
  *   weights read in place from d_weights, the f32 matrix pipe under either matrix_arithmetic.  This is the one embedding call that deploys 3 x 96-400-400-31 or
  *   3 x 96-400-31 (train_NDE.jl:97-103, train_NN_args.jl:101-103); the four single-model calls above keep to 96-50-20-31 and say so.  A shape whose activation
  *   rows do not fit a workgroup's 160 KiB of LDS is refused before any device work, with the bytes it needs (hidden widths up to 600 fit; 96-2048-2048-31 does
- *   not).  An ensemble of such networks cannot be created (colnde_create_ensemble).  COLNDE_WM_GENERIC=1 (a test switch, read per call) sends a single handle
+ *   not).  An ensemble of such networks is trained by colnde_create_tile_ensemble, whose handles this call refuses (it deploys
+ *   single handles and colnde_create_ensemble's).  COLNDE_WM_GENERIC=1 (a test switch, read per call) sends a single handle
  *   of the 96-50-20-31 shape to that kernel as well; without it that shape runs the persistent kernel, single or ensemble, with the bits it always had. */
 int colnde_ensemble_wm_embedded_dev(colnde_handle* h, const float* d_weights, const float* d_u, const float* d_v, const float* d_T,
         const float* d_top_flux, const float* d_halo_bottom, const float* d_halo_top, float Lz, float dt, const float* params,

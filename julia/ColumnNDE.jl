@@ -556,6 +556,23 @@ function EnsembleHandle(cfg::Config, save_times::Vector{Float32}, n_models::Inte
     finalizer(x -> ccall((:colnde_destroy, libcolnde), Cvoid, (Ptr{Cvoid},), x.ptr), h)
 end
 
+"""K wind-mixing models of ANY architecture a tile16 handle trains (`colnde_create_tile_ensemble`): the wide nets of wind_mixing/train_NDE.jl:97-102
+(96-400-400-31, 96-32-400-31, 96-400-31), other depths, activations and Nz.  `physics` as for `EnsembleHandle`.  Serves `ensemble_∇loss`, the
+`ensemble_*_dev!` twins, `ensemble_adam_step!`, `set_physics!`; the member loss, step schedules, the embedding and `NDE_profile` calls refuse it."""
+function TileEnsembleHandle(cfg::Config, save_times::Vector{Float32}, n_models::Integer, physics=nothing)
+    cfg.n_save = length(save_times)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    ph = physics === nothing ? C_NULL : Matrix{Float32}(permutedims(physics))       # C order [K][5]
+    GC.@preserve save_times ph begin
+        cfg.save_times = pointer(save_times)
+        check(ccall((:colnde_create_tile_ensemble, libcolnde), Cint, (Ref{Config}, Cint, Ptr{Float32}, Ref{Ptr{Cvoid}}),
+                    cfg, n_models, ph === C_NULL ? Ptr{Float32}(C_NULL) : pointer(ph), out))
+    end
+    h = Handle(out[], ccall((:colnde_n_params, libcolnde), Cint, (Ptr{Cvoid},), out[]),
+               3cfg.Nz, cfg.n_save, cfg.n_columns, 3)
+    finalizer(x -> ccall((:colnde_destroy, libcolnde), Cvoid, (Ptr{Cvoid},), x.ptr), h)
+end
+
 n_models(h::Handle) = Int(ccall((:colnde_n_models, libcolnde), Cint, (Ptr{Cvoid},), h.ptr))
 
 "new (ν₀, ν₋, ΔRi, Riᶜ, Pr) for every model: K x 5"
