@@ -76,15 +76,17 @@ __device__ __forceinline__ float dev_mish_t(float x) {
     return fast_div(n, n + 2.0f);
 }
 
-// tanh(z) = 1 - 2 / (1 + e^{2z}) on the exponential and reciprocal units
+// tanh(z) = 1 - 2 / (1 + e^{2z}) on the exponential and reciprocal units.  fminf / fmaxf are minNum / maxNum and answer their other operand to a NaN:
+// the clamp alone would turn a NaN z into -15 and tanh into -1.  One compare and select hands the NaN on (Flux's tanh; every other z keeps its bits).
 __device__ __forceinline__ float dev_tanh(float z) {
-    const float e = __expf(2.0f * fminf(fmaxf(z, -15.0f), 15.0f));
+    const float c = fminf(fmaxf(z, -15.0f), 15.0f);
+    const float e = __expf(2.0f * (z != z ? z : c));
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
 __device__ __forceinline__ float dev_act(int a, float z) {
     switch (a) {
-        case COLNDE_ACT_RELU: return fmaxf(z, 0.0f);
+        case COLNDE_ACT_RELU: return !(z <= 0.0f) ? z : 0.0f;       // Flux's max(0, x): a NaN goes through, where fmaxf(z, 0) answers 0 to it; -0.0 gives +0.0 as before
         case COLNDE_ACT_MISH: return z * dev_mish_t(z);
         case COLNDE_ACT_SWISH: return z * dev_sigmoid(z);
         case COLNDE_ACT_TANH: return dev_tanh(z);

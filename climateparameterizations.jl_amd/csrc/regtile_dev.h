@@ -147,16 +147,22 @@ __device__ __forceinline__ float rt_top_flux(const DevModel& m, float bc5, float
 extern __shared__ __attribute__((aligned(16))) float rt_smem[];
 
 // ---- activations: value, derivative, and both in one evaluation
+// tanh's argument, clamped where e^{2z} leaves float32's range; a NaN z stays NaN (fminf / fmaxf alone answer -15 to it: colnde_dev.h, dev_tanh)
+__device__ __forceinline__ float rt_tanh_arg(float z) {
+    const float c = fminf(fmaxf(z, -15.0f), 15.0f);
+    return z != z ? z : c;
+}
+
 template <int ACT>
 __device__ __forceinline__ float rt_act(float z) {
-    if (ACT == COLNDE_ACT_RELU) return fmaxf(z, 0.0f);
+    if (ACT == COLNDE_ACT_RELU) return !(z <= 0.0f) ? z : 0.0f;      // a NaN goes through (colnde_dev.h, dev_act)
     if (ACT == COLNDE_ACT_MISH) {
         const float e = __expf(__builtin_amdgcn_fmed3f(z, -3.0e38f, 20.0f));
         const float n = e * (e + 2.0f);
         return z * fast_div(n, n + 2.0f);
     }
     if (ACT == COLNDE_ACT_SWISH) return fast_div(z, 1.0f + __expf(-z));
-    if (ACT == COLNDE_ACT_TANH) { const float e = __expf(2.0f * fminf(fmaxf(z, -15.0f), 15.0f)); return 1.0f - fast_div(2.0f, 1.0f + e); }
+    if (ACT == COLNDE_ACT_TANH) { const float e = __expf(2.0f * rt_tanh_arg(z)); return 1.0f - fast_div(2.0f, 1.0f + e); }
     if (ACT == COLNDE_ACT_LEAKYRELU) return z > 0.0f ? z : 0.01f * z;
     return z;
 }
@@ -172,7 +178,7 @@ __device__ __forceinline__ float rt_act_grad(float z) {
         return t + z * (1.0f - t * t) * sg;
     }
     if (ACT == COLNDE_ACT_SWISH) { const float sg = fast_div(1.0f, 1.0f + __expf(-z)); return sg + z * sg * (1.0f - sg); }
-    if (ACT == COLNDE_ACT_TANH) { const float e = __expf(2.0f * fminf(fmaxf(z, -15.0f), 15.0f)); const float t = 1.0f - fast_div(2.0f, 1.0f + e); return 1.0f - t * t; }
+    if (ACT == COLNDE_ACT_TANH) { const float e = __expf(2.0f * rt_tanh_arg(z)); const float t = 1.0f - fast_div(2.0f, 1.0f + e); return 1.0f - t * t; }
     if (ACT == COLNDE_ACT_LEAKYRELU) return z > 0.0f ? 1.0f : 0.01f;
     return 1.0f;
 }

@@ -71,7 +71,8 @@ enum { COLNDE_STEPPER_RK4 = 0,      /* classical RK4, `substeps` per save interv
  *     significant bits) and a product is the six part-products down to 2^-16 on v_mfma_f32_*_bf16 with f32 accumulation; the three dropped
  *     part-products are below 2^-23 |a b| together — one f32 rounding of the product, which an f32 FMA chain commits at every step anyway
  *     (measured: profiles/r03ze_split_error_probe.txt).  Inf/NaN operands give NaN (Inf - Inf in the split), which the solve calls report
- *     as a non-finite loss.  Subnormals are not flushed (bf16 inputs, f32 results: measured, profiles/r04_split_edge_probe.txt), but the part of an
+ *     as a non-finite loss.  A NaN pre-activation gives a NaN activation for all five activations of the wind-mixing and generic kernels, tanh and
+ *     relu included (Flux's own behaviour); the relu of the fc32 free-convection kernels answers 0 to it (DESIGN, "A NaN member").  Subnormals are not flushed (bf16 inputs, f32 results: measured, profiles/r04_split_edge_probe.txt), but the part of an
  *     operand below 2^-133, the smallest bf16 subnormal, is dropped: operands are exact for |x| >= 2^-110 and carry an ABSOLUTE error below 2^-133
  *     (9e-41) under that — F32_MFMA keeps full relative precision down to FLT_MIN.
  *     Used where a split kernel exists (colnde_plan info[7] says which kernels ran on it); the other kernels run F32_MFMA.
