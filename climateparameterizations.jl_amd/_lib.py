@@ -94,6 +94,9 @@ SYMBOLS = [
     ("colnde_ensemble_loss_dev", ctypes.c_int, [_V, _V, _F, _V]),
     ("colnde_ensemble_loss_grad_dev", ctypes.c_int, [_V, _V, _F, _V]),
     ("colnde_ensemble_loss_grad", ctypes.c_int, [_V, _V, _F, _V]),
+    ("colnde_ensemble_error_estimate_dev", ctypes.c_int, [_V, _V, _V]),
+    ("colnde_ensemble_error_estimate", ctypes.c_int, [_V, _V, _V]),
+    ("colnde_ensemble_choose_schedule", ctypes.c_int, [_V, _V, ctypes.c_float, ctypes.POINTER(ctypes.c_int), _V]),
     ("colnde_ensemble_set_member_loss", ctypes.c_int, [_V, _V, _V]),
     ("colnde_ensemble_member_loss_dev", ctypes.c_int, [_V, _V, _V]),
     ("colnde_ensemble_member_loss_grad_dev", ctypes.c_int, [_V, _V, _V]),

@@ -374,3 +374,217 @@ extern "C" int colnde_choose_schedule(colnde_handle* h, const float* weights, fl
     }
     return 0;
 }
+
+// ---- ensembles: the estimate member by member, one schedule chosen for all K ------------------------------------------------------------
+// A net-split ensemble steps all K members by one schedule; its members differ in what decides the step (the closure constants, the weights).  The
+// estimate is colnde_error_estimate's, with the member kept: two tape-less ensemble solves (the model index in the launch grid) into scratch and
+// rel_diff_member_save_max_kernel, out[k][n].  The solves run under counts that live in the call's scratch: the handle's schedule, its device copy
+// and its tapes are not written, so what is in force afterwards is what was in force before, on failure too.
+
+// refused before any device work, each reason with the entry point's name
+static int ens_estimate_refusals(const colnde_handle* h, const char* fn) {
+    if (!h) return fail("%s: null handle", fn);
+    if (h->closure) return fail("%s estimates the solves of networks, but this is a closure handle (colnde_create_closure: no networks, %d constant sets)", fn, h->n_models);
+    if (!h->ensemble)
+        return fail("%s takes the handles of colnde_create_ensemble, colnde_create_tile_ensemble and colnde_create_fc_ensemble: a single handle's estimate is "
+                    "colnde_error_estimate", fn);
+    if (h->conv.c)
+        return fail("%s does not cover the convolutional first layer of a colnde_create_conv_ensemble handle (conv=%d): colnde_error_estimate refuses conv handles too", fn, h->conv.c);
+    if (!h->have_problem) return fail("%s: colnde_set_problem has not been called", fn);
+    if (refuse_auto_on_a_shard(h)) {
+        const std::string msg = colnde_last_error();
+        return fail("%s: %s", fn, msg.c_str());
+    }
+    return 0;
+}
+
+// the RKC2 stage count of an ensemble whose stages follow the step (cfg.rkc_stages = 0), at `substeps`: the largest any member needs, as at creation
+static int ens_stages_at(const colnde_handle* h, int substeps) {
+    if (h->cfg.stepper != COLNDE_STEPPER_RKC2 || h->cfg.rkc_stages || !h->ens_rkc_stages) return h->ens_rkc_stages;
+    colnde_config c = h->cfg;
+    c.substeps = substeps;
+    int stages = 0;
+    for (int k = 0; k < h->n_models; k++) {
+        const colnde_config ck = model_config(&c, h->phys_raw.empty() ? nullptr : h->phys_raw.data(), k);
+        stages = std::max(stages, colnde_rkc_stages(&ck));
+    }
+    return stages;
+}
+
+// what a round changes in the handle, put back by restore(): the sub-step count, the RKC2 stage count and table, the schedule and where the launches read it
+struct EnsStepKeep {
+    colnde_handle* h;
+    int substeps, stages;
+    std::vector<int> sched;
+    int* d_sched;
+    bool done = false;
+    explicit EnsStepKeep(colnde_handle* h_) : h(h_), substeps(h_->cfg.substeps), stages(h_->ens_rkc_stages), sched(h_->sched), d_sched(h_->d_sched) {}
+    EnsStepKeep(const EnsStepKeep&) = delete;
+    ~EnsStepKeep() { if (!done) (void)restore(); }           // (a path that leaves without restore(): the handle never keeps a pointer into freed scratch)
+    int restore() {
+        done = true;
+        h->cfg.substeps = substeps;
+        h->ens_rkc_stages = stages;
+        h->sched = sched;
+        h->d_sched = d_sched;
+        return refresh_rkc(h);
+    }
+};
+
+// Tape-less solve of all K members into d_sol.  S: the counts of every interval, already on the device at d_S (scratch); null: `substeps` everywhere.
+static int ens_solve_under(colnde_handle* h, const float* d_weights, float* d_sol, const std::vector<int>* S, int* d_S, int substeps) {
+    if (S) {
+        h->sched = *S;
+        h->d_sched = d_S;
+    } else {
+        h->sched.clear();
+        h->ens_rkc_stages = ens_stages_at(h, substeps);
+        h->cfg.substeps = substeps;
+        if (refresh_rkc(h)) return 1;
+    }
+    return colnde_ensemble_forward_dev(h, d_weights, d_sol);
+}
+
+// the scratch of the two calls: two solutions of all K members, the estimates, and the counts of a round and their doubles — on the device and on the host,
+// where they outlive the copies queued from them (members are destroyed after `sc`, whose destructor drains the stream)
+struct EnsScratch {
+    std::vector<int> at, at2;
+    DevScratch sc;
+    float *d_a = nullptr, *d_b = nullptr, *d_est = nullptr;
+    int* d_S = nullptr;
+    explicit EnsScratch(hipStream_t s) : sc(s) {}
+    int alloc(const colnde_handle* h) {
+        const size_t n = ((size_t)h->n_models * h->n_col * h->cfg.n_save * h->m.ns + 3) / 4 * 4, ne = ((size_t)h->n_models * h->cfg.n_save + 3) / 4 * 4;
+        HIPCHK(sc.alloc((2 * n + ne) * sizeof(float) + 2 * (size_t)h->cfg.n_save * sizeof(int)));
+        d_a = sc.p;
+        d_b = sc.p + n;
+        d_est = sc.p + 2 * n;
+        d_S = reinterpret_cast<int*>(sc.p + 2 * n + ne);
+        return 0;
+    }
+};
+
+// One round into s.d_est [K][n_save] (Richardson's factor not applied): the solve under S (null: `substeps` everywhere) against every interval doubled
+static int ens_estimate_round(colnde_handle* h, const float* d_weights, const std::vector<int>* S, int substeps, float floor_, EnsScratch& s) {
+    const int n_iv = h->cfg.n_save - 1;
+    if (S) {
+        s.at = *S;
+        s.at2 = *S;
+        for (int& c : s.at2) c *= 2;
+        if (hipMemcpyAsync(s.d_S, s.at.data(), (size_t)n_iv * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipMemcpyAsync(s.d_S + n_iv, s.at2.data(), (size_t)n_iv * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess)
+            return fail("uploading the round's step counts failed");
+    }
+    if (ens_solve_under(h, d_weights, s.d_a, S ? &s.at : nullptr, s.d_S, substeps) || ens_solve_under(h, d_weights, s.d_b, S ? &s.at2 : nullptr, s.d_S + n_iv, 2 * substeps))
+        return 1;
+    const hipError_t e = launch_rel_diff_member_save_max(s.d_a, s.d_b, h->n_models, h->n_col, h->cfg.n_save, h->m.ns, floor_, s.d_est, h->stream);
+    if (e != hipSuccess) return fail("error-estimate launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int colnde_ensemble_error_estimate_dev(colnde_handle* h, const float* d_weights, float* estimates) {
+    if (!h) return fail("%s: null handle", __func__);
+    if (!d_weights || !estimates) return fail("%s: null pointer argument", __func__);
+    if (ens_estimate_refusals(h, __func__)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    EnsScratch s(h->stream);
+    if (s.alloc(h)) return 1;
+    const size_t ne = (size_t)h->n_models * h->cfg.n_save;
+    EnsStepKeep keep(h);
+    int rc = ens_estimate_round(h, d_weights, keep.sched.empty() ? nullptr : &keep.sched, keep.substeps, norm_floor(h->cfg.reltol), s);
+    if (!rc && (hipMemcpyAsync(estimates, s.d_est, ne * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess))
+        rc = fail("%s: device-to-host copy failed", __func__);
+    const std::string msg = rc ? colnde_last_error() : "";
+    if (keep.restore()) return 1;
+    if (rc) return fail("%s", msg.c_str());
+    const float factor = richardson_factor(h);
+    for (size_t i = 0; i < ne; i++) estimates[i] *= factor;
+    return 0;
+}
+
+extern "C" int colnde_ensemble_error_estimate(colnde_handle* h, const float* weights, float* estimates) {
+    if (!h) return fail("%s: null handle", __func__);
+    if (!weights || !estimates) return fail("%s: null pointer argument", __func__);
+    if (ens_estimate_refusals(h, __func__)) return 1;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * (size_t)h->n_models * user_params(h), hipMemcpyHostToDevice, h->stream));
+    return colnde_ensemble_error_estimate_dev(h, h->d_w, estimates);
+}
+
+// colnde_choose_schedule's greedy run with E[n] = the maximum over the members (step_schedule.h: sched_choose_round); on success S holds the schedule,
+// member_est [K] every member's own maximum over the save points at it
+static int ens_choose_rounds(colnde_handle* h, const float* d_weights, float reltol, EnsScratch& s, std::vector<int>& S, std::vector<float>& member_est, float* est_out) {
+    const int K = h->n_models, n_save = h->cfg.n_save;
+    if (schedule_minima(h, &S)) return 1;
+    for (int& c : S) c = sched_pow2_ceil(c);
+    std::vector<float> est((size_t)K * n_save), E((size_t)n_save);
+    const float factor = richardson_factor(h);
+    float prev = -1.0f;
+    for (;;) {
+        if (ens_estimate_round(h, d_weights, &S, 0, norm_floor(reltol), s)) return 1;
+        if (hipMemcpyAsync(est.data(), s.d_est, est.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+            return fail("colnde_ensemble_choose_schedule: device-to-host copy failed");
+        const int total = (int)sched_total(S.data(), n_save - 1);
+        std::fill(E.begin(), E.end(), 0.0f);
+        for (int k = 0; k < K; k++) {
+            member_est[(size_t)k] = 0.0f;
+            for (int n = 0; n < n_save; n++) {
+                const float e = est[(size_t)k * n_save + n] * factor;
+                if (!(e == e) || e > 3.0e38f)
+                    return fail("the solve of member %d is not finite under a schedule of %d steps in all: no schedule can be chosen", k, total);
+                E[(size_t)n] = std::max(E[(size_t)n], e);
+                member_est[(size_t)k] = std::max(member_est[(size_t)k], e);
+            }
+        }
+        float mx = 0.0f;
+        switch (sched_choose_round(E.data(), n_save, reltol, prev, S.data(), &mx)) {
+        case SCHED_ROUND_MET: *est_out = mx; return 0;
+        case SCHED_ROUND_DOUBLED: prev = mx; break;
+        // (not reached: the loop above has named the member; kept so that the switch covers the rule's verdicts)
+        case SCHED_ROUND_NOT_FINITE: return fail("the solve is not finite under a schedule of %d steps in all: no schedule can be chosen", total);
+        case SCHED_ROUND_FLOOR:
+            return fail("reltol = %g is below the float32 round-off floor of this solve: the estimate stopped falling at %g (%d steps in all, %g before the last doubling)",
+                        reltol, mx, total, prev);
+        case SCHED_ROUND_TOO_STIFF:
+            return fail("reltol = %g is not met with %d steps in the save intervals that carry the error (estimate %g): the right-hand side is too stiff for this stepper",
+                        reltol, COLNDE_SCHEDULE_MAX, mx);
+        }
+    }
+}
+
+extern "C" int colnde_ensemble_choose_schedule(colnde_handle* h, const float* weights, float reltol, int* counts, float* estimates) {
+    if (!h) return fail("%s: null handle", __func__);
+    if (!weights) return fail("%s: null weights", __func__);
+    NOT_A_TILE_ENSEMBLE(h);
+    if (h->closure || !h->ensemble) {
+        if (refuse_schedule(h)) return 1;                    // (a closure handle: its own reason)
+        return fail("%s takes the handles of colnde_create_ensemble: a single handle's schedule is chosen by colnde_choose_schedule", __func__);
+    }
+    if (refuse_schedule(h)) return 1;
+    if (ens_estimate_refusals(h, __func__)) return 1;
+    if (reltol == 0.0f) reltol = h->cfg.reltol;
+    if (!(reltol > 0.0f)) return fail("%s: reltol must be > 0", __func__);
+    HIPCHK(hipSetDevice(h->device));
+    const int K = h->n_models, n_iv = h->cfg.n_save - 1;
+    std::vector<int> S;
+    std::vector<float> member_est((size_t)K);
+    float est = -1.0f;
+    {
+        EnsScratch s(h->stream);
+        if (s.alloc(h)) return 1;
+        HIPCHK(hipMemcpyAsync(h->d_w, weights, sizeof(float) * (size_t)K * user_params(h), hipMemcpyHostToDevice, h->stream));
+        EnsStepKeep keep(h);
+        const int rc = ens_choose_rounds(h, h->d_w, reltol, s, S, member_est, &est);
+        (void)hipStreamSynchronize(h->stream);
+        const std::string msg = rc ? colnde_last_error() : "";
+        if (keep.restore()) return 1;
+        if (rc) return fail("%s", msg.c_str());
+    }                                                        // (the scratch is freed before the tapes are planned again)
+    // the handle keeps the schedule: colnde_set_schedule's own steps (validation, upload, the tapes planned again; a total that does not fit is refused with
+    // the bytes and the previous schedule and tapes kept)
+    if (colnde_set_schedule(h, S.data())) return 1;
+    h->last_estimate = est;
+    if (counts) std::copy(S.begin(), S.begin() + n_iv, counts);
+    if (estimates) std::copy(member_est.begin(), member_est.end(), estimates);
+    return 0;
+}

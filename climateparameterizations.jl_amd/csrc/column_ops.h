@@ -35,6 +35,9 @@ hipError_t launch_loss_per_tstep(const float* sol, const float* truth, int n_col
 hipError_t launch_rel_diff_max(const float* a, const float* b, long n_rows, int row, float floor, float* partial, float* out, hipStream_t stream);
 // ... per save point: out[n] (n < n_save) = the maximum over the n_col columns of that norm of rows [column][n_save][row]
 hipError_t launch_rel_diff_save_max(const float* a, const float* b, int n_col, int n_save, int row, float floor, float* out, hipStream_t stream);
+// ... per member and save point: a, b [K][n_col][n_save][row] (colnde_ensemble_forward_dev's layout), out[k][n] (device, [K][n_save]); K in grid.y,
+// at most 65,535; a non-finite entry makes its own (k, n) +inf and no other
+hipError_t launch_rel_diff_member_save_max(const float* a, const float* b, int K, int n_col, int n_save, int row, float floor, float* out, hipStream_t stream);
 // Free-convection ensembles.  out[k][c][n] = mean over Nz (32 | 64) levels of (sol[k][c][n][:] - truth[c][n][:])^2; rows_per_model = n_col * n_save
 hipError_t launch_column_loss(const float* sol, const float* truth, int Nz, long rows_per_model, int n_models, float* out, hipStream_t stream);
 // result[k][n_params + 6] += coeff[k] * sum_{r < q} W1_k[r, q]^2, result[k][index of W1[r, q]] += 2 coeff[k] W1_k[r, q] (W1: H x M at w1_off,

@@ -579,6 +579,43 @@ hipError_t launch_rel_diff_save_max(const float* a, const float* b, int n_col, i
     return hipGetLastError();
 }
 
+// ... and per member and save point (colnde_ensemble_error_estimate, colnde_ensemble_choose_schedule): out[k][n] = max over the columns of the row norm
+// of rows [member][column][n_save][row].  One workgroup per (save point, member); 16 lanes share a column's row — lane j takes the entries j, j + 16, ...
+// in that order, the 16 partial sums meet in a butterfly — and the workgroup walks the columns 16 at a time, so eight simulations fill half a wavefront
+// where a lane per column would fill an eighth, and the row is read in 64-byte runs.  Every sum has one order and a maximum has none: two launches
+// give the same bits.  Scalar loads: nothing is asked of the rows' alignment.
+__global__ void __launch_bounds__(256) rel_diff_member_save_max_kernel(const float* __restrict__ a, const float* __restrict__ b, int n_col, int n_save, int row, float floor,
+                                                                       float* __restrict__ out) {
+    const int n = blockIdx.x, k = blockIdx.y, j = threadIdx.x & 15;
+    float mx = 0.0f;
+    for (int c0 = 0; c0 < n_col; c0 += 16) {                                          // (uniform trip count: every lane reaches the shuffles)
+        const int c = c0 + (threadIdx.x >> 4);
+        float s2 = 0.0f;
+        if (c < n_col) {
+            const size_t r = (((size_t)k * n_col + c) * n_save + n) * row;
+            for (int i = j; i < row; i += 16) {
+                const float q = (a[r + i] - b[r + i]) / (floor + fabsf(b[r + i]));
+                s2 += q * q;
+            }
+        }
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) s2 += __shfl_xor(s2, off, 16);
+        const float v = sqrtf(s2 / (float)row);
+        mx = (v <= 3.0e38f) ? fmaxf(mx, v) : __int_as_float(0x7f800000);              // a NaN or Inf anywhere: +inf
+    }
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_down(mx, off));
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) out[(size_t)k * n_save + n] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+hipError_t launch_rel_diff_member_save_max(const float* a, const float* b, int K, int n_col, int n_save, int row, float floor, float* out, hipStream_t stream) {
+    if (K < 1 || K > 65535 || n_col < 1 || n_save < 1 || row < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rel_diff_member_save_max_kernel, dim3(n_save, K), dim3(256), 0, stream, a, b, n_col, n_save, row, floor, out);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // Free-convection ensembles (colnde_create_fc_ensemble): judging K networks on the same simulations.
 // ------------------------------------------------------------------------------------------------

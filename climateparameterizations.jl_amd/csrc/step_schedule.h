@@ -54,3 +54,42 @@ inline SchedVerdict sched_validate(const int* counts, const int* minima, int n_i
     }
     return SCHED_OK;
 }
+
+// One round of the greedy choice (colnde_choose_schedule's rule; colnde_ensemble_choose_schedule applies it through this function).  E[n_save]: the
+// estimate at every save point alone — of an ensemble already the maximum over the members — with Richardson's factor applied; prev_est: the last
+// round's *est (<= 0: none); S[n_save - 1]: the counts the estimates were formed at, doubled in place where the rule says so.  *est = max E.
+//   NOT_FINITE  an entry is NaN or above 3e38 (S untouched; *est = that entry)
+//   MET         est <= reltol
+//   FLOOR       the estimate fell by less than a fifth since the last round: float32 round-off of the two solves it compares
+//   DOUBLED     every interval whose own addition d[n] = max(0, E[n+1] - E[n]) (E[0] taken as 0) is at least half the largest, and below
+//               COLNDE_SCHEDULE_MAX, was doubled
+//   TOO_STIFF   none could be
+enum SchedRound { SCHED_ROUND_MET = 0, SCHED_ROUND_DOUBLED = 1, SCHED_ROUND_NOT_FINITE = 2, SCHED_ROUND_FLOOR = 3, SCHED_ROUND_TOO_STIFF = 4 };
+inline SchedRound sched_choose_round(const float* E, int n_save, float reltol, float prev_est, int* S, float* est) {
+    float mx = 0.0f;
+    for (int i = 0; i < n_save; i++) {
+        if (!(E[i] == E[i]) || E[i] > 3.0e38f) {
+            *est = E[i];
+            return SCHED_ROUND_NOT_FINITE;
+        }
+        if (E[i] > mx) mx = E[i];
+    }
+    *est = mx;
+    if (mx <= reltol) return SCHED_ROUND_MET;
+    if (prev_est > 0.0f && mx > 0.8f * prev_est) return SCHED_ROUND_FLOOR;
+    const int n_iv = n_save - 1;
+    float dmax = 0.0f;
+    for (int i = 0; i < n_iv; i++) {
+        const float d = E[i + 1] - (i ? E[i] : 0.0f);
+        if (d > dmax) dmax = d;
+    }
+    bool doubled = false;
+    for (int i = 0; i < n_iv; i++) {
+        const float d = E[i + 1] - (i ? E[i] : 0.0f);
+        if ((d > 0.0f ? d : 0.0f) >= 0.5f * dmax && S[i] < COLNDE_SCHEDULE_MAX) {
+            S[i] *= 2;
+            doubled = true;
+        }
+    }
+    return doubled ? SCHED_ROUND_DOUBLED : SCHED_ROUND_TOO_STIFF;
+}

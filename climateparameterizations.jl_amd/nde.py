@@ -564,6 +564,31 @@ class ColumnNDEEnsemble(ColumnNDE):
         _lib.check(self._L.colnde_ensemble_loss_grad(self._h, _ptr(w), sc, _ptr(res)))
         return res
 
+    # ---- the error estimate member by member, one schedule for all K (include/colnde.h: colnde_ensemble_error_estimate) ----
+    def ensemble_error_estimate(self, weights):
+        """`colnde_ensemble_error_estimate[_dev]`: ndarray [K, n_save], row k what `ColumnNDE.error_estimate` gives for member k at every save point
+        alone (column 0 is 0; a member whose solve is not finite has +inf in its own row).  Two tape-less solves of all K members — under the counts
+        in force and with every interval doubled — and one kernel; the handle is left as it was.  Torch device weights go to the `_dev` form on
+        torch's current stream."""
+        est = np.empty((self.n_models, self.cfg.n_save), dtype=np.float32)
+        if _is_torch(weights):
+            self._chk_dev(weights, (self.n_models, self.n_params))
+            self.use_torch_stream()
+            _lib.check(self._L.colnde_ensemble_error_estimate_dev(self._h, weights.data_ptr(), _ptr(est)))
+        else:
+            w = _f32(weights, (self.n_models, self.n_params))
+            _lib.check(self._L.colnde_ensemble_error_estimate(self._h, _ptr(w), _ptr(est)))
+        return est
+
+    def choose_ensemble_schedule(self, weights, reltol: float = 0.0):
+        """`colnde_ensemble_choose_schedule`: `ColumnNDE.choose_schedule`'s greedy run on the maximum over the members (wind-mixing ensembles under
+        RK4); the handle keeps the schedule and plans its tapes for it.  Returns (counts, estimates): the counts and ndarray [K], every member's own
+        estimate at them (the largest drives the schedule).  reltol = 0: cfg.reltol."""
+        w = _f32(weights.cpu().numpy() if _is_torch(weights) else weights, (self.n_models, self.n_params))
+        c, est = (ctypes.c_int * (self.cfg.n_save - 1))(), np.empty((self.n_models,), dtype=np.float32)
+        _lib.check(self._L.colnde_ensemble_choose_schedule(self._h, _ptr(w), float(reltol), c, _ptr(est)))
+        return tuple(int(v) for v in c), est
+
     # ---- the member loss: every member its own scalings and its own training simulations (include/colnde.h: colnde_ensemble_set_member_loss) ----
     def set_member_loss(self, scalings=None, column_weights=None):
         """`colnde_ensemble_set_member_loss`: member k is differentiated under sum_q s[k][q] sum_c w[k][c] (term q of column c) / sum_c w[k][c].

@@ -52,6 +52,8 @@ def apply_loss_scalings(losses, scalings):
 class TrainResult:
     weights: np.ndarray
     history: List[dict]
+    schedule: Optional[tuple] = None             # train_NDE_ensemble(schedule="choose"): the counts chosen for all K members ...
+    schedule_estimate: Optional[float] = None    # ... and this member's own error estimate at them
 
 
 class WindMixingNDE:
@@ -301,13 +303,15 @@ def member_fractions(n_models: int, training_fractions):
 
 def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: int = 1, maxiters: int = 500, beta=(0.9, 0.999),
                        eps: float = 1e-8, schedule=None, training_fractions=None, training_simulations=None,
-                       gradient_scaling=None) -> List[TrainResult]:
+                       gradient_scaling=None, reltol=None) -> List[TrainResult]:
     """`train_NDE_device`'s loop (NDE_training.jl:340-372: ADAM, per-solve state reset, save_best) for K models at once — the sweep of
     wind_mixing/train_NDE_args.jl, which trains one model per process with its own ADAM rate (ARGS[2], :143) and Pacanowski-Philander constants
     (ARGS[3], :175).  weights [K, n_params], physics [K, 5] = (nu0, nu_minus, dRi, Ric, Pr) per model or None (the problem's constants), etas [K].
     One `colnde_ensemble_loss_grad_dev` and one `colnde_ensemble_adam_step_dev` per iteration for all models, on the problem's simulations and
     loss scalings; `save_best` per model (torch.where over rows).  Returns one TrainResult per model.
-    schedule: RK4 steps per save interval shared by the K models (`ColumnNDEEnsemble.set_schedule`), None: cfg.substeps.
+    schedule: RK4 steps per save interval shared by the K models (`ColumnNDEEnsemble.set_schedule`), None: cfg.substeps; "choose": chosen before the
+    first gradient from the initial weights and every member's constants (`ColumnNDEEnsemble.choose_ensemble_schedule` at `reltol`, None:
+    cfg.reltol) — every TrainResult then carries the counts (`schedule`) and its member's own estimate at them (`schedule_estimate`).
     The member loss (`ColumnNDEEnsemble.set_member_loss`) — with all three of the following None the function issues the calls above:
     training_fractions: dict(T, dTdz, profile) for all members or a list of K dicts — `determine_loss_scalings` per member (NDE_training.jl:256-288):
     one `member_loss` at the initial weights under unit scalings, then `calculate_loss_scalings` (loss.jl:11-31) on every row, so that each member
@@ -331,13 +335,18 @@ def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: i
     eng = problem.engine
     ens = (ColumnNDEEnsemble if net_split else TileNDEEnsemble)(problem.cfg, problem.n_simulations, K, physics=ph, device=eng.device,
                                                                  matrix_arithmetic=eng.matrix_arithmetic)
+    chosen, chosen_est = None, None
     try:
-        if schedule is not None:
+        if schedule is not None and not isinstance(schedule, str):
             ens.set_schedule(schedule)
+        elif schedule is not None and schedule != "choose":
+            raise ValueError("schedule: counts per save interval, None or \"choose\", got %r" % (schedule,))
         dev = torch.device("cuda", eng.device)
         t = lambda a: a if a is None or _is_torch_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32))
         x0, bcs, truth = (t(a).to(dev).contiguous() for a in (problem.uvT0, problem.BCs, problem.uvT_trains))
         ens.set_problem(x0, bcs, truth)
+        if isinstance(schedule, str):
+            chosen, chosen_est = ens.choose_ensemble_schedule(W, 0.0 if reltol is None else float(reltol))
         n = ens.n_params
         theta = torch.as_tensor(W).to(dev).contiguous()
         eta_d = torch.as_tensor(et).to(dev).contiguous()
@@ -388,7 +397,8 @@ def train_NDE_ensemble(problem: WindMixingNDE, weights, physics, etas, epochs: i
         th = theta.cpu().numpy()
     finally:
         ens.close()
-    return [TrainResult(th[k], [dict(total=float(r[k, 6]), **{q: float(r[k, i]) for i, q in enumerate(LOSS_KEYS)}) for r in H]) for k in range(K)]
+    return [TrainResult(th[k], [dict(total=float(r[k, 6]), **{q: float(r[k, i]) for i, q in enumerate(LOSS_KEYS)}) for r in H], chosen,
+                        None if chosen_est is None else float(chosen_est[k])) for k in range(K)]
 
 
 def _is_torch_tensor(x):

@@ -540,6 +540,30 @@ int colnde_ensemble_loss_dev(colnde_handle* h, const float* d_weights, const flo
 int colnde_ensemble_loss_grad_dev(colnde_handle* h, const float* d_weights, const float scalings[6], float* d_out);
 /* the same with host arrays: weights [K][n_params], out [K][n_params + 8]; synchronises the stream */
 int colnde_ensemble_loss_grad(colnde_handle* h, const float* weights, const float scalings[6], float* out);
+/* ---- ensembles: the error estimate member by member, and one step schedule chosen for all K -----------------------------------------------------------
+ * The members of a sweep differ in what decides the step — nu0, nu_minus, dRi, Ric, Pr and the weights — and the reference gives every run its own
+ * adaptive ROCK4 at reltol = 1e-3 (1e-4 for free convection); an ensemble steps all K by one count or one schedule.
+ * colnde_ensemble_error_estimate[_dev]: estimates [K][n_save] (HOST in both forms), estimates[k][n] = colnde_error_estimate's number for member k at save
+ *   point n alone (the maximum over the columns; the same Richardson factor and the same floor 1e-6 / cfg.reltol).  Two tape-less solves of all K members
+ *   on the handle's stream — under the counts in force (the schedule if one is set, else cfg.substeps everywhere) and with every interval doubled — into
+ *   scratch, one kernel, one device-to-host copy, one synchronisation (RKC2 with rkc_stages = 0 excepted: the doubled solve and the restoration each upload
+ *   a stage table and wait for it, as in colnde_error_estimate).  estimates[k][0] = 0 (both solves hold x0 there); a member whose solve is not finite
+ *   has +inf in its own row and no other.  The handle computes afterwards what it computed before: schedule, its device copy, cfg.substeps, the RKC2 stage
+ *   table and the tapes are untouched, on failure too.  Under RKC2 with rkc_stages = 0 the doubled solve runs the stage count its own step needs (the
+ *   largest over the members, as at creation).  Serves colnde_create_ensemble (RK4, RKC2, with or without a schedule), colnde_create_tile_ensemble and
+ *   colnde_create_fc_ensemble handles.  Refused before any device work, each naming the call: null arguments, a single handle (colnde_error_estimate),
+ *   a closure handle, a conv ensemble, no problem set, a column shard (colnde_set_global_columns above the handle's own count).
+ * colnde_ensemble_choose_schedule (the handles colnde_set_schedule accepts among ensembles: colnde_create_ensemble under RK4; colnde_set_schedule's refusals
+ *   with their words, and those above): colnde_choose_schedule's greedy run with E[n] = the maximum over the members.  From the stability minima of the
+ *   members' constants (the largest per interval) rounded up to powers of two; each round solves at S and 2 S for all K at once.  On success the handle
+ *   keeps the schedule exactly as after colnde_set_schedule (the tapes planned again; a total that does not fit is refused with the bytes, the previous
+ *   schedule and tapes kept); counts [n_save - 1] (nullable) receives it, estimates [K] (HOST, nullable) every member's own maximum over the save points
+ *   at it — the member that drives the schedule is the largest.  reltol = 0: cfg.reltol.  Failures keep the previous schedule: a member whose solve is
+ *   not finite (named), the float32 round-off floor and "too stiff" in colnde_choose_schedule's words. */
+int colnde_ensemble_error_estimate_dev(colnde_handle* h, const float* d_weights /* [K][n_params] */, float* estimates /* HOST [K][n_save] */);
+int colnde_ensemble_error_estimate(colnde_handle* h, const float* weights /* host [K][n_params] */, float* estimates /* [K][n_save] */);
+int colnde_ensemble_choose_schedule(colnde_handle* h, const float* weights /* host [K][n_params] */, float reltol, int* counts /* [n_save - 1], nullable */,
+                                    float* estimates /* [K], nullable */);
 /* ---- the member loss: every member its own loss scalings and its own training simulations --------------------------------------------------------------
  * In the reference the loss is per run in two ways.  determine_loss_scalings (wind_mixing/src/NDE_training.jl:256-288) solves once with the run's own
  * initial weights and constants and feeds the six unscaled terms to calculate_loss_scalings (loss.jl:11-31), so two runs of a sweep train under different

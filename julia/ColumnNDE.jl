@@ -599,6 +599,27 @@ ensemble_loss_dev!(h::Handle, dθ::Ptr{Float32}, sc::Vector{Float32}, dout::Ptr{
 ensemble_loss_grad_dev!(h::Handle, dθ::Ptr{Float32}, sc::Vector{Float32}, dout::Ptr{Float32}) =
     check(ccall((:colnde_ensemble_loss_grad_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, sc, dout))
 
+"""The error estimate of every member at every save point (colnde_ensemble_error_estimate): weights n_params x K -> n_save x K, column k what
+`error_estimate` gives for member k at each save point alone.  With device weights (`Ptr{Float32}`) the `_dev` form; the result is a host array either way."""
+function ensemble_error_estimate(h::Handle, weights::AbstractMatrix{Float32})
+    est = zeros(Float32, h.n_save, size(weights, 2))
+    check(ccall((:colnde_ensemble_error_estimate, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, Matrix{Float32}(weights), est))
+    est
+end
+function ensemble_error_estimate(h::Handle, dθ::Ptr{Float32}, n_models::Integer)
+    est = zeros(Float32, h.n_save, n_models)
+    check(ccall((:colnde_ensemble_error_estimate_dev, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), h.ptr, dθ, est))
+    est
+end
+"""One step schedule for all K members of a wind-mixing ensemble (colnde_ensemble_choose_schedule): `choose_schedule!`'s greedy run on the maximum over
+the members; the handle keeps it.  Returns (counts, estimates): n_save - 1 counts and every member's own estimate at them."""
+function ensemble_choose_schedule!(h::Handle, weights::AbstractMatrix{Float32}, reltol=0f0)
+    counts = Vector{Cint}(undef, h.n_save - 1); est = zeros(Float32, size(weights, 2))
+    check(ccall((:colnde_ensemble_choose_schedule, libcolnde), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cfloat, Ptr{Cint}, Ptr{Float32}),
+                h.ptr, Matrix{Float32}(weights), reltol, counts, est))
+    Int.(counts), est
+end
+
 """The member loss (colnde_ensemble_set_member_loss): member k is differentiated under Σ_q s[q, k] Σ_c w[c, k] (term q of column c) / Σ_c w[c, k] —
 `determine_loss_scalings` per run (wind_mixing/src/NDE_training.jl:256-288, loss.jl:11-31) and the run's own training simulations
 (train_free_convection_nde.jl:60-66).  scalings 6 x K or `nothing` (every scaling 1), column_weights n_columns x K or `nothing` (every column 1);
